@@ -8,10 +8,14 @@ One "step" = zero_grad + mask sampling + VTMAE forward + backward (+ RCCL gradie
 parameter buffer, m3l_amd.parallel.FlatAdam, numerically torch.optim.Adam).  Weak scaling: 256 samples per GPU.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs   # + the last timed step's outputs as <DIR>/<name>.npy
+  python bench.py --full                                                # + every figure beyond the headline (below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel, HIP-event timed inside the
-timed region) and `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample).
+Rank 0 prints ONE JSON line: the headline `value` (samples/s) and `ms_per_step` of the K timed steps.  With --full the timed region
+also carries HIP-event brackets around the dominant kernel, and the line adds `roofline` (that kernel), `kernel_ms_sampled`, figures
+quoted from profiles/, `secondary` (other architectures, timed after the headline run) and `cpu_baseline` (the CPU oracle timed on the
+host's cores on a bounded sample).
 """
 import argparse
 import json
@@ -283,6 +287,35 @@ def cpu_baseline():
             "all": rows}
 
 
+# --dump-outputs caps, in elements per array: cfg 2's parameters and gradients (7.2 M each) are written whole, and no dump exceeds
+# 2 x 7.4 M + 2 x 0.5 M float32 values (under 64 MB)
+DUMP_FLAT_CAP = 7_400_000
+DUMP_MASK_CAP = 500_000
+
+
+def _dump_array(t, cap):
+    """t as float32 on the host; a tensor of more than `cap` elements is flattened and sampled at `cap` fixed indices (seeded: the same
+    indices for the same size, so that two runs compare element for element)."""
+    import numpy as np
+    t = t.detach()
+    if t.numel() > cap:
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(d, loss, last_mask, sync):
+    """What the timed step hands its caller, from the last timed step: the loss, the masked / unmasked token indices (exact in float32),
+    the gradients and the parameters after the Adam update (GradSync's flat buffers, in their order), as d/<name>.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {"loss": np.asarray([float(loss.detach())], dtype=np.float64),
+              "masked_indices": _dump_array(last_mask[0], DUMP_MASK_CAP), "unmasked_indices": _dump_array(last_mask[1], DUMP_MASK_CAP),
+              "grads": _dump_array(sync.flat, DUMP_FLAT_CAP), "params": _dump_array(sync.flat_params, DUMP_FLAT_CAP)}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -295,7 +328,13 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the short secondary-workload runs (cfg 4, cfg 5 MAE, reference default)")
     ap.add_argument("--roofline-kernel", default="wgrad[", help="kernel class event-timed inside the timed region ('' = every tracked class, diagnostic)")
     ap.add_argument("--no-optimizer", action="store_true", help="diagnostic only: time fwd+bwd without the Adam update")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline line: roofline (event brackets inside the "
+                                                        "timed region), profile figures, secondary workloads, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, mask indices, gradients and updated parameters as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # stdout carries exactly ONE line, the result: anything else a library prints there (RCCL's version banner goes to stdout)
     # is sent to stderr by pointing fd 1 at fd 2 for the whole run and keeping the real stdout aside for the JSON line
     sys.stdout.flush()
@@ -336,6 +375,7 @@ def main():
     sync = GradSync(mae, force_comm=force_comm)
     opt = FlatAdam(sync, lr=1e-4)                 # torch.optim.Adam semantics, one HIP launch over the flat buffers
     B = args.batch
+    init_params = sync.flat_params.clone()
     torch.manual_seed(1234 + rank)
     x = synthetic_batch(c, B, dev)
 
@@ -367,29 +407,42 @@ def main():
             done = bool(flag.item() > 0)
         if done:
             break
+    # warm-up and timed steps start from the initial weights, fresh Adam moments and a fixed seed for the mask noise: the priming above
+    # runs for a time, not a step count, so without this the last step's outputs (`loss`, --dump-outputs) would differ from run to run
+    with torch.no_grad():
+        sync.flat_params.copy_(init_params)
+    del init_params
+    opt.exp_avg.zero_()
+    opt.exp_avg_sq.zero_()
+    opt.step_count = 0
+    torch.manual_seed(4321 + rank)
     for _ in range(args.warmup):
         step()
     lib = _lib.lib()
     barrier()
-    # launches of the roofline kernel are bracketed by HIP events on the stream they are launched on
-    # (the weight-gradient class is 5-7 launches per step: every launch is bracketed — a stride that divides the per-step count would
-    # sample the same launch of every step)
-    prof_stride = 1 if (args.roofline_kernel or "").startswith("wgrad") else 5
-    lib.m3l_prof_begin(args.roofline_kernel.encode() if args.roofline_kernel else None, prof_stride if args.roofline_kernel else 1)
+    if args.full:
+        # launches of the roofline kernel are bracketed by HIP events on the stream they are launched on
+        # (the weight-gradient class is 5-7 launches per step: every launch is bracketed — a stride that divides the per-step count would
+        # sample the same launch of every step)
+        prof_stride = 1 if (args.roofline_kernel or "").startswith("wgrad") else 5
+        lib.m3l_prof_begin(args.roofline_kernel.encode() if args.roofline_kernel else None, prof_stride if args.roofline_kernel else 1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
     t_enq = time.perf_counter() - t0          # host done enqueueing (diagnostic: equal to `el` means the host is the bound)
     barrier()
     el = time.perf_counter() - t0
-    lib.m3l_prof_end()
-    ev_overhead_us = lib.m3l_prof_event_overhead_us(torch.cuda.current_stream().cuda_stream, 200)
+    if args.full:
+        lib.m3l_prof_end()
+        ev_overhead_us = lib.m3l_prof_event_overhead_us(torch.cuda.current_stream().cuda_stream, 200)
     if world > 1:
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     ms = el / args.steps * 1e3
     value = B * world * args.steps / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, mae.last_mask, sync)
 
     out = {"metric": "MAE fwd+bwd samples/sec (image+tactile)", "value": round(value, 1), "unit": "samples/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
@@ -403,7 +456,7 @@ def main():
                       "rccl_probe_sum": getattr(sync, "rccl_probe", None),     # all-reduce of (rank + 1) by the library's communicator = N (N + 1) / 2
                       "step": "zero_grad + mask + fwd + bwd + grad all-reduce + Adam" if not args.no_optimizer else "fwd + bwd (diagnostic)"},
            "loss": round(float(loss.detach()), 5), "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 3)}
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
         # ---- roofline of the dominant kernel (HIP events recorded by the library around its launches, inside the timed region, on
         # the stream the kernel is launched on — the library's side stream for the weight gradients).  By rocprofv3
@@ -538,6 +591,7 @@ def main():
             out["secondary"] = secondary_workloads(args.dtype, dev)
         if world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
             out["cpu_baseline"] = cpu_baseline()
+    if rank == 0:
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if dist.is_initialized():
         sync.close()                      # the library's own RCCL communicator (collective), then torch's

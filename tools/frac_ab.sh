@@ -4,7 +4,7 @@
 R=$PWD
 for rep in 1 2; do
   for setting in "$@"; do
-    out=$(env $setting python3 $R/bench.py --no-cpu-baseline --no-secondary --steps 30 --warmup 10 2>/dev/null)
+    out=$(env $setting python3 $R/bench.py --full --no-cpu-baseline --no-secondary --steps 30 --warmup 10 2>/dev/null)
     python3 - "$setting" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2]); r = d["roofline"]; sa = r.get("stand_alone") or {}

@@ -24,5 +24,5 @@ python3 tools/kernel_budget.py > $OUT/final/${TAG}_kernel_budget.json 2> $OUT/bu
 rm -rf $OUT/stats $OUT/fetch $OUT/write $OUT/mfma
 # the bench line quotes the traffic / phase profiles it finds under profiles/: put the fresh ones there first (this tree is the box's copy)
 cp $OUT/final/${TAG}_traffic.json $OUT/final/${TAG}_attn_phases.json profiles/ 2>/dev/null || true
-python3 bench.py > $OUT/final/${TAG}_bench_n1.json 2> $OUT/bench.log
+python3 bench.py --full > $OUT/final/${TAG}_bench_n1.json 2> $OUT/bench.log
 tail -c 700 $OUT/final/${TAG}_bench_n1.json
