@@ -7,8 +7,9 @@
  *   - allocates nothing (the caller passes workspaces sized by the *_ws_bytes functions),
  *   - returns 0 on success, non-zero on error (text via m3l_last_error; nothing is thrown across the ABI),
  *   - takes device pointers unless a parameter says "host".
- * dtype codes: 0 = f32 compute (parity path), 1 = bf16 compute (fp32 master weights, fp32 accumulation,
- * fp32 residual stream).  dim_head is 64 everywhere (all reference configs).
+ * dtype codes: 0 = f32 compute (parity path), 1 = bf16 compute (fp32 master weights, fp32 accumulation; the residual stream
+ * of a stack is bf16 or fp32, m3l_set_residual_bf16).  dim_head is 64 everywhere (all reference configs).  Transformer dropout
+ * (vit_pytorch's four nn.Dropout sites) is the *_dropout forms with an m3l_dropout descriptor; see "Dropout" below.
  *
  * Reference interface each entry replaces:
  *   m3l_mask_sample        torch.rand(B,n).argsort(-1) per modality + slicing      pretrain_models.py:223-248
@@ -51,6 +52,26 @@ typedef struct m3l_tf_cfg {
     int project_out;         /* vit_pytorch: to_out is Identity when heads == 1 and dim_head == dim */
     int dtype;
 } m3l_tf_cfg;
+
+/* ---- Dropout.  A descriptor of p > 0 (NULL = none) applies vit_pytorch's nn.Dropout(p) at four sites s of every layer l:
+ *   s = 0  attention probabilities softmax(QK^T / 8) before P V, (B, H, n, n)     row = (b H + h) n + query, column = key
+ *   s = 1  out-proj output before the residual add, (B n, D)  (absent when to_out is Identity)
+ *   s = 2  hidden activation GELU(fc1) before fc2, (B n, mlp)
+ *   s = 3  fc2 output before the residual add, (B n, D)
+ * Masks are never stored: every kernel regenerates them.  Generator: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments
+ * 0x9E3779B9, 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32), counter = (q & 0xffffffff, q >> 32, 4 l + s, 0).  Element (row, c) of
+ * a site whose last axis has length N uses word c % 4 of the block q = row * ceil(N / 4) + c / 4 (words in Random123 order).  It is
+ * kept iff word >= T, T = min(2^32 - 1, floor(p 2^32)), and a kept value is multiplied by scale = (float)(1 / (1 - p)); p is the
+ * descriptor's float32 value, widened to double for both (scale computed in double, rounded once; p = 1: scale = 0, every element is
+ * zero).  The attention's saved log-sum-exp is that of the un-dropped softmax.
+ * With p > 0 a stack runs every layer on the per-op kernel chain (no fused block / row-tile kernels); its workspace is
+ * m3l_transformer_ws_bytes_dropout, and its backward must get the descriptor of its forward (checked).  Shapes: beyond what every stack
+ * needs (dim % 64 == 0, dim <= 1024), dropout needs mlp_dim % 64 == 0 in bf16 (% 32 in f32) — the K of the fc2 GEMM, whose epilogue
+ * applies site 3 — and is refused with an error otherwise. */
+typedef struct m3l_dropout {
+    float p;
+    uint64_t seed;
+} m3l_dropout;
 
 int m3l_version(void);
 int m3l_last_error(char* buf, size_t n);
@@ -157,6 +178,17 @@ int m3l_transformer_bwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
 int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws,
                               const void* dy, int dy_dtype, float* dx_in, float* const* grads, int layer_hi, int layer_lo, void* stream);
 
+/* the same four with a dropout descriptor (NULL or p == 0: exactly the forms above).  With dropout the range backward writes the
+ * fc2.bias gradient of layer l inside the range of l (without, the range of l + 1 does). */
+size_t m3l_transformer_ws_bytes_dropout(const m3l_tf_cfg* c, int B, int n, const m3l_dropout* drop);
+int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t,
+                                float* y32, const m3l_dropout* drop, void* stream);
+int m3l_transformer_bwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, const void* dy,
+                                int dy_dtype, float* dx_in, float* const* grads, const m3l_dropout* drop, void* stream);
+int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws,
+                                      const void* dy, int dy_dtype, float* dx_in, float* const* grads, int layer_hi, int layer_lo,
+                                      const m3l_dropout* drop, void* stream);
+
 /* ---- frozen ViT forward (inference only): the DINOv2-S/14-reg image feature of the cfg-5 fusion head
  * (models/pretrain_models_dino_cat_mae.py:886 `self.dino_model(obs_viso)`; train_dino_cat_mae.py:29).  x: tokens (B, n, dim) f32
  * (cls + registers + patches, positions already added); y32: final-norm output (B, n, dim) f32.
@@ -231,6 +263,14 @@ int m3l_mae_step_fwd(const m3l_mae_cfg* c, int B, const float* image, const floa
 int m3l_mae_step_bwd(const m3l_mae_cfg* c, int B, const float* image, const float* const* tactiles, const int64_t* masked,
                      const int64_t* unmasked, const void* const* tensors, void* ws, const float* dloss, float* const* grads,
                      const m3l_comm_plan* comm, void* stream);
+/* the step with a dropout descriptor for the encoder (NULL = none; the decoder never drops, as in the reference) */
+size_t m3l_mae_step_ws_bytes_dropout(const m3l_mae_cfg* c, int B, const m3l_dropout* enc_drop);
+int m3l_mae_step_fwd_dropout(const m3l_mae_cfg* c, int B, const float* image, const float* const* tactiles, const float* const* noise,
+                             const void* const* tensors, void* ws, float* loss, int64_t* masked, int64_t* unmasked, const m3l_dropout* enc_drop,
+                             void* stream);
+int m3l_mae_step_bwd_dropout(const m3l_mae_cfg* c, int B, const float* image, const float* const* tactiles, const int64_t* masked,
+                             const int64_t* unmasked, const void* const* tensors, void* ws, const float* dloss, float* const* grads,
+                             const m3l_comm_plan* comm, const m3l_dropout* enc_drop, void* stream);
 
 /* ---- the policy-side consumer of the MAE in two calls: MAEExtractor.forward (models/pretrain_models.py:819-841; run on every environment
  * step at B = number of envs, and with grad on every PPO minibatch, models/ppo_mae.py:280):
@@ -245,6 +285,14 @@ int m3l_extractor_fwd(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const
                       const void* const* tensors, void* ws, float* out, void* stream);
 int m3l_extractor_bwd(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const float* image, const float* const* tactiles,
                       const void* const* tensors, void* ws, const float* dout, float* const* grads, void* stream);
+/* the same with dropout descriptors for the encoder and the head (NULL = none) */
+size_t m3l_extractor_ws_bytes_dropout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const m3l_dropout* enc_drop, const m3l_dropout* head_drop);
+int m3l_extractor_fwd_dropout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const float* image, const float* const* tactiles,
+                              const void* const* tensors, void* ws, float* out, const m3l_dropout* enc_drop, const m3l_dropout* head_drop,
+                              void* stream);
+int m3l_extractor_bwd_dropout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const float* image, const float* const* tactiles,
+                              const void* const* tensors, void* ws, const float* dout, float* const* grads, const m3l_dropout* enc_drop,
+                              const m3l_dropout* head_drop, void* stream);
 
 /* ---- EarlyCNN stem (early_conv_masking=True, the reference's default flag; pretrain_models.py:37-56,180-191): three
  * Conv2d+ReLU and a 1x1 Conv2d as im2col + MFMA GEMM.  srcs: nsrc NCHW f32 inputs of B samples each (the tactile sensors share
@@ -348,6 +396,8 @@ int m3l_op_vit_tokens(const float* emb, const float* cls, const float* regs, con
 int m3l_op_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, void* stream);
 int m3l_op_attn_bwd(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
                     int n, int H, void* stream);
+/* the dropout mask of site `site` of layer `layer` ("Dropout" above) for a (rows, N) tensor: out[row * N + c] = 1 kept / 0 dropped */
+int m3l_op_dropout_mask(float p, uint64_t seed, int layer, int site, long rows, int N, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

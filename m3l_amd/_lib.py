@@ -32,6 +32,11 @@ class MaeCfg(C.Structure):
     _fields_ = [("geom", Geom), ("enc", TfCfg), ("dec", TfCfg), ("masking_ratio", C.c_double), ("early_conv", c_i), ("learned_pos", c_i)]
 
 
+class Dropout(C.Structure):
+    """m3l_dropout: rate and the 64-bit seed of one stack's masks (include/m3l_amd.h "Dropout")."""
+    _fields_ = [("p", C.c_float), ("seed", C.c_uint64)]
+
+
 class CommPlan(C.Structure):
     _fields_ = [("flat", c_p), ("total", C.c_long), ("min_bucket", C.c_long), ("layers_per_chunk", c_i), ("n_stages", c_i),
                 ("stage_end", C.POINTER(C.c_long)), ("sent_out", C.POINTER(C.c_long))]
@@ -73,6 +78,10 @@ _SIGS = {
     "m3l_transformer_fwd": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "m3l_transformer_bwd": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
     "m3l_transformer_bwd_range": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p]),
+    "m3l_transformer_ws_bytes_dropout": (c_sz, [C.POINTER(TfCfg), c_i, c_i, C.POINTER(Dropout)]),
+    "m3l_transformer_fwd_dropout": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_p, C.POINTER(Dropout), c_p]),
+    "m3l_transformer_bwd_dropout": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, C.POINTER(Dropout), c_p]),
+    "m3l_transformer_bwd_range_dropout": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, C.POINTER(Dropout), c_p]),
     "m3l_frozen_vit_ws_bytes": (c_sz, [C.POINTER(TfCfg), c_i, c_i]),
     "m3l_frozen_vit_fwd": (c_i, [C.POINTER(TfCfg), C.c_float, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "m3l_unshuffle_ws_bytes": (c_sz, [C.POINTER(Geom), c_i, c_i, c_i, c_i, c_i, c_i]),
@@ -89,10 +98,16 @@ _SIGS = {
     "m3l_mae_step_ws_bytes": (c_sz, [C.POINTER(MaeCfg), c_i]),
     "m3l_mae_step_fwd": (c_i, [C.POINTER(MaeCfg), c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "m3l_mae_step_bwd": (c_i, [C.POINTER(MaeCfg), c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(CommPlan), c_p]),
+    "m3l_mae_step_ws_bytes_dropout": (c_sz, [C.POINTER(MaeCfg), c_i, C.POINTER(Dropout)]),
+    "m3l_mae_step_fwd_dropout": (c_i, [C.POINTER(MaeCfg), c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(Dropout), c_p]),
+    "m3l_mae_step_bwd_dropout": (c_i, [C.POINTER(MaeCfg), c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(CommPlan), C.POINTER(Dropout), c_p]),
     "m3l_extractor_num_tensors": (c_i, [C.POINTER(MaeCfg), C.POINTER(TfCfg)]),
     "m3l_extractor_ws_bytes": (c_sz, [C.POINTER(MaeCfg), C.POINTER(TfCfg), c_i]),
     "m3l_extractor_fwd": (c_i, [C.POINTER(MaeCfg), C.POINTER(TfCfg), c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "m3l_extractor_bwd": (c_i, [C.POINTER(MaeCfg), C.POINTER(TfCfg), c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_extractor_ws_bytes_dropout": (c_sz, [C.POINTER(MaeCfg), C.POINTER(TfCfg), c_i, C.POINTER(Dropout), C.POINTER(Dropout)]),
+    "m3l_extractor_fwd_dropout": (c_i, [C.POINTER(MaeCfg), C.POINTER(TfCfg), c_i, c_p, c_p, c_p, c_p, c_p, C.POINTER(Dropout), C.POINTER(Dropout), c_p]),
+    "m3l_extractor_bwd_dropout": (c_i, [C.POINTER(MaeCfg), C.POINTER(TfCfg), c_i, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(Dropout), C.POINTER(Dropout), c_p]),
     "m3l_earlycnn_ws_bytes": (c_sz, [C.POINTER(CnnCfg), c_i, c_i]),
     "m3l_earlycnn_fwd": (c_i, [C.POINTER(CnnCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "m3l_earlycnn_bwd": (c_i, [C.POINTER(CnnCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
@@ -130,6 +145,7 @@ _SIGS = {
     "m3l_op_vit_tokens": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     "m3l_op_attn_fwd": (c_i, [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "m3l_op_attn_bwd": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "m3l_op_dropout_mask": (c_i, [C.c_float, C.c_uint64, c_i, c_i, C.c_long, c_i, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

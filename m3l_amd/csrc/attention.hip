@@ -41,9 +41,15 @@ __device__ __forceinline__ void store4(bf16* p, f32x4 v) {
 }
 __device__ __forceinline__ void store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
-template <typename T>
+// word w (0..3) of a Philox block, w varying per lane
+__device__ __forceinline__ uint32_t word_of(uint4 v, int w) { return w == 0 ? v.x : (w == 1 ? v.y : (w == 2 ? v.z : v.w)); }
+// dropout factor of one element: scale when kept, 0 when dropped
+__device__ __forceinline__ float keep_f(uint32_t word, const DropCtx& dr) { return word >= dr.thr ? dr.scale : 0.f; }
+
+// DROP: site-0 dropout (include/m3l_amd.h "Dropout") — element (row = (b H + h) n + query, key) of the probabilities
+template <typename T, bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ o, float* __restrict__ lse,
-                                                         int n, int H, float scale) {
+                                                         int n, int H, float scale, DropCtx dr) {
     constexpr int ROW = AtCfg<T>::ROW;
     __shared__ __attribute__((aligned(16))) T Ks[32 * ROW];
     __shared__ __attribute__((aligned(16))) T Vs[32 * ROW];
@@ -104,6 +110,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv
             }
         lsum = lsum * alpha + ps;
         m = mn;
+        if constexpr (DROP) {     // the sum above is the un-dropped softmax's: only P.V sees the mask
+            const uint64_t qb = ((uint64_t)blockIdx.y * n + q) * (uint64_t)((n + 3) >> 2) + kt * 8 + g;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const uint4 wd = drop_words(dr.k0, dr.k1, dr.ctr2, qb + 4 * t);
+                s[t][0] *= keep_f(wd.x, dr); s[t][1] *= keep_f(wd.y, dr); s[t][2] *= keep_f(wd.z, dr); s[t][3] *= keep_f(wd.w, dr);
+            }
+        }
 #pragma unroll
         for (int d = 0; d < 4; ++d) oacc[d] *= alpha;
         const Frag<T> fp = acc_to_frag<T>(s[0], s[1]);
@@ -126,11 +140,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv
 }
 
 // dQ pass (also produces Dsum[b,h,q] = sum_d dO*O for the dK/dV pass)
-template <typename T>
+// DROP: dS = P (mask scale dP - D), D = rowsum(dO o O) unchanged (it equals rowsum of the dropped P times dP)
+template <typename T, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ o,
                                                             const T* __restrict__ dO, const float* __restrict__ lse,
                                                             float* __restrict__ dsum, T* __restrict__ dqkv, int n, int H,
-                                                            float scale) {
+                                                            float scale, DropCtx dr) {
     constexpr int ROW = AtCfg<T>::ROW;
     __shared__ __attribute__((aligned(16))) T Ks[32 * ROW];
     __shared__ __attribute__((aligned(16))) T Vs[32 * ROW];
@@ -179,6 +194,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ 
                 s = mma16(fk, fq[ks], s);
                 dp = mma16(fv, fdo[ks], dp);
             }
+            if constexpr (DROP) {
+                const uint4 wd = drop_words(dr.k0, dr.k1, dr.ctr2, ((uint64_t)blockIdx.y * n + q) * (uint64_t)((n + 3) >> 2) + kt * 8 + 4 * t + g);
+                dp[0] *= keep_f(wd.x, dr); dp[1] *= keep_f(wd.y, dr); dp[2] *= keep_f(wd.z, dr); dp[3] *= keep_f(wd.w, dr);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int key = kt * 32 + 16 * t + 4 * g + r;
@@ -202,10 +221,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ 
 }
 
 // dK / dV pass: a wave owns 16 keys and sweeps all queries.
-template <typename T>
+// DROP: dV takes the dropped P, dS as in the dQ pass.  The key is on the lane here, so every element is a Philox block of its own
+// (one word used)
+template <typename T, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__ qkv, const T* __restrict__ dO,
                                                              const float* __restrict__ lse, const float* __restrict__ dsum,
-                                                             T* __restrict__ dqkv, int n, int H, float scale) {
+                                                             T* __restrict__ dqkv, int n, int H, float scale, DropCtx dr) {
     constexpr int ROW = AtCfg<T>::ROW;
     __shared__ __attribute__((aligned(16))) T Qs[32 * ROW];
     __shared__ __attribute__((aligned(16))) T Gs[32 * ROW];   // dO tile
@@ -256,8 +277,16 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
             for (int r = 0; r < 4; ++r) {
                 const int ql = 16 * t + 4 * g + r;
                 const float pv = (key < n) ? __expf(s[r] * scale - Ls[ql]) : 0.f;
-                p[t][r] = pv;
-                ds[t][r] = pv * (dp[r] - Ds[ql]) * scale;
+                if constexpr (DROP) {
+                    const uint64_t row = (uint64_t)blockIdx.y * n + qt * 32 + ql;
+                    const uint4 wd = drop_words(dr.k0, dr.k1, dr.ctr2, row * (uint64_t)((n + 3) >> 2) + (key >> 2));
+                    const float mk = keep_f(word_of(wd, key & 3), dr);
+                    p[t][r] = pv * mk;
+                    ds[t][r] = pv * (dp[r] * mk - Ds[ql]) * scale;
+                } else {
+                    p[t][r] = pv;
+                    ds[t][r] = pv * (dp[r] - Ds[ql]) * scale;
+                }
             }
         }
         const Frag<T> fp = acc_to_frag<T>(p[0], p[1]);
@@ -284,34 +313,43 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
 
 }  // namespace
 
-int m3l_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, hipStream_t st) {
+int m3l_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, hipStream_t st, const DropCtx* drop) {
     M3L_CHECK(dtype == 0 || dtype == 1, "attn_fwd: bad dtype %d", dtype);
     M3L_CHECK(B > 0 && n > 0 && H > 0, "attn_fwd: empty problem B=%d n=%d H=%d", B, n, H);
     dim3 grid(cdiv(n, 64), B * H);
     const float scale = 0.125f;   // dim_head ** -0.5, dim_head = 64
     ProfScope prof("attn_fwd", B, n, H, 4.0 * B * H * (double)n * n * 64, st);
-    if (dtype == 1)
-        attn_fwd_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)o, lse, n, H, scale);
+    const DropCtx dr = drop ? *drop : DropCtx{};
+    if (dr.on) {
+        if (dtype == 1)
+            attn_fwd_kernel<bf16, true><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)o, lse, n, H, scale, dr);
+        else
+            attn_fwd_kernel<float, true><<<grid, 256, 0, st>>>((const float*)qkv, (float*)o, lse, n, H, scale, dr);
+    } else if (dtype == 1)
+        attn_fwd_kernel<bf16, false><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)o, lse, n, H, scale, dr);
     else
-        attn_fwd_kernel<float><<<grid, 256, 0, st>>>((const float*)qkv, (float*)o, lse, n, H, scale);
+        attn_fwd_kernel<float, false><<<grid, 256, 0, st>>>((const float*)qkv, (float*)o, lse, n, H, scale, dr);
     M3L_LAUNCH_CHECK();
     return 0;
 }
 
 int m3l_attn_bwd(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
-                 int n, int H, hipStream_t st) {
+                 int n, int H, hipStream_t st, const DropCtx* drop) {
     M3L_CHECK(dtype == 0 || dtype == 1, "attn_bwd: bad dtype %d", dtype);
     M3L_CHECK(B > 0 && n > 0 && H > 0, "attn_bwd: empty problem B=%d n=%d H=%d", B, n, H);
     dim3 grid(cdiv(n, 64), B * H);
     const float scale = 0.125f;
     ProfScope prof("attn_bwd", B, n, H, 10.0 * B * H * (double)n * n * 64, st);
+    const DropCtx dr = drop ? *drop : DropCtx{};
+#define ATTN_BWD(T, D)                                                                                                                        \
+    attn_bwd_dq_kernel<T, D><<<grid, 256, 0, st>>>((const T*)qkv, (const T*)o, (const T*)dO, lse, dsum, (T*)dqkv, n, H, scale, dr);         \
+    attn_bwd_dkv_kernel<T, D><<<grid, 256, 0, st>>>((const T*)qkv, (const T*)dO, lse, dsum, (T*)dqkv, n, H, scale, dr)
     if (dtype == 1) {
-        attn_bwd_dq_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)qkv, (const bf16*)o, (const bf16*)dO, lse, dsum, (bf16*)dqkv, n, H, scale);
-        attn_bwd_dkv_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)qkv, (const bf16*)dO, lse, dsum, (bf16*)dqkv, n, H, scale);
+        if (dr.on) { ATTN_BWD(bf16, true); } else { ATTN_BWD(bf16, false); }
     } else {
-        attn_bwd_dq_kernel<float><<<grid, 256, 0, st>>>((const float*)qkv, (const float*)o, (const float*)dO, lse, dsum, (float*)dqkv, n, H, scale);
-        attn_bwd_dkv_kernel<float><<<grid, 256, 0, st>>>((const float*)qkv, (const float*)dO, lse, dsum, (float*)dqkv, n, H, scale);
+        if (dr.on) { ATTN_BWD(float, true); } else { ATTN_BWD(float, false); }
     }
+#undef ATTN_BWD
     M3L_LAUNCH_CHECK();
     return 0;
 }

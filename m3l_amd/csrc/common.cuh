@@ -278,3 +278,22 @@ void m3l_set_error(const char* fmt, ...);
 #define M3L_LAUNCH_CHECK() M3L_HIP(hipGetLastError())
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Philox4x32-10 (Salmon et al., SC'11; the generator of the dropout masks, contract in include/m3l_amd.h).  One call = 4 words; the
+// multiplies are v_mul_hi_u32 / v_mul_lo_u32 pairs.
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+// the 4 words of Philox block q of a dropout site (element (row, c) of a site with last-axis length N uses word c % 4 of block
+// q = row * ceil(N / 4) + c / 4)
+__device__ __forceinline__ uint4 drop_words(uint32_t k0, uint32_t k1, uint32_t ctr2, uint64_t q) {
+    return philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), ctr2, 0u), k0, k1);
+}

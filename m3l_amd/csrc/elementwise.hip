@@ -1858,3 +1858,93 @@ int m3l_mse(int dtype, const float* pred, int pdpad, const PatchGroup* pg, const
     if (nblocks_out) *nblocks_out = G;
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// dropout (include/m3l_amd.h "Dropout"): the key / counter word / threshold of one site, the backward of the GEMM-output sites and the
+// mask export
+DropCtx m3l_drop_ctx(float p, uint64_t seed, int layer, int site) {
+    DropCtx d;
+    memset(&d, 0, sizeof(d));
+    d.on = p > 0.f ? 1 : 0;
+    const double pd = p;
+    const double t = floor(pd * 4294967296.0);
+    d.thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+    d.scale = pd >= 1.0 ? 0.f : (float)(1.0 / (1.0 - pd));
+    d.k0 = (uint32_t)seed;
+    d.k1 = (uint32_t)(seed >> 32);
+    d.ctr2 = (uint32_t)(4 * layer + site);
+    return d;
+}
+
+namespace {
+// a block owns `rpb` rows: thread (x, y) the 4 columns 4x of rows y, y + RY, ...; the column sums of the block go to part[block][N]
+// in a fixed order (deterministic bias gradient)
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(const T* __restrict__ dy, T* __restrict__ out, float* __restrict__ part, int M, int N,
+                                                           int rpb, DropCtx dr) {
+    __shared__ float red[1024];
+    const int NQ = N >> 2, RY = blockDim.y, tx = threadIdx.x, ty = threadIdx.y;
+    const int r0 = blockIdx.x * rpb, r1 = min(M, r0 + rpb);
+    float cs[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int r = r0 + ty; r < r1; r += RY) {
+        const long o = (long)r * N + 4 * tx;
+        const uint4 wd = drop_words(dr.k0, dr.k1, dr.ctr2, (uint64_t)r * NQ + tx);
+        const uint32_t w[4] = {wd.x, wd.y, wd.z, wd.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const T v = from_f32<T>(to_f32(dy[o + j]) * (w[j] >= dr.thr ? dr.scale : 0.f));
+            out[o + j] = v;
+            cs[j] += to_f32(v);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[ty * N + 4 * tx + j] = cs[j];
+    __syncthreads();
+    if (ty == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float s = 0.f;
+            for (int y = 0; y < RY; ++y) s += red[y * N + 4 * tx + j];
+            part[(long)blockIdx.x * N + 4 * tx + j] = s;
+        }
+    }
+}
+
+__global__ void dropout_mask_kernel(DropCtx dr, long rows, int N, uint8_t* __restrict__ out) {
+    const int NQ = (N + 3) >> 2;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * NQ) return;
+    const long r = i / NQ;
+    const int c0 = (int)(i % NQ) * 4;
+    const uint4 wd = drop_words(dr.k0, dr.k1, dr.ctr2, (uint64_t)i);
+    const uint32_t w[4] = {wd.x, wd.y, wd.z, wd.w};
+    for (int j = 0; j < 4 && c0 + j < N; ++j) out[r * N + c0 + j] = w[j] >= dr.thr ? 1 : 0;
+}
+
+int dropout_rows_per_block(int M) { return std::max(32, cdiv(M, 1024)); }
+}  // namespace
+
+int m3l_dropout_bwd_blocks(int M) { return cdiv(M, dropout_rows_per_block(M)); }
+
+int m3l_dropout_bwd(int dtype, const void* dy, int M, int N, const DropCtx* drop, void* out, float* part, hipStream_t st) {
+    M3L_CHECK(dtype == 0 || dtype == 1, "dropout_bwd: bad dtype %d", dtype);
+    M3L_CHECK(M > 0 && N > 0 && N % 4 == 0 && N <= 1024, "dropout_bwd: M=%d N=%d (N must be a multiple of 4, <= 1024)", M, N);
+    const int rpb = dropout_rows_per_block(M), NQ = N / 4;
+    const dim3 blk(NQ, std::max(1, 256 / NQ));
+    const int G = cdiv(M, rpb);
+    ProfScope prof("dropout_bwd", M, N, 0, 0.0, st, (double)M * N * (dtype ? 4.0 : 8.0));
+    if (dtype == 1)
+        dropout_bwd_kernel<bf16><<<G, blk, 0, st>>>((const bf16*)dy, (bf16*)out, part, M, N, rpb, *drop);
+    else
+        dropout_bwd_kernel<float><<<G, blk, 0, st>>>((const float*)dy, (float*)out, part, M, N, rpb, *drop);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_dropout_mask(const DropCtx* drop, long rows, int N, uint8_t* out, hipStream_t st) {
+    M3L_CHECK(rows > 0 && N > 0, "dropout_mask: rows=%ld N=%d", rows, N);
+    const long total = rows * ((N + 3) / 4);
+    dropout_mask_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(*drop, rows, N, out);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}

@@ -175,7 +175,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const T* __restrict__ A, i
 // combinations of the transformer get branch-free code the compiler can schedule across the unrolled row segments):
 //   1 FC1    bias + pre-activation copy + GELU -> out_t          2 DGELU  * gelu'(u) -> out_t (+ column-sum partials)
 //   3 PLAIN  (bias) -> out_t                                      4 RES32  bias + fp32 residual -> out_f32
-enum { EPI_GENERIC = 0, EPI_FC1 = 1, EPI_DGELU = 2, EPI_PLAIN = 3, EPI_RES32 = 4, EPI_RES16 = 5 };
+//   5 RES16  bias + bf16 residual -> out_t                         6 DROP   generic + the dropout mask (epi.drop), never taken without it
+enum { EPI_GENERIC = 0, EPI_FC1 = 1, EPI_DGELU = 2, EPI_PLAIN = 3, EPI_RES32 = 4, EPI_RES16 = 5, EPI_DROP = 6 };
 template <typename T, int BN, int R, int BM = 128, int EPI = 0>
 __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(const T* __restrict__ A, int lda, const T* __restrict__ W, int ldw,
                                                              int M, int N, int K, GemmEpi epi) {
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(const T* __restrict__
     T* out_t = reinterpret_cast<T*>(epi.out_t);
     T* out_pre = reinterpret_cast<T*>(epi.out_pre);
     const T* gelu_u = reinterpret_cast<const T*>(epi.gelu_u);
-    constexpr bool GEN = (EPI == EPI_GENERIC);
+    constexpr bool GEN = (EPI == EPI_GENERIC || EPI == EPI_DROP);
     const bool f_gelu_u = GEN ? (gelu_u != nullptr) : (EPI == EPI_DGELU);
     const bool f_out_pre = GEN ? (out_pre != nullptr) : (EPI == EPI_FC1);
     const int f_act = GEN ? epi.act : (EPI == EPI_FC1 ? 1 : 0);
@@ -410,6 +411,15 @@ __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(const T* __restrict__
                 const T* rr = reinterpret_cast<const T*>(epi.relu_ref);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = to_f32(rr[o + j]) > 0.f ? v[j] : 0.f;
+            }
+            if constexpr (EPI == EPI_DROP) {
+                // 8 columns = 2 Philox blocks (N % 8 == 0: ceil(N / 4) = N / 4)
+                const uint64_t qb = (uint64_t)row * (uint64_t)(N >> 2) + (col >> 2);
+                const uint4 w0 = drop_words(epi.drop.k0, epi.drop.k1, epi.drop.ctr2, qb);
+                const uint4 w1 = drop_words(epi.drop.k0, epi.drop.k1, epi.drop.ctr2, qb + 1);
+                const uint32_t wd[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] *= wd[j] >= epi.drop.thr ? epi.drop.scale : 0.f;
             }
             if (f_res) {
                 const f32x4 q0 = rq0[i], q1 = rq1[i];
@@ -644,7 +654,7 @@ int m3l_gemm_init() {
     M3L_HIP(hipFuncSetAttribute((const void*)gemm_nt_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES));
     M3L_HIP(hipFuncSetAttribute((const void*)gemm_nt_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES));
 #define NT_ATTR(T, BMv, E) M3L_HIP(hipFuncSetAttribute((const void*)gemm_nt_glds_kernel<T, 64, 2, BMv, E>, hipFuncAttributeMaxDynamicSharedMemorySize, glds_lds_bytes(64, 2, BMv)))
-#define NT_ATTR5(T, BMv) NT_ATTR(T, BMv, 0); NT_ATTR(T, BMv, 1); NT_ATTR(T, BMv, 2); NT_ATTR(T, BMv, 3); NT_ATTR(T, BMv, 4); NT_ATTR(T, BMv, 5)
+#define NT_ATTR5(T, BMv) NT_ATTR(T, BMv, 0); NT_ATTR(T, BMv, 1); NT_ATTR(T, BMv, 2); NT_ATTR(T, BMv, 3); NT_ATTR(T, BMv, 4); NT_ATTR(T, BMv, 5); NT_ATTR(T, BMv, 6)
     NT_ATTR5(bf16, 128); NT_ATTR5(float, 128); NT_ATTR5(bf16, 64); NT_ATTR5(float, 64);
 #undef NT_ATTR5
 #undef NT_ATTR
@@ -678,7 +688,9 @@ int m3l_gemm_nt(int dtype, const void* A, int lda, const void* W, int ldw, int M
         // tiles at 1-2 workgroups per CU); 64-row tiles when 128-row tiles would leave the chip under-filled
         const bool plain_alpha = epi->alpha == 1.0f && !epi->relu_ref;
         int mode = EPI_GENERIC;
-        if (plain_alpha && epi->out_t && epi->out_pre && epi->act == 1 && !epi->gelu_u && !epi->res && !epi->res_t && !epi->out_f32 && !epi->colsum_part)
+        if (epi->drop.on)
+            mode = EPI_DROP;
+        else if (plain_alpha && epi->out_t && epi->out_pre && epi->act == 1 && !epi->gelu_u && !epi->res && !epi->res_t && !epi->out_f32 && !epi->colsum_part)
             mode = EPI_FC1;
         else if (plain_alpha && epi->out_t && epi->gelu_u && !epi->out_pre && epi->act == 0 && !epi->res && !epi->res_t && !epi->out_f32)
             mode = EPI_DGELU;
@@ -698,6 +710,7 @@ int m3l_gemm_nt(int dtype, const void* A, int lda, const void* W, int ldw, int M
         case EPI_PLAIN: NT_LAUNCH(T, BMv, EPI_PLAIN); break;   \
         case EPI_RES32: NT_LAUNCH(T, BMv, EPI_RES32); break;   \
         case EPI_RES16: NT_LAUNCH(T, BMv, EPI_RES16); break;   \
+        case EPI_DROP: NT_LAUNCH(T, BMv, EPI_DROP); break;     \
         default: NT_LAUNCH(T, BMv, EPI_GENERIC); break;        \
     }
         if (dtype == 1) {
@@ -709,6 +722,7 @@ int m3l_gemm_nt(int dtype, const void* A, int lda, const void* W, int ldw, int M
 #undef NT_LAUNCH
     } else {
         M3L_CHECK(epi->colsum_part == nullptr, "gemm_nt: colsum epilogue needs K %% %d == 0", bke);
+        M3L_CHECK(!epi->drop.on, "gemm_nt: the dropout epilogue needs K %% %d == 0 (got K=%d)", bke, K);
         dim3 grid(cdiv(N, BN), cdiv(M, BM));
         if (dtype == 1)
             gemm_nt_kernel<bf16><<<grid, 256, NT_LDS_BYTES, st>>>((const bf16*)A, lda, (const bf16*)W, ldw, M, N, K, *epi);

@@ -11,6 +11,18 @@
 
 // dtype codes: 0 = f32, 1 = bf16
 
+// Dropout of one site of one layer (the generator contract is in include/m3l_amd.h, "Dropout"): Philox4x32-10 with key = the call
+// seed, counter = (q_lo, q_hi, ctr2 = 4 layer + site, 0); an element is kept iff its word >= thr and then multiplied by scale.  on == 0:
+// no dropout (the launchers take the kernels without the mask code).
+struct DropCtx {
+    uint32_t thr;
+    float scale;
+    uint32_t k0, k1;
+    uint32_t ctr2;
+    int on;
+};
+DropCtx m3l_drop_ctx(float p, uint64_t seed, int layer, int site);     // on = (p > 0)
+
 // RAII HIP-event bracket around one launch (prof.hip); a no-op unless m3l_prof_begin() is active.
 struct ProfScope {
     int idx;
@@ -34,6 +46,7 @@ struct GemmEpi {
     int n_bias;            // bias has n_bias valid entries (columns beyond read as 0); 0 -> N
     float* colsum_part;    // [m3l_gemm_nt_colsum_rows(M, N), N] per-row-block column sums of out_t (bias gradient fused into a dgrad) or null
     const void* res_t;     // bf16 [M, ldc] residual added last (bf16 residual stream: the result goes to out_t), or null; not with res / gelu_u
+    DropCtx drop;          // on: multiply by mask * scale after the activation / gelu'(u) factor, before the residual (element (row, col), N = GEMM N)
 };
 
 struct WeightDesc {
@@ -188,9 +201,16 @@ int m3l_qkv_bwd_t192_supported(int dtype, int D, int K, int M);
 int m3l_qkv_bwd_t192_tiles(int D, int M);
 int m3l_qkv_bwd_t192(int D, int M, int K, const void* dqkv, const float* x, const float* ln1_w, const void* wqkvT, const float* dres, float eps,
                      float* dx_out, void* dxt_out, float* ln_part, hipStream_t st);
-int m3l_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, hipStream_t st);
+// drop (optional, site 0): the probabilities that multiply V are masked and scaled; lse stays that of the un-dropped softmax
+int m3l_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, hipStream_t st, const DropCtx* drop = nullptr);
 int m3l_attn_bwd(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B, int n,
-                 int H, hipStream_t st);
+                 int H, hipStream_t st, const DropCtx* drop = nullptr);
+// dropout backward of a GEMM output site (1, 3): out = mask * scale * dy (compute type, [M, N] dense) and the column sums of out
+// (= the Linear's bias gradient) as partial rows part[m3l_dropout_bwd_blocks(M)][N]
+int m3l_dropout_bwd_blocks(int M);
+int m3l_dropout_bwd(int dtype, const void* dy, int M, int N, const DropCtx* drop, void* out, float* part, hipStream_t st);
+// the mask itself (uint8 0 / 1, [rows, N]): the debug export of the generator
+int m3l_dropout_mask(const DropCtx* drop, long rows, int N, uint8_t* out, hipStream_t st);
 
 int m3l_ln_fwd(int out_dtype, const float* x, int M, int D, const float* gamma, const float* beta, float eps, void* y, float* y32,
                hipStream_t st);

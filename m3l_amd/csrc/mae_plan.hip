@@ -279,8 +279,28 @@ struct TfWs {
     float* ln_part;       // [2 depth + 1][ln_part_stride]: dgamma / dbeta / bias-grad partials of every LayerNorm backward, reduced in one launch
     size_t ln_part_stride;
     size_t scratch_b, scratch_tn_b;
+    // dropout (layout of a stack called with a descriptor of p > 0 only): the masked residual gradients of sites 3 (fc2 output) and 1
+    // (out-proj output) per operand set — the operands of the dgrad, the weight gradient and the bias column sums — and the column-sum
+    // partial rows of their bias gradients
+    std::vector<void*> dp3, dp1;
+    float* dpart;
     size_t total;
 };
+// what the forward of a stack ran with, by workspace: the backward checks that it recomputes the same (the backward re-derives
+// the forward's kernel choices from process-global switches).  The choices that decide WHAT the workspace holds must not change in
+// between: the residual mode (bf16 or fp32 activations), whether the fused feed-forward kernels saved h (drop_h), the dropout descriptor
+// (the masks).  The kernel family (enc_mega / block / row tile / per-op) may differ: every family reads and writes the same workspace
+// tensors with the same meaning.  A record is dropped by the backward that reaches layer 0; the map is cleared if it ever holds more than
+// kTfRecMax workspaces (forwards without a backward), which only skips the check for those.
+struct TfRecord {
+    int rb, drop_h;
+    float p;
+    uint64_t seed;
+};
+constexpr size_t kTfRecMax = 4096;
+std::mutex g_tf_rec_mu;
+std::map<const void*, TfRecord> g_tf_rec;
+inline bool drop_active(const m3l_dropout* d) { return d != nullptr && d->p > 0.f; }
 // bf16 residual mode: the fp32 running-gradient buffer w.dx is not used; its memory holds the stack's input as bf16 (kept for the backward
 // of layer 0) and the bf16 gradient of layer 0's input (cast to the caller's fp32 dx_in)
 inline void* rb_xin(const TfWs& w) { return w.dx; }
@@ -295,7 +315,7 @@ void layer_wgrad_problems(TnProblem* pr, int D, int HD, int mlp, bool project_ou
     if (project_out) { pr[np].N = D; pr[np++].K = HD; }
     *np_out = np;
 }
-TfWs tf_layout(const m3l_tf_cfg* c, int B, int n, void* ws) {
+TfWs tf_layout(const m3l_tf_cfg* c, int B, int n, void* ws, bool dropout = false) {
     Arena a(ws);
     const size_t M = (size_t)B * n, D = c->dim, HD = (size_t)c->heads * 64, mlp = c->mlp_dim, e = esz(c->dtype);
     TfWs w;
@@ -351,6 +371,16 @@ TfWs tf_layout(const m3l_tf_cfg* c, int B, int n, void* ws) {
     for (int i = 0; i < w.nset; ++i) w.scratch2[i] = a.take_n<float>((size_t)std::max(std::max(m3l_gemm_nt_colsum_rows((int)M, (int)mlp), B), t192_rows_max) * mlp);   // B: one partial row per sample (block kernels)
     w.ln_part_stride = (size_t)std::max(std::max(m3l_ln_bwd_blocks((int)M), B), t192_tiles_max) * 3 * D;
     w.ln_part = a.take_n<float>((size_t)(2 * c->depth + 1) * w.ln_part_stride);
+    w.dpart = nullptr;
+    if (dropout) {
+        w.dp3.resize(w.nset);
+        w.dp1.resize(w.nset);
+        for (int i = 0; i < w.nset; ++i) {
+            w.dp3[i] = a.take(M * D * e);
+            w.dp1[i] = a.take(M * D * e);
+        }
+        w.dpart = a.take_n<float>((size_t)m3l_dropout_bwd_blocks((int)M) * D);
+    }
     w.total = a.off + 256;
     return w;
 }
@@ -370,7 +400,7 @@ int check_tf(const m3l_tf_cfg* c, int B, int n) {
 // =================================================================================================================
 extern "C" {
 
-int m3l_version(void) { return 400; }
+int m3l_version(void) { return 401; }
 
 // diagnostic switch (bench.py's stand-alone roofline figure, PMC passes): 1 = every weight gradient on the caller's stream
 int m3l_set_wgrad_inline(int on) {
@@ -608,16 +638,30 @@ int m3l_embed_bwd(const m3l_geom* g, int D, int dtype, int B, int L, int cnt_img
 
 // ---------------------------------------------------------------------------------------------------------------
 // transformer
-size_t m3l_transformer_ws_bytes(const m3l_tf_cfg* c, int B, int n) {
+size_t m3l_transformer_ws_bytes(const m3l_tf_cfg* c, int B, int n) { return m3l_transformer_ws_bytes_dropout(c, B, n, nullptr); }
+
+size_t m3l_transformer_ws_bytes_dropout(const m3l_tf_cfg* c, int B, int n, const m3l_dropout* drop) {
     if (check_tf(c, B, n)) return 0;
-    return tf_layout(c, B, n, nullptr).total;
+    return tf_layout(c, B, n, nullptr, drop_active(drop)).total;
 }
 
 int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t,
                         float* y32, void* stream) {
+    return m3l_transformer_fwd_dropout(c, B, n, x_in, tensors, ws, y_t, y32, nullptr, stream);
+}
+
+// With a dropout descriptor of p > 0 every layer takes the per-op chain (LN, QKV GEMM, attention, out-proj GEMM, LN, fc1, fc2): the
+// masks live in the attention kernels and the NT GEMM epilogue only.  The residual mode is the one tf_rb picks without dropout.
+int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t,
+                                float* y32, const m3l_dropout* drop, void* stream) {
     if (check_tf(c, B, n)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    TfWs w = tf_layout(c, B, n, ws);
+    const bool dp = drop_active(drop);
+    M3L_CHECK(!dp || drop->p <= 1.f, "transformer: dropout p=%g outside [0, 1]", (double)drop->p);
+    // the per-op chain's fc2 GEMM takes the dropout epilogue only on the LDS-DMA kernel: K = mlp_dim in whole K tiles
+    M3L_CHECK(!dp || c->mlp_dim % (c->dtype ? 64 : 32) == 0, "transformer: dropout needs mlp_dim %% %d == 0 (got %d)", c->dtype ? 64 : 32,
+              c->mlp_dim);
+    TfWs w = tf_layout(c, B, n, ws, dp);
     const int M = B * n, D = c->dim, HD = c->heads * 64, mlp = c->mlp_dim, dt = c->dtype;
     const float* x = x_in;
     // compute-type weight copies (+ transposes for the dgrads) of every layer: one launch per 16 layers, on the caller's stream
@@ -640,12 +684,19 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
     if (m3l_prep_mode() == 1) return 0;            // collect pass of a call chain (mae_step.hip)
     // LayerNorms fused into the epilogue of the GEMM that produces their input (gemm_rowln.hip) when the row width allows it:
     // out-proj + LN2 of the layer, fc2 + LN1 of the next layer (or the final norm).  Only the very first LN1 is a kernel.
-    const bool fuse = use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, HD) && m3l_gemm_nt_rowln_supported(dt, D, mlp);
+    const bool fuse_cfg = use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, HD) && m3l_gemm_nt_rowln_supported(dt, D, mlp);
+    const bool fuse = fuse_cfg && !dp;
     const void* const* tfin = tensors + 11 * c->depth;
     bool final_done = false;
     // bf16 residual stream: the stack's input as bf16 (kept for the backward of layer 0 in the otherwise unused w.dx buffer); from here on
     // every `float*` of the residual stream points at bf16 data and the launchers are told so
-    const bool rb = tf_rb(c, B, n, fuse);
+    const bool rb = tf_rb(c, B, n, fuse_cfg);
+    {
+        std::lock_guard<std::mutex> lock(g_tf_rec_mu);
+        if (g_tf_rec.size() >= kTfRecMax && g_tf_rec.find(ws) == g_tf_rec.end()) g_tf_rec.clear();
+        g_tf_rec[ws] = TfRecord{rb ? 1 : 0, drop_h() ? 1 : 0, dp ? drop->p : 0.f, dp ? drop->seed : 0};
+    }
+    auto dctx = [&](int layer, int site) { return dp ? m3l_drop_ctx(drop->p, drop->seed, layer, site) : DropCtx{}; };
     if (rb && !m3l_call_io()) {          // (m3l_call_io: the caller hands x_in over as bf16 already)
         if (m3l_cast_f32(1, x_in, (long)M * D, rb_xin(w), st)) return 1;
         x = reinterpret_cast<const float*>(rb_xin(w));
@@ -653,7 +704,7 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
     RbScope rb_scope(rb);
     // short sequences whose every half layer takes a block kernel: the whole stack in ONE launch (enc_mega.hip)
     int l_begin = 0;
-    if ((m3l_enc_mega_enabled() & 1) && !fuse && c->depth >= 1 && c->depth <= M3L_MEGA_MAX_LAYERS && c->project_out &&
+    if (!dp && (m3l_enc_mega_enabled() & 1) && !fuse && c->depth >= 1 && c->depth <= M3L_MEGA_MAX_LAYERS && c->project_out &&
         m3l_attn_block_supported(dt, D, c->heads, n, c->project_out) && m3l_mlp_block_supported(dt, D, mlp, n) &&
         !(m3l_mlp_t192_short() && m3l_mlp_t192_supported(dt, D, mlp, M))) {
         const void* lay[M3L_MEGA_MAX_LAYERS][20];
@@ -676,14 +727,14 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
         const float *ln1_w = (const float*)t[0], *ln1_b = (const float*)t[1], *out_b = (const float*)t[4], *ln2_w = (const float*)t[5],
                     *ln2_b = (const float*)t[6], *fc1_b = (const float*)t[8], *fc2_b = (const float*)t[10];
 
-        const bool block = !fuse && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out);
+        const bool block = !dp && !fuse && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out);
         if (block) {
             // the whole attention half of the layer in one launch (short sequences: the MAE encoder)
             if (m3l_attn_block_fwd(D, B, n, x, ln1_w, ln1_b, L.wqkv, L.wo, out_b, ln2_w, ln2_b, LN_EPS, L.xn1, L.qkv, L.o, L.lse, L.x1,
                                    L.xn2, st))
                 return 1;
         }
-        const bool attn_t = !block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B);
+        const bool attn_t = !dp && !block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B);
         if (attn_t) {
             // long sequences: LN1 + QKV + attention of a sample in one launch (the out-proj + LN2 continue in the feed-forward launch)
             if (m3l_attn_t192_fwd(D, B, n, x, ln1_w, ln1_b, L.wqkv, LN_EPS, L.xn1, L.qkv, L.o, L.lse, st)) return 1;
@@ -696,9 +747,10 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
         if (!block) {
         if (!attn_t) {
         if (m3l_gemm_nt(dt, L.xn1, D, L.wqkv, D, M, 3 * HD, D, &e, st)) return 1;
-        if (m3l_attn_fwd(dt, L.qkv, L.o, L.lse, B, n, c->heads, st)) return 1;
+        const DropCtx d0 = dctx(l, 0);
+        if (m3l_attn_fwd(dt, L.qkv, L.o, L.lse, B, n, c->heads, st, &d0)) return 1;
         }
-        if (c->project_out && !fuse && m3l_attn_tail_mlp_t192_supported(dt, D, HD, mlp, M)) {
+        if (!dp && c->project_out && !fuse && m3l_attn_tail_mlp_t192_supported(dt, D, HD, mlp, M)) {
             // long sequences: out-proj + residual + LN2 + fc1 + GELU + fc2 + residual in ONE launch per 192-row tile
             if (m3l_attn_tail_mlp_t192_fwd(D, M, mlp, L.o, x, L.wo, out_b, ln2_w, ln2_b, LN_EPS, L.x1, L.xn2, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused,
                                            L.xout, st))
@@ -715,6 +767,7 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
             if (c->project_out) {
                 e = epi0(D);
                 e.bias = out_b;
+                e.drop = dctx(l, 1);
                 if (rb) { e.res_t = x; e.out_t = L.x1; } else { e.res = x; e.out_f32 = L.x1; }
                 if (m3l_gemm_nt(dt, L.o, HD, L.wo, HD, M, D, HD, &e, st)) return 1;
             } else {
@@ -723,20 +776,21 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
             if (m3l_ln_fwd(dt, L.x1, M, D, ln2_w, ln2_b, LN_EPS, L.xn2, nullptr, st)) return 1;
         }
         }
-        if (block && !(m3l_mlp_t192_short() && m3l_mlp_t192_supported(dt, D, mlp, M)) && m3l_mlp_block_supported(dt, D, mlp, n)) {
+        if (!dp && block && !(m3l_mlp_t192_short() && m3l_mlp_t192_supported(dt, D, mlp, M)) && m3l_mlp_block_supported(dt, D, mlp, n)) {
             // the feed-forward half in one launch as well
             if (m3l_mlp_block_fwd(D, mlp, B, n, L.xn2, L.x1, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused, L.xout, st)) return 1;
             x = L.xout;
             continue;
         }
-        if (!fuse && m3l_mlp_t192_supported(dt, D, mlp, M)) {
+        if (!dp && !fuse && m3l_mlp_t192_supported(dt, D, mlp, M)) {
             // long sequences: fc1 + GELU + fc2 + residual per 192-row tile, the hidden activation never leaves the CU between the GEMMs
             if (m3l_mlp_t192_fwd(D, M, mlp, L.xn2, L.x1, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused, L.xout, st)) return 1;
             x = L.xout;
             continue;
         }
         e = epi0(mlp);
-        e.bias = fc1_b; e.act = 1; e.out_pre = L.u; e.out_t = L.h;
+        e.bias = fc1_b; e.act = 1; e.out_pre = L.u; e.out_t = L.h;     // dropout: h is saved dropped (fc2's operand and its wgrad operand)
+        e.drop = dctx(l, 2);
         if (m3l_gemm_nt(dt, L.xn2, D, L.w1, D, M, mlp, D, &e, st)) return 1;
         if (fuse) {
             RowLnEpi r;
@@ -756,6 +810,7 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
         } else {
             e = epi0(D);
             e.bias = fc2_b;
+            e.drop = dctx(l, 3);
             if (rb) { e.res_t = L.x1; e.out_t = L.xout; } else { e.res = L.x1; e.out_f32 = L.xout; }
             if (m3l_gemm_nt(dt, L.h, mlp, L.w2, mlp, M, D, mlp, &e, st)) return 1;
         }
@@ -767,21 +822,34 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
 
 int m3l_transformer_bwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, const void* dy,
                         int dy_dtype, float* dx_in, float* const* grads, void* stream) {
-    return m3l_transformer_bwd_range(c, B, n, x_in, tensors, ws, dy, dy_dtype, dx_in, grads, c->depth, 0, stream);
+    return m3l_transformer_bwd_range_dropout(c, B, n, x_in, tensors, ws, dy, dy_dtype, dx_in, grads, c->depth, 0, nullptr, stream);
+}
+int m3l_transformer_bwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, const void* dy,
+                                int dy_dtype, float* dx_in, float* const* grads, const m3l_dropout* drop, void* stream) {
+    return m3l_transformer_bwd_range_dropout(c, B, n, x_in, tensors, ws, dy, dy_dtype, dx_in, grads, c->depth, 0, drop, stream);
+}
+int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, const void* dy,
+                              int dy_dtype, float* dx_in, float* const* grads, int layer_hi, int layer_lo, void* stream) {
+    return m3l_transformer_bwd_range_dropout(c, B, n, x_in, tensors, ws, dy, dy_dtype, dx_in, grads, layer_hi, layer_lo, nullptr, stream);
 }
 
 // Backward of layers [layer_lo, layer_hi), descending.  layer_hi == depth also runs the final-norm backward (consumes dy);
 // layer_lo == 0 writes dx_in.  The running residual gradient lives in the workspace between calls, so a caller can split the
 // backward into chunks and start the gradient all-reduce of a chunk while the next one computes.  On return every gradient of
 // the layers in the range (and fc2.bias of layer_lo - 1) is ordered on `stream`.
-int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, const void* dy,
-                              int dy_dtype, float* dx_in, float* const* grads, int layer_hi, int layer_lo, void* stream) {
+// With dropout the bias gradients of out-proj and fc2 are the column sums of the masked gradients (site 1 / 3 launches of the layer
+// itself), not of the LayerNorm backwards' results; every gradient of the layers in the range is still complete on return.
+int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, const void* dy,
+                                      int dy_dtype, float* dx_in, float* const* grads, int layer_hi, int layer_lo, const m3l_dropout* drop,
+                                      void* stream) {
     if (check_tf(c, B, n)) return 1;
+    const bool dp = drop_active(drop);
     M3L_CHECK(0 <= layer_lo && layer_lo <= layer_hi && layer_hi <= c->depth, "transformer_bwd: bad layer range [%d, %d)", layer_lo, layer_hi);
     M3L_CHECK(dy_dtype == 0 || dy_dtype == c->dtype, "transformer_bwd: dy dtype %d incompatible with compute dtype %d", dy_dtype, c->dtype);
     hipStream_t st = (hipStream_t)stream;
-    TfWs w = tf_layout(c, B, n, ws);
+    TfWs w = tf_layout(c, B, n, ws, dp);
     const int M = B * n, D = c->dim, HD = c->heads * 64, mlp = c->mlp_dim, dt = c->dtype;
+    auto dctx = [&](int layer, int site) { return dp ? m3l_drop_ctx(drop->p, drop->seed, layer, site) : DropCtx{}; };
     // every LayerNorm backward leaves its [G][3 D] partials (dgamma | dbeta | column sums = bias gradient of the Linear that fed the
     // residual branch) in its own slot; ONE batched reduce at the end of the range, on the side stream, replaces 2 small launches per
     // layer on the critical path
@@ -802,6 +870,18 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
     };
     const float* x_last = c->depth ? w.L[c->depth - 1].xout : x_in;
     const bool rb = tf_rb(c, B, n, use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, mlp) && m3l_gemm_nt_rowln_supported(dt, D, 3 * HD));
+    {
+        std::lock_guard<std::mutex> lock(g_tf_rec_mu);
+        auto it = g_tf_rec.find(ws);
+        if (it != g_tf_rec.end()) {
+            const TfRecord& r = it->second;
+            M3L_CHECK(r.rb == (rb ? 1 : 0) && r.drop_h == (drop_h() ? 1 : 0) && r.p == (dp ? drop->p : 0.f) && r.seed == (dp ? drop->seed : 0),
+                      "transformer_bwd: the forward on this workspace ran with residual mode %d, drop_h %d, dropout p=%g seed=%llu; the backward "
+                      "got %d, %d, p=%g seed=%llu", r.rb, r.drop_h, (double)r.p, (unsigned long long)r.seed, rb ? 1 : 0, drop_h() ? 1 : 0,
+                      dp ? (double)drop->p : 0.0, (unsigned long long)(dp ? drop->seed : 0));
+            if (layer_lo == 0) g_tf_rec.erase(it);
+        }
+    }
     RbScope rb_scope(rb);     // bf16 residual stream: x / x1 / xout hold bf16, the running residual gradient lives in the dx_t sets only
     const void* const* tf = tensors + 11 * c->depth;
     float* const* gf = grads + 11 * c->depth;
@@ -809,14 +889,14 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
     // (= bias gradient of the Linear that produced the residual branch): no separate cast / colsum passes.
     const int NS = w.nset;
     if (layer_hi == c->depth) {
-        float* db_last = c->depth ? grads[11 * (c->depth - 1) + 10] : nullptr;   // fc2 bias of the last layer
+        float* db_last = (c->depth && !dp) ? grads[11 * (c->depth - 1) + 10] : nullptr;   // fc2 bias of the last layer
         const int top = c->depth ? (c->depth - 1) % NS : 0;
         if (m3l_ln_bwd(dy_dtype, dy, x_last, M, D, (const float*)tf[0], LN_EPS, nullptr, rb ? nullptr : w.dx, c->depth ? w.dx_t[top] : nullptr, dt,
                        ln_slot(2 * c->depth, gf[0], gf[1], db_last), nullptr, nullptr, nullptr, 0, st))
             return 1;
     }
     if (side_init()) return 2;
-    const bool fuse = use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, mlp) && m3l_gemm_nt_rowln_supported(dt, D, 3 * HD);
+    const bool fuse = !dp && use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, mlp) && m3l_gemm_nt_rowln_supported(dt, D, 3 * HD);
     const bool wg_inline = wgrad_inline();
     hipStream_t s2 = wg_inline ? st : g_side.s;
     // completion of the wgrad launch that last read operand set i.  A backward split into several range calls (chunks, for the
@@ -863,7 +943,7 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
     };
     const int csrows = m3l_gemm_nt_colsum_rows(M, mlp);
     // short sequences whose both backward halves take a block kernel: one launch per weight-gradient group of layers (enc_mega.hip)
-    const bool mega_bwd = (m3l_enc_mega_enabled() & 2) && !fuse && c->project_out && m3l_mlp_block_bwd_supported(dt, D, mlp, n) &&
+    const bool mega_bwd = !dp && (m3l_enc_mega_enabled() & 2) && !fuse && c->project_out && m3l_mlp_block_bwd_supported(dt, D, mlp, n) &&
                           !(m3l_mlp_t192_supported(dt, D, mlp, M) && m3l_mlp_t192_short()) && m3l_attn_block_bwd_enabled() &&
                           m3l_attn_block_supported(dt, D, c->heads, n, c->project_out) && w.wg_batch <= M3L_MEGA_BWD_MAX_LAYERS;
     for (int l = layer_hi - 1; l >= layer_lo; --l) {
@@ -908,8 +988,16 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
         // set `cur` (dx_t[cur] was written by layer l+1's last kernel, which claimed the set) receives du / dx1_t / dqkv of this layer
         // ---- feed-forward: x_out = x1 + fc2(gelu(fc1(LN2(x1))))
         GemmEpi e = epi0(mlp);
-        const bool mlp_t192 = !fuse && m3l_mlp_t192_supported(dt, D, mlp, M) && (m3l_mlp_t192_short() || !m3l_mlp_block_bwd_supported(dt, D, mlp, n));
-        const bool mlp_block = !fuse && !mlp_t192 && m3l_mlp_block_bwd_supported(dt, D, mlp, n);
+        // dropout: dpre3 = mask3 scale dx (the fc2 output's gradient) -> fc2 bias gradient now, operand of the dgrad and of dW2
+        const void* dy3 = w.dx_t[cur];
+        if (dp) {
+            const DropCtx d3 = dctx(l, 3);
+            if (m3l_dropout_bwd(dt, w.dx_t[cur], M, D, &d3, w.dp3[cur], w.dpart, st)) return 1;
+            if (g[10] && m3l_reduce_rows(w.dpart, m3l_dropout_bwd_blocks(M), D, D, g[10], 0, st)) return 1;
+            dy3 = w.dp3[cur];
+        }
+        const bool mlp_t192 = !dp && !fuse && m3l_mlp_t192_supported(dt, D, mlp, M) && (m3l_mlp_t192_short() || !m3l_mlp_block_bwd_supported(dt, D, mlp, n));
+        const bool mlp_block = !dp && !fuse && !mlp_t192 && m3l_mlp_block_bwd_supported(dt, D, mlp, n);
         int cs_rows = csrows;
         if (mlp_block) {
             // short sequences: du, its column sums, dxn2 and the LN2 backward in one launch; one partial row per sample
@@ -925,7 +1013,8 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
                 return 1;
         } else {
         e.out_t = w.du[cur]; e.gelu_u = L.u; e.colsum_part = w.scratch2[cur];
-        if (m3l_gemm_nt(dt, w.dx_t[cur], D, L.w2T, D, M, mlp, D, &e, st)) return 1;                   // du = (dx W2) * gelu'(u)
+        e.drop = dctx(l, 2);                                                                             // (dropout: * mask2 scale)
+        if (m3l_gemm_nt(dt, dy3, D, L.w2T, D, M, mlp, D, &e, st)) return 1;                            // du = (dx W2) * gelu'(u)
         // (the per-row-block column sums in scratch2[cur] = fc1 bias gradient partials are reduced by the wgrad group's reduce)
         }
         if (mlp_block || mlp_t192) {
@@ -943,14 +1032,14 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
             // dx1 = dx + LN2-backward (in place), + compute-type copy, + out-proj bias grad
             // (bf16 residual stream: the residual gradient is dx_t[cur] itself, the result exists in the compute type only)
             if (m3l_ln_bwd(dt, w.dxn, L.x1, M, D, (const float*)t[5], LN_EPS, rb ? reinterpret_cast<const float*>(w.dx_t[cur]) : w.dx,
-                           rb ? nullptr : w.dx, w.dx1_t[cur], dt, ln_slot(2 * l + 1, g[5], g[6], c->project_out ? g[4] : nullptr), nullptr,
+                           rb ? nullptr : w.dx, w.dx1_t[cur], dt, ln_slot(2 * l + 1, g[5], g[6], (c->project_out && !dp) ? g[4] : nullptr), nullptr,
                            nullptr, nullptr, 0, st))
                 return 1;
         }
         // ---- attention: x1 = x + to_out(attn(LN1(x)))
         const bool attn_block = mlp_block && m3l_attn_block_bwd_enabled() && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out);
         float* dx_dst = (l == 0 && dx_in) ? dx_in : w.dx;
-        float* db_prev = l ? grads[11 * (l - 1) + 10] : nullptr;                                      // fc2 bias of layer l-1
+        float* db_prev = (l && !dp) ? grads[11 * (l - 1) + 10] : nullptr;                             // fc2 bias of layer l-1
         if (attn_block) {
             // short sequences: dO, the attention backward, dxn1 and the LN1 backward in one launch.  It writes dx_t[nxt] (the next
             // layer's operand set)
@@ -966,7 +1055,14 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
                 return 1;
         }
         const void* d_o = w.dx1_t[cur];
-        const bool attn_t = !attn_block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B);
+        const void* dy1 = w.dx1_t[cur];           // gradient of the out-proj output (dropout: dpre1 = mask1 scale dx1)
+        if (dp && c->project_out) {
+            const DropCtx d1 = dctx(l, 1);
+            if (m3l_dropout_bwd(dt, w.dx1_t[cur], M, D, &d1, w.dp1[cur], w.dpart, st)) return 1;
+            if (g[4] && m3l_reduce_rows(w.dpart, m3l_dropout_bwd_blocks(M), D, D, g[4], 0, st)) return 1;
+            dy1 = w.dp1[cur];
+        }
+        const bool attn_t = !dp && !attn_block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B);
         if (attn_t) {
             // long sequences: dO + both attention-backward passes of a sample in one launch
             if (m3l_attn_t192_bwd(D, B, n, w.dx1_t[cur], L.qkv, L.o, L.lse, L.woT, w.dqkv[cur], st)) return 1;
@@ -975,20 +1071,21 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
         if (c->project_out) {
             e = epi0(HD);
             e.out_t = w.d_o;
-            if (m3l_gemm_nt(dt, w.dx1_t[cur], D, L.woT, D, M, HD, D, &e, st)) return 1;               // do = dx1 Wo
+            if (m3l_gemm_nt(dt, dy1, D, L.woT, D, M, HD, D, &e, st)) return 1;                          // do = dx1 Wo
             d_o = w.d_o;
         }
-        if (m3l_attn_bwd(dt, L.qkv, L.o, d_o, L.lse, w.dsum, w.dqkv[cur], B, n, c->heads, st)) return 1;
+        const DropCtx d0 = dctx(l, 0);
+        if (m3l_attn_bwd(dt, L.qkv, L.o, d_o, L.lse, w.dsum, w.dqkv[cur], B, n, c->heads, st, &d0)) return 1;
         }
         // ---- the weight gradients of the layer join the pending group; every wg_batch layers (and at the end of the range) the group
         // goes out as ONE grouped TN launch + one reduce on the side stream, overlapping the dgrad chains of the layers below
         {
             // dW2 = dx^T h; when the forward did not save h the kernel stages u and applies the GELU of the kernel that made it
-            const int hk = (drop_h() && fused_mlp_kind(c, B, n, fuse)) ? 2 : 0;     // every bf16 kernel evaluates the fitted GELU (form 2)
-            pend.push_back(TnProblem{w.dx_t[cur], hk ? L.u : L.h, D, mlp, D, mlp, g[9], mlp, D, mlp, 0, 0, hk});
+            const int hk = (!dp && drop_h() && fused_mlp_kind(c, B, n, fuse)) ? 2 : 0;     // every bf16 kernel evaluates the fitted GELU (form 2)
+            pend.push_back(TnProblem{dy3, hk ? L.u : L.h, D, mlp, D, mlp, g[9], mlp, D, mlp, 0, 0, hk});
             pend.push_back(TnProblem{w.du[cur], L.xn2, mlp, D, mlp, D, g[7], D, mlp, D, 0, 0});             // dW1 = du^T xn2
             pend.push_back(TnProblem{w.dqkv[cur], L.xn1, 3 * HD, D, 3 * HD, D, g[2], D, 3 * HD, D, 0, 0}); // dWqkv = dqkv^T xn1
-            if (c->project_out) pend.push_back(TnProblem{w.dx1_t[cur], L.o, D, HD, D, HD, g[3], HD, D, HD, 0, 0});   // dWo = dx1^T o
+            if (c->project_out) pend.push_back(TnProblem{dy1, L.o, D, HD, D, HD, g[3], HD, D, HD, 0, 0});   // dWo = dx1^T o
             pend_ex.push_back(TnExtra{w.scratch2[cur], g[8], cs_rows, mlp});                                // fc1 bias gradient
             pend_sets.push_back(cur);
             if ((int)pend_sets.size() >= w.wg_batch || l == layer_lo) {
@@ -1005,7 +1102,7 @@ int m3l_transformer_bwd_range(const m3l_tf_cfg* c, int B, int n, const float* x_
             r.part = w.scratch; r.eps = LN_EPS;
             if (m3l_gemm_nt_rowln(dt, ROWLN_BWD, w.dqkv[cur], 3 * HD, L.wqkvT, 3 * HD, M, D, 3 * HD, &r, st)) return 1;   // dxn1 + LN1 backward
             if (m3l_reduce_rows_seg3(w.scratch, cdiv(M, 64), D, g[0], g[1], db_prev, 0, st)) return 1;
-        } else if (m3l_qkv_bwd_t192_supported(dt, D, 3 * HD, M)) {
+        } else if (!dp && m3l_qkv_bwd_t192_supported(dt, D, 3 * HD, M)) {
             // long sequences: dxn1 and the LN1 backward per 192-row tile, dxn1 never leaves the registers
             if (l && claim_set(nxt)) return 2;
             const int tiles = m3l_qkv_bwd_t192_tiles(D, M);
@@ -1700,6 +1797,11 @@ int m3l_op_patch_cols(int dtype, const float* x, int B, int C, int H, int W, int
 int m3l_op_vit_tokens(const float* emb, const float* cls, const float* regs, const float* pos, int B, int npatch, int R, int D, float* tok,
                       void* stream) {
     return m3l_vit_tokens(emb, cls, regs, pos, B, npatch, R, D, tok, (hipStream_t)stream);
+}
+int m3l_op_dropout_mask(float p, uint64_t seed, int layer, int site, long rows, int N, uint8_t* out, void* stream) {
+    M3L_CHECK(p >= 0.f && p <= 1.f && site >= 0 && site < 4 && layer >= 0, "op_dropout_mask: p=%g site=%d layer=%d", (double)p, site, layer);
+    const DropCtx d = m3l_drop_ctx(p, seed, layer, site);
+    return m3l_dropout_mask(&d, rows, N, out, (hipStream_t)stream);
 }
 int m3l_op_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, void* stream) {
     return m3l_attn_fwd(dtype, qkv, o, lse, B, n, H, (hipStream_t)stream);

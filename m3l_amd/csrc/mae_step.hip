@@ -18,6 +18,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
+#include <mutex>
 
 #include "../../include/m3l_amd.h"
 #include "common.cuh"
@@ -148,7 +150,7 @@ void front_layout(Arena& a, const m3l_mae_cfg* c, const StepDims& d, int B, int 
     }
 }
 
-StepWs step_layout(const m3l_mae_cfg* c, const StepDims& d, int B, void* ws) {
+StepWs step_layout(const m3l_mae_cfg* c, const StepDims& d, int B, void* ws, const m3l_dropout* enc_drop = nullptr) {
     Arena a(ws);
     StepWs w;
     memset(&w, 0, sizeof(w));
@@ -164,7 +166,7 @@ StepWs step_layout(const m3l_mae_cfg* c, const StepDims& d, int B, void* ws) {
     w.d_enc = a.take(Mv * d.D * 4);
     w.dtokens = (float*)a.take(Mv * d.D * 4);
     front_layout(a, c, d, B, d.nvis, c->learned_pos != 0, &w.f);
-    w.ws_enc = a.take(m3l_transformer_ws_bytes(&c->enc, B, d.nvis));
+    w.ws_enc = a.take(m3l_transformer_ws_bytes_dropout(&c->enc, B, d.nvis, enc_drop));
     w.ws_glue = a.take(m3l_unshuffle_ws_bytes(&c->geom, d.D, d.dd, d.dt, B, d.nvis, d.nmask));
     w.ws_dec = a.take(m3l_transformer_ws_bytes(&c->dec, B, d.N));
     const int nrows = c->early_conv ? d.N : d.nmask;       // early conv: loss over all patches
@@ -239,20 +241,68 @@ extern "C" {
 
 int m3l_mae_step_num_tensors(const m3l_mae_cfg* c) { return groups_of(c).total; }
 
-size_t m3l_mae_step_ws_bytes(const m3l_mae_cfg* c, int B) {
+}  // extern "C"
+namespace {
+// the dropout descriptors a step / extractor forward ran with, by workspace: the backward checks them BEFORE it starts — the workspace
+// layout depends on them (an encoder workspace sized for dropout), so a mismatch must not reach any kernel.  Dropped by the backward.
+struct StepDrop {
+    float p[2];
+    uint64_t seed[2];
+};
+std::mutex g_step_drop_mu;
+std::map<const void*, StepDrop> g_step_drop;
+StepDrop step_drop(const m3l_dropout* a, const m3l_dropout* b) {
+    StepDrop r;
+    const m3l_dropout* d[2] = {a, b};
+    for (int i = 0; i < 2; ++i) {
+        const bool on = d[i] && d[i]->p > 0.f;
+        r.p[i] = on ? d[i]->p : 0.f;
+        r.seed[i] = on ? d[i]->seed : 0;
+    }
+    return r;
+}
+void step_drop_record(const void* ws, const m3l_dropout* a, const m3l_dropout* b) {
+    std::lock_guard<std::mutex> lock(g_step_drop_mu);
+    if (g_step_drop.size() >= 4096 && g_step_drop.find(ws) == g_step_drop.end()) g_step_drop.clear();
+    g_step_drop[ws] = step_drop(a, b);
+}
+int step_drop_check(const char* what, const void* ws, const m3l_dropout* a, const m3l_dropout* b) {
+    std::lock_guard<std::mutex> lock(g_step_drop_mu);
+    auto it = g_step_drop.find(ws);
+    if (it == g_step_drop.end()) return 0;
+    const StepDrop r = it->second, now = step_drop(a, b);
+    g_step_drop.erase(it);
+    for (int i = 0; i < 2; ++i)
+        M3L_CHECK(r.p[i] == now.p[i] && r.seed[i] == now.seed[i], "%s: the forward on this workspace ran with dropout p=%g seed=%llu (%s), the "
+                  "backward got p=%g seed=%llu", what, (double)r.p[i], (unsigned long long)r.seed[i], i ? "head" : "encoder", (double)now.p[i],
+                  (unsigned long long)now.seed[i]);
+    return 0;
+}
+}  // namespace
+extern "C" {
+
+size_t m3l_mae_step_ws_bytes(const m3l_mae_cfg* c, int B) { return m3l_mae_step_ws_bytes_dropout(c, B, nullptr); }
+size_t m3l_mae_step_ws_bytes_dropout(const m3l_mae_cfg* c, int B, const m3l_dropout* enc_drop) {
     StepDims d;
     if (B <= 0 || step_dims(c, &d)) return 0;
-    return step_layout(c, d, B, nullptr).total;
+    return step_layout(c, d, B, nullptr, enc_drop).total;
 }
 
 int m3l_mae_step_fwd(const m3l_mae_cfg* c, int B, const float* image, const float* const* tactiles, const float* const* noise,
                      const void* const* tensors, void* ws, float* loss, int64_t* masked, int64_t* unmasked, void* stream) {
+    return m3l_mae_step_fwd_dropout(c, B, image, tactiles, noise, tensors, ws, loss, masked, unmasked, nullptr, stream);
+}
+// enc_drop: dropout of the encoder stack (the decoder never drops: the reference builds it with dropout = 0)
+int m3l_mae_step_fwd_dropout(const m3l_mae_cfg* c, int B, const float* image, const float* const* tactiles, const float* const* noise,
+                             const void* const* tensors, void* ws, float* loss, int64_t* masked, int64_t* unmasked, const m3l_dropout* enc_drop,
+                             void* stream) {
     StepDims d;
     M3L_CHECK(B > 0 && tensors && ws && loss && noise && masked && unmasked, "mae_step_fwd: null argument / B=%d", B);
     if (step_dims(c, &d)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const StepWs w = step_layout(c, d, B, ws);
+    const StepWs w = step_layout(c, d, B, ws, enc_drop);
     const Groups g = groups_of(c);
+    step_drop_record(ws, enc_drop, nullptr);
     // mask sampling (pretrain_models.py:223-248) -> the caller's index lists (the backward reads them again)
     if (m3l_mask_sample_counts(&c->geom, d.nm_img, d.nm_tac, B, noise, masked, unmasked, st)) return 1;
     // every module's compute-type weight copies in one launch per 64 matrices: a collect pass over the chain (each module records its
@@ -264,7 +314,7 @@ int m3l_mae_step_fwd(const m3l_mae_cfg* c, int B, const float* image, const floa
     // patch embed of the visible tokens (:157-216,255-256) / EarlyCNN stems over the frames, then the visible gather (:180-191)
     if (front_fwd(c, d, w.f, B, d.nvis, d.nvis_img, unmasked, image, tactiles, tensors + g.embed, w.tokens, st)) return 1;
     // encoder (:266)
-    if (m3l_transformer_fwd(&c->enc, B, d.nvis, w.tokens, tensors + g.enc, w.ws_enc, w.enc_t, w.enc32, st)) return 1;
+    if (m3l_transformer_fwd_dropout(&c->enc, B, d.nvis, w.tokens, tensors + g.enc, w.ws_enc, w.enc_t, w.enc32, enc_drop, st)) return 1;
     // enc_to_dec + un-shuffle + decoder positions (:270-307); f32 compute: the "compute-type" encoder output is the f32 one.  When the
     // decoder runs the bf16 residual stream, its input (and, in the backward, the gradient of it) is exchanged as bf16: no boundary casts
     const IoScope dec_io(m3l_transformer_rb(&c->dec, B, d.N) && !c->learned_pos);      // (the same rule as the backward's)
@@ -300,11 +350,17 @@ int m3l_mae_step_fwd(const m3l_mae_cfg* c, int B, const float* image, const floa
 int m3l_mae_step_bwd(const m3l_mae_cfg* c, int B, const float* image, const float* const* tactiles, const int64_t* masked,
                      const int64_t* unmasked, const void* const* tensors, void* ws, const float* dloss, float* const* grads,
                      const m3l_comm_plan* comm, void* stream) {
+    return m3l_mae_step_bwd_dropout(c, B, image, tactiles, masked, unmasked, tensors, ws, dloss, grads, comm, nullptr, stream);
+}
+int m3l_mae_step_bwd_dropout(const m3l_mae_cfg* c, int B, const float* image, const float* const* tactiles, const int64_t* masked,
+                             const int64_t* unmasked, const void* const* tensors, void* ws, const float* dloss, float* const* grads,
+                             const m3l_comm_plan* comm, const m3l_dropout* enc_drop, void* stream) {
     StepDims d;
     M3L_CHECK(B > 0 && tensors && ws && grads && masked && unmasked, "mae_step_bwd: null argument / B=%d", B);
     if (step_dims(c, &d)) return 1;
+    if (step_drop_check("mae_step_bwd", ws, enc_drop, nullptr)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const StepWs w = step_layout(c, d, B, ws);
+    const StepWs w = step_layout(c, d, B, ws, enc_drop);
     const Groups g = groups_of(c);
     const int chunk = (comm && comm->layers_per_chunk > 0) ? comm->layers_per_chunk : 0;
     long sent = 0;
@@ -323,14 +379,14 @@ int m3l_mae_step_bwd(const m3l_mae_cfg* c, int B, const float* image, const floa
         return 0;
     };
     auto tf_bwd = [&](const m3l_tf_cfg* cfg, int n, const float* x_in, const void* const* t, void* tws, const void* dy, int dy_code,
-                      float* dx, float* const* gr) -> int {
+                      float* dx, float* const* gr, const m3l_dropout* drop) -> int {
         if (!chunk || chunk >= cfg->depth) {
-            if (m3l_transformer_bwd(cfg, B, n, x_in, t, tws, dy, dy_code, dx, gr, stream)) return 1;
+            if (m3l_transformer_bwd_dropout(cfg, B, n, x_in, t, tws, dy, dy_code, dx, gr, drop, stream)) return 1;
             return stage_done();
         }
         for (int hi = cfg->depth; hi > 0;) {
             const int lo = std::max(0, hi - chunk);
-            if (m3l_transformer_bwd_range(cfg, B, n, x_in, t, tws, dy, dy_code, dx, gr, hi, lo, stream)) return 1;
+            if (m3l_transformer_bwd_range_dropout(cfg, B, n, x_in, t, tws, dy, dy_code, dx, gr, hi, lo, drop, stream)) return 1;
             if (stage_done()) return 1;
             hi = lo;
         }
@@ -346,7 +402,7 @@ int m3l_mae_step_bwd(const m3l_mae_cfg* c, int B, const float* image, const floa
     int enc_code = 0;
     {
         const IoScope io(dec_io);
-        if (tf_bwd(&c->dec, d.N, w.dec_in, tensors + g.dec, w.ws_dec, w.d_dec, d.dt, w.d_dec_in, grads + g.dec)) return 1;
+        if (tf_bwd(&c->dec, d.N, w.dec_in, tensors + g.dec, w.ws_dec, w.d_dec, d.dt, w.d_dec_in, grads + g.dec, nullptr)) return 1;
         if (m3l_unshuffle_bwd(&c->geom, d.D, d.dd, d.dt, B, d.nvis, d.nmask, unmasked, masked, d.dt ? w.enc_t : (void*)w.enc32,
                               tensors + g.glue, w.ws_glue, w.d_dec_in, w.d_enc, &enc_code, grads + g.glue, st))
             return 1;
@@ -358,7 +414,7 @@ int m3l_mae_step_bwd(const m3l_mae_cfg* c, int B, const float* image, const floa
         if (gg[5] && d.k && m3l_reduce_rows(w.d_dec_in + (size_t)d.n_img * d.dd, B, stride, d.k * d.n_tac * d.dd, gg[5], 0, st)) return 1;
     }
     if (stage_done()) return 1;
-    if (tf_bwd(&c->enc, d.nvis, w.tokens, tensors + g.enc, w.ws_enc, w.d_enc, enc_code, w.dtokens, grads + g.enc)) return 1;
+    if (tf_bwd(&c->enc, d.nvis, w.tokens, tensors + g.enc, w.ws_enc, w.d_enc, enc_code, w.dtokens, grads + g.enc, enc_drop)) return 1;
     if (front_bwd(c, d, w.f, B, d.nvis, d.nvis_img, unmasked, image, tactiles, tensors + g.embed, w.dtokens, grads + g.embed, st)) return 1;
     if (stage_done()) return 1;
     if (comm) {
@@ -388,7 +444,8 @@ int ext_dims(const m3l_mae_cfg* c, const m3l_tf_cfg* head, StepDims* d) {
               head->dim, head->dtype, c->enc.dim, c->enc.dtype);
     return 0;
 }
-ExtWs ext_layout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, const StepDims& d, int B, void* ws) {
+ExtWs ext_layout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, const StepDims& d, int B, void* ws, const m3l_dropout* enc_drop = nullptr,
+                 const m3l_dropout* head_drop = nullptr) {
     Arena a(ws);
     ExtWs w;
     memset(&w, 0, sizeof(w));
@@ -400,8 +457,8 @@ ExtWs ext_layout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, const StepDims& d
     w.d_enc = (float*)a.take(Ma * d.D * 4);
     w.dtokens = (float*)a.take(Ma * d.D * 4);
     front_layout(a, c, d, B, d.N, false, &w.f);
-    w.ws_enc = a.take(m3l_transformer_ws_bytes(&c->enc, B, d.N));
-    w.ws_head = a.take(m3l_transformer_ws_bytes(head, B, d.N));
+    w.ws_enc = a.take(m3l_transformer_ws_bytes_dropout(&c->enc, B, d.N, enc_drop));
+    w.ws_head = a.take(m3l_transformer_ws_bytes_dropout(head, B, d.N, head_drop));
     w.total = a.off + 256;
     return w;
 }
@@ -410,26 +467,33 @@ ExtWs ext_layout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, const StepDims& d
 int m3l_extractor_num_tensors(const m3l_mae_cfg* c, const m3l_tf_cfg* head) {
     return front_tensors(c) + 11 * c->enc.depth + 2 + 11 * head->depth + 2;
 }
-size_t m3l_extractor_ws_bytes(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B) {
+size_t m3l_extractor_ws_bytes(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B) { return m3l_extractor_ws_bytes_dropout(c, head, B, nullptr, nullptr); }
+size_t m3l_extractor_ws_bytes_dropout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const m3l_dropout* enc_drop, const m3l_dropout* head_drop) {
     StepDims d;
     if (B <= 0 || ext_dims(c, head, &d)) return 0;
-    return ext_layout(c, head, d, B, nullptr).total;
+    return ext_layout(c, head, d, B, nullptr, enc_drop, head_drop).total;
 }
 int m3l_extractor_fwd(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const float* image, const float* const* tactiles,
                       const void* const* tensors, void* ws, float* out, void* stream) {
+    return m3l_extractor_fwd_dropout(c, head, B, image, tactiles, tensors, ws, out, nullptr, nullptr, stream);
+}
+int m3l_extractor_fwd_dropout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const float* image, const float* const* tactiles,
+                              const void* const* tensors, void* ws, float* out, const m3l_dropout* enc_drop, const m3l_dropout* head_drop,
+                              void* stream) {
     StepDims d;
     M3L_CHECK(B > 0 && tensors && ws && out, "extractor_fwd: null argument / B=%d", B);
     if (ext_dims(c, head, &d)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const ExtWs w = ext_layout(c, head, d, B, ws);
+    const ExtWs w = ext_layout(c, head, d, B, ws, enc_drop, head_drop);
     const int g_enc = front_tensors(c), g_head = g_enc + 11 * c->enc.depth + 2;
+    step_drop_record(ws, enc_drop, head_drop);
     struct PrepReset { ~PrepReset() { m3l_prep_set_mode(0); } } prep_reset;
     for (int pass = prep_first_pass(); pass <= 2; ++pass) {        // collect the chain's weight copies, flush them as one launch, run the chain
         m3l_prep_set_mode(prep_mode_of(pass));
         if (pass == 2 && m3l_prep_flush(st)) return 1;
         if (front_fwd(c, d, w.f, B, d.N, d.n_img, nullptr, image, tactiles, tensors, w.tokens, st)) return 1;
-        if (m3l_transformer_fwd(&c->enc, B, d.N, w.tokens, tensors + g_enc, w.ws_enc, nullptr, w.enc32, st)) return 1;
-        if (m3l_transformer_fwd(head, B, d.N, w.enc32, tensors + g_head, w.ws_head, nullptr, w.head32, st)) return 1;
+        if (m3l_transformer_fwd_dropout(&c->enc, B, d.N, w.tokens, tensors + g_enc, w.ws_enc, nullptr, w.enc32, enc_drop, st)) return 1;
+        if (m3l_transformer_fwd_dropout(head, B, d.N, w.enc32, tensors + g_head, w.ws_head, nullptr, w.head32, head_drop, st)) return 1;
     }
     m3l_prep_set_mode(0);
     mean_tokens_kernel<<<B, 256, 0, st>>>(w.head32, d.N, d.D, out);
@@ -439,16 +503,22 @@ int m3l_extractor_fwd(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const
 // dout (B, D) f32 -> parameter gradients (same order as tensors; NULL = not wanted)
 int m3l_extractor_bwd(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const float* image, const float* const* tactiles,
                       const void* const* tensors, void* ws, const float* dout, float* const* grads, void* stream) {
+    return m3l_extractor_bwd_dropout(c, head, B, image, tactiles, tensors, ws, dout, grads, nullptr, nullptr, stream);
+}
+int m3l_extractor_bwd_dropout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int B, const float* image, const float* const* tactiles,
+                              const void* const* tensors, void* ws, const float* dout, float* const* grads, const m3l_dropout* enc_drop,
+                              const m3l_dropout* head_drop, void* stream) {
     StepDims d;
     M3L_CHECK(B > 0 && tensors && ws && dout && grads, "extractor_bwd: null argument / B=%d", B);
     if (ext_dims(c, head, &d)) return 1;
+    if (step_drop_check("extractor_bwd", ws, enc_drop, head_drop)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const ExtWs w = ext_layout(c, head, d, B, ws);
+    const ExtWs w = ext_layout(c, head, d, B, ws, enc_drop, head_drop);
     const int g_enc = front_tensors(c), g_head = g_enc + 11 * c->enc.depth + 2;
     mean_tokens_bwd_kernel<<<dim3(cdiv((long)d.N * d.D, 256), B), 256, 0, st>>>(dout, d.N, d.D, w.d_head);
     M3L_LAUNCH_CHECK();
-    if (m3l_transformer_bwd(head, B, d.N, w.enc32, tensors + g_head, w.ws_head, w.d_head, 0, w.d_enc, grads + g_head, stream)) return 1;
-    if (m3l_transformer_bwd(&c->enc, B, d.N, w.tokens, tensors + g_enc, w.ws_enc, w.d_enc, 0, w.dtokens, grads + g_enc, stream)) return 1;
+    if (m3l_transformer_bwd_dropout(head, B, d.N, w.enc32, tensors + g_head, w.ws_head, w.d_head, 0, w.d_enc, grads + g_head, head_drop, stream)) return 1;
+    if (m3l_transformer_bwd_dropout(&c->enc, B, d.N, w.tokens, tensors + g_enc, w.ws_enc, w.d_enc, 0, w.dtokens, grads + g_enc, enc_drop, stream)) return 1;
     return front_bwd(c, d, w.f, B, d.N, d.n_img, nullptr, image, tactiles, tensors, w.dtokens, grads, st);
 }
 

@@ -230,23 +230,28 @@ class EmbedFn(torch.autograd.Function):
         return (None,) * 9 + tuple(out)
 
 
+def _byref(s):
+    return C.byref(s) if s is not None else None
+
+
 class TransformerFn(torch.autograd.Function):
     """x (B, n, D) f32 -> (y_t compute-type, y32 f32) = final LayerNorm output, twice (the heads consume the
-    compute-type copy, torch-side consumers the f32 one)."""
+    compute-type copy, torch-side consumers the f32 one).  drop: L.Dropout of this call or None; the backward regenerates its masks."""
 
     @staticmethod
-    def forward(ctx, sink, cfg, x, *tensors):
+    def forward(ctx, sink, cfg, drop, x, *tensors):
         _require_cuda(x, "transformer input")
         B, n, D = x.shape
         assert D == cfg.dim, (D, cfg.dim)
         x = _f32c(x)
         tens = [_f32c(t) for t in tensors]
-        ws = _ws(L.lib().m3l_transformer_ws_bytes(C.byref(cfg), B, n), x.device)
+        ws = _ws(L.lib().m3l_transformer_ws_bytes_dropout(C.byref(cfg), B, n, _byref(drop)), x.device)
         y32 = torch.empty(B, n, D, dtype=torch.float32, device=x.device)
         y_t = torch.empty(B, n, D, dtype=torch.bfloat16, device=x.device) if cfg.dtype == DT_BF16 else None
-        L.check(L.lib().m3l_transformer_fwd(C.byref(cfg), B, n, L.ptr(x), L.ptr_array(tens), L.ptr(ws),
-                                            L.ptr(y_t), L.ptr(y32), _stream()), "m3l_transformer_fwd")
+        L.check(L.lib().m3l_transformer_fwd_dropout(C.byref(cfg), B, n, L.ptr(x), L.ptr_array(tens), L.ptr(ws),
+                                                    L.ptr(y_t), L.ptr(y32), _byref(drop), _stream()), "m3l_transformer_fwd")
         ctx.saved = (cfg, x, tens, ws)
+        ctx.drop = drop
         ctx.params, ctx.sink = tensors, sink
         ctx.versions = _versions(tensors)
         ctx.set_materialize_grads(False)     # an unused output must arrive as None in backward, not as a zero tensor to add and convert
@@ -260,7 +265,8 @@ class TransformerFn(torch.autograd.Function):
         cfg, x, tens, ws = ctx.saved
         B, n, D = x.shape
         if dy_t is None and dy32 is None:         # nothing downstream used this stack
-            return (None, None, None) + (None,) * len(ctx.params)
+            return (None, None, None, None) + (None,) * len(ctx.params)
+        drop = _byref(ctx.drop)
         if dy_t is not None and dy32 is not None:
             dy, code = (dy32 + dy_t.float()).contiguous(), DT_F32
         elif dy_t is not None:
@@ -282,16 +288,16 @@ class TransformerFn(torch.autograd.Function):
             if chunk is None and sink is not None and sink[1] is not None and sink[0]._comm:
                 chunk = sink[0].layers_per_chunk
             if not chunk or chunk >= cfg.depth:
-                L.check(L.lib().m3l_transformer_bwd(C.byref(cfg), B, n, L.ptr(x), L.ptr_array(tens), L.ptr(ws), L.ptr(dy), code,
-                                                    L.ptr(dx), L.ptr_array(grads), _stream()), "m3l_transformer_bwd")
+                L.check(L.lib().m3l_transformer_bwd_dropout(C.byref(cfg), B, n, L.ptr(x), L.ptr_array(tens), L.ptr(ws), L.ptr(dy), code,
+                                                            L.ptr(dx), L.ptr_array(grads), drop, _stream()), "m3l_transformer_bwd")
                 _done(sink)
             else:
                 tens_a, grads_a = L.ptr_array(tens), L.ptr_array(grads)
                 hi = cfg.depth
                 while hi > 0:
                     lo = max(0, hi - chunk)
-                    L.check(L.lib().m3l_transformer_bwd_range(C.byref(cfg), B, n, L.ptr(x), tens_a, L.ptr(ws), L.ptr(dy), code, L.ptr(dx),
-                                                              grads_a, hi, lo, _stream()), "m3l_transformer_bwd_range")
+                    L.check(L.lib().m3l_transformer_bwd_range_dropout(C.byref(cfg), B, n, L.ptr(x), tens_a, L.ptr(ws), L.ptr(dy), code,
+                                                                      L.ptr(dx), grads_a, hi, lo, drop, _stream()), "m3l_transformer_bwd_range")
                     if sink is not None and sink[1] is not None:
                         done = list(ctx.params[11 * lo:11 * hi]) + (list(ctx.params[11 * cfg.depth:]) if hi == cfg.depth else [])
                         sink[0].range_done(sink[1], done, last=(lo == 0))
@@ -299,7 +305,7 @@ class TransformerFn(torch.autograd.Function):
         finally:
             if defer:
                 L.lib().m3l_set_defer_join(0)
-        return (None, None, dx) + _returned(sink, grads)
+        return (None, None, None, dx) + _returned(sink, grads)
 
 
 class UnshuffleFn(torch.autograd.Function):
@@ -418,7 +424,10 @@ class StepPlan:
     """Everything one fused step needs, assembled by VTMAE._step_fused: cfg (L.MaeCfg), the five tensor groups as one list, which of
     them take a gradient in this call, the inputs and the GradSync (or None)."""
     __slots__ = ("cfg", "tensors", "used", "image", "tactiles", "noises", "sync", "B", "nmask", "nvis", "ws", "keep", "versions", "tens_arr",
-                 "tac_arr", "masked", "unmasked", "extra", "head_cfg", "in_versions")
+                 "tac_arr", "masked", "unmasked", "extra", "head_cfg", "in_versions", "drop", "head_drop")
+
+    def __init__(self):
+        self.drop = self.head_drop = None     # L.Dropout of the encoder / the extractor's head, or None
 
 
 def _comm_plan(sync, plan, cfg):
@@ -473,14 +482,15 @@ class MaeStepFn(torch.autograd.Function):
         dev = plan.image.device if plan.image is not None else plan.tactiles[0].device
         cfg = plan.cfg
         plan.keep = []
-        plan.ws = _ws(lib.m3l_mae_step_ws_bytes(C.byref(cfg), plan.B), dev)
+        plan.ws = _ws(lib.m3l_mae_step_ws_bytes_dropout(C.byref(cfg), plan.B, _byref(plan.drop)), dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         plan.masked = torch.empty(plan.B, plan.nmask, dtype=torch.int64, device=dev)
         plan.unmasked = torch.empty(plan.B, plan.nvis, dtype=torch.int64, device=dev)
         plan.tens_arr = _dev_ptrs(plan.tensors, plan.keep)
         plan.tac_arr = L.ptr_array(plan.tactiles)
-        L.check(lib.m3l_mae_step_fwd(C.byref(cfg), plan.B, L.ptr(plan.image), plan.tac_arr, L.ptr_array(plan.noises), plan.tens_arr,
-                                     L.ptr(plan.ws), L.ptr(loss), L.ptr(plan.masked), L.ptr(plan.unmasked), _stream()), "m3l_mae_step_fwd")
+        L.check(lib.m3l_mae_step_fwd_dropout(C.byref(cfg), plan.B, L.ptr(plan.image), plan.tac_arr, L.ptr_array(plan.noises), plan.tens_arr,
+                                             L.ptr(plan.ws), L.ptr(loss), L.ptr(plan.masked), L.ptr(plan.unmasked), _byref(plan.drop), _stream()),
+                "m3l_mae_step_fwd")
         plan.versions = _versions(plan.tensors)
         plan.in_versions = _versions([plan.image] + list(plan.tactiles))
         plan.noises = None
@@ -510,9 +520,9 @@ class MaeStepFn(torch.autograd.Function):
             sync._keep.append((plan.ws, plan.keep, grads, dloss, plan.image, plan.tactiles))
             lib.m3l_set_defer_join(1)
         try:
-            L.check(lib.m3l_mae_step_bwd(C.byref(plan.cfg), plan.B, L.ptr(plan.image), plan.tac_arr, L.ptr(plan.masked), L.ptr(plan.unmasked), plan.tens_arr,
-                                         L.ptr(plan.ws), L.ptr(dloss),
-                                         L.ptr_array(grads), C.byref(comm[0]) if comm is not None else None, _stream()), "m3l_mae_step_bwd")
+            L.check(lib.m3l_mae_step_bwd_dropout(C.byref(plan.cfg), plan.B, L.ptr(plan.image), plan.tac_arr, L.ptr(plan.masked), L.ptr(plan.unmasked),
+                                                 plan.tens_arr, L.ptr(plan.ws), L.ptr(dloss), L.ptr_array(grads),
+                                                 C.byref(comm[0]) if comm is not None else None, _byref(plan.drop), _stream()), "m3l_mae_step_bwd")
         finally:
             if defer:
                 lib.m3l_set_defer_join(0)
@@ -557,12 +567,13 @@ class ExtractorFn(torch.autograd.Function):
         lib = L.lib()
         dev = plan.image.device if plan.image is not None else plan.tactiles[0].device
         plan.keep = []
-        plan.ws = _ws(lib.m3l_extractor_ws_bytes(C.byref(plan.cfg), C.byref(plan.head_cfg), plan.B), dev)
+        plan.ws = _ws(lib.m3l_extractor_ws_bytes_dropout(C.byref(plan.cfg), C.byref(plan.head_cfg), plan.B, _byref(plan.drop),
+                                                         _byref(plan.head_drop)), dev)
         out = torch.empty(plan.B, plan.cfg.enc.dim, dtype=torch.float32, device=dev)
         plan.tens_arr = _dev_ptrs(plan.tensors, plan.keep)
         plan.tac_arr = L.ptr_array(plan.tactiles)
-        L.check(lib.m3l_extractor_fwd(C.byref(plan.cfg), C.byref(plan.head_cfg), plan.B, L.ptr(plan.image), plan.tac_arr, plan.tens_arr, L.ptr(plan.ws),
-                                      L.ptr(out), _stream()), "m3l_extractor_fwd")
+        L.check(lib.m3l_extractor_fwd_dropout(C.byref(plan.cfg), C.byref(plan.head_cfg), plan.B, L.ptr(plan.image), plan.tac_arr, plan.tens_arr,
+                                              L.ptr(plan.ws), L.ptr(out), _byref(plan.drop), _byref(plan.head_drop), _stream()), "m3l_extractor_fwd")
         plan.versions = _versions(plan.tensors)
         plan.in_versions = _versions([plan.image] + list(plan.tactiles))
         ctx.plan = plan
@@ -578,8 +589,9 @@ class ExtractorFn(torch.autograd.Function):
         _check_inputs("ExtractorFn", [plan.image] + list(plan.tactiles), plan.in_versions)
         grads = [torch.zeros_like(t) if (t is not None and u) else None for t, u in zip(plan.tensors, plan.used)]
         dout = _f32c(dout)
-        L.check(L.lib().m3l_extractor_bwd(C.byref(plan.cfg), C.byref(plan.head_cfg), plan.B, L.ptr(plan.image), plan.tac_arr, plan.tens_arr, L.ptr(plan.ws),
-                                          L.ptr(dout), L.ptr_array(grads), _stream()), "m3l_extractor_bwd")
+        L.check(L.lib().m3l_extractor_bwd_dropout(C.byref(plan.cfg), C.byref(plan.head_cfg), plan.B, L.ptr(plan.image), plan.tac_arr, plan.tens_arr,
+                                                  L.ptr(plan.ws), L.ptr(dout), L.ptr_array(grads), _byref(plan.drop), _byref(plan.head_drop), _stream()),
+                "m3l_extractor_bwd")
         return (None,) + tuple(g for g, t in zip(grads, plan.tensors) if t is not None)
 
 

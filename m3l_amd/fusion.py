@@ -43,6 +43,7 @@ def pooled_embeddings(mae, head, vt, use_tactile=True):
     learned = not mae.use_sincosmod_encodings
     plan.cfg = L.MaeCfg(geom, enc_tf._cfg(), enc_tf._cfg(), 0.5, int(mae.early_conv_masking), int(learned))
     plan.head_cfg = head._cfg()
+    plan.drop, plan.head_drop = enc_tf._drop(), head._drop()
     has_img, has_tac = image is not None, len(tactiles) > 0
     front, used = mae._front_tensors(geom, has_img, has_tac)
     plan.tensors = front + enc_tf._tensors() + head._tensors()

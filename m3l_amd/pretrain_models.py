@@ -11,6 +11,8 @@ Extensions over the reference signature (all optional, defaults keep reference b
     (one (B, n) tensor per modality in RNG order image, tactile1..k).  Needed for bit-exact mask parity.
   * `compute_dtype='fp32' | 'bf16'` (constructor kwarg / `set_compute_dtype`): bf16 = bf16 MFMA operands, fp32
     accumulation, fp32 master weights, fp32 residual stream.
+  * `Transformer(dropout=p)`: the masks come from a counter-based generator inside the kernels (include/m3l_amd.h "Dropout"), seeded by
+    one draw from torch's default CPU generator per training-mode forward (`transformer.last_dropout_seed`).
 """
 import math
 
@@ -69,9 +71,11 @@ class Transformer(nn.Module):
 
     def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout=0.):
         super().__init__()
-        if dropout != 0.:
-            raise NotImplementedError("dropout > 0 is not implemented in the HIP path (the reference trains with dropout = 0)")
+        if not 0. <= dropout <= 1.:
+            raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
         self.dim, self.depth, self.heads, self.mlp_dim = dim, depth, heads, mlp_dim
+        self.dropout_p = float(dropout)
+        self.last_dropout_seed = None   # seed of the last forward that dropped (the masks are a function of it: include/m3l_amd.h "Dropout")
         self.project_out = not (heads == 1 and dim_head == dim)
         self.compute_dtype = "fp32"
         self._sink = None            # (GradSync, bucket) when gradients go straight into a flat buffer (m3l_amd.parallel)
@@ -115,9 +119,17 @@ class Transformer(nn.Module):
     def _cfg(self):
         return L.TfCfg(self.dim, self.depth, self.heads, self.mlp_dim, int(self.project_out), Fn.dtype_code(self.compute_dtype))
 
+    def _drop(self):
+        """The dropout descriptor of one forward: active iff training and p > 0 (nn.Dropout's rule), with a fresh 63-bit seed drawn from
+        torch's default CPU generator (no device sync; torch.manual_seed reproduces the masks) — or None."""
+        if not (self.training and self.dropout_p > 0.):
+            return None
+        self.last_dropout_seed = int(torch.randint(0, 2 ** 63 - 1, (), dtype=torch.int64).item())
+        return L.Dropout(self.dropout_p, self.last_dropout_seed)
+
     def run(self, x):
         """-> (y in compute dtype, y in f32); both carry gradient."""
-        return Fn.TransformerFn.apply(self._sink, self._cfg(), x, *self._tensors())
+        return Fn.TransformerFn.apply(self._sink, self._cfg(), self._drop(), x, *self._tensors())
 
     def forward(self, x):
         return self.run(x)[1]
@@ -338,6 +350,7 @@ class VTMAE(nn.Module):
         """The whole step inside the library (csrc/mae_step.hip: m3l_mae_step_fwd / _bwd): one autograd node, two host calls."""
         plan = Fn.StepPlan()
         enc_tf, dec_tf = self.encoder.transformer, self.decoder
+        plan.drop = enc_tf._drop()          # the decoder never drops (built with dropout = 0, as in the reference)
         learned = not self.use_sincosmod_encodings
         plan.cfg = L.MaeCfg(geom, enc_tf._cfg(), dec_tf._cfg(), float(self.masking_ratio), int(self.early_conv_masking), int(learned))
         has_img, has_tac = image is not None, len(tactiles) > 0
