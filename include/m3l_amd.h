@@ -8,7 +8,7 @@
  *   - returns 0 on success, non-zero on error (text via m3l_last_error; nothing is thrown across the ABI),
  *   - takes device pointers unless a parameter says "host".
  * dtype codes: 0 = f32 compute (parity path), 1 = bf16 compute (fp32 master weights, fp32 accumulation; the residual stream
- * of a stack is bf16 or fp32, m3l_set_residual_bf16).  dim_head is 64 everywhere (all reference configs).  Transformer dropout
+ * of a stack is bf16 or fp32, m3l_set_residual_bf16).  dim_head (m3l_tf_cfg) is 32, 64 or 128; see m3l_tf_cfg.  Transformer dropout
  * (vit_pytorch's four nn.Dropout sites) is the *_dropout forms with an m3l_dropout descriptor; see "Dropout" below.
  *
  * Reference interface each entry replaces:
@@ -47,14 +47,21 @@ typedef struct m3l_geom {
     int use_tactile;         /* 0 -> tactile tokens absent from this call */
 } m3l_geom;
 
+/* dim_head: width of one attention head, 32, 64 or 128; 0 means 64 (so an initializer that stops at dtype keeps its meaning), any
+ * other value is refused with an error.  The inner width heads * dim_head may differ from dim (to_qkv [3 heads dim_head, dim],
+ * to_out [dim, heads dim_head]).  A stack with dim_head = 64 takes the fused block / row-tile / one-launch kernels where its shape
+ * allows; any other width runs every layer on the per-op kernel chain (LN, QKV GEMM, attention, out-proj GEMM, LN, fc1, fc2), as a
+ * stack with dropout does.  The bf16 residual stream (m3l_set_residual_bf16) also needs heads * dim_head % 64 == 0 (the out-proj's
+ * K in whole K tiles); other stacks keep fp32 residuals. */
 typedef struct m3l_tf_cfg {
     int dim, depth, heads, mlp_dim;
     int project_out;         /* vit_pytorch: to_out is Identity when heads == 1 and dim_head == dim */
     int dtype;
+    int dim_head;            /* 0 = 64 */
 } m3l_tf_cfg;
 
 /* ---- Dropout.  A descriptor of p > 0 (NULL = none) applies vit_pytorch's nn.Dropout(p) at four sites s of every layer l:
- *   s = 0  attention probabilities softmax(QK^T / 8) before P V, (B, H, n, n)     row = (b H + h) n + query, column = key
+ *   s = 0  attention probabilities softmax(QK^T / sqrt(dim_head)) before P V, (B, H, n, n)     row = (b H + h) n + query, column = key
  *   s = 1  out-proj output before the residual add, (B n, D)  (absent when to_out is Identity)
  *   s = 2  hidden activation GELU(fc1) before fc2, (B n, mlp)
  *   s = 3  fc2 output before the residual add, (B n, D)
@@ -396,6 +403,11 @@ int m3l_op_vit_tokens(const float* emb, const float* cls, const float* regs, con
 int m3l_op_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, void* stream);
 int m3l_op_attn_bwd(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
                     int n, int H, void* stream);
+/* the same for heads of width dim_head in {32, 64, 128}: qkv [B n, 3 H dim_head], o / dO [B n, H dim_head]; the two forms above are
+ * these at dim_head = 64 */
+int m3l_op_attn_fwd_dh(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, void* stream, int dim_head);
+int m3l_op_attn_bwd_dh(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
+                       int n, int H, void* stream, int dim_head);
 /* the dropout mask of site `site` of layer `layer` ("Dropout" above) for a (rows, N) tensor: out[row * N + c] = 1 kept / 0 dropped */
 int m3l_op_dropout_mask(float p, uint64_t seed, int layer, int site, long rows, int N, uint8_t* out, void* stream);
 

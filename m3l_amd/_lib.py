@@ -25,7 +25,8 @@ class CnnCfg(C.Structure):
 
 
 class TfCfg(C.Structure):
-    _fields_ = [(n, c_i) for n in ("dim", "depth", "heads", "mlp_dim", "project_out", "dtype")]
+    """m3l_tf_cfg.  dim_head is the trailing field (0 = 64), so construction with the first six values keeps its meaning."""
+    _fields_ = [(n, c_i) for n in ("dim", "depth", "heads", "mlp_dim", "project_out", "dtype", "dim_head")]
 
 
 class MaeCfg(C.Structure):
@@ -145,6 +146,8 @@ _SIGS = {
     "m3l_op_vit_tokens": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     "m3l_op_attn_fwd": (c_i, [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "m3l_op_attn_bwd": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "m3l_op_attn_fwd_dh": (c_i, [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i]),
+    "m3l_op_attn_bwd_dh": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i]),
     "m3l_op_dropout_mask": (c_i, [C.c_float, C.c_uint64, c_i, c_i, C.c_long, c_i, c_p, c_p]),
 }
 

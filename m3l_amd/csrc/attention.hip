@@ -1,4 +1,4 @@
-// Multi-head attention of the ViT encoder/decoder (vit_pytorch Attention.forward: softmax(Q K^T d_h^-0.5) V, d_h = 64)
+// Multi-head attention of the ViT encoder/decoder (vit_pytorch Attention.forward: softmax(Q K^T d_h^-0.5) V, d_h = DH in {32, 64, 128})
 // for gfx950.  QK^T, PV and the five backward products all run on MFMA 16x16 tiles; K/V (fwd, dQ pass) or Q/dO
 // (dK/dV pass) are staged in LDS, the softmax is computed inside one wavefront.
 //
@@ -8,26 +8,35 @@
 // V^T / K^T operands come from the row-major LDS tile through the hardware transpose read (load_ks).
 // The dK/dV pass computes S = Q K^T with the KEY on the lane for the same reason: dV^T = dO^T P, dK^T = Q^T dS.
 //
-// Layout: qkv [B*n, 3*H*64] as written by the to_qkv GEMM (q | k | v, head-major inside each), o / dO [B*n, H*64].
+// Layout: qkv [B*n, 3*H*DH] as written by the to_qkv GEMM (q | k | v, head-major inside each), o / dO [B*n, H*DH].
+// The head width DH is a template parameter: DH / 32 k-steps of the QK^T / dO V^T products, DH / 16 accumulator tiles of the
+// O / dQ / dK / dV products.  DH = 64 is the loop order and scale constant the library always had.
 #include "common.cuh"
 #include "kernels.h"
 
 namespace {
 
-template <typename T> struct AtCfg;
-template <> struct AtCfg<bf16> { static constexpr int ROW = 80; };   // 160-byte rows: conflict-free tr reads (rows 0..7 -> 8 slots)
-template <> struct AtCfg<float> { static constexpr int ROW = 68; };  // 272-byte rows
+// LDS row pitch of a staged [32 x DH] tile: DH plus 32 bytes of padding (bf16: 48 / 80 / 144 elements = 96 / 160 / 288 bytes).
+// With the bank rule of the HIP guide (section 2: banks (a/4) % 64 for ds_read_b128 and ds_read_b64_tr_b16, four 16-lane groups for
+// b128, 32-lane halves for tr_b16) both the row reads (16 rows x 16 bytes at 8 g) and the transposed reads (rows 4 g + q, 8 bytes at
+// column 4 p) are conflict-free at these three pitches; a pitch of DH (no padding) is 2-, 4- and 8-way, DH + 8 or DH + 24 2-way.
+// Every pitch is a multiple of 16 bytes, so each tr_b16 lane address (row pitch + 8 bytes x p) stays 8-byte aligned: a misaligned
+// tr_b16 address returns wrong operands without a fault.  f32 keeps DH + 4 floats (272 bytes at DH = 64).
+template <typename T, int DH> struct AtCfg;
+template <int DH> struct AtCfg<bf16, DH> { static constexpr int ROW = DH + 16; };
+template <int DH> struct AtCfg<float, DH> { static constexpr int ROW = DH + 4; };
+static_assert(AtCfg<bf16, 64>::ROW == 80 && AtCfg<float, 64>::ROW == 68, "DH = 64 keeps its pitch");
 
-// stage a [32 x 64] tile (rows r0..r0+31 of a [n x ld] matrix, zero-filled past n) into LDS
-template <typename T>
+// stage a [32 x DH] tile (rows r0..r0+31 of a [n x ld] matrix, zero-filled past n) into LDS
+template <typename T, int DH>
 __device__ __forceinline__ void stage_tile(T* dst, const T* src, long ld, int r0, int n, int tid) {
-    constexpr int EPC = Chunk<T>::N, CPR = 64 / EPC, TOT = 32 * CPR;
+    constexpr int EPC = Chunk<T>::N, CPR = DH / EPC, TOT = 32 * CPR;
 #pragma unroll
     for (int c = tid; c < TOT; c += 256) {
         const int row = c / CPR, cc = c % CPR;
         uint4 v = {0u, 0u, 0u, 0u};
         if (r0 + row < n) v = *reinterpret_cast<const uint4*>(src + (long)(r0 + row) * ld + cc * EPC);
-        *reinterpret_cast<uint4*>(dst + row * AtCfg<T>::ROW + cc * EPC) = v;
+        *reinterpret_cast<uint4*>(dst + row * AtCfg<T, DH>::ROW + cc * EPC) = v;
     }
 }
 
@@ -47,40 +56,40 @@ __device__ __forceinline__ uint32_t word_of(uint4 v, int w) { return w == 0 ? v.
 __device__ __forceinline__ float keep_f(uint32_t word, const DropCtx& dr) { return word >= dr.thr ? dr.scale : 0.f; }
 
 // DROP: site-0 dropout (include/m3l_amd.h "Dropout") — element (row = (b H + h) n + query, key) of the probabilities
-template <typename T, bool DROP>
+template <typename T, int DH, bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ o, float* __restrict__ lse,
                                                          int n, int H, float scale, DropCtx dr) {
-    constexpr int ROW = AtCfg<T>::ROW;
+    constexpr int ROW = AtCfg<T, DH>::ROW, KS = DH / 32, ND = DH / 16;
     __shared__ __attribute__((aligned(16))) T Ks[32 * ROW];
     __shared__ __attribute__((aligned(16))) T Vs[32 * ROW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
     const int b = blockIdx.y / H, hh = blockIdx.y % H;
-    const long ld = 3L * H * 64, ldo = (long)H * 64;
-    const T* Q = qkv + (long)b * n * ld + hh * 64;
-    const T* K = Q + H * 64;
-    const T* V = K + H * 64;
+    const long ld = 3L * H * DH, ldo = (long)H * DH;
+    const T* Q = qkv + (long)b * n * ld + hh * DH;
+    const T* K = Q + H * DH;
+    const T* V = K + H * DH;
     const int q = blockIdx.x * 64 + wave * 16 + li;
     const int qc = min(q, n - 1);
-    Frag<T> fq[2];
-    fq[0] = load_kc(Q + (long)qc * ld + 8 * g);
-    fq[1] = load_kc(Q + (long)qc * ld + 32 + 8 * g);
-
-    f32x4 oacc[4];
+    Frag<T> fq[KS];
 #pragma unroll
-    for (int d = 0; d < 4; ++d) oacc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < KS; ++ks) fq[ks] = load_kc(Q + (long)qc * ld + ks * 32 + 8 * g);
+
+    f32x4 oacc[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) oacc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, lsum = 0.f;
 
     const int ntile = (n + 31) / 32;
     for (int kt = 0; kt < ntile; ++kt) {
-        stage_tile<T>(Ks, K, ld, kt * 32, n, tid);
-        stage_tile<T>(Vs, V, ld, kt * 32, n, tid);
+        stage_tile<T, DH>(Ks, K, ld, kt * 32, n, tid);
+        stage_tile<T, DH>(Vs, V, ld, kt * 32, n, tid);
         __syncthreads();
         f32x4 s[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
+            for (int ks = 0; ks < KS; ++ks) {
                 const Frag<T> fk = load_kc(Ks + (16 * t + li) * ROW + ks * 32 + 8 * g);
                 s[t] = mma16(fk, fq[ks], s[t]);
             }
@@ -119,10 +128,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv
             }
         }
 #pragma unroll
-        for (int d = 0; d < 4; ++d) oacc[d] *= alpha;
+        for (int d = 0; d < ND; ++d) oacc[d] *= alpha;
         const Frag<T> fp = acc_to_frag<T>(s[0], s[1]);
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
+        for (int d = 0; d < ND; ++d) {
             const Frag<T> fv = load_ks<KMAP_ACC>(Vs, ROW, 0, 16 * d, lane);
             oacc[d] = mma16(fv, fp, oacc[d]);
         }
@@ -132,37 +141,37 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv
     lsum = xor32_sum(lsum);
     if (q < n) {
         const float inv = 1.0f / lsum;
-        T* orow = o + ((long)b * n + q) * ldo + hh * 64;
+        T* orow = o + ((long)b * n + q) * ldo + hh * DH;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) store4(orow + 16 * d + 4 * g, oacc[d] * inv);
+        for (int d = 0; d < ND; ++d) store4(orow + 16 * d + 4 * g, oacc[d] * inv);
         if (g == 0) lse[((long)b * H + hh) * n + q] = m + __logf(lsum);
     }
 }
 
 // dQ pass (also produces Dsum[b,h,q] = sum_d dO*O for the dK/dV pass)
 // DROP: dS = P (mask scale dP - D), D = rowsum(dO o O) unchanged (it equals rowsum of the dropped P times dP)
-template <typename T, bool DROP>
+template <typename T, int DH, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ o,
                                                             const T* __restrict__ dO, const float* __restrict__ lse,
                                                             float* __restrict__ dsum, T* __restrict__ dqkv, int n, int H,
                                                             float scale, DropCtx dr) {
-    constexpr int ROW = AtCfg<T>::ROW;
+    constexpr int ROW = AtCfg<T, DH>::ROW, KS = DH / 32, ND = DH / 16;
     __shared__ __attribute__((aligned(16))) T Ks[32 * ROW];
     __shared__ __attribute__((aligned(16))) T Vs[32 * ROW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
     const int b = blockIdx.y / H, hh = blockIdx.y % H;
-    const long ld = 3L * H * 64, ldo = (long)H * 64;
-    const T* Q = qkv + (long)b * n * ld + hh * 64;
-    const T* K = Q + H * 64;
-    const T* V = K + H * 64;
+    const long ld = 3L * H * DH, ldo = (long)H * DH;
+    const T* Q = qkv + (long)b * n * ld + hh * DH;
+    const T* K = Q + H * DH;
+    const T* V = K + H * DH;
     const int q = blockIdx.x * 64 + wave * 16 + li;
     const int qc = min(q, n - 1);
-    const T* dOr = dO + ((long)b * n + qc) * ldo + hh * 64;
-    const T* Or = o + ((long)b * n + qc) * ldo + hh * 64;
-    Frag<T> fq[2], fdo[2];
+    const T* dOr = dO + ((long)b * n + qc) * ldo + hh * DH;
+    const T* Or = o + ((long)b * n + qc) * ldo + hh * DH;
+    Frag<T> fq[KS], fdo[KS];
     float dpart = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
         fq[ks] = load_kc(Q + (long)qc * ld + ks * 32 + 8 * g);
         fdo[ks] = load_kc(dOr + ks * 32 + 8 * g);
         const Frag<T> fo = load_kc(Or + ks * 32 + 8 * g);
@@ -175,20 +184,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ 
     const float lq = lse[((long)b * H + hh) * n + qc];
     if (q < n && g == 0) dsum[((long)b * H + hh) * n + q] = Dq;
 
-    f32x4 dq[4];
+    f32x4 dq[ND];
 #pragma unroll
-    for (int d = 0; d < 4; ++d) dq[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int d = 0; d < ND; ++d) dq[d] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int ntile = (n + 31) / 32;
     for (int kt = 0; kt < ntile; ++kt) {
-        stage_tile<T>(Ks, K, ld, kt * 32, n, tid);
-        stage_tile<T>(Vs, V, ld, kt * 32, n, tid);
+        stage_tile<T, DH>(Ks, K, ld, kt * 32, n, tid);
+        stage_tile<T, DH>(Vs, V, ld, kt * 32, n, tid);
         __syncthreads();
         f32x4 ds[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
+            for (int ks = 0; ks < KS; ++ks) {
                 const Frag<T> fk = load_kc(Ks + (16 * t + li) * ROW + ks * 32 + 8 * g);
                 const Frag<T> fv = load_kc(Vs + (16 * t + li) * ROW + ks * 32 + 8 * g);
                 s = mma16(fk, fq[ks], s);
@@ -207,55 +216,55 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ 
         }
         const Frag<T> fds = acc_to_frag<T>(ds[0], ds[1]);
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
+        for (int d = 0; d < ND; ++d) {
             const Frag<T> fkT = load_ks<KMAP_ACC>(Ks, ROW, 0, 16 * d, lane);
             dq[d] = mma16(fkT, fds, dq[d]);
         }
         __syncthreads();
     }
     if (q < n) {
-        T* row = dqkv + ((long)b * n + q) * ld + hh * 64;
+        T* row = dqkv + ((long)b * n + q) * ld + hh * DH;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) store4(row + 16 * d + 4 * g, dq[d]);
+        for (int d = 0; d < ND; ++d) store4(row + 16 * d + 4 * g, dq[d]);
     }
 }
 
 // dK / dV pass: a wave owns 16 keys and sweeps all queries.
 // DROP: dV takes the dropped P, dS as in the dQ pass.  The key is on the lane here, so every element is a Philox block of its own
 // (one word used)
-template <typename T, bool DROP>
+template <typename T, int DH, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__ qkv, const T* __restrict__ dO,
                                                              const float* __restrict__ lse, const float* __restrict__ dsum,
                                                              T* __restrict__ dqkv, int n, int H, float scale, DropCtx dr) {
-    constexpr int ROW = AtCfg<T>::ROW;
+    constexpr int ROW = AtCfg<T, DH>::ROW, KS = DH / 32, ND = DH / 16;
     __shared__ __attribute__((aligned(16))) T Qs[32 * ROW];
     __shared__ __attribute__((aligned(16))) T Gs[32 * ROW];   // dO tile
     __shared__ float Ls[32], Ds[32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
     const int b = blockIdx.y / H, hh = blockIdx.y % H;
-    const long ld = 3L * H * 64, ldo = (long)H * 64;
-    const T* Q = qkv + (long)b * n * ld + hh * 64;
-    const T* K = Q + H * 64;
-    const T* V = K + H * 64;
-    const T* dOb = dO + (long)b * n * ldo + hh * 64;
+    const long ld = 3L * H * DH, ldo = (long)H * DH;
+    const T* Q = qkv + (long)b * n * ld + hh * DH;
+    const T* K = Q + H * DH;
+    const T* V = K + H * DH;
+    const T* dOb = dO + (long)b * n * ldo + hh * DH;
     const int key = blockIdx.x * 64 + wave * 16 + li;
     const int kc = min(key, n - 1);
-    Frag<T> fk[2], fv[2];
+    Frag<T> fk[KS], fv[KS];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
         fk[ks] = load_kc(K + (long)kc * ld + ks * 32 + 8 * g);
         fv[ks] = load_kc(V + (long)kc * ld + ks * 32 + 8 * g);
     }
-    f32x4 dk[4], dv[4];
+    f32x4 dk[ND], dv[ND];
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
+    for (int d = 0; d < ND; ++d) {
         dk[d] = f32x4{0.f, 0.f, 0.f, 0.f};
         dv[d] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const int ntile = (n + 31) / 32;
     for (int qt = 0; qt < ntile; ++qt) {
-        stage_tile<T>(Qs, Q, ld, qt * 32, n, tid);
-        stage_tile<T>(Gs, dOb, ldo, qt * 32, n, tid);
+        stage_tile<T, DH>(Qs, Q, ld, qt * 32, n, tid);
+        stage_tile<T, DH>(Gs, dOb, ldo, qt * 32, n, tid);
         if (tid < 32) {
             const int qq = qt * 32 + tid;
             Ls[tid] = (qq < n) ? lse[((long)b * H + hh) * n + qq] : INFINITY;
@@ -267,7 +276,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
         for (int t = 0; t < 2; ++t) {
             f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
+            for (int ks = 0; ks < KS; ++ks) {
                 const Frag<T> fa = load_kc(Qs + (16 * t + li) * ROW + ks * 32 + 8 * g);
                 const Frag<T> fg = load_kc(Gs + (16 * t + li) * ROW + ks * 32 + 8 * g);
                 s = mma16(fa, fk[ks], s);
@@ -292,7 +301,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
         const Frag<T> fp = acc_to_frag<T>(p[0], p[1]);
         const Frag<T> fds = acc_to_frag<T>(ds[0], ds[1]);
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
+        for (int d = 0; d < ND; ++d) {
             const Frag<T> fgT = load_ks<KMAP_ACC>(Gs, ROW, 0, 16 * d, lane);
             const Frag<T> fqT = load_ks<KMAP_ACC>(Qs, ROW, 0, 16 * d, lane);
             dv[d] = mma16(fgT, fp, dv[d]);
@@ -301,10 +310,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
         __syncthreads();
     }
     if (key < n) {
-        T* krow = dqkv + ((long)b * n + key) * ld + H * 64 + hh * 64;
-        T* vrow = krow + H * 64;
+        T* krow = dqkv + ((long)b * n + key) * ld + H * DH + hh * DH;
+        T* vrow = krow + H * DH;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
+        for (int d = 0; d < ND; ++d) {
             store4(krow + 16 * d + 4 * g, dk[d]);
             store4(vrow + 16 * d + 4 * g, dv[d]);
         }
@@ -313,43 +322,64 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
 
 }  // namespace
 
-int m3l_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, hipStream_t st, const DropCtx* drop) {
-    M3L_CHECK(dtype == 0 || dtype == 1, "attn_fwd: bad dtype %d", dtype);
-    M3L_CHECK(B > 0 && n > 0 && H > 0, "attn_fwd: empty problem B=%d n=%d H=%d", B, n, H);
+namespace {
+
+template <int DH>
+void attn_fwd_launch(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, hipStream_t st, const DropCtx& dr) {
     dim3 grid(cdiv(n, 64), B * H);
-    const float scale = 0.125f;   // dim_head ** -0.5, dim_head = 64
-    ProfScope prof("attn_fwd", B, n, H, 4.0 * B * H * (double)n * n * 64, st);
-    const DropCtx dr = drop ? *drop : DropCtx{};
+    const float scale = (float)(1.0 / sqrt((double)DH));   // dim_head ** -0.5 in fp32 (exactly 0.125f at 64)
     if (dr.on) {
         if (dtype == 1)
-            attn_fwd_kernel<bf16, true><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)o, lse, n, H, scale, dr);
+            attn_fwd_kernel<bf16, DH, true><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)o, lse, n, H, scale, dr);
         else
-            attn_fwd_kernel<float, true><<<grid, 256, 0, st>>>((const float*)qkv, (float*)o, lse, n, H, scale, dr);
+            attn_fwd_kernel<float, DH, true><<<grid, 256, 0, st>>>((const float*)qkv, (float*)o, lse, n, H, scale, dr);
     } else if (dtype == 1)
-        attn_fwd_kernel<bf16, false><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)o, lse, n, H, scale, dr);
+        attn_fwd_kernel<bf16, DH, false><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)o, lse, n, H, scale, dr);
     else
-        attn_fwd_kernel<float, false><<<grid, 256, 0, st>>>((const float*)qkv, (float*)o, lse, n, H, scale, dr);
-    M3L_LAUNCH_CHECK();
-    return 0;
+        attn_fwd_kernel<float, DH, false><<<grid, 256, 0, st>>>((const float*)qkv, (float*)o, lse, n, H, scale, dr);
 }
 
-int m3l_attn_bwd(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
-                 int n, int H, hipStream_t st, const DropCtx* drop) {
-    M3L_CHECK(dtype == 0 || dtype == 1, "attn_bwd: bad dtype %d", dtype);
-    M3L_CHECK(B > 0 && n > 0 && H > 0, "attn_bwd: empty problem B=%d n=%d H=%d", B, n, H);
+template <int DH>
+void attn_bwd_launch(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B, int n,
+                     int H, hipStream_t st, const DropCtx& dr) {
     dim3 grid(cdiv(n, 64), B * H);
-    const float scale = 0.125f;
-    ProfScope prof("attn_bwd", B, n, H, 10.0 * B * H * (double)n * n * 64, st);
-    const DropCtx dr = drop ? *drop : DropCtx{};
+    const float scale = (float)(1.0 / sqrt((double)DH));
 #define ATTN_BWD(T, D)                                                                                                                        \
-    attn_bwd_dq_kernel<T, D><<<grid, 256, 0, st>>>((const T*)qkv, (const T*)o, (const T*)dO, lse, dsum, (T*)dqkv, n, H, scale, dr);         \
-    attn_bwd_dkv_kernel<T, D><<<grid, 256, 0, st>>>((const T*)qkv, (const T*)dO, lse, dsum, (T*)dqkv, n, H, scale, dr)
+    attn_bwd_dq_kernel<T, DH, D><<<grid, 256, 0, st>>>((const T*)qkv, (const T*)o, (const T*)dO, lse, dsum, (T*)dqkv, n, H, scale, dr);     \
+    attn_bwd_dkv_kernel<T, DH, D><<<grid, 256, 0, st>>>((const T*)qkv, (const T*)dO, lse, dsum, (T*)dqkv, n, H, scale, dr)
     if (dtype == 1) {
         if (dr.on) { ATTN_BWD(bf16, true); } else { ATTN_BWD(bf16, false); }
     } else {
         if (dr.on) { ATTN_BWD(float, true); } else { ATTN_BWD(float, false); }
     }
 #undef ATTN_BWD
+}
+
+}  // namespace
+
+int m3l_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, int DH, hipStream_t st, const DropCtx* drop) {
+    M3L_CHECK(dtype == 0 || dtype == 1, "attn_fwd: bad dtype %d", dtype);
+    M3L_CHECK(B > 0 && n > 0 && H > 0, "attn_fwd: empty problem B=%d n=%d H=%d", B, n, H);
+    M3L_CHECK(DH == 32 || DH == 64 || DH == 128, "attn_fwd: dim_head %d is not one of 32, 64, 128", DH);
+    ProfScope prof("attn_fwd", B, n, H, 4.0 * B * H * (double)n * n * DH, st);
+    const DropCtx dr = drop ? *drop : DropCtx{};
+    if (DH == 32) attn_fwd_launch<32>(dtype, qkv, o, lse, B, n, H, st, dr);
+    else if (DH == 64) attn_fwd_launch<64>(dtype, qkv, o, lse, B, n, H, st, dr);
+    else attn_fwd_launch<128>(dtype, qkv, o, lse, B, n, H, st, dr);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_attn_bwd(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
+                 int n, int H, int DH, hipStream_t st, const DropCtx* drop) {
+    M3L_CHECK(dtype == 0 || dtype == 1, "attn_bwd: bad dtype %d", dtype);
+    M3L_CHECK(B > 0 && n > 0 && H > 0, "attn_bwd: empty problem B=%d n=%d H=%d", B, n, H);
+    M3L_CHECK(DH == 32 || DH == 64 || DH == 128, "attn_bwd: dim_head %d is not one of 32, 64, 128", DH);
+    ProfScope prof("attn_bwd", B, n, H, 10.0 * B * H * (double)n * n * DH, st);
+    const DropCtx dr = drop ? *drop : DropCtx{};
+    if (DH == 32) attn_bwd_launch<32>(dtype, qkv, o, dO, lse, dsum, dqkv, B, n, H, st, dr);
+    else if (DH == 64) attn_bwd_launch<64>(dtype, qkv, o, dO, lse, dsum, dqkv, B, n, H, st, dr);
+    else attn_bwd_launch<128>(dtype, qkv, o, dO, lse, dsum, dqkv, B, n, H, st, dr);
     M3L_LAUNCH_CHECK();
     return 0;
 }

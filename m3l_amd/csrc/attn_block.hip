@@ -871,10 +871,10 @@ extern "C" int m3l_set_attn_block(int mode) {
 extern "C" void m3l_set_attn_phase_buffer(void* dev_buf) { g_attn_phase_ts = reinterpret_cast<unsigned long long*>(dev_buf); }
 unsigned long long* m3l_attn_phase_buffer(void) { return g_attn_phase_ts; }
 
-// 1 when the fused attention-block kernel takes this problem
-int m3l_attn_block_supported(int dtype, int D, int heads, int n, int project_out) {
+// 1 when the fused attention-block kernel takes this problem (built for 64-wide heads only)
+int m3l_attn_block_supported(int dtype, int D, int heads, int n, int project_out, int dim_head) {
     if (ab_state() < 1) return 0;
-    return dtype == 1 && project_out && (D == 128 || D == 192) && heads * 64 == D && n >= 1 && n <= 48;
+    return dtype == 1 && project_out && dim_head == 64 && (D == 128 || D == 192) && heads * 64 == D && n >= 1 && n <= 48;
 }
 
 // The attention BACKWARD block (mode bit 2).  Round 1 kept it opt-in: the weight-gradient side stream (2.5 ms per step) then bounded

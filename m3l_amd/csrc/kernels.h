@@ -152,7 +152,7 @@ int m3l_gemm_init();
 int m3l_gemm_nt_colsum_rows(int M, int N);   // number of partial rows written through GemmEpi::colsum_part
 
 // fused LN1 + QKV + attention + out-proj + residual + LN2 for short sequences (attn_block.hip)
-int m3l_attn_block_supported(int dtype, int D, int heads, int n, int project_out);
+int m3l_attn_block_supported(int dtype, int D, int heads, int n, int project_out, int dim_head);
 int m3l_attn_block_bwd_enabled(void);
 int m3l_attn_block_fwd(int D, int B, int n, const float* x, const float* ln1_w, const float* ln1_b, const void* wqkv, const void* wo,
                        const float* bo, const float* ln2_w, const float* ln2_b, float eps, void* xn1, void* qkv, void* o, float* lse,
@@ -181,13 +181,13 @@ int m3l_mlp_t192_supported(int dtype, int D, int mlp, int M);
 int m3l_mlp_t192_fwd(int D, int M, int mlp, const void* xn2, const float* x1, const void* w1, const float* b1, const void* w2, const float* b2,
                      void* u, void* h, float* xout, hipStream_t st);
 // LN1 + QKV + attention per sample for 48 < n <= 192 (D = 192 / 3 heads, D = 256 / 4 heads): xn1, qkv, o, lse as the per-op kernels write them
-int m3l_attn_t192_fwd_supported(int dtype, int D, int heads, int n, int B);
+int m3l_attn_t192_fwd_supported(int dtype, int D, int heads, int n, int B, int dim_head);
 int m3l_attn_t192_fwd(int D, int B, int n, const float* x, const float* ln_w, const float* ln_b, const void* wqkv, float eps, void* xn1, void* qkv,
                       void* o, float* lse, hipStream_t st);
 // dO = dx1_t Wo + the whole attention backward of a sample -> dqkv (same support as the forward)
 int m3l_attn_t192_bwd(int D, int B, int n, const void* dx1t, const void* qkv, const void* o, const float* lse, const void* woT, void* dqkv,
                       hipStream_t st);
-int m3l_attn_tail_mlp_t192_supported(int dtype, int D, int HD, int mlp, int M);
+int m3l_attn_tail_mlp_t192_supported(int dtype, int D, int HD, int mlp, int M, int dim_head);
 int m3l_attn_tail_mlp_t192_fwd(int D, int M, int mlp, const void* o, const float* x, const void* wo, const float* bo, const float* ln2_w,
                                const float* ln2_b, float eps, float* x1, void* xn2, const void* w1, const float* b1, const void* w2,
                                const float* b2, void* u, void* h, float* xout, hipStream_t st);
@@ -201,10 +201,11 @@ int m3l_qkv_bwd_t192_supported(int dtype, int D, int K, int M);
 int m3l_qkv_bwd_t192_tiles(int D, int M);
 int m3l_qkv_bwd_t192(int D, int M, int K, const void* dqkv, const float* x, const float* ln1_w, const void* wqkvT, const float* dres, float eps,
                      float* dx_out, void* dxt_out, float* ln_part, hipStream_t st);
+// DH: head width (dim_head), one of 32, 64, 128; qkv [B n, 3 H DH], o / dO [B n, H DH]
 // drop (optional, site 0): the probabilities that multiply V are masked and scaled; lse stays that of the un-dropped softmax
-int m3l_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, hipStream_t st, const DropCtx* drop = nullptr);
+int m3l_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, int DH, hipStream_t st, const DropCtx* drop = nullptr);
 int m3l_attn_bwd(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B, int n,
-                 int H, hipStream_t st, const DropCtx* drop = nullptr);
+                 int H, int DH, hipStream_t st, const DropCtx* drop = nullptr);
 // dropout backward of a GEMM output site (1, 3): out = mask * scale * dy (compute type, [M, N] dense) and the column sums of out
 // (= the Linear's bias gradient) as partial rows part[m3l_dropout_bwd_blocks(M)][N]
 int m3l_dropout_bwd_blocks(int M);

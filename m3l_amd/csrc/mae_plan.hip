@@ -162,13 +162,15 @@ struct RbScope {          // residual mode of the launches issued inside the sco
     explicit RbScope(bool on) { m3l_set_call_rb(on ? 1 : 0); }
     ~RbScope() { m3l_set_call_rb(0); }
 };
+// head width of a stack (m3l_tf_cfg.dim_head, 0 = 64)
+inline int tf_dh(const m3l_tf_cfg* c) { return c->dim_head ? c->dim_head : 64; }
 bool tf_rb(const m3l_tf_cfg* c, int B, int n, bool fuse) {
     if (!res_bf16_mode() || c->dtype != 1 || fuse || !c->project_out || c->depth < 1) return false;
     // every kernel a bf16 stack can take has a bf16-residual form — the per-sample blocks, the row tiles, and (since the EPI_RES16 epilogue
     // of the NT GEMM and the typed dres of ln_bwd) the per-op chain — except the one-launch encoder backward; the residual epilogue of the
-    // out-proj / fc2 GEMMs needs K = heads * 64 / mlp_dim to be a multiple of the 64-element K tile
-    if (c->mlp_dim % 64 != 0) return false;
-    if ((m3l_enc_mega_enabled() & 2) && m3l_attn_block_supported(1, c->dim, c->heads, n, c->project_out)) return false;
+    // out-proj / fc2 GEMMs needs K = heads * dim_head / mlp_dim to be a multiple of the 64-element K tile
+    if (c->mlp_dim % 64 != 0 || (c->heads * tf_dh(c)) % 64 != 0) return false;
+    if ((m3l_enc_mega_enabled() & 2) && m3l_attn_block_supported(1, c->dim, c->heads, n, c->project_out, tf_dh(c))) return false;
     (void)B;
     return true;
 }
@@ -177,8 +179,8 @@ bool tf_rb(const m3l_tf_cfg* c, int B, int n, bool fuse) {
 // (both evaluate the fitted GELU, as every bf16 kernel does).  The backward reads it to know whether h exists and which GELU reproduces it.
 int fused_mlp_kind(const m3l_tf_cfg* c, int B, int n, bool fuse) {
     const int M = B * n, D = c->dim, mlp = c->mlp_dim, dt = c->dtype;
-    if (fuse || dt != 1) return 0;
-    const bool block = m3l_attn_block_supported(dt, D, c->heads, n, c->project_out);
+    if (fuse || dt != 1 || tf_dh(c) != 64) return 0;     // dim_head != 64: the per-op chain (m3l_transformer_fwd_dropout)
+    const bool block = m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, 64);
     const bool t192 = m3l_mlp_t192_supported(dt, D, mlp, M);
     if (block && !(m3l_mlp_t192_short() && t192) && m3l_mlp_block_supported(dt, D, mlp, n)) return 1;
     return t192 ? 2 : 0;
@@ -317,7 +319,7 @@ void layer_wgrad_problems(TnProblem* pr, int D, int HD, int mlp, bool project_ou
 }
 TfWs tf_layout(const m3l_tf_cfg* c, int B, int n, void* ws, bool dropout = false) {
     Arena a(ws);
-    const size_t M = (size_t)B * n, D = c->dim, HD = (size_t)c->heads * 64, mlp = c->mlp_dim, e = esz(c->dtype);
+    const size_t M = (size_t)B * n, D = c->dim, HD = (size_t)c->heads * tf_dh(c), mlp = c->mlp_dim, e = esz(c->dtype);
     TfWs w;
     w.L.resize(c->depth);
     for (auto& l : w.L) {
@@ -389,7 +391,9 @@ int check_tf(const m3l_tf_cfg* c, int B, int n) {
     M3L_CHECK(c->dim > 0 && c->dim % 8 == 0 && c->dim <= 1024, "transformer: dim=%d must be a multiple of 8, <= 1024", c->dim);
     M3L_CHECK(c->mlp_dim > 0 && c->mlp_dim % 8 == 0, "transformer: mlp_dim=%d must be a multiple of 8", c->mlp_dim);
     M3L_CHECK(c->heads > 0 && c->depth >= 0, "transformer: heads=%d depth=%d", c->heads, c->depth);
-    M3L_CHECK(c->project_out || c->heads * 64 == c->dim, "transformer: identity to_out needs heads*64 == dim");
+    M3L_CHECK(c->dim_head == 0 || c->dim_head == 32 || c->dim_head == 64 || c->dim_head == 128,
+              "transformer: dim_head=%d is not one of 32, 64, 128 (0 = 64)", c->dim_head);
+    M3L_CHECK(c->project_out || c->heads * tf_dh(c) == c->dim, "transformer: identity to_out needs heads*dim_head == dim");
     M3L_CHECK(c->dim % 64 == 0, "transformer: dim=%d must be a multiple of 64 (LDS-DMA GEMM K-tile)", c->dim);
     M3L_CHECK(B > 0 && n > 0, "transformer: empty input B=%d n=%d", B, n);
     return 0;
@@ -400,7 +404,7 @@ int check_tf(const m3l_tf_cfg* c, int B, int n) {
 // =================================================================================================================
 extern "C" {
 
-int m3l_version(void) { return 401; }
+int m3l_version(void) { return 402; }
 
 // diagnostic switch (bench.py's stand-alone roofline figure, PMC passes): 1 = every weight gradient on the caller's stream
 int m3l_set_wgrad_inline(int on) {
@@ -458,7 +462,7 @@ int m3l_side_pending(void) {
 
 // 1 when this stack runs the bf16 residual stream at (B, n) (mae_step.hip: whether its neighbours exchange bf16 with it)
 int m3l_transformer_rb(const m3l_tf_cfg* c, int B, int n) {
-    const int D = c->dim, HD = c->heads * 64, mlp = c->mlp_dim;
+    const int D = c->dim, HD = c->heads * tf_dh(c), mlp = c->mlp_dim;
     return tf_rb(c, B, n, use_rowln() && m3l_gemm_nt_rowln_supported(c->dtype, D, HD) && m3l_gemm_nt_rowln_supported(c->dtype, D, mlp)) ? 1 : 0;
 }
 
@@ -652,17 +656,19 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
 
 // With a dropout descriptor of p > 0 every layer takes the per-op chain (LN, QKV GEMM, attention, out-proj GEMM, LN, fc1, fc2): the
 // masks live in the attention kernels and the NT GEMM epilogue only.  The residual mode is the one tf_rb picks without dropout.
+// A stack whose heads are not 64 wide takes the same per-op chain (the block, row-tile and one-launch kernels are built for 64).
 int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t,
                                 float* y32, const m3l_dropout* drop, void* stream) {
     if (check_tf(c, B, n)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const bool dp = drop_active(drop);
+    const bool po = dp || tf_dh(c) != 64;     // every layer on the per-op chain
     M3L_CHECK(!dp || drop->p <= 1.f, "transformer: dropout p=%g outside [0, 1]", (double)drop->p);
     // the per-op chain's fc2 GEMM takes the dropout epilogue only on the LDS-DMA kernel: K = mlp_dim in whole K tiles
     M3L_CHECK(!dp || c->mlp_dim % (c->dtype ? 64 : 32) == 0, "transformer: dropout needs mlp_dim %% %d == 0 (got %d)", c->dtype ? 64 : 32,
               c->mlp_dim);
     TfWs w = tf_layout(c, B, n, ws, dp);
-    const int M = B * n, D = c->dim, HD = c->heads * 64, mlp = c->mlp_dim, dt = c->dtype;
+    const int M = B * n, D = c->dim, HD = c->heads * tf_dh(c), mlp = c->mlp_dim, dt = c->dtype;
     const float* x = x_in;
     // compute-type weight copies (+ transposes for the dgrads) of every layer: one launch per 16 layers, on the caller's stream
     {
@@ -685,7 +691,7 @@ int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* 
     // LayerNorms fused into the epilogue of the GEMM that produces their input (gemm_rowln.hip) when the row width allows it:
     // out-proj + LN2 of the layer, fc2 + LN1 of the next layer (or the final norm).  Only the very first LN1 is a kernel.
     const bool fuse_cfg = use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, HD) && m3l_gemm_nt_rowln_supported(dt, D, mlp);
-    const bool fuse = fuse_cfg && !dp;
+    const bool fuse = fuse_cfg && !po;
     const void* const* tfin = tensors + 11 * c->depth;
     bool final_done = false;
     // bf16 residual stream: the stack's input as bf16 (kept for the backward of layer 0 in the otherwise unused w.dx buffer); from here on
@@ -704,8 +710,8 @@ int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* 
     RbScope rb_scope(rb);
     // short sequences whose every half layer takes a block kernel: the whole stack in ONE launch (enc_mega.hip)
     int l_begin = 0;
-    if (!dp && (m3l_enc_mega_enabled() & 1) && !fuse && c->depth >= 1 && c->depth <= M3L_MEGA_MAX_LAYERS && c->project_out &&
-        m3l_attn_block_supported(dt, D, c->heads, n, c->project_out) && m3l_mlp_block_supported(dt, D, mlp, n) &&
+    if (!po && (m3l_enc_mega_enabled() & 1) && !fuse && c->depth >= 1 && c->depth <= M3L_MEGA_MAX_LAYERS && c->project_out &&
+        m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, tf_dh(c)) && m3l_mlp_block_supported(dt, D, mlp, n) &&
         !(m3l_mlp_t192_short() && m3l_mlp_t192_supported(dt, D, mlp, M))) {
         const void* lay[M3L_MEGA_MAX_LAYERS][20];
         for (int l = 0; l < c->depth; ++l) {
@@ -727,14 +733,14 @@ int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* 
         const float *ln1_w = (const float*)t[0], *ln1_b = (const float*)t[1], *out_b = (const float*)t[4], *ln2_w = (const float*)t[5],
                     *ln2_b = (const float*)t[6], *fc1_b = (const float*)t[8], *fc2_b = (const float*)t[10];
 
-        const bool block = !dp && !fuse && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out);
+        const bool block = !po && !fuse && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, tf_dh(c));
         if (block) {
             // the whole attention half of the layer in one launch (short sequences: the MAE encoder)
             if (m3l_attn_block_fwd(D, B, n, x, ln1_w, ln1_b, L.wqkv, L.wo, out_b, ln2_w, ln2_b, LN_EPS, L.xn1, L.qkv, L.o, L.lse, L.x1,
                                    L.xn2, st))
                 return 1;
         }
-        const bool attn_t = !dp && !block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B);
+        const bool attn_t = !po && !block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B, tf_dh(c));
         if (attn_t) {
             // long sequences: LN1 + QKV + attention of a sample in one launch (the out-proj + LN2 continue in the feed-forward launch)
             if (m3l_attn_t192_fwd(D, B, n, x, ln1_w, ln1_b, L.wqkv, LN_EPS, L.xn1, L.qkv, L.o, L.lse, st)) return 1;
@@ -748,9 +754,9 @@ int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* 
         if (!attn_t) {
         if (m3l_gemm_nt(dt, L.xn1, D, L.wqkv, D, M, 3 * HD, D, &e, st)) return 1;
         const DropCtx d0 = dctx(l, 0);
-        if (m3l_attn_fwd(dt, L.qkv, L.o, L.lse, B, n, c->heads, st, &d0)) return 1;
+        if (m3l_attn_fwd(dt, L.qkv, L.o, L.lse, B, n, c->heads, tf_dh(c), st, &d0)) return 1;
         }
-        if (!dp && c->project_out && !fuse && m3l_attn_tail_mlp_t192_supported(dt, D, HD, mlp, M)) {
+        if (!po && c->project_out && !fuse && m3l_attn_tail_mlp_t192_supported(dt, D, HD, mlp, M, tf_dh(c))) {
             // long sequences: out-proj + residual + LN2 + fc1 + GELU + fc2 + residual in ONE launch per 192-row tile
             if (m3l_attn_tail_mlp_t192_fwd(D, M, mlp, L.o, x, L.wo, out_b, ln2_w, ln2_b, LN_EPS, L.x1, L.xn2, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused,
                                            L.xout, st))
@@ -776,13 +782,13 @@ int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* 
             if (m3l_ln_fwd(dt, L.x1, M, D, ln2_w, ln2_b, LN_EPS, L.xn2, nullptr, st)) return 1;
         }
         }
-        if (!dp && block && !(m3l_mlp_t192_short() && m3l_mlp_t192_supported(dt, D, mlp, M)) && m3l_mlp_block_supported(dt, D, mlp, n)) {
+        if (!po && block && !(m3l_mlp_t192_short() && m3l_mlp_t192_supported(dt, D, mlp, M)) && m3l_mlp_block_supported(dt, D, mlp, n)) {
             // the feed-forward half in one launch as well
             if (m3l_mlp_block_fwd(D, mlp, B, n, L.xn2, L.x1, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused, L.xout, st)) return 1;
             x = L.xout;
             continue;
         }
-        if (!dp && !fuse && m3l_mlp_t192_supported(dt, D, mlp, M)) {
+        if (!po && !fuse && m3l_mlp_t192_supported(dt, D, mlp, M)) {
             // long sequences: fc1 + GELU + fc2 + residual per 192-row tile, the hidden activation never leaves the CU between the GEMMs
             if (m3l_mlp_t192_fwd(D, M, mlp, L.xn2, L.x1, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused, L.xout, st)) return 1;
             x = L.xout;
@@ -844,11 +850,12 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
                                       void* stream) {
     if (check_tf(c, B, n)) return 1;
     const bool dp = drop_active(drop);
+    const bool po = dp || tf_dh(c) != 64;     // every layer on the per-op chain (the forward's decision)
     M3L_CHECK(0 <= layer_lo && layer_lo <= layer_hi && layer_hi <= c->depth, "transformer_bwd: bad layer range [%d, %d)", layer_lo, layer_hi);
     M3L_CHECK(dy_dtype == 0 || dy_dtype == c->dtype, "transformer_bwd: dy dtype %d incompatible with compute dtype %d", dy_dtype, c->dtype);
     hipStream_t st = (hipStream_t)stream;
     TfWs w = tf_layout(c, B, n, ws, dp);
-    const int M = B * n, D = c->dim, HD = c->heads * 64, mlp = c->mlp_dim, dt = c->dtype;
+    const int M = B * n, D = c->dim, HD = c->heads * tf_dh(c), mlp = c->mlp_dim, dt = c->dtype;
     auto dctx = [&](int layer, int site) { return dp ? m3l_drop_ctx(drop->p, drop->seed, layer, site) : DropCtx{}; };
     // every LayerNorm backward leaves its [G][3 D] partials (dgamma | dbeta | column sums = bias gradient of the Linear that fed the
     // residual branch) in its own slot; ONE batched reduce at the end of the range, on the side stream, replaces 2 small launches per
@@ -896,7 +903,7 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             return 1;
     }
     if (side_init()) return 2;
-    const bool fuse = !dp && use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, mlp) && m3l_gemm_nt_rowln_supported(dt, D, 3 * HD);
+    const bool fuse = !po && use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, mlp) && m3l_gemm_nt_rowln_supported(dt, D, 3 * HD);
     const bool wg_inline = wgrad_inline();
     hipStream_t s2 = wg_inline ? st : g_side.s;
     // completion of the wgrad launch that last read operand set i.  A backward split into several range calls (chunks, for the
@@ -943,9 +950,9 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
     };
     const int csrows = m3l_gemm_nt_colsum_rows(M, mlp);
     // short sequences whose both backward halves take a block kernel: one launch per weight-gradient group of layers (enc_mega.hip)
-    const bool mega_bwd = !dp && (m3l_enc_mega_enabled() & 2) && !fuse && c->project_out && m3l_mlp_block_bwd_supported(dt, D, mlp, n) &&
+    const bool mega_bwd = !po && (m3l_enc_mega_enabled() & 2) && !fuse && c->project_out && m3l_mlp_block_bwd_supported(dt, D, mlp, n) &&
                           !(m3l_mlp_t192_supported(dt, D, mlp, M) && m3l_mlp_t192_short()) && m3l_attn_block_bwd_enabled() &&
-                          m3l_attn_block_supported(dt, D, c->heads, n, c->project_out) && w.wg_batch <= M3L_MEGA_BWD_MAX_LAYERS;
+                          m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, tf_dh(c)) && w.wg_batch <= M3L_MEGA_BWD_MAX_LAYERS;
     for (int l = layer_hi - 1; l >= layer_lo; --l) {
         if (mega_bwd && pend_sets.empty()) {
             const int g_lo = std::max(layer_lo, l - w.wg_batch + 1), cnt = l - g_lo + 1;
@@ -996,8 +1003,8 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             if (g[10] && m3l_reduce_rows(w.dpart, m3l_dropout_bwd_blocks(M), D, D, g[10], 0, st)) return 1;
             dy3 = w.dp3[cur];
         }
-        const bool mlp_t192 = !dp && !fuse && m3l_mlp_t192_supported(dt, D, mlp, M) && (m3l_mlp_t192_short() || !m3l_mlp_block_bwd_supported(dt, D, mlp, n));
-        const bool mlp_block = !dp && !fuse && !mlp_t192 && m3l_mlp_block_bwd_supported(dt, D, mlp, n);
+        const bool mlp_t192 = !po && !fuse && m3l_mlp_t192_supported(dt, D, mlp, M) && (m3l_mlp_t192_short() || !m3l_mlp_block_bwd_supported(dt, D, mlp, n));
+        const bool mlp_block = !po && !fuse && !mlp_t192 && m3l_mlp_block_bwd_supported(dt, D, mlp, n);
         int cs_rows = csrows;
         if (mlp_block) {
             // short sequences: du, its column sums, dxn2 and the LN2 backward in one launch; one partial row per sample
@@ -1037,7 +1044,7 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
                 return 1;
         }
         // ---- attention: x1 = x + to_out(attn(LN1(x)))
-        const bool attn_block = mlp_block && m3l_attn_block_bwd_enabled() && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out);
+        const bool attn_block = mlp_block && m3l_attn_block_bwd_enabled() && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, tf_dh(c));
         float* dx_dst = (l == 0 && dx_in) ? dx_in : w.dx;
         float* db_prev = (l && !dp) ? grads[11 * (l - 1) + 10] : nullptr;                             // fc2 bias of layer l-1
         if (attn_block) {
@@ -1062,7 +1069,7 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             if (g[4] && m3l_reduce_rows(w.dpart, m3l_dropout_bwd_blocks(M), D, D, g[4], 0, st)) return 1;
             dy1 = w.dp1[cur];
         }
-        const bool attn_t = !dp && !attn_block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B);
+        const bool attn_t = !po && !attn_block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B, tf_dh(c));
         if (attn_t) {
             // long sequences: dO + both attention-backward passes of a sample in one launch
             if (m3l_attn_t192_bwd(D, B, n, w.dx1_t[cur], L.qkv, L.o, L.lse, L.woT, w.dqkv[cur], st)) return 1;
@@ -1075,13 +1082,13 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             d_o = w.d_o;
         }
         const DropCtx d0 = dctx(l, 0);
-        if (m3l_attn_bwd(dt, L.qkv, L.o, d_o, L.lse, w.dsum, w.dqkv[cur], B, n, c->heads, st, &d0)) return 1;
+        if (m3l_attn_bwd(dt, L.qkv, L.o, d_o, L.lse, w.dsum, w.dqkv[cur], B, n, c->heads, tf_dh(c), st, &d0)) return 1;
         }
         // ---- the weight gradients of the layer join the pending group; every wg_batch layers (and at the end of the range) the group
         // goes out as ONE grouped TN launch + one reduce on the side stream, overlapping the dgrad chains of the layers below
         {
             // dW2 = dx^T h; when the forward did not save h the kernel stages u and applies the GELU of the kernel that made it
-            const int hk = (!dp && drop_h() && fused_mlp_kind(c, B, n, fuse)) ? 2 : 0;     // every bf16 kernel evaluates the fitted GELU (form 2)
+            const int hk = (!po && drop_h() && fused_mlp_kind(c, B, n, fuse)) ? 2 : 0;     // every bf16 kernel evaluates the fitted GELU (form 2)
             pend.push_back(TnProblem{dy3, hk ? L.u : L.h, D, mlp, D, mlp, g[9], mlp, D, mlp, 0, 0, hk});
             pend.push_back(TnProblem{w.du[cur], L.xn2, mlp, D, mlp, D, g[7], D, mlp, D, 0, 0});             // dW1 = du^T xn2
             pend.push_back(TnProblem{w.dqkv[cur], L.xn1, 3 * HD, D, 3 * HD, D, g[2], D, 3 * HD, D, 0, 0}); // dWqkv = dqkv^T xn1
@@ -1102,7 +1109,7 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             r.part = w.scratch; r.eps = LN_EPS;
             if (m3l_gemm_nt_rowln(dt, ROWLN_BWD, w.dqkv[cur], 3 * HD, L.wqkvT, 3 * HD, M, D, 3 * HD, &r, st)) return 1;   // dxn1 + LN1 backward
             if (m3l_reduce_rows_seg3(w.scratch, cdiv(M, 64), D, g[0], g[1], db_prev, 0, st)) return 1;
-        } else if (!dp && m3l_qkv_bwd_t192_supported(dt, D, 3 * HD, M)) {
+        } else if (!po && m3l_qkv_bwd_t192_supported(dt, D, 3 * HD, M)) {
             // long sequences: dxn1 and the LN1 backward per 192-row tile, dxn1 never leaves the registers
             if (l && claim_set(nxt)) return 2;
             const int tiles = m3l_qkv_bwd_t192_tiles(D, M);
@@ -1182,7 +1189,7 @@ struct FvWs {
 FvWs fv_layout(const m3l_tf_cfg* c, int B, int n, void* ws) {
     Arena a(ws);
     FvWs w;
-    const size_t M = (size_t)B * n, e = esz(c->dtype), HD = (size_t)c->heads * 64;
+    const size_t M = (size_t)B * n, e = esz(c->dtype), HD = (size_t)c->heads * tf_dh(c);
     w.xn = a.take(M * c->dim * e);
     w.qkv = a.take(M * 3 * HD * e);
     w.o = a.take(M * HD * e);
@@ -1207,7 +1214,7 @@ int m3l_frozen_vit_fwd(const m3l_tf_cfg* c, float ln_eps, int B, int n, const fl
     M3L_CHECK(ln_eps > 0.f && x_in && tensors && ws && y32, "frozen_vit: null argument / eps");
     hipStream_t st = (hipStream_t)stream;
     FvWs w = fv_layout(c, B, n, ws);
-    const int M = B * n, D = c->dim, HD = c->heads * 64, mlp = c->mlp_dim, dt = c->dtype;
+    const int M = B * n, D = c->dim, HD = c->heads * tf_dh(c), mlp = c->mlp_dim, dt = c->dtype;
     const float* x = x_in;
     for (int l = 0; l < c->depth; ++l) {
         const void* const* t = tensors + 12 * l;
@@ -1217,7 +1224,7 @@ int m3l_frozen_vit_fwd(const m3l_tf_cfg* c, float ln_eps, int B, int n, const fl
         GemmEpi e = epi0(3 * HD);
         e.bias = (const float*)t[3]; e.out_t = w.qkv;
         if (m3l_gemm_nt(dt, w.xn, D, t[2], D, M, 3 * HD, D, &e, st)) return 1;
-        if (m3l_attn_fwd(dt, w.qkv, w.o, w.lse, B, n, c->heads, st)) return 1;
+        if (m3l_attn_fwd(dt, w.qkv, w.o, w.lse, B, n, c->heads, tf_dh(c), st)) return 1;
         e = epi0(D);
         e.bias = (const float*)t[5]; e.res = x; e.out_f32 = x1;
         if (m3l_gemm_nt(dt, w.o, HD, t[4], HD, M, D, HD, &e, st)) return 1;
@@ -1804,11 +1811,18 @@ int m3l_op_dropout_mask(float p, uint64_t seed, int layer, int site, long rows, 
     return m3l_dropout_mask(&d, rows, N, out, (hipStream_t)stream);
 }
 int m3l_op_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, void* stream) {
-    return m3l_attn_fwd(dtype, qkv, o, lse, B, n, H, (hipStream_t)stream);
+    return m3l_attn_fwd(dtype, qkv, o, lse, B, n, H, 64, (hipStream_t)stream);
 }
 int m3l_op_attn_bwd(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
                     int n, int H, void* stream) {
-    return m3l_attn_bwd(dtype, qkv, o, dO, lse, dsum, dqkv, B, n, H, (hipStream_t)stream);
+    return m3l_attn_bwd(dtype, qkv, o, dO, lse, dsum, dqkv, B, n, H, 64, (hipStream_t)stream);
+}
+int m3l_op_attn_fwd_dh(int dtype, const void* qkv, void* o, float* lse, int B, int n, int H, void* stream, int dim_head) {
+    return m3l_attn_fwd(dtype, qkv, o, lse, B, n, H, dim_head, (hipStream_t)stream);
+}
+int m3l_op_attn_bwd_dh(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
+                       int n, int H, void* stream, int dim_head) {
+    return m3l_attn_bwd(dtype, qkv, o, dO, lse, dsum, dqkv, B, n, H, dim_head, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -591,7 +591,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_block_bwd_kernel(const bf16* _
 
 static size_t mb_fwd_lds(int kt, int mlp);
 int m3l_mlp_block_supported(int dtype, int D, int mlp, int n) {
-    return m3l_attn_block_supported(dtype, D, D / 64, n, 1) && mlp % 64 == 0 && mlp >= 64 && mb_fwd_lds(D / 64, mlp) <= 160 * 1024;
+    return m3l_attn_block_supported(dtype, D, D / 64, n, 1, 64) && mlp % 64 == 0 && mlp >= 64 && mb_fwd_lds(D / 64, mlp) <= 160 * 1024;
 }
 
 // LDS of the forward: the layout + [mlp] floats (b1); of the backward: the layout + [3][mlp] floats of column sums

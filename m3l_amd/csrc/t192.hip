@@ -1581,8 +1581,8 @@ int m3l_mlp_t192_fwd(int Dm, int M, int mlp, const void* xn2, const float* x1, c
 }
 
 // the same with the attention half's tail in front (x1 = x + o Wo^T + bo, xn2 = LN2(x1)): one launch for three of the per-op path
-int m3l_attn_tail_mlp_t192_supported(int dtype, int D, int HD, int mlp, int M) {
-    if (!(m3l_mlp_t192_supported(dtype, D, mlp, M) && HD == D)) return 0;
+int m3l_attn_tail_mlp_t192_supported(int dtype, int D, int HD, int mlp, int M, int dim_head) {
+    if (!(m3l_mlp_t192_supported(dtype, D, mlp, M) && HD == D && dim_head == 64)) return 0;
     return D != 192 || cdiv(M, 192) >= t192_min_tiles() || forced();
 }
 int m3l_attn_tail_mlp_t192_fwd(int Dm, int M, int mlp, const void* o, const float* x, const void* wo, const float* bo, const float* ln2_w,
@@ -1653,10 +1653,11 @@ int m3l_qkv_bwd_t192(int Dm, int M, int K, const void* dqkv, const float* x, con
     return 0;
 }
 
-// per-sample attention kernels: D = 192 with 3 heads (the MAE decoder) or D = 256 with 4 heads (M3L's default decoder), 48 < n <= 192
-int m3l_attn_t192_fwd_supported(int dtype, int D, int heads, int n, int B) {
+// per-sample attention kernels: D = 192 with 3 heads (the MAE decoder) or D = 256 with 4 heads (M3L's default decoder), 48 < n <= 192,
+// heads 64 wide
+int m3l_attn_t192_fwd_supported(int dtype, int D, int heads, int n, int B, int dim_head) {
     static const int attn_on = getenv("M3L_T192_ATTN") ? atoi(getenv("M3L_T192_ATTN")) : 1;      // 0: per-op attention (A/B measurements)
-    const bool shape = (D == 192 && heads == 3) || (D == 256 && heads == 4);
+    const bool shape = dim_head == 64 && ((D == 192 && heads == 3) || (D == 256 && heads == 4));
     return attn_on > 0 && t192_state() > 0 && dtype == 1 && shape && n > 48 && n <= 192 && (B >= t192_min_tiles() || forced());
 }
 int m3l_attn_t192_fwd(int Dm, int B, int n, const float* x, const float* ln_w, const float* ln_b, const void* wqkv, float eps, void* xn1, void* qkv,

@@ -43,11 +43,15 @@ class Rearrange(nn.Module):
         return x.reshape(b, c, h, self.p1, w, self.p2).permute(0, 2, 4, 3, 5, 1).reshape(b, h * w, self.p1 * self.p2 * c)
 
 
+# head widths the attention kernels are built for (m3l_tf_cfg.dim_head); 64 also takes the fused block / row-tile kernels
+DIM_HEADS = (32, 64, 128)
+
+
 class Attention(nn.Module):
     def __init__(self, dim, heads=8, dim_head=64, dropout=0.):
         super().__init__()
-        if dim_head != 64:
-            raise NotImplementedError("m3l_amd attention kernels are built for dim_head = 64 (all reference configs)")
+        if dim_head not in DIM_HEADS:
+            raise NotImplementedError(f"m3l_amd attention kernels are built for dim_head in {DIM_HEADS}, got {dim_head}")
         inner_dim = dim_head * heads
         project_out = not (heads == 1 and dim_head == dim)
         self.heads = heads
@@ -73,7 +77,7 @@ class Transformer(nn.Module):
         super().__init__()
         if not 0. <= dropout <= 1.:
             raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
-        self.dim, self.depth, self.heads, self.mlp_dim = dim, depth, heads, mlp_dim
+        self.dim, self.depth, self.heads, self.dim_head, self.mlp_dim = dim, depth, heads, dim_head, mlp_dim
         self.dropout_p = float(dropout)
         self.last_dropout_seed = None   # seed of the last forward that dropped (the masks are a function of it: include/m3l_amd.h "Dropout")
         self.project_out = not (heads == 1 and dim_head == dim)
@@ -117,7 +121,7 @@ class Transformer(nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
     def _cfg(self):
-        return L.TfCfg(self.dim, self.depth, self.heads, self.mlp_dim, int(self.project_out), Fn.dtype_code(self.compute_dtype))
+        return L.TfCfg(self.dim, self.depth, self.heads, self.mlp_dim, int(self.project_out), Fn.dtype_code(self.compute_dtype), self.dim_head)
 
     def _drop(self):
         """The dropout descriptor of one forward: active iff training and p > 0 (nn.Dropout's rule), with a fresh 63-bit seed drawn from
