@@ -411,6 +411,44 @@ int m3l_op_attn_bwd_dh(int dtype, const void* qkv, const void* o, const void* dO
 /* the dropout mask of site `site` of layer `layer` ("Dropout" above) for a (rows, N) tensor: out[row * N + c] = 1 kept / 0 dropped */
 int m3l_op_dropout_mask(float p, uint64_t seed, int layer, int site, long rows, int N, uint8_t* out, void* stream);
 
+/* ---- DINO self-distillation step (models/vtdino.py, tactile_ssl/model/layers/dino_head.py, tactile_ssl/loss/dino_loss.py, tactile_ssl/utils/ema.py)
+ * The head's MLP runs on m3l_op_gemm_nt / m3l_op_gemm_tn / m3l_op_colsum; these are the kernels it adds.  All row-major, f32 unless a dtype says
+ * otherwise; none of them uses a float atomic, so every result is the same bits on every run.
+ *
+ * Row L2 normalisation, y = x / max(||x||, eps) (F.normalize): y (compute type `out_dtype`) and / or y32 receive the result, norm[M] the
+ * un-clamped row norms the backward needs.  Backward: dx = (dy - y (y . dy)) / ||x||, and dy / eps where the norm was clamped. */
+int m3l_op_l2norm_fwd(int out_dtype, const float* x, int M, int D, float eps, void* y, float* y32, float* norm, void* stream);
+int m3l_op_l2norm_bwd(const float* dy, const float* x, const float* norm, int M, int D, float eps, float* dx, void* stream);
+/* Weight normalisation over dim 0 (torch.nn.utils.weight_norm of the prototype layer): W[k] = v[k] * (g[k] / ||v[k]||) for v [K, D], g [K], in
+ * the compute type, W [K, D]; vnorm[K] = ||v[k]|| (may be NULL).
+ * Backward from dW [K, D]: dg[k] = dW[k] . v[k] / ||v[k]||, dv[k] = g[k] / ||v[k]|| (dW[k] - v[k] (dW[k] . v[k]) / ||v[k]||^2). */
+int m3l_op_weightnorm_fwd(int dtype, const float* v, const float* g, int K, int D, void* W, float* vnorm, void* stream);
+int m3l_op_weightnorm_bwd(const float* dW, const float* v, const float* g, const float* vnorm, int K, int D, float* dv, float* dg, void* stream);
+/* DINO cross-entropy of P student views against Q centred, sharpened teacher views of B samples over K prototypes (K % 4 == 0):
+ *   loss = sum_p sum_q mean_b ( - sum_k T[q,b,k] log_softmax(S[p,b,:] * inv_ts)[k] ),  T = softmax((teacher - center) * inv_tt)
+ * (every pair, a view with itself included, and no division by the number of pairs: DINOLoss.forward).  S [P, B, K] and the teacher
+ * logits T [Q, B, K] are view-major.  Order of calls: m3l_op_dino_rowstats for the student rows (center NULL, inv_ts) and the teacher rows
+ * (center, inv_tt) -> stats [rows, 2] = (max, log-sum-exp) of the scaled row; m3l_op_dino_loss -> loss[0]; m3l_op_dino_grad ->
+ * dS[p,b,k] = dloss[0] * inv_ts / B * (Q softmax(S[p,b,:] * inv_ts)[k] - sum_q T[q,b,k]) in `out_dtype` (dloss: device scalar), stored
+ * TRANSPOSED: dST[k * ldr + p B + b], ldr >= P B (a multiple of 8 for the GEMMs), columns P B .. ldr - 1 zero.  That is the operand form of
+ * the prototype layer's two backward GEMMs: dW [K, D] = dST x_n as m3l_op_gemm_nt(A = dST, W = x_n^T), dx_n [P B, D] = dS W as
+ * m3l_op_gemm_tn(Y = dST, X = W), which reduces over the K rows in splits.  B <= 255.
+ * ws: m3l_op_dino_ws_bytes(rows of the call, K) bytes (for loss: rows = B). */
+size_t m3l_op_dino_ws_bytes(int rows, int K);
+int m3l_op_dino_rowstats(const float* logits, int rows, int K, const float* center, float inv_temp, void* ws, float* stats, void* stream);
+int m3l_op_dino_loss(const float* S, int P, const float* T, int Q, int B, int K, const float* center, float inv_ts, float inv_tt, const float* s_stats,
+                     const float* t_stats, void* ws, float* loss, void* stream);
+int m3l_op_dino_grad(int out_dtype, const float* S, int P, const float* T, int Q, int B, int K, const float* center, float inv_ts, float inv_tt,
+                     const float* s_stats, const float* t_stats, const float* dloss, void* dST, int ldr, void* stream);
+/* The teacher centre (DINOLoss.update_center / apply_center_update): pending[k] = sum over the rows of the teacher logits (per rank: all-reduce it
+ * over the ranks before it is applied), and, at the start of the NEXT step, center = center * momentum + (pending / count) * one_minus_momentum
+ * with count = rows * world size. */
+int m3l_op_dino_center_sum(const float* T, int rows, int K, float* pending, void* stream);
+int m3l_op_dino_center_apply(float* center, const float* pending, int K, float momentum, float one_minus_momentum, float count, void* stream);
+/* Moving average of `count` tensors in one launch per 128 tensors (update_moving_average): dst[i] = dst[i] * beta + one_minus_beta * src[i] over
+ * len[i] floats.  dst / src / len: host arrays (device pointers, element counts). */
+int m3l_op_ema(float* const* dst, const float* const* src, const long* len, int count, float beta, float one_minus_beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

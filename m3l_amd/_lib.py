@@ -149,6 +149,17 @@ _SIGS = {
     "m3l_op_attn_fwd_dh": (c_i, [c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i]),
     "m3l_op_attn_bwd_dh": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i]),
     "m3l_op_dropout_mask": (c_i, [C.c_float, C.c_uint64, c_i, c_i, C.c_long, c_i, c_p, c_p]),
+    "m3l_op_l2norm_fwd": (c_i, [c_i, c_p, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p]),
+    "m3l_op_l2norm_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, C.c_float, c_p, c_p]),
+    "m3l_op_weightnorm_fwd": (c_i, [c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "m3l_op_weightnorm_bwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "m3l_op_dino_ws_bytes": (c_sz, [c_i, c_i]),
+    "m3l_op_dino_rowstats": (c_i, [c_p, c_i, c_i, c_p, C.c_float, c_p, c_p, c_p]),
+    "m3l_op_dino_loss": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, C.c_float, C.c_float, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_op_dino_grad": (c_i, [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p, C.c_float, C.c_float, c_p, c_p, c_p, c_p, c_i, c_p]),
+    "m3l_op_dino_center_sum": (c_i, [c_p, c_i, c_i, c_p, c_p]),
+    "m3l_op_dino_center_apply": (c_i, [c_p, c_p, c_i, C.c_float, C.c_float, C.c_float, c_p]),
+    "m3l_op_ema": (c_i, [c_p, c_p, c_p, c_i, C.c_float, C.c_float, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

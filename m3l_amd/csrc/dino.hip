@@ -1,0 +1,429 @@
+// DINO self-distillation head and loss (include/m3l_amd.h "DINO step"): row L2 normalisation, weight normalisation of the prototype
+// layer, the fused centred-teacher / student cross-entropy over rows of K logits, the teacher centre and the multi-tensor moving average.
+//
+// The loss kernels are bandwidth kernels over a few hundred rows of K = 65536 floats.  Every row (or every sample's group of rows) is split
+// over several workgroups so that the 256 CUs have work; each workgroup leaves one partial in the workspace and a small second kernel adds
+// the partials in a fixed order: no float atomics anywhere, so loss and gradient are the same bits on every run.
+//   row statistics : online (max, sum exp) per thread over 16-byte loads -> wave shuffle -> LDS across the 4 waves -> partial; combine
+//   loss           : loss = 1/B sum_b ( Q sum_p lse_s[p,b] - 1/ts sum_k (sum_q T[q,b,k]) (sum_p S[p,b,k]) ), T = softmax of the centred teacher
+//   gradient       : dS[p,b,k] = g / (ts B) ( Q softmax(S[p,b,:] / ts)[k] - sum_q T[q,b,k] ), written k-major in the compute type of the two GEMMs
+#include <math.h>
+#include <string.h>
+
+#include "../../include/m3l_amd.h"
+#include "common.cuh"
+#include "kernels.h"
+
+#define DINO_THREADS 256
+#define DINO_MAX_SPLITS 64
+#define DINO_MAX_VIEWS 64
+
+// ---- reductions over a 256-thread workgroup (every thread calls) ------------------------------------------------------
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+}
+// (max, sum of exp(x - max)) pairs; an empty pair is (-inf, 0)
+__device__ __forceinline__ void ms_merge(float& m, float& s, float m2, float s2) {
+    const float M = fmaxf(m, m2);
+    if (M == -INFINITY) return;
+    s = s * __expf(m - M) + s2 * __expf(m2 - M);
+    m = M;
+}
+
+// ---- row L2 normalisation: y = x / max(||x||, eps)   (torch.nn.functional.normalize, p = 2) ---------------------------
+// one wave per row: the rows are the head's bottleneck vectors (a few hundred rows of 256)
+template <typename T>
+__global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* __restrict__ x, int M, int D, float eps, T* __restrict__ y, float* __restrict__ y32,
+                                                         float* __restrict__ norm) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const float* xr = x + (long)row * D;
+    float ss = 0.f;
+    for (int c = lane; c < D; c += 64) ss = fmaf(xr[c], xr[c], ss);
+    const float n = sqrtf(wave_sum(ss));
+    const float den = fmaxf(n, eps);
+    for (int c = lane; c < D; c += 64) {
+        const float v = xr[c] / den;
+        if (y) y[(long)row * D + c] = from_f32<T>(v);
+        if (y32) y32[(long)row * D + c] = v;
+    }
+    if (lane == 0 && norm) norm[row] = n;
+}
+// dx = (dy - y (y . dy)) / ||x||, or dy / eps where the norm was clamped (the clamp has no gradient)
+__global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ norm, int M,
+                                                         int D, float eps, float* __restrict__ dx) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const float* xr = x + (long)row * D;
+    const float* gr = dy + (long)row * D;
+    const float n = norm[row];
+    if (n < eps) {
+        for (int c = lane; c < D; c += 64) dx[(long)row * D + c] = gr[c] / eps;
+        return;
+    }
+    float dot = 0.f;
+    for (int c = lane; c < D; c += 64) dot = fmaf(xr[c], gr[c], dot);
+    dot = wave_sum(dot) / (n * n);                       // (y . dy) / ||x|| with y = x / ||x||, times 1 / ||x|| once more below
+    for (int c = lane; c < D; c += 64) dx[(long)row * D + c] = (gr[c] - xr[c] * dot) / n;
+}
+
+// ---- weight normalisation of the prototype layer: W[k] = v[k] * (g[k] / ||v[k]||)   (torch.nn.utils.weight_norm, dim 0) ----
+// one wave per row of v [K, D]
+template <typename T>
+__global__ __launch_bounds__(256) void weightnorm_fwd_kernel(const float* __restrict__ v, const float* __restrict__ g, int K, int D, T* __restrict__ W,
+                                                             float* __restrict__ vnorm) {
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (k >= K) return;
+    const float* vr = v + (long)k * D;
+    float ss = 0.f;
+    for (int c = lane; c < D; c += 64) ss = fmaf(vr[c], vr[c], ss);
+    const float n = sqrtf(wave_sum(ss));
+    const float sc = g[k] / n;
+    for (int c = lane; c < D; c += 64) W[(long)k * D + c] = from_f32<T>(vr[c] * sc);
+    if (lane == 0 && vnorm) vnorm[k] = n;
+}
+// dg[k] = (dW[k] . v[k]) / ||v[k]||,  dv[k] = g / ||v|| (dW[k] - v[k] (dW[k] . v[k]) / ||v||^2); one wave per row
+__global__ __launch_bounds__(256) void weightnorm_bwd_kernel(const float* __restrict__ dW, const float* __restrict__ v, const float* __restrict__ g,
+                                                             const float* __restrict__ vnorm, int K, int D, float* __restrict__ dv,
+                                                             float* __restrict__ dg) {
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (k >= K) return;
+    const float* vr = v + (long)k * D;
+    const float* wr = dW + (long)k * D;
+    float dot = 0.f;
+    for (int c = lane; c < D; c += 64) dot = fmaf(vr[c], wr[c], dot);
+    dot = wave_sum(dot);
+    const float n = vnorm[k], sc = g[k] / n, back = dot / (n * n);
+    for (int c = lane; c < D; c += 64) dv[(long)k * D + c] = sc * (wr[c] - vr[c] * back);
+    if (lane == 0) dg[k] = dot / n;
+}
+
+// ---- DINO loss ---------------------------------------------------------------------------------------------------------
+// how many workgroups share one row (or one sample's group of rows): enough for ~4 workgroups per CU, at least 2048 columns each
+static int dino_splits(int groups, int K) {
+    int s = cdiv(1024, groups);
+    const int max_s = K / 2048;
+    if (s > max_s) s = max_s;
+    if (s > DINO_MAX_SPLITS) s = DINO_MAX_SPLITS;
+    return s < 1 ? 1 : s;
+}
+static int dino_chunk(int K, int splits) { return 4 * cdiv(cdiv(K, splits), 4); }
+
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// partial (max, sum exp) of z = (x - center) * scale over columns [split * chunk, +chunk) of one row
+__global__ __launch_bounds__(256) void dino_rowstats_part_kernel(const float* __restrict__ X, int K, int chunk, const float* __restrict__ center, float scale,
+                                                                 float2* __restrict__ part) {
+    __shared__ float red_m[4], red_s[4];
+    const int row = blockIdx.y, sp = blockIdx.x, splits = gridDim.x;
+    const int k0 = sp * chunk, k1 = min(K, k0 + chunk);
+    const float* xr = X + (long)row * K;
+    float m = -INFINITY, s = 0.f;
+    for (int k = k0 + threadIdx.x * 4; k < k1; k += DINO_THREADS * 4) {
+        f32x4 z = ld4(xr + k);
+        if (center) z -= ld4(center + k);
+        z *= scale;
+        const float mx = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+        if (mx > m) { s *= __expf(m - mx); m = mx; }
+        s += (__expf(z[0] - m) + __expf(z[1] - m)) + (__expf(z[2] - m) + __expf(z[3] - m));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ms_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+    if ((threadIdx.x & 63) == 0) { red_m[threadIdx.x >> 6] = m; red_s[threadIdx.x >> 6] = s; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) ms_merge(m, s, red_m[w], red_s[w]);
+        part[(long)row * splits + sp] = make_float2(m, s);
+    }
+}
+// stats[row] = (max, log-sum-exp) from the row's partials, in split order
+__global__ void dino_rowstats_combine_kernel(const float2* __restrict__ part, int rows, int splits, float2* __restrict__ stats) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    float m = -INFINITY, s = 0.f;
+    for (int i = 0; i < splits; ++i) { const float2 p = part[(long)row * splits + i]; ms_merge(m, s, p.x, p.y); }
+    stats[row] = make_float2(m, m + logf(s));
+}
+
+// sum_q softmax((T[q,b,:] - center) / tt)[k .. k+3]
+__device__ __forceinline__ f32x4 teacher_sum4(const float* __restrict__ T, const float2* __restrict__ t_stats, const float* __restrict__ center, int Q, int B,
+                                              int b, int K, int k, float inv_tt) {
+    const f32x4 c = ld4(center + k);
+    f32x4 ts = {0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < Q; ++q) {
+        const f32x4 t = (ld4(T + ((long)q * B + b) * K + k) - c) * inv_tt;
+        const float lse = t_stats[q * B + b].y;
+        ts[0] += __expf(t[0] - lse); ts[1] += __expf(t[1] - lse); ts[2] += __expf(t[2] - lse); ts[3] += __expf(t[3] - lse);
+    }
+    return ts;
+}
+
+// cross term of sample b over one chunk of columns: sum_k (sum_q T) (sum_p S)
+__global__ __launch_bounds__(256) void dino_loss_part_kernel(const float* __restrict__ S, int P, const float* __restrict__ T, int Q, int B, int K, int chunk,
+                                                             const float* __restrict__ center, float inv_tt, const float2* __restrict__ t_stats,
+                                                             float* __restrict__ part) {
+    __shared__ float red[4];
+    const int b = blockIdx.y, sp = blockIdx.x, splits = gridDim.x;
+    const int k0 = sp * chunk, k1 = min(K, k0 + chunk);
+    float cross = 0.f;
+    for (int k = k0 + threadIdx.x * 4; k < k1; k += DINO_THREADS * 4) {
+        const f32x4 ts = teacher_sum4(T, t_stats, center, Q, B, b, K, k, inv_tt);
+        f32x4 ss = {0.f, 0.f, 0.f, 0.f};
+        for (int p = 0; p < P; ++p) ss += ld4(S + ((long)p * B + b) * K + k);
+        cross += (ts[0] * ss[0] + ts[1] * ss[1]) + (ts[2] * ss[2] + ts[3] * ss[3]);
+    }
+    cross = block_sum(cross, red);
+    if (threadIdx.x == 0) part[b * splits + sp] = cross;
+}
+// one wave: lane b adds its sample's terms in a fixed order, then the wave total
+__global__ __launch_bounds__(64) void dino_loss_final_kernel(const float* __restrict__ part, int splits, const float2* __restrict__ s_stats, int P, int Q, int B,
+                                                             float inv_ts, float* __restrict__ loss) {
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < B; b += 64) {
+        float lse = 0.f, cross = 0.f;
+        for (int p = 0; p < P; ++p) lse += s_stats[p * B + b].y;
+        for (int i = 0; i < splits; ++i) cross += part[b * splits + i];
+        acc += (float)Q * lse - inv_ts * cross;
+    }
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) loss[0] = acc / (float)B;
+}
+
+// dS^T[k, r] for r = p B + b, leading dimension ldr >= P B (columns beyond P B are written as zeros): the k-major form both backward GEMMs
+// of the prototype layer want — dW = dS^T x_n is an NT GEMM with K rows, dx_n = dS W a TN GEMM that reduces over K — so neither runs as
+// a 320-row problem with a 65536-long inner loop.  One workgroup per 32 columns: the teacher sums of every sample go to LDS once, then the
+// student rows pass through a 32 x 256 LDS tile in slabs of 256 rows, read along k (128-byte row segments) and written along r.
+#define DG_TK 32
+#define DG_TR 256
+template <typename TO>
+__global__ __launch_bounds__(256) void dino_grad_t_kernel(const float* __restrict__ S, int P, const float* __restrict__ T, int Q, int B, int K,
+                                                          const float* __restrict__ center, float inv_ts, float inv_tt, const float2* __restrict__ s_stats,
+                                                          const float2* __restrict__ t_stats, const float* __restrict__ dloss, TO* __restrict__ dST, int ldr) {
+    extern __shared__ float dg_lds[];
+    float* tsum = dg_lds;                                   // [B][DG_TK]
+    float (*tile)[DG_TR + 1] = reinterpret_cast<float (*)[DG_TR + 1]>(dg_lds + (size_t)B * DG_TK);      // [DG_TK][DG_TR + 1]
+    const int k0 = blockIdx.x * DG_TK, grp = threadIdx.x >> 3, j = threadIdx.x & 7, k = k0 + 4 * j, R = P * B;
+    const bool kin = k < K;                                 // K % 4 == 0: a thread's four columns are inside or outside together
+    const float gs = dloss[0] * inv_ts / (float)B, fq = (float)Q;
+    for (int b = grp; b < B; b += 32) {
+        f32x4 ts = {0.f, 0.f, 0.f, 0.f};
+        if (kin) ts = teacher_sum4(T, t_stats, center, Q, B, b, K, k, inv_tt);
+        *reinterpret_cast<f32x4*>(tsum + b * DG_TK + 4 * j) = ts;
+    }
+    __syncthreads();
+    for (int r0 = 0; r0 < ldr; r0 += DG_TR) {
+        for (int rl = grp; rl < DG_TR; rl += 32) {
+            const int r = r0 + rl;
+            f32x4 d = {0.f, 0.f, 0.f, 0.f};
+            if (r < R && kin) {
+                const f32x4 z = ld4(S + (long)r * K + k) * inv_ts;
+                const float lse = s_stats[r].y;
+                const f32x4 ts = *reinterpret_cast<const f32x4*>(tsum + (r % B) * DG_TK + 4 * j);
+                d[0] = gs * (fq * __expf(z[0] - lse) - ts[0]); d[1] = gs * (fq * __expf(z[1] - lse) - ts[1]);
+                d[2] = gs * (fq * __expf(z[2] - lse) - ts[2]); d[3] = gs * (fq * __expf(z[3] - lse) - ts[3]);
+            }
+            tile[4 * j + 0][rl] = d[0]; tile[4 * j + 1][rl] = d[1]; tile[4 * j + 2][rl] = d[2]; tile[4 * j + 3][rl] = d[3];
+        }
+        __syncthreads();
+        const int r = r0 + threadIdx.x;
+        if (r < ldr)
+            for (int kk = 0; kk < DG_TK && k0 + kk < K; ++kk) dST[(long)(k0 + kk) * ldr + r] = from_f32<TO>(tile[kk][threadIdx.x]);
+        __syncthreads();
+    }
+}
+
+// pending[k] = sum over rows of T[row, k] (fixed row order); 4 columns per thread
+__global__ __launch_bounds__(64) void dino_center_sum_kernel(const float* __restrict__ T, int rows, int K, float* __restrict__ pending) {
+    const int k = (blockIdx.x * 64 + threadIdx.x) * 4;
+    if (k >= K) return;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < rows; ++r) acc += ld4(T + (long)r * K + k);
+    *reinterpret_cast<f32x4*>(pending + k) = acc;
+}
+// center = center * m + (pending / count) * (1 - m), each product and the quotient rounded on its own as the tensor expression rounds them
+__global__ void dino_center_apply_kernel(float* __restrict__ center, const float* __restrict__ pending, int K, float momentum, float one_minus, float count) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    center[k] = center[k] * momentum + (pending[k] / count) * one_minus;
+}
+
+// ---- multi-tensor moving average: dst = dst * beta + (1 - beta) * src over up to M3L_EMA_MAX tensors per launch ---------------------
+#define M3L_EMA_MAX 128
+#define EMA_BLOCK_ELEMS 4096
+struct EmaPack {
+    float* dst[M3L_EMA_MAX];
+    const float* src[M3L_EMA_MAX];
+    long len[M3L_EMA_MAX];
+    int blk0[M3L_EMA_MAX + 1];      // first workgroup of each tensor
+    int count;
+};
+// (no contraction into an fma: each product is rounded on its own, as the tensor expression old * beta + (1 - beta) * new rounds it)
+__global__ __launch_bounds__(256) void ema_kernel(const EmaPack pk, float beta, float one_minus) {
+#pragma clang fp contract(off)
+    int lo = 0, hi = pk.count;      // the tensor this workgroup belongs to: last i with blk0[i] <= blockIdx.x
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pk.blk0[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+    }
+    float* d = pk.dst[lo];
+    const float* s = pk.src[lo];
+    const long n = pk.len[lo], e0 = (long)(blockIdx.x - pk.blk0[lo]) * EMA_BLOCK_ELEMS;
+    const long e1 = e0 + EMA_BLOCK_ELEMS < n ? e0 + EMA_BLOCK_ELEMS : n;
+    if ((((uintptr_t)d | (uintptr_t)s) & 15) == 0) {
+        for (long e = e0 + threadIdx.x * 4; e < e1; e += 1024) {
+            if (e + 4 <= e1) {
+                const f32x4 a = ld4(d + e), b = ld4(s + e);
+                f32x4 r;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) r[j] = a[j] * beta + one_minus * b[j];
+                *reinterpret_cast<f32x4*>(d + e) = r;
+            } else {
+                for (long t = e; t < e1; ++t) d[t] = d[t] * beta + one_minus * s[t];
+            }
+        }
+    } else {
+        for (long e = e0 + threadIdx.x; e < e1; e += 256) d[e] = d[e] * beta + one_minus * s[e];
+    }
+}
+
+// ======================================================= C ABI ==========================================================
+extern "C" {
+
+int m3l_op_l2norm_fwd(int out_dtype, const float* x, int M, int D, float eps, void* y, float* y32, float* norm, void* stream) {
+    M3L_CHECK(x && M > 0 && D > 0 && (y || y32) && (out_dtype == 0 || out_dtype == 1), "l2norm_fwd: bad arguments (M=%d D=%d dtype=%d)", M, D, out_dtype);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("l2norm_fwd", M, D, 0, 3.0 * M * D, st, (double)M * D * (4.0 + (y ? (out_dtype ? 2.0 : 4.0) : 0.0) + (y32 ? 4.0 : 0.0)));
+    if (out_dtype == 1)
+        l2norm_fwd_kernel<bf16><<<cdiv(M, 4), 256, 0, st>>>(x, M, D, eps, (bf16*)y, y32, norm);
+    else
+        l2norm_fwd_kernel<float><<<cdiv(M, 4), 256, 0, st>>>(x, M, D, eps, (float*)y, y32, norm);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_l2norm_bwd(const float* dy, const float* x, const float* norm, int M, int D, float eps, float* dx, void* stream) {
+    M3L_CHECK(dy && x && norm && dx && M > 0 && D > 0, "l2norm_bwd: bad arguments (M=%d D=%d)", M, D);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("l2norm_bwd", M, D, 0, 5.0 * M * D, st, 12.0 * M * D);
+    l2norm_bwd_kernel<<<cdiv(M, 4), 256, 0, st>>>(dy, x, norm, M, D, eps, dx);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_weightnorm_fwd(int dtype, const float* v, const float* g, int K, int D, void* W, float* vnorm, void* stream) {
+    M3L_CHECK(v && g && K > 0 && D > 0 && W && (dtype == 0 || dtype == 1), "weightnorm_fwd: bad arguments (K=%d D=%d dtype=%d)", K, D, dtype);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("weightnorm_fwd", K, D, 0, 3.0 * K * D, st, (double)K * D * (4.0 + (dtype ? 2.0 : 4.0)));
+    if (dtype == 1)
+        weightnorm_fwd_kernel<bf16><<<cdiv(K, 4), 256, 0, st>>>(v, g, K, D, (bf16*)W, vnorm);
+    else
+        weightnorm_fwd_kernel<float><<<cdiv(K, 4), 256, 0, st>>>(v, g, K, D, (float*)W, vnorm);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_weightnorm_bwd(const float* dW, const float* v, const float* g, const float* vnorm, int K, int D, float* dv, float* dg, void* stream) {
+    M3L_CHECK(dW && v && g && vnorm && dv && dg && K > 0 && D > 0, "weightnorm_bwd: bad arguments (K=%d D=%d)", K, D);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("weightnorm_bwd", K, D, 0, 5.0 * K * D, st, 12.0 * K * D);
+    weightnorm_bwd_kernel<<<cdiv(K, 4), 256, 0, st>>>(dW, v, g, vnorm, K, D, dv, dg);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t m3l_op_dino_ws_bytes(int rows, int K) {
+    (void)K;
+    return (size_t)(rows > 0 ? rows : 1) * DINO_MAX_SPLITS * sizeof(float2) + 256;
+}
+int m3l_op_dino_rowstats(const float* logits, int rows, int K, const float* center, float inv_temp, void* ws, float* stats, void* stream) {
+    M3L_CHECK(logits && ws && stats && rows > 0 && K > 0 && K % 4 == 0, "dino_rowstats: bad arguments (rows=%d K=%d; K must be a multiple of 4)", rows, K);
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = dino_splits(rows, K), chunk = dino_chunk(K, splits);
+    ProfScope prof("dino_rowstats", rows, K, splits, 6.0 * rows * K, st, 4.0 * rows * K + (center ? 4.0 * K : 0.0));
+    dino_rowstats_part_kernel<<<dim3(splits, rows), DINO_THREADS, 0, st>>>(logits, K, chunk, center, inv_temp, (float2*)ws);
+    dino_rowstats_combine_kernel<<<cdiv(rows, 64), 64, 0, st>>>((const float2*)ws, rows, splits, (float2*)stats);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+static int dino_check(const char* what, const void* S, int P, const void* T, int Q, int B, int K, const void* center, const void* a, const void* b) {
+    M3L_CHECK(S && T && center && a && b && P > 0 && Q > 0 && B > 0 && K > 0 && K % 4 == 0 && P <= DINO_MAX_VIEWS && Q <= DINO_MAX_VIEWS,
+              "%s: bad arguments (P=%d Q=%d B=%d K=%d; K must be a multiple of 4, at most %d views)", what, P, Q, B, K, DINO_MAX_VIEWS);
+    return 0;
+}
+int m3l_op_dino_loss(const float* S, int P, const float* T, int Q, int B, int K, const float* center, float inv_ts, float inv_tt, const float* s_stats,
+                     const float* t_stats, void* ws, float* loss, void* stream) {
+    if (dino_check("dino_loss", S, P, T, Q, B, K, center, s_stats, t_stats)) return 1;
+    M3L_CHECK(ws && loss, "dino_loss: null workspace or output");
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = dino_splits(B, K), chunk = dino_chunk(K, splits);
+    ProfScope prof("dino_loss", (long)(P + Q) * B, K, splits, (double)B * K * (P + 8.0 * Q + 2.0), st, 4.0 * (double)(P + Q) * B * K);
+    dino_loss_part_kernel<<<dim3(splits, B), DINO_THREADS, 0, st>>>(S, P, T, Q, B, K, chunk, center, inv_tt, (const float2*)t_stats, (float*)ws);
+    dino_loss_final_kernel<<<1, 64, 0, st>>>((const float*)ws, splits, (const float2*)s_stats, P, Q, B, inv_ts, loss);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_dino_grad(int out_dtype, const float* S, int P, const float* T, int Q, int B, int K, const float* center, float inv_ts, float inv_tt,
+                     const float* s_stats, const float* t_stats, const float* dloss, void* dST, int ldr, void* stream) {
+    if (dino_check("dino_grad", S, P, T, Q, B, K, center, s_stats, t_stats)) return 1;
+    M3L_CHECK(dloss && dST && (out_dtype == 0 || out_dtype == 1), "dino_grad: null gradient or bad dtype %d", out_dtype);
+    M3L_CHECK(ldr >= P * B, "dino_grad: leading dimension %d below the %d student rows", ldr, P * B);
+    const size_t lds = ((size_t)B * DG_TK + (size_t)DG_TK * (DG_TR + 1)) * sizeof(float);
+    M3L_CHECK(lds <= 65536, "dino_grad: batch %d needs %zu bytes of LDS for the teacher sums (at most 65536: B <= 255)", B, lds);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("dino_grad", (long)(P + Q) * B, K, 0, (double)B * K * (8.0 * P + 8.0 * Q), st,
+                   (double)K * (4.0 * (P + Q) * B + (out_dtype ? 2.0 : 4.0) * ldr));
+    if (out_dtype == 1)
+        dino_grad_t_kernel<bf16><<<cdiv(K, DG_TK), 256, lds, st>>>(S, P, T, Q, B, K, center, inv_ts, inv_tt, (const float2*)s_stats, (const float2*)t_stats,
+                                                                   dloss, (bf16*)dST, ldr);
+    else
+        dino_grad_t_kernel<float><<<cdiv(K, DG_TK), 256, lds, st>>>(S, P, T, Q, B, K, center, inv_ts, inv_tt, (const float2*)s_stats, (const float2*)t_stats,
+                                                                    dloss, (float*)dST, ldr);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_dino_center_sum(const float* T, int rows, int K, float* pending, void* stream) {
+    M3L_CHECK(T && pending && rows > 0 && K > 0 && K % 4 == 0, "dino_center_sum: bad arguments (rows=%d K=%d; K must be a multiple of 4)", rows, K);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("dino_center_sum", rows, K, 0, (double)rows * K, st, 4.0 * ((double)rows + 1.0) * K);
+    dino_center_sum_kernel<<<cdiv(K, 256), 64, 0, st>>>(T, rows, K, pending);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_dino_center_apply(float* center, const float* pending, int K, float momentum, float one_minus_momentum, float count, void* stream) {
+    M3L_CHECK(center && pending && K > 0 && count > 0.f, "dino_center_apply: bad arguments (K=%d count=%g)", K, (double)count);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("dino_center_apply", K, 0, 0, 4.0 * K, st, 12.0 * K);
+    dino_center_apply_kernel<<<cdiv(K, 256), 256, 0, st>>>(center, pending, K, momentum, one_minus_momentum, count);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_ema(float* const* dst, const float* const* src, const long* len, int count, float beta, float one_minus_beta, void* stream) {
+    M3L_CHECK(dst && src && len && count > 0, "ema: bad arguments (count=%d)", count);
+    hipStream_t st = (hipStream_t)stream;
+    for (int c0 = 0; c0 < count; c0 += M3L_EMA_MAX) {
+        EmaPack pk;
+        memset(&pk, 0, sizeof(pk));
+        double total = 0;
+        int blocks = 0;
+        for (int i = c0; i < count && i < c0 + M3L_EMA_MAX; ++i) {
+            M3L_CHECK(dst[i] && src[i] && len[i] > 0, "ema: tensor %d is null or empty", i);
+            const int j = pk.count++;
+            pk.dst[j] = dst[i]; pk.src[j] = src[i]; pk.len[j] = len[i];
+            pk.blk0[j] = blocks;
+            const long nb = (len[i] + EMA_BLOCK_ELEMS - 1) / EMA_BLOCK_ELEMS;
+            M3L_CHECK(blocks + nb < 2147483647L, "ema: too many elements for one launch");
+            blocks += (int)nb;
+            total += (double)len[i];
+        }
+        pk.blk0[pk.count] = blocks;
+        ProfScope prof("ema", pk.count, (long)total, 0, 3.0 * total, st, 12.0 * total);
+        ema_kernel<<<blocks, 256, 0, st>>>(pk, beta, one_minus_beta);
+        M3L_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+}  // extern "C"

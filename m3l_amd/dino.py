@@ -1,0 +1,421 @@
+"""DINO self-distillation pieces on the HIP kernels of m3l_amd/csrc/dino.hip: the projection head, the fused cross-entropy with its
+teacher centre, and the teacher's moving average.
+
+Drop-ins for `tactile_ssl/model/layers/dino_head.py` (DINOHead), `tactile_ssl/loss/dino_loss.py` (DINOLoss) and
+`tactile_ssl/utils/ema.py` (update_moving_average) of the reference: same constructor arguments, parameter / buffer names and shapes,
+seeded initial values and arithmetic.
+
+  head : Linear + GELU(erf) per hidden layer, Linear, row L2 normalisation (eps 1e-12), y = x_n W^T with W[k] = g[k] v[k] / ||v[k]||.
+         The MLP is the NT GEMM with its bias / GELU epilogues forwards and the TN GEMM, the column sums and the NT GEMM with the gelu'
+         epilogue backwards; L2 normalisation and weight normalisation are kernels of their own.
+  loss : sum_p sum_q mean_b( -sum_k T[q,b,k] log_softmax(S[p,b,:] / ts)[k] ), T = softmax((teacher - center) / tt), every (p, q) pair, not
+         divided by the number of pairs.  Because each row of T sums to one this is
+         mean_b( Q sum_p lse(S[p,b,:] / ts) - 1/ts sum_k (sum_q T[q,b,k]) (sum_p S[p,b,k]) ), and
+         dS[p,b,k] = g / (ts B) (Q softmax(S[p,b,:] / ts)[k] - sum_q T[q,b,k]): neither the P x Q products nor a log-softmax are stored.
+  centre : the column sums of this step's teacher logits wait in `pending` and enter the centre at the start of the NEXT step
+         (DINOLoss.apply_center_update), so the first step runs with a zero centre.
+
+There is no eager fallback: every number comes from a kernel, torch owns memory and the autograd tape.
+"""
+import ctypes as C
+import math
+
+import torch
+import torch.distributed as dist
+from torch import nn
+from torch.nn.init import trunc_normal_
+
+from . import _lib as L
+from .functional import DT_BF16, DT_F32, _f32c, _require_cuda, _stream, _ws, dtype_code, tdtype
+
+
+def _cast(x, dt, transposed=False):
+    """f32 (rows, cols) -> compute-type copy, or its transpose (cols, rows)."""
+    rows, cols = x.shape
+    if dt == DT_F32 and not transposed:
+        return x
+    out = torch.empty((cols, rows) if transposed else (rows, cols), dtype=tdtype(dt), device=x.device)
+    L.check(L.lib().m3l_op_prep_weight(dt, L.ptr(x), rows, cols, None if transposed else L.ptr(out), L.ptr(out) if transposed else None,
+                                       _stream()), "m3l_op_prep_weight")
+    return out
+
+
+def _gemm_nt(dt, a, w, M, N, K, bias=None, out_f32=None, out_t=None, out_pre=None, gelu_u=None, act=0):
+    L.check(L.lib().m3l_op_gemm_nt(dt, L.ptr(a), K, L.ptr(w), K, M, N, K, L.ptr(bias), None, L.ptr(out_f32), L.ptr(out_t), L.ptr(out_pre),
+                                   L.ptr(gelu_u), act, N, _stream()), "m3l_op_gemm_nt (DINO head)")
+
+
+def _gemm_tn(dt, y, x, M, N, K):
+    """dW (N, K) f32 = y^T x for y (M, N), x (M, K) in the compute type."""
+    lib = L.lib()
+    out = torch.empty(N, K, dtype=torch.float32, device=y.device)
+    nb = lib.m3l_op_gemm_tn_ws_bytes(M, N, K)
+    ws = _ws(nb, y.device)
+    L.check(lib.m3l_op_gemm_tn(dt, L.ptr(y), N, L.ptr(x), K, M, N, K, L.ptr(ws), nb, L.ptr(out), K, _stream()), "m3l_op_gemm_tn (DINO head)")
+    return out
+
+
+def _colsum(dt, y, M, N):
+    lib = L.lib()
+    out = torch.empty(N, dtype=torch.float32, device=y.device)
+    ws = _ws(lib.m3l_op_colsum_ws_bytes(N), y.device)
+    L.check(lib.m3l_op_colsum(dt, L.ptr(y), M, N, N, L.ptr(ws), L.ptr(out), _stream()), "m3l_op_colsum (DINO head)")
+    return out
+
+
+class HeadMlpFn(torch.autograd.Function):
+    """x (M, in) f32 -> (M, bottleneck) f32 through Linear [+ GELU] ... Linear.  params: weight_0, bias_0, weight_1, ... (bias None when
+    the head has none).  Between the layers the activations stay in the compute type; each hidden layer's pre-activation is kept for the
+    gelu' epilogue of the input-gradient GEMM of the layer above it."""
+
+    @staticmethod
+    def forward(ctx, dt, x, *params):
+        _require_cuda(x, "DINO head input")
+        x = _f32c(x)
+        M = x.shape[0]
+        ws_, bs_ = [_f32c(p) for p in params[0::2]], [_f32c(p) for p in params[1::2]]
+        n = len(ws_)
+        h, hs, us = _cast(x, dt), [], []
+        y = None
+        for i, (w, b) in enumerate(zip(ws_, bs_)):
+            N, K = w.shape
+            hs.append(h)
+            wt = _cast(w, dt)
+            if i < n - 1:
+                a = torch.empty(M, N, dtype=tdtype(dt), device=x.device)
+                u = torch.empty_like(a)
+                _gemm_nt(dt, h, wt, M, N, K, bias=b, out_t=a, out_pre=u, act=1)
+                us.append(u)
+                h = a
+            else:
+                y = torch.empty(M, N, dtype=torch.float32, device=x.device)
+                _gemm_nt(dt, h, wt, M, N, K, bias=b, out_f32=y)
+        ctx.saved = (dt, M, ws_, [b is not None for b in bs_], hs, us)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dt, M, ws_, has_b, hs, us = ctx.saved
+        d = _cast(_f32c(dy), dt)
+        grads = [None] * (2 * len(ws_))
+        dx = None
+        for i in range(len(ws_) - 1, -1, -1):
+            N, K = ws_[i].shape
+            grads[2 * i] = _gemm_tn(dt, d, hs[i], M, N, K)
+            if has_b[i]:
+                grads[2 * i + 1] = _colsum(dt, d, M, N)
+            if i > 0:
+                prev = torch.empty(M, K, dtype=tdtype(dt), device=d.device)
+                _gemm_nt(dt, d, _cast(ws_[i], dt, transposed=True), M, K, N, out_t=prev, gelu_u=us[i - 1])
+                d = prev
+            elif ctx.needs_input_grad[1]:
+                dx = torch.empty(M, K, dtype=torch.float32, device=d.device)
+                _gemm_nt(dt, d, _cast(ws_[i], dt, transposed=True), M, K, N, out_f32=dx)
+        return (None, dx) + tuple(grads)
+
+
+class L2NormFn(torch.autograd.Function):
+    """F.normalize(x, dim=-1, p=2, eps) for x (M, D) f32."""
+
+    @staticmethod
+    def forward(ctx, x, eps):
+        _require_cuda(x, "l2norm input")
+        x = _f32c(x)
+        M, D = x.shape
+        y = torch.empty_like(x)
+        norm = torch.empty(M, dtype=torch.float32, device=x.device)
+        L.check(L.lib().m3l_op_l2norm_fwd(DT_F32, L.ptr(x), M, D, float(eps), None, L.ptr(y), L.ptr(norm), _stream()), "m3l_op_l2norm_fwd")
+        ctx.saved = (x, norm, float(eps))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, norm, eps = ctx.saved
+        M, D = x.shape
+        dx = torch.empty_like(x)
+        L.check(L.lib().m3l_op_l2norm_bwd(L.ptr(_f32c(dy)), L.ptr(x), L.ptr(norm), M, D, eps, L.ptr(dx), _stream()), "m3l_op_l2norm_bwd")
+        return dx, None
+
+
+def _weightnorm(dt, v, g):
+    """v (K, D), g (K, 1) -> W (K, D) in the compute type and ||v[k]||."""
+    K, D = v.shape
+    w = torch.empty(K, D, dtype=tdtype(dt), device=v.device)
+    vnorm = torch.empty(K, dtype=torch.float32, device=v.device)
+    L.check(L.lib().m3l_op_weightnorm_fwd(dt, L.ptr(v), L.ptr(g), K, D, L.ptr(w), L.ptr(vnorm), _stream()), "m3l_op_weightnorm_fwd")
+    return w, vnorm
+
+
+def _pad_rows(x, rows):
+    """(M, n) -> (rows, n) with zero rows appended (the GEMMs want leading dimensions that are multiples of 8)."""
+    if x.shape[0] == rows:
+        return x
+    out = torch.zeros(rows, x.shape[1], dtype=x.dtype, device=x.device)
+    out[:x.shape[0]] = x
+    return out
+
+
+def _ld8(rows):
+    return (rows + 7) // 8 * 8
+
+
+def _last_layer_backward(dt, dST, xn, w, v, g, vnorm, need_dx):
+    """dS^T (K, ldr) in the compute type, x_n (M, D) f32, W (K, D) -> dx_n (M, D) f32, dv, dg.  Both products have K (the prototypes) as
+    their long side: dW = dS^T x_n is an NT GEMM with K rows, dx_n = dS W a TN GEMM that reduces over K in splits; then the weight-norm
+    backward."""
+    K, D = v.shape
+    M, ldr = xn.shape[0], dST.shape[1]
+    xnT = _cast(_pad_rows(xn, ldr), dt, transposed=True)              # (D, ldr)
+    dW = torch.empty(K, D, dtype=torch.float32, device=dST.device)
+    _gemm_nt(dt, dST, xnT, K, D, ldr, out_f32=dW)
+    dx = _gemm_tn(dt, dST, w, K, ldr, D)[:M] if need_dx else None
+    dv, dg = torch.empty_like(v), torch.empty_like(g)
+    L.check(L.lib().m3l_op_weightnorm_bwd(L.ptr(dW), L.ptr(v), L.ptr(g), L.ptr(vnorm), K, D, L.ptr(dv), L.ptr(dg), _stream()), "m3l_op_weightnorm_bwd")
+    return dx, dv, dg
+
+
+class WeightNormLinearFn(torch.autograd.Function):
+    """logits (M, K) f32 = x_n W^T, W = weight_norm(v, g): the prototype layer on its own (teacher pass, head used outside the fused loss)."""
+
+    @staticmethod
+    def forward(ctx, dt, xn, v, g):
+        _require_cuda(xn, "DINO head input")
+        xn, v, g = _f32c(xn), _f32c(v), _f32c(g)
+        M, D = xn.shape
+        K = v.shape[0]
+        w, vnorm = _weightnorm(dt, v, g)
+        y = torch.empty(M, K, dtype=torch.float32, device=xn.device)
+        _gemm_nt(dt, _cast(xn, dt), w, M, K, D, out_f32=y)
+        ctx.saved = (dt, xn, w, v, g, vnorm)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dt, xn, w, v, g, vnorm = ctx.saved
+        dST = _cast(_pad_rows(_f32c(dy), _ld8(xn.shape[0])), dt, transposed=True)
+        dx, dv, dg = _last_layer_backward(dt, dST, xn, w, v, g, vnorm, ctx.needs_input_grad[1])
+        return None, dx, dv, dg
+
+
+def _row_stats(logits, rows, K, center, inv_temp):
+    lib = L.lib()
+    stats = torch.empty(rows, 2, dtype=torch.float32, device=logits.device)
+    ws = _ws(lib.m3l_op_dino_ws_bytes(rows, K), logits.device)
+    L.check(lib.m3l_op_dino_rowstats(L.ptr(logits), rows, K, L.ptr(center), float(inv_temp), L.ptr(ws), L.ptr(stats), _stream()), "m3l_op_dino_rowstats")
+    return stats
+
+
+def _loss_forward(S, T, center, P, Q, B, K, inv_ts, inv_tt):
+    lib = L.lib()
+    s_stats = _row_stats(S, P * B, K, None, inv_ts)
+    t_stats = _row_stats(T, Q * B, K, center, inv_tt)
+    loss = torch.empty((), dtype=torch.float32, device=S.device)
+    ws = _ws(lib.m3l_op_dino_ws_bytes(B, K), S.device)
+    L.check(lib.m3l_op_dino_loss(L.ptr(S), P, L.ptr(T), Q, B, K, L.ptr(center), inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats), L.ptr(ws),
+                                 L.ptr(loss), _stream()), "m3l_op_dino_loss")
+    return loss, s_stats, t_stats
+
+
+def _loss_grad(dt, S, T, center, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats, dloss):
+    """-> dS^T (K, ldr) in the compute type, ldr = P B rounded up to a multiple of 8 (pad columns zero)."""
+    ldr = _ld8(P * B)
+    dST = torch.empty(K, ldr, dtype=tdtype(dt), device=S.device)
+    L.check(L.lib().m3l_op_dino_grad(dt, L.ptr(S), P, L.ptr(T), Q, B, K, L.ptr(center), inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats),
+                                     L.ptr(dloss), L.ptr(dST), ldr, _stream()), "m3l_op_dino_grad")
+    return dST
+
+
+def _loss_args(student, teacher, center):
+    _require_cuda(student, "student logits")
+    S, T = _f32c(student), _f32c(teacher)
+    if S.dim() != 3 or T.dim() != 3 or S.shape[1:] != T.shape[1:]:
+        raise ValueError(f"student (P, B, K) and teacher (Q, B, K) logits expected, got {tuple(S.shape)} and {tuple(T.shape)}")
+    c = _f32c(center).reshape(-1)
+    if c.numel() != S.shape[2]:
+        raise ValueError(f"center has {c.numel()} entries for K = {S.shape[2]}")
+    return S, T, c
+
+
+class DinoLossFn(torch.autograd.Function):
+    """loss(student (P, B, K), teacher logits (Q, B, K), center (K)) with an f32 gradient for the student logits: the loss on its own."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, center, student_temp, teacher_temp):
+        S, T, c = _loss_args(student, teacher, center)
+        (P, B, K), Q = S.shape, T.shape[0]
+        inv_ts, inv_tt = 1.0 / float(student_temp), 1.0 / float(teacher_temp)
+        loss, s_stats, t_stats = _loss_forward(S, T, c, P, Q, B, K, inv_ts, inv_tt)
+        ctx.saved = (S, T, c.clone(), P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        S, T, c, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
+        dST = _loss_grad(DT_F32, S, T, c, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
+        return dST.t()[:P * B].reshape(P, B, K), None, None, None, None
+
+
+class HeadLossFn(torch.autograd.Function):
+    """Prototype layer + loss in one node: x_n (P B, D) f32, v, g, teacher logits (Q, B, K), center -> loss.  The gradient kernel writes
+    dS^T in the compute type, which is what the two backward GEMMs of the prototype layer read; no f32 (P B, K) gradient exists."""
+
+    @staticmethod
+    def forward(ctx, dt, P, xn, v, g, teacher, center, student_temp, teacher_temp, keep):
+        _require_cuda(xn, "DINO head input")
+        xn, v, g = _f32c(xn), _f32c(v), _f32c(g)
+        M, D = xn.shape
+        K, B = v.shape[0], M // P
+        w, vnorm = _weightnorm(dt, v, g)
+        S = torch.empty(P, B, K, dtype=torch.float32, device=xn.device)
+        _gemm_nt(dt, _cast(xn, dt), w, M, K, D, out_f32=S)
+        S, T, c = _loss_args(S, teacher, center)
+        Q = T.shape[0]
+        inv_ts, inv_tt = 1.0 / float(student_temp), 1.0 / float(teacher_temp)
+        loss, s_stats, t_stats = _loss_forward(S, T, c, P, Q, B, K, inv_ts, inv_tt)
+        ctx.saved = (dt, xn, w, v, g, vnorm, S, T, c.clone(), P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats)
+        if keep is not None:
+            keep["student_logits"] = S
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dt, xn, w, v, g, vnorm, S, T, c, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
+        dST = _loss_grad(dt, S, T, c, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
+        dx, dv, dg = _last_layer_backward(dt, dST, xn, w, v, g, vnorm, ctx.needs_input_grad[2])
+        return None, None, dx, dv, dg, None, None, None, None, None
+
+
+class WeightNormLinear(nn.Module):
+    """`weight_norm(nn.Linear(in, out, bias=False))`: parameters weight_g (out, 1) and weight_v (out, in), registered in that order; weight_v
+    gets nn.Linear's default initial values, weight_g the row norms."""
+
+    def __init__(self, in_features, out_features):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        v = torch.empty(out_features, in_features)
+        nn.init.kaiming_uniform_(v, a=math.sqrt(5))
+        self.weight_g = nn.Parameter(v.norm(dim=1, keepdim=True))
+        self.weight_v = nn.Parameter(v)
+
+
+class DINOHead(nn.Module):
+    def __init__(self, in_dim, out_dim, use_bn=False, nlayers=3, hidden_dim=2048, bottleneck_dim=256, mlp_bias=True, compute_dtype="fp32"):
+        super().__init__()
+        if use_bn:
+            raise NotImplementedError("DINOHead(use_bn=True): BatchNorm1d between the head's layers has no kernel here; no configuration of "
+                                      "the reference sets it")
+        nlayers = max(nlayers, 1)
+        if nlayers == 1:
+            self.mlp = nn.Linear(in_dim, bottleneck_dim, bias=mlp_bias)
+        else:
+            layers = [nn.Linear(in_dim, hidden_dim, bias=mlp_bias), nn.GELU()]
+            for _ in range(nlayers - 2):
+                layers += [nn.Linear(hidden_dim, hidden_dim, bias=mlp_bias), nn.GELU()]
+            layers.append(nn.Linear(hidden_dim, bottleneck_dim, bias=mlp_bias))
+            self.mlp = nn.Sequential(*layers)
+        for m in self.modules():
+            if isinstance(m, nn.Linear):
+                trunc_normal_(m.weight, std=0.02)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        self.last_layer = WeightNormLinear(bottleneck_dim, out_dim)
+        self.last_layer.weight_g.data.fill_(1)
+        self.compute_dtype = compute_dtype
+        self.eps = 1e-12
+
+    def _linears(self):
+        return [self.mlp] if isinstance(self.mlp, nn.Linear) else [m for m in self.mlp if isinstance(m, nn.Linear)]
+
+    def normalized(self, x):
+        """(..., in_dim) -> (rows, bottleneck) L2-normalised bottleneck vectors."""
+        dt = dtype_code(self.compute_dtype)
+        params = []
+        for lin in self._linears():
+            params += [lin.weight, lin.bias]
+        y = HeadMlpFn.apply(dt, x.reshape(-1, x.shape[-1]), *params)
+        return L2NormFn.apply(y, self.eps)
+
+    def forward(self, x):
+        xn = self.normalized(x)
+        y = WeightNormLinearFn.apply(dtype_code(self.compute_dtype), xn, self.last_layer.weight_v, self.last_layer.weight_g)
+        return y.view(*x.shape[:-1], y.shape[-1])
+
+
+class DINOLoss(nn.Module):
+    """The loss with its centre.  `forward(student (P, B, K), teacher logits (Q, B, K), teacher_temp)` applies the pending centre update,
+    computes the loss against the centred teacher and leaves this step's teacher column sums pending (one-step delay, as the reference's
+    softmax_center_teacher / update_center pair).  With torch.distributed initialised the pending sums are all-reduced over
+    `process_group` and divided by rows x world size; on one rank they are the local sums."""
+
+    def __init__(self, out_dim, student_temp=0.1, center_momentum=0.9, process_group=None):
+        super().__init__()
+        self.student_temp = student_temp
+        self.center_momentum = center_momentum
+        self.register_buffer("center", torch.zeros(1, out_dim))
+        self.process_group = process_group
+        self.updated = True
+        self.reduce_handle = None
+        self.len_teacher_output = None
+        self.async_batch_center = None
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # the reference's centre becomes (1, 1, K) at its first update (it broadcasts against the (rows, 1, K) teacher output): same values
+        c = state_dict.get(prefix + "center")
+        if c is not None and c.dim() == 3 and c.shape[0] == 1 and tuple(c.shape[1:]) == tuple(self.center.shape):
+            state_dict[prefix + "center"] = c[0]
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    @torch.no_grad()
+    def apply_center_update(self):
+        if self.updated is False:
+            world = dist.get_world_size(self.process_group) if dist.is_initialized() else 1
+            if self.reduce_handle is not None:
+                self.reduce_handle.wait()
+                self.reduce_handle = None
+            K = self.center.shape[1]
+            if self.center.dtype != torch.float32 or not self.center.is_contiguous():
+                raise L.M3LError("DINOLoss.center must be a contiguous float32 buffer")
+            m = float(self.center_momentum)
+            L.check(L.lib().m3l_op_dino_center_apply(L.ptr(self.center), L.ptr(self.async_batch_center), K, m, 1 - m,
+                                                     float(self.len_teacher_output * world), _stream()), "m3l_op_dino_center_apply")
+            self.updated = True
+
+    @torch.no_grad()
+    def update_center(self, teacher_output):
+        _require_cuda(teacher_output, "teacher logits")
+        T = _f32c(teacher_output)
+        K = T.shape[-1]
+        rows = T.numel() // K
+        self.updated = False
+        self.len_teacher_output = rows
+        self.async_batch_center = torch.empty(1, K, dtype=torch.float32, device=T.device)
+        L.check(L.lib().m3l_op_dino_center_sum(L.ptr(T), rows, K, L.ptr(self.async_batch_center), _stream()), "m3l_op_dino_center_sum")
+        if dist.is_initialized():
+            self.reduce_handle = dist.all_reduce(self.async_batch_center, op=dist.ReduceOp.SUM, group=self.process_group, async_op=True)
+
+    def forward(self, student_logits, teacher_logits, teacher_temp):
+        self.apply_center_update()
+        loss = DinoLossFn.apply(student_logits, teacher_logits, self.center, self.student_temp, teacher_temp)
+        self.update_center(teacher_logits)
+        return loss
+
+
+@torch.no_grad()
+def update_moving_average(ma_model, current_model, beta):
+    """teacher_p = teacher_p * beta + (1 - beta) * student_p over the two modules' parameters() paired in order, in one multi-tensor launch."""
+    dst, src = [], []
+    for cur, ma in zip(current_model.parameters(), ma_model.parameters()):
+        if cur.shape != ma.shape:
+            raise ValueError(f"moving average over parameters of different shapes: {tuple(ma.shape)} and {tuple(cur.shape)}")
+        _require_cuda(ma, "moving-average parameter")
+        if ma.dtype != torch.float32 or cur.dtype != torch.float32 or not ma.is_contiguous() or not cur.is_contiguous():
+            raise L.M3LError("update_moving_average needs contiguous float32 parameters")
+        if ma.numel():
+            dst.append(ma)
+            src.append(cur)
+    if not dst:
+        return
+    n = len(dst)
+    lens = (C.c_long * n)(*[t.numel() for t in dst])
+    beta = float(beta)
+    L.check(L.lib().m3l_op_ema(L.ptr_array(dst), L.ptr_array(src), lens, n, beta, 1.0 - beta, _stream()), "m3l_op_ema")

@@ -1,0 +1,131 @@
+"""Time of one DINO self-distillation step at the reference configuration (EXPERIMENTS.md "DINO step").
+
+Encoder 256 wide / depth 4 / 8 heads / mlp 512 / one register token, 64x64 image at patch 8 and two 32x32 tactiles at patch 4, head
+256 -> 2048 -> 2048 -> 256 -> 65536, 2 global + 8 local masks (local scale (0.2, 0.48): the reference's 0.1 lower bound can draw a block
+that never passes), B = 32, in bf16 and in fp32.
+
+  1. ms per step of training_step + backward + AdamW + on_train_batch_end: mean over --steps steps after --warmup steps (CUDA events
+     around the whole loop, one synchronisation at the end; training_step itself reads the loss back each step, as the reference's does).
+  2. With the in-library event brackets (m3l_prof_*) on every launch for --prof-steps further steps: the share of the bracketed kernel
+     time spent in head + loss (the new kernels and every GEMM / column sum over the register-token rows or the prototypes), and for each loss
+     kernel its algorithmic bytes per launch and the rate they amount to against the 6.3 TB/s the HBM achieves.  The brackets serialise
+     the launches, so (2) apportions time and (1) is the step time.
+
+There is no pass mark: the parent commit cannot run this step.  Usage: python tools/bench_dino.py  (one JSON line on stdout)"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+from functools import partial
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import m3l_amd  # noqa: E402
+from m3l_amd import _lib as L  # noqa: E402
+
+DEV = "cuda:0"
+HBM_TBS = 6.3
+B, N_GLOBAL, N_LOCAL, K_OUT = 32, 2, 8, 65536
+NEW_KINDS = ("dino_", "l2norm", "weightnorm", "ema")
+
+
+def build(dt):
+    torch.manual_seed(0)
+    enc = m3l_amd.DinoVTT(image_size=64, tactile_size=32, image_patch_size=8, tactile_patch_size=4, dim=256, depth=4, heads=8, mlp_dim=512,
+                          num_tactiles=2, num_register_tokens=1, compute_dtype=dt)
+    model = m3l_amd.VTDINO(encoder=enc, dino_head=partial(m3l_amd.DINOHead, out_dim=K_OUT, use_bn=False, nlayers=3, hidden_dim=2048, bottleneck_dim=256),
+                           optim_cfg=partial(torch.optim.AdamW, lr=5e-4, weight_decay=0.05),
+                           lr_scheduler_cfg=lambda optimizer, T_max, steps_per_epoch: torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max, eta_min=1e-6),
+                           wd_scheduler_cfg=None,
+                           local_mask_scale=(0.2, 0.48), global_mask_scale=(0.48, 1.0), num_global_masks=N_GLOBAL, num_local_masks=N_LOCAL,
+                           min_keep_num_sensors=4, allow_mask_overlap=True, moving_average_decay=[0.994, 1.0], teacher_temp=[0.04, 0.07]).to(DEV)
+    opt, lr_entry, _ = model.configure_optimizers(100, 10)
+    model.lr_scheduler = lr_entry["scheduler"]
+    g = torch.Generator().manual_seed(1)
+    x = {"image": torch.rand(B, 3, 64, 64, generator=g).to(DEV), "tactile1": torch.rand(B, 3, 32, 32, generator=g).to(DEV),
+         "tactile2": torch.rand(B, 3, 32, 32, generator=g).to(DEV)}
+    return model, opt, x
+
+
+def step(model, opt, x, i):
+    opt.zero_grad(set_to_none=True)
+    out = model.training_step(x, i)
+    out["loss"].backward()
+    opt.step()
+    model.lr_scheduler.step()
+    model.on_train_batch_end(out, x, i)
+    return out["ssl_loss"]
+
+
+def is_head(name):
+    kind, dims = name.split("[")
+    dims = [int(d) for d in dims.rstrip("]").split("x")]
+    rows = {(N_GLOBAL + N_LOCAL) * B, N_GLOBAL * B}
+    # a head launch has the P B or Q B rows of the register tokens as its M, or the prototype count among its dimensions (the encoder's
+    # launches have thousands of token rows as M)
+    return kind.startswith(NEW_KINDS) or K_OUT in dims or (kind.startswith(("gemm", "wgrad", "colsum")) and dims[0] in rows)
+
+
+def classes():
+    lib = L.lib()
+    out = {}
+    for i in range(lib.m3l_prof_count()):
+        name = C.create_string_buffer(96)
+        ms, n, w, b = C.c_double(), C.c_long(), C.c_double(), C.c_double()
+        lib.m3l_prof_get(i, name, 96, C.byref(ms), C.byref(n), C.byref(w), C.byref(b))
+        if n.value:
+            out[name.value.decode()] = (ms.value, n.value, b.value)
+    return out
+
+
+def run(dt, steps, warmup, prof_steps):
+    model, opt, x = build(dt)
+    for i in range(warmup):
+        loss = step(model, opt, x, i)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(warmup, warmup + steps):
+        loss = step(model, opt, x, i)
+    e1.record()
+    torch.cuda.synchronize()
+    res = {"ms_per_step": round(e0.elapsed_time(e1) / steps, 3), "loss_last": round(loss, 4)}
+    L.lib().m3l_prof_begin(None, 1)
+    for i in range(prof_steps):
+        step(model, opt, x, warmup + steps + i)
+    torch.cuda.synchronize()
+    L.lib().m3l_prof_end()
+    cls = classes()
+    total = sum(v[0] for v in cls.values())
+    head = sum(v[0] for k, v in cls.items() if is_head(k))
+    res["bracketed_kernel_ms_per_step"] = round(total / prof_steps, 3)
+    res["head_loss_ms_per_step"] = round(head / prof_steps, 3)
+    res["head_loss_share"] = round(head / total, 3) if total else None
+    res["new_kernels"] = {k: {"us_per_launch": round(v[0] / v[1] * 1e3, 1), "launches_per_step": v[1] / prof_steps,
+                              "mb_per_launch": round(v[2] / v[1] / 1e6, 2), "tb_per_s": round(v[2] / v[0] / 1e9, 3),
+                              "of_hbm_rate": round(v[2] / v[0] / 1e9 / HBM_TBS, 3)}
+                          for k, v in sorted(cls.items()) if k.startswith(NEW_KINDS)}
+    res["head_gemms"] = {k: {"us_per_launch": round(v[0] / v[1] * 1e3, 1), "launches_per_step": v[1] / prof_steps}
+                         for k, v in sorted(cls.items()) if is_head(k) and not k.startswith(NEW_KINDS)}
+    res["loss_kernel_mb_per_step"] = round(sum(v[2] for k, v in cls.items() if k.startswith("dino_")) / prof_steps / 1e6, 1)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--prof-steps", type=int, default=3)
+    ap.add_argument("--dtypes", default="bf16,fp32")
+    a = ap.parse_args()
+    out = {"config": f"DinoVTT 256/4/8/512 + head 256-2048-2048-256-{K_OUT}, B={B}, {N_GLOBAL}+{N_LOCAL} views", "hbm_tb_per_s": HBM_TBS}
+    for dt in a.dtypes.split(","):
+        out[dt] = run(dt, a.steps, a.warmup, a.prof_steps)
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
