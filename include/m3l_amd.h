@@ -7,6 +7,20 @@
  *   - allocates nothing (the caller passes workspaces sized by the *_ws_bytes functions),
  *   - returns 0 on success, non-zero on error (text via m3l_last_error; nothing is thrown across the ABI),
  *   - takes device pointers unless a parameter says "host".
+ * Memory contract (tests/test_memory_contract_gpu.py holds every entry point to it, bit for bit):
+ *   - workspaces and outputs may hold ANYTHING on entry (stale NaN patterns included): whatever a kernel reads from them it, or an
+ *     earlier kernel of the same call, has written first, pad columns of padded leading dimensions included; a backward reads the
+ *     workspace its forward left behind and nothing else that is stale;
+ *   - gradient slots (`grads[i]`, dx / d_enc / d_dec) are OVERWRITTEN, never added to: a backward may be pointed straight at a flat
+ *     gradient buffer that was not zeroed.  A slot whose tensor takes no gradient in the call (NULL tensor, absent modality, the
+ *     modality tables when learned positions replace them) is left exactly as it was.  With learned_pos the position tables' slots
+ *     receive the batch sums (overwritten, like every other slot); the Python modules hand those two to autograd, which ADDS them
+ *     to the parameters' .grad, so in a GradSync flat buffer their span — and only theirs — must start zeroed;
+ *   - zeroed by the caller: `dst_zeroed` of m3l_scatter_tokens (rows no index names are not written) and the modality-table gradient
+ *     of m3l_tokens_assemble_bwd (it fills the rows of the image and of the sensors of this call; m3l_mae_step_bwd zeroes its own).
+ *     The prediction / target dumps of m3l_heads_loss_fwd2 are passed zeroed by the Python wrapper; treat that as required;
+ *   - no byte is written outside [ws, ws + *_ws_bytes(...)) and the documented extent of each output; with a caller-chosen leading
+ *     dimension (ldc, ldo) the columns between the logical width and the leading dimension are not touched.
  * dtype codes: 0 = f32 compute (parity path), 1 = bf16 compute (fp32 master weights, fp32 accumulation; the residual stream
  * of a stack is bf16 or fp32, m3l_set_residual_bf16).  dim_head (m3l_tf_cfg) is 32, 64 or 128; see m3l_tf_cfg.  Transformer dropout
  * (vit_pytorch's four nn.Dropout sites) is the *_dropout forms with an m3l_dropout descriptor; see "Dropout" below.
