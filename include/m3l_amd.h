@@ -459,6 +459,22 @@ int m3l_op_dino_grad(int out_dtype, const float* S, int P, const float* T, int Q
  * with count = rows * world size. */
 int m3l_op_dino_center_sum(const float* T, int rows, int K, float* pending, void* stream);
 int m3l_op_dino_center_apply(float* center, const float* pending, int K, float momentum, float one_minus_momentum, float count, void* stream);
+/* Sinkhorn-Knopp teacher targets (DINOLoss.sinkhorn_knopp_teacher), factored: with z = logits * inv_temp and w = 0, n_iterations times
+ *   u[k] = logsumexp over ALL ranks' rows of (z[r,k] - w[r]);   w[r] = logsumexp_k (z[r,k] - u[k]);   T[r,k] = exp(z[r,k] - u[k] - w[r])
+ * (the reference's constants sum_Q, K, B, world size only move a constant between u and w).  So T = softmax((logits - c) * inv_temp) with
+ * c = temp * u: c takes the centre's place in m3l_op_dino_rowstats / _loss / _grad, and the w pass is m3l_op_dino_rowstats(center = c).
+ *   m3l_op_sk_colstats   col_pairs[k] = (max_r, sum_r exp(. - max)) of logits[r,k] * inv_temp - row_stats[r].y over the local rows, [K, 2];
+ *                        row_stats: the [rows, 2] array of m3l_op_dino_rowstats, NULL for w = 0.  The rows are reduced in
+ *                        m3l_op_sk_row_splits(rows, K) ranges merged in range order; ws: m3l_op_sk_ws_bytes(rows, K) bytes.  K % 4 == 0.
+ *   m3l_op_sk_colcombine merges nparts sets of K pairs (parts [nparts, K, 2]: one rank's col_pairs, or every rank's gathered in rank order)
+ *                        in part order: center_out[k] = temp * (max + log(sum)); the same bits on every rank.
+ *   m3l_op_sk_probs      probs[r,k] = exp((logits[r,k] - center[k]) * inv_temp - row_stats[r].y), the distribution itself, for callers that
+ *                        want it stored (center may be NULL; rows <= 65535).  The training step never calls it. */
+int m3l_op_sk_row_splits(int rows, int K);
+size_t m3l_op_sk_ws_bytes(int rows, int K);
+int m3l_op_sk_colstats(const float* logits, int rows, int K, float inv_temp, const float* row_stats, void* ws, float* col_pairs, void* stream);
+int m3l_op_sk_colcombine(const float* parts, int nparts, int K, float temp, float* center_out, void* stream);
+int m3l_op_sk_probs(const float* logits, int rows, int K, const float* center, float inv_temp, const float* row_stats, float* probs, void* stream);
 /* Moving average of `count` tensors in one launch per 128 tensors (update_moving_average): dst[i] = dst[i] * beta + one_minus_beta * src[i] over
  * len[i] floats.  dst / src / len: host arrays (device pointers, element counts). */
 int m3l_op_ema(float* const* dst, const float* const* src, const long* len, int count, float beta, float one_minus_beta, void* stream);

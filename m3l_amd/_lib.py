@@ -159,6 +159,11 @@ _SIGS = {
     "m3l_op_dino_grad": (c_i, [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p, C.c_float, C.c_float, c_p, c_p, c_p, c_p, c_i, c_p]),
     "m3l_op_dino_center_sum": (c_i, [c_p, c_i, c_i, c_p, c_p]),
     "m3l_op_dino_center_apply": (c_i, [c_p, c_p, c_i, C.c_float, C.c_float, C.c_float, c_p]),
+    "m3l_op_sk_row_splits": (c_i, [c_i, c_i]),
+    "m3l_op_sk_ws_bytes": (c_sz, [c_i, c_i]),
+    "m3l_op_sk_colstats": (c_i, [c_p, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p]),
+    "m3l_op_sk_colcombine": (c_i, [c_p, c_i, c_i, C.c_float, c_p, c_p]),
+    "m3l_op_sk_probs": (c_i, [c_p, c_i, c_i, c_p, C.c_float, c_p, c_p, c_p]),
     "m3l_op_ema": (c_i, [c_p, c_p, c_p, c_i, C.c_float, C.c_float, c_p]),
 }
 

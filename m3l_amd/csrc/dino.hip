@@ -7,6 +7,7 @@
 //   row statistics : online (max, sum exp) per thread over 16-byte loads -> wave shuffle -> LDS across the 4 waves -> partial; combine
 //   loss           : loss = 1/B sum_b ( Q sum_p lse_s[p,b] - 1/ts sum_k (sum_q T[q,b,k]) (sum_p S[p,b,k]) ), T = softmax of the centred teacher
 //   gradient       : dS[p,b,k] = g / (ts B) ( Q softmax(S[p,b,:] / ts)[k] - sum_q T[q,b,k] ), written k-major in the compute type of the two GEMMs
+//   Sinkhorn-Knopp : the teacher's other target; a K-vector in the centre's place, from column passes (max, sum exp) down the rows
 #include <math.h>
 #include <string.h>
 
@@ -253,6 +254,84 @@ __global__ void dino_center_apply_kernel(float* __restrict__ center, const float
     center[k] = center[k] * momentum + (pending[k] / count) * one_minus;
 }
 
+// ---- Sinkhorn-Knopp teacher: the column pass ------------------------------------------------------------------------------------------
+// The iteration is a diagonal scaling of exp(L / tt); in the log domain, with z[r,k] = L[r,k] / tt and w = 0,
+//   repeat n: u[k] = logsumexp_r(z[r,k] - w[r]);  w[r] = logsumexp_k(z[r,k] - u[k]);      T[r,k] = exp(z[r,k] - u[k] - w[r])
+// so T = softmax((L - c) / tt) with c = tt u: the vector c stands where the centre stands in the row statistics, the loss and the gradient
+// kernels above, and the w pass IS dino_rowstats with c as its centre.  What is new is the u pass: a reduction DOWN the columns of a
+// row-major matrix.  A thread owns four adjacent columns (16-byte loads, a wave reads 1 KiB of one row) and keeps an online (max, sum)
+// pair per column; the rows are cut into ranges over grid.y so that 64 rows x 65536 columns still give ~1024 workgroups, each range
+// leaves K pairs in the workspace, and a second kernel merges them in range order — the same kernel that merges the ranks' pairs.
+#define SK_COLS (DINO_THREADS * 4)      // columns of one workgroup
+#define SK_MIN_ROWS 4                   // a row range is at least this long (four loads in flight per thread)
+#define SK_MAX_SPLITS 64
+
+// rows per range: ~1024 workgroups over the column blocks, at most SK_MAX_SPLITS ranges of at least SK_MIN_ROWS rows
+static int sk_rows_per_split(int rows, int K) {
+    int s = cdiv(1024, cdiv(K, SK_COLS));
+    const int max_s = cdiv(rows, SK_MIN_ROWS);
+    if (s > max_s) s = max_s;
+    if (s > SK_MAX_SPLITS) s = SK_MAX_SPLITS;
+    return cdiv(rows, s < 1 ? 1 : s);
+}
+
+// accurate e^x for the materialised probabilities: x log2(e) in two floats (the product's rounding and the constant's low part), v_exp_f32 on
+// the high one, a first-order correction for the low one.  |x| reaches 100 here and __expf's single product would cost 100 * 2^-24 relative.
+__device__ __forceinline__ float exp_acc(float x) {
+    const float hi = 1.44269502162933349609375f, lo = 1.925963033500011e-8f;
+    const float t = x * hi;
+    const float e = fmaf(x, hi, -t) + x * lo;
+    const float r = __builtin_amdgcn_exp2f(t);
+    return fmaf(r, e * 0.693147180559945f, r);
+}
+
+// part[range][k] = (max, sum exp(. - max)) over the rows of the range of z = X[r,k] * scale - w[r] (w = row_stats[r].y, or 0)
+__global__ __launch_bounds__(256) void sk_colstats_part_kernel(const float* __restrict__ X, int rows, int K, int rows_per, float scale,
+                                                               const float2* __restrict__ row_stats, float2* __restrict__ part) {
+    const int k = (blockIdx.x * DINO_THREADS + threadIdx.x) * 4;
+    if (k >= K) return;                                     // K % 4 == 0: the four columns are inside or outside together
+    const int r0 = blockIdx.y * rows_per, r1 = min(rows, r0 + rows_per);
+    f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int r = r0; r < r1; ++r) {
+        const float w = row_stats ? row_stats[r].y : 0.f;
+        const f32x4 z = ld4(X + (long)r * K + k) * scale - w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                       // z is finite, so M is: no (-inf) - (-inf)
+            const float M = fmaxf(m[j], z[j]);
+            s[j] = s[j] * __expf(m[j] - M) + __expf(z[j] - M);
+            m[j] = M;
+        }
+    }
+    f32x4* out = reinterpret_cast<f32x4*>(part + (long)blockIdx.y * K + k);
+    out[0] = f32x4{m[0], s[0], m[1], s[1]};
+    out[1] = f32x4{m[2], s[2], m[3], s[3]};
+}
+// merges nparts sets of K pairs in part order; FINAL: center[k] = temp * (max + log(sum)), else pairs[k] = (max, sum)
+template <bool FINAL>
+__global__ __launch_bounds__(256) void sk_merge_kernel(const float2* __restrict__ parts, int nparts, int K, float temp, float2* __restrict__ pairs,
+                                                       float* __restrict__ center) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    float m = -INFINITY, s = 0.f;
+    for (int i = 0; i < nparts; ++i) { const float2 p = parts[(long)i * K + k]; ms_merge(m, s, p.x, p.y); }
+    if (FINAL) center[k] = temp * (m + logf(s));
+    else pairs[k] = make_float2(m, s);
+}
+// probs[r, k] = exp((X[r,k] - center[k]) * scale - lse[r]); one rounding for the scaled difference minus lse
+__global__ __launch_bounds__(256) void sk_probs_kernel(const float* __restrict__ X, int K, const float* __restrict__ center, float scale,
+                                                       const float2* __restrict__ row_stats, float* __restrict__ probs) {
+    const int k = (blockIdx.x * DINO_THREADS + threadIdx.x) * 4, row = blockIdx.y;
+    if (k >= K) return;
+    f32x4 d = ld4(X + (long)row * K + k);
+    if (center) d -= ld4(center + k);
+    const float lse = row_stats[row].y;
+    f32x4 p;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = exp_acc(fmaf(d[j], scale, -lse));
+    *reinterpret_cast<f32x4*>(probs + (long)row * K + k) = p;
+}
+
 // ---- multi-tensor moving average: dst = dst * beta + (1 - beta) * src over up to M3L_EMA_MAX tensors per launch ---------------------
 #define M3L_EMA_MAX 128
 #define EMA_BLOCK_ELEMS 4096
@@ -397,6 +476,43 @@ int m3l_op_dino_center_apply(float* center, const float* pending, int K, float m
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("dino_center_apply", K, 0, 0, 4.0 * K, st, 12.0 * K);
     dino_center_apply_kernel<<<cdiv(K, 256), 256, 0, st>>>(center, pending, K, momentum, one_minus_momentum, count);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_sk_row_splits(int rows, int K) {
+    if (rows <= 0 || K <= 0) return 1;
+    return cdiv(rows, sk_rows_per_split(rows, K));
+}
+size_t m3l_op_sk_ws_bytes(int rows, int K) {
+    if (rows <= 0 || K <= 0) return 256;
+    return (size_t)m3l_op_sk_row_splits(rows, K) * (size_t)K * sizeof(float2) + 256;
+}
+int m3l_op_sk_colstats(const float* logits, int rows, int K, float inv_temp, const float* row_stats, void* ws, float* col_pairs, void* stream) {
+    M3L_CHECK(logits && ws && col_pairs && rows > 0 && K > 0 && K % 4 == 0, "sk_colstats: bad arguments (rows=%d K=%d; K must be a multiple of 4)", rows, K);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows_per = sk_rows_per_split(rows, K), splits = cdiv(rows, rows_per);
+    ProfScope prof("sk_colstats", rows, K, splits, 10.0 * rows * K, st, 4.0 * rows * K + 8.0 * K + (row_stats ? 8.0 * rows : 0.0));
+    // one range: its pairs are the result
+    sk_colstats_part_kernel<<<dim3(cdiv(K, SK_COLS), splits), DINO_THREADS, 0, st>>>(logits, rows, K, rows_per, inv_temp, (const float2*)row_stats,
+                                                                                     splits == 1 ? (float2*)col_pairs : (float2*)ws);
+    if (splits > 1) sk_merge_kernel<false><<<cdiv(K, 256), 256, 0, st>>>((const float2*)ws, splits, K, 0.f, (float2*)col_pairs, nullptr);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_sk_colcombine(const float* parts, int nparts, int K, float temp, float* center_out, void* stream) {
+    M3L_CHECK(parts && center_out && nparts > 0 && K > 0, "sk_colcombine: bad arguments (nparts=%d K=%d)", nparts, K);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sk_colcombine", nparts, K, 0, 4.0 * nparts * K, st, (8.0 * nparts + 4.0) * K);
+    sk_merge_kernel<true><<<cdiv(K, 256), 256, 0, st>>>((const float2*)parts, nparts, K, temp, nullptr, center_out);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_sk_probs(const float* logits, int rows, int K, const float* center, float inv_temp, const float* row_stats, float* probs, void* stream) {
+    M3L_CHECK(logits && row_stats && probs && rows > 0 && rows <= 65535 && K > 0 && K % 4 == 0,
+              "sk_probs: bad arguments (rows=%d K=%d; K must be a multiple of 4, at most 65535 rows)", rows, K);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sk_probs", rows, K, 0, 8.0 * rows * K, st, 8.0 * rows * K + (center ? 4.0 * K : 0.0));
+    sk_probs_kernel<<<dim3(cdiv(K, SK_COLS), rows), DINO_THREADS, 0, st>>>(logits, K, center, inv_temp, (const float2*)row_stats, probs);
     M3L_LAUNCH_CHECK();
     return 0;
 }

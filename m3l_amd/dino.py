@@ -14,6 +14,10 @@ seeded initial values and arithmetic.
          dS[p,b,k] = g / (ts B) (Q softmax(S[p,b,:] / ts)[k] - sum_q T[q,b,k]): neither the P x Q products nor a log-softmax are stored.
   centre : the column sums of this step's teacher logits wait in `pending` and enter the centre at the start of the NEXT step
          (DINOLoss.apply_center_update), so the first step runs with a zero centre.
+  Sinkhorn-Knopp : the teacher's other target (`centering="sinkhorn_knopp"`).  The reference scales exp(T / tt) to unit column and row sums
+         n times; in the log domain that is u[k] = logsumexp_r(z[r,k] - w[r]), w[r] = logsumexp_k(z[r,k] - u[k]) from w = 0, and the
+         targets are softmax((T - c) / tt) with c = tt u: one K-vector in the centre's place, no assignment matrix.  The u pass is the
+         column kernel (m3l_op_sk_colstats / m3l_op_sk_colcombine), the w pass the row statistics the loss computes anyway.
 
 There is no eager fallback: every number comes from a kernel, torch owns memory and the autograd tape.
 """
@@ -205,6 +209,27 @@ def _row_stats(logits, rows, K, center, inv_temp):
     return stats
 
 
+def _gather_col_pairs(pairs, group=None):
+    """(K, 2) column pairs of this rank -> (world, K, 2), every rank's in rank order (the same tensor on every rank).  Device-agnostic."""
+    world = dist.get_world_size(group)
+    out = torch.empty((world,) + tuple(pairs.shape), dtype=pairs.dtype, device=pairs.device)
+    dist.all_gather(list(out.unbind(0)), pairs.contiguous(), group=group)
+    return out
+
+
+def _probs(logits, rows, K, center, inv_temp, stats):
+    out = torch.empty(rows, K, dtype=torch.float32, device=logits.device)
+    L.check(L.lib().m3l_op_sk_probs(L.ptr(logits), rows, K, L.ptr(center), float(inv_temp), L.ptr(stats), L.ptr(out), _stream()), "m3l_op_sk_probs")
+    return out
+
+
+def _teacher_rows(teacher_output):
+    _require_cuda(teacher_output, "teacher logits")
+    T = _f32c(teacher_output)
+    K = T.shape[-1]
+    return T.reshape(-1, K), T.numel() // K, K
+
+
 def _loss_forward(S, T, center, P, Q, B, K, inv_ts, inv_tt):
     lib = L.lib()
     s_stats = _row_stats(S, P * B, K, None, inv_ts)
@@ -345,7 +370,9 @@ class DINOLoss(nn.Module):
     """The loss with its centre.  `forward(student (P, B, K), teacher logits (Q, B, K), teacher_temp)` applies the pending centre update,
     computes the loss against the centred teacher and leaves this step's teacher column sums pending (one-step delay, as the reference's
     softmax_center_teacher / update_center pair).  With torch.distributed initialised the pending sums are all-reduced over
-    `process_group` and divided by rows x world size; on one rank they are the local sums."""
+    `process_group` and divided by rows x world size; on one rank they are the local sums.  `forward(..., centering="sinkhorn_knopp")`
+    takes the Sinkhorn-Knopp targets instead and leaves the centre alone; `softmax_center_teacher` / `sinkhorn_knopp_teacher` return the two
+    target distributions themselves, as the reference's methods of those names do."""
 
     def __init__(self, out_dim, student_temp=0.1, center_momentum=0.9, process_group=None):
         super().__init__()
@@ -393,7 +420,52 @@ class DINOLoss(nn.Module):
         if dist.is_initialized():
             self.reduce_handle = dist.all_reduce(self.async_batch_center, op=dist.ReduceOp.SUM, group=self.process_group, async_op=True)
 
-    def forward(self, student_logits, teacher_logits, teacher_temp):
+    @torch.no_grad()
+    def sinkhorn_knopp_center(self, teacher_logits, teacher_temp, n_iterations=3):
+        """The (K,) float32 vector c with sinkhorn_knopp_teacher(T) = softmax((T - c) / teacher_temp): `n_iterations` column passes over the
+        rows of every rank (each rank's pairs all-gathered over `process_group` and merged in rank order) and n_iterations - 1 local row
+        passes.  Pass it where the loss functions take the centre."""
+        if n_iterations < 1:
+            raise ValueError(f"sinkhorn_knopp: n_iterations = {n_iterations}; without a column normalisation the result is no distribution")
+        T, rows, K = _teacher_rows(teacher_logits)
+        lib = L.lib()
+        temp, inv_temp = float(teacher_temp), 1.0 / float(teacher_temp)
+        center = torch.empty(K, dtype=torch.float32, device=T.device)
+        pairs = torch.empty(K, 2, dtype=torch.float32, device=T.device)
+        ws = _ws(lib.m3l_op_sk_ws_bytes(rows, K), T.device)
+        stats = None
+        for it in range(n_iterations):
+            L.check(lib.m3l_op_sk_colstats(L.ptr(T), rows, K, inv_temp, L.ptr(stats), L.ptr(ws), L.ptr(pairs), _stream()), "m3l_op_sk_colstats")
+            parts = _gather_col_pairs(pairs, self.process_group) if dist.is_initialized() else pairs
+            L.check(lib.m3l_op_sk_colcombine(L.ptr(parts), parts.numel() // (2 * K), K, temp, L.ptr(center), _stream()), "m3l_op_sk_colcombine")
+            if it < n_iterations - 1:
+                stats = _row_stats(T, rows, K, center, inv_temp)
+        return center
+
+    @torch.no_grad()
+    def sinkhorn_knopp_teacher(self, teacher_output, teacher_temp, n_iterations=3):
+        """The reference's return value: the assignment as probabilities, (rows, K) float32 with the leading dimensions flattened to rows."""
+        center = self.sinkhorn_knopp_center(teacher_output, teacher_temp, n_iterations)
+        T, rows, K = _teacher_rows(teacher_output)
+        inv_temp = 1.0 / float(teacher_temp)
+        return _probs(T, rows, K, center, inv_temp, _row_stats(T, rows, K, center, inv_temp))
+
+    @torch.no_grad()
+    def softmax_center_teacher(self, teacher_output, teacher_temp):
+        """softmax((teacher_output - center) / teacher_temp) after the pending centre update, (rows, K) float32."""
+        self.apply_center_update()
+        T, rows, K = _teacher_rows(teacher_output)
+        inv_temp = 1.0 / float(teacher_temp)
+        center = _f32c(self.center).reshape(-1)
+        return _probs(T, rows, K, center, inv_temp, _row_stats(T, rows, K, center, inv_temp))
+
+    def forward(self, student_logits, teacher_logits, teacher_temp, centering="centering", n_iterations=3):
+        if centering == "sinkhorn_knopp":
+            # the centre, `updated` and the pending sums stay as they are: this branch of the reference never calls update_center
+            center = self.sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations)
+            return DinoLossFn.apply(student_logits, teacher_logits, center, self.student_temp, teacher_temp)
+        if centering != "centering":
+            raise ValueError(f"DINOLoss.forward: centering must be 'centering' or 'sinkhorn_knopp', got {centering!r}")
         self.apply_center_update()
         loss = DinoLossFn.apply(student_logits, teacher_logits, self.center, self.student_temp, teacher_temp)
         self.update_center(teacher_logits)

@@ -7,6 +7,10 @@ every view goes through the head's MLP and L2 normalisation in one batch of P x 
 and the prototype layer, the centred-teacher cross-entropy and their backward are one autograd node on the kernels of csrc/dino.hip
 (m3l_amd/dino.py).  The block-mask sampler runs on the CPU with `self.generator` and returns the reference's indices bit for bit.
 
+`centering="sinkhorn_knopp"` (a trailing keyword the reference's VTDINO does not have; its DINOv2 algorithm does) takes the Sinkhorn-Knopp
+assignment of the teacher logits as the targets: DINOLoss.sinkhorn_knopp_center gives the K-vector that stands in the centre's place, and
+the centre is neither applied nor updated.
+
 Not built: online probes and their logging (a non-empty `online_probes` is refused).
 """
 import copy
@@ -24,8 +28,11 @@ class VTDINO(nn.Module):
     def __init__(self, encoder, dino_head, optim_cfg, lr_scheduler_cfg, wd_scheduler_cfg, online_probes=None, online_probes_lrs=[],
                  local_mask_scale=(0.2, 0.8), global_mask_scale=(0.2, 0.8), num_global_masks=1, num_local_masks=4, min_keep_num_sensors=4,
                  allow_mask_overlap=False, moving_average_decay=0.99, teacher_temp=(0.04, 0.07), teacher_warmup_epochs=10, use_momentum=True,
-                 log_freq_reconstruction=1000):
+                 log_freq_reconstruction=1000, centering="centering"):
         super().__init__()
+        if centering not in ("centering", "sinkhorn_knopp"):
+            raise ValueError(f"VTDINO(centering=...): 'centering' or 'sinkhorn_knopp' expected, got {centering!r}")
+        self.centering = centering
         if online_probes:
             raise NotImplementedError("VTDINO(online_probes=...): online probes and their logging are not part of this package")
         assert len(online_probes_lrs) == 0, "Number of online probes should match the number of learning rates"
@@ -187,11 +194,16 @@ class VTDINO(nn.Module):
         with torch.no_grad():
             t_rows = self._register_rows(teacher["backbone"], x, global_masks)
             t_logits = teacher["dino_head"](t_rows).view(Q, B, -1)
-            self.dino_loss.apply_center_update()
+            if self.centering == "sinkhorn_knopp":      # the targets' K-vector stands where the centre stands; the centre itself is never updated
+                center = self.dino_loss.sinkhorn_knopp_center(t_logits.view(Q * B, -1), self.current_teacher_temp)
+            else:
+                self.dino_loss.apply_center_update()
+                center = self.dino_loss.center
         loss = HeadLossFn.apply(Fn.dtype_code(self.compute_dtype), P, xn, head.last_layer.weight_v, head.last_layer.weight_g, t_logits,
-                                self.dino_loss.center, self.dino_loss.student_temp, self.current_teacher_temp, self.last)
+                                center, self.dino_loss.student_temp, self.current_teacher_temp, self.last)
         self.last["teacher_logits"] = t_logits
-        self.dino_loss.update_center(t_logits)
+        if self.centering != "sinkhorn_knopp":
+            self.dino_loss.update_center(t_logits)
         return loss
 
     def training_step(self, batch, batch_idx):
