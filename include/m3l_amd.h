@@ -475,6 +475,25 @@ size_t m3l_op_sk_ws_bytes(int rows, int K);
 int m3l_op_sk_colstats(const float* logits, int rows, int K, float inv_temp, const float* row_stats, void* ws, float* col_pairs, void* stream);
 int m3l_op_sk_colcombine(const float* parts, int nparts, int K, float temp, float* center_out, void* stream);
 int m3l_op_sk_probs(const float* logits, int rows, int K, const float* center, float inv_temp, const float* row_stats, float* probs, void* stream);
+/* KoLeo regulariser (tactile_ssl/loss/koleo_loss.py, Sablayrolles et al. 2018) over `groups` independent sets of n rows each, x [groups * n, D],
+ * float32 throughout:  y_i = x_i / max(||x_i||, eps);  I(i) = argmax_{j != i, same group} y_i . y_j, the lowest j when products are equal (a
+ * single row is its own neighbour);  d_i = ||y_i - y_I(i) + 1e-8||_2 from the explicit difference (nn.PairwiseDistance(2, eps=1e-8));
+ *   loss[0] = sum over groups of -(1/n) sum_i log(d_i + eps).
+ * The products run on the f32 MFMA in 128 x 128 tiles through LDS with a running (max, argmax) per row; the n x n matrix is never stored.
+ * Forward, 3 launches: normalise; search (one (max, argmax) pair per row and column range into ws); merge + distances + loss.  Each group's sum
+ * is formed in an order that depends on n alone and the groups are added in a fixed order, so a group contributes the same bits alone or among
+ * others.  Outputs: y [groups * n, D], norm [groups * n] (un-clamped), nn [groups * n] the neighbour's index INSIDE its group, nn64 the same
+ * as int64 (may be NULL), dist [groups * n].
+ * Backward, 1 launch, a gather: with g_i = -dloss[0] / (n (d_i + eps)) and u_i = (y_i - y_I(i) + 1e-8) / d_i, the wave that owns row j adds
+ *   dy_j = g_j u_j - sum_{i : I(i) = j} g_i u_i   in ascending i,
+ * then dx_j as m3l_op_l2norm_bwd (dy_j / eps where the norm was clamped).  I is a constant for the gradient.  dloss: device scalar.
+ * Shapes: 1 <= n <= 4096, 1 <= D <= 1024 (any D, any row alignment), groups * n <= 65535; anything else is an error and nothing is written.
+ * ws: m3l_op_koleo_ws_bytes(groups, n, D) bytes. */
+size_t m3l_op_koleo_ws_bytes(int groups, int n, int D);
+int m3l_op_koleo_fwd(const float* x, int groups, int n, int D, float eps, void* ws, float* y, float* norm, int* nn, long long* nn64, float* dist,
+                     float* loss, void* stream);
+int m3l_op_koleo_bwd(const float* dloss, const float* x, const float* y, const float* norm, const int* nn, const float* dist, int groups, int n, int D,
+                     float eps, float* dx, void* stream);
 /* Moving average of `count` tensors in one launch per 128 tensors (update_moving_average): dst[i] = dst[i] * beta + one_minus_beta * src[i] over
  * len[i] floats.  dst / src / len: host arrays (device pointers, element counts). */
 int m3l_op_ema(float* const* dst, const float* const* src, const long* len, int count, float beta, float one_minus_beta, void* stream);

@@ -164,6 +164,9 @@ _SIGS = {
     "m3l_op_sk_colstats": (c_i, [c_p, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p]),
     "m3l_op_sk_colcombine": (c_i, [c_p, c_i, c_i, C.c_float, c_p, c_p]),
     "m3l_op_sk_probs": (c_i, [c_p, c_i, c_i, c_p, C.c_float, c_p, c_p, c_p]),
+    "m3l_op_koleo_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "m3l_op_koleo_fwd": (c_i, [c_p, c_i, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_op_koleo_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, C.c_float, c_p, c_p]),
     "m3l_op_ema": (c_i, [c_p, c_p, c_p, c_i, C.c_float, C.c_float, c_p]),
 }
 

@@ -8,6 +8,7 @@
 //   loss           : loss = 1/B sum_b ( Q sum_p lse_s[p,b] - 1/ts sum_k (sum_q T[q,b,k]) (sum_p S[p,b,k]) ), T = softmax of the centred teacher
 //   gradient       : dS[p,b,k] = g / (ts B) ( Q softmax(S[p,b,:] / ts)[k] - sum_q T[q,b,k] ), written k-major in the compute type of the two GEMMs
 //   Sinkhorn-Knopp : the teacher's other target; a K-vector in the centre's place, from column passes (max, sum exp) down the rows
+//   KoLeo          : float32 nearest neighbour of every row inside its group on the f32 MFMA, -mean log distance; the backward is a gather
 #include <math.h>
 #include <string.h>
 
@@ -332,6 +333,300 @@ __global__ __launch_bounds__(256) void sk_probs_kernel(const float* __restrict__
     *reinterpret_cast<f32x4*>(probs + (long)row * K + k) = p;
 }
 
+// ---- KoLeo regulariser (tactile_ssl/loss/koleo_loss.py): nearest neighbour of every row inside its group, in float32 --------------------
+//   y_i = x_i / max(||x_i||, eps);  I(i) = argmax_{j != i} y_i . y_j (lowest j on a tie);  d_i = ||y_i - y_I(i) + 1e-8||;
+//   loss = sum over groups of -(1/n) sum_i log(d_i + eps)
+// forward, three launches: (1) normalise (one wave per row; it also clears the counter of launch 3); (2) the search: a workgroup owns 128 rows
+// and a range of 128-column tiles of its group, multiplies them on the f32 MFMA through LDS in chunks of 16 along D and keeps a running
+// (max, argmax) per row — the n x n products never leave the registers — and leaves one (max, argmax) pair per row and column range in the
+// workspace; (3) one wave per row merges the pairs in range order, forms d_i from the explicit difference and log(d_i + eps); the workgroup
+// that arrives last adds the workgroups' partial sums in a fixed order (an integer arrival counter, no float atomic).
+// backward, one launch: the wave that owns row j scans the group's neighbour list (in LDS) and adds the terms of the rows that chose j in
+// ascending i — a gather, so the bits do not depend on scheduling — then applies the normalisation backward of l2norm_bwd_kernel.
+#define KL_TM 128            // rows of a workgroup
+#define KL_TN 128            // columns of one tile
+#define KL_KC 16             // chunk along D
+#define KL_LD (KL_KC + 1)    // LDS row stride in floats: the 32 rows a half-wave reads at one k fall into 32 different banks
+#define KL_MAX_N 4096
+#define KL_MAX_D 1024
+#define KL_MAX_ROWS 65535
+#define KL_PD_EPS 1e-8f      // nn.PairwiseDistance(2, eps=1e-8) adds it to every component of the difference
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+// column ranges per row tile: enough workgroups for ~2 per CU, never more than there are column tiles
+static int koleo_splits(int groups, int n) {
+    const int tiles = cdiv(n, KL_TN);
+    int s = cdiv(512, (long)groups * cdiv(n, KL_TM));
+    if (s > tiles) s = tiles;
+    return s < 1 ? 1 : s;
+}
+struct KoleoWs {
+    size_t part_off, gloss_off, pair_off, bytes;      // [0, 256): the arrival counter
+    int splits;
+};
+static KoleoWs koleo_ws(int groups, int n) {
+    KoleoWs w;
+    w.splits = koleo_splits(groups, n);
+    w.part_off = 256;                                                                   // float [groups][cdiv(n, 4)]
+    w.gloss_off = w.part_off + ((size_t)groups * cdiv(n, 4) * sizeof(float) + 255) / 256 * 256;     // float [groups]
+    w.pair_off = w.gloss_off + ((size_t)groups * sizeof(float) + 255) / 256 * 256;      // (float, int) [groups * n][splits]
+    w.bytes = w.pair_off + (size_t)groups * n * w.splits * 8;
+    return w;
+}
+
+__global__ __launch_bounds__(256) void koleo_norm_kernel(const float* __restrict__ x, int M, int D, float eps, float* __restrict__ y, float* __restrict__ norm,
+                                                         unsigned* __restrict__ counter) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) counter[0] = 0u;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const float* xr = x + (long)row * D;
+    float ss = 0.f;
+    for (int c = lane; c < D; c += 64) ss = fmaf(xr[c], xr[c], ss);
+    const float n = sqrtf(wave_sum(ss));
+    const float den = fmaxf(n, eps);
+    for (int c = lane; c < D; c += 64) y[(long)row * D + c] = xr[c] / den;
+    if (lane == 0) norm[row] = n;
+}
+
+// four floats of row `r` of the group from column k (zeros outside the n x D matrix)
+template <bool VEC>
+__device__ __forceinline__ f32x4 koleo_ld(const float* __restrict__ yg, int r, int n, int k, int D) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (r < n) {
+        const float* p = yg + (long)r * D + k;
+        if (VEC) {                                          // D % 4 == 0: the four columns are inside or outside together, 16-byte aligned
+            if (k < D) v = *reinterpret_cast<const f32x4*>(p);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (k + j < D) v[j] = p[j];
+        }
+    }
+    return v;
+}
+
+// grid (row tiles, column ranges, groups).  4 waves as 2 x 2, each 64 rows x 64 columns of the tile: 2 x 2 MFMA 32x32x2 accumulators.
+// Accumulator register r of lane l holds row 8 (r / 4) + 4 (l / 32) + r % 4 and column l % 32 of its 32 x 32 block.
+template <bool VEC>
+__global__ __launch_bounds__(256) void koleo_search_kernel(const float* __restrict__ y, int n, int D, int tiles_per, float2* __restrict__ pairs, int splits) {
+    __shared__ float As[KL_TM * KL_LD], Bs[KL_TN * KL_LD];
+    __shared__ float red_v[2][KL_TM];
+    __shared__ int red_i[2][KL_TM];
+    const int g = blockIdx.z, row0 = blockIdx.x * KL_TM, sp = blockIdx.y;
+    const float* yg = y + (long)g * n * D;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int l32 = lane & 31, lh = lane >> 5;
+    const int ntiles = (n + KL_TN - 1) / KL_TN, t0 = sp * tiles_per, t1 = min(ntiles, t0 + tiles_per);
+    const int lr = tid >> 2, lk = (tid & 3) * 4;            // this thread stages rows lr and lr + 64 of each operand, columns lk .. lk + 3 of the chunk
+
+    float best_v[2][16];
+    int best_i[2][16];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { best_v[a][r] = -INFINITY; best_i[a][r] = 0x7fffffff; }
+
+    for (int t = t0; t < t1; ++t) {
+        const int col0 = t * KL_TN;
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+        f32x4 ga0 = koleo_ld<VEC>(yg, row0 + lr, n, lk, D), ga1 = koleo_ld<VEC>(yg, row0 + lr + 64, n, lk, D);
+        f32x4 gb0 = koleo_ld<VEC>(yg, col0 + lr, n, lk, D), gb1 = koleo_ld<VEC>(yg, col0 + lr + 64, n, lk, D);
+        for (int k0 = 0; k0 < D; k0 += KL_KC) {
+            __syncthreads();                                // the previous chunk (or tile, or the merge below) has been read
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                As[lr * KL_LD + lk + j] = ga0[j]; As[(lr + 64) * KL_LD + lk + j] = ga1[j];
+                Bs[lr * KL_LD + lk + j] = gb0[j]; Bs[(lr + 64) * KL_LD + lk + j] = gb1[j];
+            }
+            __syncthreads();
+            if (k0 + KL_KC < D) {                           // the next chunk's loads fly while this one multiplies
+                const int k = k0 + KL_KC + lk;
+                ga0 = koleo_ld<VEC>(yg, row0 + lr, n, k, D); ga1 = koleo_ld<VEC>(yg, row0 + lr + 64, n, k, D);
+                gb0 = koleo_ld<VEC>(yg, col0 + lr, n, k, D); gb1 = koleo_ld<VEC>(yg, col0 + lr + 64, n, k, D);
+            }
+#pragma unroll
+            for (int kk = 0; kk < KL_KC; kk += 2) {
+                const float a0 = As[(wr * 64 + l32) * KL_LD + kk + lh], a1 = As[(wr * 64 + 32 + l32) * KL_LD + kk + lh];
+                const float b0 = Bs[(wc * 64 + l32) * KL_LD + kk + lh], b1 = Bs[(wc * 64 + 32 + l32) * KL_LD + kk + lh];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+            }
+        }
+        // running (max, argmax): a lane meets its columns in ascending order, so `>` keeps the lowest index of equal products; the
+        // diagonal and the columns past n never enter
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int col = col0 + wc * 64 + b * 32 + l32;
+            if (col < n) {
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = row0 + wr * 64 + a * 32 + 8 * (r >> 2) + 4 * lh + (r & 3);
+                        const float v = acc[a][b][r];
+                        if (col != row && v > best_v[a][r]) { best_v[a][r] = v; best_i[a][r] = col; }
+                    }
+            }
+        }
+    }
+    // across the 32 lanes that share a row, then across the two waves that share it: larger product, lower index when equal
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = best_v[a][r];
+            int i = best_i[a][r];
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) {
+                const float v2 = __shfl_xor(v, o, 64);
+                const int i2 = __shfl_xor(i, o, 64);
+                if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+            }
+            if (l32 == 0) {
+                const int rl = wr * 64 + a * 32 + 8 * (r >> 2) + 4 * lh + (r & 3);
+                red_v[wc][rl] = v; red_i[wc][rl] = i;
+            }
+        }
+    __syncthreads();
+    if (tid < KL_TM && row0 + tid < n) {
+        float v = red_v[0][tid];
+        int i = red_i[0][tid];
+        const float v2 = red_v[1][tid];
+        const int i2 = red_i[1][tid];
+        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+        pairs[((long)g * n + row0 + tid) * splits + sp] = make_float2(v, __int_as_float(i));
+    }
+}
+
+// grid (cdiv(n, 4), groups), one wave per row
+__global__ __launch_bounds__(256) void koleo_finish_kernel(const float* __restrict__ y, const float2* __restrict__ pairs, int splits, int groups, int n, int D,
+                                                           float eps, int* __restrict__ nn, long long* __restrict__ nn64, float* __restrict__ dist,
+                                                           float* __restrict__ part, float* __restrict__ gloss, unsigned* __restrict__ counter,
+                                                           float* __restrict__ loss) {
+    __shared__ float terms[4];
+    __shared__ bool last;
+    const int g = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + wave, nb = gridDim.x;
+    float term = 0.f;
+    if (i < n) {
+        const long row = (long)g * n + i;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int s = 0; s < splits; ++s) {                  // ranges hold ascending columns: `>` keeps the lowest index
+            const float2 p = pairs[row * splits + s];
+            if (p.x > bv) { bv = p.x; bi = __float_as_int(p.y); }
+        }
+        if (bi < 0 || bi >= n) bi = (i == 0 && n > 1) ? 1 : 0;      // a single row is its own neighbour (the reference's diagonal of -1 wins there)
+        const float* yi = y + row * D;
+        const float* yj = y + ((long)g * n + bi) * D;
+        float ss = 0.f;
+        for (int c = lane; c < D; c += 64) { const float d = (yi[c] - yj[c]) + KL_PD_EPS; ss = fmaf(d, d, ss); }
+        const float d = sqrtf(wave_sum(ss));
+        term = logf(d + eps);
+        if (lane == 0) {
+            nn[row] = bi;
+            if (nn64) nn64[row] = bi;
+            dist[row] = d;
+        }
+    }
+    if (lane == 0) terms[wave] = term;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[(long)g * nb + blockIdx.x] = (terms[0] + terms[1]) + (terms[2] + terms[3]);
+        __threadfence();                                    // the partial is visible to the device before the arrival is counted
+        last = atomicAdd(counter, 1u) == (unsigned)(nb * groups) - 1u;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    // a group's sum depends on n alone (lane-strided, then the butterfly), so a group gives the same bits alone or among others
+    const volatile float* vp = part;
+    for (int gg = wave; gg < groups; gg += 4) {
+        float s = 0.f;
+        for (int b = lane; b < nb; b += 64) s += vp[(long)gg * nb + b];
+        s = wave_sum(s);
+        if (lane == 0) gloss[gg] = -s / (float)n;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float s = 0.f;
+        for (int gg = lane; gg < groups; gg += 64) s += gloss[gg];
+        s = wave_sum(s);
+        if (lane == 0) loss[0] = s;
+    }
+}
+
+// grid (cdiv(n, 4), groups), one wave per row j:  dy_j = g_j u_j - sum_{i : I(i) = j} g_i u_i,  g_i = -dloss / (n (d_i + eps)),
+// u_i = (y_i - y_I(i) + 1e-8) / d_i;  then dx_j = (dy_j - x_j (x_j . dy_j) / ||x_j||^2) / ||x_j||, or dy_j / eps where the norm was clamped
+__global__ __launch_bounds__(256) void koleo_bwd_kernel(const float* __restrict__ dloss, const float* __restrict__ x, const float* __restrict__ y,
+                                                        const float* __restrict__ norm, const int* __restrict__ nn, const float* __restrict__ dist, int n, int D,
+                                                        float eps, float* __restrict__ dx) {
+#pragma clang fp contract(off)      // g u is rounded before it is added or subtracted: a row that is its own neighbour (n = 1) gets exactly 0
+    __shared__ int nn_s[KL_MAX_N];
+    const int g = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = blockIdx.x * 4 + wave;
+    const long base = (long)g * n;
+    for (int i = threadIdx.x; i < n; i += 256) nn_s[i] = nn[base + i];
+    __syncthreads();
+    if (j >= n) return;
+    const float gs = -dloss[0] / (float)n;
+    const float* yj = y + (base + j) * D;
+    float dy[KL_MAX_D / 64];
+    {
+        const float* yo = y + (base + nn_s[j]) * D;
+        const float dj = dist[base + j], gj = gs / (dj + eps);
+#pragma unroll
+        for (int t = 0; t < KL_MAX_D / 64; ++t) {
+            const int c = t * 64 + lane;
+            dy[t] = c < D ? gj * (((yj[c] - yo[c]) + KL_PD_EPS) / dj) : 0.f;
+        }
+    }
+    for (int i0 = 0; i0 < n; i0 += 64) {                    // ascending i: the lanes vote, the wave walks the set bits from the lowest
+        const int i = i0 + lane;
+        unsigned long long m = __ballot(i < n && nn_s[i] == j);
+        while (m) {
+            const int ii = i0 + __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const float* yi = y + (base + ii) * D;
+            const float di = dist[base + ii], gi = gs / (di + eps);
+#pragma unroll
+            for (int t = 0; t < KL_MAX_D / 64; ++t) {
+                const int c = t * 64 + lane;
+                if (c < D) dy[t] -= gi * (((yi[c] - yj[c]) + KL_PD_EPS) / di);
+            }
+        }
+    }
+    const float* xr = x + (base + j) * D;
+    float* dr = dx + (base + j) * D;
+    const float nr = norm[base + j];
+    if (nr < eps) {
+#pragma unroll
+        for (int t = 0; t < KL_MAX_D / 64; ++t) {
+            const int c = t * 64 + lane;
+            if (c < D) dr[c] = dy[t] / eps;
+        }
+        return;
+    }
+    float dot = 0.f;
+#pragma unroll
+    for (int t = 0; t < KL_MAX_D / 64; ++t) {
+        const int c = t * 64 + lane;
+        if (c < D) dot = fmaf(xr[c], dy[t], dot);
+    }
+    dot = wave_sum(dot) / (nr * nr);
+#pragma unroll
+    for (int t = 0; t < KL_MAX_D / 64; ++t) {
+        const int c = t * 64 + lane;
+        if (c < D) dr[c] = (dy[t] - xr[c] * dot) / nr;
+    }
+}
+
 // ---- multi-tensor moving average: dst = dst * beta + (1 - beta) * src over up to M3L_EMA_MAX tensors per launch ---------------------
 #define M3L_EMA_MAX 128
 #define EMA_BLOCK_ELEMS 4096
@@ -513,6 +808,45 @@ int m3l_op_sk_probs(const float* logits, int rows, int K, const float* center, f
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("sk_probs", rows, K, 0, 8.0 * rows * K, st, 8.0 * rows * K + (center ? 4.0 * K : 0.0));
     sk_probs_kernel<<<dim3(cdiv(K, SK_COLS), rows), DINO_THREADS, 0, st>>>(logits, K, center, inv_temp, (const float2*)row_stats, probs);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+static int koleo_shape_ok(int groups, int n, int D) {
+    return groups > 0 && n >= 1 && n <= KL_MAX_N && D >= 1 && D <= KL_MAX_D && (long)groups * n <= KL_MAX_ROWS;
+}
+size_t m3l_op_koleo_ws_bytes(int groups, int n, int D) {
+    if (!koleo_shape_ok(groups, n, D)) return 256;
+    return koleo_ws(groups, n).bytes;
+}
+int m3l_op_koleo_fwd(const float* x, int groups, int n, int D, float eps, void* ws, float* y, float* norm, int* nn, long long* nn64, float* dist,
+                     float* loss, void* stream) {
+    M3L_CHECK(koleo_shape_ok(groups, n, D), "koleo_fwd: unsupported shape (groups=%d n=%d D=%d; 1 <= n <= %d, 1 <= D <= %d, groups * n <= %d)", groups, n, D,
+              KL_MAX_N, KL_MAX_D, KL_MAX_ROWS);
+    M3L_CHECK(x && ws && y && norm && nn && dist && loss, "koleo_fwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const KoleoWs w = koleo_ws(groups, n);
+    char* base = (char*)ws;
+    unsigned* counter = (unsigned*)base;
+    float2* pairs = (float2*)(base + w.pair_off);
+    const int rows = groups * n, tiles_per = cdiv(cdiv(n, KL_TN), w.splits), splits = cdiv(cdiv(n, KL_TN), tiles_per);
+    ProfScope prof("koleo_fwd", rows, D, splits, 2.0 * groups * n * n * D, st, 12.0 * rows * D);
+    koleo_norm_kernel<<<cdiv(rows, 4), 256, 0, st>>>(x, rows, D, eps, y, norm, counter);
+    const dim3 grid(cdiv(n, KL_TM), splits, groups);
+    if (D % 4 == 0 && ((uintptr_t)y & 15) == 0) koleo_search_kernel<true><<<grid, 256, 0, st>>>(y, n, D, tiles_per, pairs, splits);
+    else koleo_search_kernel<false><<<grid, 256, 0, st>>>(y, n, D, tiles_per, pairs, splits);
+    koleo_finish_kernel<<<dim3(cdiv(n, 4), groups), 256, 0, st>>>(y, pairs, splits, groups, n, D, eps, nn, nn64, dist, (float*)(base + w.part_off),
+                                                                 (float*)(base + w.gloss_off), counter, loss);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_koleo_bwd(const float* dloss, const float* x, const float* y, const float* norm, const int* nn, const float* dist, int groups, int n, int D,
+                     float eps, float* dx, void* stream) {
+    M3L_CHECK(koleo_shape_ok(groups, n, D), "koleo_bwd: unsupported shape (groups=%d n=%d D=%d; 1 <= n <= %d, 1 <= D <= %d, groups * n <= %d)", groups, n, D,
+              KL_MAX_N, KL_MAX_D, KL_MAX_ROWS);
+    M3L_CHECK(dloss && x && y && norm && nn && dist && dx, "koleo_bwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("koleo_bwd", groups * n, D, 0, 8.0 * groups * n * D, st, 20.0 * groups * n * D);
+    koleo_bwd_kernel<<<dim3(cdiv(n, 4), groups), 256, 0, st>>>(dloss, x, y, norm, nn, dist, n, D, eps, dx);
     M3L_LAUNCH_CHECK();
     return 0;
 }

@@ -472,6 +472,65 @@ class DINOLoss(nn.Module):
         return loss
 
 
+class KoLeoFn(torch.autograd.Function):
+    """KoLeo loss of x (groups * n, D) f32, summed over `groups` independent sets of n consecutive rows -> 0-d f32.  keep["indices"] receives
+    the (groups, n) int64 nearest neighbours (index inside the group).  The neighbours are constants for the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, groups, eps, keep):
+        _require_cuda(x, "KoLeo input")
+        x = _f32c(x)
+        if x.dim() != 2 or groups < 1 or x.shape[0] % groups:
+            raise ValueError(f"KoLeoFn: (groups * n, D) rows expected, got {tuple(x.shape)} for {groups} group(s)")
+        lib = L.lib()
+        (M, D), n = x.shape, x.shape[0] // groups
+        y = torch.empty_like(x)
+        norm = torch.empty(M, dtype=torch.float32, device=x.device)
+        dist_ = torch.empty(M, dtype=torch.float32, device=x.device)
+        nn32 = torch.empty(M, dtype=torch.int32, device=x.device)
+        nn64 = torch.empty(groups, n, dtype=torch.int64, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        ws = _ws(lib.m3l_op_koleo_ws_bytes(groups, n, D), x.device)
+        L.check(lib.m3l_op_koleo_fwd(L.ptr(x), groups, n, D, float(eps), L.ptr(ws), L.ptr(y), L.ptr(norm), L.ptr(nn32), L.ptr(nn64), L.ptr(dist_),
+                                     L.ptr(loss), _stream()), "m3l_op_koleo_fwd")
+        ctx.saved = (x, y, norm, nn32, dist_, groups, n, D, float(eps))
+        if keep is not None:
+            keep["indices"] = nn64
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x, y, norm, nn32, dist_, groups, n, D, eps = ctx.saved
+        dx = torch.empty_like(x)
+        L.check(L.lib().m3l_op_koleo_bwd(L.ptr(_f32c(dloss)), L.ptr(x), L.ptr(y), L.ptr(norm), L.ptr(nn32), L.ptr(dist_), groups, n, D, eps, L.ptr(dx),
+                                         _stream()), "m3l_op_koleo_bwd")
+        return dx, None, None, None
+
+
+class KoLeoLoss(nn.Module):
+    """Kozachenko-Leonenko regulariser (`tactile_ssl/loss/koleo_loss.py`): -mean_i log(||y_i - y_I(i) + 1e-8|| + eps) over the L2-normalised
+    rows y of a (B, D) batch, I(i) the row with the largest inner product with row i.  No parameters, no buffers; float32 whatever the
+    model's compute type (the reference switches autocast off).  `last` holds the neighbours of the last call."""
+
+    def __init__(self):
+        super().__init__()
+        self.last = None
+
+    @torch.no_grad()
+    def pairwise_NNs_inner(self, x):
+        """(B,) int64 nearest neighbours of the rows of x by inner product (the kernel normalises; a normalised x is left as it is up to
+        rounding, and the neighbours of x and of normalize(x) are the same rows)."""
+        keep = {}
+        KoLeoFn.apply(x.detach(), 1, 1e-8, keep)
+        return keep["indices"][0]
+
+    def forward(self, student_output, eps=1e-8):
+        keep = {}
+        loss = KoLeoFn.apply(student_output, 1, eps, keep)
+        self.last = keep["indices"][0]
+        return loss
+
+
 @torch.no_grad()
 def update_moving_average(ma_model, current_model, beta):
     """teacher_p = teacher_p * beta + (1 - beta) * student_p over the two modules' parameters() paired in order, in one multi-tensor launch."""

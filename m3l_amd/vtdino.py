@@ -11,6 +11,10 @@ and the prototype layer, the centred-teacher cross-entropy and their backward ar
 assignment of the teacher logits as the targets: DINOLoss.sinkhorn_knopp_center gives the K-vector that stands in the centre's place, and
 the centre is neither applied nor updated.
 
+`koleo_weight > 0` (another trailing keyword; the reference's DINOv2 algorithm has it, 0.1 there) adds the KoLeo regulariser of
+`tactile_ssl/loss/koleo_loss.py` on the student's register rows of the global views: one group per global view, so samples of different
+views are never compared, the views' losses summed, all in one set of launches (KoLeoFn).  At 0.0 the step is the one without it.
+
 Not built: online probes and their logging (a non-empty `online_probes` is refused).
 """
 import copy
@@ -21,15 +25,18 @@ import torch
 from torch import nn
 
 from . import functional as Fn
-from .dino import DINOLoss, HeadLossFn, update_moving_average
+from .dino import DINOLoss, HeadLossFn, KoLeoFn, KoLeoLoss, update_moving_average
 
 
 class VTDINO(nn.Module):
     def __init__(self, encoder, dino_head, optim_cfg, lr_scheduler_cfg, wd_scheduler_cfg, online_probes=None, online_probes_lrs=[],
                  local_mask_scale=(0.2, 0.8), global_mask_scale=(0.2, 0.8), num_global_masks=1, num_local_masks=4, min_keep_num_sensors=4,
                  allow_mask_overlap=False, moving_average_decay=0.99, teacher_temp=(0.04, 0.07), teacher_warmup_epochs=10, use_momentum=True,
-                 log_freq_reconstruction=1000, centering="centering"):
+                 log_freq_reconstruction=1000, centering="centering", koleo_weight=0.0):
         super().__init__()
+        if not koleo_weight >= 0:
+            raise ValueError(f"VTDINO(koleo_weight=...): a weight >= 0 expected, got {koleo_weight!r}")
+        self.koleo_weight = float(koleo_weight)
         if centering not in ("centering", "sinkhorn_knopp"):
             raise ValueError(f"VTDINO(centering=...): 'centering' or 'sinkhorn_knopp' expected, got {centering!r}")
         self.centering = centering
@@ -63,6 +70,7 @@ class VTDINO(nn.Module):
         for head in (self.student_encoder_dict["dino_head"], self.teacher_encoder_dict["dino_head"]):
             head.compute_dtype = self.compute_dtype
         self.dino_loss = DINOLoss(out_dim=self.student_encoder_dict["dino_head"].last_layer.out_features)
+        self.koleo_loss = KoLeoLoss()                              # no parameters, no buffers: the state dict is unchanged
 
         self.patch_size = encoder.image_patch_height
         self.img_size = encoder.image_height
@@ -77,6 +85,7 @@ class VTDINO(nn.Module):
         self.teacher_warmup_epochs = teacher_warmup_epochs
         self.val_reconstruction_error = []
         self.last = {}                       # student / teacher logits of the last forward (detached), for inspection
+        self.loss_terms = None               # (DINO loss, weighted KoLeo loss) of the last forward when koleo_weight > 0
 
     @staticmethod
     def _float_or_pair(value, name):
@@ -186,8 +195,8 @@ class VTDINO(nn.Module):
         assert global_masks is not None and local_masks is not None, "Masks are required for DINOModule during training"
         student, teacher = self.student_encoder_dict, self.teacher_encoder_dict
         P, Q = len(global_masks) + len(local_masks), len(global_masks)
-        rows = torch.cat([self._register_rows(student["backbone"], x, global_masks),
-                          self._register_rows(student["backbone"], x, local_masks)], dim=0)
+        global_rows = self._register_rows(student["backbone"], x, global_masks)
+        rows = torch.cat([global_rows, self._register_rows(student["backbone"], x, local_masks)], dim=0)
         head = student["dino_head"]
         xn = head.normalized(rows)
         B = xn.shape[0] // P
@@ -204,6 +213,14 @@ class VTDINO(nn.Module):
         self.last["teacher_logits"] = t_logits
         if self.centering != "sinkhorn_knopp":
             self.dino_loss.update_center(t_logits)
+        self.loss_terms = None
+        if self.koleo_weight > 0:
+            # one group per global view (the rows are view-major); local to the rank under data parallelism, as in the reference
+            keep = {}
+            koleo = self.koleo_weight * KoLeoFn.apply(global_rows, Q, 1e-8, keep)
+            self.last["koleo_indices"] = self.koleo_loss.last = keep["indices"]
+            self.loss_terms = (loss.detach(), koleo.detach())
+            loss = loss + koleo
         return loss
 
     def training_step(self, batch, batch_idx):
@@ -211,7 +228,11 @@ class VTDINO(nn.Module):
         self.generator.manual_seed(self.step)
         global_masks, local_masks = self.sample_masks(batch["image"])
         loss = self.forward(batch, global_masks, local_masks)
-        output = {"ssl_loss": loss.item()}
+        if self.loss_terms is None:
+            output = {"ssl_loss": loss.item()}
+        else:                                                # the three scalars in one device-to-host copy
+            total, dino, koleo = torch.stack((loss.detach(),) + self.loss_terms).tolist()
+            output = {"ssl_loss": total, "dino_loss": dino, "koleo_loss": koleo}
         online_probes_loss = 0.0
         output["loss"] = loss
         output["online_probes_loss"] = online_probes_loss

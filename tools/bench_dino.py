@@ -12,9 +12,10 @@ that never passes), B = 32, in bf16 and in fp32.
      the launches, so (2) apportions time and (1) is the step time.
 
 --centering sinkhorn_knopp runs the step with the Sinkhorn-Knopp teacher targets (three column passes and two extra row passes over the
-64 x 65536 teacher logits per step, no centre update).
+64 x 65536 teacher logits per step, no centre update).  --koleo-weight W runs it with VTDINO(koleo_weight=W): the KoLeo regulariser over the
+two global views' register rows (2 groups of 32 rows of 256), 3 + 1 launches per step.
 
-There is no pass mark.  Usage: python tools/bench_dino.py [--centering sinkhorn_knopp]  (one JSON line on stdout)"""
+There is no pass mark.  Usage: python tools/bench_dino.py [--centering sinkhorn_knopp] [--koleo-weight 0.1]  (one JSON line on stdout)"""
 import argparse
 import ctypes as C
 import json
@@ -31,10 +32,10 @@ from m3l_amd import _lib as L  # noqa: E402
 DEV = "cuda:0"
 HBM_TBS = 6.3
 B, N_GLOBAL, N_LOCAL, K_OUT = 32, 2, 8, 65536
-NEW_KINDS = ("dino_", "sk_", "l2norm", "weightnorm", "ema")
+NEW_KINDS = ("dino_", "sk_", "koleo_", "l2norm", "weightnorm", "ema")
 
 
-def build(dt, centering="centering"):
+def build(dt, centering="centering", koleo_weight=0.0):
     torch.manual_seed(0)
     enc = m3l_amd.DinoVTT(image_size=64, tactile_size=32, image_patch_size=8, tactile_patch_size=4, dim=256, depth=4, heads=8, mlp_dim=512,
                           num_tactiles=2, num_register_tokens=1, compute_dtype=dt)
@@ -44,7 +45,8 @@ def build(dt, centering="centering"):
                            wd_scheduler_cfg=None,
                            local_mask_scale=(0.2, 0.48), global_mask_scale=(0.48, 1.0), num_global_masks=N_GLOBAL, num_local_masks=N_LOCAL,
                            min_keep_num_sensors=4, allow_mask_overlap=True, moving_average_decay=[0.994, 1.0], teacher_temp=[0.04, 0.07],
-                           **({} if centering == "centering" else {"centering": centering})).to(DEV)
+                           **({} if centering == "centering" else {"centering": centering}),
+                           **({"koleo_weight": koleo_weight} if koleo_weight else {})).to(DEV)
     opt, lr_entry, _ = model.configure_optimizers(100, 10)
     model.lr_scheduler = lr_entry["scheduler"]
     g = torch.Generator().manual_seed(1)
@@ -84,8 +86,8 @@ def classes():
     return out
 
 
-def run(dt, steps, warmup, prof_steps, centering="centering"):
-    model, opt, x = build(dt, centering)
+def run(dt, steps, warmup, prof_steps, centering="centering", koleo_weight=0.0):
+    model, opt, x = build(dt, centering, koleo_weight)
     for i in range(warmup):
         loss = step(model, opt, x, i)
     torch.cuda.synchronize()
@@ -124,11 +126,12 @@ def main():
     ap.add_argument("--prof-steps", type=int, default=3)
     ap.add_argument("--dtypes", default="bf16,fp32")
     ap.add_argument("--centering", default="centering", choices=["centering", "sinkhorn_knopp"], help="teacher targets (VTDINO's keyword)")
+    ap.add_argument("--koleo-weight", type=float, default=0.0, help="VTDINO's koleo_weight (0 = the step without the regulariser)")
     a = ap.parse_args()
     out = {"config": f"DinoVTT 256/4/8/512 + head 256-2048-2048-256-{K_OUT}, B={B}, {N_GLOBAL}+{N_LOCAL} views", "hbm_tb_per_s": HBM_TBS,
-           "centering": a.centering}
+           "centering": a.centering, "koleo_weight": a.koleo_weight}
     for dt in a.dtypes.split(","):
-        out[dt] = run(dt, a.steps, a.warmup, a.prof_steps, a.centering)
+        out[dt] = run(dt, a.steps, a.warmup, a.prof_steps, a.centering, a.koleo_weight)
         torch.cuda.empty_cache()
     print(json.dumps(out))
 
