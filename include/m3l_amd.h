@@ -394,6 +394,11 @@ int m3l_op_gemm_nt(int dtype, const void* A, int lda, const void* W, int ldw, in
 size_t m3l_op_gemm_tn_ws_bytes(int M, int N, int K);
 int m3l_op_gemm_tn(int dtype, const void* Y, int ldy, const void* X, int ldx, int M, int N, int K, void* ws, size_t ws_bytes,
                    float* out, int ldo, void* stream);
+/* the same with accumulate != 0 adding to `out` instead of overwriting it.  Both operands are addressed through 32-bit buffer offsets: M * ldy and
+ * M * ldx times 4 bytes (2 in bf16) must stay below 2 GiB, or the call is refused; a caller with a longer reduction runs it in chunks of rows,
+ * the first overwriting and the others accumulating (what the prototype layer's dx_n = dS W does at 65536 prototypes x > 8191 rows in f32). */
+int m3l_op_gemm_tn_acc(int dtype, const void* Y, int ldy, const void* X, int ldx, int M, int N, int K, void* ws, size_t ws_bytes, float* out, int ldo,
+                       int accumulate, void* stream);
 /* `count` weight gradients that share M in ONE grouped launch (what a transformer layer group's backward issues: dW_i [N_i, K_i] = Y_i^T X_i,
  * every nn.Linear.weight.grad of vit_pytorch Attention / FeedForward via loss.backward(), models/ppo_mae.py:263); bf16 operands take the
  * 256 x 192 split-M kernel of wgrad.hip.  Y / X / out: host arrays of device pointers; ld* / N / K: host int arrays. */
@@ -494,6 +499,30 @@ int m3l_op_koleo_fwd(const float* x, int groups, int n, int D, float eps, void* 
                      float* loss, void* stream);
 int m3l_op_koleo_bwd(const float* dloss, const float* x, const float* y, const float* norm, const int* nn, const float* dist, int groups, int n, int D,
                      float eps, float* dx, void* stream);
+/* iBOT patch loss (tactile_ssl/loss/ibot_patch_loss.py, iBOTPatchLoss.forward as tactile_ssl/algorithm/dinov2.py calls it): the DINO cross-entropy
+ * above with Q student views against Q teacher views of R = B n patch rows each (n kept patches of a global mask; row r = b n + k of every student
+ * view is paired with row r of every teacher view), S and the teacher logits T both [Q, R, K], K % 4 == 0:
+ *   loss = 1/R sum_r ( Q sum_p lse(S[p,r,:] * inv_ts) - inv_ts sum_k tsum[r,k] sum_p S[p,r,k] ),  tsum[r,k] = sum_q softmax((T[q,r,:] - center) * inv_tt)[k]
+ *   dS[p,r,k] = dloss[0] * inv_ts / R * (Q softmax(S[p,r,:] * inv_ts)[k] - tsum[r,k])
+ * Every kernel is tiled over the rows, so R is bounded by a launch limit only and no kernel's LDS use depends on it.  Order of calls:
+ * m3l_op_dino_rowstats for the Q R student rows (center NULL, inv_ts) and the Q R teacher rows (center, inv_tt), then
+ *   m3l_op_ibot_loss        loss[0]: one workgroup per pair-row and column range leaves its cross term in ws, a second kernel forms the rows' terms and
+ *                           adds them per 256 rows, a third adds those sums in a fixed order (two-stage over R, no atomics: the same bits on every run)
+ *   m3l_op_ibot_grad        dST[k * ldr + p R + r] in `out_dtype`, ldr >= Q R (a multiple of 8 for the GEMMs), columns Q R .. ldr - 1 zero: the operand
+ *                           form of m3l_op_dino_grad.  One workgroup per 64 columns x 64 pair-rows: tsum of the tile once (registers), then the Q student
+ *                           rows of each pair through a 64 x 64 LDS transpose tile; T and S are read once, dST is written once
+ *   m3l_op_ibot_center_sum  pending[k] = scale * sum over `rows` rows of T[row, k]: the rows are cut into m3l_op_sk_row_splits(rows, K) ranges over the
+ *                           workgroups, a second kernel adds the ranges' sums in range order.  scale = 1 / n gives iBOTPatchLoss.update_center's
+ *                           sum_b mean_k; the centre itself is m3l_op_dino_center_apply with count = Q B world size.
+ * Launch limit: Q R <= 65535 (m3l_op_dino_rowstats and the loss use one grid row per logit row) and Q <= 64; m3l_op_ibot_center_sum takes any row count.
+ * A shape outside the limits, K % 4 != 0 or ldr < Q R is an error and nothing is written.
+ * ws (loss, center_sum): m3l_op_ibot_ws_bytes(rows, K) bytes, rows = R for the loss, the row count for center_sum (Q R covers both). */
+size_t m3l_op_ibot_ws_bytes(int rows, int K);
+int m3l_op_ibot_loss(const float* S, const float* T, int Q, int R, int K, const float* center, float inv_ts, float inv_tt, const float* s_stats,
+                     const float* t_stats, void* ws, float* loss, void* stream);
+int m3l_op_ibot_grad(int out_dtype, const float* S, const float* T, int Q, int R, int K, const float* center, float inv_ts, float inv_tt,
+                     const float* s_stats, const float* t_stats, const float* dloss, void* dST, int ldr, void* stream);
+int m3l_op_ibot_center_sum(const float* T, int rows, int K, float scale, void* ws, float* pending, void* stream);
 /* Moving average of `count` tensors in one launch per 128 tensors (update_moving_average): dst[i] = dst[i] * beta + one_minus_beta * src[i] over
  * len[i] floats.  dst / src / len: host arrays (device pointers, element counts). */
 int m3l_op_ema(float* const* dst, const float* const* src, const long* len, int count, float beta, float one_minus_beta, void* stream);

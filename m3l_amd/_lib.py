@@ -135,6 +135,7 @@ _SIGS = {
     "m3l_op_gemm_nt": (c_i, [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
     "m3l_op_gemm_tn_ws_bytes": (c_sz, [c_i, c_i, c_i]),
     "m3l_op_gemm_tn": (c_i, [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p, c_i, c_p]),
+    "m3l_op_gemm_tn_acc": (c_i, [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p, c_i, c_i, c_p]),
     "m3l_op_gemm_tn_grouped_ws_bytes": (c_sz, [c_i, c_i, c_i, c_p, c_p]),
     "m3l_op_gemm_tn_grouped": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "m3l_op_colsum_ws_bytes": (c_sz, [c_i]),
@@ -167,6 +168,10 @@ _SIGS = {
     "m3l_op_koleo_ws_bytes": (c_sz, [c_i, c_i, c_i]),
     "m3l_op_koleo_fwd": (c_i, [c_p, c_i, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "m3l_op_koleo_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, C.c_float, c_p, c_p]),
+    "m3l_op_ibot_ws_bytes": (c_sz, [c_i, c_i]),
+    "m3l_op_ibot_loss": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, C.c_float, C.c_float, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_op_ibot_grad": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_p, C.c_float, C.c_float, c_p, c_p, c_p, c_p, c_i, c_p]),
+    "m3l_op_ibot_center_sum": (c_i, [c_p, c_i, c_i, C.c_float, c_p, c_p, c_p]),
     "m3l_op_ema": (c_i, [c_p, c_p, c_p, c_i, C.c_float, C.c_float, c_p]),
 }
 

@@ -9,6 +9,7 @@
 //   gradient       : dS[p,b,k] = g / (ts B) ( Q softmax(S[p,b,:] / ts)[k] - sum_q T[q,b,k] ), written k-major in the compute type of the two GEMMs
 //   Sinkhorn-Knopp : the teacher's other target; a K-vector in the centre's place, from column passes (max, sum exp) down the rows
 //   KoLeo          : float32 nearest neighbour of every row inside its group on the f32 MFMA, -mean log distance; the backward is a gather
+//   iBOT patch loss: the same cross-entropy over B n patch rows per view, every kernel tiled over the rows
 #include <math.h>
 #include <string.h>
 
@@ -627,6 +628,104 @@ __global__ __launch_bounds__(256) void koleo_bwd_kernel(const float* __restrict_
     }
 }
 
+// ---- iBOT patch loss (tactile_ssl/loss/ibot_patch_loss.py): the DINO cross-entropy over R = B n patch rows per view -----------------------
+// The arithmetic is dino_loss / dino_grad with P = Q and B = R, but R is 500 to 1600 (3100 logit rows of 65536 floats), so nothing here keeps a
+// per-row quantity of all rows in LDS or walks all rows in one thread:
+//   cross term : dino_loss_part_kernel as it is (one workgroup per pair-row and column range; its grid row is the pair-row)
+//   reduction  : thread r forms Q sum_p lse_s[p,r] - inv_ts sum_i part[r,i], a workgroup adds 256 rows, one wave adds the workgroups' sums
+//   gradient   : grid (column slabs of 64, tiles of 64 pair-rows).  A thread owns 4 columns of 4 pair-rows: their teacher sums stay in 16
+//                registers, then for each student view the 64 x 64 block goes through the LDS tile and leaves along r (a wave writes 64
+//                consecutive elements of one row of dS^T)
+//   centre     : column sums over row ranges (grid.y), then the ranges in order, times `scale`
+#define IB_TK 64             // columns of a workgroup
+#define IB_TR 64             // pair-rows of a workgroup
+#define IB_MAX_ROWS 65535    // Q R: one grid row per logit row in the row statistics, one per pair-row in the cross term
+
+__global__ __launch_bounds__(256) void ibot_loss_rows_kernel(const float* __restrict__ part, int splits, const float2* __restrict__ s_stats, int Q, int R,
+                                                             float inv_ts, float* __restrict__ part2) {
+    __shared__ float red[4];
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    float term = 0.f;
+    if (r < R) {
+        float lse = 0.f, cross = 0.f;
+        for (int p = 0; p < Q; ++p) lse += s_stats[(long)p * R + r].y;
+        for (int i = 0; i < splits; ++i) cross += part[(long)r * splits + i];
+        term = (float)Q * lse - inv_ts * cross;
+    }
+    term = block_sum(term, red);
+    if (threadIdx.x == 0) part2[blockIdx.x] = term;
+}
+// one wave: lane-strided over the workgroups' sums, then the butterfly; the order depends on R alone
+__global__ __launch_bounds__(64) void ibot_loss_final_kernel(const float* __restrict__ part2, int n, int R, float* __restrict__ loss) {
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n; i += 64) acc += part2[i];
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) loss[0] = acc / (float)R;
+}
+
+template <typename TO>
+__global__ __launch_bounds__(256) void ibot_grad_t_kernel(const float* __restrict__ S, const float* __restrict__ T, int Q, int R, int K,
+                                                          const float* __restrict__ center, float inv_ts, float inv_tt, const float2* __restrict__ s_stats,
+                                                          const float2* __restrict__ t_stats, const float* __restrict__ dloss, TO* __restrict__ dST, int ldr) {
+    __shared__ float tile[IB_TK][IB_TR + 1];
+    const int k0 = blockIdx.x * IB_TK, r0 = blockIdx.y * IB_TR, j = threadIdx.x & 15, grp = threadIdx.x >> 4, k = k0 + 4 * j;
+    const bool kin = k < K;                                 // K % 4 == 0: a thread's four columns are inside or outside together
+    const float gs = dloss[0] * inv_ts / (float)R, fq = (float)Q;
+    f32x4 ts[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = r0 + grp + 16 * i;
+        ts[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (r < R && kin) ts[i] = teacher_sum4(T, t_stats, center, Q, R, r, K, k, inv_tt);
+    }
+    const int rl = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int p = 0; p < Q; ++p) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = r0 + grp + 16 * i;
+            f32x4 d = {0.f, 0.f, 0.f, 0.f};
+            if (r < R && kin) {
+                const long row = (long)p * R + r;
+                const f32x4 z = ld4(S + row * K + k) * inv_ts;
+                const float lse = s_stats[row].y;
+                d[0] = gs * (fq * __expf(z[0] - lse) - ts[i][0]); d[1] = gs * (fq * __expf(z[1] - lse) - ts[i][1]);
+                d[2] = gs * (fq * __expf(z[2] - lse) - ts[i][2]); d[3] = gs * (fq * __expf(z[3] - lse) - ts[i][3]);
+            }
+            tile[4 * j + 0][grp + 16 * i] = d[0]; tile[4 * j + 1][grp + 16 * i] = d[1];
+            tile[4 * j + 2][grp + 16 * i] = d[2]; tile[4 * j + 3][grp + 16 * i] = d[3];
+        }
+        __syncthreads();
+        if (r0 + rl < R)
+            for (int kk = wv; kk < IB_TK && k0 + kk < K; kk += 4) dST[(long)(k0 + kk) * ldr + (long)p * R + r0 + rl] = from_f32<TO>(tile[kk][rl]);
+        __syncthreads();
+    }
+    // the pad columns Q R .. ldr - 1 of this slab's rows: the workgroups of the last row tile write them
+    const int npad = ldr - Q * R;
+    if (blockIdx.y == gridDim.y - 1 && npad > 0)
+        for (int idx = threadIdx.x; idx < IB_TK * npad; idx += 256) {
+            const int kk = idx / npad, c = idx - kk * npad;
+            if (k0 + kk < K) dST[(long)(k0 + kk) * ldr + (long)Q * R + c] = from_f32<TO>(0.f);
+        }
+}
+
+// part[range][k .. k+3] = sum over the rows of the range of T[r, k .. k+3] (ascending r)
+__global__ __launch_bounds__(256) void ibot_colsum_part_kernel(const float* __restrict__ T, int rows, int K, int rows_per, float* __restrict__ part) {
+    const int k = (blockIdx.x * DINO_THREADS + threadIdx.x) * 4;
+    if (k >= K) return;
+    const int r0 = blockIdx.y * rows_per, r1 = min(rows, r0 + rows_per);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int r = r0; r < r1; ++r) acc += ld4(T + (long)r * K + k);
+    *reinterpret_cast<f32x4*>(part + (long)blockIdx.y * K + k) = acc;
+}
+__global__ __launch_bounds__(256) void ibot_colsum_combine_kernel(const float* __restrict__ part, int nparts, int K, float scale, float* __restrict__ pending) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    float acc = 0.f;
+    for (int i = 0; i < nparts; ++i) acc += part[(long)i * K + k];
+    pending[k] = acc * scale;
+}
+
 // ---- multi-tensor moving average: dst = dst * beta + (1 - beta) * src over up to M3L_EMA_MAX tensors per launch ---------------------
 #define M3L_EMA_MAX 128
 #define EMA_BLOCK_ELEMS 4096
@@ -847,6 +946,62 @@ int m3l_op_koleo_bwd(const float* dloss, const float* x, const float* y, const f
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("koleo_bwd", groups * n, D, 0, 8.0 * groups * n * D, st, 20.0 * groups * n * D);
     koleo_bwd_kernel<<<dim3(cdiv(n, 4), groups), 256, 0, st>>>(dloss, x, y, norm, nn, dist, n, D, eps, dx);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+// workspace of the loss: float part[R][DINO_MAX_SPLITS], then float part2[cdiv(R, 256)]; of the centre sums: float part[ranges][K]
+static size_t ibot_part2_off(int R) { return ((size_t)R * DINO_MAX_SPLITS * sizeof(float) + 255) / 256 * 256; }
+size_t m3l_op_ibot_ws_bytes(int rows, int K) {
+    if (rows <= 0 || K <= 0) return 256;
+    const size_t loss = ibot_part2_off(rows) + (size_t)cdiv(rows, 256) * sizeof(float);
+    const size_t sums = (size_t)cdiv(rows, sk_rows_per_split(rows, K)) * (size_t)K * sizeof(float);
+    return (loss > sums ? loss : sums) + 256;
+}
+static int ibot_check(const char* what, const void* S, const void* T, int Q, int R, int K, const void* center, const void* a, const void* b) {
+    M3L_CHECK(Q > 0 && R > 0 && K > 0 && K % 4 == 0 && Q <= DINO_MAX_VIEWS && (long)Q * R <= IB_MAX_ROWS,
+              "%s: unsupported shape (Q=%d R=%d K=%d; K must be a multiple of 4, at most %d views, Q R <= %d)", what, Q, R, K, DINO_MAX_VIEWS, IB_MAX_ROWS);
+    M3L_CHECK(S && T && center && a && b, "%s: null argument", what);
+    return 0;
+}
+int m3l_op_ibot_loss(const float* S, const float* T, int Q, int R, int K, const float* center, float inv_ts, float inv_tt, const float* s_stats,
+                     const float* t_stats, void* ws, float* loss, void* stream) {
+    if (ibot_check("ibot_loss", S, T, Q, R, K, center, s_stats, t_stats)) return 1;
+    M3L_CHECK(ws && loss, "ibot_loss: null workspace or output");
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = dino_splits(R, K), chunk = dino_chunk(K, splits), nb = cdiv(R, 256);
+    float* part = (float*)ws;
+    float* part2 = (float*)((char*)ws + ibot_part2_off(R));
+    ProfScope prof("ibot_loss", 2L * Q * R, K, splits, (double)R * K * (9.0 * Q + 2.0), st, 8.0 * (double)Q * R * K);
+    dino_loss_part_kernel<<<dim3(splits, R), DINO_THREADS, 0, st>>>(S, Q, T, Q, R, K, chunk, center, inv_tt, (const float2*)t_stats, part);
+    ibot_loss_rows_kernel<<<nb, 256, 0, st>>>(part, splits, (const float2*)s_stats, Q, R, inv_ts, part2);
+    ibot_loss_final_kernel<<<1, 64, 0, st>>>(part2, nb, R, loss);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_ibot_grad(int out_dtype, const float* S, const float* T, int Q, int R, int K, const float* center, float inv_ts, float inv_tt,
+                     const float* s_stats, const float* t_stats, const float* dloss, void* dST, int ldr, void* stream) {
+    if (ibot_check("ibot_grad", S, T, Q, R, K, center, s_stats, t_stats)) return 1;
+    M3L_CHECK(dloss && dST && (out_dtype == 0 || out_dtype == 1), "ibot_grad: null gradient or bad dtype %d", out_dtype);
+    M3L_CHECK(ldr >= Q * R, "ibot_grad: leading dimension %d below the %d student rows", ldr, Q * R);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("ibot_grad", 2L * Q * R, K, 0, 16.0 * (double)Q * R * K, st, (double)K * (8.0 * Q * R + (out_dtype ? 2.0 : 4.0) * ldr));
+    const dim3 grid(cdiv(K, IB_TK), cdiv(R, IB_TR));
+    if (out_dtype == 1)
+        ibot_grad_t_kernel<bf16><<<grid, 256, 0, st>>>(S, T, Q, R, K, center, inv_ts, inv_tt, (const float2*)s_stats, (const float2*)t_stats, dloss,
+                                                       (bf16*)dST, ldr);
+    else
+        ibot_grad_t_kernel<float><<<grid, 256, 0, st>>>(S, T, Q, R, K, center, inv_ts, inv_tt, (const float2*)s_stats, (const float2*)t_stats, dloss,
+                                                        (float*)dST, ldr);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+int m3l_op_ibot_center_sum(const float* T, int rows, int K, float scale, void* ws, float* pending, void* stream) {
+    M3L_CHECK(T && ws && pending && rows > 0 && K > 0 && K % 4 == 0, "ibot_center_sum: bad arguments (rows=%d K=%d; K must be a multiple of 4)", rows, K);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows_per = sk_rows_per_split(rows, K), splits = cdiv(rows, rows_per);
+    ProfScope prof("ibot_center_sum", rows, K, splits, (double)rows * K, st, 4.0 * ((double)rows + 2.0 * splits + 1.0) * K);
+    ibot_colsum_part_kernel<<<dim3(cdiv(K, SK_COLS), splits), DINO_THREADS, 0, st>>>(T, rows, K, rows_per, (float*)ws);
+    ibot_colsum_combine_kernel<<<cdiv(K, 256), 256, 0, st>>>((const float*)ws, splits, K, scale, pending);
     M3L_LAUNCH_CHECK();
     return 0;
 }

@@ -404,7 +404,7 @@ int check_tf(const m3l_tf_cfg* c, int B, int n) {
 // =================================================================================================================
 extern "C" {
 
-int m3l_version(void) { return 405; }
+int m3l_version(void) { return 406; }
 
 // diagnostic switch (bench.py's stand-alone roofline figure, PMC passes): 1 = every weight gradient on the caller's stream
 int m3l_set_wgrad_inline(int on) {
@@ -1754,6 +1754,10 @@ size_t m3l_op_gemm_tn_ws_bytes(int M, int N, int K) { return m3l_gemm_tn_ws_byte
 int m3l_op_gemm_tn(int dtype, const void* Y, int ldy, const void* X, int ldx, int M, int N, int K, void* ws, size_t ws_bytes,
                    float* out, int ldo, void* stream) {
     return m3l_gemm_tn(dtype, Y, ldy, X, ldx, M, N, K, (float*)ws, ws_bytes, out, ldo, N, K, 0, (hipStream_t)stream);
+}
+int m3l_op_gemm_tn_acc(int dtype, const void* Y, int ldy, const void* X, int ldx, int M, int N, int K, void* ws, size_t ws_bytes, float* out, int ldo,
+                       int accumulate, void* stream) {
+    return m3l_gemm_tn(dtype, Y, ldy, X, ldx, M, N, K, (float*)ws, ws_bytes, out, ldo, N, K, accumulate ? 1 : 0, (hipStream_t)stream);
 }
 size_t m3l_op_gemm_tn_grouped_ws_bytes(int dtype, int count, int M, const int* N, const int* K) {
     (void)dtype;

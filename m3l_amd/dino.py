@@ -59,6 +59,29 @@ def _gemm_tn(dt, y, x, M, N, K):
     return out
 
 
+TN_OPERAND_LIMIT = 2 ** 31 - 1      # bytes of one operand of m3l_op_gemm_tn (32-bit buffer offsets; include/m3l_amd.h)
+
+
+def _gemm_tn_rows(dt, y, x, M, N, K):
+    """_gemm_tn for a reduction too long for one call: y (M, N) and x (M, K) are cut into chunks of rows whose operands stay below
+    TN_OPERAND_LIMIT, the first chunk overwrites `out`, the others add to it, in row order (the same bits on every run)."""
+    esize = 2 if dt == DT_BF16 else 4
+    if M * max(N, K) * esize < TN_OPERAND_LIMIT:
+        return _gemm_tn(dt, y, x, M, N, K)
+    rows = (TN_OPERAND_LIMIT - 1) // (max(N, K) * esize) // 64 * 64
+    if rows < 64:
+        raise L.M3LError(f"gemm_tn: rows of {max(N, K)} elements are too long to cut the {M}-row reduction into chunks below 2 GiB")
+    lib = L.lib()
+    out = torch.empty(N, K, dtype=torch.float32, device=y.device)
+    for m0 in range(0, M, rows):
+        mc = min(rows, M - m0)
+        nb = lib.m3l_op_gemm_tn_ws_bytes(mc, N, K)
+        ws = _ws(nb, y.device)
+        L.check(lib.m3l_op_gemm_tn_acc(dt, L.ptr(y[m0:m0 + mc]), N, L.ptr(x[m0:m0 + mc]), K, mc, N, K, L.ptr(ws), nb, L.ptr(out), K, int(m0 > 0), _stream()),
+                "m3l_op_gemm_tn_acc (DINO head)")
+    return out
+
+
 def _colsum(dt, y, M, N):
     lib = L.lib()
     out = torch.empty(N, dtype=torch.float32, device=y.device)
@@ -172,7 +195,7 @@ def _last_layer_backward(dt, dST, xn, w, v, g, vnorm, need_dx):
     xnT = _cast(_pad_rows(xn, ldr), dt, transposed=True)              # (D, ldr)
     dW = torch.empty(K, D, dtype=torch.float32, device=dST.device)
     _gemm_nt(dt, dST, xnT, K, D, ldr, out_f32=dW)
-    dx = _gemm_tn(dt, dST, w, K, ldr, D)[:M] if need_dx else None
+    dx = _gemm_tn_rows(dt, dST, w, K, ldr, D)[:M] if need_dx else None
     dv, dg = torch.empty_like(v), torch.empty_like(g)
     L.check(L.lib().m3l_op_weightnorm_bwd(L.ptr(dW), L.ptr(v), L.ptr(g), L.ptr(vnorm), K, D, L.ptr(dv), L.ptr(dg), _stream()), "m3l_op_weightnorm_bwd")
     return dx, dv, dg
@@ -366,6 +389,29 @@ class DINOHead(nn.Module):
         return y.view(*x.shape[:-1], y.shape[-1])
 
 
+@torch.no_grad()
+def _sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations, process_group):
+    """The (K,) float32 vector c with sinkhorn_knopp_teacher(T) = softmax((T - c) / teacher_temp): `n_iterations` column passes over the
+    rows of every rank (each rank's pairs all-gathered over `process_group` and merged in rank order) and n_iterations - 1 local row
+    passes.  Pass it where the loss functions take the centre."""
+    if n_iterations < 1:
+        raise ValueError(f"sinkhorn_knopp: n_iterations = {n_iterations}; without a column normalisation the result is no distribution")
+    T, rows, K = _teacher_rows(teacher_logits)
+    lib = L.lib()
+    temp, inv_temp = float(teacher_temp), 1.0 / float(teacher_temp)
+    center = torch.empty(K, dtype=torch.float32, device=T.device)
+    pairs = torch.empty(K, 2, dtype=torch.float32, device=T.device)
+    ws = _ws(lib.m3l_op_sk_ws_bytes(rows, K), T.device)
+    stats = None
+    for it in range(n_iterations):
+        L.check(lib.m3l_op_sk_colstats(L.ptr(T), rows, K, inv_temp, L.ptr(stats), L.ptr(ws), L.ptr(pairs), _stream()), "m3l_op_sk_colstats")
+        parts = _gather_col_pairs(pairs, process_group) if dist.is_initialized() else pairs
+        L.check(lib.m3l_op_sk_colcombine(L.ptr(parts), parts.numel() // (2 * K), K, temp, L.ptr(center), _stream()), "m3l_op_sk_colcombine")
+        if it < n_iterations - 1:
+            stats = _row_stats(T, rows, K, center, inv_temp)
+    return center
+
+
 class DINOLoss(nn.Module):
     """The loss with its centre.  `forward(student (P, B, K), teacher logits (Q, B, K), teacher_temp)` applies the pending centre update,
     computes the loss against the centred teacher and leaves this step's teacher column sums pending (one-step delay, as the reference's
@@ -420,27 +466,9 @@ class DINOLoss(nn.Module):
         if dist.is_initialized():
             self.reduce_handle = dist.all_reduce(self.async_batch_center, op=dist.ReduceOp.SUM, group=self.process_group, async_op=True)
 
-    @torch.no_grad()
     def sinkhorn_knopp_center(self, teacher_logits, teacher_temp, n_iterations=3):
-        """The (K,) float32 vector c with sinkhorn_knopp_teacher(T) = softmax((T - c) / teacher_temp): `n_iterations` column passes over the
-        rows of every rank (each rank's pairs all-gathered over `process_group` and merged in rank order) and n_iterations - 1 local row
-        passes.  Pass it where the loss functions take the centre."""
-        if n_iterations < 1:
-            raise ValueError(f"sinkhorn_knopp: n_iterations = {n_iterations}; without a column normalisation the result is no distribution")
-        T, rows, K = _teacher_rows(teacher_logits)
-        lib = L.lib()
-        temp, inv_temp = float(teacher_temp), 1.0 / float(teacher_temp)
-        center = torch.empty(K, dtype=torch.float32, device=T.device)
-        pairs = torch.empty(K, 2, dtype=torch.float32, device=T.device)
-        ws = _ws(lib.m3l_op_sk_ws_bytes(rows, K), T.device)
-        stats = None
-        for it in range(n_iterations):
-            L.check(lib.m3l_op_sk_colstats(L.ptr(T), rows, K, inv_temp, L.ptr(stats), L.ptr(ws), L.ptr(pairs), _stream()), "m3l_op_sk_colstats")
-            parts = _gather_col_pairs(pairs, self.process_group) if dist.is_initialized() else pairs
-            L.check(lib.m3l_op_sk_colcombine(L.ptr(parts), parts.numel() // (2 * K), K, temp, L.ptr(center), _stream()), "m3l_op_sk_colcombine")
-            if it < n_iterations - 1:
-                stats = _row_stats(T, rows, K, center, inv_temp)
-        return center
+        """The (K,) float32 vector c with sinkhorn_knopp_teacher(T) = softmax((T - c) / teacher_temp), over `process_group` (_sinkhorn_knopp_center)."""
+        return _sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations, self.process_group)
 
     @torch.no_grad()
     def sinkhorn_knopp_teacher(self, teacher_output, teacher_temp, n_iterations=3):
@@ -528,6 +556,191 @@ class KoLeoLoss(nn.Module):
         keep = {}
         loss = KoLeoFn.apply(student_output, 1, eps, keep)
         self.last = keep["indices"][0]
+        return loss
+
+
+# ---- iBOT patch loss (tactile_ssl/loss/ibot_patch_loss.py) ---------------------------------------------------------------------------------
+IBOT_MAX_ROWS = 65535          # Q R of one call (include/m3l_amd.h, "iBOT patch loss")
+
+
+def _ibot_args(student, teacher, center):
+    _require_cuda(student, "student patch logits")
+    S, T = _f32c(student), _f32c(teacher)
+    if S.dim() != 3 or T.dim() != 3 or S.shape != T.shape:
+        raise ValueError(f"student and teacher patch logits of one shape (Q, R, K) expected, got {tuple(S.shape)} and {tuple(T.shape)}")
+    if S.shape[0] * S.shape[1] > IBOT_MAX_ROWS:
+        raise ValueError(f"iBOT patch loss: {S.shape[0]} x {S.shape[1]} patch rows in one call, at most {IBOT_MAX_ROWS}")
+    c = _f32c(center).reshape(-1)
+    if c.numel() != S.shape[2]:
+        raise ValueError(f"center has {c.numel()} entries for K = {S.shape[2]}")
+    return S, T, c
+
+
+def _ibot_forward(S, T, center, Q, R, K, inv_ts, inv_tt):
+    lib = L.lib()
+    s_stats = _row_stats(S, Q * R, K, None, inv_ts)
+    t_stats = _row_stats(T, Q * R, K, center, inv_tt)
+    loss = torch.empty((), dtype=torch.float32, device=S.device)
+    ws = _ws(lib.m3l_op_ibot_ws_bytes(R, K), S.device)
+    L.check(lib.m3l_op_ibot_loss(L.ptr(S), L.ptr(T), Q, R, K, L.ptr(center), inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats), L.ptr(ws), L.ptr(loss),
+                                 _stream()), "m3l_op_ibot_loss")
+    return loss, s_stats, t_stats
+
+
+def _ibot_grad(dt, S, T, center, Q, R, K, inv_ts, inv_tt, s_stats, t_stats, dloss):
+    """-> dS^T (K, ldr) in the compute type, ldr = Q R rounded up to a multiple of 8 (pad columns zero)."""
+    ldr = _ld8(Q * R)
+    dST = torch.empty(K, ldr, dtype=tdtype(dt), device=S.device)
+    L.check(L.lib().m3l_op_ibot_grad(dt, L.ptr(S), L.ptr(T), Q, R, K, L.ptr(center), inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats), L.ptr(dloss),
+                                     L.ptr(dST), ldr, _stream()), "m3l_op_ibot_grad")
+    return dST
+
+
+class IbotLossFn(torch.autograd.Function):
+    """loss(student (Q, R, K), teacher logits (Q, R, K), center (K)) with an f32 gradient for the student logits: the patch loss on its own."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, center, student_temp, teacher_temp):
+        S, T, c = _ibot_args(student, teacher, center)
+        Q, R, K = S.shape
+        inv_ts, inv_tt = 1.0 / float(student_temp), 1.0 / float(teacher_temp)
+        loss, s_stats, t_stats = _ibot_forward(S, T, c, Q, R, K, inv_ts, inv_tt)
+        ctx.saved = (S, T, c.clone(), Q, R, K, inv_ts, inv_tt, s_stats, t_stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        S, T, c, Q, R, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
+        dST = _ibot_grad(DT_F32, S, T, c, Q, R, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
+        return dST.t()[:Q * R].reshape(Q, R, K), None, None, None, None
+
+
+class IbotHeadLossFn(torch.autograd.Function):
+    """Prototype layer + patch loss in one node: x_n (Q R, D) f32, v, g, teacher logits (Q, R, K), center -> loss.  As HeadLossFn: the gradient
+    kernel writes dS^T in the compute type for the two backward GEMMs of the prototype layer; no f32 (Q R, K) gradient exists."""
+
+    @staticmethod
+    def forward(ctx, dt, Q, xn, v, g, teacher, center, student_temp, teacher_temp, keep):
+        _require_cuda(xn, "iBOT head input")
+        xn, v, g = _f32c(xn), _f32c(v), _f32c(g)
+        M, D = xn.shape
+        K, R = v.shape[0], M // Q
+        w, vnorm = _weightnorm(dt, v, g)
+        S = torch.empty(Q, R, K, dtype=torch.float32, device=xn.device)
+        _gemm_nt(dt, _cast(xn, dt), w, M, K, D, out_f32=S)
+        S, T, c = _ibot_args(S, teacher, center)
+        inv_ts, inv_tt = 1.0 / float(student_temp), 1.0 / float(teacher_temp)
+        loss, s_stats, t_stats = _ibot_forward(S, T, c, Q, R, K, inv_ts, inv_tt)
+        ctx.saved = (dt, xn, w, v, g, vnorm, S, T, c.clone(), Q, R, K, inv_ts, inv_tt, s_stats, t_stats)
+        if keep is not None:
+            keep["student_patch_logits"] = S
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dt, xn, w, v, g, vnorm, S, T, c, Q, R, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
+        dST = _ibot_grad(dt, S, T, c, Q, R, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
+        dx, dv, dg = _last_layer_backward(dt, dST, xn, w, v, g, vnorm, ctx.needs_input_grad[2])
+        return None, None, dx, dv, dg, None, None, None, None, None
+
+
+def _stack_views(x):
+    return torch.stack(list(x)) if isinstance(x, (list, tuple)) else x
+
+
+class iBOTPatchLoss(nn.Module):
+    """The reference's iBOTPatchLoss (`tactile_ssl/loss/ibot_patch_loss.py`) on the row-tiled kernels (m3l_op_ibot_*): buffer `center` (1, 1, K).
+
+    `forward(student_logits, teacher_logits, teacher_temp)` takes the LOGITS of Q student and Q teacher views, (Q, R, K) tensors or lists of Q
+    (R, K) tensors with R = B n patch rows (row r of every student view is paired with row r of every teacher view), and returns the
+    reference's unscaled `forward`: sum over all (student view, teacher view) pairs of the mean over rows of the cross-entropy.  The centre
+    follows this package's DINOLoss: the pending update is applied first, this step's sums are left pending (one-step delay) and are
+    all-reduced asynchronously over `process_group`.  `update_center` takes the reference's (Q B, n, K) teacher tokens: pending = sum_b mean_k,
+    count = Q B x world; handed (Q, R, K), as `forward` is, it takes the Q views as the samples (pending = sum over rows / R, count = Q), which
+    is the same centre.  `centering="sinkhorn_knopp"` takes the Sinkhorn-Knopp targets over all Q R rows and leaves the centre alone.
+
+    `sinkhorn_knopp_teacher(teacher_output, teacher_temp, n_masked_patches_tensor)`: the reference divides by B = n_masked_patches_tensor after
+    each column normalisation, the next normalisation removes any constant factor, and its final `Q *= B` restores the last one, so the
+    argument does not change the result; it is accepted and ignored (tests/golden/ibot_loss.npz pins this with two values).
+
+    Not built: `forward_masked` (nothing in the reference calls it)."""
+
+    def __init__(self, patch_out_dim, student_temp=0.1, center_momentum=0.9, process_group=None):
+        super().__init__()
+        self.student_temp = student_temp
+        self.center_momentum = center_momentum
+        self.register_buffer("center", torch.zeros(1, 1, patch_out_dim))
+        self.process_group = process_group
+        self.updated = True
+        self.reduce_handle = None
+        self.len_teacher_patch_tokens = None
+        self.async_batch_center = None
+
+    @torch.no_grad()
+    def apply_center_update(self):
+        if self.updated is False:
+            world = dist.get_world_size(self.process_group) if dist.is_initialized() else 1
+            if self.reduce_handle is not None:
+                self.reduce_handle.wait()
+                self.reduce_handle = None
+            K = self.center.shape[-1]
+            if self.center.dtype != torch.float32 or not self.center.is_contiguous():
+                raise L.M3LError("iBOTPatchLoss.center must be a contiguous float32 buffer")
+            m = float(self.center_momentum)
+            L.check(L.lib().m3l_op_dino_center_apply(L.ptr(self.center), L.ptr(self.async_batch_center), K, m, 1 - m,
+                                                     float(self.len_teacher_patch_tokens * world), _stream()), "m3l_op_dino_center_apply")
+            self.updated = True
+
+    @torch.no_grad()
+    def update_center(self, teacher_patch_tokens):
+        _require_cuda(teacher_patch_tokens, "teacher patch logits")
+        T = _f32c(teacher_patch_tokens)
+        if T.dim() < 3:
+            raise ValueError(f"iBOTPatchLoss.update_center: (samples, patches, K) teacher logits expected, got {tuple(T.shape)}")
+        lib = L.lib()
+        K, samples = T.shape[-1], T.shape[0]
+        rows = T.numel() // K
+        self.updated = False
+        self.len_teacher_patch_tokens = samples
+        self.async_batch_center = torch.empty(1, K, dtype=torch.float32, device=T.device)
+        ws = _ws(lib.m3l_op_ibot_ws_bytes(rows, K), T.device)
+        L.check(lib.m3l_op_ibot_center_sum(L.ptr(T), rows, K, float(samples) / float(rows), L.ptr(ws), L.ptr(self.async_batch_center), _stream()),
+                "m3l_op_ibot_center_sum")
+        if dist.is_initialized():
+            self.reduce_handle = dist.all_reduce(self.async_batch_center, op=dist.ReduceOp.SUM, group=self.process_group, async_op=True)
+
+    reduce_center_update = update_center
+    def sinkhorn_knopp_center(self, teacher_logits, teacher_temp, n_iterations=3):
+        """The (K,) float32 vector c with sinkhorn_knopp_teacher(T) = softmax((T - c) / teacher_temp), over `process_group` (_sinkhorn_knopp_center)."""
+        return _sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations, self.process_group)
+
+    @torch.no_grad()
+    def sinkhorn_knopp_teacher(self, teacher_output, teacher_temp, n_masked_patches_tensor=None, n_iterations=3):
+        """(rows, K) float32 probabilities.  `n_masked_patches_tensor` cancels (class docstring) and is ignored."""
+        center = self.sinkhorn_knopp_center(teacher_output, teacher_temp, n_iterations)
+        T, rows, K = _teacher_rows(teacher_output)
+        inv_temp = 1.0 / float(teacher_temp)
+        return _probs(T, rows, K, center, inv_temp, _row_stats(T, rows, K, center, inv_temp))
+
+    @torch.no_grad()
+    def softmax_center_teacher(self, teacher_patch_tokens, teacher_temp):
+        """softmax((teacher_patch_tokens - center) / teacher_temp) after the pending centre update, float32 in the shape of the input."""
+        self.apply_center_update()
+        T, rows, K = _teacher_rows(teacher_patch_tokens)
+        inv_temp = 1.0 / float(teacher_temp)
+        center = _f32c(self.center).reshape(-1)
+        return _probs(T, rows, K, center, inv_temp, _row_stats(T, rows, K, center, inv_temp)).view(teacher_patch_tokens.shape)
+
+    def forward(self, student_logits, teacher_logits, teacher_temp, centering="centering", n_iterations=3):
+        student_logits, teacher_logits = _stack_views(student_logits), _stack_views(teacher_logits)
+        if centering == "sinkhorn_knopp":
+            center = self.sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations)
+            return IbotLossFn.apply(student_logits, teacher_logits, center, self.student_temp, teacher_temp)
+        if centering != "centering":
+            raise ValueError(f"iBOTPatchLoss.forward: centering must be 'centering' or 'sinkhorn_knopp', got {centering!r}")
+        self.apply_center_update()
+        loss = IbotLossFn.apply(student_logits, teacher_logits, self.center, self.student_temp, teacher_temp)
+        self.update_center(teacher_logits)
         return loss
 
 

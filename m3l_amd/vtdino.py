@@ -15,6 +15,14 @@ the centre is neither applied nor updated.
 `tactile_ssl/loss/koleo_loss.py` on the student's register rows of the global views: one group per global view, so samples of different
 views are never compared, the views' losses summed, all in one set of launches (KoLeoFn).  At 0.0 the step is the one without it.
 
+`ibot=True` (a trailing keyword; the third term of the reference's DINOv2 algorithm, `tactile_ssl/algorithm/dinov2.py`) adds the iBOT patch loss
+`ibot_patch_loss(student patch logits, teacher patch targets) / num_global_masks`: the patch tokens of the student's global pass (the same
+forward_features call that yields the register rows) go through `dino_head`'s MLP — or `ibot_head`'s with `ibot_separate_head=True`, a
+fresh head in each of the student and teacher dicts — the teacher's global patch tokens through the teacher's, and the prototype layer, the
+cross-entropy over the Q x (B n) patch rows and their backward are one autograd node (IbotHeadLossFn, the row-tiled kernels m3l_op_ibot_*).
+The targets are centred (iBOTPatchLoss.center, one-step delay) or Sinkhorn-Knopp over all patch rows, as `centering` says.  With the
+defaults neither `ibot_patch_loss` nor `ibot_head` exists and the module, its state dict and its step are the ones without the keywords.
+
 Not built: online probes and their logging (a non-empty `online_probes` is refused).
 """
 import copy
@@ -25,15 +33,21 @@ import torch
 from torch import nn
 
 from . import functional as Fn
-from .dino import DINOLoss, HeadLossFn, KoLeoFn, KoLeoLoss, update_moving_average
+from .dino import DINOLoss, HeadLossFn, IbotHeadLossFn, KoLeoFn, KoLeoLoss, iBOTPatchLoss, update_moving_average
 
 
 class VTDINO(nn.Module):
     def __init__(self, encoder, dino_head, optim_cfg, lr_scheduler_cfg, wd_scheduler_cfg, online_probes=None, online_probes_lrs=[],
                  local_mask_scale=(0.2, 0.8), global_mask_scale=(0.2, 0.8), num_global_masks=1, num_local_masks=4, min_keep_num_sensors=4,
                  allow_mask_overlap=False, moving_average_decay=0.99, teacher_temp=(0.04, 0.07), teacher_warmup_epochs=10, use_momentum=True,
-                 log_freq_reconstruction=1000, centering="centering", koleo_weight=0.0):
+                 log_freq_reconstruction=1000, centering="centering", koleo_weight=0.0, ibot=False, ibot_separate_head=False):
         super().__init__()
+        for name, value in (("ibot", ibot), ("ibot_separate_head", ibot_separate_head)):
+            if not isinstance(value, bool):
+                raise ValueError(f"VTDINO({name}=...): True or False expected, got {value!r}")
+        if ibot_separate_head and not ibot:
+            raise ValueError("VTDINO(ibot_separate_head=True) needs ibot=True: without the patch loss nothing would use the head")
+        self.ibot, self.ibot_separate_head = ibot, ibot_separate_head
         if not koleo_weight >= 0:
             raise ValueError(f"VTDINO(koleo_weight=...): a weight >= 0 expected, got {koleo_weight!r}")
         self.koleo_weight = float(koleo_weight)
@@ -62,14 +76,22 @@ class VTDINO(nn.Module):
         self.student_encoder_dict, self.teacher_encoder_dict = dict(), dict()
         self.student_encoder_dict["backbone"] = encoder
         self.student_encoder_dict["dino_head"] = dino_head()
+        if ibot_separate_head:
+            self.student_encoder_dict["ibot_head"] = dino_head()
         self.student_encoder = nn.ModuleDict(self.student_encoder_dict)
         self.teacher_encoder_dict["backbone"] = copy.deepcopy(encoder)
         self.teacher_encoder_dict["dino_head"] = dino_head()          # a fresh head, not a copy of the student's
+        if ibot_separate_head:
+            self.teacher_encoder_dict["ibot_head"] = dino_head()
         self.teacher_encoder = nn.ModuleDict(self.teacher_encoder_dict)
         self.teacher_encoder.requires_grad_(False)
-        for head in (self.student_encoder_dict["dino_head"], self.teacher_encoder_dict["dino_head"]):
-            head.compute_dtype = self.compute_dtype
+        for net in (self.student_encoder_dict, self.teacher_encoder_dict):
+            for name in ("dino_head", "ibot_head"):
+                if name in net:
+                    net[name].compute_dtype = self.compute_dtype
         self.dino_loss = DINOLoss(out_dim=self.student_encoder_dict["dino_head"].last_layer.out_features)
+        if ibot:
+            self.ibot_patch_loss = iBOTPatchLoss(patch_out_dim=self.student_encoder_dict["dino_head"].last_layer.out_features)
         self.koleo_loss = KoLeoLoss()                              # no parameters, no buffers: the state dict is unchanged
 
         self.patch_size = encoder.image_patch_height
@@ -86,6 +108,7 @@ class VTDINO(nn.Module):
         self.val_reconstruction_error = []
         self.last = {}                       # student / teacher logits of the last forward (detached), for inspection
         self.loss_terms = None               # (DINO loss, weighted KoLeo loss) of the last forward when koleo_weight > 0
+        self.loss_parts = None               # {name: term} of the last forward when it has more than the DINO term (ibot, koleo_weight > 0)
 
     @staticmethod
     def _float_or_pair(value, name):
@@ -184,24 +207,28 @@ class VTDINO(nn.Module):
 
     # ---- the step -------------------------------------------------------------------------------------------------------------------
     @staticmethod
-    def _register_rows(backbone, x, masks):
+    def _rows_and_patches(backbone, x, masks):
         out = backbone.forward_features(x, masks)
         assert "x_norm_regtokens" in out, "Dino requires backbone to contain 1 register token"
         reg = out["x_norm_regtokens"]
         assert reg.shape[1] == 1, f"VTDINO needs exactly one register token, the backbone has {reg.shape[1]}"
-        return reg[:, 0]                                    # ((p b), c), view-major
+        return reg[:, 0], out["x_norm_patchtokens"]         # ((p b), c) and ((p b), n, c), view-major
+
+    @classmethod
+    def _register_rows(cls, backbone, x, masks):
+        return cls._rows_and_patches(backbone, x, masks)[0]
 
     def forward(self, x, global_masks, local_masks):
         assert global_masks is not None and local_masks is not None, "Masks are required for DINOModule during training"
         student, teacher = self.student_encoder_dict, self.teacher_encoder_dict
         P, Q = len(global_masks) + len(local_masks), len(global_masks)
-        global_rows = self._register_rows(student["backbone"], x, global_masks)
+        global_rows, global_patches = self._rows_and_patches(student["backbone"], x, global_masks)
         rows = torch.cat([global_rows, self._register_rows(student["backbone"], x, local_masks)], dim=0)
         head = student["dino_head"]
         xn = head.normalized(rows)
         B = xn.shape[0] // P
         with torch.no_grad():
-            t_rows = self._register_rows(teacher["backbone"], x, global_masks)
+            t_rows, t_patches = self._rows_and_patches(teacher["backbone"], x, global_masks)
             t_logits = teacher["dino_head"](t_rows).view(Q, B, -1)
             if self.centering == "sinkhorn_knopp":      # the targets' K-vector stands where the centre stands; the centre itself is never updated
                 center = self.dino_loss.sinkhorn_knopp_center(t_logits.view(Q * B, -1), self.current_teacher_temp)
@@ -213,14 +240,44 @@ class VTDINO(nn.Module):
         self.last["teacher_logits"] = t_logits
         if self.centering != "sinkhorn_knopp":
             self.dino_loss.update_center(t_logits)
-        self.loss_terms = None
+        self.loss_terms = self.loss_parts = None
+        terms = {"dino_loss": loss.detach()}
+        if self.ibot:
+            patch = self._patch_loss(global_patches, t_patches, Q) / self.num_global_masks
+            terms["ibot_loss"] = patch.detach()
+            loss = loss + patch
         if self.koleo_weight > 0:
             # one group per global view (the rows are view-major); local to the rank under data parallelism, as in the reference
             keep = {}
             koleo = self.koleo_weight * KoLeoFn.apply(global_rows, Q, 1e-8, keep)
             self.last["koleo_indices"] = self.koleo_loss.last = keep["indices"]
-            self.loss_terms = (loss.detach(), koleo.detach())
+            terms["koleo_loss"] = koleo.detach()
+            self.loss_terms = (terms["dino_loss"], terms["koleo_loss"])
             loss = loss + koleo
+        if len(terms) > 1:
+            self.loss_parts = terms
+        return loss
+
+    def _patch_loss(self, patches, t_patches, Q):
+        """Unscaled iBOT term: patches ((q b), n, c) of the student's global views, t_patches the teacher's (no gradient)."""
+        student, teacher = self.student_encoder_dict, self.teacher_encoder_dict
+        name = "ibot_head" if self.ibot_separate_head else "dino_head"
+        head, pl = student[name], self.ibot_patch_loss
+        QB, n, _ = patches.shape
+        R = QB // Q * n                                     # rows of a view: r = b n + k
+        xn = head.normalized(patches)
+        with torch.no_grad():
+            t_logits = teacher[name](t_patches)                 # ((q b), n, K)
+            if self.centering == "sinkhorn_knopp":      # over all Q R rows; the centre is never updated
+                center = pl.sinkhorn_knopp_center(t_logits.view(Q * R, -1), self.current_teacher_temp)
+            else:
+                pl.apply_center_update()
+                center = pl.center
+        loss = IbotHeadLossFn.apply(Fn.dtype_code(self.compute_dtype), Q, xn, head.last_layer.weight_v, head.last_layer.weight_g,
+                                    t_logits.view(Q, R, -1), center, pl.student_temp, self.current_teacher_temp, self.last)
+        self.last["teacher_patch_logits"] = t_logits.view(Q, R, -1)
+        if self.centering != "sinkhorn_knopp":
+            pl.update_center(t_logits)
         return loss
 
     def training_step(self, batch, batch_idx):
@@ -228,11 +285,12 @@ class VTDINO(nn.Module):
         self.generator.manual_seed(self.step)
         global_masks, local_masks = self.sample_masks(batch["image"])
         loss = self.forward(batch, global_masks, local_masks)
-        if self.loss_terms is None:
+        if self.loss_parts is None:
             output = {"ssl_loss": loss.item()}
-        else:                                                # the three scalars in one device-to-host copy
-            total, dino, koleo = torch.stack((loss.detach(),) + self.loss_terms).tolist()
-            output = {"ssl_loss": total, "dino_loss": dino, "koleo_loss": koleo}
+        else:                                                # every scalar in one device-to-host copy
+            names = list(self.loss_parts)
+            values = torch.stack([loss.detach()] + [self.loss_parts[k] for k in names]).tolist()
+            output = dict(zip(["ssl_loss"] + names, values))
         online_probes_loss = 0.0
         output["loss"] = loss
         output["online_probes_loss"] = online_probes_loss

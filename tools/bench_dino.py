@@ -13,9 +13,13 @@ that never passes), B = 32, in bf16 and in fp32.
 
 --centering sinkhorn_knopp runs the step with the Sinkhorn-Knopp teacher targets (three column passes and two extra row passes over the
 64 x 65536 teacher logits per step, no centre update).  --koleo-weight W runs it with VTDINO(koleo_weight=W): the KoLeo regulariser over the
-two global views' register rows (2 groups of 32 rows of 256), 3 + 1 launches per step.
+two global views' register rows (2 groups of 32 rows of 256), 3 + 1 launches per step.  --ibot runs it with VTDINO(ibot=True): the iBOT patch loss
+over the 2 x (32 x 3 n) patch rows of the global views (n = 25 to 64 patches of the 8 x 8 grid per modality at this global scale), through
+`dino_head` or, with --ibot-separate-head, a head of its own.  Every run also reports the peak device memory of the timed steps, so a run with and
+one without --ibot in the same job give the term's cost in time and memory.
 
-There is no pass mark.  Usage: python tools/bench_dino.py [--centering sinkhorn_knopp] [--koleo-weight 0.1]  (one JSON line on stdout)"""
+There is no pass mark.  Usage: python tools/bench_dino.py [--centering sinkhorn_knopp] [--koleo-weight 0.1] [--ibot [--ibot-separate-head]]
+(one JSON line on stdout)"""
 import argparse
 import ctypes as C
 import json
@@ -32,10 +36,10 @@ from m3l_amd import _lib as L  # noqa: E402
 DEV = "cuda:0"
 HBM_TBS = 6.3
 B, N_GLOBAL, N_LOCAL, K_OUT = 32, 2, 8, 65536
-NEW_KINDS = ("dino_", "sk_", "koleo_", "l2norm", "weightnorm", "ema")
+NEW_KINDS = ("dino_", "sk_", "koleo_", "ibot_", "l2norm", "weightnorm", "ema")
 
 
-def build(dt, centering="centering", koleo_weight=0.0):
+def build(dt, centering="centering", koleo_weight=0.0, ibot=False, ibot_separate_head=False):
     torch.manual_seed(0)
     enc = m3l_amd.DinoVTT(image_size=64, tactile_size=32, image_patch_size=8, tactile_patch_size=4, dim=256, depth=4, heads=8, mlp_dim=512,
                           num_tactiles=2, num_register_tokens=1, compute_dtype=dt)
@@ -46,7 +50,8 @@ def build(dt, centering="centering", koleo_weight=0.0):
                            local_mask_scale=(0.2, 0.48), global_mask_scale=(0.48, 1.0), num_global_masks=N_GLOBAL, num_local_masks=N_LOCAL,
                            min_keep_num_sensors=4, allow_mask_overlap=True, moving_average_decay=[0.994, 1.0], teacher_temp=[0.04, 0.07],
                            **({} if centering == "centering" else {"centering": centering}),
-                           **({"koleo_weight": koleo_weight} if koleo_weight else {})).to(DEV)
+                           **({"koleo_weight": koleo_weight} if koleo_weight else {}),
+                           **({"ibot": True, "ibot_separate_head": ibot_separate_head} if ibot else {})).to(DEV)
     opt, lr_entry, _ = model.configure_optimizers(100, 10)
     model.lr_scheduler = lr_entry["scheduler"]
     g = torch.Generator().manual_seed(1)
@@ -86,18 +91,20 @@ def classes():
     return out
 
 
-def run(dt, steps, warmup, prof_steps, centering="centering", koleo_weight=0.0):
-    model, opt, x = build(dt, centering, koleo_weight)
+def run(dt, steps, warmup, prof_steps, centering="centering", koleo_weight=0.0, ibot=False, ibot_separate_head=False):
+    model, opt, x = build(dt, centering, koleo_weight, ibot, ibot_separate_head)
     for i in range(warmup):
         loss = step(model, opt, x, i)
     torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for i in range(warmup, warmup + steps):
         loss = step(model, opt, x, i)
     e1.record()
     torch.cuda.synchronize()
-    res = {"ms_per_step": round(e0.elapsed_time(e1) / steps, 3), "loss_last": round(loss, 4)}
+    res = {"ms_per_step": round(e0.elapsed_time(e1) / steps, 3), "loss_last": round(loss, 4),
+           "peak_memory_mb": round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)}
     L.lib().m3l_prof_begin(None, 1)
     for i in range(prof_steps):
         step(model, opt, x, warmup + steps + i)
@@ -115,7 +122,7 @@ def run(dt, steps, warmup, prof_steps, centering="centering", koleo_weight=0.0):
                           for k, v in sorted(cls.items()) if k.startswith(NEW_KINDS)}
     res["head_gemms"] = {k: {"us_per_launch": round(v[0] / v[1] * 1e3, 1), "launches_per_step": v[1] / prof_steps}
                          for k, v in sorted(cls.items()) if is_head(k) and not k.startswith(NEW_KINDS)}
-    res["loss_kernel_mb_per_step"] = round(sum(v[2] for k, v in cls.items() if k.startswith("dino_")) / prof_steps / 1e6, 1)
+    res["loss_kernel_mb_per_step"] = round(sum(v[2] for k, v in cls.items() if k.startswith(("dino_", "ibot_"))) / prof_steps / 1e6, 1)
     return res
 
 
@@ -127,11 +134,15 @@ def main():
     ap.add_argument("--dtypes", default="bf16,fp32")
     ap.add_argument("--centering", default="centering", choices=["centering", "sinkhorn_knopp"], help="teacher targets (VTDINO's keyword)")
     ap.add_argument("--koleo-weight", type=float, default=0.0, help="VTDINO's koleo_weight (0 = the step without the regulariser)")
+    ap.add_argument("--ibot", action="store_true", help="VTDINO(ibot=True): add the iBOT patch loss")
+    ap.add_argument("--ibot-separate-head", action="store_true", help="with --ibot: VTDINO(ibot_separate_head=True)")
     a = ap.parse_args()
+    if a.ibot_separate_head and not a.ibot:
+        ap.error("--ibot-separate-head needs --ibot")
     out = {"config": f"DinoVTT 256/4/8/512 + head 256-2048-2048-256-{K_OUT}, B={B}, {N_GLOBAL}+{N_LOCAL} views", "hbm_tb_per_s": HBM_TBS,
-           "centering": a.centering, "koleo_weight": a.koleo_weight}
+           "centering": a.centering, "koleo_weight": a.koleo_weight, "ibot": a.ibot, "ibot_separate_head": a.ibot_separate_head}
     for dt in a.dtypes.split(","):
-        out[dt] = run(dt, a.steps, a.warmup, a.prof_steps, a.centering, a.koleo_weight)
+        out[dt] = run(dt, a.steps, a.warmup, a.prof_steps, a.centering, a.koleo_weight, a.ibot, a.ibot_separate_head)
         torch.cuda.empty_cache()
     print(json.dumps(out))
 
