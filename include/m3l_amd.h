@@ -379,6 +379,32 @@ int m3l_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
  * corrections (float[2] scratch), so a captured launch stays correct on every replay (torch's Adam(capturable=True)) */
 int m3l_adam_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int* step_dev, float* bias_corr_dev, void* stream);
+/* DinoAdamW (ABI 407): the whole optimizer tail of a DINO iteration over flat fp32 buffers of n elements — clip_grad_norm_, AdamW with
+ * per-group lr / weight decay, and the teacher's moving average — as the two reduction launches of m3l_adamw_step plus ONE update launch.
+ *   seg_start[n_segments + 1] (int64, DEVICE memory): ascending, seg_start[0] = 0, seg_start[n_segments] = n; boundaries are arbitrary
+ *   seg_group[n_segments]     (int32, DEVICE memory): the hyper-parameter group of each segment, or -1
+ *   group_lr / group_weight_decay [n_groups <= 8] (HOST memory): read during the call and handed to the kernel by value, so a scheduler
+ *     that changes them every step costs no copy
+ * The tables belong to the caller and live on the device: the call cannot read them.  It is the CALLER's duty that seg_start ends at n
+ * and that every group index is -1 or below n_groups; whatever they hold, no element outside [0, n) and no table entry outside
+ * seg_start[0 .. n_segments - 1] / seg_group[0 .. n_segments - 1] is touched, and an index outside [0, n_groups) is taken as -1.
+ * Group k >= 0: torch.optim.AdamW's update with lr_k, weight_decay_k, the per-element arithmetic of m3l_adamw_step.  beta1 / beta2 are
+ * doubles: 1 - beta and the bias corrections 1 - beta^step are formed in double and rounded to f32 once, as torch forms them
+ * (m3l_adamw_step takes float betas and subtracts in f32: its 1 - 0.999f is 1.3e-5 away from torch's, and its second moment with it;
+ * so for uniform hyper-parameters the two entries agree to rounding, not to the bit).
+ * Group -1 (a parameter that received no gradient: torch skips `.grad is None`): params and both moments are neither changed nor written;
+ * its gradient slots must hold zeros if the clip is on (they then do not change the norm).
+ * teacher != NULL: every element, group -1 included, then gets teacher = teacher * b + (1 - b) * params_new with b = (float)ema_beta and
+ * (1 - b) = (float)(1.0 - ema_beta), each product rounded on its own: the bits of m3l_op_ema(teacher, params, beta, 1 - beta) run after the
+ * step.  teacher == NULL: no moving average, ema_beta ignored.
+ * step >= 1, grad_scale, max_grad_norm (<= 0: no clip, norm_ws may be NULL), norm_ws (1026 floats: [1024] coefficient, [1025] norm) and
+ * scale_grads as in m3l_adamw_step.  Errors (returned before any device call, nothing written): a NULL buffer / table / array, n < 1,
+ * step < 1, n_segments < 1, n_groups outside 1..8, a base pointer (params, grads, exp_avg, exp_avg_sq, teacher) not 16-byte aligned,
+ * clipping without norm_ws.  No allocation, no float atomics, fixed summation order, graph-capturable. */
+int m3l_dino_opt_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* teacher, long n, const int64_t* seg_start,
+                      const int32_t* seg_group, int n_segments, const float* group_lr, const float* group_weight_decay, int n_groups,
+                      double beta1, double beta2, float eps, int step, float grad_scale, float max_grad_norm, float* norm_ws, int scale_grads,
+                      double ema_beta, void* stream);
 
 /* ---- in-library HIP-event timing of kernel classes (bench.py roofline).  filter: substring of "kind[AxBxC]" or NULL = all;
  * stride: bracket every stride-th matching launch (sampling keeps the perturbation of the timed region small). */

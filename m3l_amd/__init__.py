@@ -5,8 +5,9 @@ from .pretrain_models import VTMAE, VTT, Transformer  # noqa: F401
 from .dino_vtt import VTT as DinoVTT  # noqa: F401  (reference: models/VTT.py — a second class that is also called VTT)
 from .dino import DINOHead, DINOLoss, KoLeoLoss, iBOTPatchLoss, update_moving_average  # noqa: F401  (reference: tactile_ssl dino_head.py, dino_loss.py, koleo_loss.py, utils/ema.py)
 from .vtdino import VTDINO  # noqa: F401  (reference: models/vtdino.py)
+from .optim import CosineWDSchedule, DinoAdamW, WarmupCosineScheduler  # noqa: F401  (reference: trainer.py:305-342, tactile_ssl/model/custom_scheduler.py)
 from .pretrain_utils import vt_load  # noqa: F401
 from .dinov2 import DinoV2Frozen  # noqa: F401  (reference: torch.hub dinov2_vits14_reg, train_dino_cat_mae.py:29)
 from .fusion import DinoCatMAEExtractor, MAEExtractor  # noqa: F401  (reference: MAEExtractor, models/pretrain_models.py:788-841 and models/pretrain_models_dino_cat_mae.py:793-904)
 
-__all__ = ["VTT", "VTMAE", "Transformer", "DinoVTT", "VTDINO", "DINOHead", "DINOLoss", "KoLeoLoss", "iBOTPatchLoss", "update_moving_average", "DinoV2Frozen", "DinoCatMAEExtractor", "MAEExtractor", "vt_load", "M3LError", "LIB_PATH"]
+__all__ = ["VTT", "VTMAE", "Transformer", "DinoVTT", "VTDINO", "DINOHead", "DINOLoss", "KoLeoLoss", "iBOTPatchLoss", "update_moving_average", "DinoAdamW", "WarmupCosineScheduler", "CosineWDSchedule", "DinoV2Frozen", "DinoCatMAEExtractor", "MAEExtractor", "vt_load", "M3LError", "LIB_PATH"]

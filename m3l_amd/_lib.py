@@ -126,6 +126,8 @@ _SIGS = {
     "m3l_adamw_step": (c_i, [c_p, c_p, c_p, c_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, c_i, C.c_float, C.c_float, c_p, c_i, c_p]),
     "m3l_adam_step": (c_i, [c_p, c_p, c_p, c_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, c_i, c_p]),
     "m3l_adam_step_scaled": (c_i, [c_p, c_p, c_p, c_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, c_i, C.c_float, c_p]),
+    "m3l_dino_opt_step": (c_i, [c_p, c_p, c_p, c_p, c_p, C.c_long, c_p, c_p, c_i, C.POINTER(C.c_float), C.POINTER(C.c_float), c_i,
+                                C.c_double, C.c_double, C.c_float, c_i, C.c_float, C.c_float, c_p, c_i, C.c_double, c_p]),
     "m3l_prof_begin": (None, [C.c_char_p, c_i]),
     "m3l_prof_end": (None, []),
     "m3l_prof_event_overhead_us": (C.c_double, [c_p, c_i]),

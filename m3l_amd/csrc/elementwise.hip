@@ -537,6 +537,21 @@ __global__ __launch_bounds__(256) void tokens_assemble_bwd_kernel(const float* _
         part[(long)blockIdx.x * PL + i] = sm[i] + sm[PL + i] + sm[2 * PL + i] + sm[3 * PL + i];
 }
 
+// One element of torch's Adam / AdamW update, for adam_flat_kernel and dino_opt_kernel alike (one text for both); g is left scaled.
+// omb1 / omb2: the factors 1 - beta1 and 1 - beta2 as the caller rounds them (adam_flat_kernel: 1.0f - b in f32, the bits it always gave;
+// dino_opt_kernel: formed in double from the double betas and rounded once, as torch forms the scalars of lerp_ and addcmul_).
+template <int DEC>
+__device__ __forceinline__ void adam_elem(float& p, float& g, float& m, float& v, float gscale, float lr, float omb1, float b2, float omb2,
+                                          float eps, float wd, float bc1, float bc2_sqrt) {
+    g = g * gscale;                                             // gscale: 1 / world of a SUM all-reduce (1.0f is exact)
+    if (DEC) p = p * wd;                                        // DEC: wd carries the factor 1 - lr * weight_decay
+    const float gr = DEC ? g : g + wd * p;
+    m = m + (gr - m) * omb1;                                    // lerp, as torch: exp_avg.lerp_(grad, 1 - beta1)
+    v = v * b2 + omb2 * gr * gr;
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = p - (lr / bc1) * (m / denom);
+}
+
 // Adam over ONE flat parameter / gradient / moment buffer (reference optimizer: torch.optim.Adam(mae.parameters(), lr=1e-4),
 // models/ppo_mae.py:182-183): same update rule and operation order as torch's, one launch for all 7.3 M parameters.
 // DEC = 1: torch.optim.AdamW (the optimizer of VTMAE.initialize_training, pretrain_models.py:675): decoupled weight decay, p *= 1 - lr wd
@@ -559,13 +574,9 @@ __global__ void adam_flat_kernel(float* __restrict__ p, float* __restrict__ g, f
         f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            gg[j] = gg[j] * gscale;                                     // gscale: 1 / world of a SUM all-reduce (1.0f is exact)
-            if (DEC) pp[j] = pp[j] * wd;                                // DEC: wd carries the factor 1 - lr * weight_decay
-            const float gr = DEC ? gg[j] : gg[j] + wd * pp[j];
-            mm[j] = mm[j] + (gr - mm[j]) * (1.0f - b1);                 // lerp, as torch: exp_avg.lerp_(grad, 1 - beta1)
-            vv[j] = vv[j] * b2 + (1.0f - b2) * gr * gr;
-            const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-            pp[j] = pp[j] - (lr / bc1) * (mm[j] / denom);
+            float pj = pp[j], gj = gg[j], mj = mm[j], vj = vv[j];      // (a vector element cannot bind to a reference)
+            adam_elem<DEC>(pj, gj, mj, vj, gscale, lr, 1.0f - b1, b2, 1.0f - b2, eps, wd, bc1, bc2_sqrt);
+            pp[j] = pj; gg[j] = gj; mm[j] = mj; vv[j] = vj;
         }
         *reinterpret_cast<f32x4*>(p + i) = pp;
         *reinterpret_cast<f32x4*>(m + i) = mm;
@@ -573,13 +584,12 @@ __global__ void adam_flat_kernel(float* __restrict__ p, float* __restrict__ g, f
         if (scale_g) *reinterpret_cast<f32x4*>(g + i) = gg;
     } else {
         for (long k = i; k < n; ++k) {
-            const float gs = g[k] * gscale;
-            if (DEC) p[k] = p[k] * wd;
-            const float gr = DEC ? gs : gs + wd * p[k];
-            m[k] = m[k] + (gr - m[k]) * (1.0f - b1);
-            v[k] = v[k] * b2 + (1.0f - b2) * gr * gr;
-            p[k] = p[k] - (lr / bc1) * (m[k] / (sqrtf(v[k]) / bc2_sqrt + eps));
-            if (scale_g) g[k] = gs;
+            float pk = p[k], gk = g[k], mk = m[k], vk = v[k];
+            adam_elem<DEC>(pk, gk, mk, vk, gscale, lr, 1.0f - b1, b2, 1.0f - b2, eps, wd, bc1, bc2_sqrt);
+            p[k] = pk;
+            m[k] = mk;
+            v[k] = vk;
+            if (scale_g) g[k] = gk;
         }
     }
 }
@@ -612,6 +622,104 @@ __global__ __launch_bounds__(64) void gradnorm_final_kernel(const float* __restr
         const float c = max_norm / (norm + 1e-6f);
         out[0] = c < 1.0f ? c : 1.0f;
         out[1] = norm;
+    }
+}
+
+// DinoAdamW (m3l_dino_opt_step): the AdamW update of adam_flat_kernel<1> with PER-SEGMENT hyper-parameters, and the teacher's moving
+// average of ema_kernel, in one pass over the flat buffers.  The flat range [0, n) is cut into S segments (seg_start[S + 1] ascending from 0
+// to n, seg_group[S] = a group index or -1, both in device memory); group k carries lr[k] and decay[k] = 1 - lr_k wd_k by value.  Group -1
+// (a parameter without a gradient: torch.optim.AdamW skips `.grad is None`): p, m, v are not written.  With a teacher every element,
+// group -1 included, gets t = t * beta + (1 - beta) * p_new.  A workgroup owns DOPT_BLOCK_ELEMS consecutive elements: it binary-searches
+// the segment of its first element, each thread then walks forward from there; four elements inside one segment move as 16 bytes, a
+// quad across a boundary (or the ragged end) goes element by element.  The walk never reads seg_start past its entry S - 1 and no element
+// index reaches n, whatever the tables hold.
+#define DOPT_BLOCK_ELEMS 4096
+#define DOPT_MAX_GROUPS 8
+struct DinoOptHyper {
+    float lr[DOPT_MAX_GROUPS];
+    float decay[DOPT_MAX_GROUPS];
+    int count;
+};
+// (selects, not an indexed read: a per-lane index into a by-value argument would send the arrays to scratch memory)
+__device__ __forceinline__ void dopt_hyper(const DinoOptHyper& hp, int k, float& lr, float& decay) {
+    lr = hp.lr[0];
+    decay = hp.decay[0];
+#pragma unroll
+    for (int j = 1; j < DOPT_MAX_GROUPS; ++j)
+        if (k == j) {
+            lr = hp.lr[j];
+            decay = hp.decay[j];
+        }
+}
+// (no contraction into an fma: each product is rounded on its own, the expression of ema_kernel in dino.hip)
+__device__ __forceinline__ float dopt_ema(float t, float p, float beta, float one_minus) {
+#pragma clang fp contract(off)
+    return t * beta + one_minus * p;
+}
+__global__ __launch_bounds__(256) void dino_opt_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                       float* __restrict__ t, long n, const int64_t* __restrict__ seg_start,
+                                                       const int* __restrict__ seg_group, int S, const DinoOptHyper hp, float omb1, float b2, float omb2,
+                                                       float eps, float bc1, float bc2_sqrt, float gscale, const float* __restrict__ clip_dev,
+                                                       int scale_g, float ema_b, float ema_1mb) {
+    const long e0 = (long)blockIdx.x * DOPT_BLOCK_ELEMS;
+    const long e1 = e0 + DOPT_BLOCK_ELEMS < n ? e0 + DOPT_BLOCK_ELEMS : n;
+    if (clip_dev) gscale *= clip_dev[0];
+    int lo = 0, hi = S;                 // the segment of this workgroup's first element: last s with seg_start[s] <= e0
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (seg_start[mid] <= e0) lo = mid; else hi = mid;
+    }
+    int s = lo;
+    for (long e = e0 + threadIdx.x * 4; e < e1; e += 1024) {
+        while (s + 1 < S && seg_start[s + 1] <= e) ++s;
+        const long seg_end = s + 1 < S ? (long)seg_start[s + 1] : n;
+        if (e + 4 <= e1 && e + 4 <= seg_end) {
+            int k = seg_group[s];
+            if ((unsigned)k >= (unsigned)hp.count) k = -1;
+            f32x4 pp = *reinterpret_cast<const f32x4*>(p + e);
+            if (k >= 0) {
+                float lr, decay;
+                dopt_hyper(hp, k, lr, decay);
+                f32x4 gg = *reinterpret_cast<const f32x4*>(g + e), mm = *reinterpret_cast<const f32x4*>(m + e);
+                f32x4 vv = *reinterpret_cast<const f32x4*>(v + e);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float pj = pp[j], gj = gg[j], mj = mm[j], vj = vv[j];
+                    adam_elem<1>(pj, gj, mj, vj, gscale, lr, omb1, b2, omb2, eps, decay, bc1, bc2_sqrt);
+                    pp[j] = pj; gg[j] = gj; mm[j] = mj; vv[j] = vj;
+                }
+                *reinterpret_cast<f32x4*>(p + e) = pp;
+                *reinterpret_cast<f32x4*>(m + e) = mm;
+                *reinterpret_cast<f32x4*>(v + e) = vv;
+                if (scale_g) *reinterpret_cast<f32x4*>(g + e) = gg;
+            }
+            if (t) {
+                f32x4 tt = *reinterpret_cast<const f32x4*>(t + e);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) tt[j] = dopt_ema(tt[j], pp[j], ema_b, ema_1mb);
+                *reinterpret_cast<f32x4*>(t + e) = tt;
+            }
+        } else {
+            const long q1 = e + 4 < e1 ? e + 4 : e1;
+            int s2 = s;
+            for (long q = e; q < q1; ++q) {
+                while (s2 + 1 < S && seg_start[s2 + 1] <= q) ++s2;
+                int k = seg_group[s2];
+                if ((unsigned)k >= (unsigned)hp.count) k = -1;
+                float pq = p[q];
+                if (k >= 0) {
+                    float lr, decay;
+                    dopt_hyper(hp, k, lr, decay);
+                    float gq = g[q], mq = m[q], vq = v[q];
+                    adam_elem<1>(pq, gq, mq, vq, gscale, lr, omb1, b2, omb2, eps, decay, bc1, bc2_sqrt);
+                    p[q] = pq;
+                    m[q] = mq;
+                    v[q] = vq;
+                    if (scale_g) g[q] = gq;
+                }
+                if (t) t[q] = dopt_ema(t[q], pq, ema_b, ema_1mb);
+            }
+        }
     }
 }
 
@@ -1554,6 +1662,48 @@ int m3l_adamw_flat(float* p, float* g, float* m, float* v, long n, float lr, flo
     const float decay = (float)(1.0 - (double)lr * (double)wd);      // as torch: param.mul_(1 - lr * weight_decay), the factor formed in double
     adam_flat_kernel<1><<<cdiv(cdiv(n, 4), 256), 256, 0, st>>>(p, g, m, v, n, lr, b1, b2, eps, decay, bc1, bc2_sqrt, nullptr, gscale, clip,
                                                               scale_grads && (clip || gscale != 1.0f));
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+// DinoAdamW: the clip of m3l_adamw_flat (same two launches over the whole buffer, same workspace layout) + dino_opt_kernel.  lr / wd: host
+// arrays of n_groups <= 8 entries, read here and handed to the kernel by value; ema_beta: a double, rounded as the host loop rounds the two
+// factors it hands to m3l_op_ema — (float)beta and (float)(1.0 - beta).  beta1 / beta2: doubles too, so that 1 - beta is torch's scalar
+// ((float)(1.0 - 0.999) = 1.0000000e-3; 1.0f - 0.999f = 0.9999871e-3 is 1.3e-5 away, which the second moment would carry).
+int m3l_dino_opt_flat(float* p, float* g, float* m, float* v, float* teacher, long n, const int64_t* seg_start, const int* seg_group, int S,
+                      const float* lr, const float* wd, int n_groups, double beta1, double beta2, float eps, int step, float gscale, float max_norm,
+                      float* norm_ws, int scale_grads, double ema_beta, hipStream_t st) {
+    M3L_CHECK(p && g && m && v && seg_start && seg_group && lr && wd, "dino_opt: a buffer, a segment table or a hyper-parameter array is null");
+    M3L_CHECK(n >= 1 && step >= 1 && S >= 1, "dino_opt: n=%ld step=%d segments=%d (each must be >= 1)", n, step, S);
+    M3L_CHECK(n_groups >= 1 && n_groups <= DOPT_MAX_GROUPS, "dino_opt: %d groups (1 to %d)", n_groups, DOPT_MAX_GROUPS);
+    M3L_CHECK((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)teacher) & 15) == 0,
+              "dino_opt: params, grads, both moments and the teacher must be 16-byte aligned");
+    M3L_CHECK(max_norm <= 0.f || norm_ws, "dino_opt: clipping needs the norm workspace");
+    const long blocks = (n + DOPT_BLOCK_ELEMS - 1) / DOPT_BLOCK_ELEMS;
+    M3L_CHECK(blocks < 2147483647L, "dino_opt: too many elements for one launch");
+    // the scalars as torch forms them: in double (Python floats) from the double betas, rounded to f32 once
+    const float bc1 = (float)(1.0 - pow(beta1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
+    DinoOptHyper hp;
+    memset(&hp, 0, sizeof(hp));
+    hp.count = n_groups;
+    for (int k = 0; k < n_groups; ++k) {
+        hp.lr[k] = lr[k];
+        hp.decay[k] = (float)(1.0 - (double)lr[k] * (double)wd[k]);      // as m3l_adamw_flat forms it
+    }
+    const float* clip = nullptr;
+    if (max_norm > 0.f) {
+        const int G = (int)std::min<long>(1024, cdiv(cdiv(n, 4), 256));
+        gradnorm_part_kernel<<<G, 256, 0, st>>>(g, n, norm_ws);
+        M3L_LAUNCH_CHECK();
+        gradnorm_final_kernel<<<1, 64, 0, st>>>(norm_ws, G, gscale, max_norm, norm_ws + 1024);
+        M3L_LAUNCH_CHECK();
+        clip = norm_ws + 1024;
+    }
+    ProfScope prof("dino_opt", n, S, teacher ? 1 : 0, 12.0 * n, st, 4.0 * (teacher ? 9.0 : 7.0) * n);
+    dino_opt_kernel<<<(int)blocks, 256, 0, st>>>(p, g, m, v, teacher, n, seg_start, seg_group, S, hp, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, bc1,
+                                                 bc2_sqrt, gscale, clip,
+                                                 scale_grads && (clip || gscale != 1.0f), (float)ema_beta, (float)(1.0 - ema_beta));
     M3L_LAUNCH_CHECK();
     return 0;
 }

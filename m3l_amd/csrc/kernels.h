@@ -267,6 +267,9 @@ int m3l_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr
                   float gscale, hipStream_t st);
 int m3l_adamw_flat(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd, int step, float gscale,
                    float max_norm, float* norm_ws, int scale_grads, hipStream_t st);
+int m3l_dino_opt_flat(float* p, float* g, float* m, float* v, float* teacher, long n, const int64_t* seg_start, const int* seg_group, int S,
+                      const float* lr, const float* wd, int n_groups, double beta1, double beta2, float eps, int step, float gscale, float max_norm,
+                      float* norm_ws, int scale_grads, double ema_beta, hipStream_t st);
 int m3l_adam_flat_dev(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd,
                       int* step_dev, float* bc_dev, hipStream_t st);
 struct MaskRankGroup { const float* noise; int n, nm, token_offset, masked_off, unmasked_off; };

@@ -404,7 +404,7 @@ int check_tf(const m3l_tf_cfg* c, int B, int n) {
 // =================================================================================================================
 extern "C" {
 
-int m3l_version(void) { return 406; }
+int m3l_version(void) { return 407; }
 
 // diagnostic switch (bench.py's stand-alone roofline figure, PMC passes): 1 = every weight gradient on the caller's stream
 int m3l_set_wgrad_inline(int on) {
@@ -1736,6 +1736,14 @@ int m3l_adamw_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
                    float weight_decay, int step, float grad_scale, float max_grad_norm, float* norm_ws, int scale_grads, void* stream) {
     return m3l_adamw_flat(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, max_grad_norm, norm_ws,
                           scale_grads, (hipStream_t)stream);
+}
+
+int m3l_dino_opt_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* teacher, long n, const int64_t* seg_start,
+                      const int32_t* seg_group, int n_segments, const float* group_lr, const float* group_weight_decay, int n_groups,
+                      double beta1, double beta2, float eps, int step, float grad_scale, float max_grad_norm, float* norm_ws, int scale_grads,
+                      double ema_beta, void* stream) {
+    return m3l_dino_opt_flat(params, grads, exp_avg, exp_avg_sq, teacher, n, seg_start, seg_group, n_segments, group_lr, group_weight_decay,
+                             n_groups, beta1, beta2, eps, step, grad_scale, max_grad_norm, norm_ws, scale_grads, ema_beta, (hipStream_t)stream);
 }
 
 int m3l_adam_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,

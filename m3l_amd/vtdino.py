@@ -101,7 +101,8 @@ class VTDINO(nn.Module):
         self.online_probes_lrs = online_probes_lrs
 
         self.momentum_scheduler = None
-        self.moving_average_decay = self._float_or_pair(moving_average_decay, "moving_average_decay")
+        self._ema_in_step = False            # set by DinoAdamW.step() (bound teacher): this batch's moving average is already applied
+        self.moving_average_decay =self._float_or_pair(moving_average_decay, "moving_average_decay")
         self.teacher_temp_scheduler = None
         self.teacher_temp = self._float_or_pair(teacher_temp, "teacher_temp")
         self.teacher_warmup_epochs = teacher_warmup_epochs
@@ -302,9 +303,16 @@ class VTDINO(nn.Module):
     def on_train_batch_end(self, outputs, batch, batch_idx, trainer_instance=None):
         assert self.teacher_encoder is not None, "target encoder has not been created"
         self.current_teacher_temp = next(self.teacher_temp_scheduler) if self.teacher_temp_scheduler is not None else self.teacher_temp
+        if self._ema_in_step:      # a DinoAdamW with this model's teacher bound drew the decay and applied the average inside its step()
+            self._ema_in_step = False
+            return
         if self.use_momentum:
-            beta = next(self.momentum_scheduler) if self.momentum_scheduler is not None else self.moving_average_decay
-            update_moving_average(self.teacher_encoder, self.student_encoder, beta)
+            update_moving_average(self.teacher_encoder, self.student_encoder, self.next_moving_average_decay())
+
+    def next_moving_average_decay(self):
+        """The teacher's decay for the next update: the next value of the schedule configure_optimizers() set up, or the constant.  Each
+        call consumes one value (on_train_batch_end, or DinoAdamW.step() with a bound teacher — never both for one batch)."""
+        return next(self.momentum_scheduler) if self.momentum_scheduler is not None else self.moving_average_decay
 
     def configure_optimizers(self, num_iterations_per_epoch, num_epochs):
         params = [p for pn, p in self.named_parameters() if not pn.startswith("online_probes") and p.requires_grad]
