@@ -1,0 +1,406 @@
+"""float64 restatement of the pre-norm transformer stack, forward AND backward written out.  *** TEST INFRASTRUCTURE ONLY ***
+
+`run(x, cot, P, prefix, depth, heads, dim_head, rc)` is oracle.vtmae_oracle.transformer plus the gradient of <y, cot> with respect to x and to
+every parameter, in plain CPU torch.  It returns y, dx, the parameter gradients and, per layer, every tensor the workspace of
+m3l_amd/csrc/mae_plan.hip keeps (TfLayer: xn1, qkv, o, lse, x1, xn2, u, h, xout).  tests/test_tf_refs_cpu.py anchors it to the oracle's
+autograd (1e-12) and to the reference's own recorded block (tests/golden/block_stack.npz).
+
+Three ways to evaluate it:
+
+  X  rc = EXACT, float64          no rounding, erf GELU: the truth
+  F  rc = EXACT, float32          the same arithmetic in float32: the yardstick of the fp32 kernels
+  R  rc = recipe(...), float64    float64 arithmetic BETWEEN the points where the bf16 plan stores a compute-type tensor or rounds an MFMA
+                                  operand, and the fitted GELU of common.cuh (gelu_fast / gelu_grad_fast restated below), so that the fit
+                                  error sits inside |R - X|
+
+The rounding points of R, each read off the code.  Cited by kernel or function of m3l_amd/csrc (a line number, where given, is that of
+commit ec2aef2 and only a help to find the statement):
+
+  forward (TfLayer / tf_layout, launch sequence of m3l_transformer_fwd_dropout)
+    wqkv, wo, w1, w2 (+ transposes)   compute-type copies of the weights (m3l_prep_weights); both copies hold the same values
+    xn1, xn2                          LayerNorm outputs (ln_fwd_kernel stores TO; attn_block_fwd_body: the two `pk[..] = (bf16)y[..]` stores)
+    qkv                               GemmEpi::out_t of gemm_nt_glds_kernel; attn_block_fwd_body: `(bf16)acc[r]` into the QKV image
+    P                                 exp(s - running max) of a 32-key tile, UNNORMALISED, rounded by acc_to_frag before the P V MFMA; the row
+                                      sum adds the unrounded f32 values and divides after the product (attn_fwd_kernel: `lsum = lsum * alpha
+                                      + ps` ... `oacc[d] * inv`, attention.hip:116-146; the attention loop of attn_block_fwd_body).
+                                      attn_t192_fwd_kernel takes the max over the whole row first (no rescale; `__expf(sc[t][r] - mx)`,
+                                      t192.hip:1038-1077): recipe field kt = None instead of 32
+    o                                 rounded after the division by the row sum (same places)
+    lse                               f32
+    u                                 fc1 + bias rounded; h = GELU of the ROUNDED u, rounded (the `f_out_pre` / `f_act` steps of the
+                                      gemm_nt_glds_kernel epilogue; mlp_block_fwd_body `ub` / `hb`; mlp_t192_fwd_kernel `ub` / `hb`)
+    x1, xout                          f32 — with the bf16 residual stream (tf_rb, m3l_set_residual_bf16) bf16, and so is the stack's input
+    y                                 the f32 copy of the final LayerNorm: not rounded
+  backward (TfWs, m3l_transformer_bwd_range_dropout)
+    dx_t, dx1_t                       compute-type copy of every LayerNorm backward's result (ln_bwd_kernel `dx_t_out`; the `dxt_out` stores
+                                      of attn_block_bwd_body and ln_bwd_rows): operand of the dgrad GEMMs and of dW2 / dWo.  The f32 result
+                                      itself is the residual gradient — in residual-bf16 mode the residual gradient IS the rounded copy
+    fc2 / out-proj bias gradients     column sums of the UNROUNDED f32 result (ln_bwd_kernel `dc`; attn_block_bwd_body `pc = rr`)
+    du                                (dx_t W2) gelu'(u) rounded; the fc1 bias gradient sums the ROUNDED du (gemm_nt_glds_kernel `csum +=
+                                      to_f32(pk.v[j])`; mlp_block_bwd_body `db_` / `csum`; mlp_t192_bwd_kernel `dub` / `cs`)
+    dxn2, dxn1                        TfWs::dxn: stored by the per-op chain (GemmEpi::out_t) — field dxn2_stored / dxn1_stored; the block
+                                      kernels, the row tiles and the GEMM + LayerNorm epilogue keep them in f32 (header comments of
+                                      mlp_block_bwd_body and mlp_t192_bwd_kernel: "never leaves the CU / the registers";
+                                      attn_block_bwd_body writes `yacc` to LDS as float)
+    d_o                               dx1_t Wo rounded (GemmEpi::out_t; attn_block_bwd_body `(bf16)acc[r]` into TDO; attn_t192_bwd_kernel)
+    Dsum                              f32 sum of the rounded dO times the rounded o (attn_bwd_dq_kernel `dpart`; attn_block_bwd_body `sdo`)
+    P (backward)                      exp(s - lse): normalised, f32; rounded only as the operand of dV = P^T dO (attn_bwd_dkv_kernel `fp`)
+    dS                                P (dP - Dsum) scale rounded by acc_to_frag before the dQ / dK MFMAs (attn_bwd_dq_kernel and
+                                      attn_bwd_dkv_kernel `fds`); dP itself is an f32 accumulator and never rounded
+    dqkv                              dq | dk | dv rounded at the store
+
+Recipes (one per distinct rounding scheme):
+  perop     LN / GEMM / attention.hip launches, one per operation: kt 32, dxn1 and dxn2 stored
+  block1    m3l_set_attn_block(1): block kernels forward, mlp_block backward (dxn2 in f32), per-op attention backward (dxn1 stored)
+  block3    m3l_set_attn_block(3) and enc_mega.hip (the same bodies): dxn1 and dxn2 in f32
+  rowtile   t192.hip: dxn1 and dxn2 in f32; kt None where the per-sample attention runs (48 < n <= 192, D 192 / 256), else 32
+  rowln     gemm_rowln.hip epilogues: as block3 (never with the bf16 residual stream)
+With rnd = ident nothing is rounded and the key tiling has nothing to place: the attention then takes the plain softmax, which makes such a
+recipe with the erf GELU bit-equal to X.
+
+`trained_like(...)` builds the inputs of the slice tests (tests/test_tf_slices_gpu.py); the case table, the slicer and the bound check are in
+tests/tf_cases.py."""
+import math
+from dataclasses import dataclass
+from typing import Callable, Optional
+
+import numpy as np
+import torch
+
+from stage_refs import bf16_rnd, ident
+
+F64 = torch.float64
+LN_EPS = 1e-5
+
+# ---- the fitted GELU of m3l_amd/csrc/common.cuh (M3L_GF_A / _B / _C as the float32 values the compiler sees)
+GF_A, GF_B, GF_C = float(np.float32(1.59501577)), float(np.float32(7.40112921e-02)), float(np.float32(-7.03033579e-04))
+
+
+def _gelu_fit_sig(x):
+    xc = x.clamp(-8.0, 8.0)
+    x2 = xc * xc
+    return torch.sigmoid(((GF_C * x2 + GF_B) * x2 + GF_A) * xc), x2
+
+
+def gelu_fit(x):
+    """gelu_fast: x sigmoid(a x + b x^3 + c x^5), the polynomial's argument clamped to [-8, 8]"""
+    return x * _gelu_fit_sig(x)[0]
+
+
+def gelu_fit_grad(x):
+    """gelu_grad_fast: s + x s (1 - s) (a + 3 b x^2 + 5 c x^4)"""
+    s, x2 = _gelu_fit_sig(x)
+    return s + (x * s) * (1.0 - s) * ((5.0 * GF_C * x2 + 3.0 * GF_B) * x2 + GF_A)
+
+
+def gelu_erf(x):
+    return x * 0.5 * (1.0 + torch.erf(x * math.sqrt(0.5)))
+
+
+def gelu_erf_grad(x):
+    return 0.5 * (1.0 + torch.erf(x * math.sqrt(0.5))) + x * torch.exp(-0.5 * x * x) * (1.0 / math.sqrt(2.0 * math.pi))
+
+
+@dataclass(frozen=True)
+class Recipe:
+    rnd: Callable = ident            # applied at every storage / operand-rounding point
+    fit_gelu: bool = False           # the fitted GELU and its derivative instead of erf
+    rb: bool = False                 # bf16 residual stream: stack input, x1, xout and the residual gradient rounded
+    kt: Optional[int] = 32           # key tile of the online softmax (None: whole row)
+    dxn1_stored: bool = True
+    dxn2_stored: bool = True
+
+
+EXACT = Recipe()
+_RECIPES = {"perop": dict(dxn1_stored=True, dxn2_stored=True), "block1": dict(dxn1_stored=True, dxn2_stored=False),
+            "block3": dict(dxn1_stored=False, dxn2_stored=False), "rowtile": dict(dxn1_stored=False, dxn2_stored=False),
+            "rowln": dict(dxn1_stored=False, dxn2_stored=False)}
+
+
+def recipe(name, rb=False, kt=32, rnd=bf16_rnd, fit_gelu=True):
+    return Recipe(rnd=rnd, fit_gelu=fit_gelu, rb=bool(rb), kt=kt, **_RECIPES[name])
+
+
+# -------------------------------------------------------------------------------------------------------------------
+def _heads(t, B, n, H, dh):
+    return t.reshape(B, n, H, dh).transpose(1, 2)
+
+
+def _merge(t, B, n, H, dh):
+    return t.transpose(1, 2).reshape(B, n, H * dh)
+
+
+def _attn_fwd(q, k, v, scale, rc):
+    """q, k, v (B, H, n, dh) -> o (rounded), lse"""
+    s = (q @ k.transpose(-1, -2)) * scale
+    if rc.rnd is ident:
+        lse = torch.logsumexp(s, -1)
+        return s.softmax(-1) @ v, lse
+    n = s.shape[-1]
+    kt = rc.kt or n
+    m = torch.full(s.shape[:-1], -math.inf, dtype=s.dtype)
+    lsum = torch.zeros_like(m)
+    acc = torch.zeros_like(q)
+    for k0 in range(0, n, kt):
+        st = s[..., k0:k0 + kt]
+        mn = torch.maximum(m, st.max(-1).values)
+        alpha = torch.exp(m - mn)
+        p = torch.exp(st - mn[..., None])
+        lsum = lsum * alpha + p.sum(-1)
+        acc = acc * alpha[..., None] + rc.rnd(p) @ v[..., k0:k0 + kt, :]
+        m = mn
+    return rc.rnd(acc / lsum[..., None]), m + torch.log(lsum)
+
+
+def _attn_bwd(q, k, v, o, d_o, lse, scale, rc):
+    """all (B, H, n, dh), lse (B, H, n) -> dq, dk, dv (rounded)"""
+    r = rc.rnd
+    dsum = (d_o * o).sum(-1)
+    p = torch.exp((q @ k.transpose(-1, -2)) * scale - lse[..., None])
+    dp = d_o @ v.transpose(-1, -2)
+    ds = r(p * (dp - dsum[..., None]) * scale)
+    return r(ds @ k), r(ds.transpose(-1, -2) @ q), r(r(p).transpose(-1, -2) @ d_o)
+
+
+def _ln_fwd(x, g, b):
+    mean = x.mean(-1, keepdim=True)
+    d = x - mean
+    rstd = torch.rsqrt((d * d).mean(-1, keepdim=True) + LN_EPS)
+    xh = d * rstd
+    return xh * g + b, xh, rstd
+
+
+def _ln_bwd(dy, xh, rstd, g):
+    """-> dx, dgamma, dbeta"""
+    gd = dy * g
+    s1 = gd.mean(-1, keepdim=True)
+    s2 = (gd * xh).mean(-1, keepdim=True)
+    return (gd - s1 - xh * s2) * rstd, (dy * xh).sum((0, 1)), dy.sum((0, 1))
+
+
+def _tn(a, b):
+    """a^T b over the rows of (B, n, .) operands: the weight-gradient GEMM"""
+    return a.reshape(-1, a.shape[-1]).t() @ b.reshape(-1, b.shape[-1])
+
+
+def run(x, cot, P, prefix, depth, heads, dim_head, rc=EXACT, dtype=F64):
+    """-> dict(y, dx, grads {parameter name without prefix: gradient}, layers [dict of the workspace tensors])."""
+    r = rc.rnd
+    rr = r if rc.rb else ident
+    act, dact = (gelu_fit, gelu_fit_grad) if rc.fit_gelu else (gelu_erf, gelu_erf_grad)
+    B, n, D = x.shape
+    H, dh = heads, dim_head
+    scale = dh ** -0.5
+    T = lambda k: P[prefix + k].detach().to(dtype)
+    x = rr(x.detach().to(dtype))
+    cot = cot.detach().to(dtype)
+    L = []
+    for i in range(depth):
+        a, f = f"layers.{i}.0.", f"layers.{i}.1.net."
+        s = dict(x=x, po=(prefix + a + "to_out.0.weight") in P)
+        s["wqkv"], s["w1"], s["w2"] = r(T(a + "to_qkv.weight")), r(T(f + "1.weight")), r(T(f + "4.weight"))
+        s["g1"], s["g2"] = T(a + "norm.weight"), T(f + "0.weight")
+        y1, s["xh1"], s["rstd1"] = _ln_fwd(x, s["g1"], T(a + "norm.bias"))
+        s["xn1"] = r(y1)
+        s["qkv"] = r(s["xn1"] @ s["wqkv"].t())
+        q, k, v = [_heads(t, B, n, H, dh) for t in s["qkv"].chunk(3, -1)]
+        o, s["lse"] = _attn_fwd(q, k, v, scale, rc)
+        s["o"] = _merge(o, B, n, H, dh)
+        if s["po"]:
+            s["wo"] = r(T(a + "to_out.0.weight"))
+            s["x1"] = rr(s["o"] @ s["wo"].t() + T(a + "to_out.0.bias") + x)
+        else:
+            s["x1"] = rr(x + s["o"])
+        y2, s["xh2"], s["rstd2"] = _ln_fwd(s["x1"], s["g2"], T(f + "0.bias"))
+        s["xn2"] = r(y2)
+        s["u"] = r(s["xn2"] @ s["w1"].t() + T(f + "1.bias"))
+        s["h"] = r(act(s["u"]))
+        s["xout"] = rr(s["h"] @ s["w2"].t() + T(f + "4.bias") + s["x1"])
+        x = s["xout"]
+        L.append(s)
+    G = {}
+    gf = T("norm.weight")
+    y, xhf, rstdf = _ln_fwd(x, gf, T("norm.bias"))
+    res, G["norm.weight"], G["norm.bias"] = _ln_bwd(cot, xhf, rstdf, gf)
+    # res: the f32 result of the LayerNorm backward just run (residual gradient included)
+    for i in reversed(range(depth)):
+        s = L[i]
+        a, f = f"layers.{i}.0.", f"layers.{i}.1.net."
+        q, k, v = [_heads(t, B, n, H, dh) for t in s["qkv"].chunk(3, -1)]
+        G[f + "4.bias"] = res.sum((0, 1))
+        dx_t, dres = r(res), rr(res)
+        G[f + "4.weight"] = _tn(dx_t, s["h"])
+        du = r((dx_t @ s["w2"]) * dact(s["u"]))
+        G[f + "1.bias"] = du.sum((0, 1))
+        G[f + "1.weight"] = _tn(du, s["xn2"])
+        dxn2 = du @ s["w1"]
+        if rc.dxn2_stored:
+            dxn2 = r(dxn2)
+        d, G[f + "0.weight"], G[f + "0.bias"] = _ln_bwd(dxn2, s["xh2"], s["rstd2"], s["g2"])
+        res = d + dres
+        dx1_t, dres = r(res), rr(res)
+        if s["po"]:
+            G[a + "to_out.0.bias"] = res.sum((0, 1))
+            G[a + "to_out.0.weight"] = _tn(dx1_t, s["o"])
+            d_o = r(dx1_t @ s["wo"])
+        else:
+            d_o = dx1_t
+        dq, dk, dv = _attn_bwd(q, k, v, _heads(s["o"], B, n, H, dh), _heads(d_o, B, n, H, dh), s["lse"], scale, rc)
+        dqkv = torch.cat([_merge(t, B, n, H, dh) for t in (dq, dk, dv)], -1)
+        G[a + "to_qkv.weight"] = _tn(dqkv, s["xn1"])
+        dxn1 = dqkv @ s["wqkv"]
+        if rc.dxn1_stored:
+            dxn1 = r(dxn1)
+        d, G[a + "norm.weight"], G[a + "norm.bias"] = _ln_bwd(dxn1, s["xh1"], s["rstd1"], s["g1"])
+        res = d + dres
+    keep = ("xn1", "qkv", "o", "lse", "x1", "xn2", "u", "h", "xout")
+    return dict(y=y, dx=rr(res), grads=G, layers=[{k: s[k] for k in keep} for s in L])
+
+
+# -------------------------------------------------------------------------------------------------------------------
+# inputs away from initialisation statistics
+def state_names(depth, project_out=True):
+    out = []
+    for i in range(depth):
+        a, f = f"layers.{i}.0.", f"layers.{i}.1.net."
+        out += [a + "norm.weight", a + "norm.bias", a + "to_qkv.weight"] + ([a + "to_out.0.weight", a + "to_out.0.bias"] if project_out else [])
+        out += [f + "0.weight", f + "0.bias", f + "1.weight", f + "1.bias", f + "4.weight", f + "4.bias"]
+    return out + ["norm.weight", "norm.bias"]
+
+
+def _linear_init(out_f, in_f, g, bias=True):
+    """nn.Linear's default: U(-1/sqrt(in), 1/sqrt(in)) for weight and bias"""
+    b = 1.0 / math.sqrt(in_f)
+    w = (torch.rand(out_f, in_f, generator=g, dtype=F64) * 2 - 1) * b
+    return w, ((torch.rand(out_f, generator=g, dtype=F64) * 2 - 1) * b if bias else None)
+
+
+def _ln_gain(D, g):
+    """magnitudes U[0.25, 3] with random signs"""
+    mag = 0.25 + 2.75 * torch.rand(D, generator=g, dtype=F64)
+    return mag * (torch.randint(0, 2, (D,), generator=g).to(F64) * 2 - 1)
+
+
+def key_tile_of(n):
+    """first key index of the last 32-key tile"""
+    return 32 * ((n - 1) // 32)
+
+
+def _logits(xn1, wqkv, heads, dim_head):
+    B, n, _ = xn1.shape
+    HD = heads * dim_head
+    q, k = [_heads(xn1 @ wqkv[j * HD:(j + 1) * HD].t(), B, n, heads, dim_head) for j in (0, 1)]
+    return (q @ k.transpose(-1, -2)) * dim_head ** -0.5
+
+
+def trained_like(D, depth, heads, dim_head, mlp, n, B, tile, seed=0, logit_std=3.0, max_prob=0.4, u_std=2.0):
+    """One seeded builder of (state dict, x, cot), all float32, for every slice-test case.  A default-initialised stack with
+      * the q and k rows of every to_qkv.weight scaled by one gain per layer, set so that the layer's attention logits have std `logit_std`
+        (the stack is evaluated in float64 layer by layer while it is built);
+      * LayerNorm gains +-U[0.25, 3] (mixed signs), LayerNorm biases and every Linear bias N(0, 0.5);
+      * the fc1 rows of every layer scaled so that the pre-activation u has std `u_std`;
+      * x = white noise of std 1.5 + a per-channel offset U[-8, 8], three outlier channels at 30 times the scale, sample 0 scaled by 0.05 (its input gradient is
+        20 times the others'; the cotangent's extra component below sits at the other end of the batch);
+      * planted dominant keys (n >= 8): in EVERY sample token n - 1 (last key tile) is pushed towards the direction that the mean query of
+        head 0 of layer 0 likes best, token 0 (first tile) towards that of head 1, by `A` row standard deviations; A is
+        found by bisection so that the mean largest probability per row is `max_prob` at the prescribed logit std (near-Gaussian logits
+        of std <= 4 cannot reach 0.2 once n is in the hundreds: the tail has to be planted).  The online softmax so meets its dominant
+        key late in head 0 (rescale of a populated accumulator) and early in head 1 (everything after it is small);
+      * cot = white noise + a component of equal norm confined to the last `tile`-row tile of the flattened [B n, D] matrix (the ragged one
+        where B n is no multiple of `tile`)."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    HD, po = heads * dim_head, not (heads == 1 and dim_head == D)
+    x = 1.5 * torch.randn(B, n, D, generator=g, dtype=F64) + (16.0 * torch.rand(D, generator=g, dtype=F64) - 8.0)
+    out_ch = torch.randperm(D, generator=g)[:3]
+    x[..., out_ch] = 30.0 * 1.5 * torch.randn(B, n, 3, generator=g, dtype=F64)
+    x[0] *= 0.05
+    P = {}
+    cur = x
+    for i in range(depth):
+        a, f = f"layers.{i}.0.", f"layers.{i}.1.net."
+        g1, b1n = _ln_gain(D, g), 0.5 * torch.randn(D, generator=g, dtype=F64)
+        P[a + "norm.weight"], P[a + "norm.bias"] = g1, b1n
+        wqkv, _ = _linear_init(3 * HD, D, g, bias=False)
+        if i == 0 and n >= 8:
+            qbar = (_ln_fwd(x, g1, b1n)[0] @ wqkv[:HD].t()).mean((0, 1))
+            zs = []
+            for par in (0, 1):
+                sel = torch.tensor([float(h == min(par, heads - 1)) for h in range(heads)], dtype=F64).repeat_interleave(dim_head)
+                z = (wqkv[HD:2 * HD].t() @ (qbar * sel)) / g1
+                z = z - z.mean()
+                zs.append(z / z.pow(2).mean().sqrt())
+            base = x
+
+            def push(A):
+                xa = base.clone()
+                for tok, z in ((n - 1, zs[0]), (0, zs[1])):
+                    xa[:, tok] += A * base[:, tok].std(-1, keepdim=True) * z
+                return xa
+
+            def peak(A):                                                 # mean largest probability at push A (first 16 samples: enough for a mean)
+                s = _logits(_ln_fwd(push(A)[:16], g1, b1n)[0], wqkv, heads, dim_head)
+                return float((s * (logit_std / float(s.std()))).softmax(-1).max(-1).values.mean())
+
+            # Short sequences are peaked enough at logit std 3 without any push (0.42 at n = 17); they still get the two planted keys, by a
+            # fixed quarter of a row standard deviation, so that every case has them.  Otherwise: bisection on the push.
+            A = 0.25
+            if peak(0.0) < max_prob:
+                lo, hi = 0.0, 16.0
+                for _ in range(12):
+                    A = 0.5 * (lo + hi)
+                    lo, hi = (A, hi) if peak(A) < max_prob else (lo, A)
+            cur = x = push(A)
+        xn1 = _ln_fwd(cur, g1, b1n)[0]
+        s0 = float(_logits(xn1, wqkv, heads, dim_head).std()) if n > 1 else 1.0
+        wqkv[:2 * HD] *= math.sqrt(logit_std / max(s0, 1e-30))          # the logits are bilinear in the two gains
+        P[a + "to_qkv.weight"] = wqkv
+        qkv = xn1 @ wqkv.t()
+        q, k, v = [_heads(t, B, n, heads, dim_head) for t in qkv.chunk(3, -1)]
+        o = _merge(((q @ k.transpose(-1, -2)) * dim_head ** -0.5).softmax(-1) @ v, B, n, heads, dim_head)
+        if po:
+            P[a + "to_out.0.weight"], _ = _linear_init(D, HD, g)
+            P[a + "to_out.0.bias"] = 0.5 * torch.randn(D, generator=g, dtype=F64)
+            x1 = o @ P[a + "to_out.0.weight"].t() + P[a + "to_out.0.bias"] + cur
+        else:
+            x1 = o + cur
+        P[f + "0.weight"], P[f + "0.bias"] = _ln_gain(D, g), 0.5 * torch.randn(D, generator=g, dtype=F64)
+        xn2 = _ln_fwd(x1, P[f + "0.weight"], P[f + "0.bias"])[0]
+        w1, _ = _linear_init(mlp, D, g)
+        b1 = 0.5 * torch.randn(mlp, generator=g, dtype=F64)
+        w1 *= math.sqrt(max(u_std ** 2 - 0.25, 0.25)) / float((xn2 @ w1.t()).std())
+        P[f + "1.weight"], P[f + "1.bias"] = w1, b1
+        P[f + "4.weight"], _ = _linear_init(D, mlp, g)
+        P[f + "4.bias"] = 0.5 * torch.randn(D, generator=g, dtype=F64)
+        cur = gelu_erf(xn2 @ w1.t() + b1) @ P[f + "4.weight"].t() + P[f + "4.bias"] + x1
+    P["norm.weight"], P["norm.bias"] = _ln_gain(D, g), 0.5 * torch.randn(D, generator=g, dtype=F64)
+    M = B * n
+    cot = torch.randn(M, D, generator=g, dtype=F64)
+    r0 = tile * ((M - 1) // tile)
+    extra = torch.randn(M - r0, D, generator=g, dtype=F64)
+    cot[r0:] += extra * (cot.norm() / extra.norm())
+    return {k_: v_.to(torch.float32) for k_, v_ in P.items()}, x.to(torch.float32), cot.reshape(B, n, D).to(torch.float32)
+
+
+def regime(x, P, heads, dim_head):
+    """layer-0 figures of an input, float64: std of the attention logits, mean largest probability per row, std of u, fraction of u below
+    -0.75 and above 2 (the GELU's dip and its linear tail), and how many queries of one sample have their dominant key (p > 0.5) in the last key
+    tile / in the first (of the sample where the smaller of the two counts is largest)"""
+    z = run(x, torch.zeros_like(x), P, "", 1, heads, dim_head)["layers"][0]
+    B, n, _ = x.shape
+    q, k = [_heads(t, B, n, heads, dim_head) for t in z["qkv"].chunk(3, -1)[:2]]
+    s = (q @ k.transpose(-1, -2)) * dim_head ** -0.5
+    p = s.softmax(-1)
+    pm, am = p.max(-1)                                            # (B, H, n)
+    last = ((pm > 0.5) & (am >= key_tile_of(n))).sum((1, 2))
+    first = ((pm > 0.5) & (am < 32)).sum((1, 2))
+    best = int(torch.minimum(last, first).argmax())              # the sample where both kinds of query are most numerous
+    return dict(logit_std=float(s.std()) if n > 1 else 0.0, max_prob=float(p.max(-1).values.mean()), u_std=float(z["u"].std()),
+                u_dip=float((z["u"] < -0.75).double().mean()), u_tail=float((z["u"] > 2.0).double().mean()),
+                dom_last=int(last[best]), dom_first=int(first[best]))
+
+
+def tensors_of(res):
+    """{'y', 'dx', parameter names} of a run() result or of (y, dx, grads)"""
+    if isinstance(res, dict):
+        res = (res["y"], res["dx"], res["grads"])
+    return {"y": res[0], "dx": res[1], **res[2]}
