@@ -210,6 +210,43 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
                                       const void* dy, int dy_dtype, float* dx_in, float* const* grads, int layer_hi, int layer_lo,
                                       const m3l_dropout* drop, void* stream);
 
+/* ---- kernel selection (ABI 408).  Which kernel family runs each half layer of a stack is decided once per call from the configuration,
+ * (B, n), the dropout descriptor and the process-wide switches; forward and backward switch on the result.  m3l_transformer_plan returns
+ * that decision under the switches in force at the time of the call: host arithmetic only, no launch, no device (it works in a process
+ * that never initialises HIP).  Returns 1, with m3l_last_error set, for a configuration the transformer entry points refuse. */
+enum {
+    M3L_TF_PER_OP = 0,       /* the per-op chain: LayerNorm, GEMM and attention kernels, one launch each */
+    M3L_TF_BLOCK = 1,        /* per-sample block kernel (short sequences: m3l_set_attn_block) */
+    M3L_TF_T192 = 2,         /* row-tile / per-sample kernel of the long-sequence family (m3l_set_t192) */
+    M3L_TF_ROWLN = 3,        /* GEMM with the LayerNorm in its epilogue (m3l_set_rowln) */
+    M3L_TF_IN_BLOCK = 4,     /* no launch of its own: done by the attention block kernel of the same half layer */
+    M3L_TF_TAIL_T192 = 5,    /* out-proj + LN2 run at the head of the row-tiled feed-forward launch */
+    M3L_TF_IN_TAIL = 6,      /* the feed-forward launch is that out-proj + LN2 + fc1 + GELU + fc2 kernel */
+    M3L_TF_GEMM = 7,         /* out-proj as a GEMM with the residual in its epilogue, then the LN2 kernel */
+    M3L_TF_IDENTITY = 8      /* no out-projection (project_out == 0): residual add, then the LN2 kernel */
+};
+typedef struct m3l_tf_plan {
+    int per_op;              /* 1: dropout is active or dim_head != 64 — every layer on the per-op chain */
+    int rowln_cfg;           /* 1: m3l_set_rowln is on and the row widths allow the GEMM + LayerNorm epilogue */
+    int rowln;               /* rowln_cfg && !per_op: the layers run it */
+    int rb;                  /* 1: bf16 residual stream (what m3l_set_residual_bf16 asks for, where every kernel of the stack supports it) */
+    int drop_h;              /* m3l_set_drop_h at the time of the call */
+    int h_from_u;            /* 1: the fused forward did not write h; the fc2 weight gradient stages u and applies the GELU itself */
+    int mega_fwd;            /* 1: the whole forward of the stack in one launch (m3l_set_enc_mega bit 1) */
+    int mega_bwd;            /* 1: the backward in one launch per weight-gradient group of layers (bit 2) */
+    int dropout;             /* 1: a descriptor of p > 0 was given */
+    int fwd_attn;            /* forward, LN1 + QKV + attention:        BLOCK, T192, PER_OP */
+    int fwd_outproj;         /* forward, out-proj + residual + LN2:    IN_BLOCK, TAIL_T192, ROWLN, GEMM, IDENTITY */
+    int fwd_mlp;             /* forward, feed-forward half:            BLOCK, T192, IN_TAIL, ROWLN, PER_OP */
+    int bwd_mlp;             /* backward, feed-forward half + LN2:     BLOCK, T192, ROWLN, PER_OP */
+    int bwd_attn;            /* backward, out-proj dgrad + attention:  BLOCK, T192, PER_OP */
+    int bwd_qkv;             /* backward, QKV dgrad + LN1:             IN_BLOCK, ROWLN, T192, PER_OP */
+    int row_tiles;           /* row tiles of the feed-forward backward when bwd_mlp == T192, else 0 */
+    int qkv_tiles;           /* row tiles of the QKV backward when bwd_qkv == T192, else 0 */
+    int cs_rows;             /* partial rows of the fc1 bias gradient that the selected feed-forward backward writes */
+} m3l_tf_plan;
+int m3l_transformer_plan(const m3l_tf_cfg* c, int B, int n, const m3l_dropout* drop, m3l_tf_plan* out);
+
 /* ---- frozen ViT forward (inference only): the DINOv2-S/14-reg image feature of the cfg-5 fusion head
  * (models/pretrain_models_dino_cat_mae.py:886 `self.dino_model(obs_viso)`; train_dino_cat_mae.py:29).  x: tokens (B, n, dim) f32
  * (cls + registers + patches, positions already added); y32: final-norm output (B, n, dim) f32.

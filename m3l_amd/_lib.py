@@ -38,6 +38,16 @@ class Dropout(C.Structure):
     _fields_ = [("p", C.c_float), ("seed", C.c_uint64)]
 
 
+class TfPlan(C.Structure):
+    """m3l_tf_plan: the kernel selection of a transformer stack (include/m3l_amd.h "kernel selection"); family fields hold TF_* codes."""
+    _fields_ = [(n, c_i) for n in ("per_op", "rowln_cfg", "rowln", "rb", "drop_h", "h_from_u", "mega_fwd", "mega_bwd", "dropout",
+                                   "fwd_attn", "fwd_outproj", "fwd_mlp", "bwd_mlp", "bwd_attn", "bwd_qkv", "row_tiles", "qkv_tiles", "cs_rows")]
+
+
+# the M3L_TF_* codes of the family fields
+TF_PER_OP, TF_BLOCK, TF_T192, TF_ROWLN, TF_IN_BLOCK, TF_TAIL_T192, TF_IN_TAIL, TF_GEMM, TF_IDENTITY = range(9)
+
+
 class CommPlan(C.Structure):
     _fields_ = [("flat", c_p), ("total", C.c_long), ("min_bucket", C.c_long), ("layers_per_chunk", c_i), ("n_stages", c_i),
                 ("stage_end", C.POINTER(C.c_long)), ("sent_out", C.POINTER(C.c_long))]
@@ -83,6 +93,7 @@ _SIGS = {
     "m3l_transformer_fwd_dropout": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_p, C.POINTER(Dropout), c_p]),
     "m3l_transformer_bwd_dropout": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, C.POINTER(Dropout), c_p]),
     "m3l_transformer_bwd_range_dropout": (c_i, [C.POINTER(TfCfg), c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, C.POINTER(Dropout), c_p]),
+    "m3l_transformer_plan": (c_i, [C.POINTER(TfCfg), c_i, c_i, C.POINTER(Dropout), C.POINTER(TfPlan)]),
     "m3l_frozen_vit_ws_bytes": (c_sz, [C.POINTER(TfCfg), c_i, c_i]),
     "m3l_frozen_vit_fwd": (c_i, [C.POINTER(TfCfg), C.c_float, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "m3l_unshuffle_ws_bytes": (c_sz, [C.POINTER(Geom), c_i, c_i, c_i, c_i, c_i, c_i]),

@@ -15,6 +15,7 @@
 #include "../../include/m3l_amd.h"
 #include "common.cuh"
 #include "kernels.h"
+#include "tf_plan.h"
 
 
 namespace {
@@ -130,62 +131,11 @@ struct Arena {
 
 inline int pad8(int x) { return (x + 7) & ~7; }
 inline int pad64(int x) { return (x + 63) & ~63; }
-// LayerNorm forward / backward fused into the epilogue of the neighbouring GEMM (gemm_rowln.hip).  Correct (parity-tested) but
-// measured 2-3 % SLOWER than the separate kernels at cfg 2 on MI355X (a full-row tile caps the kernel at 2 workgroups per CU,
-// the stand-alone LayerNorm kernels run at 8 waves per SIMD), so it is off unless requested (M3L_ROWLN=1 / m3l_set_rowln).
-int g_rowln = -1;
-inline bool use_rowln() {
-    if (g_rowln < 0) g_rowln = getenv("M3L_ROWLN") != nullptr ? 1 : 0;
-    return g_rowln == 1;
-}
 inline size_t esz(int dtype) { return dtype ? 2 : 4; }
-// Hidden activation h = GELU(u) of the fused MLP kernels: 1 = not written by the forward — the weight-gradient kernel of fc2 stages the
-// pre-activation u instead and applies the GELU in its LDS stage (wgrad.hip), bit-identical gradients, 0.7 GB less HBM traffic per cfg-2
-// step — and a 40 % longer weight-gradient kernel (140 -> 196 us: the GELU pass is NOT hidden behind its memory waits), which the side
-// stream absorbs: same step time.  0 (default) = saved.  env M3L_DROP_H / m3l_set_drop_h.
-int g_drop_h = -1;
-inline bool drop_h() {
-    if (g_drop_h < 0) g_drop_h = getenv("M3L_DROP_H") ? (atoi(getenv("M3L_DROP_H")) > 0 ? 1 : 0) : 0;
-    return g_drop_h == 1;
-}
-// bf16 residual stream (round 4; default ON, env M3L_RES_BF16=0 / m3l_set_residual_bf16(0) restore fp32): x, x1, xout of every layer of a stack and its running
-// residual gradient travel through HBM as bf16 instead of fp32 (fp32 in registers: the arithmetic is unchanged, each half layer's result is
-// rounded once).  The tails of the fused kernels move mostly residual-type data at ~5.5 TB/s, so halving it is direct time; the residual
-// gradient needs no separate copy at all (the compute-type copy the GEMMs read IS it).  A stack runs in this mode when every layer takes
-// kernels that support it; its input and its input gradient stay fp32 at the interface (one cast each).
-int g_res_bf16 = -1;
-inline bool res_bf16_mode() {
-    if (g_res_bf16 < 0) g_res_bf16 = getenv("M3L_RES_BF16") ? (atoi(getenv("M3L_RES_BF16")) > 0 ? 1 : 0) : 1;
-    return g_res_bf16 == 1;
-}
 struct RbScope {          // residual mode of the launches issued inside the scope (read by the launchers: m3l_call_rb)
     explicit RbScope(bool on) { m3l_set_call_rb(on ? 1 : 0); }
     ~RbScope() { m3l_set_call_rb(0); }
 };
-// head width of a stack (m3l_tf_cfg.dim_head, 0 = 64)
-inline int tf_dh(const m3l_tf_cfg* c) { return c->dim_head ? c->dim_head : 64; }
-bool tf_rb(const m3l_tf_cfg* c, int B, int n, bool fuse) {
-    if (!res_bf16_mode() || c->dtype != 1 || fuse || !c->project_out || c->depth < 1) return false;
-    // every kernel a bf16 stack can take has a bf16-residual form — the per-sample blocks, the row tiles, and (since the EPI_RES16 epilogue
-    // of the NT GEMM and the typed dres of ln_bwd) the per-op chain — except the one-launch encoder backward; the residual epilogue of the
-    // out-proj / fc2 GEMMs needs K = heads * dim_head / mlp_dim to be a multiple of the 64-element K tile
-    if (c->mlp_dim % 64 != 0 || (c->heads * tf_dh(c)) % 64 != 0) return false;
-    if ((m3l_enc_mega_enabled() & 2) && m3l_attn_block_supported(1, c->dim, c->heads, n, c->project_out, tf_dh(c))) return false;
-    (void)B;
-    return true;
-}
-// which fused kernel (if any) computes the feed-forward half of a layer in the FORWARD — the same decisions as m3l_transformer_fwd below:
-// 0 = per-op GEMMs (h is the operand of the fc2 GEMM: always saved), 1 = per-sample block kernel, 2 = row-tiled kernel
-// (both evaluate the fitted GELU, as every bf16 kernel does).  The backward reads it to know whether h exists and which GELU reproduces it.
-int fused_mlp_kind(const m3l_tf_cfg* c, int B, int n, bool fuse) {
-    const int M = B * n, D = c->dim, mlp = c->mlp_dim, dt = c->dtype;
-    if (fuse || dt != 1 || tf_dh(c) != 64) return 0;     // dim_head != 64: the per-op chain (m3l_transformer_fwd_dropout)
-    const bool block = m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, 64);
-    const bool t192 = m3l_mlp_t192_supported(dt, D, mlp, M);
-    if (block && !(m3l_mlp_t192_short() && t192) && m3l_mlp_block_supported(dt, D, mlp, n)) return 1;
-    return t192 ? 2 : 0;
-}
-
 // scratch big enough for every reduction / split-K slab of one module
 size_t scratch_bytes(int M, const std::vector<std::pair<int, int>>& wshapes, int maxcols) {
     size_t s = (size_t)2048 * 4 * (size_t)maxcols * sizeof(float);
@@ -288,21 +238,16 @@ struct TfWs {
     float* dpart;
     size_t total;
 };
-// what the forward of a stack ran with, by workspace: the backward checks that it recomputes the same (the backward re-derives
-// the forward's kernel choices from process-global switches).  The choices that decide WHAT the workspace holds must not change in
-// between: the residual mode (bf16 or fp32 activations), whether the fused feed-forward kernels saved h (drop_h), the dropout descriptor
-// (the masks).  The kernel family (enc_mega / block / row tile / per-op) may differ: every family reads and writes the same workspace
-// tensors with the same meaning.  A record is dropped by the backward that reaches layer 0; the map is cleared if it ever holds more than
-// kTfRecMax workspaces (forwards without a backward), which only skips the check for those.
-struct TfRecord {
-    int rb, drop_h;
-    float p;
-    uint64_t seed;
-};
+// the plan the forward of a stack ran with, by workspace: the backward makes its own plan from the switches in force when IT is called
+// and checks the fields that decide WHAT the workspace holds, which must not change in between: the residual mode (bf16 or fp32
+// activations), whether the fused feed-forward kernels saved h (drop_h), the dropout descriptor (the masks).  The family fields (one launch
+// / block / row tile / per-op) are NOT compared: every family reads and writes the same workspace tensors with the same meaning, and a
+// test may flip a family switch in between.  A record is dropped by the backward that reaches layer 0; the map is cleared if it ever holds
+// more than kTfRecMax workspaces (forwards without a backward), which only skips the check for those.
+typedef TfPlan TfRecord;
 constexpr size_t kTfRecMax = 4096;
 std::mutex g_tf_rec_mu;
 std::map<const void*, TfRecord> g_tf_rec;
-inline bool drop_active(const m3l_dropout* d) { return d != nullptr && d->p > 0.f; }
 // bf16 residual mode: the fp32 running-gradient buffer w.dx is not used; its memory holds the stack's input as bf16 (kept for the backward
 // of layer 0) and the bf16 gradient of layer 0's input (cast to the caller's fp32 dx_in)
 inline void* rb_xin(const TfWs& w) { return w.dx; }
@@ -404,7 +349,7 @@ int check_tf(const m3l_tf_cfg* c, int B, int n) {
 // =================================================================================================================
 extern "C" {
 
-int m3l_version(void) { return 407; }
+int m3l_version(void) { return 408; }
 
 // diagnostic switch (bench.py's stand-alone roofline figure, PMC passes): 1 = every weight gradient on the caller's stream
 int m3l_set_wgrad_inline(int on) {
@@ -461,9 +406,13 @@ int m3l_side_pending(void) {
 }
 
 // 1 when this stack runs the bf16 residual stream at (B, n) (mae_step.hip: whether its neighbours exchange bf16 with it)
-int m3l_transformer_rb(const m3l_tf_cfg* c, int B, int n) {
-    const int D = c->dim, HD = c->heads * tf_dh(c), mlp = c->mlp_dim;
-    return tf_rb(c, B, n, use_rowln() && m3l_gemm_nt_rowln_supported(c->dtype, D, HD) && m3l_gemm_nt_rowln_supported(c->dtype, D, mlp)) ? 1 : 0;
+int m3l_transformer_rb(const m3l_tf_cfg* c, int B, int n) { return tf_plan(c, B, n, nullptr).rb; }
+
+// the kernel selection of a stack under the switches in force now (host arithmetic only: no launch, no device)
+int m3l_transformer_plan(const m3l_tf_cfg* c, int B, int n, const m3l_dropout* drop, m3l_tf_plan* out) {
+    if (check_tf(c, B, n)) return 1;
+    *out = tf_plan(c, B, n, drop);
+    return 0;
 }
 
 int m3l_set_residual_bf16(int on) {
@@ -655,14 +604,15 @@ int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, co
 }
 
 // With a dropout descriptor of p > 0 every layer takes the per-op chain (LN, QKV GEMM, attention, out-proj GEMM, LN, fc1, fc2): the
-// masks live in the attention kernels and the NT GEMM epilogue only.  The residual mode is the one tf_rb picks without dropout.
+// masks live in the attention kernels and the NT GEMM epilogue only.  The residual mode is the one the plan picks without dropout.
 // A stack whose heads are not 64 wide takes the same per-op chain (the block, row-tile and one-launch kernels are built for 64).
+// Which kernel runs each half layer is decided once, in tf_plan (tf_plan.h).
 int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t,
                                 float* y32, const m3l_dropout* drop, void* stream) {
     if (check_tf(c, B, n)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const bool dp = drop_active(drop);
-    const bool po = dp || tf_dh(c) != 64;     // every layer on the per-op chain
+    const TfPlan pl = tf_plan(c, B, n, drop);
+    const bool dp = pl.dropout, rb = pl.rb;
     M3L_CHECK(!dp || drop->p <= 1.f, "transformer: dropout p=%g outside [0, 1]", (double)drop->p);
     // the per-op chain's fc2 GEMM takes the dropout epilogue only on the LDS-DMA kernel: K = mlp_dim in whole K tiles
     M3L_CHECK(!dp || c->mlp_dim % (c->dtype ? 64 : 32) == 0, "transformer: dropout needs mlp_dim %% %d == 0 (got %d)", c->dtype ? 64 : 32,
@@ -688,141 +638,126 @@ int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* 
         }
     }
     if (m3l_prep_mode() == 1) return 0;            // collect pass of a call chain (mae_step.hip)
-    // LayerNorms fused into the epilogue of the GEMM that produces their input (gemm_rowln.hip) when the row width allows it:
-    // out-proj + LN2 of the layer, fc2 + LN1 of the next layer (or the final norm).  Only the very first LN1 is a kernel.
-    const bool fuse_cfg = use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, HD) && m3l_gemm_nt_rowln_supported(dt, D, mlp);
-    const bool fuse = fuse_cfg && !po;
     const void* const* tfin = tensors + 11 * c->depth;
-    bool final_done = false;
-    // bf16 residual stream: the stack's input as bf16 (kept for the backward of layer 0 in the otherwise unused w.dx buffer); from here on
-    // every `float*` of the residual stream points at bf16 data and the launchers are told so
-    const bool rb = tf_rb(c, B, n, fuse_cfg);
     {
         std::lock_guard<std::mutex> lock(g_tf_rec_mu);
         if (g_tf_rec.size() >= kTfRecMax && g_tf_rec.find(ws) == g_tf_rec.end()) g_tf_rec.clear();
-        g_tf_rec[ws] = TfRecord{rb ? 1 : 0, drop_h() ? 1 : 0, dp ? drop->p : 0.f, dp ? drop->seed : 0};
+        g_tf_rec[ws] = pl;
     }
     auto dctx = [&](int layer, int site) { return dp ? m3l_drop_ctx(drop->p, drop->seed, layer, site) : DropCtx{}; };
+    // bf16 residual stream: the stack's input as bf16 (kept for the backward of layer 0 in the otherwise unused w.dx buffer); from here on
+    // every `float*` of the residual stream points at bf16 data and the launchers are told so
     if (rb && !m3l_call_io()) {          // (m3l_call_io: the caller hands x_in over as bf16 already)
         if (m3l_cast_f32(1, x_in, (long)M * D, rb_xin(w), st)) return 1;
         x = reinterpret_cast<const float*>(rb_xin(w));
     }
     RbScope rb_scope(rb);
-    // short sequences whose every half layer takes a block kernel: the whole stack in ONE launch (enc_mega.hip)
-    int l_begin = 0;
-    if (!po && (m3l_enc_mega_enabled() & 1) && !fuse && c->depth >= 1 && c->depth <= M3L_MEGA_MAX_LAYERS && c->project_out &&
-        m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, tf_dh(c)) && m3l_mlp_block_supported(dt, D, mlp, n) &&
-        !(m3l_mlp_t192_short() && m3l_mlp_t192_supported(dt, D, mlp, M))) {
+    if (pl.mega_fwd) {      // short sequences whose every half layer takes a block kernel: the whole stack in ONE launch (enc_mega.hip)
         const void* lay[M3L_MEGA_MAX_LAYERS][20];
         for (int l = 0; l < c->depth; ++l) {
             TfLayer& L = w.L[l];
             const void* const* t = tensors + 11 * l;
             const void* v[20] = {t[0], t[1], L.wqkv, L.wo, t[4], t[5], t[6], L.xn1, L.qkv, L.o, L.lse, L.x1, L.xn2,
-                                 L.w1, t[8], L.w2, t[10], L.u, drop_h() ? nullptr : L.h, L.xout};
+                                 L.w1, t[8], L.w2, t[10], L.u, pl.drop_h ? nullptr : L.h, L.xout};
             memcpy(lay[l], v, sizeof(v));
         }
         if (m3l_enc_fwd_mega(D, mlp, B, n, x, &lay[0][0], c->depth, LN_EPS, st)) return 1;
-        x = w.L[c->depth - 1].xout;
-        l_begin = c->depth;
+        return m3l_ln_fwd(dt, w.L[c->depth - 1].xout, M, D, (const float*)tfin[0], (const float*)tfin[1], LN_EPS, y_t, y32, st);
     }
-    void* const h_null = nullptr;
-    for (int l = l_begin; l < c->depth; ++l) {
+    for (int l = 0; l < c->depth; ++l) {
         TfLayer& L = w.L[l];
-        void* const h_fused = drop_h() ? h_null : L.h;        // fused MLP kernels only: the per-op fc2 GEMM reads h from memory
+        void* const h_fused = pl.drop_h ? nullptr : L.h;        // fused MLP kernels only: the per-op fc2 GEMM reads h from memory
         const void* const* t = tensors + 11 * l;
         const float *ln1_w = (const float*)t[0], *ln1_b = (const float*)t[1], *out_b = (const float*)t[4], *ln2_w = (const float*)t[5],
                     *ln2_b = (const float*)t[6], *fc1_b = (const float*)t[8], *fc2_b = (const float*)t[10];
-
-        const bool block = !po && !fuse && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, tf_dh(c));
-        if (block) {
-            // the whole attention half of the layer in one launch (short sequences: the MAE encoder)
+        GemmEpi e;
+        // ---- attention: LN1, QKV, attention ...
+        switch (pl.fwd_attn) {
+        case M3L_TF_BLOCK:      // the whole attention half of the layer in one launch (short sequences: the MAE encoder)
             if (m3l_attn_block_fwd(D, B, n, x, ln1_w, ln1_b, L.wqkv, L.wo, out_b, ln2_w, ln2_b, LN_EPS, L.xn1, L.qkv, L.o, L.lse, L.x1,
                                    L.xn2, st))
                 return 1;
-        }
-        const bool attn_t = !po && !block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B, tf_dh(c));
-        if (attn_t) {
-            // long sequences: LN1 + QKV + attention of a sample in one launch (the out-proj + LN2 continue in the feed-forward launch)
+            break;
+        case M3L_TF_T192:       // long sequences: LN1 + QKV + attention of a sample in one launch
             if (m3l_attn_t192_fwd(D, B, n, x, ln1_w, ln1_b, L.wqkv, LN_EPS, L.xn1, L.qkv, L.o, L.lse, st)) return 1;
+            break;
+        default: {
+            // (GEMM + LayerNorm epilogue: the fc2 launch of the layer before wrote xn1; only the very first LN1 is a kernel)
+            if ((!pl.rowln || l == 0) && m3l_ln_fwd(dt, x, M, D, ln1_w, ln1_b, LN_EPS, L.xn1, nullptr, st)) return 1;
+            e = epi0(3 * HD);
+            e.out_t = L.qkv;
+            if (m3l_gemm_nt(dt, L.xn1, D, L.wqkv, D, M, 3 * HD, D, &e, st)) return 1;
+            const DropCtx d0 = dctx(l, 0);
+            if (m3l_attn_fwd(dt, L.qkv, L.o, L.lse, B, n, c->heads, tf_dh(c), st, &d0)) return 1;
         }
-        if (!block && !attn_t && (!fuse || l == 0)) {
-            if (m3l_ln_fwd(dt, x, M, D, ln1_w, ln1_b, LN_EPS, L.xn1, nullptr, st)) return 1;
         }
-        GemmEpi e = epi0(3 * HD);
-        e.out_t = L.qkv;
-        if (!block) {
-        if (!attn_t) {
-        if (m3l_gemm_nt(dt, L.xn1, D, L.wqkv, D, M, 3 * HD, D, &e, st)) return 1;
-        const DropCtx d0 = dctx(l, 0);
-        if (m3l_attn_fwd(dt, L.qkv, L.o, L.lse, B, n, c->heads, tf_dh(c), st, &d0)) return 1;
-        }
-        if (!po && c->project_out && !fuse && m3l_attn_tail_mlp_t192_supported(dt, D, HD, mlp, M, tf_dh(c))) {
-            // long sequences: out-proj + residual + LN2 + fc1 + GELU + fc2 + residual in ONE launch per 192-row tile
-            if (m3l_attn_tail_mlp_t192_fwd(D, M, mlp, L.o, x, L.wo, out_b, ln2_w, ln2_b, LN_EPS, L.x1, L.xn2, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused,
-                                           L.xout, st))
-                return 1;
-            x = L.xout;
-            continue;
-        }
-        if (c->project_out && fuse) {
+        // ---- ... out-proj, residual, LN2
+        switch (pl.fwd_outproj) {
+        case M3L_TF_IN_BLOCK:       // the attention block did it
+        case M3L_TF_TAIL_T192:      // the feed-forward launch below does it
+            break;
+        case M3L_TF_ROWLN: {        // out-proj + LN2 in one GEMM (gemm_rowln.hip)
             RowLnEpi r;
             memset(&r, 0, sizeof(r));
             r.bias = out_b; r.res = x; r.x_out = L.x1; r.gamma = ln2_w; r.beta = ln2_b; r.out_t = L.xn2; r.eps = LN_EPS;
             if (m3l_gemm_nt_rowln(dt, ROWLN_FWD, L.o, HD, L.wo, HD, M, D, HD, &r, st)) return 1;
-        } else {
-            if (c->project_out) {
-                e = epi0(D);
-                e.bias = out_b;
-                e.drop = dctx(l, 1);
-                if (rb) { e.res_t = x; e.out_t = L.x1; } else { e.res = x; e.out_f32 = L.x1; }
-                if (m3l_gemm_nt(dt, L.o, HD, L.wo, HD, M, D, HD, &e, st)) return 1;
-            } else {
-                if (m3l_axpy_t(dt, x, L.o, (long)M * D, L.x1, st)) return 1;
-            }
+            break;
+        }
+        case M3L_TF_GEMM:
+            e = epi0(D);
+            e.bias = out_b;
+            e.drop = dctx(l, 1);
+            if (rb) { e.res_t = x; e.out_t = L.x1; } else { e.res = x; e.out_f32 = L.x1; }
+            if (m3l_gemm_nt(dt, L.o, HD, L.wo, HD, M, D, HD, &e, st)) return 1;
+            if (m3l_ln_fwd(dt, L.x1, M, D, ln2_w, ln2_b, LN_EPS, L.xn2, nullptr, st)) return 1;
+            break;
+        default:                    // M3L_TF_IDENTITY: no out-projection
+            if (m3l_axpy_t(dt, x, L.o, (long)M * D, L.x1, st)) return 1;
             if (m3l_ln_fwd(dt, L.x1, M, D, ln2_w, ln2_b, LN_EPS, L.xn2, nullptr, st)) return 1;
         }
-        }
-        if (!po && block && !(m3l_mlp_t192_short() && m3l_mlp_t192_supported(dt, D, mlp, M)) && m3l_mlp_block_supported(dt, D, mlp, n)) {
-            // the feed-forward half in one launch as well
+        // ---- feed-forward: fc1, GELU, fc2, residual
+        switch (pl.fwd_mlp) {
+        case M3L_TF_IN_TAIL:        // long sequences: out-proj + residual + LN2 + fc1 + GELU + fc2 + residual in ONE launch per 192-row tile
+            if (m3l_attn_tail_mlp_t192_fwd(D, M, mlp, L.o, x, L.wo, out_b, ln2_w, ln2_b, LN_EPS, L.x1, L.xn2, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused,
+                                           L.xout, st))
+                return 1;
+            break;
+        case M3L_TF_BLOCK:          // short sequences: the feed-forward half in one launch as well
             if (m3l_mlp_block_fwd(D, mlp, B, n, L.xn2, L.x1, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused, L.xout, st)) return 1;
-            x = L.xout;
-            continue;
-        }
-        if (!po && !fuse && m3l_mlp_t192_supported(dt, D, mlp, M)) {
-            // long sequences: fc1 + GELU + fc2 + residual per 192-row tile, the hidden activation never leaves the CU between the GEMMs
+            break;
+        case M3L_TF_T192:           // fc1 + GELU + fc2 + residual per 192-row tile, the hidden activation never leaves the CU between the GEMMs
             if (m3l_mlp_t192_fwd(D, M, mlp, L.xn2, L.x1, L.w1, fc1_b, L.w2, fc2_b, L.u, h_fused, L.xout, st)) return 1;
-            x = L.xout;
-            continue;
-        }
-        e = epi0(mlp);
-        e.bias = fc1_b; e.act = 1; e.out_pre = L.u; e.out_t = L.h;     // dropout: h is saved dropped (fc2's operand and its wgrad operand)
-        e.drop = dctx(l, 2);
-        if (m3l_gemm_nt(dt, L.xn2, D, L.w1, D, M, mlp, D, &e, st)) return 1;
-        if (fuse) {
-            RowLnEpi r;
-            memset(&r, 0, sizeof(r));
-            r.bias = fc2_b; r.res = L.x1; r.x_out = L.xout; r.eps = LN_EPS;
-            if (l + 1 < c->depth) {
-                const void* const* tn = tensors + 11 * (l + 1);
-                r.gamma = (const float*)tn[0]; r.beta = (const float*)tn[1]; r.out_t = w.L[l + 1].xn1;
+            break;
+        default:
+            e = epi0(mlp);
+            e.bias = fc1_b; e.act = 1; e.out_pre = L.u; e.out_t = L.h;     // dropout: h is saved dropped (fc2's operand and its wgrad operand)
+            e.drop = dctx(l, 2);
+            if (m3l_gemm_nt(dt, L.xn2, D, L.w1, D, M, mlp, D, &e, st)) return 1;
+            if (pl.fwd_mlp == M3L_TF_ROWLN) {      // fc2 + LN1 of the next layer (or the final norm) in one GEMM
+                RowLnEpi r;
+                memset(&r, 0, sizeof(r));
+                r.bias = fc2_b; r.res = L.x1; r.x_out = L.xout; r.eps = LN_EPS;
+                if (l + 1 < c->depth) {
+                    const void* const* tn = tensors + 11 * (l + 1);
+                    r.gamma = (const float*)tn[0]; r.beta = (const float*)tn[1]; r.out_t = w.L[l + 1].xn1;
+                } else {
+                    r.gamma = (const float*)tfin[0]; r.beta = (const float*)tfin[1];
+                    r.out_t = dt ? y_t : (y_t ? y_t : nullptr);
+                    r.out_f32 = y32;
+                    if (dt == 0 && y_t && y32 == nullptr) { r.out_f32 = (float*)y_t; r.out_t = nullptr; }
+                }
+                if (m3l_gemm_nt_rowln(dt, ROWLN_FWD, L.h, mlp, L.w2, mlp, M, D, mlp, &r, st)) return 1;
             } else {
-                r.gamma = (const float*)tfin[0]; r.beta = (const float*)tfin[1];
-                r.out_t = dt ? y_t : (y_t ? y_t : nullptr);
-                r.out_f32 = y32;
-                if (dt == 0 && y_t && y32 == nullptr) { r.out_f32 = (float*)y_t; r.out_t = nullptr; }
-                final_done = true;
+                e = epi0(D);
+                e.bias = fc2_b;
+                e.drop = dctx(l, 3);
+                if (rb) { e.res_t = L.x1; e.out_t = L.xout; } else { e.res = L.x1; e.out_f32 = L.xout; }
+                if (m3l_gemm_nt(dt, L.h, mlp, L.w2, mlp, M, D, mlp, &e, st)) return 1;
             }
-            if (m3l_gemm_nt_rowln(dt, ROWLN_FWD, L.h, mlp, L.w2, mlp, M, D, mlp, &r, st)) return 1;
-        } else {
-            e = epi0(D);
-            e.bias = fc2_b;
-            e.drop = dctx(l, 3);
-            if (rb) { e.res_t = L.x1; e.out_t = L.xout; } else { e.res = L.x1; e.out_f32 = L.xout; }
-            if (m3l_gemm_nt(dt, L.h, mlp, L.w2, mlp, M, D, mlp, &e, st)) return 1;
         }
         x = L.xout;
     }
-    if (final_done) return 0;
+    if (pl.fwd_mlp == M3L_TF_ROWLN && c->depth) return 0;       // the last fc2 launch wrote the final norm
     return m3l_ln_fwd(dt, x, M, D, (const float*)tfin[0], (const float*)tfin[1], LN_EPS, y_t, y32, st);
 }
 
@@ -849,8 +784,8 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
                                       int dy_dtype, float* dx_in, float* const* grads, int layer_hi, int layer_lo, const m3l_dropout* drop,
                                       void* stream) {
     if (check_tf(c, B, n)) return 1;
-    const bool dp = drop_active(drop);
-    const bool po = dp || tf_dh(c) != 64;     // every layer on the per-op chain (the forward's decision)
+    const TfPlan pl = tf_plan(c, B, n, drop);     // made from the switches in force now; what must match the forward's is checked below
+    const bool dp = pl.dropout, rb = pl.rb;
     M3L_CHECK(0 <= layer_lo && layer_lo <= layer_hi && layer_hi <= c->depth, "transformer_bwd: bad layer range [%d, %d)", layer_lo, layer_hi);
     M3L_CHECK(dy_dtype == 0 || dy_dtype == c->dtype, "transformer_bwd: dy dtype %d incompatible with compute dtype %d", dy_dtype, c->dtype);
     hipStream_t st = (hipStream_t)stream;
@@ -870,22 +805,21 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             batches.back().count = 0;
             batches.back().D = D;
         }
-        ReduceBatch& rb = batches.back();
+        ReduceBatch& bt = batches.back();
         float* slot = w.ln_part + (size_t)id * w.ln_part_stride;
-        rb.it[rb.count++] = ReduceBatchItem{slot, {dgamma, dbeta, dbias}, G > 0 ? G : lnG};
+        bt.it[bt.count++] = ReduceBatchItem{slot, {dgamma, dbeta, dbias}, G > 0 ? G : lnG};
         return slot;
     };
     const float* x_last = c->depth ? w.L[c->depth - 1].xout : x_in;
-    const bool rb = tf_rb(c, B, n, use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, mlp) && m3l_gemm_nt_rowln_supported(dt, D, 3 * HD));
     {
         std::lock_guard<std::mutex> lock(g_tf_rec_mu);
         auto it = g_tf_rec.find(ws);
         if (it != g_tf_rec.end()) {
             const TfRecord& r = it->second;
-            M3L_CHECK(r.rb == (rb ? 1 : 0) && r.drop_h == (drop_h() ? 1 : 0) && r.p == (dp ? drop->p : 0.f) && r.seed == (dp ? drop->seed : 0),
+            M3L_CHECK(r.rb == pl.rb && r.drop_h == pl.drop_h && r.p == pl.p && r.seed == pl.seed,
                       "transformer_bwd: the forward on this workspace ran with residual mode %d, drop_h %d, dropout p=%g seed=%llu; the backward "
-                      "got %d, %d, p=%g seed=%llu", r.rb, r.drop_h, (double)r.p, (unsigned long long)r.seed, rb ? 1 : 0, drop_h() ? 1 : 0,
-                      dp ? (double)drop->p : 0.0, (unsigned long long)(dp ? drop->seed : 0));
+                      "got %d, %d, p=%g seed=%llu", r.rb, r.drop_h, (double)r.p, (unsigned long long)r.seed, pl.rb, pl.drop_h, (double)pl.p,
+                      (unsigned long long)pl.seed);
             if (layer_lo == 0) g_tf_rec.erase(it);
         }
     }
@@ -903,7 +837,6 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             return 1;
     }
     if (side_init()) return 2;
-    const bool fuse = !po && use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, mlp) && m3l_gemm_nt_rowln_supported(dt, D, 3 * HD);
     const bool wg_inline = wgrad_inline();
     hipStream_t s2 = wg_inline ? st : g_side.s;
     // completion of the wgrad launch that last read operand set i.  A backward split into several range calls (chunks, for the
@@ -948,13 +881,21 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
         }
         return 0;
     };
-    const int csrows = m3l_gemm_nt_colsum_rows(M, mlp);
+    // the kernel that ends a layer writes the gradient of the layer's input = dres + its own result: fp32 to dx_out (the running w.dx, or the
+    // caller's dx_in at layer 0) and in the compute type to the next layer's operand set.  bf16 residual stream: dres is dx1_t of this layer
+    // and the result exists in the compute type only — the next layer's dx_t, or at layer 0 the caller's dx_in where it takes bf16
+    // (m3l_call_io), else a bf16 scratch (the upper half of the unused w.dx) that is cast to the fp32 dx_in
+    auto layer_out = [&](int l, auto&& launch) -> int {
+        const int cur = l % NS, nxt = l ? (l - 1) % NS : 0;
+        if (!rb) return launch(w.dx, (l == 0 && dx_in) ? dx_in : w.dx, l ? w.dx_t[nxt] : nullptr);
+        const bool io = m3l_call_io() && dx_in;
+        if (launch(reinterpret_cast<const float*>(w.dx1_t[cur]), nullptr, l ? w.dx_t[nxt] : (io ? (void*)dx_in : rb_out0(w, M, D)))) return 1;
+        return (l == 0 && dx_in && !io) ? m3l_cast_bf16_f32(rb_out0(w, M, D), (long)M * D, dx_in, st) : 0;
+    };
     // short sequences whose both backward halves take a block kernel: one launch per weight-gradient group of layers (enc_mega.hip)
-    const bool mega_bwd = !po && (m3l_enc_mega_enabled() & 2) && !fuse && c->project_out && m3l_mlp_block_bwd_supported(dt, D, mlp, n) &&
-                          !(m3l_mlp_t192_supported(dt, D, mlp, M) && m3l_mlp_t192_short()) && m3l_attn_block_bwd_enabled() &&
-                          m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, tf_dh(c)) && w.wg_batch <= M3L_MEGA_BWD_MAX_LAYERS;
+    M3L_CHECK(w.wg_batch <= M3L_MEGA_BWD_MAX_LAYERS, "transformer_bwd: weight-gradient group of %d layers (tf_layout clamps it to 4)", w.wg_batch);
     for (int l = layer_hi - 1; l >= layer_lo; --l) {
-        if (mega_bwd && pend_sets.empty()) {
+        if (pl.mega_bwd && pend_sets.empty()) {
             const int g_lo = std::max(layer_lo, l - w.wg_batch + 1), cnt = l - g_lo + 1;
             const void* lay[M3L_MEGA_BWD_MAX_LAYERS][21];
             for (int ll = l; ll >= g_lo; --ll) {
@@ -975,7 +916,7 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
                 TfLayer& LL = w.L[ll];
                 const int cur = ll % NS;
                 float* const* g = grads + 11 * ll;
-                const int hk = (drop_h() && fused_mlp_kind(c, B, n, fuse)) ? 2 : 0;
+                const int hk = pl.h_from_u ? 2 : 0;
                 pend.push_back(TnProblem{w.dx_t[cur], hk ? LL.u : LL.h, D, mlp, D, mlp, g[9], mlp, D, mlp, 0, 0, hk});
                 pend.push_back(TnProblem{w.du[cur], LL.xn2, mlp, D, mlp, D, g[7], D, mlp, D, 0, 0});
                 pend.push_back(TnProblem{w.dqkv[cur], LL.xn1, 3 * HD, D, 3 * HD, D, g[2], D, 3 * HD, D, 0, 0});
@@ -992,9 +933,12 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
         const float* xl = l ? w.L[l - 1].xout : ((rb && !m3l_call_io()) ? reinterpret_cast<const float*>(rb_xin(w)) : x_in);
         const void* const* t = tensors + 11 * l;
         float* const* g = grads + 11 * l;
+        const float *ln1_w = (const float*)t[0], *ln2_w = (const float*)t[5];
+        float* db_out = c->project_out ? g[4] : nullptr;                                               // out-proj bias
+        float* db_prev = (l && !dp) ? grads[11 * (l - 1) + 10] : nullptr;                              // fc2 bias of layer l-1
         // set `cur` (dx_t[cur] was written by layer l+1's last kernel, which claimed the set) receives du / dx1_t / dqkv of this layer
         // ---- feed-forward: x_out = x1 + fc2(gelu(fc1(LN2(x1))))
-        GemmEpi e = epi0(mlp);
+        GemmEpi e;
         // dropout: dpre3 = mask3 scale dx (the fc2 output's gradient) -> fc2 bias gradient now, operand of the dgrad and of dW2
         const void* dy3 = w.dx_t[cur];
         if (dp) {
@@ -1003,64 +947,43 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             if (g[10] && m3l_reduce_rows(w.dpart, m3l_dropout_bwd_blocks(M), D, D, g[10], 0, st)) return 1;
             dy3 = w.dp3[cur];
         }
-        const bool mlp_t192 = !po && !fuse && m3l_mlp_t192_supported(dt, D, mlp, M) && (m3l_mlp_t192_short() || !m3l_mlp_block_bwd_supported(dt, D, mlp, n));
-        const bool mlp_block = !po && !fuse && !mlp_t192 && m3l_mlp_block_bwd_supported(dt, D, mlp, n);
-        int cs_rows = csrows;
-        if (mlp_block) {
-            // short sequences: du, its column sums, dxn2 and the LN2 backward in one launch; one partial row per sample
-            cs_rows = B;
-            if (m3l_mlp_block_bwd(D, mlp, B, n, w.dx_t[cur], rb ? nullptr : w.dx, L.x1, (const float*)t[5], L.u, L.w2T, L.w1T, LN_EPS, w.du[cur], w.dx1_t[cur],
-                                  w.scratch2[cur], ln_slot(2 * l + 1, g[5], g[6], c->project_out ? g[4] : nullptr, B), st))
+        switch (pl.bwd_mlp) {
+        case M3L_TF_BLOCK:      // short sequences: du, its column sums, dxn2 and the LN2 backward in one launch; one partial row per sample
+            if (m3l_mlp_block_bwd(D, mlp, B, n, w.dx_t[cur], rb ? nullptr : w.dx, L.x1, ln2_w, L.u, L.w2T, L.w1T, LN_EPS, w.du[cur], w.dx1_t[cur],
+                                  w.scratch2[cur], ln_slot(2 * l + 1, g[5], g[6], db_out, B), st))
                 return 1;
-        } else if (mlp_t192) {
-            // long sequences: the same chain per 192-row tile; one partial row per tile
-            cs_rows = m3l_mlp_t192_cs_rows(D, M);
-            if (m3l_mlp_t192_bwd(D, M, mlp, w.dx_t[cur], rb ? nullptr : w.dx, L.x1, (const float*)t[5], L.u, L.w2T, L.w1T, LN_EPS, w.du[cur], w.dx1_t[cur],
-                                 w.scratch2[cur], ln_slot(2 * l + 1, g[5], g[6], c->project_out ? g[4] : nullptr, m3l_mlp_t192_tiles(D, M)), st))
+            break;
+        case M3L_TF_T192:       // long sequences: the same chain per 192-row tile; one partial row per tile
+            if (m3l_mlp_t192_bwd(D, M, mlp, w.dx_t[cur], rb ? nullptr : w.dx, L.x1, ln2_w, L.u, L.w2T, L.w1T, LN_EPS, w.du[cur], w.dx1_t[cur],
+                                 w.scratch2[cur], ln_slot(2 * l + 1, g[5], g[6], db_out, pl.row_tiles), st))
                 return 1;
-        } else {
-        e.out_t = w.du[cur]; e.gelu_u = L.u; e.colsum_part = w.scratch2[cur];
-        e.drop = dctx(l, 2);                                                                             // (dropout: * mask2 scale)
-        if (m3l_gemm_nt(dt, dy3, D, L.w2T, D, M, mlp, D, &e, st)) return 1;                            // du = (dx W2) * gelu'(u)
-        // (the per-row-block column sums in scratch2[cur] = fc1 bias gradient partials are reduced by the wgrad group's reduce)
-        }
-        if (mlp_block || mlp_t192) {
-        } else if (fuse) {
-            // dxn2 = du W1 and the LN2 backward in one kernel: dx1 = dx + dLN(dxn2) (in place) + compute-type copy + partials
-            RowLnEpi r;
-            memset(&r, 0, sizeof(r));
-            r.x = L.x1; r.gamma = (const float*)t[5]; r.res = w.dx; r.x_out = w.dx; r.out_t = w.dx1_t[cur]; r.part = w.scratch; r.eps = LN_EPS;
-            if (m3l_gemm_nt_rowln(dt, ROWLN_BWD, w.du[cur], mlp, L.w1T, mlp, M, D, mlp, &r, st)) return 1;
-            if (m3l_reduce_rows_seg3(w.scratch, cdiv(M, 64), D, g[5], g[6], c->project_out ? g[4] : nullptr, 0, st)) return 1;
-        } else {
-            e = epi0(D);
-            e.out_t = w.dxn;
-            if (m3l_gemm_nt(dt, w.du[cur], mlp, L.w1T, mlp, M, D, mlp, &e, st)) return 1;             // dxn2 = du W1
-            // dx1 = dx + LN2-backward (in place), + compute-type copy, + out-proj bias grad
-            // (bf16 residual stream: the residual gradient is dx_t[cur] itself, the result exists in the compute type only)
-            if (m3l_ln_bwd(dt, w.dxn, L.x1, M, D, (const float*)t[5], LN_EPS, rb ? reinterpret_cast<const float*>(w.dx_t[cur]) : w.dx,
-                           rb ? nullptr : w.dx, w.dx1_t[cur], dt, ln_slot(2 * l + 1, g[5], g[6], (c->project_out && !dp) ? g[4] : nullptr), nullptr,
-                           nullptr, nullptr, 0, st))
-                return 1;
+            break;
+        default:
+            e = epi0(mlp);
+            e.out_t = w.du[cur]; e.gelu_u = L.u; e.colsum_part = w.scratch2[cur];
+            e.drop = dctx(l, 2);                                                                             // (dropout: * mask2 scale)
+            if (m3l_gemm_nt(dt, dy3, D, L.w2T, D, M, mlp, D, &e, st)) return 1;                            // du = (dx W2) * gelu'(u)
+            // (the per-row-block column sums in scratch2[cur] = fc1 bias gradient partials are reduced by the wgrad group's reduce)
+            if (pl.bwd_mlp == M3L_TF_ROWLN) {
+                // dxn2 = du W1 and the LN2 backward in one kernel: dx1 = dx + dLN(dxn2) (in place) + compute-type copy + partials
+                RowLnEpi r;
+                memset(&r, 0, sizeof(r));
+                r.x = L.x1; r.gamma = ln2_w; r.res = w.dx; r.x_out = w.dx; r.out_t = w.dx1_t[cur]; r.part = w.scratch; r.eps = LN_EPS;
+                if (m3l_gemm_nt_rowln(dt, ROWLN_BWD, w.du[cur], mlp, L.w1T, mlp, M, D, mlp, &r, st)) return 1;
+                if (m3l_reduce_rows_seg3(w.scratch, cdiv(M, 64), D, g[5], g[6], db_out, 0, st)) return 1;
+            } else {
+                e = epi0(D);
+                e.out_t = w.dxn;
+                if (m3l_gemm_nt(dt, w.du[cur], mlp, L.w1T, mlp, M, D, mlp, &e, st)) return 1;             // dxn2 = du W1
+                // dx1 = dx + LN2-backward (in place), + compute-type copy, + out-proj bias grad
+                // (bf16 residual stream: the residual gradient is dx_t[cur] itself, the result exists in the compute type only)
+                if (m3l_ln_bwd(dt, w.dxn, L.x1, M, D, ln2_w, LN_EPS, rb ? reinterpret_cast<const float*>(w.dx_t[cur]) : w.dx,
+                               rb ? nullptr : w.dx, w.dx1_t[cur], dt, ln_slot(2 * l + 1, g[5], g[6], dp ? nullptr : db_out), nullptr,
+                               nullptr, nullptr, 0, st))
+                    return 1;
+            }
         }
         // ---- attention: x1 = x + to_out(attn(LN1(x)))
-        const bool attn_block = mlp_block && m3l_attn_block_bwd_enabled() && m3l_attn_block_supported(dt, D, c->heads, n, c->project_out, tf_dh(c));
-        float* dx_dst = (l == 0 && dx_in) ? dx_in : w.dx;
-        float* db_prev = (l && !dp) ? grads[11 * (l - 1) + 10] : nullptr;                             // fc2 bias of layer l-1
-        if (attn_block) {
-            // short sequences: dO, the attention backward, dxn1 and the LN1 backward in one launch.  It writes dx_t[nxt] (the next
-            // layer's operand set)
-            if (l && claim_set(nxt)) return 2;
-            if (rb) {      // the residual gradient is dx1_t itself; the result goes to the next layer's dx_t, or — layer 0 — through d_o to dx_in
-                const bool io = m3l_call_io() && dx_in;
-                if (m3l_attn_block_bwd(D, B, n, w.dx1_t[cur], nullptr, xl, (const float*)t[0], L.qkv, L.o, L.lse, L.woT, L.wqkvT, LN_EPS, w.dqkv[cur],
-                                       nullptr, l ? w.dx_t[nxt] : (io ? (void*)dx_in : rb_out0(w, M, D)), ln_slot(2 * l, g[0], g[1], db_prev, B), st))
-                    return 1;
-                if (l == 0 && dx_in && !io && m3l_cast_bf16_f32(rb_out0(w, M, D), (long)M * D, dx_in, st)) return 1;
-            } else if (m3l_attn_block_bwd(D, B, n, w.dx1_t[cur], w.dx, xl, (const float*)t[0], L.qkv, L.o, L.lse, L.woT, L.wqkvT, LN_EPS, w.dqkv[cur],
-                                          dx_dst, l ? w.dx_t[nxt] : nullptr, ln_slot(2 * l, g[0], g[1], db_prev, B), st))
-                return 1;
-        }
         const void* d_o = w.dx1_t[cur];
         const void* dy1 = w.dx1_t[cur];           // gradient of the out-proj output (dropout: dpre1 = mask1 scale dx1)
         if (dp && c->project_out) {
@@ -1069,90 +992,92 @@ int m3l_transformer_bwd_range_dropout(const m3l_tf_cfg* c, int B, int n, const f
             if (g[4] && m3l_reduce_rows(w.dpart, m3l_dropout_bwd_blocks(M), D, D, g[4], 0, st)) return 1;
             dy1 = w.dp1[cur];
         }
-        const bool attn_t = !po && !attn_block && !fuse && c->project_out && m3l_attn_t192_fwd_supported(dt, D, c->heads, n, B, tf_dh(c));
-        if (attn_t) {
-            // long sequences: dO + both attention-backward passes of a sample in one launch
+        switch (pl.bwd_attn) {
+        case M3L_TF_BLOCK:
+            // short sequences: dO, the attention backward, dxn1 and the LN1 backward in one launch, the last kernel of the layer: it writes
+            // dx_t[nxt] (the next layer's operand set).  (bf16 residual stream: the residual gradient is dx1_t itself, no dres)
+            if (l && claim_set(nxt)) return 2;
+            if (layer_out(l, [&](const float* dres, float* dx_out, void* dxt_out) {
+                    return m3l_attn_block_bwd(D, B, n, w.dx1_t[cur], rb ? nullptr : dres, xl, ln1_w, L.qkv, L.o, L.lse, L.woT, L.wqkvT, LN_EPS,
+                                              w.dqkv[cur], dx_out, dxt_out, ln_slot(2 * l, g[0], g[1], db_prev, B), st);
+                }))
+                return 1;
+            break;
+        case M3L_TF_T192:       // long sequences: dO + both attention-backward passes of a sample in one launch
             if (m3l_attn_t192_bwd(D, B, n, w.dx1_t[cur], L.qkv, L.o, L.lse, L.woT, w.dqkv[cur], st)) return 1;
+            break;
+        default: {
+            if (c->project_out) {
+                e = epi0(HD);
+                e.out_t = w.d_o;
+                if (m3l_gemm_nt(dt, dy1, D, L.woT, D, M, HD, D, &e, st)) return 1;                          // do = dx1 Wo
+                d_o = w.d_o;
+            }
+            const DropCtx d0 = dctx(l, 0);
+            if (m3l_attn_bwd(dt, L.qkv, L.o, d_o, L.lse, w.dsum, w.dqkv[cur], B, n, c->heads, tf_dh(c), st, &d0)) return 1;
         }
-        if (!attn_block && !attn_t) {
-        if (c->project_out) {
-            e = epi0(HD);
-            e.out_t = w.d_o;
-            if (m3l_gemm_nt(dt, dy1, D, L.woT, D, M, HD, D, &e, st)) return 1;                          // do = dx1 Wo
-            d_o = w.d_o;
-        }
-        const DropCtx d0 = dctx(l, 0);
-        if (m3l_attn_bwd(dt, L.qkv, L.o, d_o, L.lse, w.dsum, w.dqkv[cur], B, n, c->heads, tf_dh(c), st, &d0)) return 1;
         }
         // ---- the weight gradients of the layer join the pending group; every wg_batch layers (and at the end of the range) the group
         // goes out as ONE grouped TN launch + one reduce on the side stream, overlapping the dgrad chains of the layers below
         {
             // dW2 = dx^T h; when the forward did not save h the kernel stages u and applies the GELU of the kernel that made it
-            const int hk = (!po && drop_h() && fused_mlp_kind(c, B, n, fuse)) ? 2 : 0;     // every bf16 kernel evaluates the fitted GELU (form 2)
+            const int hk = pl.h_from_u ? 2 : 0;     // every bf16 kernel evaluates the fitted GELU (form 2)
             pend.push_back(TnProblem{dy3, hk ? L.u : L.h, D, mlp, D, mlp, g[9], mlp, D, mlp, 0, 0, hk});
             pend.push_back(TnProblem{w.du[cur], L.xn2, mlp, D, mlp, D, g[7], D, mlp, D, 0, 0});             // dW1 = du^T xn2
             pend.push_back(TnProblem{w.dqkv[cur], L.xn1, 3 * HD, D, 3 * HD, D, g[2], D, 3 * HD, D, 0, 0}); // dWqkv = dqkv^T xn1
             if (c->project_out) pend.push_back(TnProblem{dy1, L.o, D, HD, D, HD, g[3], HD, D, HD, 0, 0});   // dWo = dx1^T o
-            pend_ex.push_back(TnExtra{w.scratch2[cur], g[8], cs_rows, mlp});                                // fc1 bias gradient
+            pend_ex.push_back(TnExtra{w.scratch2[cur], g[8], pl.cs_rows, mlp});                             // fc1 bias gradient
             pend_sets.push_back(cur);
             if ((int)pend_sets.size() >= w.wg_batch || l == layer_lo) {
                 if (int rc = flush_wgrads()) return rc;
             }
         }
-        // the last kernel of this layer writes dx_t[nxt] (and the next layer then du / dx1_t / dqkv[nxt])
-        if (attn_block) continue;
-        if (fuse) {
+        // ---- dxn1 = dqkv Wqkv and the LN1 backward: the last kernel of this layer writes dx_t[nxt] (and the next layer then du / dx1_t /
+        // dqkv[nxt])
+        switch (pl.bwd_qkv) {
+        case M3L_TF_IN_BLOCK:       // the attention block did it
+            break;
+        case M3L_TF_ROWLN: {
             if (l && claim_set(nxt)) return 2;
             RowLnEpi r;
             memset(&r, 0, sizeof(r));
-            r.x = xl; r.gamma = (const float*)t[0]; r.res = w.dx; r.x_out = dx_dst; r.out_t = l ? w.dx_t[nxt] : nullptr;
+            r.x = xl; r.gamma = ln1_w; r.res = w.dx; r.x_out = (l == 0 && dx_in) ? dx_in : w.dx; r.out_t = l ? w.dx_t[nxt] : nullptr;
             r.part = w.scratch; r.eps = LN_EPS;
-            if (m3l_gemm_nt_rowln(dt, ROWLN_BWD, w.dqkv[cur], 3 * HD, L.wqkvT, 3 * HD, M, D, 3 * HD, &r, st)) return 1;   // dxn1 + LN1 backward
+            if (m3l_gemm_nt_rowln(dt, ROWLN_BWD, w.dqkv[cur], 3 * HD, L.wqkvT, 3 * HD, M, D, 3 * HD, &r, st)) return 1;
             if (m3l_reduce_rows_seg3(w.scratch, cdiv(M, 64), D, g[0], g[1], db_prev, 0, st)) return 1;
-        } else if (!po && m3l_qkv_bwd_t192_supported(dt, D, 3 * HD, M)) {
-            // long sequences: dxn1 and the LN1 backward per 192-row tile, dxn1 never leaves the registers
+            break;
+        }
+        case M3L_TF_T192:           // long sequences: per 192-row tile, dxn1 never leaves the registers
             if (l && claim_set(nxt)) return 2;
-            const int tiles = m3l_qkv_bwd_t192_tiles(D, M);
-            if (rb) {
-                // dres = dx1_t of this layer (bf16), result only in the compute type: the next layer's dx_t, or — layer 0 — a bf16 scratch
-                // (the upper half of the unused w.dx) that is cast to the fp32 gradient of the stack's input
-                const bool io = m3l_call_io() && dx_in;           // the caller takes the input gradient as bf16: no cast
-                void* out_t = l ? w.dx_t[nxt] : (io ? (void*)dx_in : rb_out0(w, M, D));
-                if (m3l_qkv_bwd_t192(D, M, 3 * HD, w.dqkv[cur], xl, (const float*)t[0], L.wqkvT, reinterpret_cast<const float*>(w.dx1_t[cur]), LN_EPS,
-                                     nullptr, out_t, ln_slot(2 * l, g[0], g[1], db_prev, tiles), st))
-                    return 1;
-                if (l == 0 && dx_in && !io && m3l_cast_bf16_f32(rb_out0(w, M, D), (long)M * D, dx_in, st)) return 1;
-            } else if (m3l_qkv_bwd_t192(D, M, 3 * HD, w.dqkv[cur], xl, (const float*)t[0], L.wqkvT, w.dx, LN_EPS, dx_dst, l ? w.dx_t[nxt] : nullptr,
-                                        ln_slot(2 * l, g[0], g[1], db_prev, tiles), st))
+            if (layer_out(l, [&](const float* dres, float* dx_out, void* dxt_out) {
+                    return m3l_qkv_bwd_t192(D, M, 3 * HD, w.dqkv[cur], xl, ln1_w, L.wqkvT, dres, LN_EPS, dx_out, dxt_out,
+                                            ln_slot(2 * l, g[0], g[1], db_prev, pl.qkv_tiles), st);
+                }))
                 return 1;
-        } else {
+            break;
+        default:
             e = epi0(D);
             e.out_t = w.dxn;
             if (m3l_gemm_nt(dt, w.dqkv[cur], 3 * HD, L.wqkvT, 3 * HD, M, D, 3 * HD, &e, st)) return 1;    // dxn1 = dqkv Wqkv
             if (l && claim_set(nxt)) return 2;
-            if (rb) {
-                const bool io = m3l_call_io() && dx_in;
-                void* out_t = l ? w.dx_t[nxt] : (io ? (void*)dx_in : rb_out0(w, M, D));
-                if (m3l_ln_bwd(dt, w.dxn, xl, M, D, (const float*)t[0], LN_EPS, reinterpret_cast<const float*>(w.dx1_t[cur]), nullptr, out_t, dt,
-                               ln_slot(2 * l, g[0], g[1], db_prev), nullptr, nullptr, nullptr, 0, st))
-                    return 1;
-                if (l == 0 && dx_in && !io && m3l_cast_bf16_f32(rb_out0(w, M, D), (long)M * D, dx_in, st)) return 1;
-            } else if (m3l_ln_bwd(dt, w.dxn, xl, M, D, (const float*)t[0], LN_EPS, w.dx, dx_dst, l ? w.dx_t[nxt] : nullptr, dt,
-                                  ln_slot(2 * l, g[0], g[1], db_prev), nullptr, nullptr, nullptr, 0, st))
+            if (layer_out(l, [&](const float* dres, float* dx_out, void* dxt_out) {
+                    return m3l_ln_bwd(dt, w.dxn, xl, M, D, ln1_w, LN_EPS, dres, dx_out, dxt_out, dt, ln_slot(2 * l, g[0], g[1], db_prev), nullptr,
+                                      nullptr, nullptr, 0, st);
+                }))
                 return 1;
         }
     }
     // the batched LayerNorm-parameter reduce: after the last ln_bwd of the range, on the side stream behind the weight gradients
     bool side_work = !launched.empty();
     if (batches[0].count > 0 && wg_inline) {
-        for (const ReduceBatch& rb : batches)
-            if (m3l_reduce_rows_batch(&rb, 0, st)) return 1;
+        for (const ReduceBatch& bt : batches)
+            if (m3l_reduce_rows_batch(&bt, 0, st)) return 1;
     } else if (batches[0].count > 0) {
         hipEvent_t ln_ready = side_event();
         M3L_HIP(hipEventRecord(ln_ready, st));
         M3L_HIP(hipStreamWaitEvent(g_side.s, ln_ready, 0));
-        for (const ReduceBatch& rb : batches)
-            if (m3l_reduce_rows_batch(&rb, 0, g_side.s)) return 1;
+        for (const ReduceBatch& bt : batches)
+            if (m3l_reduce_rows_batch(&bt, 0, g_side.s)) return 1;
         side_work = true;
     }
     // join: every gradient of the range is complete before anything later on the caller's stream — now, or (deferred mode) when the

@@ -123,6 +123,10 @@ int step_dims(const m3l_mae_cfg* c, StepDims* d) {
     return 0;
 }
 
+// 1: the decoder takes its input, and returns the gradient of it, as bf16 (m3l_call_io): its plan runs the bf16 residual stream — forward and
+// backward of a step ask here, once per call — and no learned positions are trained (their batch sums read the fp32 d_dec_in)
+bool step_dec_io(const m3l_mae_cfg* c, const StepDims& d, int B) { return m3l_transformer_rb(&c->dec, B, d.N) && !c->learned_pos; }
+
 // front-end buffers for L tokens per sample out of N (L == N: no gather)
 void front_layout(Arena& a, const m3l_mae_cfg* c, const StepDims& d, int B, int L, bool learned_scatter, FrontWs* f) {
     memset(f, 0, sizeof(*f));
@@ -317,7 +321,7 @@ int m3l_mae_step_fwd_dropout(const m3l_mae_cfg* c, int B, const float* image, co
     if (m3l_transformer_fwd_dropout(&c->enc, B, d.nvis, w.tokens, tensors + g.enc, w.ws_enc, w.enc_t, w.enc32, enc_drop, st)) return 1;
     // enc_to_dec + un-shuffle + decoder positions (:270-307); f32 compute: the "compute-type" encoder output is the f32 one.  When the
     // decoder runs the bf16 residual stream, its input (and, in the backward, the gradient of it) is exchanged as bf16: no boundary casts
-    const IoScope dec_io(m3l_transformer_rb(&c->dec, B, d.N) && !c->learned_pos);      // (the same rule as the backward's)
+    const IoScope dec_io(step_dec_io(c, d, B));
     if (m3l_unshuffle_fwd(&c->geom, d.D, d.dd, d.dt, B, d.nvis, d.nmask, unmasked, masked, w.enc32, d.dt ? w.enc_t : (void*)w.enc32,
                           tensors + g.glue, w.ws_glue, w.dec_in, st))
         return 1;
@@ -398,7 +402,7 @@ int m3l_mae_step_bwd_dropout(const m3l_mae_cfg* c, int B, const float* image, co
                            grads + g.heads, st))
         return 1;
     if (stage_done()) return 1;
-    const bool dec_io = m3l_transformer_rb(&c->dec, B, d.N) && !c->learned_pos;     // (the batch sums of learned positions read fp32 d_dec_in)
+    const bool dec_io = step_dec_io(c, d, B);
     int enc_code = 0;
     {
         const IoScope io(dec_io);

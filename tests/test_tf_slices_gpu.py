@@ -47,40 +47,40 @@ def _module(case):
     return _MODULES[k]
 
 
-def _q(symbol, *args):
-    """a dispatch predicate of the library (C++ linkage, so by its mangled name: a missing symbol is an AttributeError, never a quiet pass)"""
-    fn = getattr(L.lib(), symbol)
-    fn.restype, fn.argtypes = (C.c_bool if symbol.endswith("rowln_supportediii") else C.c_int), [C.c_int] * len(args)
-    return int(fn(*args))
+def _plan(case, tf):
+    """the library's kernel selection for the case under the switches in force (m3l_transformer_plan: what forward and backward dispatch on)"""
+    out = L.TfPlan()
+    L.check(L.lib().m3l_transformer_plan(C.byref(tf._cfg()), case.B, case.n, None, C.byref(out)), "m3l_transformer_plan")
+    return out
 
 
-def _assert_family(case, sw):
-    """With the case's switches in force: the predicates m3l_transformer_fwd_dropout / _bwd_range_dropout dispatch on select the family the
-    case is named after (no quiet fall-back to another one), and the row tiles have the case's height."""
-    D, H, dh, mlp, n, B = case.D, case.heads, case.dim_head, case.mlp, case.n, case.B
-    M, HD = B * n, H * dh
-    block = _q("_Z24m3l_attn_block_supportediiiiii", 1, D, H, n, 1, dh)
-    mlp_block = _q("_Z23m3l_mlp_block_supportediiii", 1, D, mlp, n)
-    tiles = _q("_Z22m3l_mlp_t192_supportediiii", 1, D, mlp, M)
-    fam = case.family
+def _assert_family(case, sw, p):
+    """With the case's switches in force the plan p selects the family the case is named after, for every half layer and both directions
+    (no quiet fall-back to another one), and the row tiles have the case's height."""
+    M, fam = case.B * case.n, case.family
+    fields = {f: getattr(p, f) for f in ("fwd_attn", "fwd_outproj", "fwd_mlp", "bwd_mlp", "bwd_attn", "bwd_qkv")}
+    block = p.fwd_attn == L.TF_BLOCK and p.fwd_outproj == L.TF_IN_BLOCK
+    mlp_block = p.fwd_mlp == L.TF_BLOCK and p.bwd_mlp == L.TF_BLOCK
+    tiles = bool({L.TF_T192, L.TF_TAIL_T192, L.TF_IN_TAIL} & set(fields.values()))
     if fam == "perop_dh":
-        assert dh != 64                                  # every layer on the per-op chain (m3l_transformer_fwd_dropout: `po`)
-    elif fam in ("perop", "rowln"):
-        assert not block and not tiles
-        if fam == "rowln":
-            assert all(_q("_Z27m3l_gemm_nt_rowln_supportediii", 1, D, k) for k in (HD, mlp, 3 * HD))
+        assert case.dim_head != 64 and p.per_op                  # every layer on the per-op chain
+    if fam in ("perop", "perop_dh"):
+        assert set(fields.values()) == {L.TF_PER_OP, L.TF_GEMM} and not p.rowln, fields
+    elif fam == "rowln":
+        assert p.rowln_cfg and p.rowln and not block and not tiles
+        assert fields == dict(fwd_attn=L.TF_PER_OP, fwd_outproj=L.TF_ROWLN, fwd_mlp=L.TF_ROWLN, bwd_mlp=L.TF_ROWLN, bwd_attn=L.TF_PER_OP, bwd_qkv=L.TF_ROWLN)
     elif fam.startswith("block") or fam.startswith("mega"):
-        assert block and mlp_block and not tiles
-        assert bool(_q("_Z26m3l_attn_block_bwd_enabledv")) == (fam != "block1")
-        assert _q("_Z20m3l_enc_mega_enabledv") == sw["enc_mega"]
+        assert block and mlp_block and not tiles, fields
+        assert (p.bwd_attn == L.TF_BLOCK) == (p.bwd_qkv == L.TF_IN_BLOCK) == (fam != "block1")
+        assert (p.mega_fwd, p.mega_bwd) == (sw["enc_mega"] & 1, sw["enc_mega"] >> 1 & 1)
     else:                                                # row tiles
-        assert not block and tiles and _q("_Z26m3l_qkv_bwd_t192_supportediiii", 1, D, 3 * HD, M)
-        assert _q("_Z18m3l_mlp_t192_tilesii", D, M) == -(-M // case.tile), (M, case.tile)
-        assert bool(_q("_Z27m3l_attn_t192_fwd_supportediiiiii", 1, D, H, n, B, dh)) == (case.kt is None)
+        assert not block and p.fwd_mlp in (L.TF_T192, L.TF_IN_TAIL) and p.bwd_mlp == L.TF_T192 and p.bwd_qkv == L.TF_T192, fields
+        assert p.row_tiles == -(-M // case.tile), (M, case.tile)
+        assert (p.fwd_attn == L.TF_T192) == (p.bwd_attn == L.TF_T192) == (case.kt is None)
 
 
 def _hip(case, dt, rb, drop_h=0, sw=None):
-    """-> (tensors of the HIP run, whether the stack ran the bf16 residual stream).  Every switch is restored whatever happens."""
+    """-> (tensors of the HIP run, whether the stack ran the bf16 residual stream, the plan of a bf16 run).  Every switch is restored whatever happens."""
     lib = L.lib()
     tf = _module(case)
     tf.compute_dtype = dt
@@ -92,8 +92,9 @@ def _hip(case, dt, rb, drop_h=0, sw=None):
         for name, v in want:
             old.append((name, getattr(lib, _SETTERS[name])(v)))
         ran_rb = bool(lib.m3l_transformer_rb(C.byref(tf._cfg()), case.B, case.n)) if dt == "bf16" else False
-        if dt == "bf16":
-            _assert_family(case, dict(case.sw, **(sw or {})))
+        plan = _plan(case, tf) if dt == "bf16" else None
+        if plan is not None:
+            _assert_family(case, dict(case.sw, **(sw or {})), plan)
         tf.zero_grad(set_to_none=True)
         xg = x.clone().requires_grad_(True)
         y = tf(xg)
@@ -102,7 +103,7 @@ def _hip(case, dt, rb, drop_h=0, sw=None):
     finally:
         for name, v in reversed(old):
             getattr(lib, _SETTERS[name])(v)
-    return T.tensors_of((y.detach().cpu(), xg.grad.cpu(), {k: p.grad.cpu().clone() for k, p in tf.named_parameters()})), ran_rb
+    return T.tensors_of((y.detach().cpu(), xg.grad.cpu(), {k: p.grad.cpu().clone() for k, p in tf.named_parameters()})), ran_rb, plan
 
 
 # Findings (EXPERIMENTS 5.13): the slices that exceed the issue's bound, each with (error, bound) as measured.  None has a cause in a kernel:
@@ -148,7 +149,7 @@ def _checked(case, dt, rb):
     """(worst ratios, failures, ran_rb) of a run, computed once"""
     rid = _run_id(case, dt, rb)
     if rid not in _RESULTS:
-        got, ran_rb = _hip(case, dt, rb)
+        got, ran_rb, _ = _hip(case, dt, rb)
         X = K.reference(case, "X")
         Y = K.reference(case, "R", ran_rb) if dt == "bf16" else K.reference(case, "F")
         assert set(got) == set(X)
@@ -213,3 +214,46 @@ def test_drop_h_is_bit_identical_on_these_inputs(case, rb):
     a, b = _hip(case, "bf16", rb, drop_h=0)[0], _hip(case, "bf16", rb, drop_h=1)[0]
     for k in a:
         assert torch.equal(a[k], b[k]), k
+
+
+# one case per family, at the smallest depth the family has: (family, D, n, depth)
+NAMED = [("perop", 192, 40, 1), ("perop_dh", 128, 33, 2), ("block1", 128, 17, 2), ("block3", 128, 17, 2), ("mega1", 192, 48, 2), ("mega2", 192, 48, 2),
+         ("mega3", 192, 48, 2), ("rowtile_tt12", 192, 100, 1), ("rowtile_tt12", 256, 75, 2), ("rowln", 192, 40, 1)]
+# the profiler kinds that belong to one family; ln_fwd, ln_bwd, gemm_nt..., wgrad..., prep_weights, cast, reduce_batch, colsum run under all
+FAMILY_KINDS = {"enc_fwd_mega", "enc_bwd_mega", "attn_block_fwd", "attn_block_bwd", "mlp_block_fwd", "mlp_block_bwd", "attn_t192_fwd", "attn_t192_bwd",
+                "attn_tail_mlp_t192_fwd", "mlp_t192_fwd", "mlp_t192_bwd", "qkv_bwd_t192", "gemm_nt_lnfwd", "gemm_nt_lnbwd", "attn_fwd", "attn_bwd"}
+
+
+def _kinds_of(p):
+    """the family kinds a forward + backward under plan p launches"""
+    fwd = {"enc_fwd_mega"} if p.mega_fwd else {
+        {L.TF_BLOCK: "attn_block_fwd", L.TF_T192: "attn_t192_fwd", L.TF_PER_OP: "attn_fwd"}[p.fwd_attn],
+        {L.TF_ROWLN: "gemm_nt_lnfwd"}.get(p.fwd_outproj),
+        {L.TF_IN_TAIL: "attn_tail_mlp_t192_fwd", L.TF_BLOCK: "mlp_block_fwd", L.TF_T192: "mlp_t192_fwd", L.TF_ROWLN: "gemm_nt_lnfwd"}.get(p.fwd_mlp)}
+    bwd = {"enc_bwd_mega"} if p.mega_bwd else {
+        {L.TF_BLOCK: "mlp_block_bwd", L.TF_T192: "mlp_t192_bwd", L.TF_ROWLN: "gemm_nt_lnbwd"}.get(p.bwd_mlp),
+        {L.TF_BLOCK: "attn_block_bwd", L.TF_T192: "attn_t192_bwd", L.TF_PER_OP: "attn_bwd"}[p.bwd_attn],
+        {L.TF_T192: "qkv_bwd_t192", L.TF_ROWLN: "gemm_nt_lnbwd"}.get(p.bwd_qkv)}
+    return (fwd | bwd) - {None}
+
+
+@pytest.mark.parametrize("key", NAMED, ids=lambda k: "%s-D%dn%dd%d" % k)
+def test_plan_names_the_kernels_that_run(key):
+    """forward + backward of one case per family under the profiler: the family kernels launched are EXACTLY those the plan names — what
+    m3l_transformer_plan says and what the dispatcher does cannot drift apart"""
+    case, = [c for c in K.CASES if (c.family, c.D, c.n, c.depth) == key]
+    lib = L.lib()
+    lib.m3l_prof_begin(None, 1)
+    try:
+        plan = _hip(case, "bf16", 1)[2]
+    finally:
+        lib.m3l_prof_end()
+    ran = set()
+    for i in range(lib.m3l_prof_count()):
+        name = C.create_string_buffer(96)
+        a, b, c_, d = C.c_double(), C.c_long(), C.c_double(), C.c_double()
+        lib.m3l_prof_get(i, name, 96, C.byref(a), C.byref(b), C.byref(c_), C.byref(d))
+        if b.value:
+            ran.add(name.value.decode().split("[")[0])
+    print(f"\n[plan] {case.id}: {sorted(ran)}", end="")
+    assert ran & FAMILY_KINDS == _kinds_of(plan), (sorted(ran & FAMILY_KINDS), sorted(_kinds_of(plan)))
