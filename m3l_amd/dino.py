@@ -13,7 +13,13 @@ seeded initial values and arithmetic.
          mean_b( Q sum_p lse(S[p,b,:] / ts) - 1/ts sum_k (sum_q T[q,b,k]) (sum_p S[p,b,k]) ), and
          dS[p,b,k] = g / (ts B) (Q softmax(S[p,b,:] / ts)[k] - sum_q T[q,b,k]): neither the P x Q products nor a log-softmax are stored.
   centre : the column sums of this step's teacher logits wait in `pending` and enter the centre at the start of the NEXT step
-         (DINOLoss.apply_center_update), so the first step runs with a zero centre.
+         (CenteredLoss.apply_center_update), so the first step runs with a zero centre.
+  iBOT patch loss : the same cross-entropy, row by row, over the Q x (B n) patch rows of the global views (`tactile_ssl/loss/ibot_patch_loss.py`).
+         Both terms take one path: RowFamily.args / loss_forward / loss_grad, the nodes RowLossFn and RowHeadLossFn (DinoLossFn, IbotLossFn,
+         HeadLossFn and IbotHeadLossFn only name their family), and the centre state of CenteredLoss.  What differs is data, a RowFamily:
+         DINO_ROWS (m3l_op_dino_*, a sample's teacher sums in LDS, B <= 255) or PATCH_ROWS
+         (m3l_op_ibot_*, tiles over the rows, Q = P, Q R <= 65535), and in DINOLoss / iBOTPatchLoss the centre's shape and how its pending
+         sums are formed (plain column sums over the rows; the split column sum scaled by samples / rows).
   Sinkhorn-Knopp : the teacher's other target (`centering="sinkhorn_knopp"`).  The reference scales exp(T / tt) to unit column and row sums
          n times; in the log domain that is u[k] = logsumexp_r(z[r,k] - w[r]), w[r] = logsumexp_k(z[r,k] - u[k]) from w = 0, and the
          targets are softmax((T - c) / tt) with c = tt u: one K-vector in the centre's place, no assignment matrix.  The u pass is the
@@ -23,6 +29,7 @@ There is no eager fallback: every number comes from a kernel, torch owns memory 
 """
 import ctypes as C
 import math
+from typing import Callable, NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -253,84 +260,146 @@ def _teacher_rows(teacher_output):
     return T.reshape(-1, K), T.numel() // K, K
 
 
-def _loss_forward(S, T, center, P, Q, B, K, inv_ts, inv_tt):
-    lib = L.lib()
-    s_stats = _row_stats(S, P * B, K, None, inv_ts)
-    t_stats = _row_stats(T, Q * B, K, center, inv_tt)
-    loss = torch.empty((), dtype=torch.float32, device=S.device)
-    ws = _ws(lib.m3l_op_dino_ws_bytes(B, K), S.device)
-    L.check(lib.m3l_op_dino_loss(L.ptr(S), P, L.ptr(T), Q, B, K, L.ptr(center), inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats), L.ptr(ws),
-                                 L.ptr(loss), _stream()), "m3l_op_dino_loss")
-    return loss, s_stats, t_stats
+IBOT_MAX_ROWS = 65535          # Q R of one call (include/m3l_amd.h, "iBOT patch loss")
 
 
-def _loss_grad(dt, S, T, center, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats, dloss):
-    """-> dS^T (K, ldr) in the compute type, ldr = P B rounded up to a multiple of 8 (pad columns zero)."""
-    ldr = _ld8(P * B)
-    dST = torch.empty(K, ldr, dtype=tdtype(dt), device=S.device)
-    L.check(L.lib().m3l_op_dino_grad(dt, L.ptr(S), P, L.ptr(T), Q, B, K, L.ptr(center), inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats),
-                                     L.ptr(dloss), L.ptr(dST), ldr, _stream()), "m3l_op_dino_grad")
-    return dST
+def _patch_rows_check(P, Q, rows):
+    if P != Q:
+        raise ValueError(f"iBOT patch loss: as many student as teacher views expected, got {P} and {Q}")
+    if Q * rows > IBOT_MAX_ROWS:
+        raise ValueError(f"iBOT patch loss: {Q} x {rows} patch rows in one call, at most {IBOT_MAX_ROWS}")
 
 
-def _loss_args(student, teacher, center):
-    _require_cuda(student, "student logits")
-    S, T = _f32c(student), _f32c(teacher)
-    if S.dim() != 3 or T.dim() != 3 or S.shape[1:] != T.shape[1:]:
-        raise ValueError(f"student (P, B, K) and teacher (Q, B, K) logits expected, got {tuple(S.shape)} and {tuple(T.shape)}")
-    c = _f32c(center).reshape(-1)
-    if c.numel() != S.shape[2]:
-        raise ValueError(f"center has {c.numel()} entries for K = {S.shape[2]}")
-    return S, T, c
+class RowFamily(NamedTuple):
+    """One kernel family of the paired-row cross-entropy: student views (P, rows, K) against teacher views (Q, rows, K), row r of every student
+    view paired with row r of every teacher view.  `c_loss` and `c_grad` take (lib, S, T, center, P, Q, rows, K, inv_ts, inv_tt, ...) and put
+    the arguments into their C function's order, nothing more; `check` raises for a shape the family cannot run.  The caller names the
+    family: it is never chosen from the shape."""
+    name: str           # m3l_op_<name>_loss / _grad in error messages
+    ws_bytes: Callable  # (lib, rows, K) -> bytes of the loss kernel's workspace
+    c_loss: Callable
+    c_grad: Callable
+    check: Callable     # (P, Q, rows)
+    keep: str           # key under which the head + loss node leaves the student logits in `keep`
+
+    def args(self, student, teacher, center):
+        _require_cuda(student, "student logits")
+        S, T = _f32c(student), _f32c(teacher)
+        if S.dim() != 3 or T.dim() != 3 or S.shape[1:] != T.shape[1:]:
+            raise ValueError(f"student (P, rows, K) and teacher (Q, rows, K) logits expected, got {tuple(S.shape)} and {tuple(T.shape)}")
+        self.check(S.shape[0], T.shape[0], S.shape[1])
+        c = _f32c(center).reshape(-1)
+        if c.numel() != S.shape[2]:
+            raise ValueError(f"center has {c.numel()} entries for K = {S.shape[2]}")
+        return S, T, c
+
+    def loss_forward(self, S, T, center, P, Q, rows, K, inv_ts, inv_tt):
+        lib = L.lib()
+        s_stats = _row_stats(S, P * rows, K, None, inv_ts)
+        t_stats = _row_stats(T, Q * rows, K, center, inv_tt)
+        loss = torch.empty((), dtype=torch.float32, device=S.device)
+        ws = _ws(self.ws_bytes(lib, rows, K), S.device)
+        L.check(self.c_loss(lib, L.ptr(S), L.ptr(T), L.ptr(center), P, Q, rows, K, inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats), L.ptr(ws),
+                            L.ptr(loss), _stream()), f"m3l_op_{self.name}_loss")
+        return loss, s_stats, t_stats
+
+    def loss_grad(self, dt, S, T, center, P, Q, rows, K, inv_ts, inv_tt, s_stats, t_stats, dloss):
+        """-> dS^T (K, ldr) in the compute type, ldr = P rows rounded up to a multiple of 8 (pad columns zero)."""
+        ldr = _ld8(P * rows)
+        dST = torch.empty(K, ldr, dtype=tdtype(dt), device=S.device)
+        L.check(self.c_grad(L.lib(), dt, L.ptr(S), L.ptr(T), L.ptr(center), P, Q, rows, K, inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats),
+                            L.ptr(dloss), L.ptr(dST), ldr, _stream()), f"m3l_op_{self.name}_grad")
+        return dST
 
 
-class DinoLossFn(torch.autograd.Function):
-    """loss(student (P, B, K), teacher logits (Q, B, K), center (K)) with an f32 gradient for the student logits: the loss on its own."""
+# m3l_op_dino_*: the teacher sums of a sample stay in LDS, any P and Q, rows <= 255 (checked in C)
+DINO_ROWS = RowFamily("dino", lambda lib, rows, K: lib.m3l_op_dino_ws_bytes(rows, K),
+                      lambda lib, S, T, c, P, Q, rows, K, *tail: lib.m3l_op_dino_loss(S, P, T, Q, rows, K, c, *tail),
+                      lambda lib, dt, S, T, c, P, Q, rows, K, *tail: lib.m3l_op_dino_grad(dt, S, P, T, Q, rows, K, c, *tail),
+                      lambda P, Q, rows: None, "student_logits")
+# m3l_op_ibot_*: tiles over the rows, P = Q, Q rows <= IBOT_MAX_ROWS
+PATCH_ROWS = RowFamily("ibot", lambda lib, rows, K: lib.m3l_op_ibot_ws_bytes(rows, K),
+                       lambda lib, S, T, c, P, Q, rows, K, *tail: lib.m3l_op_ibot_loss(S, T, Q, rows, K, c, *tail),
+                       lambda lib, dt, S, T, c, P, Q, rows, K, *tail: lib.m3l_op_ibot_grad(dt, S, T, Q, rows, K, c, *tail),
+                       _patch_rows_check, "student_patch_logits")
+
+# one family's helpers under the names and argument lists they had while each family had helpers of its own; the kernel tests call these
+_loss_forward, _loss_grad = DINO_ROWS.loss_forward, DINO_ROWS.loss_grad
+
+
+def _ibot_grad(dt, S, T, center, Q, *rest):
+    return PATCH_ROWS.loss_grad(dt, S, T, center, Q, Q, *rest)
+
+
+class RowLossFn(torch.autograd.Function):
+    """loss(student (P, rows, K), teacher logits (Q, rows, K), center (K)) with an f32 gradient for the student logits: the loss on its own.
+    A subclass sets `family`, nothing else."""
+    family = None
 
     @staticmethod
     def forward(ctx, student, teacher, center, student_temp, teacher_temp):
-        S, T, c = _loss_args(student, teacher, center)
-        (P, B, K), Q = S.shape, T.shape[0]
+        family = ctx._forward_cls.family
+        S, T, c = family.args(student, teacher, center)
+        (P, rows, K), Q = S.shape, T.shape[0]
         inv_ts, inv_tt = 1.0 / float(student_temp), 1.0 / float(teacher_temp)
-        loss, s_stats, t_stats = _loss_forward(S, T, c, P, Q, B, K, inv_ts, inv_tt)
-        ctx.saved = (S, T, c.clone(), P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats)
+        loss, s_stats, t_stats = family.loss_forward(S, T, c, P, Q, rows, K, inv_ts, inv_tt)
+        ctx.saved = (S, T, c.clone(), P, Q, rows, K, inv_ts, inv_tt, s_stats, t_stats)
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        S, T, c, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
-        dST = _loss_grad(DT_F32, S, T, c, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
-        return dST.t()[:P * B].reshape(P, B, K), None, None, None, None
+        S, T, c, P, Q, rows, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
+        dST = ctx._forward_cls.family.loss_grad(DT_F32, S, T, c, P, Q, rows, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
+        return dST.t()[:P * rows].reshape(P, rows, K), None, None, None, None
 
 
-class HeadLossFn(torch.autograd.Function):
-    """Prototype layer + loss in one node: x_n (P B, D) f32, v, g, teacher logits (Q, B, K), center -> loss.  The gradient kernel writes
-    dS^T in the compute type, which is what the two backward GEMMs of the prototype layer read; no f32 (P B, K) gradient exists."""
+class RowHeadLossFn(torch.autograd.Function):
+    """Prototype layer + loss in one node: x_n (P rows, D) f32, v, g, teacher logits (Q, rows, K), center -> loss.  The gradient kernel writes
+    dS^T in the compute type, which is what the two backward GEMMs of the prototype layer read; no f32 (P rows, K) gradient exists.
+    A subclass sets `family`, nothing else."""
+    family = None
 
     @staticmethod
     def forward(ctx, dt, P, xn, v, g, teacher, center, student_temp, teacher_temp, keep):
+        family = ctx._forward_cls.family
         _require_cuda(xn, "DINO head input")
         xn, v, g = _f32c(xn), _f32c(v), _f32c(g)
         M, D = xn.shape
-        K, B = v.shape[0], M // P
+        K, rows = v.shape[0], M // P
         w, vnorm = _weightnorm(dt, v, g)
-        S = torch.empty(P, B, K, dtype=torch.float32, device=xn.device)
+        S = torch.empty(P, rows, K, dtype=torch.float32, device=xn.device)
         _gemm_nt(dt, _cast(xn, dt), w, M, K, D, out_f32=S)
-        S, T, c = _loss_args(S, teacher, center)
+        S, T, c = family.args(S, teacher, center)
         Q = T.shape[0]
         inv_ts, inv_tt = 1.0 / float(student_temp), 1.0 / float(teacher_temp)
-        loss, s_stats, t_stats = _loss_forward(S, T, c, P, Q, B, K, inv_ts, inv_tt)
-        ctx.saved = (dt, xn, w, v, g, vnorm, S, T, c.clone(), P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats)
+        loss, s_stats, t_stats = family.loss_forward(S, T, c, P, Q, rows, K, inv_ts, inv_tt)
+        ctx.saved = (dt, xn, w, v, g, vnorm, S, T, c.clone(), P, Q, rows, K, inv_ts, inv_tt, s_stats, t_stats)
         if keep is not None:
-            keep["student_logits"] = S
+            keep[family.keep] = S
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        dt, xn, w, v, g, vnorm, S, T, c, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
-        dST = _loss_grad(dt, S, T, c, P, Q, B, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
+        dt, xn, w, v, g, vnorm, S, T, c, P, Q, rows, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
+        dST = ctx._forward_cls.family.loss_grad(dt, S, T, c, P, Q, rows, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
         dx, dv, dg = _last_layer_backward(dt, dST, xn, w, v, g, vnorm, ctx.needs_input_grad[2])
         return None, None, dx, dv, dg, None, None, None, None, None
+
+
+class DinoLossFn(RowLossFn):
+    family = DINO_ROWS
+
+
+class IbotLossFn(RowLossFn):
+    family = PATCH_ROWS
+
+
+class HeadLossFn(RowHeadLossFn):
+    family = DINO_ROWS
+
+
+class IbotHeadLossFn(RowHeadLossFn):
+    family = PATCH_ROWS
 
 
 class WeightNormLinear(nn.Module):
@@ -412,31 +481,30 @@ def _sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations, process_g
     return center
 
 
-class DINOLoss(nn.Module):
-    """The loss with its centre.  `forward(student (P, B, K), teacher logits (Q, B, K), teacher_temp)` applies the pending centre update,
-    computes the loss against the centred teacher and leaves this step's teacher column sums pending (one-step delay, as the reference's
-    softmax_center_teacher / update_center pair).  With torch.distributed initialised the pending sums are all-reduced over
-    `process_group` and divided by rows x world size; on one rank they are the local sums.  `forward(..., centering="sinkhorn_knopp")`
-    takes the Sinkhorn-Knopp targets instead and leaves the centre alone; `softmax_center_teacher` / `sinkhorn_knopp_teacher` return the two
-    target distributions themselves, as the reference's methods of those names do."""
+class CenteredLoss(nn.Module):
+    """What DINOLoss and iBOTPatchLoss share: the centre with its one-step delay, the two target distributions and `forward`.
 
-    def __init__(self, out_dim, student_temp=0.1, center_momentum=0.9, process_group=None):
+    `forward(student (P, rows, K), teacher logits (Q, rows, K), teacher_temp)` applies the pending centre update, computes the loss against the
+    centred teacher through `loss_fn` and leaves this step's teacher column sums pending (as the reference's softmax_center_teacher /
+    update_center pair).  With torch.distributed initialised the pending sums are all-reduced asynchronously over `process_group` and divided by
+    count x world size; on one rank they are the local sums.  `forward(..., centering="sinkhorn_knopp")` takes the Sinkhorn-Knopp targets
+    instead and leaves the centre alone; `softmax_center_teacher` / `sinkhorn_knopp_teacher` return the two target distributions themselves,
+    as the reference's methods of those names do.
+
+    A subclass sets `loss_fn` (the loss node of its kernel family) and `count_name` (the reference's attribute for the count the pending
+    sums are divided by) and gives `_center_sum(T, rows, K, out)`, which launches its column sums of T into `out` and returns that count."""
+    loss_fn = count_name = None
+
+    def __init__(self, center_shape, student_temp, center_momentum, process_group):
         super().__init__()
         self.student_temp = student_temp
         self.center_momentum = center_momentum
-        self.register_buffer("center", torch.zeros(1, out_dim))
+        self.register_buffer("center", torch.zeros(center_shape))
         self.process_group = process_group
         self.updated = True
         self.reduce_handle = None
-        self.len_teacher_output = None
+        setattr(self, self.count_name, None)
         self.async_batch_center = None
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        # the reference's centre becomes (1, 1, K) at its first update (it broadcasts against the (rows, 1, K) teacher output): same values
-        c = state_dict.get(prefix + "center")
-        if c is not None and c.dim() == 3 and c.shape[0] == 1 and tuple(c.shape[1:]) == tuple(self.center.shape):
-            state_dict[prefix + "center"] = c[0]
-        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     @torch.no_grad()
     def apply_center_update(self):
@@ -445,12 +513,11 @@ class DINOLoss(nn.Module):
             if self.reduce_handle is not None:
                 self.reduce_handle.wait()
                 self.reduce_handle = None
-            K = self.center.shape[1]
+            K = self.center.shape[-1]
             if self.center.dtype != torch.float32 or not self.center.is_contiguous():
-                raise L.M3LError("DINOLoss.center must be a contiguous float32 buffer")
-            m = float(self.center_momentum)
-            L.check(L.lib().m3l_op_dino_center_apply(L.ptr(self.center), L.ptr(self.async_batch_center), K, m, 1 - m,
-                                                     float(self.len_teacher_output * world), _stream()), "m3l_op_dino_center_apply")
+                raise L.M3LError(f"{type(self).__name__}.center must be a contiguous float32 buffer")
+            m, count = float(self.center_momentum), float(getattr(self, self.count_name) * world)
+            L.check(L.lib().m3l_op_dino_center_apply(L.ptr(self.center), L.ptr(self.async_batch_center), K, m, 1 - m, count, _stream()), "m3l_op_dino_center_apply")
             self.updated = True
 
     @torch.no_grad()
@@ -458,11 +525,11 @@ class DINOLoss(nn.Module):
         _require_cuda(teacher_output, "teacher logits")
         T = _f32c(teacher_output)
         K = T.shape[-1]
-        rows = T.numel() // K
+        pending = torch.empty(1, K, dtype=torch.float32, device=T.device)
+        count = self._center_sum(T, T.numel() // K, K, pending)
         self.updated = False
-        self.len_teacher_output = rows
-        self.async_batch_center = torch.empty(1, K, dtype=torch.float32, device=T.device)
-        L.check(L.lib().m3l_op_dino_center_sum(L.ptr(T), rows, K, L.ptr(self.async_batch_center), _stream()), "m3l_op_dino_center_sum")
+        setattr(self, self.count_name, count)
+        self.async_batch_center = pending
         if dist.is_initialized():
             self.reduce_handle = dist.all_reduce(self.async_batch_center, op=dist.ReduceOp.SUM, group=self.process_group, async_op=True)
 
@@ -470,34 +537,53 @@ class DINOLoss(nn.Module):
         """The (K,) float32 vector c with sinkhorn_knopp_teacher(T) = softmax((T - c) / teacher_temp), over `process_group` (_sinkhorn_knopp_center)."""
         return _sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations, self.process_group)
 
-    @torch.no_grad()
-    def sinkhorn_knopp_teacher(self, teacher_output, teacher_temp, n_iterations=3):
-        """The reference's return value: the assignment as probabilities, (rows, K) float32 with the leading dimensions flattened to rows."""
-        center = self.sinkhorn_knopp_center(teacher_output, teacher_temp, n_iterations)
+    def _targets(self, teacher_output, teacher_temp, center):
         T, rows, K = _teacher_rows(teacher_output)
         inv_temp = 1.0 / float(teacher_temp)
         return _probs(T, rows, K, center, inv_temp, _row_stats(T, rows, K, center, inv_temp))
+
+    @torch.no_grad()
+    def sinkhorn_knopp_teacher(self, teacher_output, teacher_temp, n_iterations=3):
+        """The reference's return value: the assignment as probabilities, (rows, K) float32 with the leading dimensions flattened to rows."""
+        return self._targets(teacher_output, teacher_temp, self.sinkhorn_knopp_center(teacher_output, teacher_temp, n_iterations))
 
     @torch.no_grad()
     def softmax_center_teacher(self, teacher_output, teacher_temp):
         """softmax((teacher_output - center) / teacher_temp) after the pending centre update, (rows, K) float32."""
         self.apply_center_update()
-        T, rows, K = _teacher_rows(teacher_output)
-        inv_temp = 1.0 / float(teacher_temp)
-        center = _f32c(self.center).reshape(-1)
-        return _probs(T, rows, K, center, inv_temp, _row_stats(T, rows, K, center, inv_temp))
+        return self._targets(teacher_output, teacher_temp, _f32c(self.center).reshape(-1))
 
     def forward(self, student_logits, teacher_logits, teacher_temp, centering="centering", n_iterations=3):
         if centering == "sinkhorn_knopp":
             # the centre, `updated` and the pending sums stay as they are: this branch of the reference never calls update_center
             center = self.sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations)
-            return DinoLossFn.apply(student_logits, teacher_logits, center, self.student_temp, teacher_temp)
+            return self.loss_fn.apply(student_logits, teacher_logits, center, self.student_temp, teacher_temp)
         if centering != "centering":
-            raise ValueError(f"DINOLoss.forward: centering must be 'centering' or 'sinkhorn_knopp', got {centering!r}")
+            raise ValueError(f"{type(self).__name__}.forward: centering must be 'centering' or 'sinkhorn_knopp', got {centering!r}")
         self.apply_center_update()
-        loss = DinoLossFn.apply(student_logits, teacher_logits, self.center, self.student_temp, teacher_temp)
+        loss = self.loss_fn.apply(student_logits, teacher_logits, self.center, self.student_temp, teacher_temp)
         self.update_center(teacher_logits)
         return loss
+
+
+class DINOLoss(CenteredLoss):
+    """The DINO loss with its centre, buffer `center` (1, K): CenteredLoss over student (P, B, K) and teacher (Q, B, K) logits on the kernels
+    that keep a sample's teacher sums in LDS (m3l_op_dino_*).  The pending sums are the plain column sums, `len_teacher_output` their rows."""
+    loss_fn, count_name = DinoLossFn, "len_teacher_output"
+
+    def __init__(self, out_dim, student_temp=0.1, center_momentum=0.9, process_group=None):
+        super().__init__((1, out_dim), student_temp, center_momentum, process_group)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # the reference's centre becomes (1, 1, K) at its first update (it broadcasts against the (rows, 1, K) teacher output): same values
+        c = state_dict.get(prefix + "center")
+        if c is not None and c.dim() == 3 and c.shape[0] == 1 and tuple(c.shape[1:]) == tuple(self.center.shape):
+            state_dict[prefix + "center"] = c[0]
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def _center_sum(self, T, rows, K, out):
+        L.check(L.lib().m3l_op_dino_center_sum(L.ptr(T), rows, K, L.ptr(out), _stream()), "m3l_op_dino_center_sum")
+        return rows
 
 
 class KoLeoFn(torch.autograd.Function):
@@ -559,102 +645,17 @@ class KoLeoLoss(nn.Module):
         return loss
 
 
-# ---- iBOT patch loss (tactile_ssl/loss/ibot_patch_loss.py) ---------------------------------------------------------------------------------
-IBOT_MAX_ROWS = 65535          # Q R of one call (include/m3l_amd.h, "iBOT patch loss")
-
-
-def _ibot_args(student, teacher, center):
-    _require_cuda(student, "student patch logits")
-    S, T = _f32c(student), _f32c(teacher)
-    if S.dim() != 3 or T.dim() != 3 or S.shape != T.shape:
-        raise ValueError(f"student and teacher patch logits of one shape (Q, R, K) expected, got {tuple(S.shape)} and {tuple(T.shape)}")
-    if S.shape[0] * S.shape[1] > IBOT_MAX_ROWS:
-        raise ValueError(f"iBOT patch loss: {S.shape[0]} x {S.shape[1]} patch rows in one call, at most {IBOT_MAX_ROWS}")
-    c = _f32c(center).reshape(-1)
-    if c.numel() != S.shape[2]:
-        raise ValueError(f"center has {c.numel()} entries for K = {S.shape[2]}")
-    return S, T, c
-
-
-def _ibot_forward(S, T, center, Q, R, K, inv_ts, inv_tt):
-    lib = L.lib()
-    s_stats = _row_stats(S, Q * R, K, None, inv_ts)
-    t_stats = _row_stats(T, Q * R, K, center, inv_tt)
-    loss = torch.empty((), dtype=torch.float32, device=S.device)
-    ws = _ws(lib.m3l_op_ibot_ws_bytes(R, K), S.device)
-    L.check(lib.m3l_op_ibot_loss(L.ptr(S), L.ptr(T), Q, R, K, L.ptr(center), inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats), L.ptr(ws), L.ptr(loss),
-                                 _stream()), "m3l_op_ibot_loss")
-    return loss, s_stats, t_stats
-
-
-def _ibot_grad(dt, S, T, center, Q, R, K, inv_ts, inv_tt, s_stats, t_stats, dloss):
-    """-> dS^T (K, ldr) in the compute type, ldr = Q R rounded up to a multiple of 8 (pad columns zero)."""
-    ldr = _ld8(Q * R)
-    dST = torch.empty(K, ldr, dtype=tdtype(dt), device=S.device)
-    L.check(L.lib().m3l_op_ibot_grad(dt, L.ptr(S), L.ptr(T), Q, R, K, L.ptr(center), inv_ts, inv_tt, L.ptr(s_stats), L.ptr(t_stats), L.ptr(dloss),
-                                     L.ptr(dST), ldr, _stream()), "m3l_op_ibot_grad")
-    return dST
-
-
-class IbotLossFn(torch.autograd.Function):
-    """loss(student (Q, R, K), teacher logits (Q, R, K), center (K)) with an f32 gradient for the student logits: the patch loss on its own."""
-
-    @staticmethod
-    def forward(ctx, student, teacher, center, student_temp, teacher_temp):
-        S, T, c = _ibot_args(student, teacher, center)
-        Q, R, K = S.shape
-        inv_ts, inv_tt = 1.0 / float(student_temp), 1.0 / float(teacher_temp)
-        loss, s_stats, t_stats = _ibot_forward(S, T, c, Q, R, K, inv_ts, inv_tt)
-        ctx.saved = (S, T, c.clone(), Q, R, K, inv_ts, inv_tt, s_stats, t_stats)
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        S, T, c, Q, R, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
-        dST = _ibot_grad(DT_F32, S, T, c, Q, R, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
-        return dST.t()[:Q * R].reshape(Q, R, K), None, None, None, None
-
-
-class IbotHeadLossFn(torch.autograd.Function):
-    """Prototype layer + patch loss in one node: x_n (Q R, D) f32, v, g, teacher logits (Q, R, K), center -> loss.  As HeadLossFn: the gradient
-    kernel writes dS^T in the compute type for the two backward GEMMs of the prototype layer; no f32 (Q R, K) gradient exists."""
-
-    @staticmethod
-    def forward(ctx, dt, Q, xn, v, g, teacher, center, student_temp, teacher_temp, keep):
-        _require_cuda(xn, "iBOT head input")
-        xn, v, g = _f32c(xn), _f32c(v), _f32c(g)
-        M, D = xn.shape
-        K, R = v.shape[0], M // Q
-        w, vnorm = _weightnorm(dt, v, g)
-        S = torch.empty(Q, R, K, dtype=torch.float32, device=xn.device)
-        _gemm_nt(dt, _cast(xn, dt), w, M, K, D, out_f32=S)
-        S, T, c = _ibot_args(S, teacher, center)
-        inv_ts, inv_tt = 1.0 / float(student_temp), 1.0 / float(teacher_temp)
-        loss, s_stats, t_stats = _ibot_forward(S, T, c, Q, R, K, inv_ts, inv_tt)
-        ctx.saved = (dt, xn, w, v, g, vnorm, S, T, c.clone(), Q, R, K, inv_ts, inv_tt, s_stats, t_stats)
-        if keep is not None:
-            keep["student_patch_logits"] = S
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        dt, xn, w, v, g, vnorm, S, T, c, Q, R, K, inv_ts, inv_tt, s_stats, t_stats = ctx.saved
-        dST = _ibot_grad(dt, S, T, c, Q, R, K, inv_ts, inv_tt, s_stats, t_stats, _f32c(dloss))
-        dx, dv, dg = _last_layer_backward(dt, dST, xn, w, v, g, vnorm, ctx.needs_input_grad[2])
-        return None, None, dx, dv, dg, None, None, None, None, None
-
-
 def _stack_views(x):
     return torch.stack(list(x)) if isinstance(x, (list, tuple)) else x
 
 
-class iBOTPatchLoss(nn.Module):
+class iBOTPatchLoss(CenteredLoss):
     """The reference's iBOTPatchLoss (`tactile_ssl/loss/ibot_patch_loss.py`) on the row-tiled kernels (m3l_op_ibot_*): buffer `center` (1, 1, K).
 
     `forward(student_logits, teacher_logits, teacher_temp)` takes the LOGITS of Q student and Q teacher views, (Q, R, K) tensors or lists of Q
     (R, K) tensors with R = B n patch rows (row r of every student view is paired with row r of every teacher view), and returns the
     reference's unscaled `forward`: sum over all (student view, teacher view) pairs of the mean over rows of the cross-entropy.  The centre
-    follows this package's DINOLoss: the pending update is applied first, this step's sums are left pending (one-step delay) and are
+    is CenteredLoss's, as DINOLoss's: the pending update is applied first, this step's sums are left pending (one-step delay) and are
     all-reduced asynchronously over `process_group`.  `update_center` takes the reference's (Q B, n, K) teacher tokens: pending = sum_b mean_k,
     count = Q B x world; handed (Q, R, K), as `forward` is, it takes the Q views as the samples (pending = sum over rows / R, count = Q), which
     is the same centre.  `centering="sinkhorn_knopp"` takes the Sinkhorn-Knopp targets over all Q R rows and leaves the centre alone.
@@ -664,84 +665,34 @@ class iBOTPatchLoss(nn.Module):
     argument does not change the result; it is accepted and ignored (tests/golden/ibot_loss.npz pins this with two values).
 
     Not built: `forward_masked` (nothing in the reference calls it)."""
+    loss_fn, count_name = IbotLossFn, "len_teacher_patch_tokens"
 
     def __init__(self, patch_out_dim, student_temp=0.1, center_momentum=0.9, process_group=None):
-        super().__init__()
-        self.student_temp = student_temp
-        self.center_momentum = center_momentum
-        self.register_buffer("center", torch.zeros(1, 1, patch_out_dim))
-        self.process_group = process_group
-        self.updated = True
-        self.reduce_handle = None
-        self.len_teacher_patch_tokens = None
-        self.async_batch_center = None
+        super().__init__((1, 1, patch_out_dim), student_temp, center_momentum, process_group)
 
-    @torch.no_grad()
-    def apply_center_update(self):
-        if self.updated is False:
-            world = dist.get_world_size(self.process_group) if dist.is_initialized() else 1
-            if self.reduce_handle is not None:
-                self.reduce_handle.wait()
-                self.reduce_handle = None
-            K = self.center.shape[-1]
-            if self.center.dtype != torch.float32 or not self.center.is_contiguous():
-                raise L.M3LError("iBOTPatchLoss.center must be a contiguous float32 buffer")
-            m = float(self.center_momentum)
-            L.check(L.lib().m3l_op_dino_center_apply(L.ptr(self.center), L.ptr(self.async_batch_center), K, m, 1 - m,
-                                                     float(self.len_teacher_patch_tokens * world), _stream()), "m3l_op_dino_center_apply")
-            self.updated = True
-
-    @torch.no_grad()
-    def update_center(self, teacher_patch_tokens):
-        _require_cuda(teacher_patch_tokens, "teacher patch logits")
-        T = _f32c(teacher_patch_tokens)
+    def _center_sum(self, T, rows, K, out):
         if T.dim() < 3:
             raise ValueError(f"iBOTPatchLoss.update_center: (samples, patches, K) teacher logits expected, got {tuple(T.shape)}")
         lib = L.lib()
-        K, samples = T.shape[-1], T.shape[0]
-        rows = T.numel() // K
-        self.updated = False
-        self.len_teacher_patch_tokens = samples
-        self.async_batch_center = torch.empty(1, K, dtype=torch.float32, device=T.device)
+        samples = T.shape[0]
         ws = _ws(lib.m3l_op_ibot_ws_bytes(rows, K), T.device)
-        L.check(lib.m3l_op_ibot_center_sum(L.ptr(T), rows, K, float(samples) / float(rows), L.ptr(ws), L.ptr(self.async_batch_center), _stream()),
-                "m3l_op_ibot_center_sum")
-        if dist.is_initialized():
-            self.reduce_handle = dist.all_reduce(self.async_batch_center, op=dist.ReduceOp.SUM, group=self.process_group, async_op=True)
+        L.check(lib.m3l_op_ibot_center_sum(L.ptr(T), rows, K, float(samples) / float(rows), L.ptr(ws), L.ptr(out), _stream()), "m3l_op_ibot_center_sum")
+        return samples
 
-    reduce_center_update = update_center
-    def sinkhorn_knopp_center(self, teacher_logits, teacher_temp, n_iterations=3):
-        """The (K,) float32 vector c with sinkhorn_knopp_teacher(T) = softmax((T - c) / teacher_temp), over `process_group` (_sinkhorn_knopp_center)."""
-        return _sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations, self.process_group)
+    reduce_center_update = CenteredLoss.update_center
 
     @torch.no_grad()
     def sinkhorn_knopp_teacher(self, teacher_output, teacher_temp, n_masked_patches_tensor=None, n_iterations=3):
         """(rows, K) float32 probabilities.  `n_masked_patches_tensor` cancels (class docstring) and is ignored."""
-        center = self.sinkhorn_knopp_center(teacher_output, teacher_temp, n_iterations)
-        T, rows, K = _teacher_rows(teacher_output)
-        inv_temp = 1.0 / float(teacher_temp)
-        return _probs(T, rows, K, center, inv_temp, _row_stats(T, rows, K, center, inv_temp))
+        return super().sinkhorn_knopp_teacher(teacher_output, teacher_temp, n_iterations)
 
     @torch.no_grad()
     def softmax_center_teacher(self, teacher_patch_tokens, teacher_temp):
         """softmax((teacher_patch_tokens - center) / teacher_temp) after the pending centre update, float32 in the shape of the input."""
-        self.apply_center_update()
-        T, rows, K = _teacher_rows(teacher_patch_tokens)
-        inv_temp = 1.0 / float(teacher_temp)
-        center = _f32c(self.center).reshape(-1)
-        return _probs(T, rows, K, center, inv_temp, _row_stats(T, rows, K, center, inv_temp)).view(teacher_patch_tokens.shape)
+        return super().softmax_center_teacher(teacher_patch_tokens, teacher_temp).view(teacher_patch_tokens.shape)
 
     def forward(self, student_logits, teacher_logits, teacher_temp, centering="centering", n_iterations=3):
-        student_logits, teacher_logits = _stack_views(student_logits), _stack_views(teacher_logits)
-        if centering == "sinkhorn_knopp":
-            center = self.sinkhorn_knopp_center(teacher_logits, teacher_temp, n_iterations)
-            return IbotLossFn.apply(student_logits, teacher_logits, center, self.student_temp, teacher_temp)
-        if centering != "centering":
-            raise ValueError(f"iBOTPatchLoss.forward: centering must be 'centering' or 'sinkhorn_knopp', got {centering!r}")
-        self.apply_center_update()
-        loss = IbotLossFn.apply(student_logits, teacher_logits, self.center, self.student_temp, teacher_temp)
-        self.update_center(teacher_logits)
-        return loss
+        return super().forward(_stack_views(student_logits), _stack_views(teacher_logits), teacher_temp, centering, n_iterations)
 
 
 @torch.no_grad()

@@ -19,8 +19,9 @@ views are never compared, the views' losses summed, all in one set of launches (
 `ibot_patch_loss(student patch logits, teacher patch targets) / num_global_masks`: the patch tokens of the student's global pass (the same
 forward_features call that yields the register rows) go through `dino_head`'s MLP — or `ibot_head`'s with `ibot_separate_head=True`, a
 fresh head in each of the student and teacher dicts — the teacher's global patch tokens through the teacher's, and the prototype layer, the
-cross-entropy over the Q x (B n) patch rows and their backward are one autograd node (IbotHeadLossFn, the row-tiled kernels m3l_op_ibot_*).
-The targets are centred (iBOTPatchLoss.center, one-step delay) or Sinkhorn-Knopp over all patch rows, as `centering` says.  With the
+cross-entropy over the Q x (B n) patch rows and their backward are one autograd node, reached through the same `_head_loss` as the DINO
+term's: IbotHeadLossFn, which is HeadLossFn on the row-tiled kernels (m3l_op_ibot_*).  The targets are centred (iBOTPatchLoss.center,
+one-step delay) or Sinkhorn-Knopp over all patch rows, as `centering` says.  With the
 defaults neither `ibot_patch_loss` nor `ibot_head` exists and the module, its state dict and its step are the ones without the keywords.
 
 Not built: online probes and their logging (a non-empty `online_probes` is refused).
@@ -225,26 +226,19 @@ class VTDINO(nn.Module):
         P, Q = len(global_masks) + len(local_masks), len(global_masks)
         global_rows, global_patches = self._rows_and_patches(student["backbone"], x, global_masks)
         rows = torch.cat([global_rows, self._register_rows(student["backbone"], x, local_masks)], dim=0)
-        head = student["dino_head"]
-        xn = head.normalized(rows)
+        xn = student["dino_head"].normalized(rows)
         B = xn.shape[0] // P
         with torch.no_grad():
             t_rows, t_patches = self._rows_and_patches(teacher["backbone"], x, global_masks)
-            t_logits = teacher["dino_head"](t_rows).view(Q, B, -1)
-            if self.centering == "sinkhorn_knopp":      # the targets' K-vector stands where the centre stands; the centre itself is never updated
-                center = self.dino_loss.sinkhorn_knopp_center(t_logits.view(Q * B, -1), self.current_teacher_temp)
-            else:
-                self.dino_loss.apply_center_update()
-                center = self.dino_loss.center
-        loss = HeadLossFn.apply(Fn.dtype_code(self.compute_dtype), P, xn, head.last_layer.weight_v, head.last_layer.weight_g, t_logits,
-                                center, self.dino_loss.student_temp, self.current_teacher_temp, self.last)
-        self.last["teacher_logits"] = t_logits
-        if self.centering != "sinkhorn_knopp":
-            self.dino_loss.update_center(t_logits)
+        loss = self._head_loss("dino_head", self.dino_loss, HeadLossFn, P, xn, t_rows, (Q, B), (Q, B), "teacher_logits")
         self.loss_terms = self.loss_parts = None
         terms = {"dino_loss": loss.detach()}
         if self.ibot:
-            patch = self._patch_loss(global_patches, t_patches, Q) / self.num_global_masks
+            # patches ((q b), n, c) of the student's global views: R = B n rows of a view, r = b n + k; the centre's sums take ((q b), n, K)
+            name = "ibot_head" if self.ibot_separate_head else "dino_head"
+            QB, n, _ = global_patches.shape
+            patch = self._head_loss(name, self.ibot_patch_loss, IbotHeadLossFn, Q, student[name].normalized(global_patches), t_patches,
+                                    (Q, QB // Q * n), (QB, n), "teacher_patch_logits") / self.num_global_masks
             terms["ibot_loss"] = patch.detach()
             loss = loss + patch
         if self.koleo_weight > 0:
@@ -259,26 +253,24 @@ class VTDINO(nn.Module):
             self.loss_parts = terms
         return loss
 
-    def _patch_loss(self, patches, t_patches, Q):
-        """Unscaled iBOT term: patches ((q b), n, c) of the student's global views, t_patches the teacher's (no gradient)."""
-        student, teacher = self.student_encoder_dict, self.teacher_encoder_dict
-        name = "ibot_head" if self.ibot_separate_head else "dino_head"
-        head, pl = student[name], self.ibot_patch_loss
-        QB, n, _ = patches.shape
-        R = QB // Q * n                                     # rows of a view: r = b n + k
-        xn = head.normalized(patches)
+    def _head_loss(self, name, loss_mod, node, views, xn, t_in, paired, samples, last_key):
+        """One cross-entropy term, unscaled: x_n (views x rows, D) of the student's head `name` against the teacher's head `name` on t_in (no
+        gradient), in the head + loss node `node` of the term's kernel family.  `paired` = (Q, rows) is the shape in which the teacher
+        logits meet the student's and are kept in self.last[last_key], `samples` the leading shape in which `loss_mod` takes them for its centre."""
+        last_layer = self.student_encoder_dict[name].last_layer
         with torch.no_grad():
-            t_logits = teacher[name](t_patches)                 # ((q b), n, K)
-            if self.centering == "sinkhorn_knopp":      # over all Q R rows; the centre is never updated
-                center = pl.sinkhorn_knopp_center(t_logits.view(Q * R, -1), self.current_teacher_temp)
+            t_logits = self.teacher_encoder_dict[name](t_in)
+            if self.centering == "sinkhorn_knopp":      # over all rows; the targets' K-vector stands where the centre stands, the centre is never updated
+                center = loss_mod.sinkhorn_knopp_center(t_logits, self.current_teacher_temp)
             else:
-                pl.apply_center_update()
-                center = pl.center
-        loss = IbotHeadLossFn.apply(Fn.dtype_code(self.compute_dtype), Q, xn, head.last_layer.weight_v, head.last_layer.weight_g,
-                                    t_logits.view(Q, R, -1), center, pl.student_temp, self.current_teacher_temp, self.last)
-        self.last["teacher_patch_logits"] = t_logits.view(Q, R, -1)
+                loss_mod.apply_center_update()
+                center = loss_mod.center
+        t_paired = t_logits.view(*paired, -1)
+        loss = node.apply(Fn.dtype_code(self.compute_dtype), views, xn, last_layer.weight_v, last_layer.weight_g, t_paired, center,
+                                loss_mod.student_temp, self.current_teacher_temp, self.last)
+        self.last[last_key] = t_paired
         if self.centering != "sinkhorn_knopp":
-            pl.update_center(t_logits)
+            loss_mod.update_center(t_logits.view(*samples, -1))
         return loss
 
     def training_step(self, batch, batch_idx):
