@@ -103,6 +103,10 @@ int m3l_set_rowln(int enable);
  * the attention backward block; env M3L_ATTN_BLOCK sets the initial mode.  Returns the
  * previous mode.  The fused kernels read and write exactly the activations of the unfused ones. */
 int m3l_set_attn_block(int mode);
+/* The attention backward block (mode bit 2 above): 1 (default) = all heads of a sample in one pass — every phase (dO, Dsum, attention
+ * backward, dxn1) runs once for all heads, the attention backward as (head, tile) tasks over the waves; 0 = one head after the other.
+ * env M3L_ATTN_BWD_HEADS sets the initial mode.  Returns the previous mode.  Bit-identical results either way. */
+int m3l_set_attn_bwd_heads(int mode);
 /* Short-sequence stacks whose every half layer takes a block kernel, a bit mask: 1 (default) = the whole forward of the stack in ONE launch
  * (the same kernel bodies, layer after layer inside one workgroup per sample); 2 = also its backward as one launch per weight-gradient
  * group of layers (opt-in: measured slower beside the side stream's weight gradients); 0 = one launch per half layer; env M3L_ENC_MEGA.

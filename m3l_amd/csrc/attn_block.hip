@@ -401,6 +401,123 @@ template <int KT> struct AbBwdLayout {
     static_assert(AB_CW * 3 * D * 4 <= A_BYTES + NT * T_BYTES, "LayerNorm partials reuse the tile region");
 };
 
+#ifndef ABB_STAMP
+#define ABB_STAMP 0         // diagnostic builds only: shader-clock stamps at the phase boundaries of both backward bodies (tools/abb_phase_probe.py)
+#endif
+#if ABB_STAMP
+__device__ unsigned long long* d_abb_stamps;        // [blocks][12 compute waves][8] accumulated cycles per phase
+#define ABB_T0() unsigned long long abb_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, abb_last = __builtin_readcyclecounter();
+#define ABB_T(i)                                                       \
+    {                                                                  \
+        const unsigned long long t_ = __builtin_readcyclecounter();    \
+        abb_acc[i] += t_ - abb_last;                                   \
+        abb_last = t_;                                                 \
+    }
+#define ABB_TEND()                                                                              \
+    if (d_abb_stamps && lane == 0) {                                                            \
+        unsigned long long* o_ = d_abb_stamps + ((long)blockIdx.x * AB_CW + wave) * 8;          \
+        for (int i_ = 0; i_ < 8; ++i_) o_[i_] = abb_acc[i_];                                    \
+    }
+#else
+#define ABB_T0()
+#define ABB_T(i)
+#define ABB_TEND()
+#endif
+// phases: 0 operands requested / in -> B0, 1 dO -> X1, 2 Dsum -> X2, 3 attention backward -> X3, 4 dq | dk | dv in place / next head's tiles + dqkv out,
+// 5 dxn1 blocks, 6 tail (per-head body: summed over the heads)
+
+// The end of the attention backward, shared by its two bodies: dxn1 (the projection waves' accumulators) -> fp32 staging in the weight ring,
+// then the LayerNorm-1 backward with the residual gradient and the per-sample [3 D] partial rows.  Barriers BE1, BE2, BE3.
+template <int KT, typename R>
+__device__ __forceinline__ void abb_tail(char* smem, char* WR, const f32x4 (&yacc)[3], const f32x4 (&xr_t)[KT], const f32x4 (&dr_t)[KT],
+                                         const f32x4 (&gm_t)[KT], int tid, int n, float eps, R* __restrict__ dx_out, bf16* __restrict__ dxt_out,
+                                         float* __restrict__ ln_part) {
+    constexpr int D = 64 * KT;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, li = lane & 15, ct = wave & 3, rt = wave >> 2;
+    const int b = blockIdx.x;
+    const long row0 = (long)b * n;
+    const int RT = (n + 15) >> 4;
+    __builtin_amdgcn_s_barrier();                                         // BE1: ring free
+    float* Y = reinterpret_cast<float*>(WR);
+    constexpr int YLD = (D * 4 + 16) / 4;
+    if (rt < RT) {
+#pragma unroll
+        for (int j = 0; j < KT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Y[(16 * rt + 4 * g + r) * YLD + 16 * (ct + 4 * j) + li] = yacc[j][r];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                         // BE2: dxn1 complete
+    // ---- LN1 backward, row = 4 wave + g on 16 lanes
+    float* LP = reinterpret_cast<float*>(smem);
+    {
+        const int r = 4 * wave + g;
+        const bool ok = r < n;
+        f32x4 xh[KT], dy[KT], gd[KT];
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < KT; ++c) {
+            xh[c] = xr_t[c];
+            s += (xh[c][0] + xh[c][1]) + (xh[c][2] + xh[c][3]);
+        }
+        const float mean = row16_sum(s) / D;
+        float q = 0.f;
+#pragma unroll
+        for (int c = 0; c < KT; ++c) {
+            xh[c] = xh[c] - mean;
+            q += (xh[c][0] * xh[c][0] + xh[c][1] * xh[c][1]) + (xh[c][2] * xh[c][2] + xh[c][3] * xh[c][3]);
+        }
+        const float rstd = rsqrtf(row16_sum(q) / D + eps);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < KT; ++c) {
+            xh[c] = xh[c] * rstd;
+            dy[c] = ok ? *reinterpret_cast<const f32x4*>(Y + r * YLD + 4 * (li + 16 * c)) : f32x4{0.f, 0.f, 0.f, 0.f};
+            gd[c] = dy[c] * gm_t[c];
+            s1 += (gd[c][0] + gd[c][1]) + (gd[c][2] + gd[c][3]);
+            const f32x4 t = gd[c] * xh[c];
+            s2 += (t[0] + t[1]) + (t[2] + t[3]);
+        }
+        s1 = row16_sum(s1) / D;
+        s2 = row16_sum(s2) / D;
+#pragma unroll
+        for (int c = 0; c < KT; ++c) {
+            const int col = 4 * (li + 16 * c);
+            f32x4 rr = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (ok) {
+                rr = (gd[c] - s1 - xh[c] * s2) * rstd + dr_t[c];
+                if (sizeof(R) == 4) st_res4<R>(dx_out + (row0 + r) * D + col, rr);
+                if (dxt_out) {
+                    bf16x4 pk;
+                    pk[0] = (bf16)rr[0]; pk[1] = (bf16)rr[1]; pk[2] = (bf16)rr[2]; pk[3] = (bf16)rr[3];
+                    *reinterpret_cast<bf16x4*>(dxt_out + (row0 + r) * D + col) = pk;
+                }
+            }
+            f32x4 pg = dy[c] * xh[c], pb = dy[c], pc = rr;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                pg[e] = xor16_sum(pg[e]); pg[e] = xor32_sum(pg[e]);
+                pb[e] = xor16_sum(pb[e]); pb[e] = xor32_sum(pb[e]);
+                pc[e] = xor16_sum(pc[e]); pc[e] = xor32_sum(pc[e]);
+            }
+            if (g == 0) {
+                *reinterpret_cast<f32x4*>(LP + (wave * 3 + 0) * D + col) = pg;
+                *reinterpret_cast<f32x4*>(LP + (wave * 3 + 1) * D + col) = pb;
+                *reinterpret_cast<f32x4*>(LP + (wave * 3 + 2) * D + col) = pc;
+            }
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                         // BE3
+    for (int id = tid; id < 3 * D; id += 64 * AB_CW) {
+        float sacc = 0.f;
+#pragma unroll
+        for (int w = 0; w < AB_CW; ++w) sacc += LP[w * 3 * D + id];
+        ln_part[(long)b * 3 * D + id] = sacc;
+    }
+}
+
 // R = storage type of the residual stream (x, dres, dx_out).  bf16: dres is not read — the incoming residual gradient IS dx1t — and dx_out is
 // not written (only the compute-type result dxt_out, which must then be given)
 template <int KT, typename R>
@@ -486,6 +603,7 @@ __device__ M3L_BODY_INLINE void attn_block_bwd_body(
     }
 
     // ---------------------------------------------------------------------- compute waves
+    ABB_T0()
     // tile loader: 4 tiles (q, k, v, o) x 48 rows x 8 pieces of 16 bytes = 1536 pieces, 2 per thread
     const int pr0 = tid >> 3, pc0 = tid & 7;                              // piece (row, 16-byte column) for tid < 384; tiles 2 * (tid / 384) + {0, 1}
     const int lrow = pr0 % 48, lt0 = (pr0 / 48) * 2;                      // lt0 in {0, 2}: this thread loads tiles lt0 and lt0 + 1
@@ -511,6 +629,7 @@ __device__ M3L_BODY_INLINE void attn_block_bwd_body(
     if (tid < 48) LS[tid] = tid < n ? lse[((long)b * H + 0) * n + tid] : INFINITY;
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                                         // B0
+    ABB_T(0)
 
     const int ct = wave & 3, rt = wave >> 2;
     f32x4 yacc[3];
@@ -554,6 +673,7 @@ __device__ M3L_BODY_INLINE void attn_block_bwd_body(
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                     // X1: dO_h visible
+        ABB_T(1)
         // ---- Dsum[q] = sum_d dO[q, d] o[q, d]: 8 threads per query
         if (tid < 384) {
             const int q = tid >> 3, part = tid & 7;
@@ -569,6 +689,7 @@ __device__ M3L_BODY_INLINE void attn_block_bwd_body(
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                     // X2: Dsum visible
+        ABB_T(2)
         if (wave < RT) {
             // ---- dQ for query tile `wave` (lane li = query): S^T = K Q^T, dP^T = V dO^T, dS^T -> operand, dQ^T += K^T dS^T
             const int q = 16 * wave + li;
@@ -705,6 +826,7 @@ __device__ M3L_BODY_INLINE void attn_block_bwd_body(
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                     // X3: dq / dk / dv of this head visible; q, k, v, o, lse free
+        ABB_T(3)
         // next head's tiles into place; this head's dq | dk | dv out to global (128-byte row segments)
         if (h + 1 < H) {
             *reinterpret_cast<uint4*>(TQ + lt0 * Ly::T_BYTES + lrow * TP + pc0 * 16) = nx0;
@@ -727,6 +849,7 @@ __device__ M3L_BODY_INLINE void attn_block_bwd_body(
                 else dr_t[c] = r < n ? ld_res4<R>(dres + (row0 + r) * D + col) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
+        ABB_T(4)
         // ---- dxn1 += dq_h Wqkv[q_h cols] + dk_h Wqkv[k_h cols] + dv_h Wqkv[v_h cols]: blocks 4h + 1 .. 4h + 3
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
@@ -752,90 +875,471 @@ __device__ M3L_BODY_INLINE void attn_block_bwd_body(
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        ABB_T(5)
     };
     for (int h = 0; h + 1 < H; ++h) head(h, std::false_type{});
     head(H - 1, std::true_type{});
-    __builtin_amdgcn_s_barrier();                                         // BE1: ring free
-    float* Y = reinterpret_cast<float*>(WR);
-    constexpr int YLD = Ly::Y_PITCH / 4;
-    if (rt < RT) {
+    abb_tail<KT, R>(smem, WR, yacc, xr_t, dr_t, gm_t, tid, n, eps, dx_out, dxt_out, ln_part);
+    ABB_T(6)
+    ABB_TEND()
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The same backward with ALL heads of the sample in one pass (m3l_set_attn_bwd_heads(1)).  The body above walks its heads one after the
+// other, each a chain of barrier-separated phases (dO, Dsum, attention, tile reload, three dxn1 blocks) in which the attention phase
+// occupies 2 RT <= 6 of the 12 compute waves.  Here every phase runs once for all H heads: dO of every head, Dsum of every head, the
+// attention backward as a list of (head, query tile) and (head, key tile) tasks over the waves, then the 3 H dxn1 blocks.  Every output
+// element is produced by the same instructions on the same operands in the same order as above (bit-identical:
+// tests/test_attn_bwd_allheads_gpu.py); only where the operands wait changes:
+//   * dx1_t has no LDS image: a projection wave holds its 16 rows x D as KSTEPS A fragments, loaded from global, for the dO products;
+//   * o has no tile: Dsum's 16-byte pieces of o are requested at the start and stay in registers;
+//   * q, k, v and dO tiles of all heads are resident (4 H tiles); dq, dk, dv wait in registers (rounded to bf16) until every wave is
+//     done with q, k, v (X3) and then take the place of q, k, v of their head;
+//   * the ring holds all H Wo^T blocks at once (H <= NSTAGE), then streams the 3 H Wqkv^T blocks (h outer; q, k, v inner).
+// Barriers, the same count for all 13 waves on every path (waves without a task only arrive):
+//   B0       (compute waves: dx1_t, lse, o requested; q | k | v after it)   DMA wave: all Wo^T blocks landed (vmcnt(0))
+//   X1       dO of every head in LDS; the ring is free              DMA wave: then issues Wqkv^T blocks 0, 1, 2
+//   X2       Dsum, lse and the q | k | v tiles of every head in LDS
+//   X3       every attention task finished reading q, k, v, dO      (results still in registers)
+//   X4       dq, dk, dv in place of q, k, v
+//   R_j      j = 0 .. 3 H - 1: Wqkv^T block j landed, block j - 1 consumed   DMA wave: counted vmcnt before, issues block j + 2 after (j >= 1)
+//   BE1-BE3  abb_tail
+template <int KT> struct AbBwdAllLayout {
+    static constexpr int D = 64 * KT, H = KT;
+    static constexpr int T_PITCH = AbBwdLayout<KT>::T_PITCH;
+    static constexpr int Y_PITCH = D * 4 + 16;
+    static constexpr int T_BYTES = 48 * T_PITCH;
+    static constexpr int NT = 4 * H;                      // per head: q (later dq), k (dk), v (dv), dO
+    static constexpr int WBLK = KT * 64 * 128;
+    static constexpr int NSTAGE = 3;
+    static constexpr int STATS = 2 * H * 48 * 4;          // lse, Dsum of every head
+    static constexpr int TOTAL = NT * T_BYTES + STATS + NSTAGE * WBLK;
+    static_assert(48 * Y_PITCH <= NSTAGE * WBLK, "dxn1 staging reuses the ring");
+    static_assert(AB_CW * 3 * D * 4 <= NT * T_BYTES, "LayerNorm partials reuse the tile region");
+    static_assert(H <= NSTAGE, "all Wo^T head blocks are in the ring at once");
+    static_assert(TOTAL <= 160 * 1024, "LDS of one CU");
+};
+
+template <int KT, typename R>
+__device__ M3L_BODY_INLINE void attn_block_bwd_allheads_body(
+    const bf16* __restrict__ dx1t, const R* __restrict__ dres, const R* __restrict__ x, const float* __restrict__ ln1_w,
+    const bf16* __restrict__ qkv, const bf16* __restrict__ o, const float* __restrict__ lse, const bf16* __restrict__ WoT,
+    const bf16* __restrict__ WqkvT, float eps, int n, bf16* __restrict__ dqkv_out, R* __restrict__ dx_out, bf16* __restrict__ dxt_out,
+    float* __restrict__ ln_part) {
+    using Ly = AbBwdAllLayout<KT>;
+    constexpr int D = Ly::D, H = KT, KSTEPS = 2 * KT, NBW = 3 * KT, NDMA = 8 * KT, TP = Ly::T_PITCH, TLD = TP / 2;
+    constexpr int NCT = 64 * AB_CW;                                       // compute threads
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* T0 = smem;                                                      // tile (h, t) at (4 h + t) * T_BYTES; t: 0 q / dq, 1 k / dk, 2 v / dv, 3 dO
+    float* LS = reinterpret_cast<float*>(T0 + Ly::NT * Ly::T_BYTES);      // [H][48]
+    float* DSUM = LS + H * 48;                                            // [H][48]
+    char* WR = reinterpret_cast<char*>(DSUM + H * 48);
+    typedef __attribute__((address_space(3))) void* lds_vp;
+    typedef __attribute__((address_space(1))) const void* gl_vp;
+    typedef __attribute__((address_space(3))) bf16x4* lds_p4;
+
+    const int tid = M3L_BODY_TID(), lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, li = lane & 15;
+    const int b = blockIdx.x;
+    const long row0 = (long)b * n;
+    const int RT = (n + 15) >> 4;
+
+    if (wave == AB_CW) {
+        // ------------------------------------------------------------------ DMA wave: Wo^T rows 64h.. of every head, then per head the
+        // Wqkv^T column blocks of q_h, k_h, v_h (columns 64h, D + 64h, 2D + 64h of the [D][3D] matrix)
+        const int srow = lane >> 3, spc = lane & 7;
+        auto issue_wo = [&](int h) {
+            char* dst = WR + h * Ly::WBLK;
 #pragma unroll
-        for (int j = 0; j < KT; ++j)
+            for (int rg = 0; rg < 8; ++rg) {
+                const bf16* src = WoT + (long)(64 * h + 8 * rg + srow) * D + ((spc ^ srow) << 3);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) Y[(16 * rt + 4 * g + r) * YLD + 16 * (ct + 4 * j) + li] = yacc[j][r];
+                for (int kt = 0; kt < KT; ++kt)
+                    __builtin_amdgcn_global_load_lds((gl_vp)(src + kt * 64), (lds_vp)(dst + kt * 8192 + rg * 1024), 16, 0, 0);
+            }
+        };
+        auto issue_w = [&](int j) {
+            char* dst = WR + (j % Ly::NSTAGE) * Ly::WBLK;
+            const int col0 = (j % 3) * D + 64 * (j / 3);
+#pragma unroll
+            for (int rg = 0; rg < 8; ++rg) {
+#pragma unroll
+                for (int i = 0; i < KT; ++i) {
+                    const bf16* src = WqkvT + (long)(64 * i + 8 * rg + srow) * 3 * D + col0 + ((spc ^ srow) << 3);
+                    __builtin_amdgcn_global_load_lds((gl_vp)src, (lds_vp)(dst + i * 8192 + rg * 1024), 16, 0, 0);
+                }
+            }
+        };
+#pragma unroll
+        for (int h = 0; h < H; ++h) issue_wo(h);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                                     // B0
+        __builtin_amdgcn_s_barrier();                                     // X1: the ring is free
+        issue_w(0);
+        issue_w(1);
+        issue_w(2);
+        __builtin_amdgcn_s_barrier();                                     // X2
+        __builtin_amdgcn_s_barrier();                                     // X3
+        __builtin_amdgcn_s_barrier();                                     // X4
+        for (int j = 0; j < NBW; ++j) {
+            if (j + 1 < NBW) {                                            // loads retire in order: only the block issued last may remain
+                if (NDMA == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            __builtin_amdgcn_s_barrier();                                 // R_j
+            if (j >= 1 && j + 2 < NBW) issue_w(j + 2);                    // into the stage block j - 1 occupied
+        }
+        __builtin_amdgcn_s_barrier();                                     // BE1
+        __builtin_amdgcn_s_barrier();                                     // BE2
+        __builtin_amdgcn_s_barrier();                                     // BE3
+        return;
+    }
+
+    // ---------------------------------------------------------------------- compute waves
+    // ---- head: the global operands of the attention phases are requested in the order in which they are needed (loads return in order):
+    // this projection wave's dx1_t rows (dO), lse and this thread's o pieces (Dsum) here; the bulk — the q | k | v rows (3 D wide: CPR
+    // 16-byte pieces per row, piece c -> tile (c % HP) / 8 of kind c / HP) of all 48 rows, zeros from row n on — only behind B0, and the
+    // tiles go to LDS only after Dsum.  All workgroups of a launch start together and their q | k | v rows come from HBM: requested and
+    // awaited here they put the chip's whole read traffic in front of the first product, and requested here they still queue in front of
+    // the DMA wave's Wo^T blocks in the CU's vector-memory path; this way they stream in behind dO and Dsum.
+    ABB_T0()
+    constexpr int CPR = 3 * D / 8, HP = D / 8;
+    constexpr int NP = (48 * CPR + NCT - 1) / NCT;                        // tile pieces per thread
+    constexpr int NDS = (H * 384 + NCT - 1) / NCT;                        // Dsum tasks (head, query, 16-byte part) per thread
+    const int ct = wave & 3, rt = wave >> 2;
+    uint4 tv[NP], ov[NDS];
+    Frag<bf16> fa[KSTEPS];
+    // (unconditional loads, rows from n on clamped to row n - 1 and zeroed where the value is used: under a branch per load the compiler
+    // waits for all of them at the first use of any)
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks) fa[ks].v = *reinterpret_cast<const bf16x8*>(dx1t + (row0 + min(16 * rt + li, n - 1)) * D + ks * 32 + 8 * g);
+    const float ls_raw = lse[((long)b * H + min(tid / 48, H - 1)) * n + min(tid % 48, n - 1)];
+#pragma unroll
+    for (int i = 0; i < NDS; ++i) {
+        const int id = tid + i * NCT, h = min(id / 384, H - 1), q = min((id % 384) >> 3, n - 1), part = id & 7;
+        ov[i] = *reinterpret_cast<const uint4*>(o + (row0 + q) * D + 64 * h + part * 8);          // (query rows from n on: Dsum is set to 0)
+    }
+    __builtin_amdgcn_s_barrier();                                         // B0
+    ABB_T(0)
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int id = tid + i * NCT, r = min(id / CPR, n - 1), c = id % CPR;
+        tv[i] = *reinterpret_cast<const uint4*>(qkv + (row0 + r) * 3 * D + c * 8);
+    }
+
+    // ---- dO_h = dx1_t Wo[:, head h] for every head: ring stage h.  (Not under `rt < RT`: the compiler would sink the dx1_t loads into that
+    // branch, behind the q | k | v requests.  A wave whose row tile holds no rows multiplies zeros into rows nobody reads.)
+    {
+        const int wrow = 16 * ct + li;
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {
+            asm volatile("" : "+v"(fa[ks].v));                           // the zeroing below stays behind the q | k | v requests: in front of
+            if (16 * rt + li >= n) fa[ks].v = bf16x8{};                  // them it would wait for these loads before they go out
+        }
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+            const char* Wb = WR + h * Ly::WBLK;
+            char* TDO = T0 + (4 * h + 3) * Ly::T_BYTES;
+            Frag<bf16> fw[KSTEPS];
+#pragma unroll
+            for (int ks = 0; ks < KSTEPS; ++ks)
+                fw[ks].v = *reinterpret_cast<const bf16x8*>(Wb + (ks >> 1) * 8192 + wrow * 128 + ((((ks & 1) * 4 + g) ^ (wrow & 7)) << 4));
+            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KSTEPS; ks += 2) {
+                acc = mma16(fa[ks], fw[ks], acc);
+                acc1 = mma16(fa[ks + 1], fw[ks + 1], acc1);
+            }
+            acc = acc + acc1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) *reinterpret_cast<bf16*>(TDO + (16 * rt + 4 * g + r) * TP + (16 * ct + li) * 2) = (bf16)acc[r];
+        }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                         // BE2: dxn1 complete
-    // ---- LN1 backward, row = 4 wave + g on 16 lanes
-    float* LP = reinterpret_cast<float*>(smem);
+    __builtin_amdgcn_s_barrier();                                         // X1: dO of every head visible
+    ABB_T(1)
+
+    // ---- Dsum[h][q] = sum_d dO_h[q, d] o_h[q, d]: 8 threads per (head, query); 384 tasks = 6 whole waves per head
+#pragma unroll
+    for (int i = 0; i < NDS; ++i) {
+        const int id = tid + i * NCT, h = id / 384;
+        if (h < H) {
+            const int q = (id % 384) >> 3, part = id & 7;
+            const bf16x8 a = *reinterpret_cast<const bf16x8*>(T0 + (4 * h + 3) * Ly::T_BYTES + q * TP + part * 16);
+            const bf16x8 c = __builtin_bit_cast(bf16x8, ov[i]);
+            float sdo = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sdo += (float)a[j] * (float)c[j];
+            sdo += __shfl_xor(sdo, 1, 64);
+            sdo += __shfl_xor(sdo, 2, 64);
+            sdo += __shfl_xor(sdo, 4, 64);
+            if (part == 0) DSUM[h * 48 + q] = q < n ? sdo : 0.f;
+        }
+    }
+    // q | k | v tiles and lse into LDS
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int id = tid + i * NCT, r = id / CPR, c = id % CPR, w = c % HP;
+        if (id < 48 * CPR) *reinterpret_cast<uint4*>(T0 + (4 * (w >> 3) + c / HP) * Ly::T_BYTES + r * TP + (w & 7) * 16) = r < n ? tv[i] : uint4{0u, 0u, 0u, 0u};
+    }
+    if (tid < H * 48) LS[tid] = tid % 48 < n ? ls_raw : INFINITY;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                         // X2: Dsum, lse and the q | k | v tiles visible
+    ABB_T(2)
+
+    // ---- attention backward as tasks: dQ of (head, query tile), dK / dV of (head, key tile); the results wait in registers
+    const int ntile = (n + 31) >> 5;
+    bf16x4 rq[4], rk[4], rv[4];
+    auto dq_task = [&](int h, int t) {
+        // dQ for query tile t (lane li = query): S^T = K Q^T, dP^T = V dO^T, dS^T -> operand, dQ^T += K^T dS^T
+        const char* TQ = T0 + 4 * h * Ly::T_BYTES;
+        const char *TK = TQ + Ly::T_BYTES, *TV = TK + Ly::T_BYTES, *TDO = TV + Ly::T_BYTES;
+        const int q = 16 * t + li;
+        Frag<bf16> fq[2], fdo[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            fq[ks].v = *reinterpret_cast<const bf16x8*>(TQ + q * TP + (ks * 32 + 8 * g) * 2);
+            fdo[ks].v = *reinterpret_cast<const bf16x8*>(TDO + q * TP + (ks * 32 + 8 * g) * 2);
+        }
+        const float Dq = DSUM[h * 48 + q], lq = LS[h * 48 + q];
+        f32x4 dq[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) dq[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kt = 0; kt < ntile; ++kt) {
+            const bool hi_ok = 32 * kt + 16 < 16 * RT;
+            f32x4 ds[2];
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                f32x4 sc = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (tt == 0 || hi_ok) {
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks) {
+                        Frag<bf16> fk, fv;
+                        fk.v = *reinterpret_cast<const bf16x8*>(TK + (32 * kt + 16 * tt + li) * TP + (ks * 32 + 8 * g) * 2);
+                        fv.v = *reinterpret_cast<const bf16x8*>(TV + (32 * kt + 16 * tt + li) * TP + (ks * 32 + 8 * g) * 2);
+                        sc = mma16(fk, fq[ks], sc);
+                        dp = mma16(fv, fdo[ks], dp);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = kt * 32 + 16 * tt + 4 * g + r;
+                    const float p = (key < n) ? __expf(sc[r] * AB_SCALE - lq) : 0.f;
+                    ds[tt][r] = p * (dp[r] - Dq) * AB_SCALE;
+                }
+            }
+            const Frag<bf16> fds = acc_to_frag<bf16>(ds[0], ds[1]);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                const int q4 = li >> 2, p4 = li & 3;
+                const bf16* kp = reinterpret_cast<const bf16*>(TK) + (32 * kt + 4 * g + q4) * TLD + 16 * d + 4 * p4;
+                const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)kp);
+                bf16x4 hi;
+                hi[0] = hi[1] = hi[2] = hi[3] = (bf16)0.f;
+                if (hi_ok) hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(kp + 16 * TLD));
+                Frag<bf16> fkT;
+                fkT.v[0] = lo[0]; fkT.v[1] = lo[1]; fkT.v[2] = lo[2]; fkT.v[3] = lo[3];
+                fkT.v[4] = hi[0]; fkT.v[5] = hi[1]; fkT.v[6] = hi[2]; fkT.v[7] = hi[3];
+                dq[d] = mma16(fkT, fds, dq[d]);
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            bf16x4 pk;
+            pk[0] = (bf16)dq[d][0]; pk[1] = (bf16)dq[d][1]; pk[2] = (bf16)dq[d][2]; pk[3] = (bf16)dq[d][3];
+            if (q >= n) pk[0] = pk[1] = pk[2] = pk[3] = (bf16)0.f;
+            rq[d] = pk;
+        }
+    };
+    auto dkv_task = [&](int h, int t) {
+        // dK / dV for key tile t (lane li = key): S = Q K^T, dP = dO V^T, dV^T += dO^T P, dK^T += Q^T dS
+        const char* TQ = T0 + 4 * h * Ly::T_BYTES;
+        const char *TK = TQ + Ly::T_BYTES, *TV = TK + Ly::T_BYTES, *TDO = TV + Ly::T_BYTES;
+        const float *LSh = LS + h * 48, *DSh = DSUM + h * 48;
+        const int key = 16 * t + li;
+        Frag<bf16> fk[2], fv[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            fk[ks].v = *reinterpret_cast<const bf16x8*>(TK + key * TP + (ks * 32 + 8 * g) * 2);
+            fv[ks].v = *reinterpret_cast<const bf16x8*>(TV + key * TP + (ks * 32 + 8 * g) * 2);
+        }
+        f32x4 dk[4], dv[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            dk[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+            dv[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        for (int qt = 0; qt < ntile; ++qt) {
+            const bool hi_ok = 32 * qt + 16 < 16 * RT;
+            f32x4 pp[2], ds[2];
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                f32x4 sc = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (tt == 0 || hi_ok) {
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks) {
+                        Frag<bf16> fqa, fg;
+                        fqa.v = *reinterpret_cast<const bf16x8*>(TQ + (32 * qt + 16 * tt + li) * TP + (ks * 32 + 8 * g) * 2);
+                        fg.v = *reinterpret_cast<const bf16x8*>(TDO + (32 * qt + 16 * tt + li) * TP + (ks * 32 + 8 * g) * 2);
+                        sc = mma16(fqa, fk[ks], sc);
+                        dp = mma16(fg, fv[ks], dp);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ql = 32 * qt + 16 * tt + 4 * g + r;
+                    const bool live = key < n && ql < n;
+                    const float pv = live ? __expf(sc[r] * AB_SCALE - LSh[live ? ql : 0]) : 0.f;
+                    pp[tt][r] = pv;
+                    ds[tt][r] = live ? pv * (dp[r] - DSh[ql]) * AB_SCALE : 0.f;
+                }
+            }
+            const Frag<bf16> fp = acc_to_frag<bf16>(pp[0], pp[1]);
+            const Frag<bf16> fds = acc_to_frag<bf16>(ds[0], ds[1]);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                const int q4 = li >> 2, p4 = li & 3;
+                const int roff = (32 * qt + 4 * g + q4) * TLD + 16 * d + 4 * p4;
+                const bf16* gp = reinterpret_cast<const bf16*>(TDO) + roff;
+                const bf16* qp = reinterpret_cast<const bf16*>(TQ) + roff;
+                const bf16x4 glo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)gp);
+                const bf16x4 qlo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)qp);
+                bf16x4 ghi, qhi;
+                ghi[0] = ghi[1] = ghi[2] = ghi[3] = (bf16)0.f;
+                qhi = ghi;
+                if (hi_ok) {
+                    ghi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(gp + 16 * TLD));
+                    qhi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(qp + 16 * TLD));
+                }
+                Frag<bf16> fgT, fqT;
+                fgT.v[0] = glo[0]; fgT.v[1] = glo[1]; fgT.v[2] = glo[2]; fgT.v[3] = glo[3];
+                fgT.v[4] = ghi[0]; fgT.v[5] = ghi[1]; fgT.v[6] = ghi[2]; fgT.v[7] = ghi[3];
+                fqT.v[0] = qlo[0]; fqT.v[1] = qlo[1]; fqT.v[2] = qlo[2]; fqT.v[3] = qlo[3];
+                fqT.v[4] = qhi[0]; fqT.v[5] = qhi[1]; fqT.v[6] = qhi[2]; fqT.v[7] = qhi[3];
+                dv[d] = mma16(fgT, fp, dv[d]);
+                dk[d] = mma16(fqT, fds, dk[d]);
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            bf16x4 kk, vv;
+            kk[0] = (bf16)dk[d][0]; kk[1] = (bf16)dk[d][1]; kk[2] = (bf16)dk[d][2]; kk[3] = (bf16)dk[d][3];
+            vv[0] = (bf16)dv[d][0]; vv[1] = (bf16)dv[d][1]; vv[2] = (bf16)dv[d][2]; vv[3] = (bf16)dv[d][3];
+            if (key >= n) { kk[0] = kk[1] = kk[2] = kk[3] = (bf16)0.f; vv = kk; }
+            rk[d] = kk;
+            rv[d] = vv;
+        }
+    };
+    // task list (wave-uniform): with 2 H RT <= 12 every task has a wave of its own — dQ tasks on waves 0 .. H RT - 1, dK / dV tasks on
+    // the H RT waves after them; otherwise (H = 3, n > 32) wave (h, t) runs dQ of query tile t and then dK / dV of key tile t
+    const int NQT = H * RT;
+    int hq = -1, tq = 0, hk = -1, tk = 0;
+    if (wave < NQT) {
+        hq = wave / RT;
+        tq = wave - hq * RT;
+        if (2 * NQT > AB_CW) { hk = hq; tk = tq; }
+    } else if (2 * NQT <= AB_CW && wave < 2 * NQT) {
+        hk = (wave - NQT) / RT;
+        tk = (wave - NQT) - hk * RT;
+    }
+    if (hq >= 0) dq_task(hq, tq);
+    if (hk >= 0) dkv_task(hk, tk);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                         // X3: nobody reads q, k, v any more
+    ABB_T(3)
+    if (hq >= 0) {
+#pragma unroll
+        for (int d = 0; d < 4; ++d) *reinterpret_cast<bf16x4*>(T0 + 4 * hq * Ly::T_BYTES + (16 * tq + li) * TP + (16 * d + 4 * g) * 2) = rq[d];
+    }
+    if (hk >= 0) {
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            *reinterpret_cast<bf16x4*>(T0 + (4 * hk + 1) * Ly::T_BYTES + (16 * tk + li) * TP + (16 * d + 4 * g) * 2) = rk[d];
+            *reinterpret_cast<bf16x4*>(T0 + (4 * hk + 2) * Ly::T_BYTES + (16 * tk + li) * TP + (16 * d + 4 * g) * 2) = rv[d];
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                         // X4: dq | dk | dv of every head in place of q | k | v
+
+    // operands of the LayerNorm tail (this thread's x / dres row chunks, gamma1): on their way during the dxn1 blocks.  Requested as
+    // stored (a bf16 residual stream is widened, and rows from n on zeroed, only in front of the tail: converting at the load makes
+    // every one of these loads wait for the one before it)
+    using RV = typename std::conditional<sizeof(R) == 2, bf16x4, f32x4>::type;
+    RV xraw[KT], draw[KT];
+    f32x4 gm_t[KT];
+    const int trow = 4 * wave + g;
     {
-        const int r = 4 * wave + g;
-        const bool ok = r < n;
-        f32x4 xh[KT], dy[KT], gd[KT];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < KT; ++c) {
-            xh[c] = xr_t[c];
-            s += (xh[c][0] + xh[c][1]) + (xh[c][2] + xh[c][3]);
-        }
-        const float mean = row16_sum(s) / D;
-        float q = 0.f;
-#pragma unroll
-        for (int c = 0; c < KT; ++c) {
-            xh[c] = xh[c] - mean;
-            q += (xh[c][0] * xh[c][0] + xh[c][1] * xh[c][1]) + (xh[c][2] * xh[c][2] + xh[c][3] * xh[c][3]);
-        }
-        const float rstd = rsqrtf(row16_sum(q) / D + eps);
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < KT; ++c) {
-            xh[c] = xh[c] * rstd;
-            dy[c] = ok ? *reinterpret_cast<const f32x4*>(Y + r * YLD + 4 * (li + 16 * c)) : f32x4{0.f, 0.f, 0.f, 0.f};
-            gd[c] = dy[c] * gm_t[c];
-            s1 += (gd[c][0] + gd[c][1]) + (gd[c][2] + gd[c][3]);
-            const f32x4 t = gd[c] * xh[c];
-            s2 += (t[0] + t[1]) + (t[2] + t[3]);
-        }
-        s1 = row16_sum(s1) / D;
-        s2 = row16_sum(s2) / D;
+        const long ro = (row0 + min(trow, n - 1)) * D;
 #pragma unroll
         for (int c = 0; c < KT; ++c) {
             const int col = 4 * (li + 16 * c);
-            f32x4 rr = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (ok) {
-                rr = (gd[c] - s1 - xh[c] * s2) * rstd + dr_t[c];
-                if (sizeof(R) == 4) st_res4<R>(dx_out + (row0 + r) * D + col, rr);
-                if (dxt_out) {
-                    bf16x4 pk;
-                    pk[0] = (bf16)rr[0]; pk[1] = (bf16)rr[1]; pk[2] = (bf16)rr[2]; pk[3] = (bf16)rr[3];
-                    *reinterpret_cast<bf16x4*>(dxt_out + (row0 + r) * D + col) = pk;
-                }
-            }
-            f32x4 pg = dy[c] * xh[c], pb = dy[c], pc = rr;
+            gm_t[c] = *reinterpret_cast<const f32x4*>(ln1_w + col);
+            xraw[c] = *reinterpret_cast<const RV*>(x + ro + col);
+            if constexpr (sizeof(R) == 2) draw[c] = *reinterpret_cast<const RV*>(dx1t + ro + col);
+            else draw[c] = *reinterpret_cast<const RV*>(dres + ro + col);
+        }
+    }
+    // ---- dqkv -> global: whole 3 D-wide rows (after the requests above: the compiler waits for the loop's stores before anything that follows it)
+    for (int id = tid; id < n * CPR; id += NCT) {
+        const int r = id / CPR, c = id % CPR, w = c % HP;
+        *reinterpret_cast<uint4*>(dqkv_out + (row0 + r) * 3 * D + c * 8) =
+            *reinterpret_cast<const uint4*>(T0 + (4 * (w >> 3) + c / HP) * Ly::T_BYTES + r * TP + (w & 7) * 16);
+    }
+    ABB_T(4)
+    // ---- dxn1 = sum over heads of dq_h Wqkv[q_h cols] + dk_h Wqkv[k_h cols] + dv_h Wqkv[v_h cols]: ring blocks 3 h + t
+    f32x4 yacc[3];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pg[e] = xor16_sum(pg[e]); pg[e] = xor32_sum(pg[e]);
-                pb[e] = xor16_sum(pb[e]); pb[e] = xor32_sum(pb[e]);
-                pc[e] = xor16_sum(pc[e]); pc[e] = xor32_sum(pc[e]);
-            }
-            if (g == 0) {
-                *reinterpret_cast<f32x4*>(LP + (wave * 3 + 0) * D + col) = pg;
-                *reinterpret_cast<f32x4*>(LP + (wave * 3 + 1) * D + col) = pb;
-                *reinterpret_cast<f32x4*>(LP + (wave * 3 + 2) * D + col) = pc;
+    for (int j = 0; j < 3; ++j) yacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int h = 0; h < H; ++h) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            __builtin_amdgcn_s_barrier();                                 // R(3h + t)
+            if (rt < RT) {
+                const char* Wb = WR + ((3 * h + t) % Ly::NSTAGE) * Ly::WBLK;
+                const char* Ts = T0 + (4 * h + t) * Ly::T_BYTES;
+                Frag<bf16> fd[2];
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) fd[ks].v = *reinterpret_cast<const bf16x8*>(Ts + (16 * rt + li) * TP + (ks * 32 + 8 * g) * 2);
+                Frag<bf16> fw2[KT][2];
+#pragma unroll
+                for (int j = 0; j < KT; ++j) {
+                    const int rw = 16 * (ct + 4 * j) + li;
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks)
+                        fw2[j][ks].v = *reinterpret_cast<const bf16x8*>(Wb + (rw >> 6) * 8192 + (rw & 63) * 128 + (((ks * 4 + g) ^ (rw & 7)) << 4));
+                }
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                    for (int j = 0; j < KT; ++j) yacc[j] = mma16(fd[ks], fw2[j][ks], yacc[j]);
             }
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                         // BE3
-    for (int id = tid; id < 3 * D; id += 64 * AB_CW) {
-        float sacc = 0.f;
+    ABB_T(5)
+    f32x4 xr_t[KT], dr_t[KT];
 #pragma unroll
-        for (int w = 0; w < AB_CW; ++w) sacc += LP[w * 3 * D + id];
-        ln_part[(long)b * 3 * D + id] = sacc;
+    for (int c = 0; c < KT; ++c) {
+        xr_t[c] = trow < n ? f32x4{(float)xraw[c][0], (float)xraw[c][1], (float)xraw[c][2], (float)xraw[c][3]} : f32x4{0.f, 0.f, 0.f, 0.f};
+        dr_t[c] = trow < n ? f32x4{(float)draw[c][0], (float)draw[c][1], (float)draw[c][2], (float)draw[c][3]} : f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    abb_tail<KT, R>(smem, WR, yacc, xr_t, dr_t, gm_t, tid, n, eps, dx_out, dxt_out, ln_part);
+    ABB_T(6)
+    ABB_TEND()
 }
 
 #ifndef M3L_BLOCK_BODIES_ONLY
+template <int KT, typename R>
+__global__ __launch_bounds__(AB_THREADS) void attn_block_bwd_allheads_kernel(
+    const bf16* __restrict__ dx1t, const R* __restrict__ dres, const R* __restrict__ x, const float* __restrict__ ln1_w,
+    const bf16* __restrict__ qkv, const bf16* __restrict__ o, const float* __restrict__ lse, const bf16* __restrict__ WoT,
+    const bf16* __restrict__ WqkvT, float eps, int n, bf16* __restrict__ dqkv_out, R* __restrict__ dx_out, bf16* __restrict__ dxt_out,
+    float* __restrict__ ln_part) {
+    attn_block_bwd_allheads_body<KT, R>(dx1t, dres, x, ln1_w, qkv, o, lse, WoT, WqkvT, eps, n, dqkv_out, dx_out, dxt_out, ln_part);
+}
+
 template <int KT, typename R>
 __global__ __launch_bounds__(AB_THREADS) void attn_block_bwd_kernel(
     const bf16* __restrict__ dx1t, const R* __restrict__ dres, const R* __restrict__ x, const float* __restrict__ ln1_w,
@@ -882,6 +1386,22 @@ int m3l_attn_block_supported(int dtype, int D, int heads, int n, int project_out
 // gradient kernel (wgrad.hip, 1.1 ms per step) it pays: 49.4k -> 50.7k, so mode 3 is the default.
 int m3l_attn_block_bwd_enabled(void) { return ab_state() > 0 && (g_ab_state & 2); }
 
+// Which body the attention backward block runs: 1 = all heads of a sample in one pass (attn_block_bwd_allheads_body), 0 = one head after
+// the other (attn_block_bwd_body, the reference and A/B baseline).  Bit-identical results; env M3L_ATTN_BWD_HEADS sets the initial mode.
+static int g_abb_heads = -1;         // -1 = environment not read yet
+int m3l_attn_bwd_heads(void) {
+    if (g_abb_heads < 0) g_abb_heads = getenv("M3L_ATTN_BWD_HEADS") ? (atoi(getenv("M3L_ATTN_BWD_HEADS")) != 0) : 1;
+    return g_abb_heads;
+}
+#if ABB_STAMP
+extern "C" int m3l_abb_set_stamps(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(d_abb_stamps), &p, sizeof(p)) == hipSuccess ? 0 : 1; }
+#endif
+extern "C" int m3l_set_attn_bwd_heads(int mode) {
+    const int old = m3l_attn_bwd_heads();
+    g_abb_heads = mode != 0;
+    return old;
+}
+
 int m3l_attn_block_fwd(int D, int B, int n, const float* x, const float* ln1_w, const float* ln1_b, const void* wqkv, const void* wo,
                        const float* bo, const float* ln2_w, const float* ln2_b, float eps, void* xn1, void* qkv, void* o, float* lse,
                        float* x1, void* xn2, hipStream_t st) {
@@ -918,20 +1438,29 @@ int m3l_attn_block_bwd(int D, int B, int n, const void* dx1t, const float* dres,
         M3L_HIP(hipFuncSetAttribute((const void*)attn_block_bwd_kernel<3, float>, hipFuncAttributeMaxDynamicSharedMemorySize, AbBwdLayout<3>::TOTAL));
         M3L_HIP(hipFuncSetAttribute((const void*)attn_block_bwd_kernel<2, bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, AbBwdLayout<2>::TOTAL));
         M3L_HIP(hipFuncSetAttribute((const void*)attn_block_bwd_kernel<3, bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, AbBwdLayout<3>::TOTAL));
+        M3L_HIP(hipFuncSetAttribute((const void*)attn_block_bwd_allheads_kernel<2, float>, hipFuncAttributeMaxDynamicSharedMemorySize, AbBwdAllLayout<2>::TOTAL));
+        M3L_HIP(hipFuncSetAttribute((const void*)attn_block_bwd_allheads_kernel<3, float>, hipFuncAttributeMaxDynamicSharedMemorySize, AbBwdAllLayout<3>::TOTAL));
+        M3L_HIP(hipFuncSetAttribute((const void*)attn_block_bwd_allheads_kernel<2, bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, AbBwdAllLayout<2>::TOTAL));
+        M3L_HIP(hipFuncSetAttribute((const void*)attn_block_bwd_allheads_kernel<3, bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, AbBwdAllLayout<3>::TOTAL));
         inited = 1;
     }
     M3L_CHECK(D == 128 || D == 192, "attn_block_bwd: D=%d unsupported", D);
     M3L_CHECK(!m3l_call_rb() || dxt_out, "attn_block_bwd: the bf16 residual mode writes its result to dxt_out only");
     ProfScope prof("attn_block_bwd", B, n, D, 2.0 * B * n * (4.0 * D * D) + 10.0 * B * (D / 64) * (double)n * n * 64, st,
                    (double)B * n * D * (18.0 + (m3l_call_rb() ? 2.0 : 12.0)));            // dx1t, qkv, o, dqkv, dx_t | x (+ fp32: dres, dx)
-#define ABB_LAUNCH(KT, R)                                                                                                               \
-    attn_block_bwd_kernel<KT, R><<<B, AB_THREADS, AbBwdLayout<KT>::TOTAL, st>>>((const bf16*)dx1t, (const R*)dres, (const R*)x, ln1_w, (const bf16*)qkv, \
-                                                                               (const bf16*)o, lse, (const bf16*)woT, (const bf16*)wqkvT, eps, n,     \
-                                                                               (bf16*)dqkv, (R*)dx_out, (bf16*)dxt_out, ln_part)
+#define ABB_ARGS(R) (const bf16*)dx1t, (const R*)dres, (const R*)x, ln1_w, (const bf16*)qkv, (const bf16*)o, lse, (const bf16*)woT, (const bf16*)wqkvT, eps, n, \
+                    (bf16*)dqkv, (R*)dx_out, (bf16*)dxt_out, ln_part
+#define ABB_LAUNCH(KT, R)                                                                                                     \
+    do {                                                                                                                      \
+        if (allheads) attn_block_bwd_allheads_kernel<KT, R><<<B, AB_THREADS, AbBwdAllLayout<KT>::TOTAL, st>>>(ABB_ARGS(R));   \
+        else attn_block_bwd_kernel<KT, R><<<B, AB_THREADS, AbBwdLayout<KT>::TOTAL, st>>>(ABB_ARGS(R));                        \
+    } while (0)
+    const int allheads = m3l_attn_bwd_heads();
     if (m3l_call_rb()) { if (D == 128) ABB_LAUNCH(2, bf16); else ABB_LAUNCH(3, bf16); }
     else if (D == 128) ABB_LAUNCH(2, float);
     else ABB_LAUNCH(3, float);
 #undef ABB_LAUNCH
+#undef ABB_ARGS
     M3L_LAUNCH_CHECK();
     return 0;
 }

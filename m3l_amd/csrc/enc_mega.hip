@@ -105,13 +105,18 @@ struct MegaBwdPack {
     int count;
 };
 
-template <int KT, typename R>
+// ALLH: the attention half runs attn_block_bwd_allheads_body (m3l_set_attn_bwd_heads), a kernel of its own so that only one of the two bodies
+// is inlined into the layer loop
+template <int KT, typename R, bool ALLH>
 __global__ __launch_bounds__(AB_THREADS) void enc_bwd_mega_kernel(float* __restrict__ dx, MegaBwdPack P, float eps, int n, int mlp) {
     for (int step = 0; step < 2 * P.count; ++step) {
         const MegaBwdLayer& L = P.L[step >> 1];
         if ((step & 1) == 0)
             mlp_block_bwd_body<KT, R>(L.dxt, reinterpret_cast<R*>(dx), reinterpret_cast<const R*>(L.x1), L.ln2_w, L.u, L.w2T, L.w1T, eps, n, mlp, L.du, L.dx1t,
                                       L.cs_part, L.ln2_part);
+        else if (ALLH)
+            attn_block_bwd_allheads_body<KT, R>(L.dx1t, reinterpret_cast<const R*>(dx), reinterpret_cast<const R*>(L.x), L.ln1_w, L.qkv, L.o, L.lse, L.woT, L.wqkvT,
+                                                eps, n, L.dqkv, reinterpret_cast<R*>(L.dx_out), L.dxt_out, L.ln1_part);
         else
             attn_block_bwd_body<KT, R>(L.dx1t, reinterpret_cast<const R*>(dx), reinterpret_cast<const R*>(L.x), L.ln1_w, L.qkv, L.o, L.lse, L.woT, L.wqkvT, eps, n,
                                        L.dqkv, reinterpret_cast<R*>(L.dx_out), L.dxt_out, L.ln1_part);
@@ -120,7 +125,8 @@ __global__ __launch_bounds__(AB_THREADS) void enc_bwd_mega_kernel(float* __restr
 }
 
 template <int KT> constexpr int mega_bwd_lds(int mlp) {
-    const int a = AbBwdLayout<KT>::TOTAL, b = MbLayout<KT>::TOTAL + 3 * mlp * (int)sizeof(float);
+    const int a0 = AbBwdLayout<KT>::TOTAL, a1 = AbBwdAllLayout<KT>::TOTAL, a = a0 > a1 ? a0 : a1;      // either attention body
+    const int b = MbLayout<KT>::TOTAL + 3 * mlp * (int)sizeof(float);
     return a > b ? a : b;
 }
 
@@ -179,8 +185,10 @@ int m3l_enc_bwd_mega(int D, int mlp, int B, int n, float* dx, const void* const*
     M3L_CHECK(lds <= 160 * 1024, "enc_bwd_mega: mlp=%d needs %d bytes of LDS", mlp, lds);
     M3L_CHECK(!m3l_call_rb(), "enc_bwd_mega: the grouped backward launch does not run the bf16 residual mode (per-half-layer launches do)");
     if (inited_mlp != mlp) {
-        M3L_HIP(hipFuncSetAttribute((const void*)enc_bwd_mega_kernel<2, float>, hipFuncAttributeMaxDynamicSharedMemorySize, mega_bwd_lds<2>(mlp)));
-        M3L_HIP(hipFuncSetAttribute((const void*)enc_bwd_mega_kernel<3, float>, hipFuncAttributeMaxDynamicSharedMemorySize, mega_bwd_lds<3>(mlp)));
+        M3L_HIP(hipFuncSetAttribute((const void*)enc_bwd_mega_kernel<2, float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mega_bwd_lds<2>(mlp)));
+        M3L_HIP(hipFuncSetAttribute((const void*)enc_bwd_mega_kernel<3, float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mega_bwd_lds<3>(mlp)));
+        M3L_HIP(hipFuncSetAttribute((const void*)enc_bwd_mega_kernel<2, float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mega_bwd_lds<2>(mlp)));
+        M3L_HIP(hipFuncSetAttribute((const void*)enc_bwd_mega_kernel<3, float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mega_bwd_lds<3>(mlp)));
         inited_mlp = mlp;
     }
     static_assert(sizeof(MegaBwdLayer) == 21 * sizeof(void*), "MegaBwdLayer is 21 pointers");
@@ -188,10 +196,13 @@ int m3l_enc_bwd_mega(int D, int mlp, int B, int n, float* dx, const void* const*
     memcpy(P.L, layers, (size_t)count * sizeof(MegaBwdLayer));
     P.count = count;
     ProfScope prof("enc_bwd_mega", B, n, count, (double)count * (2.0 * B * n * (4.0 * D * D) + 10.0 * B * (D / 64) * (double)n * n * 64 + 4.0 * B * n * (double)D * mlp), st);
-    if (D == 128)
-        enc_bwd_mega_kernel<2, float><<<B, AB_THREADS, lds, st>>>(dx, P, eps, n, mlp);
+    if (m3l_attn_bwd_heads()) {
+        if (D == 128) enc_bwd_mega_kernel<2, float, true><<<B, AB_THREADS, lds, st>>>(dx, P, eps, n, mlp);
+        else enc_bwd_mega_kernel<3, float, true><<<B, AB_THREADS, lds, st>>>(dx, P, eps, n, mlp);
+    } else if (D == 128)
+        enc_bwd_mega_kernel<2, float, false><<<B, AB_THREADS, lds, st>>>(dx, P, eps, n, mlp);
     else
-        enc_bwd_mega_kernel<3, float><<<B, AB_THREADS, lds, st>>>(dx, P, eps, n, mlp);
+        enc_bwd_mega_kernel<3, float, false><<<B, AB_THREADS, lds, st>>>(dx, P, eps, n, mlp);
     M3L_LAUNCH_CHECK();
     return 0;
 }

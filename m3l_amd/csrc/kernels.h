@@ -154,6 +154,7 @@ int m3l_gemm_nt_colsum_rows(int M, int N);   // number of partial rows written t
 // fused LN1 + QKV + attention + out-proj + residual + LN2 for short sequences (attn_block.hip)
 int m3l_attn_block_supported(int dtype, int D, int heads, int n, int project_out, int dim_head);
 int m3l_attn_block_bwd_enabled(void);
+int m3l_attn_bwd_heads(void);        // 1: the attention backward block takes all heads in one pass (env M3L_ATTN_BWD_HEADS, default 1)
 int m3l_attn_block_fwd(int D, int B, int n, const float* x, const float* ln1_w, const float* ln1_b, const void* wqkv, const void* wo,
                        const float* bo, const float* ln2_w, const float* ln2_b, float eps, void* xn1, void* qkv, void* o, float* lse,
                        float* x1, void* xn2, hipStream_t st);

@@ -1,6 +1,8 @@
 """Standalone timing of the four short-sequence block kernels (attn_block.hip, mlp_block.hip) at the cfg-2 encoder shape (B = 256,
-n = 48, D = 192, mlp = 768), back to back on one stream — diagnostic only (internal C++ launchers by their mangled names).
-usage: python tools/block_probe.py [lib.so] [kernel-name-substring]"""
+n = 48, D = 192, mlp = 768), back to back on one stream — diagnostic only (internal C++ launchers by their mangled names).  Then the two
+bodies of attn_block_bwd (m3l_set_attn_bwd_heads 0 = one head after the other, 1 = all heads in one pass) in alternating rounds of one
+process: microseconds per launch (min / median / max over the rounds) and bit-equality of every output.
+usage: python tools/block_probe.py [lib.so] [kernel-name-substring]      (env PB, PN: batch and sequence length; ROUNDS: A/B rounds)"""
 import ctypes as C
 import os
 import sys
@@ -53,22 +55,53 @@ KERNELS = {
     "attn_block_bwd": lambda: raw._Z18m3l_attn_block_bwdiiiPKvPKfS2_S2_S0_S0_S2_S0_S0_fPvPfS3_S4_P12ihipStream_t(
         D, B, n, P(dxt), P(dres), P(x), P(lw), P(qkv), P(o), P(lse), P(woT), P(wqkvT), F, P(qkv_o), P(dxo), P(dxt_o), P(ln_part), st),
 }
-tot = 0.0
-out = []
-for name, fn in KERNELS.items():
-    if ONLY and not any(s in name for s in ONLY):
-        continue
+
+
+def timed(name, fn, reps=20):
     for _ in range(3):
         rc = fn()
         assert rc == 0, (name, rc)
     torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
-    for _ in range(20):
+    for _ in range(reps):
         fn()
     b.record()
     torch.cuda.synchronize()
-    us = a.elapsed_time(b) / 20 * 1e3
+    return a.elapsed_time(b) / reps * 1e3
+
+
+tot = 0.0
+out = []
+for name, fn in KERNELS.items():
+    if ONLY and not any(s in name for s in ONLY):
+        continue
+    us = timed(name, fn)
     tot += us
     out.append(f"{name} {us:.1f}")
-print(f"{os.path.basename(LIBP)}: " + " | ".join(out) + f" | sum {tot:.1f} us")
+print(f"{os.path.basename(LIBP)}: " + " | ".join(out) + f" | sum {tot:.1f} us", flush=True)
+
+if hasattr(raw, "m3l_set_attn_bwd_heads") and (not ONLY or any(s in "attn_block_bwd" for s in ONLY)):
+    MODES = {0: "per head", 1: "all heads"}
+    outs = (qkv_o, dxo, dxt_o, ln_part)
+    bits = {}
+    old = raw.m3l_set_attn_bwd_heads(0)
+    for mode in MODES:
+        raw.m3l_set_attn_bwd_heads(mode)
+        for t in outs:
+            t.view(torch.uint8).fill_(0xFF)
+        assert KERNELS["attn_block_bwd"]() == 0
+        torch.cuda.synchronize()
+        bits[mode] = [t.view(torch.uint8).clone() for t in outs]
+    same = all(torch.equal(p, q) for p, q in zip(bits[0], bits[1]))
+    print(f"attn_block_bwd B={B} n={n}: outputs of the two modes bit-identical: {same}", flush=True)
+    times = {m: [] for m in MODES}
+    for _ in range(int(os.environ.get("ROUNDS", "7"))):
+        for mode in MODES:
+            raw.m3l_set_attn_bwd_heads(mode)
+            times[mode].append(timed("attn_block_bwd", KERNELS["attn_block_bwd"]))
+    raw.m3l_set_attn_bwd_heads(old)
+    for mode, label in MODES.items():
+        t = sorted(times[mode])
+        print(f"attn_block_bwd mode {mode} ({label:9s}): min {t[0]:6.1f}  median {t[len(t) // 2]:6.1f}  max {t[-1]:6.1f} us per launch over {len(t)} rounds", flush=True)
+    assert same
