@@ -594,6 +594,72 @@ int m3l_op_ibot_center_sum(const float* T, int rows, int K, float scale, void* w
  * len[i] floats.  dst / src / len: host arrays (device pointers, element counts). */
 int m3l_op_ema(float* const* dst, const float* const* src, const long* len, int count, float beta, float one_minus_beta, void* stream);
 
+/* ---- PPO policy head (ABI 409): the arithmetic between the extractor's features and the scalar that PPO_MAE.train calls backward on
+ * (models/ppo_mae.py:280-340), and the same head on every environment step (MAEPolicy.forward, models/pretrain_models.py:899-923).  The head is
+ * Stable-Baselines3's ActorCriticPolicy with net_arch = dict(pi=[...], vf=[...]) and Tanh (train.py:166): two MLP branches of Linear + Tanh
+ * layers, action_net, value_net and a state-independent log_std.  SB3 itself is not part of the reference tree, so the head's own arithmetic is
+ * stated here, not quoted; the loss lines are the reference's.  float32 throughout, whatever the encoder's compute type: the ratio
+ * exp(logp - logp_old) is what PPO clips on.  With x [B, F], actions a [B, A], log_std s [A]:
+ *   mu = action_net(pi(x)) [B, A];   values = value_net(vf(x)) [B]
+ *   logp_i    = sum_j ( -(a_ij - mu_ij)^2 / (2 exp(2 s_j)) - s_j - 1/2 ln 2 pi )
+ *   entropy_i = sum_j ( 1/2 + 1/2 ln 2 pi + s_j )
+ *   act: a = mu + exp(s) noise for an explicit noise [B, A] (NULL: a = mu); logp is formed from the stored a by the code that evaluates given
+ *        actions, so evaluating the returned actions on the same features gives the same bits.
+ * PPO loss (ppo_mae.py:281-331), over B rows:
+ *   Ahat = (A - mean A) / (std A + 1e-8), unbiased std, when normalize_advantage and B > 1, else A                                   :285-286
+ *   d = logp - old_logp, r = exp(d);  policy_loss = -mean min(Ahat r, Ahat clamp(r, 1 - clip_range, 1 + clip_range))               :289-294
+ *   v_pred = values, or old_values + clamp(values - old_values, -clip_range_vf, clip_range_vf);  value_loss = mean (returns - v_pred)^2  :301-311
+ *   entropy_loss = -mean entropy;  loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss                                   :319-323
+ *   stats[5] = policy_loss, value_loss, entropy_loss, clip_fraction = mean(|r - 1| > clip_range), approx_kl = mean(expm1(d) - d)     :297-331
+ *   (expm1(d) - d is the reference's (exp(d) - 1) - d, and exactly 0 at d = 0).
+ * Gradient convention, what torch's min and clamp give in total:
+ *   dloss/dlogp_i  = -Ahat_i r_i / B where Ahat_i r_i <= Ahat_i clamp(r_i) (the unclipped term is the minimum, or the two are equal: r = 1
+ *                    gets the full gradient), else 0
+ *   dloss/dvalue_i = vf_coef 2 (v_pred_i - returns_i) / B where |values_i - old_values_i| <= clip_range_vf or values are not clipped, else 0
+ *   dloss/dentropy_i = -ent_coef / B, so log_std receives -ent_coef per dimension plus its share through logp.
+ * Launches: act 1; eval_fwd 1 (grid: row tiles of 16 x the two branches; activations stay in LDS between layers, the weights stream from L2 as
+ * operands of the exact-f32 MFMA; with a workspace every hidden layer's post-Tanh activation and mu are stored for the backward, with ws NULL
+ * nothing is); eval_bwd 2 (a chain kernel per row tile: d mu, d v, back through the layers to dx — the sum of both branches — leaving each
+ * layer's pre-activation gradient in the workspace; then one grouped launch for every weight and bias gradient and d log_std); ppo_loss_fwd 1;
+ * ppo_loss_bwd 1.  No float atomics, every sum in a fixed order: two runs give the same bits.
+ * Limits: B >= 1; F and every hidden width a multiple of 16, at most 512; 0 to 3 hidden layers per branch (the branches may differ);
+ * 1 <= A <= 64; x, the weights, ws and dx 16-byte aligned.  Anything else is an error and nothing is written.
+ * Layouts are torch.nn.Linear's: weight [out, in] row-major, bias [out]; value_weight [1, last], value_bias [1].  Gradients go to a second
+ * descriptor with the same counts whose pointers name the gradient buffers; every one is overwritten.
+ * ws: m3l_policy_ws_bytes bytes; eval_bwd reads what eval_fwd of the same descriptor, B, x and actions left there. */
+#define M3L_POLICY_MAX_HIDDEN 3
+typedef struct m3l_policy_desc {
+    int features, actions;                    /* F, A */
+    int n_pi, n_vf;                           /* hidden layers of the policy / value branch */
+    int pi_width[M3L_POLICY_MAX_HIDDEN], vf_width[M3L_POLICY_MAX_HIDDEN];
+    float* pi_weight[M3L_POLICY_MAX_HIDDEN];
+    float* pi_bias[M3L_POLICY_MAX_HIDDEN];
+    float* vf_weight[M3L_POLICY_MAX_HIDDEN];
+    float* vf_bias[M3L_POLICY_MAX_HIDDEN];
+    float* action_weight;                     /* [A, last pi width or F] */
+    float* action_bias;
+    float* value_weight;                      /* [1, last vf width or F] */
+    float* value_bias;
+    float* log_std;                           /* [A] */
+} m3l_policy_desc;
+size_t m3l_policy_ws_bytes(const m3l_policy_desc* head, int B);
+/* actions [B, A], values [B], logp [B] are written; noise [B, A] or NULL (deterministic) */
+int m3l_policy_act(const m3l_policy_desc* head, int B, const float* x, const float* noise, float* actions, float* values, float* logp, void* stream);
+/* values [B], logp [B], entropy [B] are written; ws NULL when no backward follows */
+int m3l_policy_eval_fwd(const m3l_policy_desc* head, int B, const float* x, const float* actions, void* ws, float* values, float* logp, float* entropy,
+                        void* stream);
+/* dvalues, dlogp, dentropy: [B] each, NULL = zero; dx [B, F] and every buffer of `grads` are overwritten */
+int m3l_policy_eval_bwd(const m3l_policy_desc* head, int B, const float* x, const float* actions, const float* dvalues, const float* dlogp,
+                        const float* dentropy, void* ws, float* dx, const m3l_policy_desc* grads, void* stream);
+/* old_values NULL and clip_range_vf < 0: values are not clipped.  Writes loss[1], stats[5] and the per-row coefficients coef_logp [B] =
+ * dloss/dlogp, coef_values [B] = dloss/dvalues that the backward scales. */
+int m3l_policy_ppo_loss_fwd(const float* logp, const float* values, const float* entropy, const float* old_logp, const float* advantages, const float* returns,
+                            const float* old_values, int B, float clip_range, float clip_range_vf, float ent_coef, float vf_coef, int normalize_advantage,
+                            float* loss, float* stats, float* coef_logp, float* coef_values, void* stream);
+/* dloss: device scalar.  dlogp, dvalues, dentropy [B] = dloss[0] times the coefficients (dentropy: -ent_coef / B) */
+int m3l_policy_ppo_loss_bwd(const float* dloss, const float* coef_logp, const float* coef_values, int B, float ent_coef, float* dlogp, float* dvalues,
+                            float* dentropy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,13 @@ class CommPlan(C.Structure):
                 ("stage_end", C.POINTER(C.c_long)), ("sent_out", C.POINTER(C.c_long))]
 
 
+class PolicyDesc(C.Structure):
+    """m3l_policy_desc: widths, layer counts and device pointers of an actor-critic head (include/m3l_amd.h "PPO policy head")."""
+    _fields_ = [("features", c_i), ("actions", c_i), ("n_pi", c_i), ("n_vf", c_i), ("pi_width", c_i * 3), ("vf_width", c_i * 3),
+                ("pi_weight", c_p * 3), ("pi_bias", c_p * 3), ("vf_weight", c_p * 3), ("vf_bias", c_p * 3),
+                ("action_weight", c_p), ("action_bias", c_p), ("value_weight", c_p), ("value_bias", c_p), ("log_std", c_p)]
+
+
 _SIGS = {
     "m3l_version": (c_i, []),
     "m3l_last_error": (c_i, [C.c_char_p, c_sz]),
@@ -187,6 +194,12 @@ _SIGS = {
     "m3l_op_ibot_grad": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_p, C.c_float, C.c_float, c_p, c_p, c_p, c_p, c_i, c_p]),
     "m3l_op_ibot_center_sum": (c_i, [c_p, c_i, c_i, C.c_float, c_p, c_p, c_p]),
     "m3l_op_ema": (c_i, [c_p, c_p, c_p, c_i, C.c_float, C.c_float, c_p]),
+    "m3l_policy_ws_bytes": (c_sz, [C.POINTER(PolicyDesc), c_i]),
+    "m3l_policy_act": (c_i, [C.POINTER(PolicyDesc), c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_policy_eval_fwd": (c_i, [C.POINTER(PolicyDesc), c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_policy_eval_bwd": (c_i, [C.POINTER(PolicyDesc), c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(PolicyDesc), c_p]),
+    "m3l_policy_ppo_loss_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, C.c_float, C.c_float, C.c_float, C.c_float, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_policy_ppo_loss_bwd": (c_i, [c_p, c_p, c_p, c_i, C.c_float, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

@@ -1,0 +1,692 @@
+// PPO policy head (include/m3l_amd.h "PPO policy head"): the two Tanh MLPs of an actor-critic policy, action_net / value_net, the diagonal
+// Gaussian's log-probability and entropy, and the clipped PPO loss with its statistics.  float32 throughout, on the exact-f32 MFMA
+// (v_mfma_f32_16x16x4_f32 through Frag<float> / mma16 of common.cuh).
+//
+//   forward   one launch, grid (row tiles of 16, 2 branches): the tile of x goes into LDS, every Linear + Tanh reads its input from LDS and
+//             leaves its output in the other LDS buffer (and, for the backward, in the workspace); the weights stream from L2 as the k-contiguous
+//             operand.  Branch 0 ends in action_net and the Gaussian (mu, actions, log_prob, entropy), branch 1 in value_net.
+//   backward  chain kernel, one workgroup per row tile: d mu and d v, then back through the layers of the value branch and of the policy branch;
+//             each layer's pre-activation gradient goes to the workspace, dx is written by the first branch and added to by the second (the
+//             same lane owns the same element both times).  d log_std leaves one partial per row tile.
+//             grouped kernel: every weight and bias gradient (one wave per 16 x 64 block of a dW, as four interleaved tiles, reducing over all
+//             rows in row order) and
+//             the sum of the d log_std partials in tile order.
+//   loss      one workgroup: the advantage statistics, then one pass over the rows for the five sums, each thread over its rows in order and the
+//             threads' sums through block_sum.  The backward scales the stored per-row coefficients by dloss.
+// No float atomics and every sum in a fixed order: the same bits on every run.
+#include <math.h>
+#include <string.h>
+
+#include "../../include/m3l_amd.h"
+#include "common.cuh"
+#include "kernels.h"
+
+#define PH_TM 16                 // rows of a tile
+#define PH_MAXW 512              // widest layer / feature vector
+#define PH_MAXA 64               // most action dimensions
+#define PH_HLD 64                // leading dimension of the heads' LDS tiles
+#define PH_MAXLIN 8              // 3 + 3 hidden layers and the two heads
+
+namespace {
+
+struct PhBranch {
+    int n, hn;                   // hidden layers; rows of the head (A or 1)
+    int w[M3L_POLICY_MAX_HIDDEN];
+    const float* W[M3L_POLICY_MAX_HIDDEN];
+    const float* b[M3L_POLICY_MAX_HIDDEN];
+    const float* hw;
+    const float* hb;
+    long h_off[M3L_POLICY_MAX_HIDDEN];       // post-Tanh activations (forward) in the workspace, in floats
+    long d_off[M3L_POLICY_MAX_HIDDEN];       // pre-activation gradients (backward)
+};
+struct PhArgs {
+    int B, F, A, ld;             // ld: leading dimension of the LDS activation buffers, widest vector + 4
+    PhBranch br[2];              // 0 = policy branch + action_net, 1 = value branch + value_net
+    const float* log_std;
+    long mu_off, dmu_off, dv_off, part_off, total;
+};
+
+// one Linear of the grouped weight-gradient launch: dW [N, K] = dY^T X, db [N] = column sums of dY
+struct PhLin {
+    const float* dY;             // [B, N]
+    const float* X;              // [B, K]
+    float* dW;
+    float* db;
+    int N, K, kgroups, item0;    // items: (N tiles of 16) x (K groups of 64), numbered from item0
+};
+struct PhWgrad {
+    PhLin lin[PH_MAXLIN];
+    int count, items, B, A, tiles;
+    const float* part;           // [tiles, PH_MAXA] d log_std partials
+    float* dlog_std;
+};
+
+__device__ __forceinline__ Frag<float> ph_zero_frag() {
+    Frag<float> f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f.v[j] = 0.f;
+    return f;
+}
+// rows of W [N, K] as the k-contiguous operand: lane (i, g) <- W[n0 + i][k0 + 8 g .. + 8), zero outside the matrix
+__device__ __forceinline__ Frag<float> ph_w_kc(const float* __restrict__ W, int N, int K, int n0, int k0, int lane) {
+    const int n = n0 + (lane & 15), k = k0 + 8 * (lane >> 4);
+    if (n < N && k < K) return load_kc(W + (long)n * K + k);
+    return ph_zero_frag();
+}
+// an LDS tile [PH_TM, ld] with `valid` written columns (a multiple of 8): lane (i, g) <- t[i][k0 + 8 g .. + 8)
+__device__ __forceinline__ Frag<float> ph_lds_kc(const float* t, int ld, int valid, int k0, int lane) {
+    const int k = k0 + 8 * (lane >> 4);
+    if (k < valid) return load_kc(t + (lane & 15) * ld + k);
+    return ph_zero_frag();
+}
+
+// out[m][n] = act(sum_k in[m][k] W[n][k] + bias[n]) for the 16 rows of the tile, n < N; in: LDS [16, ldi] with K columns, out: LDS [16, ldo]
+// (every column up to the next multiple of 16 is written, zero past N), gout: global [B, N] rows row0 .. or null.  A wave runs the tiles
+// tb, tb + 4, tb + 8, tb + 12 together: four independent accumulator chains over one LDS fragment, so an MFMA never waits for the one before it.
+template <bool TANH>
+__device__ void ph_fwd_layer(const float* in, int ldi, int K, const float* __restrict__ W, const float* __restrict__ bias, int N, float* out, int ldo,
+                             float* __restrict__ gout, int row0, int B) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+    const int ntiles = (N + 15) >> 4;
+    for (int tb = wave; tb < ntiles; tb += 16) {
+        f32x4 acc[4];
+        Frag<float> wa[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            wa[u] = ph_w_kc(W, N, K, (tb + 4 * u) * 16, 0, lane);            // zero past N: a tile that does not exist loads nothing
+        }
+        for (int k0 = 0; k0 < K; k0 += 32) {
+            Frag<float> wn[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)                                      // the next step's weights fly while this one multiplies
+                wn[u] = (k0 + 32 < K) ? ph_w_kc(W, N, K, (tb + 4 * u) * 16, k0 + 32, lane) : ph_zero_frag();
+            const Frag<float> xb = ph_lds_kc(in, ldi, K, k0, lane);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (tb + 4 * u < ntiles) acc[u] = mma16(wa[u], xb, acc[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) wa[u] = wn[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (tb + 4 * u >= ntiles) continue;
+            // lane (i, g) register r = out[m = i][n0 + 4 g + r]
+            const int nb = (tb + 4 * u) * 16 + 4 * g;
+            f32x4 o;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = 0.f;
+                if (nb + r < N) {
+                    v = acc[u][r] + bias[nb + r];
+                    if (TANH) v = tanhf(v);
+                }
+                o[r] = v;
+            }
+            *reinterpret_cast<f32x4*>(out + i * ldo + nb) = o;
+            if (gout != nullptr && row0 + i < B) {
+                if ((N & 3) == 0) {
+                    *reinterpret_cast<f32x4*>(gout + (long)(row0 + i) * N + nb) = o;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (nb + r < N) gout[(long)(row0 + i) * N + nb + r] = o[r];
+                }
+            }
+        }
+    }
+}
+
+// W [N, K] as the operand whose k index is W's row, for FOUR tiles at once: lane (i, g) reads the 16 bytes W[n0 + 8 g + j][cbase + 4 i .. + 3] and
+// tile u takes column cbase + 4 i + u of them (K is a multiple of 16, so the four columns are inside or outside together)
+__device__ __forceinline__ void ph_w_ks4(const float* __restrict__ W, int N, int K, int n0, int cbase, int lane, Frag<float> (&f)[4]) {
+    const int c = cbase + 4 * (lane & 15), nb = n0 + 8 * (lane >> 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (nb + j < N && c < K) v = *reinterpret_cast<const f32x4*>(W + (long)(nb + j) * K + c);
+        f[0].v[j] = v[0]; f[1].v[j] = v[1]; f[2].v[j] = v[2]; f[3].v[j] = v[3];
+    }
+}
+
+// out[m][c] = (sum_n din[m][n] W[n][c]) * (1 - h[m][c]^2 when TANH), c < K (a multiple of 16); din: LDS [16, ldi] with `valid` columns written;
+// out: LDS [16, ldo] or null; gout: global [B, K] or null (add: the value already there is added, by the lane that wrote it).  A wave owns 64
+// columns, as four interleaved tiles (ph_w_ks4): register r of tile u of lane (i, g) = out[m = i][cbase + 16 g + 4 r + u].
+template <bool TANH>
+__device__ void ph_bwd_layer(const float* din, int ldi, int valid, const float* __restrict__ W, int N, int K, const float* __restrict__ h, float* out, int ldo,
+                             float* gout, bool add, int row0, int B) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+    const int groups = (K + 63) >> 6;
+    const bool live = row0 + i < B;
+    for (int gi = wave; gi < groups; gi += 4) {
+        const int cbase = gi * 64;
+        f32x4 acc[4];
+        Frag<float> wa[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        ph_w_ks4(W, N, K, 0, cbase, lane, wa);
+        for (int n0 = 0; n0 < N; n0 += 32) {
+            Frag<float> wn[4];
+            ph_w_ks4(W, N, K, n0 + 32, cbase, lane, wn);                     // rows past N read as zero
+            const Frag<float> db = ph_lds_kc(din, ldi, valid, n0, lane);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[u] = mma16(wa[u], db, acc[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) wa[u] = wn[u];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int cb = cbase + 16 * g + 4 * r;
+            if (cb >= K) continue;
+            f32x4 o = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+            if (TANH) {
+                f32x4 hv = {0.f, 0.f, 0.f, 0.f};
+                if (live) hv = *reinterpret_cast<const f32x4*>(h + (long)(row0 + i) * K + cb);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] *= 1.f - hv[e] * hv[e];
+            }
+            if (out != nullptr) *reinterpret_cast<f32x4*>(out + i * ldo + cb) = o;
+            if (gout != nullptr && live) {
+                float* p = gout + (long)(row0 + i) * K + cb;
+                if (add) {
+                    const f32x4 prev = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] += prev[e];
+                }
+                *reinterpret_cast<f32x4*>(p) = o;
+            }
+        }
+    }
+}
+
+// rows row0 .. row0 + 15 of x [B, F] into an LDS tile, zero past B
+__device__ void ph_load_x(const float* __restrict__ x, int F, int row0, int B, float* buf, int ld) {
+    const int per = F >> 2;
+    for (int e = threadIdx.x; e < PH_TM * per; e += 256) {
+        const int m = e / per, c = (e - m * per) * 4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (row0 + m < B) v = *reinterpret_cast<const f32x4*>(x + (long)(row0 + m) * F + c);
+        *reinterpret_cast<f32x4*>(buf + m * ld + c) = v;
+    }
+}
+
+#define PH_HALF_LOG_2PI 0.91893853320467274178f
+
+// grid (row tiles, 2).  mode 0: evaluate `actions`; mode 1: act (actions_out = mu + exp(log_std) noise, or mu when noise is null).
+// ws null: no activation is stored (no backward will follow).
+__global__ __launch_bounds__(256) void policy_fwd_kernel(PhArgs p, const float* __restrict__ x, const float* __restrict__ actions, const float* __restrict__ noise,
+                                                         int mode, float* __restrict__ ws, float* __restrict__ actions_out, float* __restrict__ values,
+                                                         float* __restrict__ logp, float* __restrict__ entropy) {
+    extern __shared__ __attribute__((aligned(16))) float ph_lds[];
+    __shared__ __attribute__((aligned(16))) float head[PH_TM * PH_HLD], act[PH_TM * PH_HLD];
+    float* cur = ph_lds;
+    float* nxt = ph_lds + PH_TM * p.ld;
+    const int bi = blockIdx.y, row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B, A = p.A;
+    const PhBranch& br = p.br[bi];
+    ph_load_x(x, p.F, row0, B, cur, p.ld);
+    __syncthreads();
+    int K = p.F;
+    for (int l = 0; l < br.n; ++l) {
+        ph_fwd_layer<true>(cur, p.ld, K, br.W[l], br.b[l], br.w[l], nxt, p.ld, ws ? ws + br.h_off[l] : nullptr, row0, B);
+        __syncthreads();
+        float* s = cur; cur = nxt; nxt = s;
+        K = br.w[l];
+    }
+    ph_fwd_layer<false>(cur, p.ld, K, br.hw, br.hb, br.hn, head, PH_HLD, nullptr, row0, B);
+    __syncthreads();
+    if (bi == 1) {
+        if (tid < PH_TM && row0 + tid < B) values[row0 + tid] = head[tid * PH_HLD];
+        return;
+    }
+    for (int e = tid; e < PH_TM * A; e += 256) {
+        const int m = e / A, j = e - m * A, row = row0 + m;
+        if (row < B) {
+            const float mu = head[m * PH_HLD + j];
+            float a;
+            if (mode == 1) {
+                a = noise ? mu + expf(p.log_std[j]) * noise[(long)row * A + j] : mu;
+                actions_out[(long)row * A + j] = a;
+            } else {
+                a = actions[(long)row * A + j];
+            }
+            act[m * PH_HLD + j] = a;
+            if (ws) ws[p.mu_off + (long)row * A + j] = mu;
+        }
+    }
+    __syncthreads();
+    // the log-probability is formed from the stored (rounded) action by this one piece of code in both modes
+    if (tid < PH_TM && row0 + tid < B) {
+        float lp = 0.f, en = 0.f;
+        for (int j = 0; j < A; ++j) {
+            const float s = p.log_std[j], sd = expf(s), d = act[tid * PH_HLD + j] - head[tid * PH_HLD + j];
+            lp += -(d * d) / (2.f * (sd * sd)) - s - PH_HALF_LOG_2PI;
+            en += 0.5f + PH_HALF_LOG_2PI + s;
+        }
+        logp[row0 + tid] = lp;
+        if (entropy) entropy[row0 + tid] = en;
+    }
+}
+
+// grid (row tiles).  dvalues / dlogp / dentropy: [B] or null (= zero)
+__global__ __launch_bounds__(256) void policy_bwd_chain_kernel(PhArgs p, const float* __restrict__ actions, const float* __restrict__ dvalues,
+                                                               const float* __restrict__ dlogp, const float* __restrict__ dentropy, float* __restrict__ ws,
+                                                               float* __restrict__ dx) {
+    extern __shared__ __attribute__((aligned(16))) float ph_lds[];
+    float* bufa = ph_lds;
+    float* bufb = ph_lds + PH_TM * p.ld;
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B, A = p.A;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int bi = 1 - pass;                  // the value branch first: it writes dx, the policy branch adds to it
+        const PhBranch& br = p.br[bi];
+        float* cur = bufa;
+        float* nxt = bufb;
+        int valid;
+        if (bi == 1) {
+            // d value_net output: [16, 8] with dvalues in column 0
+            if (tid < PH_TM * 8) {
+                const int m = tid >> 3, j = tid & 7, row = row0 + m;
+                float v = 0.f;
+                if (j == 0 && row < B) {
+                    v = dvalues ? dvalues[row] : 0.f;
+                    ws[p.dv_off + row] = v;
+                }
+                cur[m * p.ld + j] = v;
+            }
+            valid = 8;
+        } else {
+            // d mu[m][j] = dlogp_m (a - mu) / sigma_j^2; the rows' terms of d log_std wait in nxt for their sum
+            for (int e = tid; e < PH_TM * PH_MAXA; e += 256) {
+                const int m = e >> 6, j = e & 63, row = row0 + m;
+                float dm = 0.f, term = 0.f;
+                if (j < A && row < B) {
+                    const float sd = expf(p.log_std[j]), iv = 1.f / (sd * sd);
+                    const float d = actions[(long)row * A + j] - ws[p.mu_off + (long)row * A + j];
+                    const float g = dlogp ? dlogp[row] : 0.f;
+                    dm = g * d * iv;
+                    term = g * (d * d * iv - 1.f) + (dentropy ? dentropy[row] : 0.f);
+                    ws[p.dmu_off + (long)row * A + j] = dm;
+                }
+                cur[m * p.ld + j] = dm;
+                nxt[m * p.ld + j] = term;
+            }
+            __syncthreads();
+            if (tid < A) {
+                float s = 0.f;
+                for (int m = 0; m < PH_TM; ++m) s += nxt[m * p.ld + tid];
+                ws[p.part_off + (long)blockIdx.x * PH_MAXA + tid] = s;
+            }
+            valid = (A + 7) & ~7;
+        }
+        __syncthreads();
+        const float* W = br.hw;
+        int N = br.hn;
+        for (int l = br.n - 1; l >= 0; --l) {
+            const int K = br.w[l];
+            ph_bwd_layer<true>(cur, p.ld, valid, W, N, K, ws + br.h_off[l], nxt, p.ld, ws + br.d_off[l], false, row0, B);
+            __syncthreads();
+            float* s = cur; cur = nxt; nxt = s;
+            W = br.W[l];
+            N = K;
+            valid = K;
+        }
+        ph_bwd_layer<false>(cur, p.ld, valid, W, N, p.F, nullptr, nullptr, 0, dx, pass == 1, row0, B);
+        __syncthreads();
+    }
+}
+
+// operands of one 32-row step of a weight gradient: a = dY^T (lane i: column n of dY, rows mb .. mb + 7), b = X for four interleaved tiles (the 16
+// bytes X[row][kc .. kc + 3]: tile t takes column kc + t; K is a multiple of 16, so the four are inside or outside together)
+__device__ __forceinline__ void ph_wgrad_load(const PhLin& L, int B, int n, int kc, int mb, Frag<float>& a, Frag<float> (&b)[4]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const bool in = mb + j < B;
+        a.v[j] = (in && n < L.N) ? L.dY[(long)(mb + j) * L.N + n] : 0.f;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (in && kc < L.K) v = *reinterpret_cast<const f32x4*>(L.X + (long)(mb + j) * L.K + kc);
+        b[0].v[j] = v[0]; b[1].v[j] = v[1]; b[2].v[j] = v[2]; b[3].v[j] = v[3];
+    }
+}
+
+// grid (cdiv(items, 4) + 1): wave w of block b takes item 4 b + w; the last block sums the d log_std partials
+__global__ __launch_bounds__(256) void policy_wgrad_kernel(PhWgrad q) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
+    if (blockIdx.x == gridDim.x - 1) {
+        if (tid < q.A) {
+            float s = 0.f;
+            for (int t = 0; t < q.tiles; ++t) s += q.part[(long)t * PH_MAXA + tid];
+            q.dlog_std[tid] = s;
+        }
+        return;
+    }
+    const int item = blockIdx.x * 4 + wave;
+    if (item >= q.items) return;                  // a whole wave leaves: the lanes that stay are all active
+    int li = 0;
+    while (li + 1 < q.count && item >= q.lin[li + 1].item0) ++li;
+    const PhLin& L = q.lin[li];
+    const int local = item - L.item0, nt = local / L.kgroups, kg = local - nt * L.kgroups;
+    const int n0 = nt * 16, kbase = kg * 64, N = L.N, K = L.K, B = q.B;
+    const int n = n0 + i, kc = kbase + 4 * i;    // this lane's row of dY^T; its four columns of X and dW (tile t takes column kc + t)
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum = 0.f;
+    Frag<float> a, b[4];
+    ph_wgrad_load(L, B, n, kc, 8 * g, a, b);
+    for (int m0 = 0; m0 < B; m0 += 32) {
+        Frag<float> an, bn[4];
+        ph_wgrad_load(L, B, n, kc, m0 + 32 + 8 * g, an, bn);                 // rows past B read as zero
+#pragma unroll
+        for (int j = 0; j < 8; ++j) bsum += a.v[j];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = mma16(a, b[t], acc[t]);
+        a = an;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) b[t] = bn[t];
+    }
+    // register r of tile t of lane (i, g) = dW[n0 + 4 g + r][kc + t]
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (n0 + 4 * g + r < N && kc < K) *reinterpret_cast<f32x4*>(L.dW + (long)(n0 + 4 * g + r) * K + kc) = f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+    bsum = xor32_sum(xor16_sum(bsum));            // the four lane groups hold the four quarters of the rows
+    if (kg == 0 && g == 0 && n < N) L.db[n] = bsum;
+}
+
+// one workgroup of 256 threads
+__device__ __forceinline__ float ph_block_sum(float v, float* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+}
+__global__ __launch_bounds__(256) void ppo_loss_kernel(const float* __restrict__ logp, const float* __restrict__ values, const float* __restrict__ entropy,
+                                                       const float* __restrict__ old_logp, const float* __restrict__ adv, const float* __restrict__ returns,
+                                                       const float* __restrict__ old_values, int B, float clip, float clip_vf, float ent_coef, float vf_coef,
+                                                       int normalize, float* __restrict__ loss, float* __restrict__ stats, float* __restrict__ c_logp,
+                                                       float* __restrict__ c_v) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const float invB = 1.f / (float)B;
+    float mean = 0.f, den = 1.f;
+    const bool norm = normalize && B > 1;
+    if (norm) {
+        float s = 0.f;
+        for (int r = tid; r < B; r += 256) s += adv[r];
+        mean = ph_block_sum(s, red) * invB;
+        float ss = 0.f;
+        for (int r = tid; r < B; r += 256) {
+            const float d = adv[r] - mean;
+            ss += d * d;
+        }
+        den = sqrtf(ph_block_sum(ss, red) / (float)(B - 1)) + 1e-8f;
+    }
+    const float lo = 1.f - clip, hi = 1.f + clip;
+    float pg = 0.f, vl = 0.f, en = 0.f, cf = 0.f, kl = 0.f;
+    for (int r = tid; r < B; r += 256) {
+        const float ah = norm ? (adv[r] - mean) / den : adv[r];
+        const float d = logp[r] - old_logp[r], ratio = expf(d);
+        const float p1 = ah * ratio, p2 = ah * fminf(fmaxf(ratio, lo), hi);
+        pg += fminf(p1, p2);
+        c_logp[r] = (p1 <= p2) ? -p1 * invB : 0.f;
+        cf += (fabsf(ratio - 1.f) > clip) ? 1.f : 0.f;
+        kl += expm1f(d) - d;
+        const float v = values[r];
+        float vp = v;
+        bool open = true;
+        if (old_values != nullptr) {
+            const float dv = v - old_values[r];
+            vp = old_values[r] + fminf(fmaxf(dv, -clip_vf), clip_vf);
+            open = fabsf(dv) <= clip_vf;
+        }
+        const float e = vp - returns[r];
+        vl += e * e;
+        c_v[r] = open ? vf_coef * 2.f * e * invB : 0.f;
+        en += entropy[r];
+    }
+    pg = ph_block_sum(pg, red);
+    vl = ph_block_sum(vl, red);
+    en = ph_block_sum(en, red);
+    cf = ph_block_sum(cf, red);
+    kl = ph_block_sum(kl, red);
+    if (tid == 0) {
+        const float policy_loss = -(pg * invB), value_loss = vl * invB, entropy_loss = -(en * invB);
+        stats[0] = policy_loss;
+        stats[1] = value_loss;
+        stats[2] = entropy_loss;
+        stats[3] = cf / (float)B;
+        stats[4] = kl * invB;
+        loss[0] = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss;
+    }
+}
+__global__ __launch_bounds__(256) void ppo_loss_bwd_kernel(const float* __restrict__ dloss, const float* __restrict__ c_logp, const float* __restrict__ c_v, int B,
+                                                           float ent_coef, float* __restrict__ dlogp, float* __restrict__ dvalues, float* __restrict__ dentropy) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= B) return;
+    const float g = dloss[0];
+    dlogp[r] = g * c_logp[r];
+    dvalues[r] = g * c_v[r];
+    dentropy[r] = g * -(ent_coef / (float)B);
+}
+
+long ph_round4(long v) { return (v + 3) & ~3L; }
+
+bool ph_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the limits of the header; 0 and a message when the head is outside them
+int ph_shape_ok(const m3l_policy_desc* d, int B, char* why, size_t n) {
+    if (d == nullptr) { snprintf(why, n, "null descriptor"); return 0; }
+    if (B < 1) { snprintf(why, n, "B=%d (B >= 1)", B); return 0; }
+    if (d->features < 16 || d->features % 16 || d->features > PH_MAXW) {
+        snprintf(why, n, "features=%d (a multiple of 16, at most %d)", d->features, PH_MAXW);
+        return 0;
+    }
+    if (d->actions < 1 || d->actions > PH_MAXA) { snprintf(why, n, "actions=%d (1 <= A <= %d)", d->actions, PH_MAXA); return 0; }
+    if (d->n_pi < 0 || d->n_pi > M3L_POLICY_MAX_HIDDEN || d->n_vf < 0 || d->n_vf > M3L_POLICY_MAX_HIDDEN) {
+        snprintf(why, n, "%d / %d hidden layers (0 to %d per branch)", d->n_pi, d->n_vf, M3L_POLICY_MAX_HIDDEN);
+        return 0;
+    }
+    for (int l = 0; l < d->n_pi + d->n_vf; ++l) {
+        const int w = l < d->n_pi ? d->pi_width[l] : d->vf_width[l - d->n_pi];
+        if (w < 16 || w % 16 || w > PH_MAXW) { snprintf(why, n, "hidden width %d (a multiple of 16, at most %d)", w, PH_MAXW); return 0; }
+    }
+    if ((long)B * PH_MAXW >= 2147483647L / 4) { snprintf(why, n, "B=%d rows are more than the kernels index", B); return 0; }
+    return 1;
+}
+
+// kernel arguments and workspace layout of a head; with_params = 0 only sizes the workspace
+PhArgs ph_args(const m3l_policy_desc* d, int B, int with_params) {
+    PhArgs p;
+    memset(&p, 0, sizeof(p));
+    p.B = B;
+    p.F = d->features;
+    p.A = d->actions;
+    int widest = d->features > PH_MAXA ? d->features : PH_MAXA;      // the heads' gradient tiles are PH_MAXA columns wide
+    long off = 0;
+    for (int bi = 0; bi < 2; ++bi) {
+        PhBranch& b = p.br[bi];
+        b.n = bi == 0 ? d->n_pi : d->n_vf;
+        b.hn = bi == 0 ? d->actions : 1;
+        for (int l = 0; l < b.n; ++l) {
+            b.w[l] = bi == 0 ? d->pi_width[l] : d->vf_width[l];
+            if (b.w[l] > widest) widest = b.w[l];
+            if (with_params) {
+                b.W[l] = bi == 0 ? d->pi_weight[l] : d->vf_weight[l];
+                b.b[l] = bi == 0 ? d->pi_bias[l] : d->vf_bias[l];
+            }
+            b.h_off[l] = off;
+            off += (long)B * b.w[l];
+            b.d_off[l] = off;
+            off += (long)B * b.w[l];
+        }
+        if (with_params) {
+            b.hw = bi == 0 ? d->action_weight : d->value_weight;
+            b.hb = bi == 0 ? d->action_bias : d->value_bias;
+        }
+    }
+    p.ld = widest + 4;
+    p.log_std = with_params ? d->log_std : nullptr;
+    p.mu_off = off;
+    off = ph_round4(off + (long)B * p.A);
+    p.dmu_off = off;
+    off = ph_round4(off + (long)B * p.A);
+    p.dv_off = off;
+    off = ph_round4(off + B);
+    p.part_off = off;
+    off += (long)cdiv(B, PH_TM) * PH_MAXA;
+    p.total = off;
+    return p;
+}
+
+int ph_params_ok(const m3l_policy_desc* d, const char* who) {
+    int ok = d->action_weight && d->action_bias && d->value_weight && d->value_bias && d->log_std && ph_aligned(d->action_weight) &&
+             ph_aligned(d->value_weight);
+    for (int l = 0; l < d->n_pi; ++l) ok = ok && d->pi_weight[l] && d->pi_bias[l] && ph_aligned(d->pi_weight[l]);
+    for (int l = 0; l < d->n_vf; ++l) ok = ok && d->vf_weight[l] && d->vf_bias[l] && ph_aligned(d->vf_weight[l]);
+    M3L_CHECK(ok, "%s: a parameter pointer of the descriptor is null or a weight is not 16-byte aligned", who);
+    return 0;
+}
+
+int g_policy_inited = 0;
+#define PH_LDS_MAX (2 * PH_TM * (PH_MAXW + 4) * 4)
+int ph_init() {
+    if (g_policy_inited) return 0;
+    M3L_HIP(hipFuncSetAttribute((const void*)policy_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_MAX));
+    M3L_HIP(hipFuncSetAttribute((const void*)policy_bwd_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_MAX));
+    g_policy_inited = 1;
+    return 0;
+}
+
+int ph_forward(const char* who, const m3l_policy_desc* d, int B, const float* x, const float* actions, const float* noise, int mode, void* ws,
+               float* actions_out, float* values, float* logp, float* entropy, void* stream) {
+    char why[160];
+    M3L_CHECK(ph_shape_ok(d, B, why, sizeof(why)), "%s: unsupported shape: %s", who, why);
+    if (ph_params_ok(d, who)) return 1;
+    M3L_CHECK(x && values && logp && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "%s: null argument, or x / ws not 16-byte aligned", who);
+    if (ph_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const PhArgs p = ph_args(d, B, 1);
+    double fl = 0;
+    for (int bi = 0; bi < 2; ++bi) {
+        int K = p.F;
+        for (int l = 0; l < p.br[bi].n; ++l) { fl += 2.0 * B * K * p.br[bi].w[l]; K = p.br[bi].w[l]; }
+        fl += 2.0 * B * K * p.br[bi].hn;
+    }
+    ProfScope prof(who, B, p.F, p.A, fl, st, 4.0 * B * p.F);
+    policy_fwd_kernel<<<dim3(cdiv(B, PH_TM), 2), 256, (size_t)2 * PH_TM * p.ld * 4, st>>>(p, x, actions, noise, mode, (float*)ws, actions_out, values, logp,
+                                                                                         entropy);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t m3l_policy_ws_bytes(const m3l_policy_desc* d, int B) {
+    char why[160];
+    if (!ph_shape_ok(d, B, why, sizeof(why))) return 256;
+    return (size_t)ph_args(d, B, 0).total * sizeof(float);
+}
+
+int m3l_policy_act(const m3l_policy_desc* d, int B, const float* x, const float* noise, float* actions, float* values, float* logp, void* stream) {
+    M3L_CHECK(actions != nullptr, "policy_act: null argument");
+    return ph_forward("policy_act", d, B, x, nullptr, noise, 1, nullptr, actions, values, logp, nullptr, stream);
+}
+
+int m3l_policy_eval_fwd(const m3l_policy_desc* d, int B, const float* x, const float* actions, void* ws, float* values, float* logp, float* entropy,
+                        void* stream) {
+    M3L_CHECK(actions != nullptr && entropy != nullptr, "policy_eval_fwd: null argument");
+    return ph_forward("policy_eval_fwd", d, B, x, actions, nullptr, 0, ws, nullptr, values, logp, entropy, stream);
+}
+
+int m3l_policy_eval_bwd(const m3l_policy_desc* d, int B, const float* x, const float* actions, const float* dvalues, const float* dlogp, const float* dentropy,
+                        void* ws, float* dx, const m3l_policy_desc* grads, void* stream) {
+    char why[160];
+    M3L_CHECK(ph_shape_ok(d, B, why, sizeof(why)), "policy_eval_bwd: unsupported shape: %s", why);
+    if (ph_params_ok(d, "policy_eval_bwd")) return 1;
+    M3L_CHECK(grads != nullptr && grads->n_pi == d->n_pi && grads->n_vf == d->n_vf, "policy_eval_bwd: the gradient descriptor is null or has other layer counts");
+    if (ph_params_ok(grads, "policy_eval_bwd (gradients)")) return 1;
+    M3L_CHECK(x && actions && ws && dx && ph_aligned(x) && ph_aligned(ws) && ph_aligned(dx), "policy_eval_bwd: null argument, or x / ws / dx not 16-byte aligned");
+    if (ph_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const PhArgs p = ph_args(d, B, 1);
+    float* w = (float*)ws;
+    PhWgrad q;
+    memset(&q, 0, sizeof(q));
+    int items = 0;
+    double fl = 0;
+    for (int bi = 0; bi < 2; ++bi) {
+        const PhBranch& b = p.br[bi];
+        const float* X = x;
+        int K = p.F;
+        for (int l = 0; l <= b.n; ++l) {
+            PhLin& L = q.lin[q.count++];
+            const bool head = l == b.n;
+            L.dY = head ? (bi == 0 ? w + p.dmu_off : w + p.dv_off) : w + b.d_off[l];
+            L.X = X;
+            L.N = head ? b.hn : b.w[l];
+            L.K = K;
+            if (bi == 0) {
+                L.dW = head ? grads->action_weight : grads->pi_weight[l];
+                L.db = head ? grads->action_bias : grads->pi_bias[l];
+            } else {
+                L.dW = head ? grads->value_weight : grads->vf_weight[l];
+                L.db = head ? grads->value_bias : grads->vf_bias[l];
+            }
+            L.kgroups = cdiv(K, 64);
+            L.item0 = items;
+            items += cdiv(L.N, 16) * L.kgroups;
+            fl += 2.0 * B * L.N * K;
+            if (!head) {
+                X = w + b.h_off[l];
+                K = b.w[l];
+            }
+        }
+    }
+    q.items = items;
+    q.B = B;
+    q.A = p.A;
+    q.tiles = cdiv(B, PH_TM);
+    q.part = w + p.part_off;
+    q.dlog_std = grads->log_std;
+    {
+        ProfScope prof("policy_bwd_chain", B, p.F, p.A, fl, st, 4.0 * B * p.F);
+        policy_bwd_chain_kernel<<<cdiv(B, PH_TM), 256, (size_t)2 * PH_TM * p.ld * 4, st>>>(p, actions, dvalues, dlogp, dentropy, w, dx);
+        M3L_LAUNCH_CHECK();
+    }
+    {
+        ProfScope prof("policy_wgrad", B, items, p.A, fl, st, 0.0);
+        policy_wgrad_kernel<<<cdiv(items, 4) + 1, 256, 0, st>>>(q);
+        M3L_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int m3l_policy_ppo_loss_fwd(const float* logp, const float* values, const float* entropy, const float* old_logp, const float* advantages, const float* returns,
+                            const float* old_values, int B, float clip_range, float clip_range_vf, float ent_coef, float vf_coef, int normalize_advantage,
+                            float* loss, float* stats, float* coef_logp, float* coef_values, void* stream) {
+    M3L_CHECK(B >= 1, "policy_ppo_loss_fwd: B=%d (B >= 1)", B);
+    M3L_CHECK(logp && values && entropy && old_logp && advantages && returns && loss && stats && coef_logp && coef_values, "policy_ppo_loss_fwd: null argument");
+    M3L_CHECK(clip_range >= 0.f, "policy_ppo_loss_fwd: clip_range %g is negative", clip_range);
+    M3L_CHECK((old_values == nullptr) == (clip_range_vf < 0.f), "policy_ppo_loss_fwd: old_values goes with a clip_range_vf >= 0, null with a negative one");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("policy_ppo_loss_fwd", B, 0, 0, 40.0 * B, st, 40.0 * B);
+    ppo_loss_kernel<<<1, 256, 0, st>>>(logp, values, entropy, old_logp, advantages, returns, old_values, B, clip_range, clip_range_vf, ent_coef, vf_coef,
+                                       normalize_advantage, loss, stats, coef_logp, coef_values);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_policy_ppo_loss_bwd(const float* dloss, const float* coef_logp, const float* coef_values, int B, float ent_coef, float* dlogp, float* dvalues,
+                            float* dentropy, void* stream) {
+    M3L_CHECK(B >= 1, "policy_ppo_loss_bwd: B=%d (B >= 1)", B);
+    M3L_CHECK(dloss && coef_logp && coef_values && dlogp && dvalues && dentropy, "policy_ppo_loss_bwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("policy_ppo_loss_bwd", B, 0, 0, 3.0 * B, st, 20.0 * B);
+    ppo_loss_bwd_kernel<<<cdiv(B, 256), 256, 0, st>>>(dloss, coef_logp, coef_values, B, ent_coef, dlogp, dvalues, dentropy);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
