@@ -660,6 +660,73 @@ int m3l_policy_ppo_loss_fwd(const float* logp, const float* values, const float*
 int m3l_policy_ppo_loss_bwd(const float* dloss, const float* coef_logp, const float* coef_values, int B, float ent_coef, float* dlogp, float* dvalues,
                             float* dentropy, void* stream);
 
+/* ---- SAC policy head (ABI 410): everything behind the extractor's features in one gradient step of SAC_MAE.train (models/sac_mae.py:303-366).
+ * The head is Stable-Baselines3's SACPolicy as MAESACPolicy configures it: nn.ReLU, n_critics = 2, share_features_extractor = True,
+ * use_sde = False.  SB3 is not part of the reference tree, so the head's arithmetic is stated here, not quoted; the loss lines are the
+ * reference's.  float32 throughout.  With x [B, F], a standard-normal draw noise [B, A]:
+ *   actor   h = latent_pi(x) (Linear + ReLU pairs);  mu = Linear(h);  s = clamp(Linear(h), -20, 2), gradient 1 on the closed interval, 0 outside
+ *           u = mu + exp(s) noise;  a = tanh(u)  (noise NULL: the deterministic action tanh(mu))
+ *           logp_i = sum_j ( -(u - mu)^2 / (2 exp(s)^2) - s - 1/2 ln 2 pi ) - sum_j ln(1 - a_j^2 + 1e-6)
+ *           The kernels form (u - mu)^2 / (2 exp(s)^2) as noise^2 / 2 and 1 - a^2 as om = 4 e / (1 + e)^2, e = exp(-2 |u|): the same functions
+ *           without float32 cancellation (naive: up to 8e-4 of max(1, |logp|); this form: 5e-6).  d logp / d u = 2 a om / (om + 1e-6).
+ *   critic  q_c = Linear(qf_c(cat([x, a], dim 1)), 1) for c in {0, 1}, each qf_c Linear + ReLU pairs; the first weight is [N, F + A] row-major,
+ *           torch's layout, taken as it is (its rows are only 4-byte aligned).  x enters detached: the critics produce d actions and parameter
+ *           gradients, never dx.
+ *   step    ent_coef = exp(log_ent_coef);  ent_coef_loss = -mean(log_ent_coef (logp + target_entropy)), logp a constant            :311-312
+ *           target_q = r + (1 - done) gamma (min_c q_target_c(x', a') - ent_coef logp'),  (a', logp') = actor(x')                    :326-335
+ *           critic_loss = 0.5 sum_c mean (q_c(x, a_replay) - target_q)^2                                                           :339-342
+ *           actor_loss = mean(ent_coef logp - min_c q_c(x, a_pi)); the smaller critic takes the row's gradient (critic 0 when equal) :354-356
+ *           polyak: m3l_op_ema with beta = 1 - tau                                                                                  :365-366
+ * ent_coef reaches td_target and actor_loss_fwd as a float, or, when log_ent_coef is not NULL, as a device pointer whose exp the kernel takes:
+ * a step needs no host read.
+ * Launches: actor_fwd 1; actor_bwd 2 (chain per row tile of 16, grouped weight gradients); critic_fwd 1 (grid: row tiles x 2 critics);
+ * critic_bwd 1 (chain: d actions, critic 1 adding to critic 0) + 1 grouped weight-gradient launch when `grads` is not NULL; td_target 1 (actor
+ * and both critics of a row tile in one workgroup, a' handed on in LDS); each loss 1 forward and 1 backward (ent_coef_loss: the same entry
+ * again with dloss).  No float atomics, every sum in a fixed order: two runs give the same bits.
+ * Limits: B >= 1; F and every hidden width a multiple of 16, at most 512; 0 to 3 hidden layers per net, the two critics alike; 1 <= A <= 64;
+ * x, the weights, ws and dx 16-byte aligned.  Anything else is an error and nothing is written.
+ * Layouts are torch.nn.Linear's.  An entry reads only its part of the descriptor (actor entries the actor's pointers, critic entries the
+ * critics', td_target both: pass the target critics there).  Gradients go to a second descriptor whose pointers name the gradient buffers.
+ * ws: m3l_sac_ws_bytes bytes, one workspace per forward that a backward follows (actor and critic parts do not overlap). */
+#define M3L_SAC_MAX_HIDDEN 3
+typedef struct m3l_sac_desc {
+    int features, actions;                    /* F, A */
+    int n_pi, n_qf;                           /* hidden layers of latent_pi / of each critic */
+    int pi_width[M3L_SAC_MAX_HIDDEN], qf_width[M3L_SAC_MAX_HIDDEN];
+    float* pi_weight[M3L_SAC_MAX_HIDDEN];
+    float* pi_bias[M3L_SAC_MAX_HIDDEN];
+    float* mu_weight;                         /* [A, last pi width or F] */
+    float* mu_bias;
+    float* log_std_weight;                    /* [A, last pi width or F] */
+    float* log_std_bias;
+    float* qf_weight[2][M3L_SAC_MAX_HIDDEN];  /* [c][0]: [qf_width[0], F + A] */
+    float* qf_bias[2][M3L_SAC_MAX_HIDDEN];
+    float* q_weight[2];                       /* [1, last qf width or F + A] */
+    float* q_bias[2];
+} m3l_sac_desc;
+size_t m3l_sac_ws_bytes(const m3l_sac_desc* head, int B);
+/* actions [B, A] and logp [B] are written; noise [B, A] or NULL (deterministic); ws NULL when no backward follows */
+int m3l_sac_actor_fwd(const m3l_sac_desc* head, int B, const float* x, const float* noise, void* ws, float* actions, float* logp, void* stream);
+/* dactions [B, A], dlogp [B]: NULL = zero; dx [B, F] and the actor's buffers of `grads` are overwritten */
+int m3l_sac_actor_bwd(const m3l_sac_desc* head, int B, const float* x, const float* noise, const float* dactions, const float* dlogp, void* ws,
+                      float* dx, const m3l_sac_desc* grads, void* stream);
+/* q [2, B] is written */
+int m3l_sac_critic_fwd(const m3l_sac_desc* head, int B, const float* x, const float* actions, void* ws, float* q, void* stream);
+/* dq [2, B]: NULL = zero; dactions [B, A] or NULL (not wanted); grads NULL: no parameter gradient, the weight-gradient launch is skipped */
+int m3l_sac_critic_bwd(const m3l_sac_desc* head, int B, const float* dq, void* ws, float* dactions, const m3l_sac_desc* grads, void* stream);
+/* target_q [B] is written; rewards, dones [B]; the descriptor's critics are the target critics */
+int m3l_sac_td_target(const m3l_sac_desc* head, int B, const float* x_next, const float* noise, const float* rewards, const float* dones, float gamma,
+                      float ent_coef, const float* log_ent_coef, float* target_q, void* stream);
+/* loss[1] and coef [2, B] = dloss/dq are written; the backward writes dq [2, B] = dloss[0] coef (dloss: device scalar) */
+int m3l_sac_critic_loss_fwd(const float* q, const float* target_q, int B, float* loss, float* coef, void* stream);
+int m3l_sac_critic_loss_bwd(const float* dloss, const float* coef, int B, float* dq, void* stream);
+/* loss[1] and coef [3, B] = dloss/dlogp [B] then dloss/dq [2, B] are written; the backward writes dlogp_dq [3, B] in the same order */
+int m3l_sac_actor_loss_fwd(const float* logp, const float* q, int B, float ent_coef, const float* log_ent_coef, float* loss, float* coef, void* stream);
+int m3l_sac_actor_loss_bwd(const float* dloss, const float* coef, int B, float* dlogp_dq, void* stream);
+/* loss[1], ent_coef[1], dlog_ent_coef[1] = -dloss[0] mean(logp + target_entropy): each written when not NULL; dloss NULL = 1 */
+int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float target_entropy, int B, const float* dloss, float* loss, float* ent_coef,
+                          float* dlog_ent_coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,13 @@ class PolicyDesc(C.Structure):
                 ("action_weight", c_p), ("action_bias", c_p), ("value_weight", c_p), ("value_bias", c_p), ("log_std", c_p)]
 
 
+class SacDesc(C.Structure):
+    """m3l_sac_desc: widths, layer counts and device pointers of a SAC actor and its twin critics (include/m3l_amd.h "SAC policy head")."""
+    _fields_ = [("features", c_i), ("actions", c_i), ("n_pi", c_i), ("n_qf", c_i), ("pi_width", c_i * 3), ("qf_width", c_i * 3),
+                ("pi_weight", c_p * 3), ("pi_bias", c_p * 3), ("mu_weight", c_p), ("mu_bias", c_p), ("log_std_weight", c_p), ("log_std_bias", c_p),
+                ("qf_weight", (c_p * 3) * 2), ("qf_bias", (c_p * 3) * 2), ("q_weight", c_p * 2), ("q_bias", c_p * 2)]
+
+
 _SIGS = {
     "m3l_version": (c_i, []),
     "m3l_last_error": (c_i, [C.c_char_p, c_sz]),
@@ -200,6 +207,17 @@ _SIGS = {
     "m3l_policy_eval_bwd": (c_i, [C.POINTER(PolicyDesc), c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(PolicyDesc), c_p]),
     "m3l_policy_ppo_loss_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, C.c_float, C.c_float, C.c_float, C.c_float, c_i, c_p, c_p, c_p, c_p, c_p]),
     "m3l_policy_ppo_loss_bwd": (c_i, [c_p, c_p, c_p, c_i, C.c_float, c_p, c_p, c_p, c_p]),
+    "m3l_sac_ws_bytes": (c_sz, [C.POINTER(SacDesc), c_i]),
+    "m3l_sac_actor_fwd": (c_i, [C.POINTER(SacDesc), c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_sac_actor_bwd": (c_i, [C.POINTER(SacDesc), c_i, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(SacDesc), c_p]),
+    "m3l_sac_critic_fwd": (c_i, [C.POINTER(SacDesc), c_i, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_sac_critic_bwd": (c_i, [C.POINTER(SacDesc), c_i, c_p, c_p, c_p, C.POINTER(SacDesc), c_p]),
+    "m3l_sac_td_target": (c_i, [C.POINTER(SacDesc), c_i, c_p, c_p, c_p, c_p, C.c_float, C.c_float, c_p, c_p, c_p]),
+    "m3l_sac_critic_loss_fwd": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p]),
+    "m3l_sac_critic_loss_bwd": (c_i, [c_p, c_p, c_i, c_p, c_p]),
+    "m3l_sac_actor_loss_fwd": (c_i, [c_p, c_p, c_i, C.c_float, c_p, c_p, c_p, c_p]),
+    "m3l_sac_actor_loss_bwd": (c_i, [c_p, c_p, c_i, c_p, c_p]),
+    "m3l_sac_ent_coef_loss": (c_i, [c_p, c_p, C.c_float, c_i, c_p, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

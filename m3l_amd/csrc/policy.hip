@@ -14,18 +14,14 @@
 //   loss      one workgroup: the advantage statistics, then one pass over the rows for the five sums, each thread over its rows in order and the
 //             threads' sums through block_sum.  The backward scales the stored per-row coefficients by dloss.
 // No float atomics and every sum in a fixed order: the same bits on every run.
+// The layer, operand and weight-gradient pieces are policy_common.cuh's, shared with the SAC head (sac.hip); the activation here is Tanh.
 #include <math.h>
 #include <string.h>
 
 #include "../../include/m3l_amd.h"
 #include "common.cuh"
 #include "kernels.h"
-
-#define PH_TM 16                 // rows of a tile
-#define PH_MAXW 512              // widest layer / feature vector
-#define PH_MAXA 64               // most action dimensions
-#define PH_HLD 64                // leading dimension of the heads' LDS tiles
-#define PH_MAXLIN 8              // 3 + 3 hidden layers and the two heads
+#include "policy_common.cuh"
 
 namespace {
 
@@ -46,169 +42,12 @@ struct PhArgs {
     long mu_off, dmu_off, dv_off, part_off, total;
 };
 
-// one Linear of the grouped weight-gradient launch: dW [N, K] = dY^T X, db [N] = column sums of dY
-struct PhLin {
-    const float* dY;             // [B, N]
-    const float* X;              // [B, K]
-    float* dW;
-    float* db;
-    int N, K, kgroups, item0;    // items: (N tiles of 16) x (K groups of 64), numbered from item0
-};
 struct PhWgrad {
     PhLin lin[PH_MAXLIN];
     int count, items, B, A, tiles;
     const float* part;           // [tiles, PH_MAXA] d log_std partials
     float* dlog_std;
 };
-
-__device__ __forceinline__ Frag<float> ph_zero_frag() {
-    Frag<float> f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f.v[j] = 0.f;
-    return f;
-}
-// rows of W [N, K] as the k-contiguous operand: lane (i, g) <- W[n0 + i][k0 + 8 g .. + 8), zero outside the matrix
-__device__ __forceinline__ Frag<float> ph_w_kc(const float* __restrict__ W, int N, int K, int n0, int k0, int lane) {
-    const int n = n0 + (lane & 15), k = k0 + 8 * (lane >> 4);
-    if (n < N && k < K) return load_kc(W + (long)n * K + k);
-    return ph_zero_frag();
-}
-// an LDS tile [PH_TM, ld] with `valid` written columns (a multiple of 8): lane (i, g) <- t[i][k0 + 8 g .. + 8)
-__device__ __forceinline__ Frag<float> ph_lds_kc(const float* t, int ld, int valid, int k0, int lane) {
-    const int k = k0 + 8 * (lane >> 4);
-    if (k < valid) return load_kc(t + (lane & 15) * ld + k);
-    return ph_zero_frag();
-}
-
-// out[m][n] = act(sum_k in[m][k] W[n][k] + bias[n]) for the 16 rows of the tile, n < N; in: LDS [16, ldi] with K columns, out: LDS [16, ldo]
-// (every column up to the next multiple of 16 is written, zero past N), gout: global [B, N] rows row0 .. or null.  A wave runs the tiles
-// tb, tb + 4, tb + 8, tb + 12 together: four independent accumulator chains over one LDS fragment, so an MFMA never waits for the one before it.
-template <bool TANH>
-__device__ void ph_fwd_layer(const float* in, int ldi, int K, const float* __restrict__ W, const float* __restrict__ bias, int N, float* out, int ldo,
-                             float* __restrict__ gout, int row0, int B) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
-    const int ntiles = (N + 15) >> 4;
-    for (int tb = wave; tb < ntiles; tb += 16) {
-        f32x4 acc[4];
-        Frag<float> wa[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            wa[u] = ph_w_kc(W, N, K, (tb + 4 * u) * 16, 0, lane);            // zero past N: a tile that does not exist loads nothing
-        }
-        for (int k0 = 0; k0 < K; k0 += 32) {
-            Frag<float> wn[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)                                      // the next step's weights fly while this one multiplies
-                wn[u] = (k0 + 32 < K) ? ph_w_kc(W, N, K, (tb + 4 * u) * 16, k0 + 32, lane) : ph_zero_frag();
-            const Frag<float> xb = ph_lds_kc(in, ldi, K, k0, lane);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (tb + 4 * u < ntiles) acc[u] = mma16(wa[u], xb, acc[u]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) wa[u] = wn[u];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (tb + 4 * u >= ntiles) continue;
-            // lane (i, g) register r = out[m = i][n0 + 4 g + r]
-            const int nb = (tb + 4 * u) * 16 + 4 * g;
-            f32x4 o;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = 0.f;
-                if (nb + r < N) {
-                    v = acc[u][r] + bias[nb + r];
-                    if (TANH) v = tanhf(v);
-                }
-                o[r] = v;
-            }
-            *reinterpret_cast<f32x4*>(out + i * ldo + nb) = o;
-            if (gout != nullptr && row0 + i < B) {
-                if ((N & 3) == 0) {
-                    *reinterpret_cast<f32x4*>(gout + (long)(row0 + i) * N + nb) = o;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (nb + r < N) gout[(long)(row0 + i) * N + nb + r] = o[r];
-                }
-            }
-        }
-    }
-}
-
-// W [N, K] as the operand whose k index is W's row, for FOUR tiles at once: lane (i, g) reads the 16 bytes W[n0 + 8 g + j][cbase + 4 i .. + 3] and
-// tile u takes column cbase + 4 i + u of them (K is a multiple of 16, so the four columns are inside or outside together)
-__device__ __forceinline__ void ph_w_ks4(const float* __restrict__ W, int N, int K, int n0, int cbase, int lane, Frag<float> (&f)[4]) {
-    const int c = cbase + 4 * (lane & 15), nb = n0 + 8 * (lane >> 4);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (nb + j < N && c < K) v = *reinterpret_cast<const f32x4*>(W + (long)(nb + j) * K + c);
-        f[0].v[j] = v[0]; f[1].v[j] = v[1]; f[2].v[j] = v[2]; f[3].v[j] = v[3];
-    }
-}
-
-// out[m][c] = (sum_n din[m][n] W[n][c]) * (1 - h[m][c]^2 when TANH), c < K (a multiple of 16); din: LDS [16, ldi] with `valid` columns written;
-// out: LDS [16, ldo] or null; gout: global [B, K] or null (add: the value already there is added, by the lane that wrote it).  A wave owns 64
-// columns, as four interleaved tiles (ph_w_ks4): register r of tile u of lane (i, g) = out[m = i][cbase + 16 g + 4 r + u].
-template <bool TANH>
-__device__ void ph_bwd_layer(const float* din, int ldi, int valid, const float* __restrict__ W, int N, int K, const float* __restrict__ h, float* out, int ldo,
-                             float* gout, bool add, int row0, int B) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
-    const int groups = (K + 63) >> 6;
-    const bool live = row0 + i < B;
-    for (int gi = wave; gi < groups; gi += 4) {
-        const int cbase = gi * 64;
-        f32x4 acc[4];
-        Frag<float> wa[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        ph_w_ks4(W, N, K, 0, cbase, lane, wa);
-        for (int n0 = 0; n0 < N; n0 += 32) {
-            Frag<float> wn[4];
-            ph_w_ks4(W, N, K, n0 + 32, cbase, lane, wn);                     // rows past N read as zero
-            const Frag<float> db = ph_lds_kc(din, ldi, valid, n0, lane);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] = mma16(wa[u], db, acc[u]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) wa[u] = wn[u];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int cb = cbase + 16 * g + 4 * r;
-            if (cb >= K) continue;
-            f32x4 o = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
-            if (TANH) {
-                f32x4 hv = {0.f, 0.f, 0.f, 0.f};
-                if (live) hv = *reinterpret_cast<const f32x4*>(h + (long)(row0 + i) * K + cb);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] *= 1.f - hv[e] * hv[e];
-            }
-            if (out != nullptr) *reinterpret_cast<f32x4*>(out + i * ldo + cb) = o;
-            if (gout != nullptr && live) {
-                float* p = gout + (long)(row0 + i) * K + cb;
-                if (add) {
-                    const f32x4 prev = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] += prev[e];
-                }
-                *reinterpret_cast<f32x4*>(p) = o;
-            }
-        }
-    }
-}
-
-// rows row0 .. row0 + 15 of x [B, F] into an LDS tile, zero past B
-__device__ void ph_load_x(const float* __restrict__ x, int F, int row0, int B, float* buf, int ld) {
-    const int per = F >> 2;
-    for (int e = threadIdx.x; e < PH_TM * per; e += 256) {
-        const int m = e / per, c = (e - m * per) * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (row0 + m < B) v = *reinterpret_cast<const f32x4*>(x + (long)(row0 + m) * F + c);
-        *reinterpret_cast<f32x4*>(buf + m * ld + c) = v;
-    }
-}
 
 #define PH_HALF_LOG_2PI 0.91893853320467274178f
 
@@ -227,12 +66,12 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(PhArgs p, const float* 
     __syncthreads();
     int K = p.F;
     for (int l = 0; l < br.n; ++l) {
-        ph_fwd_layer<true>(cur, p.ld, K, br.W[l], br.b[l], br.w[l], nxt, p.ld, ws ? ws + br.h_off[l] : nullptr, row0, B);
+        ph_fwd_layer<PH_ACT_TANH>(cur, p.ld, K, br.W[l], br.b[l], br.w[l], nxt, p.ld, ws ? ws + br.h_off[l] : nullptr, row0, B);
         __syncthreads();
         float* s = cur; cur = nxt; nxt = s;
         K = br.w[l];
     }
-    ph_fwd_layer<false>(cur, p.ld, K, br.hw, br.hb, br.hn, head, PH_HLD, nullptr, row0, B);
+    ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, br.hw, br.hb, br.hn, head, PH_HLD, nullptr, row0, B);
     __syncthreads();
     if (bi == 1) {
         if (tid < PH_TM && row0 + tid < B) values[row0 + tid] = head[tid * PH_HLD];
@@ -322,34 +161,21 @@ __global__ __launch_bounds__(256) void policy_bwd_chain_kernel(PhArgs p, const f
         int N = br.hn;
         for (int l = br.n - 1; l >= 0; --l) {
             const int K = br.w[l];
-            ph_bwd_layer<true>(cur, p.ld, valid, W, N, K, ws + br.h_off[l], nxt, p.ld, ws + br.d_off[l], false, row0, B);
+            ph_bwd_layer<PH_ACT_TANH>(cur, p.ld, valid, W, N, K, ws + br.h_off[l], nxt, p.ld, ws + br.d_off[l], false, row0, B);
             __syncthreads();
             float* s = cur; cur = nxt; nxt = s;
             W = br.W[l];
             N = K;
             valid = K;
         }
-        ph_bwd_layer<false>(cur, p.ld, valid, W, N, p.F, nullptr, nullptr, 0, dx, pass == 1, row0, B);
+        ph_bwd_layer<PH_ACT_NONE>(cur, p.ld, valid, W, N, p.F, nullptr, nullptr, 0, dx, pass == 1, row0, B);
         __syncthreads();
-    }
-}
-
-// operands of one 32-row step of a weight gradient: a = dY^T (lane i: column n of dY, rows mb .. mb + 7), b = X for four interleaved tiles (the 16
-// bytes X[row][kc .. kc + 3]: tile t takes column kc + t; K is a multiple of 16, so the four are inside or outside together)
-__device__ __forceinline__ void ph_wgrad_load(const PhLin& L, int B, int n, int kc, int mb, Frag<float>& a, Frag<float> (&b)[4]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const bool in = mb + j < B;
-        a.v[j] = (in && n < L.N) ? L.dY[(long)(mb + j) * L.N + n] : 0.f;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (in && kc < L.K) v = *reinterpret_cast<const f32x4*>(L.X + (long)(mb + j) * L.K + kc);
-        b[0].v[j] = v[0]; b[1].v[j] = v[1]; b[2].v[j] = v[2]; b[3].v[j] = v[3];
     }
 }
 
 // grid (cdiv(items, 4) + 1): wave w of block b takes item 4 b + w; the last block sums the d log_std partials
 __global__ __launch_bounds__(256) void policy_wgrad_kernel(PhWgrad q) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
+    const int tid = threadIdx.x, wave = tid >> 6;
     if (blockIdx.x == gridDim.x - 1) {
         if (tid < q.A) {
             float s = 0.f;
@@ -360,46 +186,9 @@ __global__ __launch_bounds__(256) void policy_wgrad_kernel(PhWgrad q) {
     }
     const int item = blockIdx.x * 4 + wave;
     if (item >= q.items) return;                  // a whole wave leaves: the lanes that stay are all active
-    int li = 0;
-    while (li + 1 < q.count && item >= q.lin[li + 1].item0) ++li;
-    const PhLin& L = q.lin[li];
-    const int local = item - L.item0, nt = local / L.kgroups, kg = local - nt * L.kgroups;
-    const int n0 = nt * 16, kbase = kg * 64, N = L.N, K = L.K, B = q.B;
-    const int n = n0 + i, kc = kbase + 4 * i;    // this lane's row of dY^T; its four columns of X and dW (tile t takes column kc + t)
-    f32x4 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float bsum = 0.f;
-    Frag<float> a, b[4];
-    ph_wgrad_load(L, B, n, kc, 8 * g, a, b);
-    for (int m0 = 0; m0 < B; m0 += 32) {
-        Frag<float> an, bn[4];
-        ph_wgrad_load(L, B, n, kc, m0 + 32 + 8 * g, an, bn);                 // rows past B read as zero
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bsum += a.v[j];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = mma16(a, b[t], acc[t]);
-        a = an;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) b[t] = bn[t];
-    }
-    // register r of tile t of lane (i, g) = dW[n0 + 4 g + r][kc + t]
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        if (n0 + 4 * g + r < N && kc < K) *reinterpret_cast<f32x4*>(L.dW + (long)(n0 + 4 * g + r) * K + kc) = f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
-    bsum = xor32_sum(xor16_sum(bsum));            // the four lane groups hold the four quarters of the rows
-    if (kg == 0 && g == 0 && n < N) L.db[n] = bsum;
+    ph_wgrad_item(q.lin, q.count, item, q.B);
 }
 
-// one workgroup of 256 threads
-__device__ __forceinline__ float ph_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* __restrict__ logp, const float* __restrict__ values, const float* __restrict__ entropy,
                                                        const float* __restrict__ old_logp, const float* __restrict__ adv, const float* __restrict__ returns,
                                                        const float* __restrict__ old_values, int B, float clip, float clip_vf, float ent_coef, float vf_coef,
@@ -469,9 +258,6 @@ __global__ __launch_bounds__(256) void ppo_loss_bwd_kernel(const float* __restri
     dentropy[r] = g * -(ent_coef / (float)B);
 }
 
-long ph_round4(long v) { return (v + 3) & ~3L; }
-
-bool ph_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the limits of the header; 0 and a message when the head is outside them
 int ph_shape_ok(const m3l_policy_desc* d, int B, char* why, size_t n) {
@@ -627,6 +413,7 @@ int m3l_policy_eval_bwd(const m3l_policy_desc* d, int B, const float* x, const f
             L.X = X;
             L.N = head ? b.hn : b.w[l];
             L.K = K;
+            L.ldx = K;
             if (bi == 0) {
                 L.dW = head ? grads->action_weight : grads->pi_weight[l];
                 L.db = head ? grads->action_bias : grads->pi_bias[l];

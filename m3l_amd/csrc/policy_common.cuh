@@ -1,0 +1,312 @@
+// The row-tile MLP pieces that the policy heads share (policy.hip: PPO, Tanh; sac.hip: SAC, ReLU): a 16-row tile of activations lives in LDS,
+// every Linear reads its input from one LDS buffer and leaves its output in another, the weights stream from L2 as operands of the exact-f32
+// MFMA (v_mfma_f32_16x16x4_f32 through Frag<float> / mma16 of common.cuh), and every weight / bias gradient of a head is one item list of one
+// grouped launch that reduces over the rows in row order.  The activation is a template parameter; EDGE variants take a weight whose rows are
+// only 4-byte aligned and whose width is no multiple of 16 (the critics' first layer, K = F + A).
+#pragma once
+#include "common.cuh"
+
+#define PH_TM 16                 // rows of a tile
+#define PH_MAXW 512              // widest layer / feature vector
+#define PH_MAXA 64               // most action dimensions
+#define PH_HLD 64                // leading dimension of the heads' LDS tiles
+#define PH_MAXLIN 8              // most Linears of one grouped weight-gradient launch
+
+enum { PH_ACT_NONE = 0, PH_ACT_TANH = 1, PH_ACT_RELU = 2 };
+
+namespace {
+
+// one Linear of the grouped weight-gradient launch: dW [N, K] = dY^T X, db [N] = column sums of dY
+struct PhLin {
+    const float* dY;             // [B, N]
+    const float* X;              // [B, ldx], ldx >= K a multiple of 16; columns K .. ldx - 1 are zero
+    float* dW;
+    float* db;
+    int N, K, kgroups, item0;    // items: (N tiles of 16) x (K groups of 64), numbered from item0
+    int ldx, edge;               // edge: K % 4 != 0 or dW rows not 16-byte aligned, dW is stored element by element
+};
+
+__device__ __forceinline__ Frag<float> ph_zero_frag() {
+    Frag<float> f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f.v[j] = 0.f;
+    return f;
+}
+// rows of W [N, K] as the k-contiguous operand: lane (i, g) <- W[n0 + i][k0 + 8 g .. + 8), zero outside the matrix
+__device__ __forceinline__ Frag<float> ph_w_kc(const float* __restrict__ W, int N, int K, int n0, int k0, int lane) {
+    const int n = n0 + (lane & 15), k = k0 + 8 * (lane >> 4);
+    if (n < N && k < K) return load_kc(W + (long)n * K + k);
+    return ph_zero_frag();
+}
+// the same for any K and 4-byte aligned rows: eight dword loads, each inside the matrix or zero
+__device__ __forceinline__ Frag<float> ph_w_kc_edge(const float* __restrict__ W, int N, int K, int n0, int k0, int lane) {
+    const int n = n0 + (lane & 15), k = k0 + 8 * (lane >> 4);
+    Frag<float> f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f.v[j] = (n < N && k + j < K) ? W[(long)n * K + k + j] : 0.f;
+    return f;
+}
+// an LDS tile [PH_TM, ld] with `valid` written columns (a multiple of 8): lane (i, g) <- t[i][k0 + 8 g .. + 8)
+__device__ __forceinline__ Frag<float> ph_lds_kc(const float* t, int ld, int valid, int k0, int lane) {
+    const int k = k0 + 8 * (lane >> 4);
+    if (k < valid) return load_kc(t + (lane & 15) * ld + k);
+    return ph_zero_frag();
+}
+
+// out[m][n] = act(sum_k in[m][k] W[n][k] + bias[n]) for the 16 rows of the tile, n < N; in: LDS [16, ldi] with K columns (EDGE: K rounded up
+// to 8, the columns past K zero), out: LDS [16, ldo] (every column up to the next multiple of 16 is written, zero past N), gout: global [B, N]
+// rows row0 .. or null.  A wave runs the tiles tb, tb + 4, tb + 8, tb + 12 together: four independent accumulator chains over one LDS fragment,
+// so an MFMA never waits for the one before it.
+template <int ACT, bool EDGE = false>
+__device__ void ph_fwd_layer(const float* in, int ldi, int K, const float* __restrict__ W, const float* __restrict__ bias, int N, float* out, int ldo,
+                             float* __restrict__ gout, int row0, int B) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+    const int ntiles = (N + 15) >> 4;
+    const int valid = EDGE ? (K + 7) & ~7 : K;
+    for (int tb = wave; tb < ntiles; tb += 16) {
+        f32x4 acc[4];
+        Frag<float> wa[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            // zero past N: a tile that does not exist loads nothing
+            wa[u] = EDGE ? ph_w_kc_edge(W, N, K, (tb + 4 * u) * 16, 0, lane) : ph_w_kc(W, N, K, (tb + 4 * u) * 16, 0, lane);
+        }
+        for (int k0 = 0; k0 < K; k0 += 32) {
+            Frag<float> wn[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {                                    // the next step's weights fly while this one multiplies
+                if (k0 + 32 < K)
+                    wn[u] = EDGE ? ph_w_kc_edge(W, N, K, (tb + 4 * u) * 16, k0 + 32, lane) : ph_w_kc(W, N, K, (tb + 4 * u) * 16, k0 + 32, lane);
+                else
+                    wn[u] = ph_zero_frag();
+            }
+            const Frag<float> xb = ph_lds_kc(in, ldi, valid, k0, lane);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (tb + 4 * u < ntiles) acc[u] = mma16(wa[u], xb, acc[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) wa[u] = wn[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (tb + 4 * u >= ntiles) continue;
+            // lane (i, g) register r = out[m = i][n0 + 4 g + r]
+            const int nb = (tb + 4 * u) * 16 + 4 * g;
+            f32x4 o;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = 0.f;
+                if (nb + r < N) {
+                    v = acc[u][r] + bias[nb + r];
+                    if (ACT == PH_ACT_TANH) v = tanhf(v);
+                    if (ACT == PH_ACT_RELU) v = fmaxf(v, 0.f);
+                }
+                o[r] = v;
+            }
+            *reinterpret_cast<f32x4*>(out + i * ldo + nb) = o;
+            if (gout != nullptr && row0 + i < B) {
+                if ((N & 3) == 0) {
+                    *reinterpret_cast<f32x4*>(gout + (long)(row0 + i) * N + nb) = o;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (nb + r < N) gout[(long)(row0 + i) * N + nb + r] = o[r];
+                }
+            }
+        }
+    }
+}
+
+// W [N, K] as the operand whose k index is W's row, for FOUR tiles at once: lane (i, g) reads the 16 bytes W[n0 + 8 g + j][cbase + 4 i .. + 3] and
+// tile u takes column cbase + 4 i + u of them (K is a multiple of 16, so the four columns are inside or outside together)
+__device__ __forceinline__ void ph_w_ks4(const float* __restrict__ W, int N, int K, int n0, int cbase, int lane, Frag<float> (&f)[4]) {
+    const int c = cbase + 4 * (lane & 15), nb = n0 + 8 * (lane >> 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (nb + j < N && c < K) v = *reinterpret_cast<const f32x4*>(W + (long)(nb + j) * K + c);
+        f[0].v[j] = v[0]; f[1].v[j] = v[1]; f[2].v[j] = v[2]; f[3].v[j] = v[3];
+    }
+}
+// the same over the columns coff .. coff + Kc - 1 (Kc <= 64) of a W whose rows are ldw floats apart and 4-byte aligned: dword loads
+__device__ __forceinline__ void ph_w_ks4_edge(const float* __restrict__ W, int N, int ldw, int coff, int Kc, int n0, int lane, Frag<float> (&f)[4]) {
+    const int c = 4 * (lane & 15), nb = n0 + 8 * (lane >> 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) f[u].v[j] = (nb + j < N && c + u < Kc) ? W[(long)(nb + j) * ldw + coff + c + u] : 0.f;
+}
+
+// out[m][c] = (sum_n din[m][n] W[n][c]) * act'(h[m][c]), c < K (a multiple of 16); act' is 1 - h^2 for Tanh and (h > 0) for ReLU, h the stored
+// post-activation [B, K]; din: LDS [16, ldi] with `valid` columns written; out: LDS [16, ldo] or null; gout: global [B, K] or null.  add: the
+// value already in out (or, without out, in gout) is added, by the lane that wrote it.  A wave owns 64 columns, as four interleaved tiles
+// (ph_w_ks4): register r of tile u of lane (i, g) = out[m = i][cbase + 16 g + 4 r + u].
+template <int ACT>
+__device__ void ph_bwd_layer(const float* din, int ldi, int valid, const float* __restrict__ W, int N, int K, const float* __restrict__ h, float* out, int ldo,
+                             float* gout, bool add, int row0, int B) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+    const int groups = (K + 63) >> 6;
+    const bool live = row0 + i < B;
+    for (int gi = wave; gi < groups; gi += 4) {
+        const int cbase = gi * 64;
+        f32x4 acc[4];
+        Frag<float> wa[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        ph_w_ks4(W, N, K, 0, cbase, lane, wa);
+        for (int n0 = 0; n0 < N; n0 += 32) {
+            Frag<float> wn[4];
+            ph_w_ks4(W, N, K, n0 + 32, cbase, lane, wn);                     // rows past N read as zero
+            const Frag<float> db = ph_lds_kc(din, ldi, valid, n0, lane);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[u] = mma16(wa[u], db, acc[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) wa[u] = wn[u];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int cb = cbase + 16 * g + 4 * r;
+            if (cb >= K) continue;
+            f32x4 o = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+            if (ACT != PH_ACT_NONE) {
+                f32x4 hv = {0.f, 0.f, 0.f, 0.f};
+                if (live) hv = *reinterpret_cast<const f32x4*>(h + (long)(row0 + i) * K + cb);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (ACT == PH_ACT_TANH) o[e] *= 1.f - hv[e] * hv[e];
+                    if (ACT == PH_ACT_RELU) o[e] = hv[e] > 0.f ? o[e] : 0.f;
+                }
+            }
+            if (out != nullptr) {
+                if (add) {
+                    const f32x4 prev = *reinterpret_cast<const f32x4*>(out + i * ldo + cb);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] += prev[e];
+                }
+                *reinterpret_cast<f32x4*>(out + i * ldo + cb) = o;
+            }
+            if (gout != nullptr && live) {
+                float* p = gout + (long)(row0 + i) * K + cb;
+                if (add && out == nullptr) {
+                    const f32x4 prev = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] += prev[e];
+                }
+                *reinterpret_cast<f32x4*>(p) = o;
+            }
+        }
+    }
+}
+
+// gout[m][c] (+)= sum_n din[m][n] W[n][coff + c], c < Kc <= 64, rows of W ldw floats apart and only 4-byte aligned; gout: global [B, Kc], stored
+// element by element by wave 0 (add: the value there is added by the lane that wrote it).  No activation: these columns are an input.
+__device__ void ph_bwd_edge(const float* din, int ldi, int valid, const float* __restrict__ W, int N, int ldw, int coff, int Kc, float* gout, bool add,
+                            int row0, int B) {
+    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    if (threadIdx.x >= 64) return;
+    f32x4 acc[4];
+    Frag<float> wa[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n0 = 0; n0 < N; n0 += 32) {
+        ph_w_ks4_edge(W, N, ldw, coff, Kc, n0, lane, wa);
+        const Frag<float> db = ph_lds_kc(din, ldi, valid, n0, lane);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = mma16(wa[u], db, acc[u]);
+    }
+    if (row0 + i >= B) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = 16 * g + 4 * r + u;
+            if (c < Kc) {
+                float* p = gout + (long)(row0 + i) * Kc + c;
+                *p = add ? *p + acc[u][r] : acc[u][r];
+            }
+        }
+}
+
+// rows row0 .. row0 + 15 of x [B, F] into an LDS tile, zero past B
+__device__ void ph_load_x(const float* __restrict__ x, int F, int row0, int B, float* buf, int ld) {
+    const int per = F >> 2;
+    for (int e = threadIdx.x; e < PH_TM * per; e += 256) {
+        const int m = e / per, c = (e - m * per) * 4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (row0 + m < B) v = *reinterpret_cast<const f32x4*>(x + (long)(row0 + m) * F + c);
+        *reinterpret_cast<f32x4*>(buf + m * ld + c) = v;
+    }
+}
+
+// operands of one 32-row step of a weight gradient: a = dY^T (lane i: column n of dY, rows mb .. mb + 7), b = X for four interleaved tiles (the 16
+// bytes X[row][kc .. kc + 3]: tile t takes column kc + t; ldx is a multiple of 16, so the four are inside or outside together)
+__device__ __forceinline__ void ph_wgrad_load(const PhLin& L, int B, int n, int kc, int mb, Frag<float>& a, Frag<float> (&b)[4]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const bool in = mb + j < B;
+        a.v[j] = (in && n < L.N) ? L.dY[(long)(mb + j) * L.N + n] : 0.f;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (in && kc < L.ldx) v = *reinterpret_cast<const f32x4*>(L.X + (long)(mb + j) * L.ldx + kc);
+        b[0].v[j] = v[0]; b[1].v[j] = v[1]; b[2].v[j] = v[2]; b[3].v[j] = v[3];
+    }
+}
+
+// one wave's item of a grouped weight-gradient launch: a 16 x 64 block of one Linear's dW as four interleaved tiles, reducing over all rows in
+// row order, and (the item of K group 0) the 16 entries of db.  The whole wave calls it or none of it does.
+__device__ void ph_wgrad_item(const PhLin* lin, int count, int item, int B) {
+    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    int li = 0;
+    while (li + 1 < count && item >= lin[li + 1].item0) ++li;
+    const PhLin& L = lin[li];
+    const int local = item - L.item0, nt = local / L.kgroups, kg = local - nt * L.kgroups;
+    const int n0 = nt * 16, kbase = kg * 64, N = L.N, K = L.K;
+    const int n = n0 + i, kc = kbase + 4 * i;    // this lane's row of dY^T; its four columns of X and dW (tile t takes column kc + t)
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum = 0.f;
+    Frag<float> a, b[4];
+    ph_wgrad_load(L, B, n, kc, 8 * g, a, b);
+    for (int m0 = 0; m0 < B; m0 += 32) {
+        Frag<float> an, bn[4];
+        ph_wgrad_load(L, B, n, kc, m0 + 32 + 8 * g, an, bn);                 // rows past B read as zero
+#pragma unroll
+        for (int j = 0; j < 8; ++j) bsum += a.v[j];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = mma16(a, b[t], acc[t]);
+        a = an;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) b[t] = bn[t];
+    }
+    // register r of tile t of lane (i, g) = dW[n0 + 4 g + r][kc + t]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (n0 + 4 * g + r >= N) continue;
+        float* p = L.dW + (long)(n0 + 4 * g + r) * K + kc;
+        if (L.edge) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (kc + t < K) p[t] = acc[t][r];
+        } else if (kc < K) {
+            *reinterpret_cast<f32x4*>(p) = f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+        }
+    }
+    bsum = xor32_sum(xor16_sum(bsum));            // the four lane groups hold the four quarters of the rows
+    if (kg == 0 && g == 0 && n < N) L.db[n] = bsum;
+}
+
+// one workgroup of 256 threads
+__device__ __forceinline__ float ph_block_sum(float v, float* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+}
+
+inline long ph_round4(long v) { return (v + 3) & ~3L; }
+inline bool ph_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace

@@ -1,0 +1,665 @@
+// SAC policy head (include/m3l_amd.h "SAC policy head"): the squashed-Gaussian actor (latent_pi, mu, a state-dependent clamped log_std, tanh),
+// the twin critics over cat([x, actions]), the TD target, and the three losses of SAC_MAE.train.  float32 throughout on the exact-f32 MFMA, with
+// the row-tile pieces of policy_common.cuh (ReLU instead of the PPO head's Tanh).
+//
+//   actor fwd    one launch, grid (row tiles of 16): x -> LDS, the hidden layers ping-pong between two LDS buffers, the mu and log_std heads
+//                leave two [16, A] tiles, then u = mu + exp(s) noise, a = tanh(u) and the row's log-probability.  With a workspace the
+//                post-ReLU activations, u and the pre-clamp log_std stay for the backward.
+//   actor bwd    chain kernel per row tile: (d actions, d log_prob) -> d mu, d log_std (clamp gate) -> back through both heads (the second
+//                adds to the first in LDS, the same lane owning an element) and the hidden layers to dx; then the grouped weight-gradient launch.
+//   critic fwd   one launch, grid (row tiles, 2 critics): the input tile is [x | a | zeros to a multiple of 16]; the first Linear has
+//                K = F + A and rows that are only 4-byte aligned, so its weights come in by dword loads (EDGE path), every other as in the PPO head.
+//   critic bwd   chain kernel per row tile, critic 0 then critic 1: d q -> hidden layers (ReLU gates) -> d actions through the action columns of
+//                the first weight (critic 1 adds to what critic 0 wrote); the features get no gradient.  The grouped weight-gradient launch
+//                runs only when parameter gradients are asked for; dW of the first layer is stored element by element.
+//   td target    one launch per row tile: the actor on x' in LDS, a' handed to both target critics in LDS, min, entropy term, Bellman line.
+//   losses       one workgroup each, every thread over its rows in order and the threads' sums through ph_block_sum; the forward stores the
+//                per-row coefficients and the backward scales them by dloss.
+// No float atomics, every sum in a fixed order: the same bits on every run.
+#include <math.h>
+#include <string.h>
+
+#include "../../include/m3l_amd.h"
+#include "common.cuh"
+#include "kernels.h"
+#include "policy_common.cuh"
+
+#define SAC_EPS 1e-6f
+#define SAC_HALF_LOG_2PI 0.91893853320467274178f
+#define SAC_LOG_STD_MIN -20.f
+#define SAC_LOG_STD_MAX 2.f
+#define SAC_NH M3L_SAC_MAX_HIDDEN
+
+namespace {
+
+struct SacArgs {
+    int B, F, A, ld;             // ld: leading dimension of the LDS activation buffers
+    int K0, Kp;                  // the critics' input width F + A, and the same rounded up to 16
+    // actor
+    int n_pi, pi_w[SAC_NH];
+    const float* pi_W[SAC_NH];
+    const float* pi_b[SAC_NH];
+    const float *mu_W, *mu_b, *s_W, *s_b;
+    long pi_h[SAC_NH], pi_d[SAC_NH];         // post-ReLU activations / pre-activation gradients in the workspace, in floats
+    long u_off, s_off, dmu_off, ds_off;      // u, pre-clamp log_std, d mu, d (pre-clamp log_std): [B, A] each
+    // critics
+    int n_qf, qf_w[SAC_NH];
+    const float* qf_W[2][SAC_NH];
+    const float* qf_b[2][SAC_NH];
+    const float* q_W[2];
+    const float* q_b[2];
+    long qf_h[2][SAC_NH], qf_d[2][SAC_NH];
+    long xa_off, dq_off;                     // the input [B, Kp]; d q [2, B]
+    long total;
+};
+
+struct SacWgrad {
+    PhLin lin[PH_MAXLIN];
+    int count, items, B;
+};
+
+// 1 - tanh(u)^2 without the cancellation: 4 e / (1 + e)^2 with e = exp(-2 |u|)
+__device__ __forceinline__ float sac_one_minus_tanh2(float u) {
+    const float e = expf(-2.f * fabsf(u)), d = 1.f + e;
+    return 4.f * e / (d * d);
+}
+
+// The actor on the rows row0 .. row0 + 15: leaves actions in hmu [16, PH_HLD] (columns < A), the rows' log-probabilities in lp_sh [16], and in
+// global memory whatever pointer is given (rows < B only).  noise null: the deterministic action tanh(mu).  Ends with a barrier.
+__device__ void sac_actor_tile(const SacArgs& p, const float* __restrict__ x, const float* __restrict__ noise, int row0, float* bufa, float* bufb, float* hmu,
+                               float* hs, float* lp_sh, float* __restrict__ ws, float* __restrict__ actions_out, float* __restrict__ logp_out) {
+    const int tid = threadIdx.x, B = p.B, A = p.A;
+    float* cur = bufa;
+    float* nxt = bufb;
+    ph_load_x(x, p.F, row0, B, cur, p.ld);
+    __syncthreads();
+    int K = p.F;
+    for (int l = 0; l < p.n_pi; ++l) {
+        ph_fwd_layer<PH_ACT_RELU>(cur, p.ld, K, p.pi_W[l], p.pi_b[l], p.pi_w[l], nxt, p.ld, ws ? ws + p.pi_h[l] : nullptr, row0, B);
+        __syncthreads();
+        float* s = cur; cur = nxt; nxt = s;
+        K = p.pi_w[l];
+    }
+    ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.mu_W, p.mu_b, A, hmu, PH_HLD, nullptr, row0, B);
+    ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.s_W, p.s_b, A, hs, PH_HLD, nullptr, row0, B);
+    __syncthreads();
+    for (int e = tid; e < PH_TM * A; e += 256) {
+        const int m = e / A, j = e - m * A, row = row0 + m;
+        const float mu = hmu[m * PH_HLD + j], sp = hs[m * PH_HLD + j];
+        const float s = fminf(fmaxf(sp, SAC_LOG_STD_MIN), SAC_LOG_STD_MAX);
+        const float n = (noise != nullptr && row < B) ? noise[(long)row * A + j] : 0.f;
+        const float u = mu + expf(s) * n, a = tanhf(u);
+        // (u - mu)^2 / (2 exp(s)^2) is n^2 / 2 exactly; formed from n it carries no rounding of the subtraction
+        const float term = -0.5f * n * n - s - SAC_HALF_LOG_2PI - logf(sac_one_minus_tanh2(u) + SAC_EPS);
+        if (row < B) {
+            if (actions_out) actions_out[(long)row * A + j] = a;
+            if (ws) {
+                ws[p.u_off + (long)row * A + j] = u;
+                ws[p.s_off + (long)row * A + j] = sp;
+            }
+        }
+        hmu[m * PH_HLD + j] = a;
+        hs[m * PH_HLD + j] = term;
+    }
+    __syncthreads();
+    if (tid < PH_TM) {
+        float lp = 0.f;
+        for (int j = 0; j < A; ++j) lp += hs[tid * PH_HLD + j];
+        lp_sh[tid] = lp;
+        if (logp_out && row0 + tid < B) logp_out[row0 + tid] = lp;
+    }
+    __syncthreads();
+}
+
+// the critics' input tile [x | a | zeros up to Kp] for the rows row0 .. row0 + 15 (zero past B); a: row m of the tile at asrc + m * lda
+__device__ void sac_build_xa(const SacArgs& p, const float* __restrict__ x, const float* asrc, int lda, int row0, float* buf) {
+    ph_load_x(x, p.F, row0, p.B, buf, p.ld);
+    const int extra = p.Kp - p.F;
+    for (int e = threadIdx.x; e < PH_TM * extra; e += 256) {
+        const int m = e / extra, j = e - m * extra;
+        buf[m * p.ld + p.F + j] = (j < p.A && row0 + m < p.B) ? asrc[(long)m * lda + j] : 0.f;
+    }
+}
+
+// Critic c on the input tile in bufa (which it overwrites): q of the 16 rows into column 0 of head [16, PH_HLD].  Ends with a barrier.
+__device__ void sac_critic_tile(const SacArgs& p, int c, int row0, float* bufa, float* bufb, float* head, float* __restrict__ ws) {
+    float* cur = bufa;
+    float* nxt = bufb;
+    int K = p.K0;
+    for (int l = 0; l < p.n_qf; ++l) {
+        float* g = ws ? ws + p.qf_h[c][l] : nullptr;
+        if (l == 0)
+            ph_fwd_layer<PH_ACT_RELU, true>(cur, p.ld, K, p.qf_W[c][l], p.qf_b[c][l], p.qf_w[l], nxt, p.ld, g, row0, p.B);
+        else
+            ph_fwd_layer<PH_ACT_RELU>(cur, p.ld, K, p.qf_W[c][l], p.qf_b[c][l], p.qf_w[l], nxt, p.ld, g, row0, p.B);
+        __syncthreads();
+        float* s = cur; cur = nxt; nxt = s;
+        K = p.qf_w[l];
+    }
+    if (p.n_qf == 0)
+        ph_fwd_layer<PH_ACT_NONE, true>(cur, p.ld, K, p.q_W[c], p.q_b[c], 1, head, PH_HLD, nullptr, row0, p.B);
+    else
+        ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.q_W[c], p.q_b[c], 1, head, PH_HLD, nullptr, row0, p.B);
+    __syncthreads();
+}
+
+// grid (row tiles)
+__global__ __launch_bounds__(256) void sac_actor_fwd_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ noise, float* __restrict__ ws,
+                                                            float* __restrict__ actions, float* __restrict__ logp) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD], hs[PH_TM * PH_HLD];
+    __shared__ float lp_sh[PH_TM];
+    sac_actor_tile(p, x, noise, blockIdx.x * PH_TM, sac_lds, sac_lds + PH_TM * p.ld, hmu, hs, lp_sh, ws, actions, logp);
+}
+
+// grid (row tiles).  dactions [B, A] / dlogp [B] or null (= zero)
+__global__ __launch_bounds__(256) void sac_actor_bwd_kernel(SacArgs p, const float* __restrict__ noise, const float* __restrict__ dactions,
+                                                            const float* __restrict__ dlogp, float* __restrict__ ws, float* __restrict__ dx) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float tmu[PH_TM * PH_HLD], ts[PH_TM * PH_HLD];
+    float* cur = sac_lds;
+    float* nxt = sac_lds + PH_TM * p.ld;
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B, A = p.A;
+    // a = tanh(u), om = 1 - a^2:  d u = d a om + d logp 2 a om / (om + eps);  d mu = d u;  d s = d u exp(s) noise - d logp, gated by the clamp
+    for (int e = tid; e < PH_TM * PH_HLD; e += 256) {
+        const int m = e >> 6, j = e & 63, row = row0 + m;
+        float dm = 0.f, dsv = 0.f;
+        if (j < A && row < B) {
+            const long at = (long)row * A + j;
+            const float u = ws[p.u_off + at], sp = ws[p.s_off + at];
+            const float gl = dlogp ? dlogp[row] : 0.f, ga = dactions ? dactions[at] : 0.f, n = noise ? noise[at] : 0.f;
+            const float a = tanhf(u), om = sac_one_minus_tanh2(u);
+            dm = ga * om + gl * (2.f * a * om / (om + SAC_EPS));
+            const bool open = sp >= SAC_LOG_STD_MIN && sp <= SAC_LOG_STD_MAX;
+            const float s = fminf(fmaxf(sp, SAC_LOG_STD_MIN), SAC_LOG_STD_MAX);
+            dsv = open ? dm * expf(s) * n - gl : 0.f;
+            ws[p.dmu_off + at] = dm;
+            ws[p.ds_off + at] = dsv;
+        }
+        tmu[e] = dm;
+        ts[e] = dsv;
+    }
+    __syncthreads();
+    const int hv = (A + 7) & ~7;
+    if (p.n_pi == 0) {
+        ph_bwd_layer<PH_ACT_NONE>(tmu, PH_HLD, hv, p.mu_W, A, p.F, nullptr, nullptr, 0, dx, false, row0, B);
+        __syncthreads();
+        ph_bwd_layer<PH_ACT_NONE>(ts, PH_HLD, hv, p.s_W, A, p.F, nullptr, nullptr, 0, dx, true, row0, B);
+        return;
+    }
+    int l = p.n_pi - 1;
+    int K = p.pi_w[l];
+    // both heads into the last hidden layer: the ReLU gate is 0 or 1, so gating each product and adding is gating the sum
+    ph_bwd_layer<PH_ACT_RELU>(tmu, PH_HLD, hv, p.mu_W, A, K, ws + p.pi_h[l], cur, p.ld, nullptr, false, row0, B);
+    __syncthreads();
+    ph_bwd_layer<PH_ACT_RELU>(ts, PH_HLD, hv, p.s_W, A, K, ws + p.pi_h[l], cur, p.ld, ws + p.pi_d[l], true, row0, B);
+    __syncthreads();
+    for (--l; l >= 0; --l) {
+        const int N = K;
+        K = p.pi_w[l];
+        ph_bwd_layer<PH_ACT_RELU>(cur, p.ld, N, p.pi_W[l + 1], N, K, ws + p.pi_h[l], nxt, p.ld, ws + p.pi_d[l], false, row0, B);
+        __syncthreads();
+        float* s = cur; cur = nxt; nxt = s;
+    }
+    ph_bwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.pi_W[0], K, p.F, nullptr, nullptr, 0, dx, false, row0, B);
+}
+
+// grid (row tiles, 2 critics).  q [2, B]
+__global__ __launch_bounds__(256) void sac_critic_fwd_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ actions, float* __restrict__ ws,
+                                                             float* __restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float head[PH_TM * PH_HLD];
+    float* bufa = sac_lds;
+    float* bufb = sac_lds + PH_TM * p.ld;
+    const int c = blockIdx.y, row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B;
+    sac_build_xa(p, x, actions + (long)row0 * p.A, p.A, row0, bufa);
+    __syncthreads();
+    if (ws != nullptr && c == 0) {
+        const int per = p.Kp >> 2;
+        for (int e = tid; e < PH_TM * per; e += 256) {
+            const int m = e / per, k = (e - m * per) * 4;
+            if (row0 + m < B) *reinterpret_cast<f32x4*>(ws + p.xa_off + (long)(row0 + m) * p.Kp + k) = *reinterpret_cast<const f32x4*>(bufa + m * p.ld + k);
+        }
+        __syncthreads();
+    }
+    sac_critic_tile(p, c, row0, bufa, bufb, head, ws);
+    if (tid < PH_TM && row0 + tid < B) q[(long)c * B + row0 + tid] = head[tid * PH_HLD];
+}
+
+// grid (row tiles).  dq [2, B] or null (= zero); dactions [B, A] or null (not wanted)
+__global__ __launch_bounds__(256) void sac_critic_bwd_kernel(SacArgs p, const float* __restrict__ dq, float* __restrict__ ws, float* __restrict__ dactions) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B;
+    for (int c = 0; c < 2; ++c) {
+        float* cur = sac_lds;
+        float* nxt = sac_lds + PH_TM * p.ld;
+        // d q of this critic: [16, 8] with the value in column 0
+        if (tid < PH_TM * 8) {
+            const int m = tid >> 3, j = tid & 7, row = row0 + m;
+            float v = 0.f;
+            if (j == 0 && row < B) {
+                v = dq ? dq[(long)c * B + row] : 0.f;
+                ws[p.dq_off + (long)c * B + row] = v;
+            }
+            cur[m * p.ld + j] = v;
+        }
+        __syncthreads();
+        const float* W = p.q_W[c];
+        int N = 1, valid = 8;
+        for (int l = p.n_qf - 1; l >= 0; --l) {
+            const int K = p.qf_w[l];
+            ph_bwd_layer<PH_ACT_RELU>(cur, p.ld, valid, W, N, K, ws + p.qf_h[c][l], nxt, p.ld, ws + p.qf_d[c][l], false, row0, B);
+            __syncthreads();
+            float* s = cur; cur = nxt; nxt = s;
+            W = p.qf_W[c][l];
+            N = K;
+            valid = K;
+        }
+        // the action columns of the first weight; critic 1 adds to what critic 0 wrote, lane for lane
+        if (dactions != nullptr) ph_bwd_edge(cur, p.ld, valid, W, N, p.K0, p.F, p.A, dactions, c == 1, row0, B);
+        __syncthreads();
+    }
+}
+
+// grid (cdiv(items, 4)): wave w of block b takes item 4 b + w
+__global__ __launch_bounds__(256) void sac_wgrad_kernel(SacWgrad q) {
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= q.items) return;                  // a whole wave leaves: the lanes that stay are all active
+    ph_wgrad_item(q.lin, q.count, item, q.B);
+}
+
+// grid (row tiles).  The critic pointers of p are the target critics'.
+__global__ __launch_bounds__(256) void sac_td_target_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ noise,
+                                                            const float* __restrict__ rewards, const float* __restrict__ dones, float gamma, float ent_coef,
+                                                            const float* __restrict__ log_ent_coef, float* __restrict__ target_q) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD], hs[PH_TM * PH_HLD];
+    __shared__ float lp_sh[PH_TM], q_sh[2][PH_TM];
+    float* bufa = sac_lds;
+    float* bufb = sac_lds + PH_TM * p.ld;
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B;
+    sac_actor_tile(p, x, noise, row0, bufa, bufb, hmu, hs, lp_sh, nullptr, nullptr, nullptr);
+    for (int c = 0; c < 2; ++c) {
+        sac_build_xa(p, x, hmu, PH_HLD, row0, bufa);
+        __syncthreads();
+        sac_critic_tile(p, c, row0, bufa, bufb, hs, nullptr);
+        if (tid < PH_TM) q_sh[c][tid] = hs[tid * PH_HLD];
+        __syncthreads();
+    }
+    if (tid < PH_TM && row0 + tid < B) {
+        const int row = row0 + tid;
+        const float ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
+        const float nq = fminf(q_sh[0][tid], q_sh[1][tid]) - ent * lp_sh[tid];
+        target_q[row] = rewards[row] + (1.f - dones[row]) * gamma * nq;
+    }
+}
+
+// one workgroup.  loss = 0.5 sum_c mean_r (q[c, r] - t[r])^2;  coef [2, B] = dloss / dq
+__global__ __launch_bounds__(256) void sac_critic_loss_kernel(const float* __restrict__ q, const float* __restrict__ t, int B, float* __restrict__ loss,
+                                                              float* __restrict__ coef) {
+    __shared__ float red[4];
+    const float invB = 1.f / (float)B;
+    float s0 = 0.f, s1 = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) {
+        const float d0 = q[r] - t[r], d1 = q[B + r] - t[r];
+        s0 += d0 * d0;
+        s1 += d1 * d1;
+        coef[r] = d0 * invB;
+        coef[B + r] = d1 * invB;
+    }
+    s0 = ph_block_sum(s0, red);
+    s1 = ph_block_sum(s1, red);
+    if (threadIdx.x == 0) loss[0] = 0.5f * (s0 * invB + s1 * invB);
+}
+
+// one workgroup.  loss = mean_r (ent logp[r] - min_c q[c, r]);  coef [3, B]: dloss / dlogp, then dloss / dq [2, B] (the smaller critic takes it,
+// critic 0 when they are equal)
+__global__ __launch_bounds__(256) void sac_actor_loss_kernel(const float* __restrict__ logp, const float* __restrict__ q, int B, float ent_coef,
+                                                             const float* __restrict__ log_ent_coef, float* __restrict__ loss, float* __restrict__ coef) {
+    __shared__ float red[4];
+    const float invB = 1.f / (float)B, ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
+    float s = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) {
+        const float q0 = q[r], q1 = q[B + r];
+        const bool first = q0 <= q1;
+        s += ent * logp[r] - (first ? q0 : q1);
+        coef[r] = ent * invB;
+        coef[B + r] = first ? -invB : 0.f;
+        coef[2 * B + r] = first ? 0.f : -invB;
+    }
+    s = ph_block_sum(s, red);
+    if (threadIdx.x == 0) loss[0] = s * invB;
+}
+
+// one workgroup.  m = mean_r (logp[r] + target_entropy):  loss = -log_ent_coef m,  ent_coef = exp(log_ent_coef),  dlog = -dloss m (dloss null: 1)
+__global__ __launch_bounds__(256) void sac_ent_coef_loss_kernel(const float* __restrict__ log_ent_coef, const float* __restrict__ logp, float target_entropy, int B,
+                                                                const float* __restrict__ dloss, float* __restrict__ loss, float* __restrict__ ent_coef,
+                                                                float* __restrict__ dlog) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) s += logp[r] + target_entropy;
+    s = ph_block_sum(s, red);
+    if (threadIdx.x == 0) {
+        const float m = s / (float)B, le = log_ent_coef[0];
+        if (loss) loss[0] = -(le * m);
+        if (ent_coef) ent_coef[0] = expf(le);
+        if (dlog) dlog[0] = -((dloss ? dloss[0] : 1.f) * m);
+    }
+}
+
+__global__ __launch_bounds__(256) void sac_scale_kernel(const float* __restrict__ dloss, const float* __restrict__ coef, int n, float* __restrict__ out) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r < n) out[r] = dloss[0] * coef[r];
+}
+
+enum { SAC_ACTOR = 1, SAC_CRITIC = 2 };
+
+// the limits of the header; 0 and a message when the head is outside them
+int sac_shape_ok(const m3l_sac_desc* d, int B, char* why, size_t n) {
+    if (d == nullptr) { snprintf(why, n, "null descriptor"); return 0; }
+    if (B < 1) { snprintf(why, n, "B=%d (B >= 1)", B); return 0; }
+    if (d->features < 16 || d->features % 16 || d->features > PH_MAXW) {
+        snprintf(why, n, "features=%d (a multiple of 16, at most %d)", d->features, PH_MAXW);
+        return 0;
+    }
+    if (d->actions < 1 || d->actions > PH_MAXA) { snprintf(why, n, "actions=%d (1 <= A <= %d)", d->actions, PH_MAXA); return 0; }
+    if (d->n_pi < 0 || d->n_pi > SAC_NH || d->n_qf < 0 || d->n_qf > SAC_NH) {
+        snprintf(why, n, "%d / %d hidden layers (0 to %d per net)", d->n_pi, d->n_qf, SAC_NH);
+        return 0;
+    }
+    for (int l = 0; l < d->n_pi + d->n_qf; ++l) {
+        const int w = l < d->n_pi ? d->pi_width[l] : d->qf_width[l - d->n_pi];
+        if (w < 16 || w % 16 || w > PH_MAXW) { snprintf(why, n, "hidden width %d (a multiple of 16, at most %d)", w, PH_MAXW); return 0; }
+    }
+    if ((long)B * (PH_MAXW + PH_MAXA) >= 2147483647L / 4) { snprintf(why, n, "B=%d rows are more than the kernels index", B); return 0; }
+    return 1;
+}
+
+// kernel arguments and workspace layout; parts: whose parameter pointers are read (0 only sizes the workspace)
+SacArgs sac_args(const m3l_sac_desc* d, int B, int parts) {
+    SacArgs p;
+    memset(&p, 0, sizeof(p));
+    p.B = B;
+    p.F = d->features;
+    p.A = d->actions;
+    p.K0 = p.F + p.A;
+    p.Kp = (p.K0 + 15) & ~15;
+    int widest = p.Kp > PH_MAXA ? p.Kp : PH_MAXA;
+    long off = 0;
+    p.n_pi = d->n_pi;
+    for (int l = 0; l < p.n_pi; ++l) {
+        p.pi_w[l] = d->pi_width[l];
+        if (p.pi_w[l] > widest) widest = p.pi_w[l];
+        p.pi_h[l] = off;
+        off += (long)B * p.pi_w[l];
+        p.pi_d[l] = off;
+        off += (long)B * p.pi_w[l];
+    }
+    p.u_off = off;
+    off = ph_round4(off + (long)B * p.A);
+    p.s_off = off;
+    off = ph_round4(off + (long)B * p.A);
+    p.dmu_off = off;
+    off = ph_round4(off + (long)B * p.A);
+    p.ds_off = off;
+    off = ph_round4(off + (long)B * p.A);
+    p.n_qf = d->n_qf;
+    for (int l = 0; l < p.n_qf; ++l) {
+        p.qf_w[l] = d->qf_width[l];
+        if (p.qf_w[l] > widest) widest = p.qf_w[l];
+    }
+    for (int c = 0; c < 2; ++c)
+        for (int l = 0; l < p.n_qf; ++l) {
+            p.qf_h[c][l] = off;
+            off += (long)B * p.qf_w[l];
+            p.qf_d[c][l] = off;
+            off += (long)B * p.qf_w[l];
+        }
+    p.xa_off = off;
+    off += (long)B * p.Kp;
+    p.dq_off = off;
+    off = ph_round4(off + 2L * B);
+    p.total = off;
+    p.ld = widest + 4;
+    if (parts & SAC_ACTOR) {
+        for (int l = 0; l < p.n_pi; ++l) { p.pi_W[l] = d->pi_weight[l]; p.pi_b[l] = d->pi_bias[l]; }
+        p.mu_W = d->mu_weight; p.mu_b = d->mu_bias; p.s_W = d->log_std_weight; p.s_b = d->log_std_bias;
+    }
+    if (parts & SAC_CRITIC)
+        for (int c = 0; c < 2; ++c) {
+            for (int l = 0; l < p.n_qf; ++l) { p.qf_W[c][l] = d->qf_weight[c][l]; p.qf_b[c][l] = d->qf_bias[c][l]; }
+            p.q_W[c] = d->q_weight[c]; p.q_b[c] = d->q_bias[c];
+        }
+    return p;
+}
+
+int sac_params_ok(const m3l_sac_desc* d, int parts, const char* who) {
+    int ok = 1;
+    if (parts & SAC_ACTOR) {
+        ok = ok && d->mu_weight && d->mu_bias && d->log_std_weight && d->log_std_bias && ph_aligned(d->mu_weight) && ph_aligned(d->log_std_weight);
+        for (int l = 0; l < d->n_pi; ++l) ok = ok && d->pi_weight[l] && d->pi_bias[l] && ph_aligned(d->pi_weight[l]);
+    }
+    if (parts & SAC_CRITIC)
+        for (int c = 0; c < 2; ++c) {
+            ok = ok && d->q_weight[c] && d->q_bias[c] && ph_aligned(d->q_weight[c]);
+            for (int l = 0; l < d->n_qf; ++l) ok = ok && d->qf_weight[c][l] && d->qf_bias[c][l] && ph_aligned(d->qf_weight[c][l]);
+        }
+    M3L_CHECK(ok, "%s: a parameter pointer of the descriptor is null or a weight is not 16-byte aligned", who);
+    return 0;
+}
+
+int g_sac_inited = 0;
+#define SAC_LDS_MAX (2 * PH_TM * (PH_MAXW + PH_MAXA + 4) * 4)
+int sac_init() {
+    if (g_sac_inited) return 0;
+    M3L_HIP(hipFuncSetAttribute((const void*)sac_actor_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
+    M3L_HIP(hipFuncSetAttribute((const void*)sac_actor_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
+    M3L_HIP(hipFuncSetAttribute((const void*)sac_critic_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
+    M3L_HIP(hipFuncSetAttribute((const void*)sac_critic_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
+    M3L_HIP(hipFuncSetAttribute((const void*)sac_td_target_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
+    g_sac_inited = 1;
+    return 0;
+}
+
+size_t sac_lds_bytes(const SacArgs& p) { return (size_t)2 * PH_TM * p.ld * 4; }
+
+double sac_actor_flops(const SacArgs& p) {
+    double fl = 0;
+    int K = p.F;
+    for (int l = 0; l < p.n_pi; ++l) { fl += 2.0 * p.B * K * p.pi_w[l]; K = p.pi_w[l]; }
+    return fl + 4.0 * p.B * K * p.A;
+}
+double sac_critic_flops(const SacArgs& p) {
+    double fl = 0;
+    int K = p.K0;
+    for (int l = 0; l < p.n_qf; ++l) { fl += 2.0 * p.B * K * p.qf_w[l]; K = p.qf_w[l]; }
+    return 2.0 * (fl + 2.0 * p.B * K);
+}
+
+void sac_add_lin(SacWgrad& q, const float* dY, const float* X, int ldx, float* dW, float* db, int N, int K) {
+    PhLin& L = q.lin[q.count++];
+    L.dY = dY; L.X = X; L.dW = dW; L.db = db; L.N = N; L.K = K; L.ldx = ldx;
+    L.edge = (K & 15) != 0;
+    L.kgroups = cdiv(K, 64);
+    L.item0 = q.items;
+    q.items += cdiv(N, 16) * L.kgroups;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t m3l_sac_ws_bytes(const m3l_sac_desc* d, int B) {
+    char why[160];
+    if (!sac_shape_ok(d, B, why, sizeof(why))) return 256;
+    return (size_t)sac_args(d, B, 0).total * sizeof(float);
+}
+
+int m3l_sac_actor_fwd(const m3l_sac_desc* d, int B, const float* x, const float* noise, void* ws, float* actions, float* logp, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_actor_fwd: unsupported shape: %s", why);
+    if (sac_params_ok(d, SAC_ACTOR, "sac_actor_fwd")) return 1;
+    M3L_CHECK(x && actions && logp && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_actor_fwd: null argument, or x / ws not 16-byte aligned");
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacArgs p = sac_args(d, B, SAC_ACTOR);
+    ProfScope prof("sac_actor_fwd", B, p.F, p.A, sac_actor_flops(p), st, 4.0 * B * p.F);
+    sac_actor_fwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, x, noise, (float*)ws, actions, logp);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_actor_bwd(const m3l_sac_desc* d, int B, const float* x, const float* noise, const float* dactions, const float* dlogp, void* ws, float* dx,
+                      const m3l_sac_desc* grads, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_actor_bwd: unsupported shape: %s", why);
+    if (sac_params_ok(d, SAC_ACTOR, "sac_actor_bwd")) return 1;
+    M3L_CHECK(grads != nullptr && grads->n_pi == d->n_pi, "sac_actor_bwd: the gradient descriptor is null or has another layer count");
+    if (sac_params_ok(grads, SAC_ACTOR, "sac_actor_bwd (gradients)")) return 1;
+    M3L_CHECK(x && ws && dx && ph_aligned(x) && ph_aligned(ws) && ph_aligned(dx), "sac_actor_bwd: null argument, or x / ws / dx not 16-byte aligned");
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacArgs p = sac_args(d, B, SAC_ACTOR);
+    float* w = (float*)ws;
+    SacWgrad q;
+    memset(&q, 0, sizeof(q));
+    q.B = B;
+    const float* X = x;
+    int K = p.F;
+    for (int l = 0; l < p.n_pi; ++l) {
+        sac_add_lin(q, w + p.pi_d[l], X, K, grads->pi_weight[l], grads->pi_bias[l], p.pi_w[l], K);
+        X = w + p.pi_h[l];
+        K = p.pi_w[l];
+    }
+    sac_add_lin(q, w + p.dmu_off, X, K, grads->mu_weight, grads->mu_bias, p.A, K);
+    sac_add_lin(q, w + p.ds_off, X, K, grads->log_std_weight, grads->log_std_bias, p.A, K);
+    {
+        ProfScope prof("sac_actor_bwd_chain", B, p.F, p.A, sac_actor_flops(p), st, 4.0 * B * p.F);
+        sac_actor_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, noise, dactions, dlogp, w, dx);
+        M3L_LAUNCH_CHECK();
+    }
+    {
+        ProfScope prof("sac_actor_wgrad", B, q.items, p.A, sac_actor_flops(p), st, 0.0);
+        sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
+        M3L_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int m3l_sac_critic_fwd(const m3l_sac_desc* d, int B, const float* x, const float* actions, void* ws, float* q, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_critic_fwd: unsupported shape: %s", why);
+    if (sac_params_ok(d, SAC_CRITIC, "sac_critic_fwd")) return 1;
+    M3L_CHECK(x && actions && q && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_critic_fwd: null argument, or x / ws not 16-byte aligned");
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacArgs p = sac_args(d, B, SAC_CRITIC);
+    ProfScope prof("sac_critic_fwd", B, p.F, p.A, sac_critic_flops(p), st, 4.0 * B * p.K0);
+    sac_critic_fwd_kernel<<<dim3(cdiv(B, PH_TM), 2), 256, sac_lds_bytes(p), st>>>(p, x, actions, (float*)ws, q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_critic_bwd(const m3l_sac_desc* d, int B, const float* dq, void* ws, float* dactions, const m3l_sac_desc* grads, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_critic_bwd: unsupported shape: %s", why);
+    if (sac_params_ok(d, SAC_CRITIC, "sac_critic_bwd")) return 1;
+    M3L_CHECK(grads == nullptr || grads->n_qf == d->n_qf, "sac_critic_bwd: the gradient descriptor has another layer count");
+    if (grads != nullptr && sac_params_ok(grads, SAC_CRITIC, "sac_critic_bwd (gradients)")) return 1;
+    M3L_CHECK(ws && ph_aligned(ws), "sac_critic_bwd: ws is null or not 16-byte aligned");
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacArgs p = sac_args(d, B, SAC_CRITIC);
+    float* w = (float*)ws;
+    {
+        ProfScope prof("sac_critic_bwd_chain", B, p.F, p.A, sac_critic_flops(p), st, 0.0);
+        sac_critic_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, dq, w, dactions);
+        M3L_LAUNCH_CHECK();
+    }
+    if (grads == nullptr) return 0;
+    SacWgrad q;
+    memset(&q, 0, sizeof(q));
+    q.B = B;
+    for (int c = 0; c < 2; ++c) {
+        const float* X = w + p.xa_off;
+        int K = p.K0, ldx = p.Kp;
+        for (int l = 0; l < p.n_qf; ++l) {
+            sac_add_lin(q, w + p.qf_d[c][l], X, ldx, grads->qf_weight[c][l], grads->qf_bias[c][l], p.qf_w[l], K);
+            X = w + p.qf_h[c][l];
+            K = ldx = p.qf_w[l];
+        }
+        sac_add_lin(q, w + p.dq_off + (long)c * B, X, ldx, grads->q_weight[c], grads->q_bias[c], 1, K);
+    }
+    ProfScope prof("sac_critic_wgrad", B, q.items, p.A, sac_critic_flops(p), st, 0.0);
+    sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_td_target(const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones, float gamma,
+                      float ent_coef, const float* log_ent_coef, float* target_q, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_td_target: unsupported shape: %s", why);
+    if (sac_params_ok(d, SAC_ACTOR | SAC_CRITIC, "sac_td_target")) return 1;
+    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "sac_td_target: null argument, or x_next not 16-byte aligned");
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacArgs p = sac_args(d, B, SAC_ACTOR | SAC_CRITIC);
+    ProfScope prof("sac_td_target", B, p.F, p.A, sac_actor_flops(p) + sac_critic_flops(p), st, 4.0 * B * p.F);
+    sac_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, x_next, noise, rewards, dones, gamma, ent_coef, log_ent_coef, target_q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_critic_loss_fwd(const float* q, const float* target_q, int B, float* loss, float* coef, void* stream) {
+    M3L_CHECK(B >= 1, "sac_critic_loss_fwd: B=%d (B >= 1)", B);
+    M3L_CHECK(q && target_q && loss && coef, "sac_critic_loss_fwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_critic_loss_fwd", B, 0, 0, 8.0 * B, st, 20.0 * B);
+    sac_critic_loss_kernel<<<1, 256, 0, st>>>(q, target_q, B, loss, coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_critic_loss_bwd(const float* dloss, const float* coef, int B, float* dq, void* stream) {
+    M3L_CHECK(B >= 1, "sac_critic_loss_bwd: B=%d (B >= 1)", B);
+    M3L_CHECK(dloss && coef && dq, "sac_critic_loss_bwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_critic_loss_bwd", B, 0, 0, 2.0 * B, st, 16.0 * B);
+    sac_scale_kernel<<<cdiv(2L * B, 256), 256, 0, st>>>(dloss, coef, 2 * B, dq);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_actor_loss_fwd(const float* logp, const float* q, int B, float ent_coef, const float* log_ent_coef, float* loss, float* coef, void* stream) {
+    M3L_CHECK(B >= 1, "sac_actor_loss_fwd: B=%d (B >= 1)", B);
+    M3L_CHECK(logp && q && loss && coef, "sac_actor_loss_fwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_actor_loss_fwd", B, 0, 0, 6.0 * B, st, 24.0 * B);
+    sac_actor_loss_kernel<<<1, 256, 0, st>>>(logp, q, B, ent_coef, log_ent_coef, loss, coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_actor_loss_bwd(const float* dloss, const float* coef, int B, float* dlogp_dq, void* stream) {
+    M3L_CHECK(B >= 1, "sac_actor_loss_bwd: B=%d (B >= 1)", B);
+    M3L_CHECK(dloss && coef && dlogp_dq, "sac_actor_loss_bwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_actor_loss_bwd", B, 0, 0, 3.0 * B, st, 24.0 * B);
+    sac_scale_kernel<<<cdiv(3L * B, 256), 256, 0, st>>>(dloss, coef, 3 * B, dlogp_dq);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float target_entropy, int B, const float* dloss, float* loss, float* ent_coef,
+                          float* dlog_ent_coef, void* stream) {
+    M3L_CHECK(B >= 1, "sac_ent_coef_loss: B=%d (B >= 1)", B);
+    M3L_CHECK(log_ent_coef && logp && (loss || ent_coef || dlog_ent_coef), "sac_ent_coef_loss: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_ent_coef_loss", B, 0, 0, 2.0 * B, st, 4.0 * B);
+    sac_ent_coef_loss_kernel<<<1, 256, 0, st>>>(log_ent_coef, logp, target_entropy, B, dloss, loss, ent_coef, dlog_ent_coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,525 @@
+"""The SAC policy head on the HIP kernels of m3l_amd/csrc/sac.hip: everything between the extractor's features and the three optimizers in one
+gradient step of `SAC_MAE.train` (`models/sac_mae.py:303-366`), and the actor on every environment step.
+
+  head  : Stable-Baselines3's `SACPolicy` as `MAESACPolicy` configures it (`nn.ReLU`, `n_critics=2`, `share_features_extractor=True`,
+          `use_sde=False`): `actor.latent_pi` of Linear + ReLU, `actor.mu`, a state-dependent `actor.log_std` clamped to [-20, 2], the
+          tanh-squashed Gaussian, and twin critics `qf0` / `qf1` over cat([features, actions]).  SB3 is not part of the reference tree:
+          PARITY UNPINNED for its arithmetic, as for vit-pytorch and the PPO head; tests/sac_cases.py restates it from torch primitives.
+  step  : the reference's own lines: the entropy-coefficient loss (:311-312), the TD target (:326-335), the critic loss (:339-342), the actor
+          loss (:354-356) and the Polyak update (:365-366).
+  nodes : `SACActorFn` (1 launch forward, 2 backward), `SACCriticFn` (1 forward, 1 or 2 backward) and one node per loss (1 + 1).  `td_target`
+          is one launch without a tape.  The entropy coefficient travels as a float or as the device tensor `log_ent_coef`, whose exp the
+          kernels take: a step reads nothing back to the host (the reference reads four values).
+
+The features enter the critics detached (the extractor is shared, as in SB3), and `actor_loss` takes the critics' gradient in the actions only:
+the critic's parameters get nothing from it.  The reference lets `actor_loss.backward()` fill those `.grad`s and discards them at the next
+`critic.optimizer.zero_grad()` (:347).  Everything is float32; there is no eager fallback.
+"""
+import ctypes as C
+import numbers
+from typing import NamedTuple, Tuple
+
+import torch
+from torch import nn
+
+from . import _lib as L
+from .dino import update_moving_average
+from .functional import _require_cuda, _stream, _ws
+from .policy import MAX_ACTIONS, MAX_HIDDEN, MAX_WIDTH, _dev, _rows, _vec
+
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
+WB = Tuple[torch.Tensor, torch.Tensor]
+
+
+class SACHeadParams(NamedTuple):
+    """The parameter tensors of a head, torch.nn.Linear layouts.  pi: (weight, bias) per hidden layer of latent_pi; qf / qf_target: per critic,
+    (weight, bias) of every Linear, the last one being the Linear(., 1)."""
+    pi: Tuple[WB, ...]
+    mu: WB
+    log_std: WB
+    qf: Tuple[Tuple[WB, ...], Tuple[WB, ...]]
+    qf_target: Tuple[Tuple[WB, ...], Tuple[WB, ...]]
+
+    def actor_flat(self):
+        return [t for wb in self.pi for t in wb] + list(self.mu) + list(self.log_std)
+
+    def critic_flat(self, target=False):
+        return [t for net in (self.qf_target if target else self.qf) for wb in net for t in wb]
+
+    @staticmethod
+    def from_policy(policy) -> "SACHeadParams":
+        """From a module with SB3's attribute names (`actor.latent_pi / mu / log_std`, `critic.qf0 / qf1`, `critic_target.qf0 / qf1`): a `SACHead`,
+        or an SB3 `SACPolicy`, whose configuration is checked against what the kernels compute."""
+        _reject_sac_flags(policy)
+        actor, critic, target = policy.actor, policy.critic, policy.critic_target
+        if getattr(actor, "use_sde", False):
+            raise ValueError("use_sde=True (generalised state-dependent exploration) is not computed by the HIP SAC head")
+        if not isinstance(getattr(actor, "log_std", None), nn.Linear):
+            raise ValueError("actor.log_std is not an nn.Linear: the HIP SAC head computes a state-dependent log_std (use_sde=False) only")
+        for name, c in (("critic", critic), ("critic_target", target)):
+            n = getattr(c, "n_critics", 2)
+            if n != 2 or hasattr(c, "qf2") or not hasattr(c, "qf1"):
+                raise ValueError(f"{name}: n_critics={n if n != 2 else 'other than 2'}: the HIP SAC head computes exactly 2 critics")
+            if not getattr(c, "share_features_extractor", True):
+                raise ValueError("share_features_extractor=False: the HIP SAC head takes one feature vector for the actor and the critics")
+        pi = _relu_pairs(actor.latent_pi, "actor.latent_pi")
+        qf = tuple(_q_net(getattr(critic, f"qf{i}"), f"critic.qf{i}") for i in range(2))
+        qt = tuple(_q_net(getattr(target, f"qf{i}"), f"critic_target.qf{i}") for i in range(2))
+        return SACHeadParams(pi, (actor.mu.weight, actor.mu.bias), (actor.log_std.weight, actor.log_std.bias), qf, qt)
+
+
+def _relu_pairs(seq, name):
+    mods = list(seq)
+    if len(mods) % 2:
+        raise ValueError(f"{name}: Linear / ReLU pairs expected, got {len(mods)} modules")
+    out = []
+    for i in range(0, len(mods), 2):
+        if not isinstance(mods[i], nn.Linear) or mods[i].bias is None:
+            raise ValueError(f"{name}.{i}: nn.Linear with a bias expected, got {type(mods[i]).__name__}")
+        if not isinstance(mods[i + 1], nn.ReLU):
+            raise ValueError(f"{name}.{i + 1}: the HIP SAC head computes ReLU only, got {type(mods[i + 1]).__name__}")
+        out.append((mods[i].weight, mods[i].bias))
+    return tuple(out)
+
+
+def _q_net(seq, name):
+    mods = list(seq)
+    if not mods or not isinstance(mods[-1], nn.Linear) or mods[-1].bias is None or mods[-1].out_features != 1:
+        raise ValueError(f"{name}: a net ending in nn.Linear(., 1) with a bias expected")
+    return _relu_pairs(mods[:-1], name) + ((mods[-1].weight, mods[-1].bias),)
+
+
+def _reject_sac_flags(policy):
+    if getattr(policy, "use_sde", False):
+        raise ValueError("use_sde=True (generalised state-dependent exploration) is not computed by the HIP SAC head")
+    if not getattr(policy, "share_features_extractor", True):
+        raise ValueError("share_features_extractor=False: the HIP SAC head takes one feature vector for the actor and the critics")
+    n = getattr(policy, "n_critics", 2)
+    if n != 2:
+        raise ValueError(f"n_critics={n}: the HIP SAC head computes exactly 2 critics")
+
+
+def _check_width(w, what="width"):
+    if w < 16 or w % 16 or w > MAX_WIDTH:
+        raise ValueError(f"{what} {w}: features and hidden widths must be multiples of 16, at most {MAX_WIDTH}")
+
+
+def _arch(F, params: SACHeadParams):
+    """(F, A, pi widths, qf widths) with every shape checked; raises ValueError for a head outside the kernels' limits."""
+    F = int(F)
+    A = int(params.mu[0].shape[0])
+    for t in params.actor_flat() + params.critic_flat() + params.critic_flat(True):
+        if t.dtype != torch.float32:
+            raise ValueError(f"SAC head parameter of dtype {t.dtype}: the HIP SAC head computes in float32 and returns float32 gradients; "
+                             "keep the head's parameters in float32 whatever the encoder's compute type")
+    if len(params.pi) > MAX_HIDDEN:
+        raise ValueError(f"pi: {len(params.pi)} hidden layers (the HIP SAC head runs 0 to {MAX_HIDDEN} per net)")
+    k, pi = F, []
+    for l, (w, b) in enumerate(params.pi):
+        if w.dim() != 2 or w.shape[1] != k or tuple(b.shape) != (w.shape[0],):
+            raise ValueError(f"pi layer {l}: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not follow an input of width {k}")
+        k = int(w.shape[0])
+        pi.append(k)
+    for name, (w, b) in (("mu", params.mu), ("log_std", params.log_std)):
+        if tuple(w.shape) != (A, k) or tuple(b.shape) != (A,):
+            raise ValueError(f"{name}: weight {tuple(w.shape)} / bias {tuple(b.shape)}, expected ({A}, {k}) / ({A},)")
+    qf = None
+    for name, nets in (("qf", params.qf), ("qf_target", params.qf_target)):
+        if len(nets) != 2:
+            raise ValueError(f"{name}: {len(nets)} critics: the HIP SAC head computes exactly 2 critics")
+        for c, net in enumerate(nets):
+            if len(net) - 1 > MAX_HIDDEN:
+                raise ValueError(f"{name}{c}: {len(net) - 1} hidden layers (the HIP SAC head runs 0 to {MAX_HIDDEN} per net)")
+            k, ws = F + A, []
+            for l, (w, b) in enumerate(net):
+                n = 1 if l == len(net) - 1 else int(w.shape[0])
+                if w.dim() != 2 or tuple(w.shape) != (n, k) or tuple(b.shape) != (n,):
+                    raise ValueError(f"{name}{c} layer {l}: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not follow an input of width {k}")
+                k = n
+                ws.append(n)
+            ws = tuple(ws[:-1])
+            if qf is not None and ws != qf:
+                raise ValueError(f"{name}{c}: hidden widths {ws}, the other critics have {qf}: the two critics and their targets must be alike")
+            qf = ws
+    for w in (F,) + tuple(pi) + qf:
+        _check_width(w)
+    if not 1 <= A <= MAX_ACTIONS:
+        raise ValueError(f"{A} action dimensions (1 to {MAX_ACTIONS})")
+    return F, A, tuple(pi), qf
+
+
+def _desc(arch, actor=None, critic=None):
+    """m3l_sac_desc over the tensors of `actor` (SACHeadParams.actor_flat order) and / or `critic` (critic_flat order); the caller keeps them alive."""
+    F, A, pi, qf = arch
+    d = L.SacDesc()
+    d.features, d.actions, d.n_pi, d.n_qf = F, A, len(pi), len(qf)
+    for l, w in enumerate(pi):
+        d.pi_width[l] = w
+    for l, w in enumerate(qf):
+        d.qf_width[l] = w
+    if actor is not None:
+        it = iter(actor)
+        for l in range(len(pi)):
+            d.pi_weight[l], d.pi_bias[l] = next(it).data_ptr(), next(it).data_ptr()
+        d.mu_weight, d.mu_bias = next(it).data_ptr(), next(it).data_ptr()
+        d.log_std_weight, d.log_std_bias = next(it).data_ptr(), next(it).data_ptr()
+    if critic is not None:
+        it = iter(critic)
+        for c in range(2):
+            for l in range(len(qf)):
+                d.qf_weight[c][l], d.qf_bias[c][l] = next(it).data_ptr(), next(it).data_ptr()
+            d.q_weight[c], d.q_bias[c] = next(it).data_ptr(), next(it).data_ptr()
+    return d
+
+
+class SACActorFn(torch.autograd.Function):
+    """(features (B, F), noise (B, A) or None, arch, store, *actor parameters in actor_flat order) -> actions (B, A), log_prob (B,).  One launch;
+    the backward (2 launches) returns d features and every actor gradient.  `store` as in ActorCriticEvalFn: a backward may follow, so the
+    forward gets a workspace; the outputs have the same bits either way."""
+
+    @staticmethod
+    def forward(ctx, x, noise, arch, store, *params):
+        B, A = x.shape[0], arch[1]
+        flat = [_dev(t) for t in params]
+        lib = L.lib()
+        d = _desc(arch, actor=flat)
+        actions = torch.empty(B, A, dtype=torch.float32, device=x.device)
+        logp = torch.empty(B, dtype=torch.float32, device=x.device)
+        ws = _ws(lib.m3l_sac_ws_bytes(C.byref(d), B), x.device) if store else None
+        L.check(lib.m3l_sac_actor_fwd(C.byref(d), B, L.ptr(x), L.ptr(noise), L.ptr(ws), L.ptr(actions), L.ptr(logp), _stream()), "m3l_sac_actor_fwd")
+        ctx.saved = (x, noise, arch, flat, ws)
+        ctx.set_materialize_grads(False)
+        return actions, logp
+
+    @staticmethod
+    def backward(ctx, dactions, dlogp):
+        x, noise, arch, flat, ws = ctx.saved
+        if ws is None:
+            raise L.M3LError("SACActorFn: the forward ran without a workspace (store=False), so it has no backward")
+        B = x.shape[0]
+        da = None if dactions is None else _dev(dactions).reshape(B, arch[1])
+        dl = None if dlogp is None else _dev(dlogp).reshape(B)
+        grads = [torch.empty_like(t) for t in flat]
+        dx = torch.empty_like(x)
+        d, gd = _desc(arch, actor=flat), _desc(arch, actor=grads)
+        L.check(L.lib().m3l_sac_actor_bwd(C.byref(d), B, L.ptr(x), L.ptr(noise), L.ptr(da), L.ptr(dl), L.ptr(ws), L.ptr(dx), C.byref(gd), _stream()),
+                "m3l_sac_actor_bwd")
+        return (dx, None, None, None) + tuple(grads)
+
+
+class SACCriticFn(torch.autograd.Function):
+    """(features (B, F), actions (B, A), arch, store, param_grads, *critic parameters in critic_flat order) -> q (2, B).  One launch.  The backward
+    returns d actions (1 launch) and, with param_grads, every critic gradient (1 more); the features never take a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, actions, arch, store, param_grads, *params):
+        B = x.shape[0]
+        flat = [_dev(t) for t in params]
+        lib = L.lib()
+        d = _desc(arch, critic=flat)
+        q = torch.empty(2, B, dtype=torch.float32, device=x.device)
+        ws = _ws(lib.m3l_sac_ws_bytes(C.byref(d), B), x.device) if store else None
+        L.check(lib.m3l_sac_critic_fwd(C.byref(d), B, L.ptr(x), L.ptr(actions), L.ptr(ws), L.ptr(q), _stream()), "m3l_sac_critic_fwd")
+        ctx.saved = (arch, flat, ws, B, bool(param_grads))
+        return q
+
+    @staticmethod
+    def backward(ctx, dq):
+        arch, flat, ws, B, param_grads = ctx.saved
+        if ws is None:
+            raise L.M3LError("SACCriticFn: the forward ran without a workspace (store=False), so it has no backward")
+        dq = _dev(dq).reshape(2, B)
+        dactions = torch.empty(B, arch[1], dtype=torch.float32, device=dq.device) if ctx.needs_input_grad[1] else None
+        grads = [torch.empty_like(t) for t in flat] if param_grads else None
+        d = _desc(arch, critic=flat)
+        gd = C.byref(_desc(arch, critic=grads)) if param_grads else None
+        L.check(L.lib().m3l_sac_critic_bwd(C.byref(d), B, L.ptr(dq), L.ptr(ws), L.ptr(dactions), gd, _stream()), "m3l_sac_critic_bwd")
+        return (None, dactions, None, None, None) + (tuple(grads) if param_grads else (None,) * len(flat))
+
+
+class SACCriticLossFn(torch.autograd.Function):
+    """(q (2, B), target_q (B,)) -> 0.5 * sum_c mse(q_c, target_q), 0-d (`sac_mae.py:342`).  One launch each way; the gradient goes to q."""
+
+    @staticmethod
+    def forward(ctx, q, target_q):
+        B = target_q.numel()
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        coef = torch.empty(2, B, dtype=torch.float32, device=q.device)
+        L.check(L.lib().m3l_sac_critic_loss_fwd(L.ptr(q), L.ptr(target_q), B, L.ptr(loss), L.ptr(coef), _stream()), "m3l_sac_critic_loss_fwd")
+        ctx.saved = (coef, B)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        coef, B = ctx.saved
+        dq = torch.empty_like(coef)
+        L.check(L.lib().m3l_sac_critic_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), B, L.ptr(dq), _stream()), "m3l_sac_critic_loss_bwd")
+        return dq, None
+
+
+class SACActorLossFn(torch.autograd.Function):
+    """(log_prob (B,), q (2, B), ent_coef float or None, log_ent_coef tensor or None) -> mean(ent_coef * log_prob - min_c q_c), 0-d
+    (`sac_mae.py:354-356`).  One launch each way; the gradient goes to log_prob and q, the entropy coefficient is a constant (:311)."""
+
+    @staticmethod
+    def forward(ctx, logp, q, ent_coef, log_ent_coef):
+        B = logp.numel()
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        coef = torch.empty(3, B, dtype=torch.float32, device=q.device)
+        L.check(L.lib().m3l_sac_actor_loss_fwd(L.ptr(logp), L.ptr(q), B, 0.0 if ent_coef is None else float(ent_coef), L.ptr(log_ent_coef), L.ptr(loss),
+                                               L.ptr(coef), _stream()), "m3l_sac_actor_loss_fwd")
+        ctx.saved = (coef, B)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        coef, B = ctx.saved
+        out = torch.empty_like(coef)
+        L.check(L.lib().m3l_sac_actor_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), B, L.ptr(out), _stream()), "m3l_sac_actor_loss_bwd")
+        return out[0], out[1:], None, None
+
+
+class SACEntCoefLossFn(torch.autograd.Function):
+    """(log_ent_coef (1,), log_prob (B,), target_entropy) -> loss 0-d = -mean(log_ent_coef * (log_prob + target_entropy)), ent_coef 0-d =
+    exp(log_ent_coef) (no gradient) (`sac_mae.py:311-312`).  One launch each way; the gradient goes to log_ent_coef."""
+
+    @staticmethod
+    def forward(ctx, log_ent_coef, logp, target_entropy):
+        B = logp.numel()
+        loss = torch.empty((), dtype=torch.float32, device=logp.device)
+        ent = torch.empty((), dtype=torch.float32, device=logp.device)
+        L.check(L.lib().m3l_sac_ent_coef_loss(L.ptr(log_ent_coef), L.ptr(logp), float(target_entropy), B, None, L.ptr(loss), L.ptr(ent), None, _stream()),
+                "m3l_sac_ent_coef_loss")
+        ctx.saved = (log_ent_coef, logp, float(target_entropy), B)
+        ctx.mark_non_differentiable(ent)
+        return loss, ent
+
+    @staticmethod
+    def backward(ctx, dloss, _dent):
+        log_ent_coef, logp, target_entropy, B = ctx.saved
+        g = torch.empty_like(log_ent_coef)
+        L.check(L.lib().m3l_sac_ent_coef_loss(L.ptr(log_ent_coef), L.ptr(logp), target_entropy, B, L.ptr(_dev(dloss)), None, None, L.ptr(g), _stream()),
+                "m3l_sac_ent_coef_loss")
+        return g, None, None
+
+
+def _features(features, on_tape):
+    _require_cuda(features, "features")
+    if features.dim() != 2 or features.shape[0] < 1:
+        raise ValueError(f"features: (B, F) expected, got {tuple(features.shape)}")
+    if not on_tape:
+        return _dev(features)
+    x = features.float().contiguous()
+    return x.clone() if x.data_ptr() % 16 else x
+
+
+def _noise(noise, B, A, device, deterministic=False):
+    if deterministic:
+        return None
+    if noise is None:
+        return torch.randn(B, A, dtype=torch.float32, device=device)
+    noise = _rows(noise, "noise", A)
+    if noise.shape[0] != B:
+        raise ValueError(f"{B} feature rows but {noise.shape[0]} noise rows")
+    return noise
+
+
+def _require_params(flat):
+    for t in flat:
+        _require_cuda(t, "SAC head parameter")
+
+
+def _ent_args(ent_coef, log_ent_coef):
+    """(float or None, device tensor or None): exactly one of the two forms."""
+    if (ent_coef is None) == (log_ent_coef is None):
+        raise ValueError("give the entropy coefficient either as ent_coef (a number) or as log_ent_coef (a device tensor), one of the two")
+    if log_ent_coef is not None:
+        _require_cuda(log_ent_coef, "log_ent_coef")
+        if log_ent_coef.numel() != 1 or log_ent_coef.dtype != torch.float32:
+            raise ValueError(f"log_ent_coef: one float32 value expected, got {tuple(log_ent_coef.shape)} {log_ent_coef.dtype}")
+        return None, log_ent_coef.detach()
+    if isinstance(ent_coef, torch.Tensor):
+        raise ValueError("ent_coef is a number; pass a tensor as log_ent_coef (its exp is taken on the device)")
+    return float(ent_coef), None
+
+
+def action_log_prob(params: SACHeadParams, features, noise=None, deterministic=False):
+    """actions (B, A) = tanh(mu + exp(log_std) * noise), log_prob (B,); differentiable in the features and the actor's parameters.  Under `no_grad`,
+    or when nothing requires a gradient, no workspace is allocated and nothing is stored."""
+    flat = params.actor_flat()
+    _require_params(flat)
+    x = _features(features, on_tape=True)
+    arch = _arch(x.shape[1], params)
+    noise = _noise(noise, x.shape[0], arch[1], x.device, deterministic)
+    store = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in flat))
+    return SACActorFn.apply(x, noise, arch, store, *flat)
+
+
+def q_values(params: SACHeadParams, features, actions, target=False, param_grads=True):
+    """q (2, B) of both critics (the target critics with target=True) at cat([features, actions]); differentiable in the actions and, unless
+    param_grads=False, the critic's parameters; the features enter detached."""
+    flat = params.critic_flat(target)
+    _require_params(flat)
+    x = _features(features, on_tape=False)
+    arch = _arch(x.shape[1], params)
+    _require_cuda(actions, "actions")
+    if actions.dim() != 2 or actions.shape[1] != arch[1]:
+        raise ValueError(f"actions: (B, {arch[1]}) expected, got {tuple(actions.shape)}")
+    if actions.shape[0] != x.shape[0]:
+        raise ValueError(f"{x.shape[0]} feature rows but {actions.shape[0]} action rows")
+    a = actions.float().contiguous()
+    if a.data_ptr() % 16:
+        a = a.clone()
+    want = param_grads and any(t.requires_grad for t in flat)
+    store = torch.is_grad_enabled() and (a.requires_grad or want)
+    return SACCriticFn.apply(x, a, arch, store, want, *flat)
+
+
+@torch.no_grad()
+def td_target(params: SACHeadParams, next_features, rewards, dones, gamma, ent_coef=None, log_ent_coef=None, noise=None):
+    """target_q (B,) = r + (1 - done) * gamma * (min_c q_target_c(x', a') - ent_coef * logp') with (a', logp') = actor(x') (`sac_mae.py:326-335`).
+    One launch, no tape."""
+    af, cf = params.actor_flat(), params.critic_flat(True)
+    _require_params(af + cf)
+    x = _features(next_features, on_tape=False)
+    arch = _arch(x.shape[1], params)
+    B = x.shape[0]
+    noise = _noise(noise, B, arch[1], x.device)
+    ent, log_ent = _ent_args(ent_coef, log_ent_coef)
+    r, dn = _vec(rewards, "rewards", B), _vec(dones, "dones", B)
+    af, cf = [_dev(t) for t in af], [_dev(t) for t in cf]
+    d = _desc(arch, actor=af, critic=cf)
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    L.check(L.lib().m3l_sac_td_target(C.byref(d), B, L.ptr(x), L.ptr(noise), L.ptr(r), L.ptr(dn), float(gamma), 0.0 if ent is None else ent, L.ptr(log_ent),
+                                      L.ptr(out), _stream()), "m3l_sac_td_target")
+    return out
+
+
+def critic_loss_from(q, target_q):
+    """0.5 * sum_c mse(q_c, target_q) from q (2, B) of `q_values`."""
+    _require_cuda(q, "q")
+    B = q.shape[-1]
+    if q.dim() != 2 or q.shape[0] != 2 or q.dtype != torch.float32:
+        raise ValueError(f"q: (2, B) float32 expected, got {tuple(q.shape)} {q.dtype}")
+    return SACCriticLossFn.apply(q.contiguous(), _vec(target_q, "target_q", B))
+
+
+def actor_loss_from(log_prob, q, ent_coef=None, log_ent_coef=None):
+    """mean(ent_coef * log_prob - min_c q_c) from the outputs of `action_log_prob` and `q_values`."""
+    _require_cuda(q, "q")
+    _require_cuda(log_prob, "log_prob")
+    B = q.shape[-1]
+    if q.dim() != 2 or q.shape[0] != 2 or q.dtype != torch.float32 or log_prob.numel() != B or log_prob.dtype != torch.float32:
+        raise ValueError(f"q (2, B) and log_prob (B,) float32 expected, got {tuple(q.shape)} {q.dtype} and {tuple(log_prob.shape)} {log_prob.dtype}")
+    ent, log_ent = _ent_args(ent_coef, log_ent_coef)
+    return SACActorLossFn.apply(log_prob.contiguous().reshape(B), q.contiguous(), ent, log_ent)
+
+
+def ent_coef_loss(log_ent_coef, log_prob, target_entropy):
+    """(loss, ent_coef) as 0-d device tensors: -mean(log_ent_coef * (log_prob + target_entropy)) with log_prob a constant, exp(log_ent_coef)."""
+    _require_cuda(log_ent_coef, "log_ent_coef")
+    if log_ent_coef.numel() != 1 or log_ent_coef.dtype != torch.float32:
+        raise ValueError(f"log_ent_coef: one float32 value expected, got {tuple(log_ent_coef.shape)} {log_ent_coef.dtype}")
+    return SACEntCoefLossFn.apply(log_ent_coef, _vec(log_prob, "log_prob", log_prob.numel()), float(target_entropy))
+
+
+class _Actor(nn.Module):
+    def __init__(self, features_dim, pi, action_dim):
+        super().__init__()
+        mods, k = [], features_dim
+        for w in pi:
+            mods += [nn.Linear(k, w), nn.ReLU()]
+            k = w
+        self.latent_pi = nn.Sequential(*mods)
+        self.mu = nn.Linear(k, action_dim)
+        self.log_std = nn.Linear(k, action_dim)
+        self.use_sde = False
+
+
+class _Critic(nn.Module):
+    def __init__(self, features_dim, qf, action_dim):
+        super().__init__()
+        self.n_critics, self.share_features_extractor = 2, True
+        for i in range(2):
+            mods, k = [], features_dim + action_dim
+            for w in qf:
+                mods += [nn.Linear(k, w), nn.ReLU()]
+                k = w
+            mods.append(nn.Linear(k, 1))
+            setattr(self, f"qf{i}", nn.Sequential(*mods))
+
+
+class SACHead(nn.Module):
+    """The parameters of SB3's `SACPolicy` behind the features extractor, with its names and layouts (`actor.latent_pi.{0,2,..}`, `actor.mu`,
+    `actor.log_std`, `critic.qf{0,1}.{0,2,..}`, `critic_target.qf{0,1}.{0,2,..}`), so that part of an SB3 policy's state dict loads with
+    strict=True, and the head's part of `SAC_MAE.train` computed by the HIP kernels.  `critic_target` starts as a copy of `critic` and takes no
+    gradient.  Initial values are torch's nn.Linear defaults, as SB3's SAC uses; parity with SB3 is unpinned (SB3 is not in the reference tree)."""
+
+    def __init__(self, features_dim, action_dim, net_arch=None, n_critics=2, activation_fn=nn.ReLU, use_sde=False, share_features_extractor=True):
+        super().__init__()
+        if activation_fn is not nn.ReLU:
+            raise ValueError(f"activation_fn={getattr(activation_fn, '__name__', activation_fn)}: the HIP SAC head computes ReLU only")
+        self.use_sde, self.share_features_extractor, self.n_critics = bool(use_sde), bool(share_features_extractor), n_critics
+        _reject_sac_flags(self)
+        if hasattr(action_dim, "n") or hasattr(action_dim, "nvec"):
+            raise ValueError(f"action_dim={action_dim!r}: discrete action spaces are not computed by the HIP SAC head; pass the length of a "
+                             "continuous (Box) action vector")
+        if isinstance(action_dim, bool) or not isinstance(action_dim, numbers.Integral):
+            raise ValueError(f"action_dim={action_dim!r}: an integer expected, the length of a continuous (Box) action vector")
+        action_dim = int(action_dim)
+        if net_arch is None:
+            net_arch = dict(pi=[256, 256], qf=[256, 256])
+        if isinstance(net_arch, (list, tuple)):
+            net_arch = dict(pi=list(net_arch), qf=list(net_arch))
+        pi, qf = [int(w) for w in net_arch.get("pi", [])], [int(w) for w in net_arch.get("qf", [])]
+        for w in [int(features_dim)] + pi + qf:
+            _check_width(w)
+        if len(pi) > MAX_HIDDEN or len(qf) > MAX_HIDDEN:
+            raise ValueError(f"net_arch {net_arch}: 0 to {MAX_HIDDEN} hidden layers per net")
+        if not 1 <= action_dim <= MAX_ACTIONS:
+            raise ValueError(f"action_dim={action_dim}: 1 to {MAX_ACTIONS}")
+        self.features_dim, self.action_dim = int(features_dim), action_dim
+        self.actor = _Actor(self.features_dim, pi, action_dim)
+        self.critic = _Critic(self.features_dim, qf, action_dim)
+        self.critic_target = _Critic(self.features_dim, qf, action_dim)
+        self.critic_target.load_state_dict(self.critic.state_dict())
+        self.critic_target.requires_grad_(False)
+
+    def params(self) -> SACHeadParams:
+        return SACHeadParams.from_policy(self)
+
+    @torch.no_grad()
+    def forward(self, features, deterministic=False, noise=None):
+        """actions (B, A), no gradient: SB3's `_predict` after `extract_features`."""
+        return action_log_prob(self.params(), features, noise, deterministic)[0]
+
+    def action_log_prob(self, features, noise=None):
+        return action_log_prob(self.params(), features, noise)
+
+    def q_values(self, features, actions, target=False):
+        return q_values(self.params(), features, actions, target)
+
+    def td_target(self, next_features, rewards, dones, gamma, ent_coef=None, log_ent_coef=None, noise=None):
+        return td_target(self.params(), next_features, rewards, dones, gamma, ent_coef, log_ent_coef, noise)
+
+    def critic_loss(self, features, actions, target_q):
+        """0.5 * sum_c mse(q_c(features, actions), target_q): 2 launches forward, 3 backward."""
+        with torch.no_grad():
+            a = actions.detach()
+        return critic_loss_from(q_values(self.params(), features, a), target_q)
+
+    def actor_loss(self, features, ent_coef=None, log_ent_coef=None, noise=None):
+        """(loss, log_prob.detach()): mean(ent_coef * log_prob - min_c q_c(features, a_pi)).  The critics give their gradient in the actions only:
+        their parameters receive nothing from this loss."""
+        p = self.params()
+        a_pi, logp = action_log_prob(p, features, noise)
+        q = q_values(p, features, a_pi, param_grads=False)
+        return actor_loss_from(logp, q, ent_coef, log_ent_coef), logp.detach()
+
+    def ent_coef_loss(self, log_ent_coef, log_prob, target_entropy):
+        return ent_coef_loss(log_ent_coef, log_prob, target_entropy)
+
+    @torch.no_grad()
+    def polyak_update(self, tau):
+        """critic_target = (1 - tau) * critic_target + tau * critic over every tensor, in one multi-tensor launch (`sac_mae.py:366`)."""
+        update_moving_average(self.critic_target, self.critic, 1.0 - float(tau))

@@ -1,0 +1,153 @@
+"""Time of the SAC policy head on synthetic features (EXPERIMENTS.md "SAC policy head"); no simulator, no extractor.  The sibling of
+policy_head_bench.py, with its method (alternating windows, device events, the library's event brackets, torch.profiler's kernel records).
+
+  (a) the head's part of one gradient step of SAC_MAE.train (sac_mae.py:303-366) at B = 256, F = 256, pi = qf = [256, 256], A = 7,
+      ent_coef = "auto" (Train_sacmae.py): action_log_prob, the entropy-coefficient loss and its backward, the TD target, the critic loss and
+      its backward, the actor loss and its backward, the Polyak update.  Optimizer steps are not part of it on either path.
+  (b) the actor under no_grad at B = 8: the head of one environment step
+
+each on two paths on the same GPU:
+  hip    m3l_amd.SACHead (m3l_amd/csrc/sac.hip)
+  eager  the float32 torch restatement of the same arithmetic (tests/sac_cases.py: nn.functional.linear, relu, clamp, tanh,
+         torch.distributions.Normal, the lines of sac_mae.py, autograd, SB3's polyak_update loop): what a user of the reference runs today
+and, for (a), with and without the reads of the logged values: the reference reads four scalars one by one (`.item()`, sac_mae.py:313, 317, 344,
+357), the HIP path needs none for the step and reads its four 0-d tensors in one stacked copy when they are to be logged.
+
+The figures per path are policy_head_bench.py's (call_us, host_us, entry_points, kernel_us / launches / copies).  Both paths' losses are printed,
+so that a wrong result cannot pass as a fast one.  Without a GPU the tool fails; it has no fallback.
+
+Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30]   (one JSON line on stdout)"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+from torch.nn import functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import sac_cases as SC  # noqa: E402
+import m3l_amd  # noqa: E402
+from m3l_amd import sac as SH  # noqa: E402
+from policy_head_bench import alternate, counted, entry_points  # noqa: E402
+
+DEV = "cuda:0"
+ARCH = (256, (256, 256), (256, 256), 7)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=500, help="calls per timed window of (a); (b) takes ten times as many")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating windows per path")
+    ap.add_argument("--warmup", type=int, default=30)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sac_head_bench: no GPU")
+    out = {"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}}
+
+    # (a) one gradient step
+    c = SC.make_inputs(ARCH, 256, False, True, seed=9)
+    head = m3l_amd.SACHead(ARCH[0], ARCH[3], net_arch=dict(pi=list(ARCH[1]), qf=list(ARCH[2])))
+    head.load_state_dict({k: torch.from_numpy(v) for k, v in c["params"].items()})
+    head = head.to(DEV)
+    P = dict(head.named_parameters())
+    t = {k: torch.from_numpy(c[k]).to(DEV) for k in ("x", "x_next", "noise_pi", "noise_next", "a_replay", "rewards", "dones")}
+    x = t["x"].clone().requires_grad_(True)
+    log_ent = torch.tensor([c["log_ent_coef"]], dtype=torch.float32, device=DEV, requires_grad=True)
+    critic_params = [p for n, p in P.items() if n.startswith("critic.")]
+    target_params = [p for n, p in P.items() if n.startswith("critic_target.")]
+    gamma, tau, te = c["gamma"], c["tau"], c["target_entropy"]
+
+    def zero():
+        x.grad = log_ent.grad = None
+        for p in head.parameters():
+            p.grad = None
+
+    def hip(read):
+        zero()
+        params = head.params()
+        a_pi, logp = SH.action_log_prob(params, x, t["noise_pi"])
+        ent_loss, ent = SH.ent_coef_loss(log_ent, logp, te)
+        ent_loss.backward()
+        target_q = SH.td_target(params, t["x_next"], t["rewards"], t["dones"], gamma, log_ent_coef=log_ent, noise=t["noise_next"])
+        critic_loss = SH.critic_loss_from(SH.q_values(params, x, t["a_replay"]), target_q)
+        critic_loss.backward()
+        actor_loss = SH.actor_loss_from(logp, SH.q_values(params, x, a_pi, param_grads=False), log_ent_coef=log_ent)
+        actor_loss.backward()
+        head.polyak_update(tau)
+        if read:
+            torch.stack([ent_loss.detach(), ent, critic_loss.detach(), actor_loss.detach()]).cpu()
+        return actor_loss, critic_loss
+
+    def eager(read):
+        zero()
+        o = SC.actor_forward(P, x, t["noise_pi"])                                               # :303
+        a_pi, log_prob = o["actions"], o["log_prob"].reshape(-1, 1)
+        ent_coef = torch.exp(log_ent.detach())                                                  # :311
+        ent_loss = -(log_ent * (log_prob + te).detach()).mean()                                 # :312
+        if read:
+            ent_loss.item(), ent_coef.item()                                                    # :313, :317
+        ent_loss.backward()
+        with torch.no_grad():                                                                   # :326-335
+            n = SC.actor_forward(P, t["x_next"], t["noise_next"])
+            qn, _ = SC.critic_forward(P, "critic_target", t["x_next"], n["actions"])
+            nq = torch.min(qn.t(), dim=1, keepdim=True)[0] - ent_coef * n["log_prob"].reshape(-1, 1)
+            target_q = t["rewards"].reshape(-1, 1) + (1 - t["dones"].reshape(-1, 1)) * gamma * nq
+        q, _ = SC.critic_forward(P, "critic", x, t["a_replay"])                                 # :339
+        critic_loss = 0.5 * sum(F.mse_loss(qc.reshape(-1, 1), target_q) for qc in q)            # :342
+        if read:
+            critic_loss.item()                                                                  # :344
+        critic_loss.backward()
+        for p in critic_params:                                                                 # :347 of the next step
+            p.grad = None
+        qp, _ = SC.critic_forward(P, "critic", x, a_pi)                                         # :354
+        actor_loss = (ent_coef * log_prob - torch.min(qp.t(), dim=1, keepdim=True)[0]).mean()   # :356
+        if read:
+            actor_loss.item()                                                                   # :357
+        actor_loss.backward()
+        with torch.no_grad():                                                                   # :366, SB3's polyak_update
+            for p, tp in zip(critic_params, target_params):
+                tp.mul_(1 - tau)
+                torch.add(tp, p, alpha=tau, out=tp)
+        return actor_loss, critic_loss
+    fns = {"hip": lambda: hip(False), "eager": lambda: eager(False), "hip_values_read": lambda: hip(True), "eager_values_read": lambda: eager(True)}
+    res, last = alternate(fns, a.iters, a.warmup, a.rounds)
+    for name, fn in fns.items():
+        res[name].update(counted(fn))
+        res[name]["actor_loss"], res[name]["critic_loss"] = float(last[name][0].detach()), float(last[name][1].detach())
+    res["hip"]["entry_points"] = entry_points(fns["hip"])
+    res["hip_over_eager_call"] = round(res["hip"]["call_us"] / res["eager"]["call_us"], 3)
+    res["hip_over_eager_call_values_read"] = round(res["hip_values_read"]["call_us"] / res["eager_values_read"]["call_us"], 3)
+    out["gradient_step_B256"] = res
+
+    # (b) one environment step
+    xb = torch.randn(8, ARCH[0], generator=torch.Generator().manual_seed(3)).to(DEV)
+    noise = torch.randn(8, ARCH[3], generator=torch.Generator().manual_seed(4)).to(DEV)
+
+    def hip_act():
+        return head(xb, noise=noise)
+
+    def eager_act():
+        with torch.no_grad():          # SB3's Actor.forward: the action alone, no log-probability
+            h = xb
+            for l in range(len(ARCH[1])):
+                h = torch.relu(F.linear(h, P[f"actor.latent_pi.{2 * l}.weight"], P[f"actor.latent_pi.{2 * l}.bias"]))
+            mu = F.linear(h, P["actor.mu.weight"], P["actor.mu.bias"])
+            s = torch.clamp(F.linear(h, P["actor.log_std.weight"], P["actor.log_std.bias"]), SC.LOG_STD_MIN, SC.LOG_STD_MAX)
+            return torch.tanh(mu + s.exp() * noise)
+    fns = {"hip": hip_act, "eager": eager_act}
+    res, last = alternate(fns, 10 * a.iters, a.warmup, a.rounds)
+    for name, fn in fns.items():
+        res[name].update(counted(fn))
+        res[name]["actions_sum"] = float(last[name].sum())
+    res["hip"]["entry_points"] = entry_points(hip_act)
+    res["hip_over_eager_call"] = round(res["hip"]["call_us"] / res["eager"]["call_us"], 3)
+    out["actor_no_grad_B8"] = res
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
