@@ -107,6 +107,11 @@ int m3l_set_attn_block(int mode);
  * backward, dxn1) runs once for all heads, the attention backward as (head, tile) tasks over the waves; 0 = one head after the other.
  * env M3L_ATTN_BWD_HEADS sets the initial mode.  Returns the previous mode.  Bit-identical results either way. */
 int m3l_set_attn_bwd_heads(int mode);
+/* The per-sample attention backward of long sequences (attn_t192_bwd, n <= 192, dim 192 / 256): 1 = the four DMA waves fetch the q, k, v, o
+ * rows and the lse of head h + 1 into their registers while the compute waves run the two passes of head h, and write them to the LDS images
+ * between the heads (no global load in the compute waves' head loop); 0 = every compute wave loads its own rows at the head of each head.
+ * env M3L_ATTN_T192_PREFETCH sets the initial mode (default 1).  Returns the previous mode.  Bit-identical results either way. */
+int m3l_set_attn_t192_bwd_prefetch(int mode);
 /* Short-sequence stacks whose every half layer takes a block kernel, a bit mask: 1 (default) = the whole forward of the stack in ONE launch
  * (the same kernel bodies, layer after layer inside one workgroup per sample); 2 = also its backward as one launch per weight-gradient
  * group of layers (opt-in: measured slower beside the side stream's weight gradients); 0 = one launch per half layer; env M3L_ENC_MEGA.

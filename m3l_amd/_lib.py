@@ -74,6 +74,7 @@ _SIGS = {
     "m3l_set_attn_block": (c_i, [c_i]),
     "m3l_set_attn_phase_buffer": (None, [c_p]),
     "m3l_set_attn_bwd_heads": (c_i, [c_i]),
+    "m3l_set_attn_t192_bwd_prefetch": (c_i, [c_i]),
     "m3l_set_enc_mega": (c_i, [c_i]),
     "m3l_set_drop_h": (c_i, [c_i]),
     "m3l_set_direct_conv": (c_i, [c_i]),

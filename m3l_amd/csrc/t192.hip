@@ -1096,7 +1096,38 @@ template <int D> struct AttnBwdLayout {
     static_assert(TOTAL <= 160 * 1024, "LDS");
 };
 
-template <int D, int H>
+#ifndef T192B_STAMP
+#define T192B_STAMP 0       // diagnostic builds only: shader-clock stamps at the phase boundaries of attn_t192_bwd (tools/attn_t192_bwd_phase_probe.py)
+#endif
+#if T192B_STAMP
+__device__ unsigned long long* d_t192b_stamps;      // [blocks][12 compute waves][16] accumulated cycles per phase
+#define T192B_T0() unsigned long long tb_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tb_last = __builtin_readcyclecounter();
+#define T192B_T(i, later)                                              \
+    {                                                                  \
+        const unsigned long long t_ = __builtin_readcyclecounter();    \
+        if (later) tb_acc[(i) + 4] += t_ - tb_last;                    \
+        else tb_acc[i] += t_ - tb_last;                                \
+        tb_last = t_;                                                  \
+    }
+#define T192B_TEND()                                                                            \
+    if (d_t192b_stamps && lane == 0) {                                                          \
+        unsigned long long* o_ = d_t192b_stamps + ((long)blockIdx.x * 12 + wave) * 16;          \
+        for (int i_ = 0; i_ < 9; ++i_) o_[i_] = tb_acc[i_];                                     \
+    }
+#else
+#define T192B_T0()
+#define T192B_T(i, later)
+#define T192B_TEND()
+#endif
+// phases: 0 kernel head (dx1_t fragments requested); per head, 1-4 for head 0 and 5-8 summed over the later heads: rows requested -> B0,
+// dO + Dsum + images written -> B1, query-owner pass, key-owner pass with the dqkv stores -> B2
+
+// PF = 1 (m3l_set_attn_t192_bwd_prefetch): the compute waves' head loop has no global load.  The four DMA waves, idle but for 24 KiB of Wo^T per
+// head, request the q, k, v, o rows and the lse of head h + 1 right after B1 of head h (48 tokens per wave: 24 16-byte loads per lane, held in
+// registers across the two passes), and after B2 write them to the Q / K / V images, o to the dO image and lse to Ls — the values the compute
+// waves stage themselves when PF = 0 (rows from n on: zeros, lse = +inf).  After B0 every compute lane takes its q and o pieces back from
+// the images, forms dO, Dsum with the same operations and writes dO over the 16 bytes it read o from.  Same barriers (B0, B1, B2) either way.
+template <int D, int H, int PF>
 __global__ __launch_bounds__((TileCfg<D, 12, 1>::THREADS)) void attn_t192_bwd_kernel(const bf16* __restrict__ dx1t, const bf16* __restrict__ qkv,
                                                                                 const bf16* __restrict__ o, const float* __restrict__ lse,
                                                                                 const bf16* __restrict__ WoT, int n, bf16* __restrict__ dqkv) {
@@ -1122,13 +1153,68 @@ __global__ __launch_bounds__((TileCfg<D, 12, 1>::THREADS)) void attn_t192_bwd_ke
         // the previous head's blocks (barrier B1 of that head), two barriers before they are needed
         const int dw = wave - NCW;
         auto load_w = [&](int h) {
+            int ln = lane;
+            if constexpr (PF) asm volatile("" : "+v"(ln));      // (as tv below: the piece addresses are not held across the head loop)
 #pragma unroll
             for (int j = 0; j < Cf::PPW; ++j) {
                 const int p = dw * Cf::PPW + j;
-                if (p < Cf::PCB) dma_f1_piece(WoT, D, 64 * h, p, WS, lane);
-                else dma_f1_piece(WoT, D, 64 * h + 32, p - Cf::PCB, WS + Cf::BLK, lane);
+                if (p < Cf::PCB) dma_f1_piece(WoT, D, 64 * h, p, WS, ln);
+                else dma_f1_piece(WoT, D, 64 * h + 32, p - Cf::PCB, WS + Cf::BLK, ln);
             }
         };
+        if constexpr (PF) {
+            // piece i of an array: tokens 48 dw + 8 i .. + 7, lane = (token lane >> 3, 16-byte chunk lane & 7) -> whole 128-byte rows per 8 lanes
+            const int t0 = 48 * dw + (lane >> 3), c8 = 8 * (lane & 7), tl = 64 * dw + lane;
+            u4v_t rq[6], rk[6], rv[6], ro[6];
+            float rl;
+            // bounded descriptors of the sample's rows; 32-bit row offsets, the head's columns in the scalar offset
+            const __amdgpu_buffer_rsrc_t qr = rows_rsrc(qkv + row0 * QKV, (long)n * QKV * 2), orr = rows_rsrc(o + row0 * D, (long)n * D * 2);
+            // (tv: the lane's first token through an opaque copy per call, so that the 30-odd offsets derived from it are recomputed where they
+            // are used and not kept in registers across the head loop beside the 96 that hold the rows)
+            auto load_rows = [&](int h) {
+                int tv = t0;
+                asm volatile("" : "+v"(tv));
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    const int tc = min(tv + 8 * i, n - 1);    // rows from n on: a valid row of the sample, zeroed where it is written
+                    const int qo = tc * (QKV * 2) + c8 * 2, oo = tc * (D * 2) + c8 * 2;
+                    rq[i] = __builtin_amdgcn_raw_buffer_load_b128(qr, qo, 128 * h, 0);
+                    ro[i] = __builtin_amdgcn_raw_buffer_load_b128(orr, oo, 128 * h, 0);
+                    rk[i] = __builtin_amdgcn_raw_buffer_load_b128(qr, qo + 2 * D, 128 * h, 0);
+                    rv[i] = __builtin_amdgcn_raw_buffer_load_b128(qr, qo + 4 * D, 128 * h, 0);
+                }
+                rl = lse[((long)b * H + h) * n + min(tl, n - 1)];
+            };
+            auto stage_rows = [&]() {
+                int tv = t0;
+                asm volatile("" : "+v"(tv));
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    const int t = tv + 8 * i, off = t * KROW + c8;
+                    const bool in = t < n;
+                    *reinterpret_cast<u4v_t*>(Qs + off) = in ? rq[i] : u4v_t{0u, 0u, 0u, 0u};
+                    *reinterpret_cast<u4v_t*>(Gs + off) = in ? ro[i] : u4v_t{0u, 0u, 0u, 0u};
+                    *reinterpret_cast<u4v_t*>(Ks + off) = in ? rk[i] : u4v_t{0u, 0u, 0u, 0u};
+                    *reinterpret_cast<u4v_t*>(Vs + off) = in ? rv[i] : u4v_t{0u, 0u, 0u, 0u};
+                }
+                if (tl < 192) Ls[tl] = tl < n ? rl : INFINITY;                  // rows past n: P = exp(.. - inf) = 0
+            };
+            load_w(0);
+            load_rows(0);
+            for (int h = 0; h < H; ++h) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                stage_rows();                                 // the images are free: B2 of head h - 1
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();                 // B0: W, rows and lse of head h are in LDS
+                __builtin_amdgcn_s_barrier();                 // B1: dO written, W slot free
+                if (h + 1 < H) {
+                    load_w(h + 1);
+                    load_rows(h + 1);
+                }
+                __builtin_amdgcn_s_barrier();                 // B2: both passes of head h done
+            }
+            return;
+        }
         load_w(0);
         for (int h = 0; h < H; ++h) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1143,12 +1229,36 @@ __global__ __launch_bounds__((TileCfg<D, 12, 1>::THREADS)) void attn_t192_bwd_ke
     const bool ok = tok < n;
     const long trow = row0 + tok;
 
+    T192B_T0();
     Frag<bf16> xb[KS];
     load_tok_frags(dx1t, ok ? trow : row0 + n - 1, ok, g, xb);
+    T192B_T(0, false);
     for (int h = 0; h < H; ++h) {
         Frag<bf16> fq[2], fdo[2];
         float dpart = 0.f;
-        {
+        if constexpr (PF) {
+        __builtin_amdgcn_s_barrier();                         // B0: the DMA waves wrote the head's q, k, v, o rows and lse; W landed
+        asm volatile("" ::: "memory");
+        T192B_T(1, h > 0);
+        // ---- dO (computed) over this lane's own o piece in the dO image; its q piece back from the Q image; D
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb) {
+            f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                a0 = mma16(frag_f1p(WS + bb * Cf::BLK, 0, ks, li, g), xb[ks], a0);
+                a1 = mma16(frag_f1p(WS + bb * Cf::BLK, 1, ks, li, g), xb[ks], a1);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { fdo[bb].v[e] = (bf16)a0[e]; fdo[bb].v[4 + e] = (bf16)a1[e]; }    // head dims 32 bb + 8 g + j
+            const int off = tok * KROW + 32 * bb + 8 * g;
+            fq[bb] = load_kc(Qs + off);
+            const bf16x8 ov = load_kc(Gs + off).v;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) dpart += (float)fdo[bb].v[j] * (float)ov[j];
+            *reinterpret_cast<bf16x8*>(Gs + off) = fdo[bb].v;
+        }
+        } else {
         // this wave's 16 rows of q, k, v, o of the head and the lse: requested before the barrier, in flight behind the dO products
         uint4 zq[2], zk[2], zv[2], zo[2];
 #pragma unroll
@@ -1164,6 +1274,7 @@ __global__ __launch_bounds__((TileCfg<D, 12, 1>::THREADS)) void attn_t192_bwd_ke
         }
         __builtin_amdgcn_s_barrier();                         // B0
         asm volatile("" ::: "memory");
+        T192B_T(1, h > 0);
         // ---- stage this wave's 16 tokens: dO (computed), Q, K, V rows; D and lse
 #pragma unroll
         for (int bb = 0; bb < 2; ++bb) {
@@ -1187,11 +1298,18 @@ __global__ __launch_bounds__((TileCfg<D, 12, 1>::THREADS)) void attn_t192_bwd_ke
         }
         }
         const float Dq = col4_sum(dpart);
-        const float lq = ok ? lse[((long)b * H + h) * n + tok] : INFINITY;          // rows past n: P = exp(.. - inf) = 0
-        if (g == 0) { Ls[tok] = lq; Ds[tok] = Dq; }
+        float lq;
+        if constexpr (PF) {
+            lq = Ls[tok];
+            if (g == 0) Ds[tok] = Dq;
+        } else {
+            lq = ok ? lse[((long)b * H + h) * n + tok] : INFINITY;                  // rows past n: P = exp(.. - inf) = 0
+            if (g == 0) { Ls[tok] = lq; Ds[tok] = Dq; }
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                         // B1: images complete
         asm volatile("" ::: "memory");
+        T192B_T(2, h > 0);
         // ---- query-owner pass: dQ^T[d][query] = sum_key K^T[d][key] dS^T[key][query], 32 keys at a time (P needs no row reduction
         // here: the softmax statistics come from the forward's lse)
         {
@@ -1230,6 +1348,7 @@ __global__ __launch_bounds__((TileCfg<D, 12, 1>::THREADS)) void attn_t192_bwd_ke
                 }
             }
         }
+        T192B_T(3, h > 0);
         // ---- key-owner pass: dV^T[d][key] = sum_q dO^T[d][q] P[q][key],  dK^T[d][key] = sum_q Q^T[d][q] dS[q][key]
         {
             Frag<bf16> fk[2], fv[2];                          // this lane's own key / value rows, back from the images
@@ -1282,7 +1401,9 @@ __global__ __launch_bounds__((TileCfg<D, 12, 1>::THREADS)) void attn_t192_bwd_ke
             }
         }
         __builtin_amdgcn_s_barrier();                         // B2: every wave is done with the images
+        T192B_T(4, h > 0);
     }
+    T192B_TEND();
 }
 
 
@@ -1437,6 +1558,18 @@ extern "C" int m3l_set_t192(int on) {
     return old;
 }
 int m3l_mlp_t192_short(void) { return t192_state() > 0 && (g_t192 & 2); }
+
+// attn_t192_bwd: 1 = the DMA waves fetch the next head's rows behind the passes (PF = 1), 0 = every compute wave loads its own rows
+static int g_attn_t192_pf = -1;     // -1 = environment not read yet
+static int attn_t192_prefetch() {
+    if (g_attn_t192_pf < 0) g_attn_t192_pf = getenv("M3L_ATTN_T192_PREFETCH") ? (atoi(getenv("M3L_ATTN_T192_PREFETCH")) != 0) : 1;
+    return g_attn_t192_pf;
+}
+extern "C" int m3l_set_attn_t192_bwd_prefetch(int mode) {
+    const int old = attn_t192_prefetch();
+    g_attn_t192_pf = mode != 0;
+    return old;
+}
 static bool forced() { return t192_state() > 0 && (g_t192 & 4); }
 
 static bool width_ok(int D) { return D == 192 || D == 256 || D == 384; }
@@ -1689,18 +1822,26 @@ int m3l_attn_t192_bwd(int Dm, int B, int n, const void* dx1t, const void* qkv, c
     const int H = Dm / 64;
     ProfScope prof("attn_t192_bwd", B, n, Dm, 2.0 * B * n * (double)Dm * Dm + 14.0 * B * H * (double)n * n * 64, st,
                    (double)B * n * (Dm * 2.0 + 3.0 * Dm * 2.0 + Dm * 2.0 + 3.0 * Dm * 2.0));
-    if (Dm == 192) {
-        LDS_ONCE((attn_t192_bwd_kernel<192, 3>), (AttnBwdLayout<192>::TOTAL));
-        attn_t192_bwd_kernel<192, 3><<<B, TileCfg<192, 12, 1>::THREADS, AttnBwdLayout<192>::TOTAL, st>>>((const bf16*)dx1t, (const bf16*)qkv, (const bf16*)o, lse,
-                                                                                                   (const bf16*)woT, n, (bf16*)dqkv);
-    } else {
-        LDS_ONCE((attn_t192_bwd_kernel<256, 4>), (AttnBwdLayout<256>::TOTAL));
-        attn_t192_bwd_kernel<256, 4><<<B, TileCfg<256, 12, 1>::THREADS, AttnBwdLayout<256>::TOTAL, st>>>((const bf16*)dx1t, (const bf16*)qkv, (const bf16*)o, lse,
-                                                                                                   (const bf16*)woT, n, (bf16*)dqkv);
+    M3L_CHECK(n >= 1 && n <= 192, "attn_t192_bwd: sequence length %d", n);
+#define ATTN_T192_BWD_GO(DV, HV, PFV)                                                                                                              \
+    {                                                                                                                                              \
+        LDS_ONCE((attn_t192_bwd_kernel<DV, HV, PFV>), (AttnBwdLayout<DV>::TOTAL));                                                                 \
+        attn_t192_bwd_kernel<DV, HV, PFV><<<B, TileCfg<DV, 12, 1>::THREADS, AttnBwdLayout<DV>::TOTAL, st>>>((const bf16*)dx1t, (const bf16*)qkv,     \
+                                                                                                           (const bf16*)o, lse, (const bf16*)woT, n, \
+                                                                                                           (bf16*)dqkv);                           \
     }
+    const int pf = attn_t192_prefetch();
+    if (Dm == 192 && pf) ATTN_T192_BWD_GO(192, 3, 1)
+    else if (Dm == 192) ATTN_T192_BWD_GO(192, 3, 0)
+    else if (pf) ATTN_T192_BWD_GO(256, 4, 1)
+    else ATTN_T192_BWD_GO(256, 4, 0)
+#undef ATTN_T192_BWD_GO
     M3L_LAUNCH_CHECK();
     return 0;
 }
+#if T192B_STAMP
+extern "C" int m3l_t192b_set_stamps(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(d_t192b_stamps), &p, sizeof(p)) == hipSuccess ? 0 : 1; }
+#endif
 
 // direct entry for tools/t192_probe.py (kernel timing outside the MAE plan)
 extern "C" int m3l_op_mlp_t192_fwd(int M, int mlp, const void* xn2, const float* x1, const void* w1, const float* b1, const void* w2,
