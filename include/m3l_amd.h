@@ -732,6 +732,43 @@ int m3l_sac_actor_loss_bwd(const float* dloss, const float* coef, int B, float* 
 int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float target_entropy, int B, const float* dloss, float* loss, float* ent_coef,
                           float* dlog_ent_coef, void* stream);
 
+/* ---- device-resident rollout (ABI 411): what PPO_MAE.train does between `rollout_buffer` and `self.mae(x)` for every minibatch, with the rollout
+ * kept in device memory in the layout the vec-env fills it in, (T, n_envs, ...).  Nothing is swapped or flattened: idx [B] (int64) holds flat
+ * indices of the reference's swapped order, j -> env = j / T, t = j % T, store row t * n_envs + env            models/ppo_dino_cat_mae.py:25-29
+ *
+ *   m3l_rollout_gather_load   obs[idx] of RolloutDataset.__getitem__ + collate + .cuda()                         :48-56,:58-70,:268-278
+ *                             the frame-stack permute / reshape of both keys                                     :295-301
+ *                             vt_load: NHWC -> NCHW, per-sensor channel pick, (x - lo) / (hi - lo)                utils/pretrain_utils.py:7-57
+ *   m3l_rollout_gather_rows   actions / values / log_probs / advantages / returns [idx]                          :51-55
+ *   m3l_rollout_gae           SB3 RolloutBuffer.compute_returns_and_advantage (SB3 is not in the reference tree: restated, parity unpinned)
+ *
+ * gather_load.  image_store (T, n_envs, fs, H, W, 3) and tactile_store (T, n_envs, fs, 3 S, h, w), each uint8 (*_u8 = 1) or f32, either NULL;
+ *   image[b, 3 f + c, y, x]     = (image_store[t, env, f, y, x, c]       - img_lo) / (img_hi - img_lo)      image (B, 3 fs, H, W) f32
+ *   tactile_s[b, 3 f + c, y, x] = (tactile_store[t, env, f, 3 s + c, y, x] - tac_lo) / (tac_hi - tac_lo)    tactile_out[s] (B, 3 fs, h, w) f32, s < S
+ * with the arithmetic of m3l_vt_load2 (lo and the span rounded to fp32 once, an IEEE division): the bits are those of vt_load on the rows
+ * the reference gathers.  One launch for both modalities; every store offset is 64-bit (a float image store of 32768 rows is 6.4 GB).
+ * Traffic: one read and one write of the minibatch.  Frames whose pixel count (image: H W, tactile: 3 h w) is a multiple of 4 in 16-byte
+ * aligned buffers move in 16-byte vectors (4-byte vectors on the uint8 side); anything else is accepted and moves element-wise.
+ * Errors, nothing written: both stores NULL, S outside 1..8, an empty normalisation range, a non-positive size.
+ * Index contract: the host cannot see idx without a read-back, which these entry points never do, so a wrong index is not an error code.
+ * A row whose index lies outside [0, T n_envs) is never read; every output element of that row is NaN instead.  Valid indices are the
+ * caller's job (DeviceRolloutBuffer generates them itself and checks injected ones on the host).
+ *
+ * gather_rows.  actions (T, n_envs, A), the other four (T, n_envs), all f32 -> actions_out (B, A) and four (B); one launch; same index contract.
+ *
+ * gae.  rewards, values, episode_starts (T, n_envs), last_values, dones (n_envs), all f32 (flags 0 / 1); backwards in time per environment:
+ *   nnt_t = 1 - episode_starts[t + 1] (t = T - 1: 1 - dones),  v_next = values[t + 1] (t = T - 1: last_values)
+ *   delta = rewards[t] + gamma v_next nnt_t - values[t];  advantages[t] = delta + gamma gae_lambda nnt_t advantages[t + 1];  returns = advantages + values
+ * One launch, one lane per environment, fp32, a fixed order: two runs give the same bits.  It runs once per rollout and is not tuned. */
+int m3l_rollout_gather_load(const void* image_store, int image_u8, int H, int W, double img_lo, double img_hi, float* image,
+                            const void* tactile_store, int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi,
+                            float* const* tactile_out, int T, int n_envs, int frame_stack, const int64_t* idx, int B, void* stream);
+int m3l_rollout_gather_rows(const float* actions, const float* values, const float* log_probs, const float* advantages, const float* returns, int T,
+                            int n_envs, int A, const int64_t* idx, int B, float* actions_out, float* values_out, float* log_probs_out,
+                            float* advantages_out, float* returns_out, void* stream);
+int m3l_rollout_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const float* dones, int T,
+                    int n_envs, float gamma, float gae_lambda, float* advantages, float* returns, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

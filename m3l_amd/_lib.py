@@ -219,6 +219,10 @@ _SIGS = {
     "m3l_sac_actor_loss_fwd": (c_i, [c_p, c_p, c_i, C.c_float, c_p, c_p, c_p, c_p]),
     "m3l_sac_actor_loss_bwd": (c_i, [c_p, c_p, c_i, c_p, c_p]),
     "m3l_sac_ent_coef_loss": (c_i, [c_p, c_p, C.c_float, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_rollout_gather_load": (c_i, [c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, c_p,
+                                      c_i, c_i, c_i, c_p, c_i, c_p]),
+    "m3l_rollout_gather_rows": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_rollout_gae": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, C.c_float, C.c_float, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

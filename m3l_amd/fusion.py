@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import functional as Fn
 from .pretrain_models import VTT
-from .pretrain_utils import vt_load
+from .pretrain_utils import LoadedObs, vt_load
 
 
 def pooled_embeddings(mae, head, vt, use_tactile=True):
@@ -57,6 +57,14 @@ def pooled_embeddings(mae, head, vt, use_tactile=True):
     return Fn.ExtractorFn.apply(plan, *[t for t in plan.tensors if t is not None])
 
 
+def _loaded(observations, frame_stack, device):
+    """The MAE's input tensors of a batch of observations: a LoadedObs (m3l_amd.rollout: gathered, flattened and normalised already) as it
+    is, anything else through the frame-stack flatten and vt_load."""
+    if isinstance(observations, LoadedObs):
+        return observations
+    return vt_load(_flatten_frame_stack(observations), frame_stack=frame_stack, device=device)
+
+
 def _flatten_frame_stack(observations):
     """(B, fs, H, W, 3) -> (B, H, W, 3*fs) and (B, fs, 6, h, w) -> (B, 6*fs, h, w), as both reference extractors do before vt_load."""
     obs = dict(observations)
@@ -88,7 +96,7 @@ class MAEExtractor(nn.Module):
 
     def forward(self, observations):
         dev = self.vit_layer.pos_embedding.device
-        vt = vt_load(_flatten_frame_stack(observations), frame_stack=self.frame_stack, device=dev)
+        vt = _loaded(observations, self.frame_stack, dev)
         return self.flatten(pooled_embeddings(self.mae_model, self.vit_layer.transformer, vt, use_tactile=not self.vision_only_control))
 
 
@@ -121,7 +129,7 @@ class DinoCatMAEExtractor(nn.Module):
 
     def forward(self, observations):
         dev = self.query.device
-        vt = vt_load(_flatten_frame_stack(observations), frame_stack=self.frame_stack, device=dev)
+        vt = _loaded(observations, self.frame_stack, dev)
         pooled = pooled_embeddings(self.mae_model, self.vit_layer.transformer, vt, use_tactile=not self.vision_only_control)
         dino = self.dino_model(self.middle_frame(vt["image"]))
         return self.run_mlp(Fn.Concat2Fn.apply(self.flatten(pooled), dino))

@@ -15,6 +15,11 @@ import torch
 from . import _lib as L
 
 
+class LoadedObs(dict):
+    """What vt_load returns — {'image': (B, 3*fs, H, W), 'tactile1..S': (B, 3*fs, h, w)} float32 on the device — marked as such: the
+    extractors take a LoadedObs as it is, any other dict goes through the frame-stack flatten and vt_load (m3l_amd.rollout yields these)."""
+
+
 def _as_cuda(a, device):
     """-> (contiguous CUDA tensor, is_uint8): float32 and uint8 observations travel as they are."""
     if isinstance(a, np.ndarray):
