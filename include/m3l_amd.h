@@ -769,6 +769,46 @@ int m3l_rollout_gather_rows(const float* actions, const float* values, const flo
 int m3l_rollout_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const float* dones, int T,
                     int n_envs, float gamma, float gae_lambda, float* advantages, float* returns, void* stream);
 
+/* ---- device-resident replay buffer (ABI 412): what `replay_data = self.replay_buffer.sample(batch_size, env=...)` does at the head of every SAC
+ * gradient step (models/sac_mae.py:240), plus the frame-stack permute :253-260 and vt_load of both observation dicts, with the ring kept in
+ * device memory in the layout the vec-env fills it in, (T, n_envs, ...).  SB3's DictReplayBuffer is not in the reference tree: its semantics
+ * are restated (tests/replay_cases.py), parity unpinned; the observation path is the rollout's and is pinned by the same fixture.
+ *
+ *   m3l_replay_gather_load   observations[rows] and next_observations[rows] -> the MAE's input tensors of both, one launch
+ *   m3l_replay_gather_rows   actions[rows], rewards[rows] (optionally normalised), dones[rows] * (1 - timeouts[rows]), one launch
+ *
+ * rows [B] (int64) holds store rows t * n_envs + e directly: no swapped order here.  row_shift (0 <= row_shift < T n_envs, normally 0) is
+ * added to every entry modulo T n_envs before use: a full single-store ring draws its rows relative to the slot after `pos` with one
+ * uniform draw and needs no launch of its own to wrap them.  gather_rows writes the rows actually read to rows_out [B] when it is not NULL.
+ *
+ * gather_load.  Stores, ranges, outputs and arithmetic are those of m3l_rollout_gather_load (above); `image` / `tactile_out` receive row
+ * t * n_envs + e of image_store / tactile_store.  `image_next` / `tactile_next_out` receive the next observation of the same rows:
+ *   *_next_store non-NULL   row t * n_envs + e of that store (same shape and element type as its store): SB3's two-store DictReplayBuffer
+ *   *_next_store NULL       row ((t + 1) % T) * n_envs + e of the store itself: SB3's optimize_memory_usage, the ring's next slot
+ * Every store offset is 64-bit.  Traffic: one read and one write of 2 B rows.  The 16-byte paths need every store and output of a modality
+ * aligned (uint8 stores: 4 bytes); anything else moves element-wise.
+ * Errors, nothing written: both stores NULL, a next store without its store, a NULL output, S outside 1..8, an empty normalisation range,
+ * a non-positive size, row_shift outside [0, T n_envs).
+ * Index contract (as for the rollout): the host never reads rows back, so a wrong row is not an error code.  A row outside [0, T n_envs) is
+ * never read — neither is its next row — and every output element of that sample is NaN in both halves.  Which rows are valid (filled
+ * slots; in the single-store mode not the slot the newest next observation overwrote) is the caller's job: DeviceReplayBuffer draws them
+ * itself and checks injected ones on the host.
+ *
+ * gather_rows.  actions (T, n_envs, A), rewards / dones / timeouts (T, n_envs), all f32 -> actions_out (B, A), rewards_out (B), dones_out (B).
+ *   rewards_out = rewards[row]                                                  reward_scale == 0
+ *               = min(max(rewards[row] / reward_scale, -reward_clip), reward_clip)   reward_scale > 0: VecNormalize.normalize_reward with
+ *                 reward_scale = (float)sqrt(var + epsilon) formed by the caller; an IEEE fp32 division
+ *   dones_out   = dones[row] * (1 - timeouts[row])   (timeouts NULL: dones[row]); exact for 0 / 1 flags
+ * Errors: a non-positive size, a NULL argument other than timeouts and rows_out, row_shift outside [0, T n_envs), a negative or non-finite
+ * reward_scale, a negative reward_clip. */
+int m3l_replay_gather_load(const void* image_store, const void* image_next_store, int image_u8, int H, int W, double img_lo, double img_hi,
+                           float* image, float* image_next, const void* tactile_store, const void* tactile_next_store, int tactile_u8, int th, int tw,
+                           int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out, float* const* tactile_next_out, int T, int n_envs,
+                           int frame_stack, const int64_t* rows, long row_shift, int B, void* stream);
+int m3l_replay_gather_rows(const float* actions, const float* rewards, const float* dones, const float* timeouts, int T, int n_envs, int A,
+                           const int64_t* rows, long row_shift, int B, float reward_scale, float reward_clip, float* actions_out,
+                           float* rewards_out, float* dones_out, int64_t* rows_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,138 @@
+// The gather-and-load pieces that the device-resident buffers share (rollout.hip: PPO's rollout; replay.hip: SAC's replay ring): one lane's
+// share of moving a stored observation row into the MAE's input layout, and the host-side geometry of such a launch.
+//
+// A stored image frame is (H, W, 3), channel innermost, and becomes three consecutive (H, W) planes of the output: a lane takes 4 pixels = 12
+// consecutive elements (three 16-byte loads of a float store, three 4-byte loads of a uint8 store), de-interleaves them in registers and writes
+// one 16-byte vector into each plane.  A tactile frame's three channels of one sensor are 3 h w consecutive elements on both sides: a copy in
+// 16-byte vectors.  Frames whose element count is no multiple of 4 (or buffers that are not 16-byte aligned) take an element-per-lane form of
+// the same arithmetic.  (float)x - lo, then an IEEE division by the span: the operations of vt_image_kernel / vt_tactile_kernel
+// (elementwise.hip), so the bits are those of vt_load on the gathered rows.  A row < 0 is not read: its outputs are NaN.
+#pragma once
+#include <stdint.h>
+
+#include "common.cuh"
+#include "kernels.h"
+
+namespace {
+
+struct GatherGeom {
+    int fs, S;
+    int HW, hw;
+    int img_u8, tac_u8, img_vec, tac_vec;
+    float img_lo, img_span, tac_lo, tac_span;
+    int img_per_sample, tac_per_sample;   // lanes of work of one sample
+};
+
+__device__ __forceinline__ float vt_norm(float x, float lo, float span) { return __fdiv_rn(x - lo, span); }
+
+__device__ __forceinline__ void load12(const float* __restrict__ p, float (&v)[12]) {
+    const f32x4 a = ((const f32x4*)p)[0], b = ((const f32x4*)p)[1], c = ((const f32x4*)p)[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        v[k] = a[k];
+        v[4 + k] = b[k];
+        v[8 + k] = c[k];
+    }
+}
+__device__ __forceinline__ void load12(const uint8_t* __restrict__ p, float (&v)[12]) {
+    const uchar4 a = ((const uchar4*)p)[0], b = ((const uchar4*)p)[1], c = ((const uchar4*)p)[2];
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+    v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+    v[8] = c.x, v[9] = c.y, v[10] = c.z, v[11] = c.w;
+}
+__device__ __forceinline__ f32x4 load4(const float* __restrict__ p) { return *(const f32x4*)p; }
+__device__ __forceinline__ f32x4 load4(const uint8_t* __restrict__ p) {
+    const uchar4 a = *(const uchar4*)p;
+    return f32x4{(float)a.x, (float)a.y, (float)a.z, (float)a.w};
+}
+
+// item r < img_per_sample of output sample b: store row `row` of img (n_rows, fs, H, W, 3) -> img_out (B, 3 fs, H, W)
+template <typename TI>
+__device__ __forceinline__ void gather_image_item(const GatherGeom& g, const void* img, float* img_out, long row, int b, int r) {
+    const long frame = 3L * g.HW;
+    const float nan = __int_as_float(0x7fc00000);
+    if (g.img_vec) {
+        const int n4 = g.HW / 4, f = r / n4, q = r % n4;
+        float v[12];
+        if (row >= 0) {
+            load12((const TI*)img + (row * g.fs + f) * frame + 12L * q, v);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) v[k] = vt_norm(v[k], g.img_lo, g.img_span);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) v[k] = nan;
+        }
+        float* __restrict__ o = img_out + ((long)b * g.fs + f) * frame + 4L * q;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *(f32x4*)(o + (long)c * g.HW) = f32x4{v[c], v[3 + c], v[6 + c], v[9 + c]};
+    } else {
+        const int f = r / g.HW, p = r % g.HW;
+        const TI* __restrict__ s = (const TI*)img + (row * g.fs + f) * frame + 3L * p;
+        float* __restrict__ o = img_out + ((long)b * g.fs + f) * frame + p;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[(long)c * g.HW] = row >= 0 ? vt_norm((float)s[c], g.img_lo, g.img_span) : nan;
+    }
+}
+
+// item r < tac_per_sample of output sample b: store row `row` of tac (n_rows, fs, 3 S, h, w) -> tac_out[s] (B, 3 fs, h, w)
+template <typename TI>
+__device__ __forceinline__ void gather_tactile_item(const GatherGeom& g, const void* tac, float* const (&tac_out)[M3L_MAX_SENSORS], long row, int b,
+                                                    int r) {
+    const long seg = 3L * g.hw;                                   // the three channels of one sensor in one frame
+    const int per_seg = g.tac_vec ? (int)(seg / 4) : (int)seg;
+    const int f = r / (g.S * per_seg), s = (r / per_seg) % g.S, q = r % per_seg;
+    float* o = tac_out[0];
+#pragma unroll
+    for (int k = 1; k < M3L_MAX_SENSORS; ++k) o = (s == k) ? tac_out[k] : o;
+    const float nan = __int_as_float(0x7fc00000);
+    const TI* __restrict__ src = (const TI*)tac + ((row * g.fs + f) * g.S + s) * seg;
+    o += ((long)b * g.fs + f) * seg;
+    if (g.tac_vec) {
+        f32x4 v = f32x4{nan, nan, nan, nan};
+        if (row >= 0) {
+            v = load4(src + 4L * q);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = vt_norm(v[k], g.tac_lo, g.tac_span);
+        }
+        *(f32x4*)(o + 4L * q) = v;
+    } else {
+        o[q] = row >= 0 ? vt_norm((float)src[q], g.tac_lo, g.tac_span) : nan;
+    }
+}
+
+inline bool gather_aligned(const void* p, size_t n) { return ((uintptr_t)p % n) == 0; }
+
+// The image half of a launch's geometry; `who` names the entry point in the messages.  img_vec starts from the store's and the first output's
+// alignment: an entry point with further stores or outputs of the same shape narrows it afterwards and then calls gather_image_items.
+inline int gather_image_geom(GatherGeom& g, const char* who, const void* image_store, int image_u8, int H, int W, double lo, double hi,
+                             const float* image) {
+    // the span as m3l_vt_load2 forms it: in double, rounded to fp32 once
+    g.img_lo = (float)lo, g.img_span = (float)(hi - lo);
+    M3L_CHECK(H >= 1 && W >= 1 && image, "%s: image H=%d W=%d", who, H, W);
+    M3L_CHECK(g.img_span != 0.f, "%s: empty image normalisation range", who);
+    M3L_CHECK((long)H * W <= (1 << 24), "%s: image of %d x %d pixels", who, H, W);
+    g.img_u8 = image_u8 ? 1 : 0, g.HW = H * W;
+    g.img_vec = g.HW % 4 == 0 && gather_aligned(image_store, image_u8 ? 4 : 16) && gather_aligned(image, 16);
+    return 0;
+}
+inline long gather_image_items(const GatherGeom& g) { return (long)g.fs * (g.img_vec ? g.HW / 4 : g.HW); }
+
+inline int gather_tactile_geom(GatherGeom& g, const char* who, const void* tactile_store, int tactile_u8, int th, int tw, int n_sensors, double lo,
+                               double hi, float* const* tactile_out, float* (&out)[M3L_MAX_SENSORS]) {
+    M3L_CHECK(n_sensors >= 1 && n_sensors <= M3L_MAX_SENSORS, "%s: n_sensors=%d (1..%d)", who, n_sensors, M3L_MAX_SENSORS);
+    g.tac_lo = (float)lo, g.tac_span = (float)(hi - lo);
+    M3L_CHECK(g.tac_span != 0.f, "%s: empty tactile normalisation range", who);
+    M3L_CHECK(th >= 1 && tw >= 1 && tactile_out, "%s: tactile h=%d w=%d", who, th, tw);
+    M3L_CHECK((long)th * tw <= (1 << 24), "%s: tactile frame of %d x %d", who, th, tw);
+    g.tac_u8 = tactile_u8 ? 1 : 0, g.hw = th * tw, g.S = n_sensors;
+    g.tac_vec = (3 * g.hw) % 4 == 0 && gather_aligned(tactile_store, tactile_u8 ? 4 : 16);
+    for (int s = 0; s < n_sensors; ++s) {
+        M3L_CHECK(tactile_out[s], "%s: tactile output %d is NULL", who, s);
+        out[s] = tactile_out[s];
+        g.tac_vec = g.tac_vec && gather_aligned(tactile_out[s], 16);
+    }
+    return 0;
+}
+inline long gather_tactile_items(const GatherGeom& g) { return (long)g.fs * g.S * (g.tac_vec ? 3 * g.hw / 4 : 3 * g.hw); }
+
+}  // namespace

@@ -14,7 +14,8 @@ the reference's swap: env = j // T, t = j % T.  `get(indices=...)` is the parity
 permutation it yields the reference's minibatches, bit for bit.
 
 SB3's own buffer arithmetic (`RolloutBuffer.compute_returns_and_advantage`) is not in the reference tree; it is restated in csrc/rollout.hip
-and, in float64, in tests/rollout_cases.py (parity unpinned).  Not covered: SAC's replay buffer, VecNormalize, discrete action spaces.
+and, in float64, in tests/rollout_cases.py (parity unpinned).  Not covered: VecNormalize of observations, discrete action spaces.  SAC's
+replay buffer is m3l_amd.replay.DeviceReplayBuffer, which shares this module's validation and csrc/gather_common.cuh.
 """
 from typing import NamedTuple
 
@@ -44,6 +45,89 @@ def _store_dtype(key, dt):
         raise ValueError(f"observation '{key}': dtype {dt} is not supported (uint8 or float32)") from None
 
 
+def _require_device(who, device, kind, host_class):
+    """The device of a device-resident buffer (DeviceRolloutBuffer, m3l_amd.replay.DeviceReplayBuffer): a CPU placement is refused."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.M3LError(f"{who}(device={str(device)!r}): the {kind} lives in GPU memory and is read by HIP kernels "
+                         f"(no CPU fallback); use SB3's {host_class} for a host-side {kind}")
+    return device
+
+
+def _obs_spec(who, obs_shapes, obs_dtypes, image_normalization, tactile_normalization):
+    """The observation layout both device-resident buffers accept: keys 'image' (fs, H, W, 3) and / or 'tactile' (fs, 3 * S, h, w), uint8 or
+    float32 -> (shapes, torch dtypes, frame_stack); anything else is a ValueError naming `who`."""
+    shapes = {k: tuple(int(v) for v in s) for k, s in obs_shapes.items()}
+    unknown = set(shapes) - {"image", "tactile"}
+    if unknown or not shapes:
+        raise ValueError(f"{who}: observation keys {sorted(shapes)} (expected 'image' and / or 'tactile')")
+    dtypes = {k: _store_dtype(k, obs_dtypes[k]) for k in shapes}
+    fs = set()
+    if "image" in shapes:
+        s = shapes["image"]
+        if len(s) != 4 or s[3] != 3:
+            raise ValueError(f"{who}: image shape {s} is not (frame_stack, H, W, 3)")
+        fs.add(s[0])
+    if "tactile" in shapes:
+        s = shapes["tactile"]
+        if len(s) != 4:
+            raise ValueError(f"{who}: tactile shape {s} is not (frame_stack, 3 * S, h, w)")
+        if s[1] % 3 or not 1 <= s[1] // 3 <= MAX_SENSORS:
+            raise ValueError(f"{who}: {s[1]} tactile channels per frame is not 3 * S with 1 <= S <= {MAX_SENSORS}")
+        fs.add(s[0])
+    if len(fs) != 1:
+        raise ValueError(f"{who}: image and tactile observations disagree on the frame stack ({sorted(fs)})")
+    for name, r in (("image", image_normalization), ("tactile", tactile_normalization)):
+        if np.float32(float(r[1]) - float(r[0])) == 0:
+            raise ValueError(f"{who}: empty {name} normalisation range {list(r)}")
+    return shapes, dtypes, fs.pop()
+
+
+def _check_obs(who, obs, shapes, n_envs):
+    """One vec-env step of observations against the buffer's layout."""
+    if set(obs) != set(shapes):
+        raise ValueError(f"{who}: observation keys {sorted(obs)} (expected {sorted(shapes)})")
+    for k, s in shapes.items():
+        if tuple(obs[k].shape) != (n_envs,) + s:
+            raise ValueError(f"{who}: observation '{k}' has shape {tuple(obs[k].shape)} (expected {(n_envs,) + s})")
+
+
+def _check_stores(who, image_store, tactile_store):
+    """The (T, n_envs, fs, ...) observation stores of a gather -> (T, n_envs, fs, H, W, th, tw, S)."""
+    ref = image_store if image_store is not None else tactile_store
+    T, n_envs, fs = ref.shape[:3]
+    H = W = th = tw = S = 0
+    for name, t in (("image_store", image_store), ("tactile_store", tactile_store)):
+        if t is not None and (t.dim() != 6 or tuple(t.shape[:3]) != (T, n_envs, fs) or not t.is_contiguous()
+                              or t.dtype not in (torch.uint8, torch.float32)):
+            raise ValueError(f"{who}: {name} must be a contiguous uint8 / float32 (T, n_envs, fs, ...) tensor of 6 dimensions")
+    if image_store is not None:
+        H, W = image_store.shape[3:5]
+        if image_store.shape[5] != 3:
+            raise ValueError(f"{who}: image_store has {image_store.shape[5]} channels (3)")
+    if tactile_store is not None:
+        CH, th, tw = tactile_store.shape[3:]
+        if CH % 3 or not 1 <= CH // 3 <= MAX_SENSORS:
+            raise ValueError(f"{who}: tactile_store has {CH} channels per frame (3 * S, 1 <= S <= {MAX_SENSORS})")
+        S = CH // 3
+    return T, n_envs, fs, H, W, th, tw, S
+
+
+def _loaded_outputs(B, fs, H, W, th, tw, S, device):
+    """Uninitialised outputs of a gather of B rows: (image or None, [tactile1..S])."""
+    img = torch.empty(B, 3 * fs, H, W, dtype=torch.float32, device=device) if H else None
+    return img, [torch.empty(B, 3 * fs, th, tw, dtype=torch.float32, device=device) for _ in range(S)]
+
+
+def _as_loaded(img_out, tac_outs):
+    out = LoadedObs()
+    if img_out is not None:
+        out["image"] = img_out
+    for s, t in enumerate(tac_outs):
+        out["tactile" + str(s + 1)] = t
+    return out
+
+
 def gather_load(image_store, tactile_store, idx, image_normalization=(0, 1), tactile_normalization=(-1, 1)):
     """image_store (T, n_envs, fs, H, W, 3) and / or tactile_store (T, n_envs, fs, 3*S, h, w), uint8 or float32 CUDA tensors, and idx (B) int64
     flat indices of the reference's swapped order -> LoadedObs {'image': (B, 3*fs, H, W), 'tactile1..S': (B, 3*fs, h, w)} float32: what
@@ -56,36 +140,15 @@ def gather_load(image_store, tactile_store, idx, image_normalization=(0, 1), tac
             _require_cuda(t, "gather_load: " + name)
     if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
         raise ValueError("gather_load: idx must be a contiguous 1-D int64 tensor")
-    T, n_envs, fs = ref.shape[:3]
+    T, n_envs, fs, H, W, th, tw, S = _check_stores("gather_load", image_store, tactile_store)
     B = idx.shape[0]
-    img_out, tac_outs = None, []
-    H = W = th = tw = S = 0
-    for name, t in (("image_store", image_store), ("tactile_store", tactile_store)):
-        if t is not None and (t.dim() != 6 or tuple(t.shape[:3]) != (T, n_envs, fs) or not t.is_contiguous()
-                              or t.dtype not in (torch.uint8, torch.float32)):
-            raise ValueError(f"gather_load: {name} must be a contiguous uint8 / float32 (T, n_envs, fs, ...) tensor of 6 dimensions")
-    if image_store is not None:
-        H, W = image_store.shape[3:5]
-        if image_store.shape[5] != 3:
-            raise ValueError(f"gather_load: image_store has {image_store.shape[5]} channels (3)")
-        img_out = torch.empty(B, 3 * fs, H, W, dtype=torch.float32, device=ref.device)
-    if tactile_store is not None:
-        CH, th, tw = tactile_store.shape[3:]
-        if CH % 3 or not 1 <= CH // 3 <= MAX_SENSORS:
-            raise ValueError(f"gather_load: tactile_store has {CH} channels per frame (3 * S, 1 <= S <= {MAX_SENSORS})")
-        S = CH // 3
-        tac_outs = [torch.empty(B, 3 * fs, th, tw, dtype=torch.float32, device=ref.device) for _ in range(S)]
+    img_out, tac_outs = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
     L.check(L.lib().m3l_rollout_gather_load(
         L.ptr(image_store), int(image_store is not None and image_store.dtype == torch.uint8), H, W, float(image_normalization[0]),
         float(image_normalization[1]), L.ptr(img_out), L.ptr(tactile_store), int(tactile_store is not None and tactile_store.dtype == torch.uint8),
         th, tw, S, float(tactile_normalization[0]), float(tactile_normalization[1]), L.ptr_array(tac_outs), T, n_envs, fs, L.ptr(idx), B,
         _stream()), "m3l_rollout_gather_load")
-    out = LoadedObs()
-    if img_out is not None:
-        out["image"] = img_out
-    for s, t in enumerate(tac_outs):
-        out["tactile" + str(s + 1)] = t
-    return out
+    return _as_loaded(img_out, tac_outs)
 
 
 def gather_rows(actions, values, log_probs, advantages, returns, idx):
@@ -142,37 +205,12 @@ class DeviceRolloutBuffer:
 
     def __init__(self, buffer_size, n_envs, obs_shapes, obs_dtypes, action_dim, gamma=0.99, gae_lambda=0.95, image_normalization=[0, 1],
                  tactile_normalization=[-1, 1], device="cuda"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.M3LError(f"DeviceRolloutBuffer(device={device!r}): the rollout lives in GPU memory and is read by HIP kernels "
-                             "(no CPU fallback); use SB3's DictRolloutBuffer for a host-side rollout")
+        self.device = _require_device("DeviceRolloutBuffer", device, "rollout", "DictRolloutBuffer")
         self.buffer_size, self.n_envs, self.action_dim = int(buffer_size), int(n_envs), int(action_dim)
         if self.buffer_size < 1 or self.n_envs < 1 or self.action_dim < 1:
             raise ValueError(f"DeviceRolloutBuffer: buffer_size={buffer_size}, n_envs={n_envs}, action_dim={action_dim} must be positive")
-        self.obs_shapes = {k: tuple(int(v) for v in s) for k, s in obs_shapes.items()}
-        unknown = set(self.obs_shapes) - {"image", "tactile"}
-        if unknown or not self.obs_shapes:
-            raise ValueError(f"DeviceRolloutBuffer: observation keys {sorted(self.obs_shapes)} (expected 'image' and / or 'tactile')")
-        self.obs_dtypes = {k: _store_dtype(k, obs_dtypes[k]) for k in self.obs_shapes}
-        fs = set()
-        if "image" in self.obs_shapes:
-            s = self.obs_shapes["image"]
-            if len(s) != 4 or s[3] != 3:
-                raise ValueError(f"DeviceRolloutBuffer: image shape {s} is not (frame_stack, H, W, 3)")
-            fs.add(s[0])
-        if "tactile" in self.obs_shapes:
-            s = self.obs_shapes["tactile"]
-            if len(s) != 4:
-                raise ValueError(f"DeviceRolloutBuffer: tactile shape {s} is not (frame_stack, 3 * S, h, w)")
-            if s[1] % 3 or not 1 <= s[1] // 3 <= MAX_SENSORS:
-                raise ValueError(f"DeviceRolloutBuffer: {s[1]} tactile channels per frame is not 3 * S with 1 <= S <= {MAX_SENSORS}")
-            fs.add(s[0])
-        if len(fs) != 1:
-            raise ValueError(f"DeviceRolloutBuffer: image and tactile observations disagree on the frame stack ({sorted(fs)})")
-        for name, r in (("image", image_normalization), ("tactile", tactile_normalization)):
-            if np.float32(float(r[1]) - float(r[0])) == 0:
-                raise ValueError(f"DeviceRolloutBuffer: empty {name} normalisation range {list(r)}")
-        self.frame_stack = fs.pop()
+        self.obs_shapes, self.obs_dtypes, self.frame_stack = _obs_spec("DeviceRolloutBuffer", obs_shapes, obs_dtypes, image_normalization,
+                                                                       tactile_normalization)
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
         self.image_normalization, self.tactile_normalization = list(image_normalization), list(tactile_normalization)
         self.observations = None
@@ -194,11 +232,7 @@ class DeviceRolloutBuffer:
         may be device tensors (the policy's outputs) and are stored without a synchronise."""
         if self.full:
             raise ValueError(f"DeviceRolloutBuffer.add: the buffer is full ({self.buffer_size} steps); call reset() first")
-        if set(obs) != set(self.obs_shapes):
-            raise ValueError(f"DeviceRolloutBuffer.add: observation keys {sorted(obs)} (expected {sorted(self.obs_shapes)})")
-        for k, s in self.obs_shapes.items():
-            if tuple(obs[k].shape) != (self.n_envs,) + s:
-                raise ValueError(f"DeviceRolloutBuffer.add: observation '{k}' has shape {tuple(obs[k].shape)} (expected {(self.n_envs,) + s})")
+        _check_obs("DeviceRolloutBuffer.add", obs, self.obs_shapes, self.n_envs)
         if self.observations is None:
             self._allocate()
         p = self.pos

@@ -1,0 +1,186 @@
+"""Time of one SAC `replay_buffer.sample()` — from indices to (observations, next_observations, actions, dones, rewards) with both observation
+dicts as the MAE's input tensors — at the reference's SAC shapes (EXPERIMENTS.md §5.21): a ring of T = 10000 steps of n_envs = 1 environment,
+frame_stack = 4, image 64 x 64 x 3, 2 tactile sensors at 32 x 32 x 3; batches B = 64 and 256; two store variants, uint8 image + float32 tactile
+and all float32; two store modes, a second store for the next observations and the single store (optimize_memory_usage).  Three paths:
+
+  (a) host      what a user of the reference pays today (models/sac_mae.py:240, :253-260): numpy fancy index of both observation stores and the
+                scalars on the host -> torch.as_tensor(...).to(device) from pageable memory -> _flatten_frame_stack -> vt_load, twice; the
+                timeout mask and VecNormalize's reward normalisation in numpy
+  (b) resident  the parent commit's means on device-resident stores: two calls of rollout.gather_load (with n_envs = 1 its swapped index is the
+                row), index_select for the three scalars, torch ops for the mask and the normalisation.  The next rows of the single-store
+                mode are computed outside the timed region
+  (c) replay    m3l_amd.replay.gather_load + gather_rows: two launches
+
+and, for the launch comparison alone, (b_obs) the two rollout.gather_load calls and (c_obs) the one replay.gather_load call.  Every call takes the
+next B rows of one fixed permutation of the valid steps, so no path re-reads rows the caches still hold.  Before the timing the three paths'
+outputs for one batch are compared bit for bit.
+
+Timing, windows and launch counts are those of tools/rollout_feed_bench.py (device events around a window of back-to-back calls, the host clock
+around the same window without its synchronise, paths alternated, median / min / max of --rounds windows; launches and copies from
+torch.profiler in a run of their own).  For (c_obs): the bytes the algorithm needs — one read of 2 B stored rows, one write of 2 B float32
+rows — over its call time, and the share of the 6.29 TB/s a float4 copy reaches on this chip.  Without a GPU the tool fails.
+
+Usage: python tools/replay_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32] [--batches 64,256]   (one JSON line)"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import m3l_amd  # noqa: E402,F401
+from m3l_amd import replay as P  # noqa: E402
+from m3l_amd import rollout as R  # noqa: E402
+from m3l_amd import vt_load  # noqa: E402
+from m3l_amd.fusion import _flatten_frame_stack  # noqa: E402
+from rollout_feed_bench import HBM_COPY_TBS, HBM_SPEC_TBS, alternate, counted  # noqa: E402
+
+DEV = "cuda:0"
+T, E, FS, H, W, S, TH, TW, A = 10000, 1, 4, 64, 64, 2, 32, 32, 7
+VAR, EPS, CLIP = 2.5, 1e-8, 10.0          # VecNormalize's running return variance (any positive value), epsilon and clip_reward defaults
+
+
+def host_stores(image_dtype, seed):
+    """(T, n_envs, ...) host stores with every page written: one random slab of 50 steps repeated, the first element of a step made distinct."""
+    g = np.random.default_rng(seed)
+    img = np.empty((T, E, FS, H, W, 3), dtype=image_dtype)
+    slab = g.integers(0, 256, (50, E, FS, H, W, 3), dtype=np.uint8) if image_dtype == np.uint8 else g.random((50, E, FS, H, W, 3), dtype=np.float32)
+    img.reshape(T // 50, 50, E, FS, H, W, 3)[:] = slab
+    tac = np.empty((T, E, FS, 3 * S, TH, TW), dtype=np.float32)
+    tac.reshape(T // 50, 50, E, FS, 3 * S, TH, TW)[:] = (2 * g.random((50, E, FS, 3 * S, TH, TW), dtype=np.float32) - 1).astype(np.float32)
+    img[:, 0, 0, 0, 0, 0] = (np.arange(T) % 251).astype(image_dtype)
+    tac[:, 0, 0, 0, 0, 0] = np.arange(T, dtype=np.float32) / T
+    return {"image": img, "tactile": tac}
+
+
+def run_config(name, single, B, host, host_next, store, store_next, scal, dscal, a):
+    n_valid = T - 1 if single else T                  # a full single store with pos = 0: every step but step 0
+    first = 1 if single else 0
+    perm = (np.random.default_rng(1).permutation(n_valid) + first).astype(np.int64)
+    batches = [perm[i:i + B] for i in range(0, n_valid - B + 1, B)]
+    d_rows = [torch.from_numpy(b).to(DEV) for b in batches]
+    d_next = [torch.from_numpy((b + 1) % T).to(DEV) for b in batches]
+    scale = float(np.float32(math.sqrt(VAR + EPS)))
+    d_scale = torch.tensor(scale, dtype=torch.float32, device=DEV)      # a device operand: torch turns a division by a host scalar into a multiplication
+    state = {}
+
+    def nxt(p):
+        i = state.get(p, 0)
+        state[p] = (i + 1) % len(batches)
+        return i
+
+    def load(obs):
+        return vt_load(_flatten_frame_stack(obs), frame_stack=FS, device=DEV)
+
+    def path_a():
+        t = batches[nxt("a")]
+        e = np.zeros_like(t)
+        obs = load({k: torch.as_tensor(v[t, e]).to(DEV) for k, v in host.items()})
+        src = host if single else host_next
+        tn = (t + 1) % T if single else t
+        nobs = load({k: torch.as_tensor(v[tn, e]).to(DEV) for k, v in src.items()})
+        dones = scal["dones"][t, e] * (1 - scal["timeouts"][t, e])
+        rewards = np.clip(scal["rewards"][t, e] / np.float32(scale), -CLIP, CLIP).astype(np.float32)
+        up = lambda x: torch.as_tensor(x).to(DEV)      # noqa: E731
+        return obs, nobs, up(scal["actions"][t, e]), up(dones.reshape(-1, 1)), up(rewards.reshape(-1, 1))
+
+    def b_obs(i):
+        obs = R.gather_load(store["image"], store["tactile"], d_rows[i])
+        if single:
+            return obs, R.gather_load(store["image"], store["tactile"], d_next[i])
+        return obs, R.gather_load(store_next["image"], store_next["tactile"], d_rows[i])
+
+    def path_b():
+        i = nxt("b")
+        obs, nobs = b_obs(i)
+        rows = d_rows[i]
+        actions = dscal["actions"].view(T * E, A).index_select(0, rows)
+        dones = dscal["dones"].view(-1).index_select(0, rows) * (1 - dscal["timeouts"].view(-1).index_select(0, rows))
+        rewards = torch.clamp(dscal["rewards"].view(-1).index_select(0, rows) / d_scale, -CLIP, CLIP)
+        return obs, nobs, actions, dones.reshape(-1, 1), rewards.reshape(-1, 1)
+
+    def c_obs(i):
+        nx = store_next or {}
+        return P.gather_load(store["image"], store["tactile"], d_rows[i], nx.get("image"), nx.get("tactile"))
+
+    def path_c():
+        i = nxt("c")
+        obs, nobs = c_obs(i)
+        actions, rewards, dones = P.gather_rows(dscal["actions"], dscal["rewards"], dscal["dones"], dscal["timeouts"], d_rows[i], scale, CLIP)
+        return obs, nobs, actions, dones, rewards
+
+    # equal bits on one batch before anything is timed
+    ra, rb, rc = path_a(), path_b(), path_c()
+    torch.cuda.synchronize()
+    for x, y, z in zip(ra, rb, rc):
+        for k in (z if isinstance(z, dict) else [None]):
+            u, v, w = (q[k] if k is not None else q for q in (x, y, z))
+            assert torch.equal(u, w) and torch.equal(v, w), f"{name}: paths disagree on {k or 'a scalar output'}"
+    checksum = float(sum(v.double().sum() for d in rc[:2] for v in d.values()) + sum(t.double().sum() for t in rc[2:]))
+
+    fns = {"a_host": path_a, "b_resident": path_b, "c_replay": path_c, "b_obs_two_launches": lambda: b_obs(nxt("bo")), "c_obs_one_launch": lambda: c_obs(nxt("co"))}
+    iters = {n: (a.host_iters if n == "a_host" else a.iters) for n in fns}
+    warm = {n: (2 if n == "a_host" else 20) for n in fns}
+    res = alternate(fns, iters, warm, a.rounds)
+    for p, fn in fns.items():
+        res[p].update(counted(fn))
+    isz = 1 if name == "u8" else 4
+    read = 2 * B * (FS * H * W * 3 * isz + FS * 3 * S * TH * TW * 4)
+    write = 2 * B * (FS * H * W * 3 + FS * 3 * S * TH * TW) * 4
+    for p in ("b_obs_two_launches", "c_obs_one_launch"):
+        c = res[p]
+        c["bytes_read"], c["bytes_written"] = read, write
+        for key, us in (("", c["call_us"]), ("_best", c["call_us_min_max"][0]), ("_worst", c["call_us_min_max"][1])):
+            tbs = (read + write) / (us * 1e-6) / 1e12
+            c["tbytes_per_s" + key] = round(tbs, 3)
+            c["share_of_measured_copy_peak" + key] = round(tbs / HBM_COPY_TBS, 3)
+    res["b_over_c"] = round(res["b_resident"]["call_us"] / res["c_replay"]["call_us"], 2)
+    res["a_over_c"] = round(res["a_host"]["call_us"] / res["c_replay"]["call_us"], 1)
+    res["b_obs_over_c_obs"] = round(res["b_obs_two_launches"]["call_us"] / res["c_obs_one_launch"]["call_us"], 3)
+    res["checksum"] = checksum
+    return res
+
+
+def run_variant(name, a):
+    image_dtype = np.uint8 if name == "u8" else np.float32
+    host, host_next = host_stores(image_dtype, 0), host_stores(image_dtype, 5)
+    store = {k: torch.from_numpy(v).to(DEV) for k, v in host.items()}
+    store_next = {k: torch.from_numpy(v).to(DEV) for k, v in host_next.items()}
+    g = np.random.default_rng(2)
+    scal = dict(actions=g.standard_normal((T, E, A)).astype(np.float32), rewards=(3 * g.standard_normal((T, E))).astype(np.float32),
+                dones=(g.random((T, E)) < 0.01).astype(np.float32))
+    scal["timeouts"] = (scal["dones"] * (g.random((T, E)) < 0.5)).astype(np.float32)
+    dscal = {k: torch.from_numpy(v).to(DEV) for k, v in scal.items()}
+    torch.cuda.synchronize()
+    out = {"store_gbytes_each": round(sum(v.numel() * v.element_size() for v in store.values()) / 1e9, 2)}
+    for B in a.batches:
+        out[f"B{B}_two_stores"] = run_config(name, False, B, host, host_next, store, store_next, scal, dscal, a)
+        out[f"B{B}_single_store"] = run_config(name, True, B, host, None, store, None, scal, dscal, a)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5, help="alternating windows per path")
+    ap.add_argument("--iters", type=int, default=200, help="calls per timed window of the device paths")
+    ap.add_argument("--host-iters", type=int, default=5, help="calls per timed window of the host path (a)")
+    ap.add_argument("--variants", default="u8,f32")
+    ap.add_argument("--batches", default="64,256")
+    a = ap.parse_args()
+    a.batches = [int(b) for b in a.batches.split(",")]
+    if not torch.cuda.is_available():
+        raise SystemExit("replay_feed_bench: no GPU")
+    out = {"shape": {"T": T, "n_envs": E, "frame_stack": FS, "image": [H, W, 3], "tactile": [3 * S, TH, TW], "B": a.batches, "action_dim": A},
+           "hbm_peak_tbytes_per_s": {"float4_copy_measured": HBM_COPY_TBS, "spec": HBM_SPEC_TBS}}
+    for name in a.variants.split(","):
+        out[name] = run_variant(name, a)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
