@@ -14,7 +14,9 @@
 //   loss      one workgroup: the advantage statistics, then one pass over the rows for the five sums, each thread over its rows in order and the
 //             threads' sums through block_sum.  The backward scales the stored per-row coefficients by dloss.
 // No float atomics and every sum in a fixed order: the same bits on every run.
-// The layer, operand and weight-gradient pieces are policy_common.cuh's, shared with the SAC head (sac.hip); the activation here is Tanh.
+// The two branches are PhMlp nets: the walks over their layers, the layer, operand and weight-gradient pieces and the host's dimension check,
+// workspace layout and item list are policy_common.cuh's, shared with the SAC head (sac.hip); the activation here is Tanh.  This file keeps the
+// Gaussian epilogue, the d log_std partials and their sum (the last block of the grouped launch), and the loss.
 #include <math.h>
 #include <string.h>
 
@@ -25,28 +27,14 @@
 
 namespace {
 
-struct PhBranch {
-    int n, hn;                   // hidden layers; rows of the head (A or 1)
-    int w[M3L_POLICY_MAX_HIDDEN];
-    const float* W[M3L_POLICY_MAX_HIDDEN];
-    const float* b[M3L_POLICY_MAX_HIDDEN];
-    const float* hw;
-    const float* hb;
-    long h_off[M3L_POLICY_MAX_HIDDEN];       // post-Tanh activations (forward) in the workspace, in floats
-    long d_off[M3L_POLICY_MAX_HIDDEN];       // pre-activation gradients (backward)
-};
 struct PhArgs {
     int B, F, A, ld;             // ld: leading dimension of the LDS activation buffers, widest vector + 4
-    PhBranch br[2];              // 0 = policy branch + action_net, 1 = value branch + value_net
+    PhMlp br[2];                 // 0 = policy branch, 1 = value branch
+    int hn[2];                   // the heads on top of them, action_net [A, .] and value_net [1, .]
+    const float* hw[2];
+    const float* hb[2];
     const float* log_std;
     long mu_off, dmu_off, dv_off, part_off, total;
-};
-
-struct PhWgrad {
-    PhLin lin[PH_MAXLIN];
-    int count, items, B, A, tiles;
-    const float* part;           // [tiles, PH_MAXA] d log_std partials
-    float* dlog_std;
 };
 
 #define PH_HALF_LOG_2PI 0.91893853320467274178f
@@ -61,17 +49,10 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(PhArgs p, const float* 
     float* cur = ph_lds;
     float* nxt = ph_lds + PH_TM * p.ld;
     const int bi = blockIdx.y, row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B, A = p.A;
-    const PhBranch& br = p.br[bi];
     ph_load_x(x, p.F, row0, B, cur, p.ld);
     __syncthreads();
-    int K = p.F;
-    for (int l = 0; l < br.n; ++l) {
-        ph_fwd_layer<PH_ACT_TANH>(cur, p.ld, K, br.W[l], br.b[l], br.w[l], nxt, p.ld, ws ? ws + br.h_off[l] : nullptr, row0, B);
-        __syncthreads();
-        float* s = cur; cur = nxt; nxt = s;
-        K = br.w[l];
-    }
-    ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, br.hw, br.hb, br.hn, head, PH_HLD, nullptr, row0, B);
+    const int K = ph_fwd_walk<PH_ACT_TANH>(p.br[bi], p.F, cur, nxt, p.ld, ws, row0, B);
+    ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.hw[bi], p.hb[bi], p.hn[bi], head, PH_HLD, nullptr, row0, B);
     __syncthreads();
     if (bi == 1) {
         if (tid < PH_TM && row0 + tid < B) values[row0 + tid] = head[tid * PH_HLD];
@@ -116,21 +97,11 @@ __global__ __launch_bounds__(256) void policy_bwd_chain_kernel(PhArgs p, const f
     const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B, A = p.A;
     for (int pass = 0; pass < 2; ++pass) {
         const int bi = 1 - pass;                  // the value branch first: it writes dx, the policy branch adds to it
-        const PhBranch& br = p.br[bi];
         float* cur = bufa;
         float* nxt = bufb;
         int valid;
         if (bi == 1) {
-            // d value_net output: [16, 8] with dvalues in column 0
-            if (tid < PH_TM * 8) {
-                const int m = tid >> 3, j = tid & 7, row = row0 + m;
-                float v = 0.f;
-                if (j == 0 && row < B) {
-                    v = dvalues ? dvalues[row] : 0.f;
-                    ws[p.dv_off + row] = v;
-                }
-                cur[m * p.ld + j] = v;
-            }
+            ph_col0_tile(dvalues, ws + p.dv_off, cur, p.ld, row0, B);      // d value_net output
             valid = 8;
         } else {
             // d mu[m][j] = dlogp_m (a - mu) / sigma_j^2; the rows' terms of d log_std wait in nxt for their sum
@@ -157,36 +128,26 @@ __global__ __launch_bounds__(256) void policy_bwd_chain_kernel(PhArgs p, const f
             valid = (A + 7) & ~7;
         }
         __syncthreads();
-        const float* W = br.hw;
-        int N = br.hn;
-        for (int l = br.n - 1; l >= 0; --l) {
-            const int K = br.w[l];
-            ph_bwd_layer<PH_ACT_TANH>(cur, p.ld, valid, W, N, K, ws + br.h_off[l], nxt, p.ld, ws + br.d_off[l], false, row0, B);
-            __syncthreads();
-            float* s = cur; cur = nxt; nxt = s;
-            W = br.W[l];
-            N = K;
-            valid = K;
-        }
+        const float* W = p.hw[bi];
+        int N = p.hn[bi];
+        ph_bwd_walk<PH_ACT_TANH>(p.br[bi], p.br[bi].n - 1, cur, nxt, p.ld, valid, W, N, ws, row0, B);
         ph_bwd_layer<PH_ACT_NONE>(cur, p.ld, valid, W, N, p.F, nullptr, nullptr, 0, dx, pass == 1, row0, B);
         __syncthreads();
     }
 }
 
-// grid (cdiv(items, 4) + 1): wave w of block b takes item 4 b + w; the last block sums the d log_std partials
-__global__ __launch_bounds__(256) void policy_wgrad_kernel(PhWgrad q) {
-    const int tid = threadIdx.x, wave = tid >> 6;
+// grid (cdiv(items, 4) + 1): the grouped weight gradient, and a last block that sums the d log_std partials part [tiles, PH_MAXA]
+__global__ __launch_bounds__(256) void policy_wgrad_kernel(PhWgrad q, int A, int tiles, const float* part, float* dlog_std) {
+    const int tid = threadIdx.x;
     if (blockIdx.x == gridDim.x - 1) {
-        if (tid < q.A) {
+        if (tid < A) {
             float s = 0.f;
-            for (int t = 0; t < q.tiles; ++t) s += q.part[(long)t * PH_MAXA + tid];
-            q.dlog_std[tid] = s;
+            for (int t = 0; t < tiles; ++t) s += part[(long)t * PH_MAXA + tid];
+            dlog_std[tid] = s;
         }
         return;
     }
-    const int item = blockIdx.x * 4 + wave;
-    if (item >= q.items) return;                  // a whole wave leaves: the lanes that stay are all active
-    ph_wgrad_item(q.lin, q.count, item, q.B);
+    ph_wgrad_block(q, blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* __restrict__ logp, const float* __restrict__ values, const float* __restrict__ entropy,
@@ -262,22 +223,7 @@ __global__ __launch_bounds__(256) void ppo_loss_bwd_kernel(const float* __restri
 // the limits of the header; 0 and a message when the head is outside them
 int ph_shape_ok(const m3l_policy_desc* d, int B, char* why, size_t n) {
     if (d == nullptr) { snprintf(why, n, "null descriptor"); return 0; }
-    if (B < 1) { snprintf(why, n, "B=%d (B >= 1)", B); return 0; }
-    if (d->features < 16 || d->features % 16 || d->features > PH_MAXW) {
-        snprintf(why, n, "features=%d (a multiple of 16, at most %d)", d->features, PH_MAXW);
-        return 0;
-    }
-    if (d->actions < 1 || d->actions > PH_MAXA) { snprintf(why, n, "actions=%d (1 <= A <= %d)", d->actions, PH_MAXA); return 0; }
-    if (d->n_pi < 0 || d->n_pi > M3L_POLICY_MAX_HIDDEN || d->n_vf < 0 || d->n_vf > M3L_POLICY_MAX_HIDDEN) {
-        snprintf(why, n, "%d / %d hidden layers (0 to %d per branch)", d->n_pi, d->n_vf, M3L_POLICY_MAX_HIDDEN);
-        return 0;
-    }
-    for (int l = 0; l < d->n_pi + d->n_vf; ++l) {
-        const int w = l < d->n_pi ? d->pi_width[l] : d->vf_width[l - d->n_pi];
-        if (w < 16 || w % 16 || w > PH_MAXW) { snprintf(why, n, "hidden width %d (a multiple of 16, at most %d)", w, PH_MAXW); return 0; }
-    }
-    if ((long)B * PH_MAXW >= 2147483647L / 4) { snprintf(why, n, "B=%d rows are more than the kernels index", B); return 0; }
-    return 1;
+    return ph_dims_ok(B, d->features, d->actions, d->n_pi, d->pi_width, d->n_vf, d->vf_width, "branch", PH_MAXW, why, n);
 }
 
 // kernel arguments and workspace layout of a head; with_params = 0 only sizes the workspace
@@ -287,28 +233,16 @@ PhArgs ph_args(const m3l_policy_desc* d, int B, int with_params) {
     p.B = B;
     p.F = d->features;
     p.A = d->actions;
+    p.hn[0] = d->actions;
+    p.hn[1] = 1;
     int widest = d->features > PH_MAXA ? d->features : PH_MAXA;      // the heads' gradient tiles are PH_MAXA columns wide
-    long off = 0;
-    for (int bi = 0; bi < 2; ++bi) {
-        PhBranch& b = p.br[bi];
-        b.n = bi == 0 ? d->n_pi : d->n_vf;
-        b.hn = bi == 0 ? d->actions : 1;
-        for (int l = 0; l < b.n; ++l) {
-            b.w[l] = bi == 0 ? d->pi_width[l] : d->vf_width[l];
-            if (b.w[l] > widest) widest = b.w[l];
-            if (with_params) {
-                b.W[l] = bi == 0 ? d->pi_weight[l] : d->vf_weight[l];
-                b.b[l] = bi == 0 ? d->pi_bias[l] : d->vf_bias[l];
-            }
-            b.h_off[l] = off;
-            off += (long)B * b.w[l];
-            b.d_off[l] = off;
-            off += (long)B * b.w[l];
-        }
-        if (with_params) {
-            b.hw = bi == 0 ? d->action_weight : d->value_weight;
-            b.hb = bi == 0 ? d->action_bias : d->value_bias;
-        }
+    long off = ph_layout(p.br[0], d->n_pi, d->pi_width, B, 0, widest);
+    off = ph_layout(p.br[1], d->n_vf, d->vf_width, B, off, widest);
+    if (with_params) {
+        ph_bind(p.br[0], d->pi_weight, d->pi_bias);
+        ph_bind(p.br[1], d->vf_weight, d->vf_bias);
+        p.hw[0] = d->action_weight; p.hb[0] = d->action_bias;
+        p.hw[1] = d->value_weight; p.hb[1] = d->value_bias;
     }
     p.ld = widest + 4;
     p.log_std = with_params ? d->log_std : nullptr;
@@ -327,8 +261,7 @@ PhArgs ph_args(const m3l_policy_desc* d, int B, int with_params) {
 int ph_params_ok(const m3l_policy_desc* d, const char* who) {
     int ok = d->action_weight && d->action_bias && d->value_weight && d->value_bias && d->log_std && ph_aligned(d->action_weight) &&
              ph_aligned(d->value_weight);
-    for (int l = 0; l < d->n_pi; ++l) ok = ok && d->pi_weight[l] && d->pi_bias[l] && ph_aligned(d->pi_weight[l]);
-    for (int l = 0; l < d->n_vf; ++l) ok = ok && d->vf_weight[l] && d->vf_bias[l] && ph_aligned(d->vf_weight[l]);
+    ok = ok && ph_ptrs_ok(d->n_pi, d->pi_weight, d->pi_bias) && ph_ptrs_ok(d->n_vf, d->vf_weight, d->vf_bias);
     M3L_CHECK(ok, "%s: a parameter pointer of the descriptor is null or a weight is not 16-byte aligned", who);
     return 0;
 }
@@ -337,11 +270,12 @@ int g_policy_inited = 0;
 #define PH_LDS_MAX (2 * PH_TM * (PH_MAXW + 4) * 4)
 int ph_init() {
     if (g_policy_inited) return 0;
-    M3L_HIP(hipFuncSetAttribute((const void*)policy_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_MAX));
-    M3L_HIP(hipFuncSetAttribute((const void*)policy_bwd_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PH_LDS_MAX));
+    if (ph_allow_lds({(const void*)policy_fwd_kernel, (const void*)policy_bwd_chain_kernel}, PH_LDS_MAX)) return 2;
     g_policy_inited = 1;
     return 0;
 }
+
+double ph_flops(const PhArgs& p) { return ph_net_flops(p.br[0], p.B, p.F, p.hn[0]) + ph_net_flops(p.br[1], p.B, p.F, p.hn[1]); }
 
 int ph_forward(const char* who, const m3l_policy_desc* d, int B, const float* x, const float* actions, const float* noise, int mode, void* ws,
                float* actions_out, float* values, float* logp, float* entropy, void* stream) {
@@ -352,13 +286,7 @@ int ph_forward(const char* who, const m3l_policy_desc* d, int B, const float* x,
     if (ph_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const PhArgs p = ph_args(d, B, 1);
-    double fl = 0;
-    for (int bi = 0; bi < 2; ++bi) {
-        int K = p.F;
-        for (int l = 0; l < p.br[bi].n; ++l) { fl += 2.0 * B * K * p.br[bi].w[l]; K = p.br[bi].w[l]; }
-        fl += 2.0 * B * K * p.br[bi].hn;
-    }
-    ProfScope prof(who, B, p.F, p.A, fl, st, 4.0 * B * p.F);
+    ProfScope prof(who, B, p.F, p.A, ph_flops(p), st, 4.0 * B * p.F);
     policy_fwd_kernel<<<dim3(cdiv(B, PH_TM), 2), 256, (size_t)2 * PH_TM * p.ld * 4, st>>>(p, x, actions, noise, mode, (float*)ws, actions_out, values, logp,
                                                                                          entropy);
     M3L_LAUNCH_CHECK();
@@ -400,51 +328,18 @@ int m3l_policy_eval_bwd(const m3l_policy_desc* d, int B, const float* x, const f
     float* w = (float*)ws;
     PhWgrad q;
     memset(&q, 0, sizeof(q));
-    int items = 0;
-    double fl = 0;
-    for (int bi = 0; bi < 2; ++bi) {
-        const PhBranch& b = p.br[bi];
-        const float* X = x;
-        int K = p.F;
-        for (int l = 0; l <= b.n; ++l) {
-            PhLin& L = q.lin[q.count++];
-            const bool head = l == b.n;
-            L.dY = head ? (bi == 0 ? w + p.dmu_off : w + p.dv_off) : w + b.d_off[l];
-            L.X = X;
-            L.N = head ? b.hn : b.w[l];
-            L.K = K;
-            L.ldx = K;
-            if (bi == 0) {
-                L.dW = head ? grads->action_weight : grads->pi_weight[l];
-                L.db = head ? grads->action_bias : grads->pi_bias[l];
-            } else {
-                L.dW = head ? grads->value_weight : grads->vf_weight[l];
-                L.db = head ? grads->value_bias : grads->vf_bias[l];
-            }
-            L.kgroups = cdiv(K, 64);
-            L.item0 = items;
-            items += cdiv(L.N, 16) * L.kgroups;
-            fl += 2.0 * B * L.N * K;
-            if (!head) {
-                X = w + b.h_off[l];
-                K = b.w[l];
-            }
-        }
-    }
-    q.items = items;
     q.B = B;
-    q.A = p.A;
-    q.tiles = cdiv(B, PH_TM);
-    q.part = w + p.part_off;
-    q.dlog_std = grads->log_std;
+    ph_add_net(q, p.br[0], w, x, p.F, p.F, grads->pi_weight, grads->pi_bias, p.hn[0], {{w + p.dmu_off, grads->action_weight, grads->action_bias}});
+    ph_add_net(q, p.br[1], w, x, p.F, p.F, grads->vf_weight, grads->vf_bias, p.hn[1], {{w + p.dv_off, grads->value_weight, grads->value_bias}});
+    const double fl = ph_flops(p);
     {
         ProfScope prof("policy_bwd_chain", B, p.F, p.A, fl, st, 4.0 * B * p.F);
         policy_bwd_chain_kernel<<<cdiv(B, PH_TM), 256, (size_t)2 * PH_TM * p.ld * 4, st>>>(p, actions, dvalues, dlogp, dentropy, w, dx);
         M3L_LAUNCH_CHECK();
     }
     {
-        ProfScope prof("policy_wgrad", B, items, p.A, fl, st, 0.0);
-        policy_wgrad_kernel<<<cdiv(items, 4) + 1, 256, 0, st>>>(q);
+        ProfScope prof("policy_wgrad", B, q.items, p.A, fl, st, 0.0);
+        policy_wgrad_kernel<<<cdiv(q.items, 4) + 1, 256, 0, st>>>(q, p.A, cdiv(B, PH_TM), w + p.part_off, grads->log_std);
         M3L_LAUNCH_CHECK();
     }
     return 0;

@@ -3,7 +3,15 @@
 // MFMA (v_mfma_f32_16x16x4_f32 through Frag<float> / mma16 of common.cuh), and every weight / bias gradient of a head is one item list of one
 // grouped launch that reduces over the rows in row order.  The activation is a template parameter; EDGE variants take a weight whose rows are
 // only 4-byte aligned and whose width is no multiple of 16 (the critics' first layer, K = F + A).
+// A net (the PPO policy and value branches, the SAC actor, each SAC critic) is a PhMlp, a run of Linear + activation layers as data: ph_fwd_walk
+// and ph_bwd_walk run it on the device, ph_layout / ph_bind / ph_add_net / ph_net_flops on the host.  The head Linears on top of a net and
+// their epilogues belong to the head's own file.
 #pragma once
+#include <stdio.h>
+
+#include <initializer_list>
+
+#include "../../include/m3l_amd.h"
 #include "common.cuh"
 
 #define PH_TM 16                 // rows of a tile
@@ -11,10 +19,22 @@
 #define PH_MAXA 64               // most action dimensions
 #define PH_HLD 64                // leading dimension of the heads' LDS tiles
 #define PH_MAXLIN 8              // most Linears of one grouped weight-gradient launch
+#define PH_MAXH 3                // most hidden layers of a net
+static_assert(M3L_POLICY_MAX_HIDDEN == PH_MAXH && M3L_SAC_MAX_HIDDEN == PH_MAXH, "PhMlp holds the hidden layers of either head");
 
 enum { PH_ACT_NONE = 0, PH_ACT_TANH = 1, PH_ACT_RELU = 2 };
 
 namespace {
+
+// a net: n hidden layers Linear + activation, layer l [w[l], w[l - 1]] (layer 0: the input's width)
+struct PhMlp {
+    int n;
+    int w[PH_MAXH];
+    const float* W[PH_MAXH];
+    const float* b[PH_MAXH];
+    long h_off[PH_MAXH];         // post-activation outputs (forward) in the workspace, in floats
+    long d_off[PH_MAXH];         // pre-activation gradients (backward)
+};
 
 // one Linear of the grouped weight-gradient launch: dW [N, K] = dY^T X, db [N] = column sums of dY
 struct PhLin {
@@ -239,6 +259,56 @@ __device__ void ph_load_x(const float* __restrict__ x, int F, int row0, int B, f
     }
 }
 
+// The hidden layers of net m on the tile in cur [16, ld] with K columns: every layer leaves its output in nxt (and, with a workspace, in
+// ws + h_off[l]), then a barrier and the two buffers swap, so cur ends as the last layer's output; returns its width (K without hidden layers).
+// EDGE0: layer 0 takes the EDGE form.
+template <int ACT, bool EDGE0 = false>
+__device__ __forceinline__ int ph_fwd_walk(const PhMlp& m, int K, float*& cur, float*& nxt, int ld, float* __restrict__ ws, int row0, int B) {
+    for (int l = 0; l < m.n; ++l) {
+        float* g = ws ? ws + m.h_off[l] : nullptr;
+        if (EDGE0 && l == 0)
+            ph_fwd_layer<ACT, true>(cur, ld, K, m.W[l], m.b[l], m.w[l], nxt, ld, g, row0, B);
+        else
+            ph_fwd_layer<ACT>(cur, ld, K, m.W[l], m.b[l], m.w[l], nxt, ld, g, row0, B);
+        __syncthreads();
+        float* s = cur; cur = nxt; nxt = s;
+        K = m.w[l];
+    }
+    return K;
+}
+
+// Back through the hidden layers top .. 0 of net m.  In: cur [16, ld] holds the gradient tile (`valid` columns written) of the output of the
+// Linear W [N, w[top]] above layer top.  Every layer leaves its pre-activation gradient in nxt and in ws + d_off[l], then a barrier and the
+// buffers swap.  Out: cur, valid, W, N are the same four for the net's input (layer 0's pre-activation gradient and weight; unchanged when
+// top < 0), which the caller takes on to dx.
+template <int ACT>
+__device__ __forceinline__ void ph_bwd_walk(const PhMlp& m, int top, float*& cur, float*& nxt, int ld, int& valid, const float*& W, int& N, float* ws,
+                                            int row0, int B) {
+    for (int l = top; l >= 0; --l) {
+        const int K = m.w[l];
+        ph_bwd_layer<ACT>(cur, ld, valid, W, N, K, ws + m.h_off[l], nxt, ld, ws + m.d_off[l], false, row0, B);
+        __syncthreads();
+        float* s = cur; cur = nxt; nxt = s;
+        W = m.W[l];
+        N = K;
+        valid = K;
+    }
+}
+
+// the gradient tile of a one-column head: [16, 8] with src[row] (null: zero) in column 0, which also stays in keep[row] for the weight gradient
+__device__ __forceinline__ void ph_col0_tile(const float* __restrict__ src, float* __restrict__ keep, float* tile, int ld, int row0, int B) {
+    const int tid = threadIdx.x;
+    if (tid < PH_TM * 8) {
+        const int m = tid >> 3, j = tid & 7, row = row0 + m;
+        float v = 0.f;
+        if (j == 0 && row < B) {
+            v = src ? src[row] : 0.f;
+            keep[row] = v;
+        }
+        tile[m * ld + j] = v;
+    }
+}
+
 // operands of one 32-row step of a weight gradient: a = dY^T (lane i: column n of dY, rows mb .. mb + 7), b = X for four interleaved tiles (the 16
 // bytes X[row][kc .. kc + 3]: tile t takes column kc + t; ldx is a multiple of 16, so the four are inside or outside together)
 __device__ __forceinline__ void ph_wgrad_load(const PhLin& L, int B, int n, int kc, int mb, Frag<float>& a, Frag<float> (&b)[4]) {
@@ -296,6 +366,18 @@ __device__ void ph_wgrad_item(const PhLin* lin, int count, int item, int B) {
     if (kg == 0 && g == 0 && n < N) L.db[n] = bsum;
 }
 
+// the item list of one grouped weight-gradient launch
+struct PhWgrad {
+    PhLin lin[PH_MAXLIN];
+    int count, items, B;
+};
+// workgroup `block` of a grouped launch (grid cdiv(items, 4), 256 threads): wave w takes item 4 block + w
+__device__ __forceinline__ void ph_wgrad_block(const PhWgrad& q, int block) {
+    const int item = block * 4 + (threadIdx.x >> 6);
+    if (item >= q.items) return;                  // a whole wave leaves: the lanes that stay are all active
+    ph_wgrad_item(q.lin, q.count, item, q.B);
+}
+
 // one workgroup of 256 threads
 __device__ __forceinline__ float ph_block_sum(float v, float* red) {
     v = wave_sum(v);
@@ -308,5 +390,91 @@ __device__ __forceinline__ float ph_block_sum(float v, float* red) {
 
 inline long ph_round4(long v) { return (v + 3) & ~3L; }
 inline bool ph_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The limits of the header for a head with two kinds of net (n0 / n1 hidden layers of widths w0 / w1); 0 and a message when it is outside
+// them.  noun: what the head calls one net; widest: the widest row the kernels index, for the bound on B.
+inline int ph_dims_ok(int B, int features, int actions, int n0, const int* w0, int n1, const int* w1, const char* noun, int widest, char* why, size_t n) {
+    if (B < 1) { snprintf(why, n, "B=%d (B >= 1)", B); return 0; }
+    if (features < 16 || features % 16 || features > PH_MAXW) {
+        snprintf(why, n, "features=%d (a multiple of 16, at most %d)", features, PH_MAXW);
+        return 0;
+    }
+    if (actions < 1 || actions > PH_MAXA) { snprintf(why, n, "actions=%d (1 <= A <= %d)", actions, PH_MAXA); return 0; }
+    if (n0 < 0 || n0 > PH_MAXH || n1 < 0 || n1 > PH_MAXH) {
+        snprintf(why, n, "%d / %d hidden layers (0 to %d per %s)", n0, n1, PH_MAXH, noun);
+        return 0;
+    }
+    for (int l = 0; l < n0 + n1; ++l) {
+        const int w = l < n0 ? w0[l] : w1[l - n0];
+        if (w < 16 || w % 16 || w > PH_MAXW) { snprintf(why, n, "hidden width %d (a multiple of 16, at most %d)", w, PH_MAXW); return 0; }
+    }
+    if ((long)B * widest >= 2147483647L / 4) { snprintf(why, n, "B=%d rows are more than the kernels index", B); return 0; }
+    return 1;
+}
+
+// net m gets its n widths and, from `off` on, the workspace places of its activations and gradients; returns the offset behind them and
+// raises `widest` to the widest layer
+inline long ph_layout(PhMlp& m, int n, const int* width, int B, long off, int& widest) {
+    m.n = n;
+    for (int l = 0; l < n; ++l) {
+        m.w[l] = width[l];
+        if (m.w[l] > widest) widest = m.w[l];
+        m.h_off[l] = off;
+        off += (long)B * m.w[l];
+        m.d_off[l] = off;
+        off += (long)B * m.w[l];
+    }
+    return off;
+}
+
+// the parameter pointers of a net's n hidden layers: every one given and every weight on a 16-byte boundary; ph_bind puts them into the net
+inline int ph_ptrs_ok(int n, float* const* W, float* const* b) {
+    int ok = 1;
+    for (int l = 0; l < n; ++l) ok = ok && W[l] && b[l] && ph_aligned(W[l]);
+    return ok;
+}
+inline void ph_bind(PhMlp& m, float* const* W, float* const* b) {
+    for (int l = 0; l < m.n; ++l) { m.W[l] = W[l]; m.b[l] = b[l]; }
+}
+
+// multiply-adds x 2 of net m on B rows of width K and of `rows` head rows on top of it
+inline double ph_net_flops(const PhMlp& m, int B, int K, int rows) {
+    double fl = 0;
+    for (int l = 0; l < m.n; ++l) { fl += 2.0 * B * K * m.w[l]; K = m.w[l]; }
+    return fl + 2.0 * B * K * rows;
+}
+
+// appends one Linear to a grouped launch: dW [N, K] from dY [B, N] and X [B, ldx]
+inline void ph_add_lin(PhWgrad& q, const float* dY, const float* X, int ldx, float* dW, float* db, int N, int K) {
+    PhLin& L = q.lin[q.count++];
+    L.dY = dY; L.X = X; L.dW = dW; L.db = db; L.N = N; L.K = K; L.ldx = ldx;
+    L.edge = (K & 15) != 0;
+    L.kgroups = cdiv(K, 64);
+    L.item0 = q.items;
+    q.items += cdiv(N, 16) * L.kgroups;
+}
+// one head Linear on top of a net: its output gradient in the workspace and where its dW / db go
+struct PhHeadGrad {
+    const float* dY;
+    float* dW;
+    float* db;
+};
+// appends the Linears of net m and then its heads (`rows` rows each).  X [B, ldx]: the net's input, K wide; the hidden layers' output
+// gradients and the deeper inputs are where the chain kernel left them in ws; dW / db: the hidden layers' gradient pointers.
+inline void ph_add_net(PhWgrad& q, const PhMlp& m, const float* ws, const float* X, int K, int ldx, float* const* dW, float* const* db, int rows,
+                       std::initializer_list<PhHeadGrad> heads) {
+    for (int l = 0; l < m.n; ++l) {
+        ph_add_lin(q, ws + m.d_off[l], X, ldx, dW[l], db[l], m.w[l], K);
+        X = ws + m.h_off[l];
+        K = ldx = m.w[l];
+    }
+    for (const PhHeadGrad& h : heads) ph_add_lin(q, h.dY, X, ldx, h.dW, h.db, rows, K);
+}
+
+// the chain kernels of a head may use `bytes` of dynamic LDS
+inline int ph_allow_lds(std::initializer_list<const void*> kernels, int bytes) {
+    for (const void* k : kernels) M3L_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return 0;
+}
 
 }  // namespace

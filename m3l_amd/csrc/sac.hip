@@ -1,6 +1,6 @@
 // SAC policy head (include/m3l_amd.h "SAC policy head"): the squashed-Gaussian actor (latent_pi, mu, a state-dependent clamped log_std, tanh),
 // the twin critics over cat([x, actions]), the TD target, and the three losses of SAC_MAE.train.  float32 throughout on the exact-f32 MFMA, with
-// the row-tile pieces of policy_common.cuh (ReLU instead of the PPO head's Tanh).
+// the row-tile pieces of policy_common.cuh (ReLU instead of the PPO head's Tanh); the actor and each critic are PhMlp nets run by its walks.
 //
 //   actor fwd    one launch, grid (row tiles of 16): x -> LDS, the hidden layers ping-pong between two LDS buffers, the mu and log_std heads
 //                leave two [16, A] tiles, then u = mu + exp(s) noise, a = tanh(u) and the row's log-probability.  With a workspace the
@@ -28,34 +28,20 @@
 #define SAC_HALF_LOG_2PI 0.91893853320467274178f
 #define SAC_LOG_STD_MIN -20.f
 #define SAC_LOG_STD_MAX 2.f
-#define SAC_NH M3L_SAC_MAX_HIDDEN
 
 namespace {
 
 struct SacArgs {
     int B, F, A, ld;             // ld: leading dimension of the LDS activation buffers
     int K0, Kp;                  // the critics' input width F + A, and the same rounded up to 16
-    // actor
-    int n_pi, pi_w[SAC_NH];
-    const float* pi_W[SAC_NH];
-    const float* pi_b[SAC_NH];
+    PhMlp pi;                                // actor: latent_pi, then the mu and log_std heads [A, .]
     const float *mu_W, *mu_b, *s_W, *s_b;
-    long pi_h[SAC_NH], pi_d[SAC_NH];         // post-ReLU activations / pre-activation gradients in the workspace, in floats
     long u_off, s_off, dmu_off, ds_off;      // u, pre-clamp log_std, d mu, d (pre-clamp log_std): [B, A] each
-    // critics
-    int n_qf, qf_w[SAC_NH];
-    const float* qf_W[2][SAC_NH];
-    const float* qf_b[2][SAC_NH];
+    PhMlp qf[2];                             // critics: alike in their widths; layer 0 [., F + A], then the head [1, .]
     const float* q_W[2];
     const float* q_b[2];
-    long qf_h[2][SAC_NH], qf_d[2][SAC_NH];
     long xa_off, dq_off;                     // the input [B, Kp]; d q [2, B]
     long total;
-};
-
-struct SacWgrad {
-    PhLin lin[PH_MAXLIN];
-    int count, items, B;
 };
 
 // 1 - tanh(u)^2 without the cancellation: 4 e / (1 + e)^2 with e = exp(-2 |u|)
@@ -73,13 +59,7 @@ __device__ void sac_actor_tile(const SacArgs& p, const float* __restrict__ x, co
     float* nxt = bufb;
     ph_load_x(x, p.F, row0, B, cur, p.ld);
     __syncthreads();
-    int K = p.F;
-    for (int l = 0; l < p.n_pi; ++l) {
-        ph_fwd_layer<PH_ACT_RELU>(cur, p.ld, K, p.pi_W[l], p.pi_b[l], p.pi_w[l], nxt, p.ld, ws ? ws + p.pi_h[l] : nullptr, row0, B);
-        __syncthreads();
-        float* s = cur; cur = nxt; nxt = s;
-        K = p.pi_w[l];
-    }
+    const int K = ph_fwd_walk<PH_ACT_RELU>(p.pi, p.F, cur, nxt, p.ld, ws, row0, B);
     ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.mu_W, p.mu_b, A, hmu, PH_HLD, nullptr, row0, B);
     ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.s_W, p.s_b, A, hs, PH_HLD, nullptr, row0, B);
     __syncthreads();
@@ -125,18 +105,8 @@ __device__ void sac_build_xa(const SacArgs& p, const float* __restrict__ x, cons
 __device__ void sac_critic_tile(const SacArgs& p, int c, int row0, float* bufa, float* bufb, float* head, float* __restrict__ ws) {
     float* cur = bufa;
     float* nxt = bufb;
-    int K = p.K0;
-    for (int l = 0; l < p.n_qf; ++l) {
-        float* g = ws ? ws + p.qf_h[c][l] : nullptr;
-        if (l == 0)
-            ph_fwd_layer<PH_ACT_RELU, true>(cur, p.ld, K, p.qf_W[c][l], p.qf_b[c][l], p.qf_w[l], nxt, p.ld, g, row0, p.B);
-        else
-            ph_fwd_layer<PH_ACT_RELU>(cur, p.ld, K, p.qf_W[c][l], p.qf_b[c][l], p.qf_w[l], nxt, p.ld, g, row0, p.B);
-        __syncthreads();
-        float* s = cur; cur = nxt; nxt = s;
-        K = p.qf_w[l];
-    }
-    if (p.n_qf == 0)
+    const int K = ph_fwd_walk<PH_ACT_RELU, true>(p.qf[c], p.K0, cur, nxt, p.ld, ws, row0, p.B);
+    if (p.qf[c].n == 0)                      // the head is the first Linear then: K = F + A, the EDGE form
         ph_fwd_layer<PH_ACT_NONE, true>(cur, p.ld, K, p.q_W[c], p.q_b[c], 1, head, PH_HLD, nullptr, row0, p.B);
     else
         ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.q_W[c], p.q_b[c], 1, head, PH_HLD, nullptr, row0, p.B);
@@ -181,27 +151,22 @@ __global__ __launch_bounds__(256) void sac_actor_bwd_kernel(SacArgs p, const flo
     }
     __syncthreads();
     const int hv = (A + 7) & ~7;
-    if (p.n_pi == 0) {
+    if (p.pi.n == 0) {
         ph_bwd_layer<PH_ACT_NONE>(tmu, PH_HLD, hv, p.mu_W, A, p.F, nullptr, nullptr, 0, dx, false, row0, B);
         __syncthreads();
         ph_bwd_layer<PH_ACT_NONE>(ts, PH_HLD, hv, p.s_W, A, p.F, nullptr, nullptr, 0, dx, true, row0, B);
         return;
     }
-    int l = p.n_pi - 1;
-    int K = p.pi_w[l];
+    const int l = p.pi.n - 1;
+    int N = p.pi.w[l], valid = N;
     // both heads into the last hidden layer: the ReLU gate is 0 or 1, so gating each product and adding is gating the sum
-    ph_bwd_layer<PH_ACT_RELU>(tmu, PH_HLD, hv, p.mu_W, A, K, ws + p.pi_h[l], cur, p.ld, nullptr, false, row0, B);
+    ph_bwd_layer<PH_ACT_RELU>(tmu, PH_HLD, hv, p.mu_W, A, N, ws + p.pi.h_off[l], cur, p.ld, nullptr, false, row0, B);
     __syncthreads();
-    ph_bwd_layer<PH_ACT_RELU>(ts, PH_HLD, hv, p.s_W, A, K, ws + p.pi_h[l], cur, p.ld, ws + p.pi_d[l], true, row0, B);
+    ph_bwd_layer<PH_ACT_RELU>(ts, PH_HLD, hv, p.s_W, A, N, ws + p.pi.h_off[l], cur, p.ld, ws + p.pi.d_off[l], true, row0, B);
     __syncthreads();
-    for (--l; l >= 0; --l) {
-        const int N = K;
-        K = p.pi_w[l];
-        ph_bwd_layer<PH_ACT_RELU>(cur, p.ld, N, p.pi_W[l + 1], N, K, ws + p.pi_h[l], nxt, p.ld, ws + p.pi_d[l], false, row0, B);
-        __syncthreads();
-        float* s = cur; cur = nxt; nxt = s;
-    }
-    ph_bwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.pi_W[0], K, p.F, nullptr, nullptr, 0, dx, false, row0, B);
+    const float* W = p.pi.W[l];
+    ph_bwd_walk<PH_ACT_RELU>(p.pi, l - 1, cur, nxt, p.ld, valid, W, N, ws, row0, B);      // the layers below the one the heads feed
+    ph_bwd_layer<PH_ACT_NONE>(cur, p.ld, valid, W, N, p.F, nullptr, nullptr, 0, dx, false, row0, B);
 }
 
 // grid (row tiles, 2 critics).  q [2, B]
@@ -229,32 +194,15 @@ __global__ __launch_bounds__(256) void sac_critic_fwd_kernel(SacArgs p, const fl
 // grid (row tiles).  dq [2, B] or null (= zero); dactions [B, A] or null (not wanted)
 __global__ __launch_bounds__(256) void sac_critic_bwd_kernel(SacArgs p, const float* __restrict__ dq, float* __restrict__ ws, float* __restrict__ dactions) {
     extern __shared__ __attribute__((aligned(16))) float sac_lds[];
-    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B;
+    const int row0 = blockIdx.x * PH_TM, B = p.B;
     for (int c = 0; c < 2; ++c) {
         float* cur = sac_lds;
         float* nxt = sac_lds + PH_TM * p.ld;
-        // d q of this critic: [16, 8] with the value in column 0
-        if (tid < PH_TM * 8) {
-            const int m = tid >> 3, j = tid & 7, row = row0 + m;
-            float v = 0.f;
-            if (j == 0 && row < B) {
-                v = dq ? dq[(long)c * B + row] : 0.f;
-                ws[p.dq_off + (long)c * B + row] = v;
-            }
-            cur[m * p.ld + j] = v;
-        }
+        ph_col0_tile(dq ? dq + (long)c * B : nullptr, ws + p.dq_off + (long)c * B, cur, p.ld, row0, B);      // d q of this critic
         __syncthreads();
         const float* W = p.q_W[c];
         int N = 1, valid = 8;
-        for (int l = p.n_qf - 1; l >= 0; --l) {
-            const int K = p.qf_w[l];
-            ph_bwd_layer<PH_ACT_RELU>(cur, p.ld, valid, W, N, K, ws + p.qf_h[c][l], nxt, p.ld, ws + p.qf_d[c][l], false, row0, B);
-            __syncthreads();
-            float* s = cur; cur = nxt; nxt = s;
-            W = p.qf_W[c][l];
-            N = K;
-            valid = K;
-        }
+        ph_bwd_walk<PH_ACT_RELU>(p.qf[c], p.qf[c].n - 1, cur, nxt, p.ld, valid, W, N, ws, row0, B);
         // the action columns of the first weight; critic 1 adds to what critic 0 wrote, lane for lane
         if (dactions != nullptr) ph_bwd_edge(cur, p.ld, valid, W, N, p.K0, p.F, p.A, dactions, c == 1, row0, B);
         __syncthreads();
@@ -262,11 +210,7 @@ __global__ __launch_bounds__(256) void sac_critic_bwd_kernel(SacArgs p, const fl
 }
 
 // grid (cdiv(items, 4)): wave w of block b takes item 4 b + w
-__global__ __launch_bounds__(256) void sac_wgrad_kernel(SacWgrad q) {
-    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (item >= q.items) return;                  // a whole wave leaves: the lanes that stay are all active
-    ph_wgrad_item(q.lin, q.count, item, q.B);
-}
+__global__ __launch_bounds__(256) void sac_wgrad_kernel(PhWgrad q) { ph_wgrad_block(q, blockIdx.x); }
 
 // grid (row tiles).  The critic pointers of p are the target critics'.
 __global__ __launch_bounds__(256) void sac_td_target_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ noise,
@@ -357,22 +301,7 @@ enum { SAC_ACTOR = 1, SAC_CRITIC = 2 };
 // the limits of the header; 0 and a message when the head is outside them
 int sac_shape_ok(const m3l_sac_desc* d, int B, char* why, size_t n) {
     if (d == nullptr) { snprintf(why, n, "null descriptor"); return 0; }
-    if (B < 1) { snprintf(why, n, "B=%d (B >= 1)", B); return 0; }
-    if (d->features < 16 || d->features % 16 || d->features > PH_MAXW) {
-        snprintf(why, n, "features=%d (a multiple of 16, at most %d)", d->features, PH_MAXW);
-        return 0;
-    }
-    if (d->actions < 1 || d->actions > PH_MAXA) { snprintf(why, n, "actions=%d (1 <= A <= %d)", d->actions, PH_MAXA); return 0; }
-    if (d->n_pi < 0 || d->n_pi > SAC_NH || d->n_qf < 0 || d->n_qf > SAC_NH) {
-        snprintf(why, n, "%d / %d hidden layers (0 to %d per net)", d->n_pi, d->n_qf, SAC_NH);
-        return 0;
-    }
-    for (int l = 0; l < d->n_pi + d->n_qf; ++l) {
-        const int w = l < d->n_pi ? d->pi_width[l] : d->qf_width[l - d->n_pi];
-        if (w < 16 || w % 16 || w > PH_MAXW) { snprintf(why, n, "hidden width %d (a multiple of 16, at most %d)", w, PH_MAXW); return 0; }
-    }
-    if ((long)B * (PH_MAXW + PH_MAXA) >= 2147483647L / 4) { snprintf(why, n, "B=%d rows are more than the kernels index", B); return 0; }
-    return 1;
+    return ph_dims_ok(B, d->features, d->actions, d->n_pi, d->pi_width, d->n_qf, d->qf_width, "net", PH_MAXW + PH_MAXA, why, n);
 }
 
 // kernel arguments and workspace layout; parts: whose parameter pointers are read (0 only sizes the workspace)
@@ -385,16 +314,7 @@ SacArgs sac_args(const m3l_sac_desc* d, int B, int parts) {
     p.K0 = p.F + p.A;
     p.Kp = (p.K0 + 15) & ~15;
     int widest = p.Kp > PH_MAXA ? p.Kp : PH_MAXA;
-    long off = 0;
-    p.n_pi = d->n_pi;
-    for (int l = 0; l < p.n_pi; ++l) {
-        p.pi_w[l] = d->pi_width[l];
-        if (p.pi_w[l] > widest) widest = p.pi_w[l];
-        p.pi_h[l] = off;
-        off += (long)B * p.pi_w[l];
-        p.pi_d[l] = off;
-        off += (long)B * p.pi_w[l];
-    }
+    long off = ph_layout(p.pi, d->n_pi, d->pi_width, B, 0, widest);
     p.u_off = off;
     off = ph_round4(off + (long)B * p.A);
     p.s_off = off;
@@ -403,18 +323,7 @@ SacArgs sac_args(const m3l_sac_desc* d, int B, int parts) {
     off = ph_round4(off + (long)B * p.A);
     p.ds_off = off;
     off = ph_round4(off + (long)B * p.A);
-    p.n_qf = d->n_qf;
-    for (int l = 0; l < p.n_qf; ++l) {
-        p.qf_w[l] = d->qf_width[l];
-        if (p.qf_w[l] > widest) widest = p.qf_w[l];
-    }
-    for (int c = 0; c < 2; ++c)
-        for (int l = 0; l < p.n_qf; ++l) {
-            p.qf_h[c][l] = off;
-            off += (long)B * p.qf_w[l];
-            p.qf_d[c][l] = off;
-            off += (long)B * p.qf_w[l];
-        }
+    for (int c = 0; c < 2; ++c) off = ph_layout(p.qf[c], d->n_qf, d->qf_width, B, off, widest);
     p.xa_off = off;
     off += (long)B * p.Kp;
     p.dq_off = off;
@@ -422,12 +331,12 @@ SacArgs sac_args(const m3l_sac_desc* d, int B, int parts) {
     p.total = off;
     p.ld = widest + 4;
     if (parts & SAC_ACTOR) {
-        for (int l = 0; l < p.n_pi; ++l) { p.pi_W[l] = d->pi_weight[l]; p.pi_b[l] = d->pi_bias[l]; }
+        ph_bind(p.pi, d->pi_weight, d->pi_bias);
         p.mu_W = d->mu_weight; p.mu_b = d->mu_bias; p.s_W = d->log_std_weight; p.s_b = d->log_std_bias;
     }
     if (parts & SAC_CRITIC)
         for (int c = 0; c < 2; ++c) {
-            for (int l = 0; l < p.n_qf; ++l) { p.qf_W[c][l] = d->qf_weight[c][l]; p.qf_b[c][l] = d->qf_bias[c][l]; }
+            ph_bind(p.qf[c], d->qf_weight[c], d->qf_bias[c]);
             p.q_W[c] = d->q_weight[c]; p.q_b[c] = d->q_bias[c];
         }
     return p;
@@ -435,15 +344,11 @@ SacArgs sac_args(const m3l_sac_desc* d, int B, int parts) {
 
 int sac_params_ok(const m3l_sac_desc* d, int parts, const char* who) {
     int ok = 1;
-    if (parts & SAC_ACTOR) {
-        ok = ok && d->mu_weight && d->mu_bias && d->log_std_weight && d->log_std_bias && ph_aligned(d->mu_weight) && ph_aligned(d->log_std_weight);
-        for (int l = 0; l < d->n_pi; ++l) ok = ok && d->pi_weight[l] && d->pi_bias[l] && ph_aligned(d->pi_weight[l]);
-    }
+    if (parts & SAC_ACTOR)
+        ok = ok && d->mu_weight && d->mu_bias && d->log_std_weight && d->log_std_bias && ph_aligned(d->mu_weight) && ph_aligned(d->log_std_weight) &&
+             ph_ptrs_ok(d->n_pi, d->pi_weight, d->pi_bias);
     if (parts & SAC_CRITIC)
-        for (int c = 0; c < 2; ++c) {
-            ok = ok && d->q_weight[c] && d->q_bias[c] && ph_aligned(d->q_weight[c]);
-            for (int l = 0; l < d->n_qf; ++l) ok = ok && d->qf_weight[c][l] && d->qf_bias[c][l] && ph_aligned(d->qf_weight[c][l]);
-        }
+        for (int c = 0; c < 2; ++c) ok = ok && d->q_weight[c] && d->q_bias[c] && ph_aligned(d->q_weight[c]) && ph_ptrs_ok(d->n_qf, d->qf_weight[c], d->qf_bias[c]);
     M3L_CHECK(ok, "%s: a parameter pointer of the descriptor is null or a weight is not 16-byte aligned", who);
     return 0;
 }
@@ -452,38 +357,17 @@ int g_sac_inited = 0;
 #define SAC_LDS_MAX (2 * PH_TM * (PH_MAXW + PH_MAXA + 4) * 4)
 int sac_init() {
     if (g_sac_inited) return 0;
-    M3L_HIP(hipFuncSetAttribute((const void*)sac_actor_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
-    M3L_HIP(hipFuncSetAttribute((const void*)sac_actor_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
-    M3L_HIP(hipFuncSetAttribute((const void*)sac_critic_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
-    M3L_HIP(hipFuncSetAttribute((const void*)sac_critic_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
-    M3L_HIP(hipFuncSetAttribute((const void*)sac_td_target_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAC_LDS_MAX));
+    if (ph_allow_lds({(const void*)sac_actor_fwd_kernel, (const void*)sac_actor_bwd_kernel, (const void*)sac_critic_fwd_kernel,
+                      (const void*)sac_critic_bwd_kernel, (const void*)sac_td_target_kernel}, SAC_LDS_MAX))
+        return 2;
     g_sac_inited = 1;
     return 0;
 }
 
 size_t sac_lds_bytes(const SacArgs& p) { return (size_t)2 * PH_TM * p.ld * 4; }
 
-double sac_actor_flops(const SacArgs& p) {
-    double fl = 0;
-    int K = p.F;
-    for (int l = 0; l < p.n_pi; ++l) { fl += 2.0 * p.B * K * p.pi_w[l]; K = p.pi_w[l]; }
-    return fl + 4.0 * p.B * K * p.A;
-}
-double sac_critic_flops(const SacArgs& p) {
-    double fl = 0;
-    int K = p.K0;
-    for (int l = 0; l < p.n_qf; ++l) { fl += 2.0 * p.B * K * p.qf_w[l]; K = p.qf_w[l]; }
-    return 2.0 * (fl + 2.0 * p.B * K);
-}
-
-void sac_add_lin(SacWgrad& q, const float* dY, const float* X, int ldx, float* dW, float* db, int N, int K) {
-    PhLin& L = q.lin[q.count++];
-    L.dY = dY; L.X = X; L.dW = dW; L.db = db; L.N = N; L.K = K; L.ldx = ldx;
-    L.edge = (K & 15) != 0;
-    L.kgroups = cdiv(K, 64);
-    L.item0 = q.items;
-    q.items += cdiv(N, 16) * L.kgroups;
-}
+double sac_actor_flops(const SacArgs& p) { return ph_net_flops(p.pi, p.B, p.F, 2 * p.A); }
+double sac_critic_flops(const SacArgs& p) { return 2.0 * ph_net_flops(p.qf[0], p.B, p.K0, 1); }
 
 }  // namespace
 
@@ -521,18 +405,11 @@ int m3l_sac_actor_bwd(const m3l_sac_desc* d, int B, const float* x, const float*
     hipStream_t st = (hipStream_t)stream;
     const SacArgs p = sac_args(d, B, SAC_ACTOR);
     float* w = (float*)ws;
-    SacWgrad q;
+    PhWgrad q;
     memset(&q, 0, sizeof(q));
     q.B = B;
-    const float* X = x;
-    int K = p.F;
-    for (int l = 0; l < p.n_pi; ++l) {
-        sac_add_lin(q, w + p.pi_d[l], X, K, grads->pi_weight[l], grads->pi_bias[l], p.pi_w[l], K);
-        X = w + p.pi_h[l];
-        K = p.pi_w[l];
-    }
-    sac_add_lin(q, w + p.dmu_off, X, K, grads->mu_weight, grads->mu_bias, p.A, K);
-    sac_add_lin(q, w + p.ds_off, X, K, grads->log_std_weight, grads->log_std_bias, p.A, K);
+    ph_add_net(q, p.pi, w, x, p.F, p.F, grads->pi_weight, grads->pi_bias, p.A,
+               {{w + p.dmu_off, grads->mu_weight, grads->mu_bias}, {w + p.ds_off, grads->log_std_weight, grads->log_std_bias}});
     {
         ProfScope prof("sac_actor_bwd_chain", B, p.F, p.A, sac_actor_flops(p), st, 4.0 * B * p.F);
         sac_actor_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, noise, dactions, dlogp, w, dx);
@@ -577,19 +454,12 @@ int m3l_sac_critic_bwd(const m3l_sac_desc* d, int B, const float* dq, void* ws, 
         M3L_LAUNCH_CHECK();
     }
     if (grads == nullptr) return 0;
-    SacWgrad q;
+    PhWgrad q;
     memset(&q, 0, sizeof(q));
     q.B = B;
-    for (int c = 0; c < 2; ++c) {
-        const float* X = w + p.xa_off;
-        int K = p.K0, ldx = p.Kp;
-        for (int l = 0; l < p.n_qf; ++l) {
-            sac_add_lin(q, w + p.qf_d[c][l], X, ldx, grads->qf_weight[c][l], grads->qf_bias[c][l], p.qf_w[l], K);
-            X = w + p.qf_h[c][l];
-            K = ldx = p.qf_w[l];
-        }
-        sac_add_lin(q, w + p.dq_off + (long)c * B, X, ldx, grads->q_weight[c], grads->q_bias[c], 1, K);
-    }
+    for (int c = 0; c < 2; ++c)
+        ph_add_net(q, p.qf[c], w, w + p.xa_off, p.K0, p.Kp, grads->qf_weight[c], grads->qf_bias[c], 1,
+                   {{w + p.dq_off + (long)c * B, grads->q_weight[c], grads->q_bias[c]}});
     ProfScope prof("sac_critic_wgrad", B, q.items, p.A, sac_critic_flops(p), st, 0.0);
     sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
     M3L_LAUNCH_CHECK();

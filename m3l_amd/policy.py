@@ -15,16 +15,16 @@ Everything is float32 whatever the encoder's compute type: the ratio exp(logp - 
 fallback: every number comes from a kernel, torch owns memory and the autograd tape.
 """
 import ctypes as C
-import numbers
 from typing import NamedTuple, Tuple
 
 import torch
 from torch import nn
 
+from . import _head as H
 from . import _lib as L
+from ._head import MAX_ACTIONS, MAX_HIDDEN, MAX_WIDTH, _dev, _rows, _vec  # noqa: F401  (the limits and the tensor preparation, under their names here)
 from .functional import _require_cuda, _stream, _ws
 
-MAX_HIDDEN, MAX_WIDTH, MAX_ACTIONS = 3, 512, 64
 STAT_NAMES = ("policy_loss", "value_loss", "entropy_loss", "clip_fraction", "approx_kl")
 
 
@@ -46,23 +46,9 @@ class HeadParams(NamedTuple):
         _reject_policy_flags(policy)
         if not isinstance(getattr(policy, "log_std", None), torch.Tensor):
             raise ValueError("the policy has no log_std: the HIP policy head computes the diagonal Gaussian of a continuous (Box) action space only")
-        return HeadParams(_branch_params(policy.mlp_extractor.policy_net, "mlp_extractor.policy_net"),
-                          _branch_params(policy.mlp_extractor.value_net, "mlp_extractor.value_net"),
+        return HeadParams(H.linear_pairs(policy.mlp_extractor.policy_net, "mlp_extractor.policy_net", nn.Tanh, "policy"),
+                          H.linear_pairs(policy.mlp_extractor.value_net, "mlp_extractor.value_net", nn.Tanh, "policy"),
                           (policy.action_net.weight, policy.action_net.bias), (policy.value_net.weight, policy.value_net.bias), policy.log_std)
-
-
-def _branch_params(seq, name):
-    mods = list(seq)
-    if len(mods) % 2:
-        raise ValueError(f"{name}: Linear / Tanh pairs expected, got {len(mods)} modules")
-    out = []
-    for i in range(0, len(mods), 2):
-        if not isinstance(mods[i], nn.Linear) or mods[i].bias is None:
-            raise ValueError(f"{name}.{i}: nn.Linear with a bias expected, got {type(mods[i]).__name__}")
-        if not isinstance(mods[i + 1], nn.Tanh):
-            raise ValueError(f"{name}.{i + 1}: the HIP policy head computes Tanh only, got {type(mods[i + 1]).__name__}")
-        out.append((mods[i].weight, mods[i].bias))
-    return tuple(out)
 
 
 def _reject_policy_flags(policy):
@@ -78,37 +64,14 @@ def _arch(x, params: HeadParams):
     """(F, A, pi widths, vf widths) with every shape checked; raises ValueError for a head outside the kernels' limits."""
     F = int(x.shape[-1])
     A = int(params.log_std.numel())
-    for t in params.flat():
-        if t.dtype != torch.float32:
-            raise ValueError(f"policy head parameter of dtype {t.dtype}: the HIP policy head computes in float32 and returns float32 gradients; "
-                             "keep the head's parameters in float32 whatever the encoder's compute type")
+    H.check_float32(params.flat(), "policy")
     widths = []
-    for name, br, (hw, hb), hn in (("pi", params.pi, params.action, A), ("vf", params.vf, params.value, 1)):
-        if len(br) > MAX_HIDDEN:
-            raise ValueError(f"{name}: {len(br)} hidden layers (the HIP policy head runs 0 to {MAX_HIDDEN} per branch)")
-        k, ws = F, []
-        for l, (w, b) in enumerate(br):
-            if w.dim() != 2 or w.shape[1] != k or tuple(b.shape) != (w.shape[0],):
-                raise ValueError(f"{name} layer {l}: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not follow an input of width {k}")
-            k = int(w.shape[0])
-            ws.append(k)
-        if tuple(hw.shape) != (hn, k) or tuple(hb.shape) != (hn,):
-            raise ValueError(f"{name} head: weight {tuple(hw.shape)} / bias {tuple(hb.shape)}, expected ({hn}, {k}) / ({hn},)")
-        widths.append(tuple(ws))
-    for w in (F,) + widths[0] + widths[1]:
-        if w < 16 or w % 16 or w > MAX_WIDTH:
-            raise ValueError(f"width {w}: features and hidden widths must be multiples of 16, at most {MAX_WIDTH}")
-    if not 1 <= A <= MAX_ACTIONS:
-        raise ValueError(f"{A} action dimensions (1 to {MAX_ACTIONS})")
+    for name, br, head_name, head, hn in (("pi", params.pi, "pi head", params.action, A), ("vf", params.vf, "vf head", params.value, 1)):
+        k, ws = H.layer_widths(F, br, name, "policy", "branch")
+        H.check_head_linear(head_name, head, hn, k)
+        widths.append(ws)
+    H.check_limits((F,) + widths[0] + widths[1], A)
     return F, A, widths[0], widths[1]
-
-
-def _dev(t):
-    """float32, contiguous, 16-byte aligned, detached."""
-    t = t.detach()
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.contiguous().float()
-    return t.clone() if t.data_ptr() % 16 else t
 
 
 def _desc(arch, flat):
@@ -127,20 +90,6 @@ def _desc(arch, flat):
     d.value_weight, d.value_bias = next(it).data_ptr(), next(it).data_ptr()
     d.log_std = next(it).data_ptr()
     return d
-
-
-def _rows(x, what, width=None):
-    _require_cuda(x, what)
-    if x.dim() != 2 or x.shape[0] < 1 or (width is not None and x.shape[1] != width):
-        raise ValueError(f"{what}: (B, {width if width is not None else 'F'}) expected, got {tuple(x.shape)}")
-    return _dev(x)
-
-
-def _vec(t, what, B):
-    _require_cuda(t, what)
-    if t.numel() != B:
-        raise ValueError(f"{what}: {B} values expected, got {tuple(t.shape)}")
-    return _dev(t).reshape(B)
 
 
 class ActorCriticEvalFn(torch.autograd.Function):
@@ -168,7 +117,7 @@ class ActorCriticEvalFn(torch.autograd.Function):
     def backward(ctx, dvalues, dlogp, dentropy):
         x, actions, arch, flat, ws = ctx.saved
         if ws is None:
-            raise L.M3LError("ActorCriticEvalFn: the forward ran without a workspace (store=False), so it has no backward")
+            raise H.no_workspace("ActorCriticEvalFn")
         B = x.shape[0]
         dv, dl, de = (None if g is None else _dev(g).reshape(B) for g in (dvalues, dlogp, dentropy))
         grads = [torch.empty_like(t) for t in flat]
@@ -221,14 +170,8 @@ class PPOStats(torch.Tensor):
 def evaluate_actions(params: HeadParams, features, actions):
     """values (B,), log_prob (B,), entropy (B,) of `actions` (B, A) under the head `params` at `features` (B, F); differentiable in the features
     and every parameter.  Under `no_grad`, or when nothing requires a gradient, no workspace is allocated and no activation is stored."""
-    for t in params.flat():
-        _require_cuda(t, "policy head parameter")
-    _require_cuda(features, "features")
-    if features.dim() != 2 or features.shape[0] < 1:
-        raise ValueError(f"features: (B, F) expected, got {tuple(features.shape)}")
-    x = features.float().contiguous()          # on the tape: the features take a gradient
-    if x.data_ptr() % 16:
-        x = x.clone()
+    H.require_params(params.flat(), "policy head parameter")
+    x = H.features_of(features, on_tape=True)          # the features take a gradient
     arch = _arch(x, params)
     a = _rows(actions.reshape(actions.shape[0], -1) if actions.dim() != 2 else actions, "actions", arch[1])
     if a.shape[0] != x.shape[0]:
@@ -242,19 +185,11 @@ def evaluate_actions(params: HeadParams, features, actions):
 def act(params: HeadParams, features, deterministic=False, noise=None):
     """actions (B, A) = mu + exp(log_std) * noise (mu when deterministic), values (B,), log_prob (B,) of those actions.  One launch, nothing kept
     for a backward.  `noise` (B, A): the standard-normal draw; made with torch.randn when not given."""
-    for t in params.flat():
-        _require_cuda(t, "policy head parameter")
-    x = _rows(features, "features")
-    F, A, pi, vf = arch = _arch(x, params)
-    B = x.shape[0]
-    if deterministic:
-        noise = None
-    elif noise is None:
-        noise = torch.randn(B, A, dtype=torch.float32, device=x.device)
-    else:
-        noise = _rows(noise, "noise", A)
-        if noise.shape[0] != B:
-            raise ValueError(f"{B} feature rows but {noise.shape[0]} noise rows")
+    H.require_params(params.flat(), "policy head parameter")
+    x = H.features_of(features, on_tape=False)
+    arch = _arch(x, params)
+    B, A = x.shape[0], arch[1]
+    noise = H.noise_of(noise, B, A, x.device, deterministic)
     flat = [_dev(t) for t in params.flat()]
     d = _desc(arch, flat)
     actions = torch.empty(B, A, dtype=torch.float32, device=x.device)
@@ -296,12 +231,8 @@ class _MlpExtractor(nn.Module):
 
     def __init__(self, features_dim, pi, vf):
         super().__init__()
-        for name, widths in (("policy_net", pi), ("value_net", vf)):
-            mods, k = [], features_dim
-            for w in widths:
-                mods += [nn.Linear(k, w), nn.Tanh()]
-                k = w
-            setattr(self, name, nn.Sequential(*mods))
+        self.policy_net = H.mlp(features_dim, pi, nn.Tanh)
+        self.value_net = H.mlp(features_dim, vf, nn.Tanh)
         self.latent_dim_pi = pi[-1] if pi else features_dim
         self.latent_dim_vf = vf[-1] if vf else features_dim
 
@@ -319,25 +250,8 @@ class ActorCriticHead(nn.Module):
             raise ValueError(f"activation_fn={getattr(activation_fn, '__name__', activation_fn)}: the HIP policy head computes Tanh only")
         self.use_sde, self.squash_output, self.share_features_extractor = bool(use_sde), bool(squash_output), bool(share_features_extractor)
         _reject_policy_flags(self)
-        if hasattr(action_dim, "n") or hasattr(action_dim, "nvec"):
-            raise ValueError(f"action_dim={action_dim!r}: discrete action spaces are not computed by the HIP policy head; pass the length of a "
-                             "continuous (Box) action vector")
-        if isinstance(action_dim, bool) or not isinstance(action_dim, numbers.Integral):
-            raise ValueError(f"action_dim={action_dim!r}: an integer expected, the length of a continuous (Box) action vector")
-        action_dim = int(action_dim)
-        if net_arch is None:
-            net_arch = dict(pi=[64, 64], vf=[64, 64])
-        if isinstance(net_arch, (list, tuple)):
-            net_arch = dict(pi=list(net_arch), vf=list(net_arch))
-        pi, vf = [int(w) for w in net_arch.get("pi", [])], [int(w) for w in net_arch.get("vf", [])]
-        for w in [int(features_dim)] + pi + vf:
-            if w < 16 or w % 16 or w > MAX_WIDTH:
-                raise ValueError(f"width {w}: features_dim and hidden widths must be multiples of 16, at most {MAX_WIDTH}")
-        if len(pi) > MAX_HIDDEN or len(vf) > MAX_HIDDEN:
-            raise ValueError(f"net_arch {net_arch}: 0 to {MAX_HIDDEN} hidden layers per branch")
-        if not 1 <= action_dim <= MAX_ACTIONS:
-            raise ValueError(f"action_dim={action_dim}: 1 to {MAX_ACTIONS}")
-        self.features_dim, self.action_dim = int(features_dim), action_dim
+        self.features_dim, self.action_dim, pi, vf = H.head_dims(features_dim, action_dim, net_arch, [64, 64], "vf", "policy", "branch", "features_dim")
+        action_dim = self.action_dim
         self.mlp_extractor = _MlpExtractor(self.features_dim, pi, vf)
         self.action_net = nn.Linear(self.mlp_extractor.latent_dim_pi, action_dim)
         self.log_std = nn.Parameter(torch.ones(action_dim) * float(log_std_init))

@@ -16,16 +16,16 @@ the critic's parameters get nothing from it.  The reference lets `actor_loss.bac
 `critic.optimizer.zero_grad()` (:347).  Everything is float32; there is no eager fallback.
 """
 import ctypes as C
-import numbers
 from typing import NamedTuple, Tuple
 
 import torch
 from torch import nn
 
+from . import _head as H
 from . import _lib as L
+from ._head import _dev, _vec
 from .dino import update_moving_average
 from .functional import _require_cuda, _stream, _ws
-from .policy import MAX_ACTIONS, MAX_HIDDEN, MAX_WIDTH, _dev, _rows, _vec
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
 WB = Tuple[torch.Tensor, torch.Tensor]
@@ -62,31 +62,17 @@ class SACHeadParams(NamedTuple):
                 raise ValueError(f"{name}: n_critics={n if n != 2 else 'other than 2'}: the HIP SAC head computes exactly 2 critics")
             if not getattr(c, "share_features_extractor", True):
                 raise ValueError("share_features_extractor=False: the HIP SAC head takes one feature vector for the actor and the critics")
-        pi = _relu_pairs(actor.latent_pi, "actor.latent_pi")
+        pi = H.linear_pairs(actor.latent_pi, "actor.latent_pi", nn.ReLU, "SAC")
         qf = tuple(_q_net(getattr(critic, f"qf{i}"), f"critic.qf{i}") for i in range(2))
         qt = tuple(_q_net(getattr(target, f"qf{i}"), f"critic_target.qf{i}") for i in range(2))
         return SACHeadParams(pi, (actor.mu.weight, actor.mu.bias), (actor.log_std.weight, actor.log_std.bias), qf, qt)
-
-
-def _relu_pairs(seq, name):
-    mods = list(seq)
-    if len(mods) % 2:
-        raise ValueError(f"{name}: Linear / ReLU pairs expected, got {len(mods)} modules")
-    out = []
-    for i in range(0, len(mods), 2):
-        if not isinstance(mods[i], nn.Linear) or mods[i].bias is None:
-            raise ValueError(f"{name}.{i}: nn.Linear with a bias expected, got {type(mods[i]).__name__}")
-        if not isinstance(mods[i + 1], nn.ReLU):
-            raise ValueError(f"{name}.{i + 1}: the HIP SAC head computes ReLU only, got {type(mods[i + 1]).__name__}")
-        out.append((mods[i].weight, mods[i].bias))
-    return tuple(out)
 
 
 def _q_net(seq, name):
     mods = list(seq)
     if not mods or not isinstance(mods[-1], nn.Linear) or mods[-1].bias is None or mods[-1].out_features != 1:
         raise ValueError(f"{name}: a net ending in nn.Linear(., 1) with a bias expected")
-    return _relu_pairs(mods[:-1], name) + ((mods[-1].weight, mods[-1].bias),)
+    return H.linear_pairs(mods[:-1], name, nn.ReLU, "SAC") + ((mods[-1].weight, mods[-1].bias),)
 
 
 def _reject_sac_flags(policy):
@@ -99,53 +85,28 @@ def _reject_sac_flags(policy):
         raise ValueError(f"n_critics={n}: the HIP SAC head computes exactly 2 critics")
 
 
-def _check_width(w, what="width"):
-    if w < 16 or w % 16 or w > MAX_WIDTH:
-        raise ValueError(f"{what} {w}: features and hidden widths must be multiples of 16, at most {MAX_WIDTH}")
-
-
 def _arch(F, params: SACHeadParams):
     """(F, A, pi widths, qf widths) with every shape checked; raises ValueError for a head outside the kernels' limits."""
     F = int(F)
     A = int(params.mu[0].shape[0])
-    for t in params.actor_flat() + params.critic_flat() + params.critic_flat(True):
-        if t.dtype != torch.float32:
-            raise ValueError(f"SAC head parameter of dtype {t.dtype}: the HIP SAC head computes in float32 and returns float32 gradients; "
-                             "keep the head's parameters in float32 whatever the encoder's compute type")
-    if len(params.pi) > MAX_HIDDEN:
-        raise ValueError(f"pi: {len(params.pi)} hidden layers (the HIP SAC head runs 0 to {MAX_HIDDEN} per net)")
-    k, pi = F, []
-    for l, (w, b) in enumerate(params.pi):
-        if w.dim() != 2 or w.shape[1] != k or tuple(b.shape) != (w.shape[0],):
-            raise ValueError(f"pi layer {l}: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not follow an input of width {k}")
-        k = int(w.shape[0])
-        pi.append(k)
-    for name, (w, b) in (("mu", params.mu), ("log_std", params.log_std)):
-        if tuple(w.shape) != (A, k) or tuple(b.shape) != (A,):
-            raise ValueError(f"{name}: weight {tuple(w.shape)} / bias {tuple(b.shape)}, expected ({A}, {k}) / ({A},)")
+    H.check_float32(params.actor_flat() + params.critic_flat() + params.critic_flat(True), "SAC")
+    k, pi = H.layer_widths(F, params.pi, "pi", "SAC", "net")
+    H.check_head_linear("mu", params.mu, A, k)
+    H.check_head_linear("log_std", params.log_std, A, k)
     qf = None
-    for name, nets in (("qf", params.qf), ("qf_target", params.qf_target)):
+    for names, nets in ((("qf0", "qf1"), params.qf), (("qf_target0", "qf_target1"), params.qf_target)):
         if len(nets) != 2:
-            raise ValueError(f"{name}: {len(nets)} critics: the HIP SAC head computes exactly 2 critics")
-        for c, net in enumerate(nets):
-            if len(net) - 1 > MAX_HIDDEN:
-                raise ValueError(f"{name}{c}: {len(net) - 1} hidden layers (the HIP SAC head runs 0 to {MAX_HIDDEN} per net)")
-            k, ws = F + A, []
-            for l, (w, b) in enumerate(net):
-                n = 1 if l == len(net) - 1 else int(w.shape[0])
-                if w.dim() != 2 or tuple(w.shape) != (n, k) or tuple(b.shape) != (n,):
-                    raise ValueError(f"{name}{c} layer {l}: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not follow an input of width {k}")
-                k = n
-                ws.append(n)
-            ws = tuple(ws[:-1])
+            raise ValueError(f"{names[0][:-1]}: {len(nets)} critics: the HIP SAC head computes exactly 2 critics")
+        for name, net in zip(names, nets):
+            k, ws = H.layer_widths(F + A, net[:-1], name, "SAC", "net")
+            for w, b in net[-1:]:          # the Linear(., 1) on top
+                if tuple(w.shape) != (1, k) or tuple(b.shape) != (1,):
+                    raise ValueError(f"{name} layer {len(net) - 1}: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not follow an input of width {k}")
             if qf is not None and ws != qf:
-                raise ValueError(f"{name}{c}: hidden widths {ws}, the other critics have {qf}: the two critics and their targets must be alike")
+                raise ValueError(f"{name}: hidden widths {ws}, the other critics have {qf}: the two critics and their targets must be alike")
             qf = ws
-    for w in (F,) + tuple(pi) + qf:
-        _check_width(w)
-    if not 1 <= A <= MAX_ACTIONS:
-        raise ValueError(f"{A} action dimensions (1 to {MAX_ACTIONS})")
-    return F, A, tuple(pi), qf
+    H.check_limits((F,) + pi + qf, A)
+    return F, A, pi, qf
 
 
 def _desc(arch, actor=None, critic=None):
@@ -195,7 +156,7 @@ class SACActorFn(torch.autograd.Function):
     def backward(ctx, dactions, dlogp):
         x, noise, arch, flat, ws = ctx.saved
         if ws is None:
-            raise L.M3LError("SACActorFn: the forward ran without a workspace (store=False), so it has no backward")
+            raise H.no_workspace("SACActorFn")
         B = x.shape[0]
         da = None if dactions is None else _dev(dactions).reshape(B, arch[1])
         dl = None if dlogp is None else _dev(dlogp).reshape(B)
@@ -227,7 +188,7 @@ class SACCriticFn(torch.autograd.Function):
     def backward(ctx, dq):
         arch, flat, ws, B, param_grads = ctx.saved
         if ws is None:
-            raise L.M3LError("SACCriticFn: the forward ran without a workspace (store=False), so it has no backward")
+            raise H.no_workspace("SACCriticFn")
         dq = _dev(dq).reshape(2, B)
         dactions = torch.empty(B, arch[1], dtype=torch.float32, device=dq.device) if ctx.needs_input_grad[1] else None
         grads = [torch.empty_like(t) for t in flat] if param_grads else None
@@ -303,32 +264,6 @@ class SACEntCoefLossFn(torch.autograd.Function):
         return g, None, None
 
 
-def _features(features, on_tape):
-    _require_cuda(features, "features")
-    if features.dim() != 2 or features.shape[0] < 1:
-        raise ValueError(f"features: (B, F) expected, got {tuple(features.shape)}")
-    if not on_tape:
-        return _dev(features)
-    x = features.float().contiguous()
-    return x.clone() if x.data_ptr() % 16 else x
-
-
-def _noise(noise, B, A, device, deterministic=False):
-    if deterministic:
-        return None
-    if noise is None:
-        return torch.randn(B, A, dtype=torch.float32, device=device)
-    noise = _rows(noise, "noise", A)
-    if noise.shape[0] != B:
-        raise ValueError(f"{B} feature rows but {noise.shape[0]} noise rows")
-    return noise
-
-
-def _require_params(flat):
-    for t in flat:
-        _require_cuda(t, "SAC head parameter")
-
-
 def _ent_args(ent_coef, log_ent_coef):
     """(float or None, device tensor or None): exactly one of the two forms."""
     if (ent_coef is None) == (log_ent_coef is None):
@@ -347,10 +282,10 @@ def action_log_prob(params: SACHeadParams, features, noise=None, deterministic=F
     """actions (B, A) = tanh(mu + exp(log_std) * noise), log_prob (B,); differentiable in the features and the actor's parameters.  Under `no_grad`,
     or when nothing requires a gradient, no workspace is allocated and nothing is stored."""
     flat = params.actor_flat()
-    _require_params(flat)
-    x = _features(features, on_tape=True)
+    H.require_params(flat, "SAC head parameter")
+    x = H.features_of(features, on_tape=True)
     arch = _arch(x.shape[1], params)
-    noise = _noise(noise, x.shape[0], arch[1], x.device, deterministic)
+    noise = H.noise_of(noise, x.shape[0], arch[1], x.device, deterministic)
     store = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in flat))
     return SACActorFn.apply(x, noise, arch, store, *flat)
 
@@ -359,8 +294,8 @@ def q_values(params: SACHeadParams, features, actions, target=False, param_grads
     """q (2, B) of both critics (the target critics with target=True) at cat([features, actions]); differentiable in the actions and, unless
     param_grads=False, the critic's parameters; the features enter detached."""
     flat = params.critic_flat(target)
-    _require_params(flat)
-    x = _features(features, on_tape=False)
+    H.require_params(flat, "SAC head parameter")
+    x = H.features_of(features, on_tape=False)
     arch = _arch(x.shape[1], params)
     _require_cuda(actions, "actions")
     if actions.dim() != 2 or actions.shape[1] != arch[1]:
@@ -380,11 +315,11 @@ def td_target(params: SACHeadParams, next_features, rewards, dones, gamma, ent_c
     """target_q (B,) = r + (1 - done) * gamma * (min_c q_target_c(x', a') - ent_coef * logp') with (a', logp') = actor(x') (`sac_mae.py:326-335`).
     One launch, no tape."""
     af, cf = params.actor_flat(), params.critic_flat(True)
-    _require_params(af + cf)
-    x = _features(next_features, on_tape=False)
+    H.require_params(af + cf, "SAC head parameter")
+    x = H.features_of(next_features, on_tape=False)
     arch = _arch(x.shape[1], params)
     B = x.shape[0]
-    noise = _noise(noise, B, arch[1], x.device)
+    noise = H.noise_of(noise, B, arch[1], x.device)
     ent, log_ent = _ent_args(ent_coef, log_ent_coef)
     r, dn = _vec(rewards, "rewards", B), _vec(dones, "dones", B)
     af, cf = [_dev(t) for t in af], [_dev(t) for t in cf]
@@ -426,11 +361,8 @@ def ent_coef_loss(log_ent_coef, log_prob, target_entropy):
 class _Actor(nn.Module):
     def __init__(self, features_dim, pi, action_dim):
         super().__init__()
-        mods, k = [], features_dim
-        for w in pi:
-            mods += [nn.Linear(k, w), nn.ReLU()]
-            k = w
-        self.latent_pi = nn.Sequential(*mods)
+        self.latent_pi = H.mlp(features_dim, pi, nn.ReLU)
+        k = pi[-1] if pi else features_dim
         self.mu = nn.Linear(k, action_dim)
         self.log_std = nn.Linear(k, action_dim)
         self.use_sde = False
@@ -441,12 +373,7 @@ class _Critic(nn.Module):
         super().__init__()
         self.n_critics, self.share_features_extractor = 2, True
         for i in range(2):
-            mods, k = [], features_dim + action_dim
-            for w in qf:
-                mods += [nn.Linear(k, w), nn.ReLU()]
-                k = w
-            mods.append(nn.Linear(k, 1))
-            setattr(self, f"qf{i}", nn.Sequential(*mods))
+            setattr(self, f"qf{i}", H.mlp(features_dim + action_dim, qf, nn.ReLU, out=1))
 
 
 class SACHead(nn.Module):
@@ -461,24 +388,8 @@ class SACHead(nn.Module):
             raise ValueError(f"activation_fn={getattr(activation_fn, '__name__', activation_fn)}: the HIP SAC head computes ReLU only")
         self.use_sde, self.share_features_extractor, self.n_critics = bool(use_sde), bool(share_features_extractor), n_critics
         _reject_sac_flags(self)
-        if hasattr(action_dim, "n") or hasattr(action_dim, "nvec"):
-            raise ValueError(f"action_dim={action_dim!r}: discrete action spaces are not computed by the HIP SAC head; pass the length of a "
-                             "continuous (Box) action vector")
-        if isinstance(action_dim, bool) or not isinstance(action_dim, numbers.Integral):
-            raise ValueError(f"action_dim={action_dim!r}: an integer expected, the length of a continuous (Box) action vector")
-        action_dim = int(action_dim)
-        if net_arch is None:
-            net_arch = dict(pi=[256, 256], qf=[256, 256])
-        if isinstance(net_arch, (list, tuple)):
-            net_arch = dict(pi=list(net_arch), qf=list(net_arch))
-        pi, qf = [int(w) for w in net_arch.get("pi", [])], [int(w) for w in net_arch.get("qf", [])]
-        for w in [int(features_dim)] + pi + qf:
-            _check_width(w)
-        if len(pi) > MAX_HIDDEN or len(qf) > MAX_HIDDEN:
-            raise ValueError(f"net_arch {net_arch}: 0 to {MAX_HIDDEN} hidden layers per net")
-        if not 1 <= action_dim <= MAX_ACTIONS:
-            raise ValueError(f"action_dim={action_dim}: 1 to {MAX_ACTIONS}")
-        self.features_dim, self.action_dim = int(features_dim), action_dim
+        self.features_dim, self.action_dim, pi, qf = H.head_dims(features_dim, action_dim, net_arch, [256, 256], "qf", "SAC", "net")
+        action_dim = self.action_dim
         self.actor = _Actor(self.features_dim, pi, action_dim)
         self.critic = _Critic(self.features_dim, qf, action_dim)
         self.critic_target = _Critic(self.features_dim, qf, action_dim)

@@ -29,6 +29,8 @@ ARCHS = {
     "mixed": (32, (32,), (64, 48, 16), 1),
     "nopi": (48, (), (16,), 2),
     "golden": (32, (32, 32), (32, 32), 3),
+    "novf": (16, (16,), (), 1),
+    "plain": (16, (), (), 2),
 }
 # flag combinations of the loss: name -> (clip_range_vf, normalize_advantage)
 FLAGS = {"default": (None, True), "vfclip": (CLIP_RANGE_VF, True), "nonorm": (None, False)}
@@ -53,6 +55,10 @@ GPU_CASES = {
     "nopi_b3": ("nopi", 3, "default", False),
     "nopi_b63": ("nopi", 63, "vfclip", True),
     "nopi_b130": ("nopi", 130, "nonorm", True),
+    "novf_b3": ("novf", 3, "default", False),
+    "novf_b17": ("novf", 17, "vfclip", True),
+    "plain_b2": ("plain", 2, "vfclip", False),
+    "plain_b33": ("plain", 33, "default", True),
 }
 
 

@@ -259,10 +259,11 @@ def test_recorded_flag_combinations_are_the_ones_asked_for():
 def test_case_grid_covers_the_tiling_edges():
     Bs = {PC.GPU_CASES[n][1] for n in PC.GPU_CASES}
     assert Bs == {1, 2, 3, 15, 17, 33, 63, 65, 130}
-    assert {PC.GPU_CASES[n][0] for n in PC.GPU_CASES} == {"a64", "a256", "mixed", "nopi"}
+    assert {PC.GPU_CASES[n][0] for n in PC.GPU_CASES} == {"a64", "a256", "mixed", "nopi", "novf", "plain"}
     assert PC.ARCHS["a64"] == (64, (64, 64), (64, 64), 3) and PC.ARCHS["a256"] == (256, (256, 256), (256, 256), 7)
     assert PC.ARCHS["mixed"] == (32, (32,), (64, 48, 16), 1) and PC.ARCHS["nopi"] == (48, (), (16,), 2)
-    for arch in ("a64", "a256", "mixed", "nopi"):
+    assert PC.ARCHS["novf"] == (16, (16,), (), 1) and PC.ARCHS["plain"] == (16, (), (), 2)
+    for arch in ("a64", "a256", "mixed", "nopi", "novf", "plain"):
         assert {PC.GPU_CASES[n][2] for n in PC.GPU_CASES if PC.GPU_CASES[n][0] == arch} >= {"default", "vfclip"}
 
 
