@@ -809,6 +809,30 @@ int m3l_replay_gather_rows(const float* actions, const float* rewards, const flo
                            const int64_t* rows, long row_shift, int B, float reward_scale, float reward_clip, float* actions_out,
                            float* rewards_out, float* dones_out, int64_t* rows_out, void* stream);
 
+/* ---- frame-deduplicated replay store (ABI 413): the reference's FrameStack wrapper (utils/frame_stack.py:76-105) makes every observation the
+ * last fs frames of its episode, so a stacked store holds each frame fs times per store.  Here each frame lies in the ring once:
+ *   image_frames (T, n_envs, H, W, 3), tactile_frames (T, n_envs, 3 S, h, w)   slot t: the newest frame of step t's observation, obs[:, -1]
+ *   *_next_frames, same shapes, or NULL                                         slot t: the newest frame of step t's next observation;
+ *                                                                               NULL: that frame lies in *_frames at slot (t + 1) % T
+ *   ages (T, n_envs) int32   how many earlier frames of the same episode the stack of step (t, e) reaches, 0 .. fs - 1 (0 at an episode's
+ *                            first step, whose stack is fs copies of the reset frame)
+ * m3l_replay_gather_load_frames is m3l_replay_gather_load on such stores: the same rows / row_shift / B, ranges, outputs and arithmetic, both
+ * LoadedObs dicts in one launch.  With a = ages[t, e]:
+ *   observation frame j (fs - 1 the newest)   = frames[(t - min(fs - 1 - j, a)) mod T, e]
+ *   next-observation frame j < fs - 1         = observation frame j + 1
+ *   next-observation frame fs - 1             = next_frames[t, e], or frames[(t + 1) mod T, e]
+ * A lane takes one 4-pixel / 4-element piece of one of the fs + 1 source frames, loads and normalises it once and writes it to both outputs it
+ * belongs to: fs + 1 frame reads for 2 fs frame writes.  Every offset is 64-bit; the 16-byte paths and the element-wise form are those above.
+ * Which steps still have their history in the ring is the caller's job (DeviceReplayBuffer: not the fs - 1 oldest of a full ring).
+ * Safety: a row outside [0, T n_envs) is never read and gives NaN in both halves; an age outside [0, fs - 1] is clamped and every source step
+ * is taken modulo T, so no value of ages causes a read outside a store.
+ * Errors, nothing written: those of m3l_replay_gather_load, and ages NULL. */
+int m3l_replay_gather_load_frames(const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
+                                  double img_hi, float* image, float* image_next, const void* tactile_frames, const void* tactile_next_frames,
+                                  int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out,
+                                  float* const* tactile_next_out, const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* rows,
+                                  long row_shift, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

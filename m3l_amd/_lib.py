@@ -226,6 +226,8 @@ _SIGS = {
     "m3l_replay_gather_load": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double,
                                      c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_i, c_p]),
     "m3l_replay_gather_rows": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_i, C.c_float, C.c_float, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_replay_gather_load_frames": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double,
+                                            C.c_double, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_i, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

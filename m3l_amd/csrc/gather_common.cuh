@@ -46,31 +46,80 @@ __device__ __forceinline__ f32x4 load4(const uint8_t* __restrict__ p) {
     return f32x4{(float)a.x, (float)a.y, (float)a.z, (float)a.w};
 }
 
+// The pieces below address a store by frame: frame index `frame` of a store of (H, W, 3) image frames or (3 S, h, w) tactile frames, whatever the
+// axes in front of it (the stacked callers pass row * fs + f; the replay ring's frame store passes slot * n_envs + e).  A frame < 0 is not read:
+// the piece is NaN.  The outputs are addressed by plane group: group b * fs + f is the three planes of frame f of sample b.
+
+// 4 pixels q < HW / 4 of an image frame, normalised
+template <typename TI>
+__device__ __forceinline__ void image_load4(const GatherGeom& g, const void* img, long frame, int q, float (&v)[12]) {
+    if (frame >= 0) {
+        load12((const TI*)img + frame * (3L * g.HW) + 12L * q, v);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) v[k] = vt_norm(v[k], g.img_lo, g.img_span);
+    } else {
+        const float nan = __int_as_float(0x7fc00000);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) v[k] = nan;
+    }
+}
+__device__ __forceinline__ void image_store4(const GatherGeom& g, float* img_out, long group, int q, const float (&v)[12]) {
+    float* __restrict__ o = img_out + group * (3L * g.HW) + 4L * q;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *(f32x4*)(o + (long)c * g.HW) = f32x4{v[c], v[3 + c], v[6 + c], v[9 + c]};
+}
+// the element-per-lane form: pixel p < HW
+template <typename TI>
+__device__ __forceinline__ void image_load1(const GatherGeom& g, const void* img, long frame, int p, float (&v)[3]) {
+    const TI* __restrict__ s = (const TI*)img + frame * (3L * g.HW) + 3L * p;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = frame >= 0 ? vt_norm((float)s[c], g.img_lo, g.img_span) : __int_as_float(0x7fc00000);
+}
+__device__ __forceinline__ void image_store1(const GatherGeom& g, float* img_out, long group, int p, const float (&v)[3]) {
+    float* __restrict__ o = img_out + group * (3L * g.HW) + p;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[(long)c * g.HW] = v[c];
+}
+
+// 4 elements q < 3 hw / 4 of the three channels of sensor s in a tactile frame, normalised; and the element-per-lane form, q < 3 hw
+template <typename TI>
+__device__ __forceinline__ f32x4 tactile_load4(const GatherGeom& g, const void* tac, long frame, int s, int q) {
+    const float nan = __int_as_float(0x7fc00000);
+    f32x4 v = f32x4{nan, nan, nan, nan};
+    if (frame >= 0) {
+        v = load4((const TI*)tac + (frame * g.S + s) * (3L * g.hw) + 4L * q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = vt_norm(v[k], g.tac_lo, g.tac_span);
+    }
+    return v;
+}
+template <typename TI>
+__device__ __forceinline__ float tactile_load1(const GatherGeom& g, const void* tac, long frame, int s, int q) {
+    const TI* __restrict__ src = (const TI*)tac + (frame * g.S + s) * (3L * g.hw);
+    return frame >= 0 ? vt_norm((float)src[q], g.tac_lo, g.tac_span) : __int_as_float(0x7fc00000);
+}
+// output of sensor s, picked with selects (an indexed read of the array would be an alloca)
+__device__ __forceinline__ float* tactile_sensor(float* const (&tac_out)[M3L_MAX_SENSORS], int s) {
+    float* o = tac_out[0];
+#pragma unroll
+    for (int k = 1; k < M3L_MAX_SENSORS; ++k) o = (s == k) ? tac_out[k] : o;
+    return o;
+}
+
 // item r < img_per_sample of output sample b: store row `row` of img (n_rows, fs, H, W, 3) -> img_out (B, 3 fs, H, W)
 template <typename TI>
 __device__ __forceinline__ void gather_image_item(const GatherGeom& g, const void* img, float* img_out, long row, int b, int r) {
-    const long frame = 3L * g.HW;
-    const float nan = __int_as_float(0x7fc00000);
+    const int per_frame = g.img_vec ? g.HW / 4 : g.HW;
+    const int f = r / per_frame, q = r % per_frame;
+    const long frame = row >= 0 ? row * g.fs + f : -1;
     if (g.img_vec) {
-        const int n4 = g.HW / 4, f = r / n4, q = r % n4;
         float v[12];
-        if (row >= 0) {
-            load12((const TI*)img + (row * g.fs + f) * frame + 12L * q, v);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) v[k] = vt_norm(v[k], g.img_lo, g.img_span);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) v[k] = nan;
-        }
-        float* __restrict__ o = img_out + ((long)b * g.fs + f) * frame + 4L * q;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(f32x4*)(o + (long)c * g.HW) = f32x4{v[c], v[3 + c], v[6 + c], v[9 + c]};
+        image_load4<TI>(g, img, frame, q, v);
+        image_store4(g, img_out, (long)b * g.fs + f, q, v);
     } else {
-        const int f = r / g.HW, p = r % g.HW;
-        const TI* __restrict__ s = (const TI*)img + (row * g.fs + f) * frame + 3L * p;
-        float* __restrict__ o = img_out + ((long)b * g.fs + f) * frame + p;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[(long)c * g.HW] = row >= 0 ? vt_norm((float)s[c], g.img_lo, g.img_span) : nan;
+        float v[3];
+        image_load1<TI>(g, img, frame, q, v);
+        image_store1(g, img_out, (long)b * g.fs + f, q, v);
     }
 }
 
@@ -81,23 +130,12 @@ __device__ __forceinline__ void gather_tactile_item(const GatherGeom& g, const v
     const long seg = 3L * g.hw;                                   // the three channels of one sensor in one frame
     const int per_seg = g.tac_vec ? (int)(seg / 4) : (int)seg;
     const int f = r / (g.S * per_seg), s = (r / per_seg) % g.S, q = r % per_seg;
-    float* o = tac_out[0];
-#pragma unroll
-    for (int k = 1; k < M3L_MAX_SENSORS; ++k) o = (s == k) ? tac_out[k] : o;
-    const float nan = __int_as_float(0x7fc00000);
-    const TI* __restrict__ src = (const TI*)tac + ((row * g.fs + f) * g.S + s) * seg;
-    o += ((long)b * g.fs + f) * seg;
-    if (g.tac_vec) {
-        f32x4 v = f32x4{nan, nan, nan, nan};
-        if (row >= 0) {
-            v = load4(src + 4L * q);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = vt_norm(v[k], g.tac_lo, g.tac_span);
-        }
-        *(f32x4*)(o + 4L * q) = v;
-    } else {
-        o[q] = row >= 0 ? vt_norm((float)src[q], g.tac_lo, g.tac_span) : nan;
-    }
+    const long frame = row >= 0 ? row * g.fs + f : -1;
+    float* o = tactile_sensor(tac_out, s) + ((long)b * g.fs + f) * seg;
+    if (g.tac_vec)
+        *(f32x4*)(o + 4L * q) = tactile_load4<TI>(g, tac, frame, s, q);
+    else
+        o[q] = tactile_load1<TI>(g, tac, frame, s, q);
 }
 
 inline bool gather_aligned(const void* p, size_t n) { return ((uintptr_t)p % n) == 0; }
@@ -115,7 +153,8 @@ inline int gather_image_geom(GatherGeom& g, const char* who, const void* image_s
     g.img_vec = g.HW % 4 == 0 && gather_aligned(image_store, image_u8 ? 4 : 16) && gather_aligned(image, 16);
     return 0;
 }
-inline long gather_image_items(const GatherGeom& g) { return (long)g.fs * (g.img_vec ? g.HW / 4 : g.HW); }
+inline long gather_image_pieces(const GatherGeom& g) { return g.img_vec ? g.HW / 4 : g.HW; }      // lanes of work of one frame
+inline long gather_image_items(const GatherGeom& g) { return (long)g.fs * gather_image_pieces(g); }
 
 inline int gather_tactile_geom(GatherGeom& g, const char* who, const void* tactile_store, int tactile_u8, int th, int tw, int n_sensors, double lo,
                                double hi, float* const* tactile_out, float* (&out)[M3L_MAX_SENSORS]) {
@@ -133,6 +172,7 @@ inline int gather_tactile_geom(GatherGeom& g, const char* who, const void* tacti
     }
     return 0;
 }
-inline long gather_tactile_items(const GatherGeom& g) { return (long)g.fs * g.S * (g.tac_vec ? 3 * g.hw / 4 : 3 * g.hw); }
+inline long gather_tactile_pieces(const GatherGeom& g) { return (long)g.S * (g.tac_vec ? 3 * g.hw / 4 : 3 * g.hw); }
+inline long gather_tactile_items(const GatherGeom& g) { return (long)g.fs * gather_tactile_pieces(g); }
 
 }  // namespace

@@ -10,6 +10,10 @@
 // gather_load is HBM-bound with no reuse: one read and one write of 2 B rows.  The per-lane work is that of the rollout's gather
 // (gather_common.cuh).  The grid is four runs of blocks — image, tactile, next image, next tactile — so which half a block serves is uniform
 // over the block and its pointers are picked with scalar selects.
+//
+// gather_load_frames is the same on the frame-deduplicated store ("frame-deduplicated replay store" in the header): a lane takes one piece of one
+// of the fs + 1 frames a sample is made of, loads and normalises it once and writes it to both stacks it lies in.  fs + 1 frame reads for 2 fs
+// frame writes; two runs of blocks, image and tactile.
 #include <math.h>
 #include <string.h>
 
@@ -81,6 +85,111 @@ __global__ void __launch_bounds__(256) replay_gather_load_kernel(ReplayLoadArgs 
             tactile_item(a.g, src, a.tac_out[1], row, b, r);
         else
             tactile_item(a.g, src, a.tac_out[0], row, b, r);
+    }
+}
+
+// ---- the frame-deduplicated store: every frame lies in the ring once, (T, n_envs, ...) without the fs axis, and a sample's two stacks are put
+// together from fs + 1 of them.  ages[t, e] says how many earlier frames of the same episode the stack of step (t, e) reaches.
+struct ReplayFramesArgs {
+    const void* img;                         // (T, n_envs, H, W, 3) or NULL: slot t holds the newest frame of step t's observation
+    const void* img_next;                    // the same shape: the newest frame of step t's next observation; NULL: that is img one step later
+    const void* tac;                         // (T, n_envs, 3 S, h, w) or NULL
+    const void* tac_next;
+    float* img_out[2];                       // (B, 3 fs, H, W): observations, next observations
+    float* tac_out[2][M3L_MAX_SENSORS];      // (B, 3 fs, h, w) each
+    const int64_t* rows;                     // (B), t * n_envs + e
+    const int32_t* ages;                     // (T, n_envs)
+    long n_rows, shift;
+    int T, n_envs;
+    GatherGeom g;                            // *_per_sample count fs + 1 source frames
+    int img_blocks;                          // blocks [0, img_blocks) do the image, the rest the tactile frames
+    long img_items, tac_items;
+};
+
+// frame slot * n_envs + e that source k of store row `row` reads, or -1 for a row that is not read.  Source k < fs is observation frame k
+// (fs - 1 the newest): min(fs - 1 - k, age) steps back in the ring; source fs is the next observation's newest frame: the same row of the
+// second store (`second`), or one step later in the ring.  The age is clamped and every step taken modulo T: no value of ages leaves the store.
+__device__ __forceinline__ long replay_frame(const int32_t* __restrict__ ages, long row, int k, int fs, int T, int n_envs, bool second) {
+    if (row < 0) return -1;
+    if (second) return row;
+    long t = row / n_envs;
+    const long e = row % n_envs;
+    if (k == fs) {
+        t = t + 1 == T ? 0 : t + 1;
+    } else {
+        const int age = min(max(ages[row], 0), fs - 1);
+        t = (t - min(fs - 1 - k, age)) % T;
+        if (t < 0) t += T;
+    }
+    return t * n_envs + e;
+}
+
+// one piece of one source frame, loaded and normalised once: observation plane group k (k < fs) and next-observation plane group k - 1 (k >= 1)
+template <typename TI>
+__device__ __forceinline__ void frames_image_piece(const GatherGeom& g, const void* src, long frame, float* out, float* out_next, int b, int k,
+                                                   int q) {
+    const long group = (long)b * g.fs + k;
+    if (g.img_vec) {
+        float v[12];
+        image_load4<TI>(g, src, frame, q, v);
+        if (k < g.fs) image_store4(g, out, group, q, v);
+        if (k >= 1) image_store4(g, out_next, group - 1, q, v);
+    } else {
+        float v[3];
+        image_load1<TI>(g, src, frame, q, v);
+        if (k < g.fs) image_store1(g, out, group, q, v);
+        if (k >= 1) image_store1(g, out_next, group - 1, q, v);
+    }
+}
+
+template <typename TI>
+__device__ __forceinline__ void frames_tactile_piece(const GatherGeom& g, const void* src, long frame, float* out, float* out_next, int b, int k,
+                                                     int s, int q) {
+    const long seg = 3L * g.hw, group = (long)b * g.fs + k;
+    if (g.tac_vec) {
+        const f32x4 v = tactile_load4<TI>(g, src, frame, s, q);
+        if (k < g.fs) *(f32x4*)(out + group * seg + 4L * q) = v;
+        if (k >= 1) *(f32x4*)(out_next + (group - 1) * seg + 4L * q) = v;
+    } else {
+        const float v = tactile_load1<TI>(g, src, frame, s, q);
+        if (k < g.fs) out[group * seg + q] = v;
+        if (k >= 1) out_next[(group - 1) * seg + q] = v;
+    }
+}
+
+__global__ void __launch_bounds__(256) replay_gather_load_frames_kernel(ReplayFramesArgs a) {
+    const int fs = a.g.fs;
+    if ((int)blockIdx.x < a.img_blocks) {                               // uniform over the block
+        const long i = (long)blockIdx.x * 256 + threadIdx.x;
+        if (i >= a.img_items) return;
+        const int per_frame = a.g.img_vec ? a.g.HW / 4 : a.g.HW;
+        const int b = (int)(i / a.g.img_per_sample), r = (int)(i % a.g.img_per_sample);
+        const int k = r / per_frame, q = r % per_frame;
+        const bool second = k == fs && a.img_next;
+        const long row = replay_row(a.rows, b, a.n_rows, a.shift, a.T, a.n_envs, 0);
+        const long frame = replay_frame(a.ages, row, k, fs, a.T, a.n_envs, second);
+        const void* src = second ? a.img_next : a.img;
+        if (a.g.img_u8)
+            frames_image_piece<uint8_t>(a.g, src, frame, a.img_out[0], a.img_out[1], b, k, q);
+        else
+            frames_image_piece<float>(a.g, src, frame, a.img_out[0], a.img_out[1], b, k, q);
+    } else {
+        const long i = (long)((int)blockIdx.x - a.img_blocks) * 256 + threadIdx.x;
+        if (i >= a.tac_items) return;
+        const int per_seg = a.g.tac_vec ? 3 * a.g.hw / 4 : 3 * a.g.hw;
+        const int b = (int)(i / a.g.tac_per_sample), r = (int)(i % a.g.tac_per_sample);
+        const int k = r / (a.g.S * per_seg), s = (r / per_seg) % a.g.S, q = r % per_seg;
+        const bool second = k == fs && a.tac_next;
+        const long row = replay_row(a.rows, b, a.n_rows, a.shift, a.T, a.n_envs, 0);
+        const long frame = replay_frame(a.ages, row, k, fs, a.T, a.n_envs, second);
+        const void* src = second ? a.tac_next : a.tac;
+        // both outputs of sensor s picked with selects from the argument block (see the comment in replay_gather_load_kernel)
+        float* out = tactile_sensor(a.tac_out[0], s);
+        float* out_next = tactile_sensor(a.tac_out[1], s);
+        if (a.g.tac_u8)
+            frames_tactile_piece<uint8_t>(a.g, src, frame, out, out_next, b, k, s, q);
+        else
+            frames_tactile_piece<float>(a.g, src, frame, out, out_next, b, k, s, q);
     }
 }
 
@@ -161,6 +270,53 @@ int m3l_replay_gather_load(const void* image_store, const void* image_next_store
     M3L_CHECK(2 * (img_blocks + tac_blocks) <= INT32_MAX, "replay_gather_load: B=%d too large", B);
     a.img_blocks = (int)img_blocks, a.half_blocks = (int)(img_blocks + tac_blocks);
     replay_gather_load_kernel<<<(unsigned)(2 * a.half_blocks), 256, 0, (hipStream_t)stream>>>(a);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_replay_gather_load_frames(const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
+                                  double img_hi, float* image, float* image_next, const void* tactile_frames, const void* tactile_next_frames,
+                                  int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out,
+                                  float* const* tactile_next_out, const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* rows,
+                                  long row_shift, int B, void* stream) {
+    const char* who = "replay_gather_load_frames";
+    M3L_CHECK(image_frames || tactile_frames, "%s: neither an image nor a tactile frame store", who);
+    M3L_CHECK((image_frames || !image_next_frames) && (tactile_frames || !tactile_next_frames), "%s: a next store without its store", who);
+    M3L_CHECK(T >= 1 && n_envs >= 1 && frame_stack >= 1 && B >= 1 && rows, "%s: T=%d n_envs=%d frame_stack=%d B=%d", who, T, n_envs, frame_stack,
+              B);
+    M3L_CHECK(ages, "%s: ages is NULL", who);
+    M3L_CHECK(row_shift >= 0 && row_shift < (long)T * n_envs, "%s: row_shift=%ld outside [0, %ld)", who, row_shift, (long)T * n_envs);
+    ReplayFramesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rows = rows, a.ages = ages;
+    a.n_rows = (long)T * n_envs, a.shift = row_shift;
+    a.T = T, a.n_envs = n_envs, a.g.fs = frame_stack;
+    long img_per = 0, tac_per = 0;
+    if (image_frames) {
+        if (gather_image_geom(a.g, who, image_frames, image_u8, H, W, img_lo, img_hi, image)) return 1;
+        M3L_CHECK(image_next, "%s: the next-observation image output is NULL", who);
+        a.img = image_frames, a.img_next = image_next_frames, a.img_out[0] = image, a.img_out[1] = image_next;
+        a.g.img_vec = a.g.img_vec && gather_aligned(image_next, 16) && (!image_next_frames || gather_aligned(image_next_frames, image_u8 ? 4 : 16));
+        img_per = (frame_stack + 1L) * gather_image_pieces(a.g);
+    }
+    if (tactile_frames) {
+        if (gather_tactile_geom(a.g, who, tactile_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, a.tac_out[0])) return 1;
+        const int vec = a.g.tac_vec;
+        M3L_CHECK(tactile_next_out, "%s: the next-observation tactile outputs are NULL", who);
+        if (gather_tactile_geom(a.g, who, tactile_next_frames ? tactile_next_frames : tactile_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi,
+                                tactile_next_out, a.tac_out[1]))
+            return 1;
+        a.g.tac_vec = a.g.tac_vec && vec;
+        a.tac = tactile_frames, a.tac_next = tactile_next_frames;
+        tac_per = (frame_stack + 1L) * gather_tactile_pieces(a.g);
+    }
+    M3L_CHECK(img_per <= INT32_MAX && tac_per <= INT32_MAX, "%s: sample too large", who);
+    a.g.img_per_sample = (int)img_per, a.g.tac_per_sample = (int)tac_per;
+    a.img_items = img_per * B, a.tac_items = tac_per * B;
+    const long img_blocks = (a.img_items + 255) / 256, tac_blocks = (a.tac_items + 255) / 256;
+    M3L_CHECK(img_blocks + tac_blocks <= INT32_MAX, "%s: B=%d too large", who, B);
+    a.img_blocks = (int)img_blocks;
+    replay_gather_load_frames_kernel<<<(unsigned)(img_blocks + tac_blocks), 256, 0, (hipStream_t)stream>>>(a);
     M3L_LAUNCH_CHECK();
     return 0;
 }

@@ -15,7 +15,13 @@ seam (what `get(indices=...)` is for the rollout).  A sample is three launches: 
 
 SB3 is not in the reference tree: the ring (`add`, `pos`, `full`), the single-store mode (`optimize_memory_usage`), the timeout mask and
 `VecNormalize.normalize_reward` are restated here and in tests/replay_cases.py (parity unpinned).  Not covered: `save_replay_buffer` pickling,
-n-step returns, HER, prioritised sampling, a frame-deduplicated store, observation normalisation (`norm_obs`).
+n-step returns, HER, prioritised sampling, observation normalisation (`norm_obs`).
+
+`frame_dedup=True` stores every frame once.  The reference's `FrameStack` wrapper (utils/frame_stack.py:76-105) makes each observation the last
+`fs` frames of its episode, so the stacked stores hold one frame `fs` times each; the deduplicated stores `frames` / `next_frames` hold the
+newest frame of each observation, `ages` says how far back a step's stack reaches into its episode, and `gather_load_frames` puts both stacks of
+a sample together from fs + 1 frames (m3l_replay_gather_load_frames).  At the reference's shapes 10^6 transitions take 73.8 GB instead of
+295 GB.  The wrapper and the vec-env's auto-reset are restated in tests/replay_frame_cases.py (parity unpinned).
 """
 import math
 from typing import NamedTuple
@@ -62,6 +68,45 @@ def gather_load(image_store, tactile_store, rows, image_next_store=None, tactile
         int(tactile_store is not None and tactile_store.dtype == torch.uint8), th, tw, S, float(tactile_normalization[0]),
         float(tactile_normalization[1]), L.ptr_array(tacs), L.ptr_array(tacs_next), T, n_envs, fs, L.ptr(rows), int(row_shift), B, _stream()),
         "m3l_replay_gather_load")
+    return _as_loaded(img, tacs), _as_loaded(img_next, tacs_next)
+
+
+def gather_load_frames(image_frames, tactile_frames, ages, rows, image_next_frames=None, tactile_next_frames=None, image_normalization=(0, 1),
+                       tactile_normalization=(-1, 1), row_shift=0, *, frame_stack):
+    """`gather_load` on frame-deduplicated stores: image_frames (T, n_envs, H, W, 3) and / or tactile_frames (T, n_envs, 3*S, h, w), uint8 or
+    float32 CUDA tensors whose slot t holds the newest frame of step t's observation, ages (T, n_envs) int32 — how many earlier frames of the
+    same episode the stack of a step reaches, clamped by the kernel to [0, frame_stack - 1] — and rows (B) int64 -> (observations,
+    next_observations) as `gather_load` returns them, in one launch (m3l_replay_gather_load_frames).  Observation frame j is the frame of step
+    t - min(frame_stack - 1 - j, age) in the ring; the next observation is frames 1.. of that and the frame of `*_next_frames` at the same row,
+    or without one of the store itself at step (t + 1) % T."""
+    who = "replay.gather_load_frames"
+    ref = image_frames if image_frames is not None else tactile_frames
+    if ref is None:
+        raise ValueError(who + ": neither an image nor a tactile frame store")
+    pairs = (("image", image_frames, image_next_frames), ("tactile", tactile_frames, tactile_next_frames))
+    for name, t, nxt in pairs:
+        for what, x in ((name + "_frames", t), (name + "_next_frames", nxt)):
+            if x is not None:
+                _require_cuda(x, f"{who}: {what}")
+        if nxt is not None and (t is None or nxt.shape != t.shape or nxt.dtype != t.dtype or not nxt.is_contiguous()):
+            raise ValueError(f"{who}: {name}_next_frames must be a contiguous tensor of {name}_frames' shape and dtype")
+    _check_rows(who, rows)
+    fs = int(frame_stack)
+    if fs < 1:
+        raise ValueError(f"{who}: frame_stack={frame_stack}")
+    T, n_envs, H, W, th, tw, S = _check_stores(who, image_frames, tactile_frames, frames=True)
+    _require_cuda(ages, who + ": ages")
+    if ages.dtype != torch.int32 or tuple(ages.shape) != (T, n_envs) or not ages.is_contiguous():
+        raise ValueError(f"{who}: ages must be a contiguous int32 tensor of shape (T, n_envs) = {(T, n_envs)}")
+    B = rows.shape[0]
+    img, tacs = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
+    img_next, tacs_next = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
+    L.check(L.lib().m3l_replay_gather_load_frames(
+        L.ptr(image_frames), L.ptr(image_next_frames), int(image_frames is not None and image_frames.dtype == torch.uint8), H, W,
+        float(image_normalization[0]), float(image_normalization[1]), L.ptr(img), L.ptr(img_next), L.ptr(tactile_frames),
+        L.ptr(tactile_next_frames), int(tactile_frames is not None and tactile_frames.dtype == torch.uint8), th, tw, S,
+        float(tactile_normalization[0]), float(tactile_normalization[1]), L.ptr_array(tacs), L.ptr_array(tacs_next), L.ptr(ages), T, n_envs, fs,
+        L.ptr(rows), int(row_shift), B, _stream()), "m3l_replay_gather_load_frames")
     return _as_loaded(img, tacs), _as_loaded(img_next, tacs_next)
 
 
@@ -124,10 +169,19 @@ class DeviceReplayBuffer:
     obs_shapes   {'image': (fs, H, W, 3), 'tactile': (fs, 3*S, h, w)}: the per-environment observation shapes of the vec-env, either key optional
     obs_dtypes   {'image': uint8 | float32, 'tactile': ...} (numpy or torch dtypes)
     The stores are allocated by the first add(), which first compares `store_bytes()` with the free memory of the device.
+
+    frame_dedup     store every frame once: `frames` / `next_frames` {'image': (T, n_envs, H, W, 3), 'tactile': (T, n_envs, 3*S, h, w)} and `ages`
+                    (T, n_envs) int32 stand where `observations` / `next_observations` stand without it.  add() keeps its signature and copies
+                    only the newest frame of each stacked observation.  The contract: the observations are the rolling stacks of the reference's
+                    FrameStack wrapper — next_obs[:, :-1] == obs[:, 1:], a constant stack at the first add() and after a `done`, otherwise obs
+                    equal to the previous next_obs.  A full ring does not sample its frame_stack - 1 oldest steps, whose history the newest
+                    steps overwrote (SB3 would sample them).  The capacity in steps must be at least frame_stack + 1.
+    check_stacking  with frame_dedup: every add() verifies that contract with torch ops on the device and one read-back — it synchronises: for
+                    tests and a first run — and raises ValueError naming the key, the environment and the rule.
     """
 
     def __init__(self, buffer_size, n_envs, obs_shapes, obs_dtypes, action_dim, optimize_memory_usage=False, handle_timeout_termination=True,
-                 image_normalization=[0, 1], tactile_normalization=[-1, 1], device="cuda"):
+                 image_normalization=[0, 1], tactile_normalization=[-1, 1], device="cuda", frame_dedup=False, check_stacking=False):
         self.device = _require_device("DeviceReplayBuffer", device, "replay buffer", "DictReplayBuffer")
         self.n_envs, self.action_dim = int(n_envs), int(action_dim)
         if int(buffer_size) < 1 or self.n_envs < 1 or self.action_dim < 1:
@@ -140,30 +194,51 @@ class DeviceReplayBuffer:
             raise ValueError("DeviceReplayBuffer: optimize_memory_usage=True needs handle_timeout_termination=False (the single store loses the "
                              "true next observation of a truncated step)")
         self.image_normalization, self.tactile_normalization = list(image_normalization), list(tactile_normalization)
+        self.frame_dedup, self.check_stacking = bool(frame_dedup), bool(check_stacking)
+        if self.check_stacking and not self.frame_dedup:
+            raise ValueError("DeviceReplayBuffer: check_stacking=True checks the contract of frame_dedup=True and needs it")
+        if self.frame_dedup and self.buffer_size < self.frame_stack + 1:
+            raise ValueError(f"DeviceReplayBuffer: frame_dedup=True with frame_stack={self.frame_stack} needs a capacity of at least "
+                             f"{self.frame_stack + 1} steps (buffer_size // n_envs is {self.buffer_size})")
         self.observations = self.next_observations = None
+        self.frames = self.next_frames = self.ages = None
         self.reset()
 
     # ---- memory
-    def store_bytes(self):
-        """Bytes of the stores, before or after allocation: {'observations', 'next_observations' (0 in the single-store mode), 'scalars', 'total'}."""
-        per_step = sum(int(np.prod(s)) * torch.empty(0, dtype=self.obs_dtypes[k]).element_size() for k, s in self.obs_shapes.items()) * self.n_envs
+    def _store_bytes(self, frame_dedup):
+        shapes = {k: s[1:] for k, s in self.obs_shapes.items()} if frame_dedup else self.obs_shapes
+        per_step = sum(int(np.prod(s)) * torch.empty(0, dtype=self.obs_dtypes[k]).element_size() for k, s in shapes.items()) * self.n_envs
         obs = per_step * self.buffer_size
         nxt = 0 if self.optimize_memory_usage else obs
-        scalars = 4 * self.buffer_size * self.n_envs * (self.action_dim + 2 + int(self.handle_timeout_termination))
+        scalars = 4 * self.buffer_size * self.n_envs * (self.action_dim + 2 + int(self.handle_timeout_termination) + int(frame_dedup))
         return {"observations": obs, "next_observations": nxt, "scalars": scalars, "total": obs + nxt + scalars}
+
+    def store_bytes(self):
+        """Bytes of the stores, before or after allocation: {'observations', 'next_observations' (0 in the single-store mode), 'scalars', 'total'}.
+        With frame_dedup the first two are the frame stores and 'scalars' counts the 4 bytes per (step, environment) of `ages`."""
+        return self._store_bytes(self.frame_dedup)
 
     def _allocate(self):
         need = self.store_bytes()["total"]
         free = torch.cuda.mem_get_info(self.device)[0]
         free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)      # blocks torch holds and can reuse
         if need > free:
+            dedup = ""
+            if not self.frame_dedup and self.frame_stack > 1:
+                n = self._store_bytes(True)["total"]
+                dedup = f", or frame_dedup=True (every frame of the frame stack stored once: {n} B, {n / 1e9:.1f} GB)"
             raise L.M3LError(f"DeviceReplayBuffer: the stores need {need} bytes ({need / 1e9:.1f} GB) and {free} bytes ({free / 1e9:.1f} GB) of "
                              f"device memory are free; ways out: uint8 stores (obs_dtypes), optimize_memory_usage=True (one observation store "
-                             f"instead of two), or a smaller buffer_size (now {self.buffer_size} steps of {self.n_envs} environments)")
+                             f"instead of two), or a smaller buffer_size (now {self.buffer_size} steps of {self.n_envs} environments){dedup}")
         T, E, dev = self.buffer_size, self.n_envs, self.device
-        self.observations = {k: torch.empty((T, E) + s, dtype=self.obs_dtypes[k], device=dev) for k, s in self.obs_shapes.items()}
-        if not self.optimize_memory_usage:
-            self.next_observations = {k: torch.empty((T, E) + s, dtype=self.obs_dtypes[k], device=dev) for k, s in self.obs_shapes.items()}
+        shapes = {k: s[1:] for k, s in self.obs_shapes.items()} if self.frame_dedup else self.obs_shapes
+        stores = {k: torch.empty((T, E) + s, dtype=self.obs_dtypes[k], device=dev) for k, s in shapes.items()}
+        second = None if self.optimize_memory_usage else {k: torch.empty((T, E) + s, dtype=self.obs_dtypes[k], device=dev) for k, s in shapes.items()}
+        if self.frame_dedup:
+            self.frames, self.next_frames = stores, second
+            self.ages = torch.empty(T, E, dtype=torch.int32, device=dev)
+        else:
+            self.observations, self.next_observations = stores, second
         self.actions = torch.empty(T, E, self.action_dim, dtype=torch.float32, device=dev)
         self.rewards = torch.empty(T, E, dtype=torch.float32, device=dev)
         self.dones = torch.empty(T, E, dtype=torch.float32, device=dev)
@@ -172,24 +247,32 @@ class DeviceReplayBuffer:
     # ---- filling
     def reset(self):
         self.pos, self.full = 0, False
+        # frame_dedup, per environment on the host: the age of the last stored step, and whether the next add() starts an episode
+        self._age = np.zeros(self.n_envs, dtype=np.int32)
+        self._episode_start = np.ones(self.n_envs, dtype=bool)
+        self._last_next_obs = None
 
     def size(self):
         return self.buffer_size if self.full else self.pos
 
     def add(self, obs, next_obs, action, reward, done, infos):
         """One vec-env step into slot `pos`: every array with one copy straight into its place, cast to the store's dtype.  In the single-store
-        mode next_obs goes to slot (pos + 1) % buffer_size of `observations`, where the next add() writes the same frames again."""
+        mode next_obs goes to slot (pos + 1) % buffer_size of `observations`, where the next add() writes the same frames again.  With
+        frame_dedup the same full stacked dicts are taken and only their newest frames are copied (`_add_frames`)."""
         _check_obs("DeviceReplayBuffer.add", obs, self.obs_shapes, self.n_envs)
         _check_obs("DeviceReplayBuffer.add (next_obs)", next_obs, self.obs_shapes, self.n_envs)
         if self.handle_timeout_termination and len(infos) != self.n_envs:
             raise ValueError(f"DeviceReplayBuffer.add: {len(infos)} infos for {self.n_envs} environments")
-        if self.observations is None:
+        if (self.frames if self.frame_dedup else self.observations) is None:
             self._allocate()
         p, T = self.pos, self.buffer_size
-        for k in self.obs_shapes:
-            self.observations[k][p].copy_(torch.as_tensor(obs[k]))
-            nxt = self.observations[k][(p + 1) % T] if self.optimize_memory_usage else self.next_observations[k][p]
-            nxt.copy_(torch.as_tensor(next_obs[k]))
+        if self.frame_dedup:
+            self._add_frames(obs, next_obs, done)
+        else:
+            for k in self.obs_shapes:
+                self.observations[k][p].copy_(torch.as_tensor(obs[k]))
+                nxt = self.observations[k][(p + 1) % T] if self.optimize_memory_usage else self.next_observations[k][p]
+                nxt.copy_(torch.as_tensor(next_obs[k]))
         self.actions[p].copy_(torch.as_tensor(action).reshape(self.n_envs, self.action_dim))
         self.rewards[p].copy_(torch.as_tensor(reward).reshape(self.n_envs))
         self.dones[p].copy_(torch.as_tensor(done).reshape(self.n_envs))
@@ -199,11 +282,54 @@ class DeviceReplayBuffer:
         if self.pos == T:
             self.full, self.pos = True, 0
 
+    _STACKING_RULES = ("next_obs[:, :-1] == obs[:, 1:]", "all frames of obs are equal at an episode's first step",
+                       "obs equals the previous add()'s next_obs")
+
+    def _add_frames(self, obs, next_obs, done):
+        """frame_dedup: the newest frame of each stacked observation into its slot — in the single-store mode next_obs's into slot (pos + 1) %
+        buffer_size of `frames`, where the next add() writes the same frame again — and the step's ages, kept per environment on the host."""
+        d = torch.as_tensor(done).reshape(self.n_envs)
+        if d.is_cuda:
+            raise ValueError("DeviceReplayBuffer.add: frame_dedup=True follows the episodes on the host and needs `done` there")
+        age = np.where(self._episode_start, 0, np.minimum(self._age + 1, self.frame_stack - 1)).astype(np.int32)
+        checked = self._check_stacking(obs, next_obs, age) if self.check_stacking else None
+        p, T = self.pos, self.buffer_size
+        for k in self.obs_shapes:
+            self.frames[k][p].copy_(torch.as_tensor(obs[k])[:, -1])
+            nxt = self.frames[k][(p + 1) % T] if self.optimize_memory_usage else self.next_frames[k][p]
+            nxt.copy_(torch.as_tensor(next_obs[k])[:, -1])
+        self.ages[p].copy_(torch.from_numpy(age))
+        self._age, self._episode_start, self._last_next_obs = age, d.numpy().astype(bool), checked
+
+    def _check_stacking(self, obs, next_obs, age):
+        """The stacking contract of this add() on the device, with one read-back -> next_obs on the device, for the next add()'s check."""
+        start = torch.from_numpy(age == 0).to(self.device)
+        rows = lambda x: x.reshape(self.n_envs, -1)      # noqa: E731
+        flags, cur = [], {}
+        for k in self.obs_shapes:
+            o, n = torch.as_tensor(obs[k]).to(self.device), torch.as_tensor(next_obs[k]).to(self.device)
+            shifted = (rows(n[:, :-1]) == rows(o[:, 1:])).all(1)
+            constant = (rows(o[:, 1:]) == rows(o[:, :-1])).all(1) | ~start
+            follows = torch.ones_like(start) if self._last_next_obs is None else (rows(o) == rows(self._last_next_obs[k])).all(1) | start
+            flags.append(torch.stack([shifted, constant, follows]))
+            cur[k] = n
+        ok = torch.stack(flags).cpu().numpy()
+        for i, k in enumerate(self.obs_shapes):
+            for r, rule in enumerate(self._STACKING_RULES):
+                if not ok[i, r].all():
+                    e = int(np.flatnonzero(~ok[i, r])[0])
+                    raise ValueError(f"DeviceReplayBuffer.add: check_stacking: observation '{k}' of environment {e} breaks the contract of "
+                                     f"frame_dedup=True: {rule} (the stack reaches {int(age[e])} earlier frames of its episode)")
+        return cur
+
     # ---- sampling
     def _valid_steps(self):
-        """The steps a sample may come from, as (first, count) in the ring: count steps starting at `first`, modulo buffer_size."""
-        if self.optimize_memory_usage and self.full:
-            return (self.pos + 1) % self.buffer_size, self.buffer_size - 1      # every step but `pos`: the newest next observation lies there
+        """The steps a sample may come from, as (first, count) in the ring: count steps starting at `first`, modulo buffer_size.  A full ring
+        leaves out step `pos` in the single-store mode — the newest next observation lies there — and with frame_dedup the frame_stack - 1
+        oldest steps after it, whose stacks reach frames that the newest steps overwrote."""
+        skip = int(self.optimize_memory_usage) + (self.frame_stack - 1 if self.frame_dedup else 0)
+        if self.full and skip:
+            return (self.pos + skip) % self.buffer_size, self.buffer_size - skip
         return 0, self.size()
 
     def _injected(self, indices):
@@ -240,8 +366,14 @@ class DeviceReplayBuffer:
                 raise ValueError(f"DeviceReplayBuffer.sample: batch_size={batch_size}")
             # rows relative to the first valid step; the kernels add `shift` modulo T n_envs
             draw, shift = torch.randint(0, count * self.n_envs, (int(batch_size),), device=self.device), first * self.n_envs
-        nxt = self.next_observations or {}
-        obs, next_obs = gather_load(self.observations.get("image"), self.observations.get("tactile"), draw, nxt.get("image"), nxt.get("tactile"),
-                                    self.image_normalization, self.tactile_normalization, shift)
+        if self.frame_dedup:
+            nxt = self.next_frames or {}
+            obs, next_obs = gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, draw, nxt.get("image"),
+                                               nxt.get("tactile"), self.image_normalization, self.tactile_normalization, shift,
+                                               frame_stack=self.frame_stack)
+        else:
+            nxt = self.next_observations or {}
+            obs, next_obs = gather_load(self.observations.get("image"), self.observations.get("tactile"), draw, nxt.get("image"), nxt.get("tactile"),
+                                        self.image_normalization, self.tactile_normalization, shift)
         actions, rewards, dones, rows = gather_rows(self.actions, self.rewards, self.dones, self.timeouts, draw, scale, clip, shift, return_rows=True)
         return ReplayBatch(obs, actions, next_obs, dones, rewards, rows)

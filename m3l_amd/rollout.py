@@ -92,25 +92,28 @@ def _check_obs(who, obs, shapes, n_envs):
             raise ValueError(f"{who}: observation '{k}' has shape {tuple(obs[k].shape)} (expected {(n_envs,) + s})")
 
 
-def _check_stores(who, image_store, tactile_store):
-    """The (T, n_envs, fs, ...) observation stores of a gather -> (T, n_envs, fs, H, W, th, tw, S)."""
+def _check_stores(who, image_store, tactile_store, frames=False):
+    """The (T, n_envs, fs, ...) observation stores of a gather -> (T, n_envs, fs, H, W, th, tw, S).  frames: the stores of single frames of
+    m3l_amd.replay.gather_load_frames, (T, n_envs, ...) without the fs axis and named *_frames -> (T, n_envs, H, W, th, tw, S)."""
     ref = image_store if image_store is not None else tactile_store
-    T, n_envs, fs = ref.shape[:3]
+    lead = 2 if frames else 3
+    head = tuple(ref.shape[:lead])
     H = W = th = tw = S = 0
-    for name, t in (("image_store", image_store), ("tactile_store", tactile_store)):
-        if t is not None and (t.dim() != 6 or tuple(t.shape[:3]) != (T, n_envs, fs) or not t.is_contiguous()
+    suffix, layout = ("_frames", "(T, n_envs, ...) tensor of 5") if frames else ("_store", "(T, n_envs, fs, ...) tensor of 6")
+    for name, t in (("image" + suffix, image_store), ("tactile" + suffix, tactile_store)):
+        if t is not None and (t.dim() != lead + 3 or tuple(t.shape[:lead]) != head or not t.is_contiguous()
                               or t.dtype not in (torch.uint8, torch.float32)):
-            raise ValueError(f"{who}: {name} must be a contiguous uint8 / float32 (T, n_envs, fs, ...) tensor of 6 dimensions")
+            raise ValueError(f"{who}: {name} must be a contiguous uint8 / float32 {layout} dimensions")
     if image_store is not None:
-        H, W = image_store.shape[3:5]
-        if image_store.shape[5] != 3:
-            raise ValueError(f"{who}: image_store has {image_store.shape[5]} channels (3)")
+        H, W, C = image_store.shape[lead:]
+        if C != 3:
+            raise ValueError(f"{who}: image{suffix} has {C} channels (3)")
     if tactile_store is not None:
-        CH, th, tw = tactile_store.shape[3:]
+        CH, th, tw = tactile_store.shape[lead:]
         if CH % 3 or not 1 <= CH // 3 <= MAX_SENSORS:
-            raise ValueError(f"{who}: tactile_store has {CH} channels per frame (3 * S, 1 <= S <= {MAX_SENSORS})")
+            raise ValueError(f"{who}: tactile{suffix} has {CH} channels per frame (3 * S, 1 <= S <= {MAX_SENSORS})")
         S = CH // 3
-    return T, n_envs, fs, H, W, th, tw, S
+    return head + (H, W, th, tw, S)
 
 
 def _loaded_outputs(B, fs, H, W, th, tw, S, device):

@@ -20,7 +20,13 @@ around the same window without its synchronise, paths alternated, median / min /
 torch.profiler in a run of their own).  For (c_obs): the bytes the algorithm needs — one read of 2 B stored rows, one write of 2 B float32
 rows — over its call time, and the share of the 6.29 TB/s a float4 copy reaches on this chip.  Without a GPU the tool fails.
 
-Usage: python tools/replay_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32] [--batches 64,256]   (one JSON line)"""
+--dedup measures the frame-deduplicated store instead (EXPERIMENTS.md §5.23), at the same shapes, windows and alternation: (d_obs) one
+replay.gather_load_frames call on frame stores against (c_obs) one replay.gather_load call on stacked stores holding the same data as rolling
+stacks — compared bit for bit over every batch before the timing — with the bytes each needs (fs + 1 against 2 fs frame reads, equal writes),
+`not_slower`: d_obs's median no higher than c_obs's median plus c_obs's own min-max spread; the host time of one add() in the four
+layouts; and store_bytes() of 10^6 transitions at the reference's defaults.
+
+Usage: python tools/replay_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32] [--batches 64,256] [--dedup]   (one JSON line)"""
 import argparse
 import json
 import math
@@ -164,6 +170,127 @@ def run_variant(name, a):
     return out
 
 
+# ---- the frame-deduplicated store (--dedup, EXPERIMENTS.md §5.23)
+def dedup_stores(image_dtype, seed):
+    """Device frame stores (T, n_envs, ...) of seeded frames, every one distinct in its first element, and the stacked stores that hold the same
+    data as rolling stacks: one endless episode round the ring, so every step's stack is the fs frames up to its own (ages fs - 1 everywhere)
+    and every step is valid in both layouts.  -> (frames, next_frames, stacked, stacked_next, stacked_single_next is the stacked store itself)."""
+    g = np.random.default_rng(seed)
+
+    def make(s):
+        slab_i = g.integers(0, 256, (50, E, H, W, 3), dtype=np.uint8) if image_dtype == np.uint8 else g.random((50, E, H, W, 3), dtype=np.float32)
+        img = np.tile(slab_i, (T // 50, 1, 1, 1, 1))
+        tac = np.tile((2 * g.random((50, E, 3 * S, TH, TW), dtype=np.float32) - 1).astype(np.float32), (T // 50, 1, 1, 1, 1))
+        img[:, 0, 0, 0, 0] = ((np.arange(T) + s) % 251).astype(image_dtype)
+        tac[:, 0, 0, 0, 0] = (np.arange(T, dtype=np.float32) + s) / (2 * T)
+        return {"image": torch.from_numpy(img).to(DEV), "tactile": torch.from_numpy(tac).to(DEV)}
+
+    frames, next_frames = make(0), make(7)
+    # obs[t, f] = frames[t - (fs - 1 - f)];  next_obs[t] = obs[t, 1:] + next_frames[t]
+    stacked = {k: torch.stack([torch.roll(v, FS - 1 - f, 0) for f in range(FS)], dim=2).contiguous() for k, v in frames.items()}
+    stacked_next = {k: torch.cat([stacked[k][:, :, 1:], next_frames[k].unsqueeze(2)], dim=2).contiguous() for k in frames}
+    return frames, next_frames, stacked, stacked_next
+
+
+def run_dedup_config(name, single, B, frames, next_frames, stacked, stacked_next, ages, a):
+    perm = np.random.default_rng(1).permutation(T).astype(np.int64)
+    d_rows = [torch.from_numpy(perm[i:i + B]).to(DEV) for i in range(0, T - B + 1, B)]
+    state = {}
+
+    def nxt(p):
+        i = state.get(p, 0)
+        state[p] = (i + 1) % len(d_rows)
+        return i
+
+    def c_stacked(i):
+        nx = {} if single else stacked_next
+        return P.gather_load(stacked["image"], stacked["tactile"], d_rows[i], nx.get("image"), nx.get("tactile"))
+
+    def d_frames(i):
+        nx = {} if single else next_frames
+        return P.gather_load_frames(frames["image"], frames["tactile"], ages, d_rows[i], nx.get("image"), nx.get("tactile"), frame_stack=FS)
+
+    # equal bits on every batch of the permutation before anything is timed
+    for i in range(len(d_rows)):
+        for x, y in zip(c_stacked(i), d_frames(i)):
+            for k in x:
+                assert torch.equal(x[k], y[k]), f"{name}: the stacked and the deduplicated store disagree on {k} (batch {i})"
+    torch.cuda.synchronize()
+    fns = {"c_obs_stacked": lambda: c_stacked(nxt("c")), "d_obs_frames": lambda: d_frames(nxt("d"))}
+    res = alternate(fns, {n: a.iters for n in fns}, {n: 20 for n in fns}, a.rounds)
+    for p, fn in fns.items():
+        res[p].update(counted(fn))
+    isz = 1 if name == "u8" else 4
+    frame_in = H * W * 3 * isz + 3 * S * TH * TW * 4
+    frame_out = (H * W * 3 + 3 * S * TH * TW) * 4
+    for p, n_read in (("c_obs_stacked", 2 * FS), ("d_obs_frames", FS + 1)):
+        c = res[p]
+        c["bytes_read"], c["bytes_written"] = B * n_read * frame_in, B * 2 * FS * frame_out
+        for key, us in (("", c["call_us"]), ("_best", c["call_us_min_max"][0]), ("_worst", c["call_us_min_max"][1])):
+            tbs = (c["bytes_read"] + c["bytes_written"]) / (us * 1e-6) / 1e12
+            c["tbytes_per_s" + key] = round(tbs, 3)
+            c["share_of_measured_copy_peak" + key] = round(tbs / HBM_COPY_TBS, 3)
+    s, d = res["c_obs_stacked"], res["d_obs_frames"]
+    res["bytes_frames_over_stacked"] = round((d["bytes_read"] + d["bytes_written"]) / (s["bytes_read"] + s["bytes_written"]), 3)
+    res["frames_over_stacked"] = round(d["call_us"] / s["call_us"], 3)
+    spread = s["call_us_min_max"][1] - s["call_us_min_max"][0]
+    res["stacked_spread_us"] = round(spread, 1)
+    res["not_slower"] = bool(d["call_us"] <= s["call_us"] + spread)      # the condition for keeping the kernel's shape
+    return res
+
+
+def time_add(name, single, dedup, n_adds=400, T_add=2000):
+    """Host time of one add() — the upload of one vec-env step from pageable numpy arrays — with a synchronise at the end of the window."""
+    import time
+    image_dtype = np.uint8 if name == "u8" else np.float32
+    buf = m3l_amd.DeviceReplayBuffer(T_add, E, {"image": (FS, H, W, 3), "tactile": (FS, 3 * S, TH, TW)}, {"image": image_dtype, "tactile": np.float32}, A,
+                                     optimize_memory_usage=single, handle_timeout_termination=not single, device=DEV, frame_dedup=dedup)
+    g = np.random.default_rng(3)
+    obs = {"image": (g.integers(0, 256, (E, FS, H, W, 3), dtype=np.uint8) if name == "u8" else g.random((E, FS, H, W, 3), dtype=np.float32)),
+           "tactile": g.random((E, FS, 3 * S, TH, TW), dtype=np.float32)}
+    rest = (np.zeros((E, A), np.float32), np.zeros(E, np.float32), np.zeros(E, bool), [{}] * E)
+    times = []
+    for r in range(6):                              # the first window allocates and warms up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n_adds):
+            buf.add(obs, obs, *rest)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) / n_adds * 1e6)
+    times = sorted(times[1:])
+    return {"add_us": round(times[len(times) // 2], 1), "add_us_min_max": [round(times[0], 1), round(times[-1], 1)], "window_adds": n_adds}
+
+
+def store_bytes_table():
+    """store_bytes() of 10^6 transitions at the reference's defaults (arithmetic: nothing is allocated)."""
+    shapes = {"image": (FS, H, W, 3), "tactile": (FS, 3 * S, TH, TW)}
+    out = {}
+    for dedup in (False, True):
+        for single in (False, True):
+            for img in ("u8", "f32"):
+                b = m3l_amd.DeviceReplayBuffer(1_000_000, 1, shapes, {"image": np.uint8 if img == "u8" else np.float32, "tactile": np.float32}, A,
+                                               optimize_memory_usage=single, handle_timeout_termination=not single, device=DEV, frame_dedup=dedup)
+                out[f"{'frames' if dedup else 'stacked'}_{'single_store' if single else 'two_stores'}_{img}"] = b.store_bytes()["total"]
+    return out
+
+
+def run_dedup(a):
+    out = {"store_bytes_1e6_transitions": store_bytes_table()}
+    ages = torch.full((T, E), FS - 1, dtype=torch.int32, device=DEV)
+    for name in a.variants.split(","):
+        frames, next_frames, stacked, stacked_next = dedup_stores(np.uint8 if name == "u8" else np.float32, 0)
+        torch.cuda.synchronize()
+        out[name] = {}
+        for B in a.batches:
+            out[name][f"B{B}_two_stores"] = run_dedup_config(name, False, B, frames, next_frames, stacked, stacked_next, ages, a)
+            out[name][f"B{B}_single_store"] = run_dedup_config(name, True, B, frames, None, stacked, None, ages, a)
+        del frames, next_frames, stacked, stacked_next
+        torch.cuda.empty_cache()
+        out[name]["add"] = {f"{'frames' if dedup else 'stacked'}_{'single_store' if single else 'two_stores'}": time_add(name, single, dedup)
+                            for dedup in (False, True) for single in (False, True)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5, help="alternating windows per path")
@@ -171,12 +298,17 @@ def main():
     ap.add_argument("--host-iters", type=int, default=5, help="calls per timed window of the host path (a)")
     ap.add_argument("--variants", default="u8,f32")
     ap.add_argument("--batches", default="64,256")
+    ap.add_argument("--dedup", action="store_true", help="measure the frame-deduplicated store against the stacked one instead of the three paths")
     a = ap.parse_args()
     a.batches = [int(b) for b in a.batches.split(",")]
     if not torch.cuda.is_available():
         raise SystemExit("replay_feed_bench: no GPU")
     out = {"shape": {"T": T, "n_envs": E, "frame_stack": FS, "image": [H, W, 3], "tactile": [3 * S, TH, TW], "B": a.batches, "action_dim": A},
            "hbm_peak_tbytes_per_s": {"float4_copy_measured": HBM_COPY_TBS, "spec": HBM_SPEC_TBS}}
+    if a.dedup:
+        out["frame_dedup"] = run_dedup(a)
+        print(json.dumps(out))
+        return
     for name in a.variants.split(","):
         out[name] = run_variant(name, a)
     print(json.dumps(out))
