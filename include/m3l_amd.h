@@ -722,6 +722,11 @@ int m3l_sac_critic_bwd(const m3l_sac_desc* head, int B, const float* dq, void* w
 /* target_q [B] is written; rewards, dones [B]; the descriptor's critics are the target critics */
 int m3l_sac_td_target(const m3l_sac_desc* head, int B, const float* x_next, const float* noise, const float* rewards, const float* dones, float gamma,
                       float ent_coef, const float* log_ent_coef, float* target_q, void* stream);
+/* (ABI 414) the same with one discount per row, discounts [B], where gamma stands: target_q = r + (1 - done) discounts (...), the target of an
+ * n-step return (discounts = gamma^(steps taken), m3l_replay_nstep_rows).  Both entries run one kernel and the discount enters one
+ * expression: discounts filled with one value gives the bits of m3l_sac_td_target with that gamma.  Errors: those above, and discounts NULL. */
+int m3l_sac_td_target_rows(const m3l_sac_desc* head, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                           const float* discounts, float ent_coef, const float* log_ent_coef, float* target_q, void* stream);
 /* loss[1] and coef [2, B] = dloss/dq are written; the backward writes dq [2, B] = dloss[0] coef (dloss: device scalar) */
 int m3l_sac_critic_loss_fwd(const float* q, const float* target_q, int B, float* loss, float* coef, void* stream);
 int m3l_sac_critic_loss_bwd(const float* dloss, const float* coef, int B, float* dq, void* stream);
@@ -832,6 +837,49 @@ int m3l_replay_gather_load_frames(const void* image_frames, const void* image_ne
                                   int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out,
                                   float* const* tactile_next_out, const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* rows,
                                   long row_shift, int B, void* stream);
+
+/* ---- n-step returns (ABI 414): a sampled transition (t, e) stands for the next n_steps steps of its episode — the sample-efficiency lever
+ * of pixel-based SAC (DrQ-v2; SB3's NStepReplayBuffer from 2.7, which is not in the reference tree: the rule is restated here and in
+ * tests/nstep_cases.py, parity unpinned).  With g = gamma (f32), newest = the step written last, (pos - 1) mod T, passed by the host:
+ *   walk        k* = the smallest k in [0, n_steps - 1] with dones[(t + k) % T, e] != 0 (SB3 stores done = 1 for a truncated step too) or
+ *               (t + k) % T == newest (beyond the write head lie unwritten slots or, in a full ring, the oldest steps); n_steps - 1 if there
+ *               is none.  last = (t + k*) % T: the walk crosses neither an episode end nor the write head.
+ *   rewards     sum over k = 0 .. k* of g^k r~[(t + k) % T, e], r~ the reward as m3l_replay_gather_rows returns it (raw or normalised), g^k by
+ *               repeated f32 multiplication, the sum in f32 in ascending k, multiplications and additions separate; k* = 0: r~ itself
+ *   dones       dones[last, e] (1 - timeouts[last, e])  (timeouts NULL: dones[last, e])
+ *   discounts   g^(k* + 1) by the same multiplication; k* = 0: g itself.  What m3l_sac_td_target_rows takes where gamma stands
+ *   rows        t n_envs + e, as gather_rows' rows_out;  next_rows  last n_envs + e: the row whose next observation the target bootstraps from
+ *   actions     those of (t, e)
+ * m3l_replay_nstep_rows: the inputs of m3l_replay_gather_rows plus n_steps, gamma and newest; one launch, no read-back, no atomics, one lane
+ * walks one sample: two runs give the same bits, and n_steps = 1 gives gather_rows' bits.  Index contract as above: a row outside
+ * [0, T n_envs) is never read, nor is anything through it; its outputs are NaN and its rows / next_rows entries -1.
+ * Errors, nothing written: those of gather_rows, a NULL output, n_steps outside [1, T], gamma outside (0, 1], newest outside [0, T).
+ *
+ * m3l_replay_gather_load_rows2 / m3l_replay_gather_load_frames_rows2 are the two observation gathers with a second row list: `rows` (with
+ * row_shift) names the observations, `next_rows` [B] the rows whose next observations are wanted — store rows already reduced modulo the
+ * ring, as nstep_rows writes them: no shift is applied.  The halves are independent: an entry outside [0, T n_envs) of either list (the -1
+ * of nstep_rows) gives NaN in that half and reads nothing.
+ *   rows2          the next half reads *_next_store at next_rows[b] (NULL: the store itself one step after next_rows[b]); the traffic of
+ *                  m3l_replay_gather_load
+ *   frames_rows2   the two stacks belong to different rows, so a sample is 2 fs source frames, each loaded, normalised and written once:
+ *                  source k < fs           observation frame k of rows[b], min(fs - 1 - k, ages[rows[b]]) steps back
+ *                  source fs + j, j < fs-1 observation frame j + 1 of next_rows[b], with that row's age -> next-observation frame j
+ *                  source 2 fs - 1         next_frames at next_rows[b] (NULL: frames one step later)   -> next-observation frame fs - 1
+ *                  2 fs frame reads for 2 fs frame writes (m3l_replay_gather_load_frames: fs + 1 reads).
+ * Errors: those of the one-list entries, and next_rows NULL. */
+int m3l_replay_nstep_rows(const float* actions, const float* rewards, const float* dones, const float* timeouts, int T, int n_envs, int A,
+                          const int64_t* rows, long row_shift, int B, float reward_scale, float reward_clip, int n_steps, float gamma, int newest,
+                          float* actions_out, float* rewards_out, float* dones_out, float* discounts_out, int64_t* rows_out, int64_t* next_rows_out,
+                          void* stream);
+int m3l_replay_gather_load_rows2(const void* image_store, const void* image_next_store, int image_u8, int H, int W, double img_lo, double img_hi,
+                                 float* image, float* image_next, const void* tactile_store, const void* tactile_next_store, int tactile_u8, int th,
+                                 int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out, float* const* tactile_next_out, int T,
+                                 int n_envs, int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, int B, void* stream);
+int m3l_replay_gather_load_frames_rows2(const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
+                                        double img_hi, float* image, float* image_next, const void* tactile_frames,
+                                        const void* tactile_next_frames, int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi,
+                                        float* const* tactile_out, float* const* tactile_next_out, const int32_t* ages, int T, int n_envs,
+                                        int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, int B, void* stream);
 
 #ifdef __cplusplus
 }

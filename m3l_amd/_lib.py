@@ -228,6 +228,14 @@ _SIGS = {
     "m3l_replay_gather_rows": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_i, C.c_float, C.c_float, c_p, c_p, c_p, c_p, c_p]),
     "m3l_replay_gather_load_frames": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double,
                                             C.c_double, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_i, c_p]),
+    # n-step returns (ABI 414): the two gathers with a second row list in front of B; gather_rows plus n_steps, gamma, newest and two outputs
+    "m3l_replay_gather_load_rows2": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double,
+                                           C.c_double, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_p, c_i, c_p]),
+    "m3l_replay_gather_load_frames_rows2": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double,
+                                                  C.c_double, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_p, c_i, c_p]),
+    "m3l_replay_nstep_rows": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_i, C.c_float, C.c_float, c_i, C.c_float, c_i, c_p, c_p, c_p,
+                                    c_p, c_p, c_p, c_p]),
+    "m3l_sac_td_target_rows": (c_i, [C.POINTER(SacDesc), c_i, c_p, c_p, c_p, c_p, c_p, C.c_float, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

@@ -106,6 +106,30 @@ __device__ __forceinline__ float* tactile_sensor(float* const (&tac_out)[M3L_MAX
     return o;
 }
 
+// one piece of one frame, loaded, normalised and written once: piece q of frame `frame` of img -> plane group `group` of img_out.  What the items
+// below do for a stacked row, for callers that put a stack together frame by frame (replay.hip, the two-list frame gather)
+template <typename TI>
+__device__ __forceinline__ void gather_image_piece(const GatherGeom& g, const void* img, float* img_out, long frame, long group, int q) {
+    if (g.img_vec) {
+        float v[12];
+        image_load4<TI>(g, img, frame, q, v);
+        image_store4(g, img_out, group, q, v);
+    } else {
+        float v[3];
+        image_load1<TI>(g, img, frame, q, v);
+        image_store1(g, img_out, group, q, v);
+    }
+}
+// the same for sensor s of a tactile frame; out is that sensor's output
+template <typename TI>
+__device__ __forceinline__ void gather_tactile_piece(const GatherGeom& g, const void* tac, float* out, long frame, long group, int s, int q) {
+    float* o = out + group * (3L * g.hw);
+    if (g.tac_vec)
+        *(f32x4*)(o + 4L * q) = tactile_load4<TI>(g, tac, frame, s, q);
+    else
+        o[q] = tactile_load1<TI>(g, tac, frame, s, q);
+}
+
 // item r < img_per_sample of output sample b: store row `row` of img (n_rows, fs, H, W, 3) -> img_out (B, 3 fs, H, W)
 template <typename TI>
 __device__ __forceinline__ void gather_image_item(const GatherGeom& g, const void* img, float* img_out, long row, int b, int r) {

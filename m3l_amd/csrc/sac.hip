@@ -212,9 +212,11 @@ __global__ __launch_bounds__(256) void sac_critic_bwd_kernel(SacArgs p, const fl
 // grid (cdiv(items, 4)): wave w of block b takes item 4 b + w
 __global__ __launch_bounds__(256) void sac_wgrad_kernel(PhWgrad q) { ph_wgrad_block(q, blockIdx.x); }
 
-// grid (row tiles).  The critic pointers of p are the target critics'.
+// grid (row tiles).  The critic pointers of p are the target critics'.  discounts: one discount per row (n-step returns), or NULL: gamma for
+// every row; the value enters one expression either way, so a constant discounts gives the bits of the scalar.
 __global__ __launch_bounds__(256) void sac_td_target_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ noise,
-                                                            const float* __restrict__ rewards, const float* __restrict__ dones, float gamma, float ent_coef,
+                                                            const float* __restrict__ rewards, const float* __restrict__ dones,
+                                                            const float* __restrict__ discounts, float gamma, float ent_coef,
                                                             const float* __restrict__ log_ent_coef, float* __restrict__ target_q) {
     extern __shared__ __attribute__((aligned(16))) float sac_lds[];
     __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD], hs[PH_TM * PH_HLD];
@@ -234,7 +236,8 @@ __global__ __launch_bounds__(256) void sac_td_target_kernel(SacArgs p, const flo
         const int row = row0 + tid;
         const float ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
         const float nq = fminf(q_sh[0][tid], q_sh[1][tid]) - ent * lp_sh[tid];
-        target_q[row] = rewards[row] + (1.f - dones[row]) * gamma * nq;
+        const float g = discounts ? discounts[row] : gamma;
+        target_q[row] = rewards[row] + (1.f - dones[row]) * g * nq;
     }
 }
 
@@ -466,19 +469,39 @@ int m3l_sac_critic_bwd(const m3l_sac_desc* d, int B, const float* dq, void* ws, 
     return 0;
 }
 
-int m3l_sac_td_target(const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones, float gamma,
-                      float ent_coef, const float* log_ent_coef, float* target_q, void* stream) {
+}  // extern "C"
+
+namespace {
+// m3l_sac_td_target (discounts NULL) and m3l_sac_td_target_rows
+int sac_td_target_launch(const char* who, const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards,
+                         const float* dones, const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, float* target_q,
+                         void* stream) {
     char why[160];
-    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_td_target: unsupported shape: %s", why);
-    if (sac_params_ok(d, SAC_ACTOR | SAC_CRITIC, "sac_td_target")) return 1;
-    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "sac_td_target: null argument, or x_next not 16-byte aligned");
+    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "%s: unsupported shape: %s", who, why);
+    if (sac_params_ok(d, SAC_ACTOR | SAC_CRITIC, who)) return 1;
+    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "%s: null argument, or x_next not 16-byte aligned", who);
     if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const SacArgs p = sac_args(d, B, SAC_ACTOR | SAC_CRITIC);
-    ProfScope prof("sac_td_target", B, p.F, p.A, sac_actor_flops(p) + sac_critic_flops(p), st, 4.0 * B * p.F);
-    sac_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, x_next, noise, rewards, dones, gamma, ent_coef, log_ent_coef, target_q);
+    ProfScope prof(who, B, p.F, p.A, sac_actor_flops(p) + sac_critic_flops(p), st, 4.0 * B * p.F);
+    sac_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, x_next, noise, rewards, dones, discounts, gamma, ent_coef, log_ent_coef,
+                                                                       target_q);
     M3L_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int m3l_sac_td_target(const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones, float gamma,
+                      float ent_coef, const float* log_ent_coef, float* target_q, void* stream) {
+    return sac_td_target_launch("sac_td_target", d, B, x_next, noise, rewards, dones, nullptr, gamma, ent_coef, log_ent_coef, target_q, stream);
+}
+
+int m3l_sac_td_target_rows(const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                           const float* discounts, float ent_coef, const float* log_ent_coef, float* target_q, void* stream) {
+    M3L_CHECK(discounts, "sac_td_target_rows: discounts is NULL");
+    return sac_td_target_launch("sac_td_target_rows", d, B, x_next, noise, rewards, dones, discounts, 0.f, ent_coef, log_ent_coef, target_q, stream);
 }
 
 int m3l_sac_critic_loss_fwd(const float* q, const float* target_q, int B, float* loss, float* coef, void* stream) {

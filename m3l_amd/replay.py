@@ -15,7 +15,18 @@ seam (what `get(indices=...)` is for the rollout).  A sample is three launches: 
 
 SB3 is not in the reference tree: the ring (`add`, `pos`, `full`), the single-store mode (`optimize_memory_usage`), the timeout mask and
 `VecNormalize.normalize_reward` are restated here and in tests/replay_cases.py (parity unpinned).  Not covered: `save_replay_buffer` pickling,
-n-step returns, HER, prioritised sampling, observation normalisation (`norm_obs`).
+HER, prioritised sampling, observation normalisation (`norm_obs`).
+
+`n_steps=n > 1` gives n-step returns (SB3's `NStepReplayBuffer` / `SAC(n_steps=)` from 2.7, restated in tests/nstep_cases.py, parity unpinned).
+From a sampled (t, e) the walk goes towards newer steps and ends at `last = (t + k*) % T`, k* the smallest k in [0, n - 1] at which
+`dones[(t + k) % T, e] != 0` (a truncated step is stored with done = 1 too) or `(t + k) % T` is the step written last, else n - 1: it crosses
+neither an episode end nor the write head.  With g = float32(gamma): rewards = sum_{k <= k*} g^k r[(t + k) % T, e] of the (normalised)
+rewards, g^k by repeated float32 multiplication and the sum in float32 in ascending k; dones = dones[last] * (1 - timeouts[last]);
+discounts = g^(k* + 1); observations, actions and rows are those of (t, e); next_observations is the next observation of (last, e) and
+next_rows = last * n_envs + e.  `sample()` returns an `NStepReplayBatch` and stays three launches with nothing read back: the draw,
+`nstep_rows` (m3l_replay_nstep_rows) and one observation gather fed `rows` and `next_rows` (m3l_replay_gather_load_rows2 /
+m3l_replay_gather_load_frames_rows2).  `head.td_target(extractor(batch.next_observations), batch.rewards, batch.dones, batch.discounts, ...)`
+takes the per-row discount.  The single-store mode is refused, as SB3 refuses it: it has no agreed next observation at `last`.
 
 `frame_dedup=True` stores every frame once.  The reference's `FrameStack` wrapper (utils/frame_stack.py:76-105) makes each observation the last
 `fs` frames of its episode, so the stacked stores hold one frame `fs` times each; the deduplicated stores `frames` / `next_frames` hold the
@@ -41,12 +52,20 @@ def _check_rows(who, rows):
         raise ValueError(f"{who}: rows must be a contiguous 1-D int64 tensor")
 
 
+def _check_next_rows(who, next_rows, rows):
+    _require_cuda(next_rows, who + ": next_rows")
+    if next_rows.dtype != torch.int64 or next_rows.shape != rows.shape or not next_rows.is_contiguous():
+        raise ValueError(f"{who}: next_rows must be a contiguous int64 tensor of rows' shape {tuple(rows.shape)}")
+
+
 def gather_load(image_store, tactile_store, rows, image_next_store=None, tactile_next_store=None, image_normalization=(0, 1),
-                tactile_normalization=(-1, 1), row_shift=0):
+                tactile_normalization=(-1, 1), row_shift=0, next_rows=None):
     """image_store (T, n_envs, fs, H, W, 3) and / or tactile_store (T, n_envs, fs, 3*S, h, w), uint8 or float32 CUDA tensors, and rows (B) int64
     store rows t * n_envs + e -> (observations, next_observations), two LoadedObs {'image': (B, 3*fs, H, W), 'tactile1..S': (B, 3*fs, h, w)}:
     what `vt_load(_flatten_frame_stack(store[t, e]))` gives for both, in one launch (m3l_replay_gather_load).  The next observation is read
-    from `*_next_store` at the same row, or without one from the store itself at step (t + 1) % T."""
+    from `*_next_store` at the same row, or without one from the store itself at step (t + 1) % T.
+    next_rows (B) int64: the next observations are those of these store rows instead, taken as they are — row_shift applies to rows alone —
+    and an entry outside [0, T n_envs) gives NaN in that half only (m3l_replay_gather_load_rows2)."""
     ref = image_store if image_store is not None else tactile_store
     if ref is None:
         raise ValueError("replay.gather_load: neither an image nor a tactile store")
@@ -58,27 +77,34 @@ def gather_load(image_store, tactile_store, rows, image_next_store=None, tactile
         if nxt is not None and (t is None or nxt.shape != t.shape or nxt.dtype != t.dtype or not nxt.is_contiguous()):
             raise ValueError(f"replay.gather_load: {name}_next_store must be a contiguous tensor of {name}_store's shape and dtype")
     _check_rows("replay.gather_load", rows)
+    if next_rows is not None:
+        _check_next_rows("replay.gather_load", next_rows, rows)
     T, n_envs, fs, H, W, th, tw, S = _check_stores("replay.gather_load", image_store, tactile_store)
     B = rows.shape[0]
     img, tacs = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
     img_next, tacs_next = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
-    L.check(L.lib().m3l_replay_gather_load(
-        L.ptr(image_store), L.ptr(image_next_store), int(image_store is not None and image_store.dtype == torch.uint8), H, W,
-        float(image_normalization[0]), float(image_normalization[1]), L.ptr(img), L.ptr(img_next), L.ptr(tactile_store), L.ptr(tactile_next_store),
-        int(tactile_store is not None and tactile_store.dtype == torch.uint8), th, tw, S, float(tactile_normalization[0]),
-        float(tactile_normalization[1]), L.ptr_array(tacs), L.ptr_array(tacs_next), T, n_envs, fs, L.ptr(rows), int(row_shift), B, _stream()),
-        "m3l_replay_gather_load")
+    head = (L.ptr(image_store), L.ptr(image_next_store), int(image_store is not None and image_store.dtype == torch.uint8), H, W,
+            float(image_normalization[0]), float(image_normalization[1]), L.ptr(img), L.ptr(img_next), L.ptr(tactile_store), L.ptr(tactile_next_store),
+            int(tactile_store is not None and tactile_store.dtype == torch.uint8), th, tw, S, float(tactile_normalization[0]),
+            float(tactile_normalization[1]), L.ptr_array(tacs), L.ptr_array(tacs_next), T, n_envs, fs, L.ptr(rows), int(row_shift))
+    if next_rows is None:
+        L.check(L.lib().m3l_replay_gather_load(*head, B, _stream()), "m3l_replay_gather_load")
+    else:
+        L.check(L.lib().m3l_replay_gather_load_rows2(*head, L.ptr(next_rows), B, _stream()), "m3l_replay_gather_load_rows2")
     return _as_loaded(img, tacs), _as_loaded(img_next, tacs_next)
 
 
 def gather_load_frames(image_frames, tactile_frames, ages, rows, image_next_frames=None, tactile_next_frames=None, image_normalization=(0, 1),
-                       tactile_normalization=(-1, 1), row_shift=0, *, frame_stack):
+                       tactile_normalization=(-1, 1), row_shift=0, next_rows=None, *, frame_stack):
     """`gather_load` on frame-deduplicated stores: image_frames (T, n_envs, H, W, 3) and / or tactile_frames (T, n_envs, 3*S, h, w), uint8 or
     float32 CUDA tensors whose slot t holds the newest frame of step t's observation, ages (T, n_envs) int32 — how many earlier frames of the
     same episode the stack of a step reaches, clamped by the kernel to [0, frame_stack - 1] — and rows (B) int64 -> (observations,
     next_observations) as `gather_load` returns them, in one launch (m3l_replay_gather_load_frames).  Observation frame j is the frame of step
     t - min(frame_stack - 1 - j, age) in the ring; the next observation is frames 1.. of that and the frame of `*_next_frames` at the same row,
-    or without one of the store itself at step (t + 1) % T."""
+    or without one of the store itself at step (t + 1) % T.
+    next_rows (B) int64: the next observations are those of these store rows instead, taken as they are, each with its own age: 2 *
+    frame_stack source frames per sample, every one written once (m3l_replay_gather_load_frames_rows2); an entry outside [0, T n_envs)
+    gives NaN in that half only."""
     who = "replay.gather_load_frames"
     ref = image_frames if image_frames is not None else tactile_frames
     if ref is None:
@@ -91,6 +117,8 @@ def gather_load_frames(image_frames, tactile_frames, ages, rows, image_next_fram
         if nxt is not None and (t is None or nxt.shape != t.shape or nxt.dtype != t.dtype or not nxt.is_contiguous()):
             raise ValueError(f"{who}: {name}_next_frames must be a contiguous tensor of {name}_frames' shape and dtype")
     _check_rows(who, rows)
+    if next_rows is not None:
+        _check_next_rows(who, next_rows, rows)
     fs = int(frame_stack)
     if fs < 1:
         raise ValueError(f"{who}: frame_stack={frame_stack}")
@@ -101,12 +129,15 @@ def gather_load_frames(image_frames, tactile_frames, ages, rows, image_next_fram
     B = rows.shape[0]
     img, tacs = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
     img_next, tacs_next = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
-    L.check(L.lib().m3l_replay_gather_load_frames(
-        L.ptr(image_frames), L.ptr(image_next_frames), int(image_frames is not None and image_frames.dtype == torch.uint8), H, W,
-        float(image_normalization[0]), float(image_normalization[1]), L.ptr(img), L.ptr(img_next), L.ptr(tactile_frames),
-        L.ptr(tactile_next_frames), int(tactile_frames is not None and tactile_frames.dtype == torch.uint8), th, tw, S,
-        float(tactile_normalization[0]), float(tactile_normalization[1]), L.ptr_array(tacs), L.ptr_array(tacs_next), L.ptr(ages), T, n_envs, fs,
-        L.ptr(rows), int(row_shift), B, _stream()), "m3l_replay_gather_load_frames")
+    head = (L.ptr(image_frames), L.ptr(image_next_frames), int(image_frames is not None and image_frames.dtype == torch.uint8), H, W,
+            float(image_normalization[0]), float(image_normalization[1]), L.ptr(img), L.ptr(img_next), L.ptr(tactile_frames),
+            L.ptr(tactile_next_frames), int(tactile_frames is not None and tactile_frames.dtype == torch.uint8), th, tw, S,
+            float(tactile_normalization[0]), float(tactile_normalization[1]), L.ptr_array(tacs), L.ptr_array(tacs_next), L.ptr(ages), T, n_envs, fs,
+            L.ptr(rows), int(row_shift))
+    if next_rows is None:
+        L.check(L.lib().m3l_replay_gather_load_frames(*head, B, _stream()), "m3l_replay_gather_load_frames")
+    else:
+        L.check(L.lib().m3l_replay_gather_load_frames_rows2(*head, L.ptr(next_rows), B, _stream()), "m3l_replay_gather_load_frames_rows2")
     return _as_loaded(img, tacs), _as_loaded(img_next, tacs_next)
 
 
@@ -131,6 +162,37 @@ def gather_rows(actions, rewards, dones, timeouts, rows, reward_scale=0.0, rewar
                                            float(reward_scale), float(reward_clip), *[L.ptr(t) for t in out], L.ptr(rows_out), _stream()),
             "m3l_replay_gather_rows")
     return tuple(out) + ((rows_out,) if return_rows else ())
+
+
+def nstep_rows(actions, rewards, dones, timeouts, rows, n_steps, gamma, newest, reward_scale=0.0, reward_clip=0.0, row_shift=0):
+    """`gather_rows` for n-step returns (m3l_replay_nstep_rows, one launch): from step t of every row the walk goes up to n_steps - 1 steps
+    towards newer ones in the ring and ends at the first done, at step `newest` (the step written last) or after n_steps - 1 moves ->
+    actions (B, A) of the rows; rewards (B, 1), the sum of gamma^k times the (normalised) rewards along the walk; dones (B, 1) of the last step,
+    masked by its timeout; discounts (B, 1), gamma^(steps walked + 1); rows (B) and next_rows (B) int64, the rows of the first and the last
+    step.  n_steps = 1 gives `gather_rows`' bits and discounts = float32(gamma).  A row outside [0, T n_envs) gives NaN and -1."""
+    who = "replay.nstep_rows"
+    for t in (actions, rewards, dones, timeouts):
+        if t is not None:
+            _require_cuda(t, who + ": every argument")
+    _check_rows(who, rows)
+    T, n_envs, A = actions.shape
+    B = rows.shape[0]
+    for t in (actions, rewards, dones, timeouts):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape[:2]) != (T, n_envs)):
+            raise ValueError(who + ": contiguous float32 (T, n_envs, ...) tensors expected")
+    if int(n_steps) != n_steps or not 1 <= int(n_steps) <= T:
+        raise ValueError(f"{who}: n_steps={n_steps} must be an integer in [1, {T}], the steps of the ring")
+    if not 0.0 < float(gamma) <= 1.0:
+        raise ValueError(f"{who}: gamma={gamma} must lie in (0, 1]")
+    if int(newest) != newest or not 0 <= int(newest) < T:
+        raise ValueError(f"{who}: newest={newest} must be a step of the ring, in [0, {T})")
+    dev = actions.device
+    out = [torch.empty(B, A, dtype=torch.float32, device=dev)] + [torch.empty(B, 1, dtype=torch.float32, device=dev) for _ in range(3)]
+    out += [torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2)]
+    L.check(L.lib().m3l_replay_nstep_rows(L.ptr(actions), L.ptr(rewards), L.ptr(dones), L.ptr(timeouts), T, n_envs, A, L.ptr(rows), int(row_shift), B,
+                                          float(reward_scale), float(reward_clip), int(n_steps), float(gamma), int(newest),
+                                          *[L.ptr(t) for t in out], _stream()), "m3l_replay_nstep_rows")
+    return tuple(out)
 
 
 def reward_normalization(env):
@@ -161,6 +223,20 @@ class ReplayBatch(NamedTuple):
     rows: torch.Tensor
 
 
+class NStepReplayBatch(NamedTuple):
+    """One batch of n-step returns (`DeviceReplayBuffer(n_steps > 1)`): `ReplayBatch`'s fields, where rewards are the discounted sums, dones and
+    next_observations those of the last step of each walk; discounts (B, 1) = gamma^(steps walked), what `td_target` takes as `gamma`; next_rows
+    (B) the rows of the last steps."""
+    observations: LoadedObs
+    actions: torch.Tensor
+    next_observations: LoadedObs
+    dones: torch.Tensor
+    rewards: torch.Tensor
+    rows: torch.Tensor
+    discounts: torch.Tensor
+    next_rows: torch.Tensor
+
+
 class DeviceReplayBuffer:
     """The surface `SAC_MAE` uses on SB3's `DictReplayBuffer` — add, sample, size, reset, pos, full — over device memory, plus the single-store
     mode of SB3's plain `ReplayBuffer` (`optimize_memory_usage`: the next observation of step t is the observation of step t + 1).
@@ -176,12 +252,15 @@ class DeviceReplayBuffer:
                     FrameStack wrapper — next_obs[:, :-1] == obs[:, 1:], a constant stack at the first add() and after a `done`, otherwise obs
                     equal to the previous next_obs.  A full ring does not sample its frame_stack - 1 oldest steps, whose history the newest
                     steps overwrote (SB3 would sample them).  The capacity in steps must be at least frame_stack + 1.
+    n_steps, gamma  n_steps > 1: `sample()` returns n-step returns as an `NStepReplayBatch` (the module's docstring has the rule); an integer
+                    from 1 to the capacity in steps, gamma in (0, 1].  n_steps = 1 is the one-step buffer and ignores gamma.  Not with
+                    optimize_memory_usage=True (SB3's rule: the single store has no agreed next observation where a walk ends).
     check_stacking  with frame_dedup: every add() verifies that contract with torch ops on the device and one read-back — it synchronises: for
                     tests and a first run — and raises ValueError naming the key, the environment and the rule.
     """
 
     def __init__(self, buffer_size, n_envs, obs_shapes, obs_dtypes, action_dim, optimize_memory_usage=False, handle_timeout_termination=True,
-                 image_normalization=[0, 1], tactile_normalization=[-1, 1], device="cuda", frame_dedup=False, check_stacking=False):
+                 image_normalization=[0, 1], tactile_normalization=[-1, 1], device="cuda", frame_dedup=False, check_stacking=False, n_steps=1, gamma=0.99):
         self.device = _require_device("DeviceReplayBuffer", device, "replay buffer", "DictReplayBuffer")
         self.n_envs, self.action_dim = int(n_envs), int(action_dim)
         if int(buffer_size) < 1 or self.n_envs < 1 or self.action_dim < 1:
@@ -200,6 +279,14 @@ class DeviceReplayBuffer:
         if self.frame_dedup and self.buffer_size < self.frame_stack + 1:
             raise ValueError(f"DeviceReplayBuffer: frame_dedup=True with frame_stack={self.frame_stack} needs a capacity of at least "
                              f"{self.frame_stack + 1} steps (buffer_size // n_envs is {self.buffer_size})")
+        if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or not 1 <= int(n_steps) <= self.buffer_size:
+            raise ValueError(f"DeviceReplayBuffer: n_steps={n_steps!r} must be an integer from 1 to the capacity in steps ({self.buffer_size})")
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.floating)) or not 0.0 < float(gamma) <= 1.0:
+            raise ValueError(f"DeviceReplayBuffer: gamma={gamma!r} must be a number in (0, 1]")
+        self.n_steps, self.gamma = int(n_steps), float(gamma)
+        if self.n_steps > 1 and self.optimize_memory_usage:
+            raise ValueError("DeviceReplayBuffer: n_steps > 1 needs optimize_memory_usage=False (the single store has no agreed next observation at "
+                             "the step where a walk ends: the slot after it holds the next episode's reset stack or the ring's oldest step)")
         self.observations = self.next_observations = None
         self.frames = self.next_frames = self.ages = None
         self.reset()
@@ -353,7 +440,8 @@ class DeviceReplayBuffer:
     def sample(self, batch_size, env=None, indices=None):
         """`batch_size` transitions drawn uniformly over the valid (step, environment) pairs with one torch.randint on the device (nothing is
         read back), or the pairs of `indices` = (batch_inds, env_indices).  env: a VecNormalize-like object whose reward normalisation is
-        applied (`norm_reward`, `ret_rms.var`, `epsilon`, `clip_reward`), or None for raw rewards."""
+        applied (`norm_reward`, `ret_rms.var`, `epsilon`, `clip_reward`), or None for raw rewards.  With n_steps > 1 the batch is an
+        `NStepReplayBatch`: still three launches — the draw, `nstep_rows`, one gather fed rows and next_rows — and nothing read back."""
         scale, clip = reward_normalization(env)
         first, count = self._valid_steps()
         if count < 1:
@@ -366,6 +454,8 @@ class DeviceReplayBuffer:
                 raise ValueError(f"DeviceReplayBuffer.sample: batch_size={batch_size}")
             # rows relative to the first valid step; the kernels add `shift` modulo T n_envs
             draw, shift = torch.randint(0, count * self.n_envs, (int(batch_size),), device=self.device), first * self.n_envs
+        if self.n_steps > 1:
+            return self._sample_nstep(draw, shift, scale, clip)
         if self.frame_dedup:
             nxt = self.next_frames or {}
             obs, next_obs = gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, draw, nxt.get("image"),
@@ -377,3 +467,16 @@ class DeviceReplayBuffer:
                                         self.image_normalization, self.tactile_normalization, shift)
         actions, rewards, dones, rows = gather_rows(self.actions, self.rewards, self.dones, self.timeouts, draw, scale, clip, shift, return_rows=True)
         return ReplayBatch(obs, actions, next_obs, dones, rewards, rows)
+
+    def _sample_nstep(self, draw, shift, scale, clip):
+        newest = (self.pos - 1) % self.buffer_size
+        actions, rewards, dones, discounts, rows, next_rows = nstep_rows(self.actions, self.rewards, self.dones, self.timeouts, draw, self.n_steps,
+                                                                         self.gamma, newest, scale, clip, shift)
+        if self.frame_dedup:
+            obs, next_obs = gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, draw, self.next_frames.get("image"),
+                                               self.next_frames.get("tactile"), self.image_normalization, self.tactile_normalization, shift,
+                                               next_rows, frame_stack=self.frame_stack)
+        else:
+            obs, next_obs = gather_load(self.observations.get("image"), self.observations.get("tactile"), draw, self.next_observations.get("image"),
+                                        self.next_observations.get("tactile"), self.image_normalization, self.tactile_normalization, shift, next_rows)
+        return NStepReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows)

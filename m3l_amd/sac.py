@@ -16,6 +16,7 @@ the critic's parameters get nothing from it.  The reference lets `actor_loss.bac
 `critic.optimizer.zero_grad()` (:347).  Everything is float32; there is no eager fallback.
 """
 import ctypes as C
+import numbers
 from typing import NamedTuple, Tuple
 
 import torch
@@ -313,7 +314,8 @@ def q_values(params: SACHeadParams, features, actions, target=False, param_grads
 @torch.no_grad()
 def td_target(params: SACHeadParams, next_features, rewards, dones, gamma, ent_coef=None, log_ent_coef=None, noise=None):
     """target_q (B,) = r + (1 - done) * gamma * (min_c q_target_c(x', a') - ent_coef * logp') with (a', logp') = actor(x') (`sac_mae.py:326-335`).
-    One launch, no tape."""
+    One launch, no tape.  gamma: a Python number, or a float32 CUDA tensor of B values, (B,) or (B, 1): one discount per row, the `discounts` of
+    an n-step batch (m3l_sac_td_target_rows; a constant tensor gives the bits of the number)."""
     af, cf = params.actor_flat(), params.critic_flat(True)
     H.require_params(af + cf, "SAC head parameter")
     x = H.features_of(next_features, on_tape=False)
@@ -322,11 +324,24 @@ def td_target(params: SACHeadParams, next_features, rewards, dones, gamma, ent_c
     noise = H.noise_of(noise, B, arch[1], x.device)
     ent, log_ent = _ent_args(ent_coef, log_ent_coef)
     r, dn = _vec(rewards, "rewards", B), _vec(dones, "dones", B)
+    per_row = isinstance(gamma, torch.Tensor)
+    if per_row:
+        _require_cuda(gamma, "gamma")
+        if gamma.dtype != torch.float32 or tuple(gamma.shape) not in ((B,), (B, 1)):
+            raise ValueError(f"gamma: a number, or a float32 tensor of shape ({B},) or ({B}, 1), one discount per row; got {tuple(gamma.shape)} "
+                             f"{gamma.dtype}")
+        gamma = _vec(gamma, "gamma", B)
+    elif not isinstance(gamma, numbers.Real):
+        raise ValueError(f"gamma: a number or a float32 CUDA tensor of {B} values expected, got {type(gamma).__name__}")
     af, cf = [_dev(t) for t in af], [_dev(t) for t in cf]
     d = _desc(arch, actor=af, critic=cf)
     out = torch.empty(B, dtype=torch.float32, device=x.device)
-    L.check(L.lib().m3l_sac_td_target(C.byref(d), B, L.ptr(x), L.ptr(noise), L.ptr(r), L.ptr(dn), float(gamma), 0.0 if ent is None else ent, L.ptr(log_ent),
-                                      L.ptr(out), _stream()), "m3l_sac_td_target")
+    if per_row:
+        L.check(L.lib().m3l_sac_td_target_rows(C.byref(d), B, L.ptr(x), L.ptr(noise), L.ptr(r), L.ptr(dn), L.ptr(gamma), 0.0 if ent is None else ent,
+                                               L.ptr(log_ent), L.ptr(out), _stream()), "m3l_sac_td_target_rows")
+    else:
+        L.check(L.lib().m3l_sac_td_target(C.byref(d), B, L.ptr(x), L.ptr(noise), L.ptr(r), L.ptr(dn), float(gamma), 0.0 if ent is None else ent,
+                                          L.ptr(log_ent), L.ptr(out), _stream()), "m3l_sac_td_target")
     return out
 
 

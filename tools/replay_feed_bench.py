@@ -26,7 +26,19 @@ stacks — compared bit for bit over every batch before the timing — with the 
 `not_slower`: d_obs's median no higher than c_obs's median plus c_obs's own min-max spread; the host time of one add() in the four
 layouts; and store_bytes() of 10^6 transitions at the reference's defaults.
 
-Usage: python tools/replay_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32] [--batches 64,256] [--dedup]   (one JSON line)"""
+--n-steps N measures n-step returns (EXPERIMENTS.md §5.24) on the stores of --dedup, full with pos = 0, with seeded scalars whose dones end
+one walk in a hundred: the scalar launch, replay.nstep_rows(n_steps=N) against replay.gather_rows; the stacked gather fed rows and next_rows
+against the one-list call (equal bytes); the frame-deduplicated gather fed both lists (2 fs frame reads a sample) against the one-list call
+(fs + 1); and `sample()` of a DeviceReplayBuffer over the same stores with n_steps = 1 and N, stacked and frame-deduplicated.  The two-list
+gathers are compared bit for bit with each other over every batch before the timing, and with n_steps = 1 against the one-list calls.
+--parent-lib PATH adds, in the same alternation, the one-list gathers, gather_rows and `sample()` at n_steps = 1 through a second shared library
+— one built from the parent commit — so that the default path of both commits is timed in one run: `*_parent` entries, their bits compared with
+this commit's first, and `*_again` entries, this commit's own calls once more in a later slot of every round.  The spread of a path is the
+largest of its two min-max ranges and of the gap between this commit's two slots (what the place in the alternation alone does to a median);
+`default_path_within_spread`: every median of this commit no further from the parent's than that.
+
+Usage: python tools/replay_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32] [--batches 64,256] [--dedup | --n-steps N]
+(one JSON line)"""
 import argparse
 import json
 import math
@@ -291,6 +303,153 @@ def run_dedup(a):
     return out
 
 
+# ---- n-step returns (--n-steps, EXPERIMENTS.md §5.24)
+def through_library(path):
+    """-> wrap(fn): fn with every m3l_amd call going through the shared library at `path` (the bindings of m3l_amd._lib that it exports)."""
+    import ctypes as C
+    from m3l_amd import _lib as L
+    other = C.CDLL(path)
+    for sym, (res, args) in L._SIGS.items():
+        if hasattr(other, sym):
+            getattr(other, sym).restype, getattr(other, sym).argtypes = res, args
+    own = L.lib()
+
+    def wrap(fn):
+        def call():
+            L._lib = other
+            try:
+                return fn()
+            finally:
+                L._lib = own
+        return call
+    return wrap
+
+
+def resident_buffer(image_dtype, frame_dedup, n_steps, stores, next_stores, ages, dscal):
+    """A full DeviceReplayBuffer (pos = 0) standing on stores that are already on the device."""
+    shapes = {"image": (FS, H, W, 3), "tactile": (FS, 3 * S, TH, TW)}
+    buf = m3l_amd.DeviceReplayBuffer(T * E, E, shapes, {"image": image_dtype, "tactile": np.float32}, A, device=DEV, frame_dedup=frame_dedup,
+                                     n_steps=n_steps, gamma=0.99)
+    if frame_dedup:
+        buf.frames, buf.next_frames, buf.ages = stores, next_stores, ages
+    else:
+        buf.observations, buf.next_observations = stores, next_stores
+    buf.actions, buf.rewards, buf.dones, buf.timeouts = (dscal[k] for k in ("actions", "rewards", "dones", "timeouts"))
+    buf.pos, buf.full = 0, True
+    return buf
+
+
+def run_nstep_config(name, B, n, frames, next_frames, stacked, stacked_next, ages, dscal, a):
+    image_dtype = np.uint8 if name == "u8" else np.float32
+    perm = np.random.default_rng(1).permutation(T).astype(np.int64)
+    d_rows = [torch.from_numpy(perm[i:i + B]).to(DEV) for i in range(0, T - B + 1, B)]
+    scale, newest = float(np.float32(math.sqrt(VAR + EPS))), T - 1
+    sc = (dscal["actions"], dscal["rewards"], dscal["dones"], dscal["timeouts"])
+    walks = [P.nstep_rows(*sc, r, n, 0.99, newest, scale, CLIP) for r in d_rows]
+    d_next = [w[5] for w in walks]
+    moved = float(np.mean([(w[5] != w[4]).double().mean().item() for w in walks]))
+    state = {}
+
+    def nxt(p):
+        i = state.get(p, 0)
+        state[p] = (i + 1) % len(d_rows)
+        return i
+
+    def stacked_call(i, two):
+        return P.gather_load(stacked["image"], stacked["tactile"], d_rows[i], stacked_next["image"], stacked_next["tactile"],
+                             next_rows=d_next[i] if two else None)
+
+    def frames_call(i, two):
+        return P.gather_load_frames(frames["image"], frames["tactile"], ages, d_rows[i], next_frames["image"], next_frames["tactile"],
+                                    next_rows=d_next[i] if two else None, frame_stack=FS)
+
+    def same(x, y, what):
+        for u, v in zip(x, y):
+            for k in u:
+                assert torch.equal(u[k], v[k]), f"{name} B={B}: {what} disagree on {k}"
+    for i in range(len(d_rows)):
+        same(stacked_call(i, True), frames_call(i, True), "the stacked and the deduplicated two-list gathers")
+    one = P.nstep_rows(*sc, d_rows[0], 1, 0.99, newest, scale, CLIP)
+    ref = P.gather_rows(*sc, d_rows[0], scale, CLIP, return_rows=True)
+    assert all(torch.equal(x, y) for x, y in zip(ref, (one[0], one[1], one[2], one[4]))) and torch.equal(one[5], one[4])
+    saved = d_next[0]
+    d_next[0] = one[5]
+    same(stacked_call(0, True), stacked_call(0, False), "the two-list stacked gather with next_rows = rows and the one-list call")
+    same(frames_call(0, True), frames_call(0, False), "the two-list deduplicated gather with next_rows = rows and the one-list call")
+    d_next[0] = saved
+    bufs = {(dedup, k): resident_buffer(image_dtype, dedup, k, frames if dedup else stacked, next_frames if dedup else stacked_next, ages, dscal)
+            for dedup in (False, True) for k in (1, n)}
+    env = type("Env", (), dict(norm_obs=False, norm_reward=True, ret_rms=type("Rms", (), dict(var=VAR)), epsilon=EPS, clip_reward=CLIP))
+    torch.cuda.synchronize()
+    fns = {"rows_gather_rows": lambda: P.gather_rows(*sc, d_rows[nxt("r1")], scale, CLIP, return_rows=True),
+           "rows_nstep_rows": lambda: P.nstep_rows(*sc, d_rows[nxt("rn")], n, 0.99, newest, scale, CLIP),
+           "stacked_one_list": lambda: stacked_call(nxt("s1"), False), "stacked_two_lists": lambda: stacked_call(nxt("s2"), True),
+           "frames_one_list": lambda: frames_call(nxt("f1"), False), "frames_two_lists": lambda: frames_call(nxt("f2"), True)}
+    for (dedup, k), buf in bufs.items():
+        fns[f"sample_{'frames' if dedup else 'stacked'}_n{k}"] = (lambda b: lambda: b.sample(B, env=env))(buf)
+    default_path = ("rows_gather_rows", "stacked_one_list", "frames_one_list", "sample_stacked_n1", "sample_frames_n1")
+    if a.parent_lib:
+        wrap = through_library(a.parent_lib)
+        for p in default_path:
+            fns[p + "_parent"] = wrap(fns[p])
+        for p in default_path:
+            fns[p + "_again"] = (lambda f: lambda: f())(fns[p])
+        state.clear()
+        for p in default_path[:3]:                    # the same batch through both libraries: equal bits
+            state.clear()
+            mine = fns[p]()
+            state.clear()
+            theirs = fns[p + "_parent"]()
+            for x, y in zip(mine, theirs):
+                for k in (x if isinstance(x, dict) else [None]):
+                    assert torch.equal(x[k] if k is not None else x, y[k] if k is not None else y), f"{name} B={B}: {p} differs from the parent library"
+    res = alternate(fns, {p: a.iters for p in fns}, {p: 20 for p in fns}, a.rounds)
+    for p, fn in fns.items():
+        res[p].update(counted(fn))
+    if a.parent_lib:
+        res["default_path_vs_parent"] = {}
+        for p in default_path:
+            mine, theirs, again = res[p], res[p + "_parent"], res[p + "_again"]
+            spread = max(theirs["call_us_min_max"][1] - theirs["call_us_min_max"][0], mine["call_us_min_max"][1] - mine["call_us_min_max"][0],
+                         abs(mine["call_us"] - again["call_us"]))
+            res["default_path_vs_parent"][p] = {"this_us": mine["call_us"], "parent_us": theirs["call_us"], "this_again_us": again["call_us"],
+                                                "spread_us": round(spread, 1), "within_spread": bool(abs(mine["call_us"] - theirs["call_us"]) <= spread)}
+        res["default_path_within_spread"] = all(v["within_spread"] for v in res["default_path_vs_parent"].values())
+    isz = 1 if name == "u8" else 4
+    frame_in = H * W * 3 * isz + 3 * S * TH * TW * 4
+    frame_out = (H * W * 3 + 3 * S * TH * TW) * 4
+    for p, n_read in (("stacked_one_list", 2 * FS), ("stacked_two_lists", 2 * FS), ("frames_one_list", FS + 1), ("frames_two_lists", 2 * FS)):
+        c = res[p]
+        c["bytes_read"], c["bytes_written"] = B * n_read * frame_in, B * 2 * FS * frame_out
+        for key, us in (("", c["call_us"]), ("_best", c["call_us_min_max"][0]), ("_worst", c["call_us_min_max"][1])):
+            tbs = (c["bytes_read"] + c["bytes_written"]) / (us * 1e-6) / 1e12
+            c["tbytes_per_s" + key] = round(tbs, 3)
+            c["share_of_measured_copy_peak" + key] = round(tbs / HBM_COPY_TBS, 3)
+    for num, den in (("rows_nstep_rows", "rows_gather_rows"), ("stacked_two_lists", "stacked_one_list"), ("frames_two_lists", "frames_one_list"),
+                     (f"sample_stacked_n{n}", "sample_stacked_n1"), (f"sample_frames_n{n}", "sample_frames_n1")):
+        res[f"{num}_over_{den}"] = round(res[num]["call_us"] / res[den]["call_us"], 3)
+    res["share_of_walks_that_move"] = round(moved, 4)
+    return res
+
+
+def run_nstep(a):
+    n = a.n_steps
+    ages = torch.full((T, E), FS - 1, dtype=torch.int32, device=DEV)
+    g = np.random.default_rng(2)
+    scal = dict(actions=g.standard_normal((T, E, A)).astype(np.float32), rewards=(3 * g.standard_normal((T, E))).astype(np.float32),
+                dones=(g.random((T, E)) < 0.01).astype(np.float32))
+    scal["timeouts"] = (scal["dones"] * (g.random((T, E)) < 0.5)).astype(np.float32)
+    dscal = {k: torch.from_numpy(v).to(DEV) for k, v in scal.items()}
+    out = {"n_steps": n}
+    for name in a.variants.split(","):
+        frames, next_frames, stacked, stacked_next = dedup_stores(np.uint8 if name == "u8" else np.float32, 0)
+        torch.cuda.synchronize()
+        out[name] = {f"B{B}": run_nstep_config(name, B, n, frames, next_frames, stacked, stacked_next, ages, dscal, a) for B in a.batches}
+        del frames, next_frames, stacked, stacked_next
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5, help="alternating windows per path")
@@ -299,14 +458,18 @@ def main():
     ap.add_argument("--variants", default="u8,f32")
     ap.add_argument("--batches", default="64,256")
     ap.add_argument("--dedup", action="store_true", help="measure the frame-deduplicated store against the stacked one instead of the three paths")
+    ap.add_argument("--n-steps", type=int, default=0, help="measure n-step returns with this n_steps (>= 2) instead of the three paths")
+    ap.add_argument("--parent-lib", default=None, help="with --n-steps: a shared library built from the parent commit, timed on the default path")
     a = ap.parse_args()
+    if a.n_steps and (a.n_steps < 2 or a.dedup):
+        raise SystemExit("replay_feed_bench: --n-steps takes a value of at least 2 and excludes --dedup")
     a.batches = [int(b) for b in a.batches.split(",")]
     if not torch.cuda.is_available():
         raise SystemExit("replay_feed_bench: no GPU")
     out = {"shape": {"T": T, "n_envs": E, "frame_stack": FS, "image": [H, W, 3], "tactile": [3 * S, TH, TW], "B": a.batches, "action_dim": A},
            "hbm_peak_tbytes_per_s": {"float4_copy_measured": HBM_COPY_TBS, "spec": HBM_SPEC_TBS}}
-    if a.dedup:
-        out["frame_dedup"] = run_dedup(a)
+    if a.dedup or a.n_steps:
+        out.update({"n_step": run_nstep(a)} if a.n_steps else {"frame_dedup": run_dedup(a)})
         print(json.dumps(out))
         return
     for name in a.variants.split(","):
