@@ -730,6 +730,13 @@ int m3l_sac_td_target_rows(const m3l_sac_desc* head, int B, const float* x_next,
 /* loss[1] and coef [2, B] = dloss/dq are written; the backward writes dq [2, B] = dloss[0] coef (dloss: device scalar) */
 int m3l_sac_critic_loss_fwd(const float* q, const float* target_q, int B, float* loss, float* coef, void* stream);
 int m3l_sac_critic_loss_bwd(const float* dloss, const float* coef, int B, float* dq, void* stream);
+/* (ABI 415) the critic loss under importance weights, for prioritised replay: weights [B] (NULL: ones),
+ *   loss[1] = 0.5 sum_c mean_r weights[r] (q[c, r] - target_q[r])^2,  coef [2, B] = weights[r] (q[c, r] - target_q[r]) / B,
+ *   td_abs [B] = 0.5 (|q[0, r] - target_q[r]| + |q[1, r] - target_q[r]|): what m3l_replay_per_update takes as td.
+ * The backward is m3l_sac_critic_loss_bwd.  The weight multiplies the difference before the square is taken: weights of ones (or NULL) give the
+ * bits of m3l_sac_critic_loss_fwd in loss and coef. */
+int m3l_sac_critic_loss_w_fwd(const float* q, const float* target_q, const float* weights, int B, float* loss, float* coef, float* td_abs,
+                              void* stream);
 /* loss[1] and coef [3, B] = dloss/dlogp [B] then dloss/dq [2, B] are written; the backward writes dlogp_dq [3, B] in the same order */
 int m3l_sac_actor_loss_fwd(const float* logp, const float* q, int B, float ent_coef, const float* log_ent_coef, float* loss, float* coef, void* stream);
 int m3l_sac_actor_loss_bwd(const float* dloss, const float* coef, int B, float* dlogp_dq, void* stream);
@@ -880,6 +887,52 @@ int m3l_replay_gather_load_frames_rows2(const void* image_frames, const void* im
                                         const void* tactile_next_frames, int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi,
                                         float* const* tactile_out, float* const* tactile_next_out, const int32_t* ages, int T, int n_envs,
                                         int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, int B, void* stream);
+
+/* ---- prioritised replay (ABI 415): proportional prioritised experience replay (Schaul et al. 2016) for the ring above, without a host-side
+ * sum tree and without reading a TD error back.  Neither the reference tree nor SB3 has it: the rule is restated in tests/per_cases.py in
+ * float64, parity unpinned.  N = T n_envs store rows; all arrays f32 on the device:
+ *   mass [N]            priority^alpha of each row, priority = |td| + priority_eps; 0 for a row that must not be sampled
+ *   block_mass [nb]     the sum of the leaves of each run of M3L_PER_BLOCK rows, nb = ceil(N / M3L_PER_BLOCK)
+ *   block_min [nb]      the smallest positive leaf of the run, +inf where it has none
+ *   max_priority [1]    the largest priority seen; it never decreases
+ * A block's sum and minimum are always recomputed from its leaves, in an order that depends on the leaf's place in the block alone: they never
+ * drift and equal leaves give equal bits.  There is no tree and no floating-point atomic; two runs give the same bits.  N is at most
+ * M3L_PER_BLOCK * M3L_PER_MAX_BLOCKS = 2^22 rows: the block prefix of a sample lies in LDS.
+ *
+ * m3l_replay_per_refresh   block_mass and block_min of every block from mass; one launch.
+ * m3l_replay_per_add       what add() does: the n_set rows from first_row (modulo N) take max_priority^alpha, the n_zero rows after them (the
+ *                          steps that left the valid window) 0, then the blocks that range touches are recomputed; two launches.
+ * m3l_replay_per_sample    u [B] in [0, 1), beta, stratified -> rows [B] int64, weights [B]; one launch, a wave per sample.  With every operation
+ *                          a separate f32 round-to-nearest one, in this order:
+ *     1. total = the sum of block_mass, the last entry of the block prefix P (formed in one fixed order)
+ *     2. x_k = (k + u_k) * (total / B) if stratified, else u_k * total
+ *     3. block j = the smallest j with block_mass[j] > 0 and P[j] > x_k
+ *     4. residual = x_k - P[j - 1]  (0 in front of block 0)
+ *     5. leaf i = the smallest i of block j with mass > 0 and p[i] > residual, p the inclusive prefix of the block's leaves
+ *   Where rounding leaves no such leaf, or no such block, the answer is the last leaf, or block, of positive mass.  The prefixes are sums in a
+ *   tree order and under rounding need not be monotone over a run of zeros; the "> 0" of 3 and 5 changes nothing in exact arithmetic and
+ *   guarantees that a row of zero mass is never returned while total > 0.  total == 0: rows are -1 and weights NaN.
+ *     weights[k] = (min over block_min / mass[rows[k]])^beta: the paper's (N P(i))^-beta / max_j w_j, in which N and total cancel
+ *   rows_in [B] not NULL: the rows are these (u may be NULL) and only the weights are formed; a row outside [0, N) or of zero mass gives NaN.
+ * m3l_replay_per_update    rows [B] int64 and td [B] -> mass[rows[b]] = (|td[b]| + priority_eps)^alpha; two launches, nothing read back.
+ *     a non-finite td[b] takes the value max_priority had before the call as its priority
+ *     a row outside [0, N) or of zero mass is skipped (the row is invalid now); its neighbours are untouched
+ *     duplicate rows: the largest priority wins (among equal ones the first entry), by comparison of every entry with every other: no atomic,
+ *     no "last writer"; B is at most M3L_PER_MAX_UPDATE
+ *     max_priority becomes the max of itself and the finite priorities of the entries that were not skipped
+ *     then the blocks of the rows named are recomputed from their leaves; every other block keeps its bits
+ * Errors, nothing written: a NULL argument (u with rows_in, rows_in), N outside [1, 2^22], mass not 16-byte aligned, B < 1, alpha or beta
+ * outside [0, 1], a non-positive or non-finite priority_eps, a range of per_add that does not fit the ring. */
+#define M3L_PER_BLOCK 1024
+#define M3L_PER_MAX_BLOCKS 4096
+#define M3L_PER_MAX_UPDATE 16384
+int m3l_replay_per_refresh(const float* mass, long N, float* block_mass, float* block_min, void* stream);
+int m3l_replay_per_add(float* mass, float* block_mass, float* block_min, const float* max_priority, long N, long first_row, long n_set, long n_zero,
+                       float alpha, void* stream);
+int m3l_replay_per_sample(const float* mass, const float* block_mass, const float* block_min, long N, const float* u, const int64_t* rows_in, int B,
+                          float beta, int stratified, int64_t* rows, float* weights, void* stream);
+int m3l_replay_per_update(float* mass, float* block_mass, float* block_min, float* max_priority, long N, const int64_t* rows, const float* td, int B,
+                          float alpha, float priority_eps, void* stream);
 
 #ifdef __cplusplus
 }

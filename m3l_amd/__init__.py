@@ -12,6 +12,6 @@ from .fusion import DinoCatMAEExtractor, MAEExtractor  # noqa: F401  (reference:
 from .sac import SACHead  # noqa: F401  (reference: the head's part of models/sac_mae.py:303-366; SB3's SACPolicy behind the extractor)
 from .policy import ActorCriticHead  # noqa: F401  (reference: the policy head and loss of models/ppo_mae.py:280-340; SB3's ActorCriticPolicy behind the extractor)
 from .rollout import DeviceRolloutBuffer, LoadedObs, RolloutBatch  # noqa: F401  (reference: the rollout's way to the device, models/ppo_dino_cat_mae.py:25-71,268-332; SB3's DictRolloutBuffer)
-from .replay import DeviceReplayBuffer, NStepReplayBatch, ReplayBatch  # noqa: F401  (reference: `self.replay_buffer.sample` and what follows it, models/sac_mae.py:240,253-260; SB3's DictReplayBuffer)
+from .replay import DeviceReplayBuffer, NStepReplayBatch, PrioritizedReplayBatch, ReplayBatch, per_refresh, per_sample, per_update  # noqa: F401  (reference: `self.replay_buffer.sample` and what follows it, models/sac_mae.py:240,253-260; SB3's DictReplayBuffer)
 
-__all__ = ["VTT", "VTMAE", "Transformer", "DinoVTT", "VTDINO", "DINOHead", "DINOLoss", "KoLeoLoss", "iBOTPatchLoss", "update_moving_average", "DinoAdamW", "WarmupCosineScheduler", "CosineWDSchedule", "DinoV2Frozen", "DinoCatMAEExtractor", "MAEExtractor", "ActorCriticHead", "SACHead", "DeviceRolloutBuffer", "LoadedObs", "RolloutBatch", "DeviceReplayBuffer", "ReplayBatch", "NStepReplayBatch", "vt_load", "M3LError", "LIB_PATH"]
+__all__ = ["VTT", "VTMAE", "Transformer", "DinoVTT", "VTDINO", "DINOHead", "DINOLoss", "KoLeoLoss", "iBOTPatchLoss", "update_moving_average", "DinoAdamW", "WarmupCosineScheduler", "CosineWDSchedule", "DinoV2Frozen", "DinoCatMAEExtractor", "MAEExtractor", "ActorCriticHead", "SACHead", "DeviceRolloutBuffer", "LoadedObs", "RolloutBatch", "DeviceReplayBuffer", "ReplayBatch", "NStepReplayBatch", "PrioritizedReplayBatch", "per_refresh", "per_sample", "per_update", "vt_load", "M3LError", "LIB_PATH"]

@@ -236,6 +236,12 @@ _SIGS = {
     "m3l_replay_nstep_rows": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_i, C.c_float, C.c_float, c_i, C.c_float, c_i, c_p, c_p, c_p,
                                     c_p, c_p, c_p, c_p]),
     "m3l_sac_td_target_rows": (c_i, [C.POINTER(SacDesc), c_i, c_p, c_p, c_p, c_p, c_p, C.c_float, c_p, c_p, c_p]),
+    # prioritised replay (ABI 415): the priority structure's refresh, add, sample and update, and the critic loss under importance weights
+    "m3l_replay_per_refresh": (c_i, [c_p, C.c_long, c_p, c_p, c_p]),
+    "m3l_replay_per_add": (c_i, [c_p, c_p, c_p, c_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_float, c_p]),
+    "m3l_replay_per_sample": (c_i, [c_p, c_p, c_p, C.c_long, c_p, c_p, c_i, C.c_float, c_i, c_p, c_p, c_p]),
+    "m3l_replay_per_update": (c_i, [c_p, c_p, c_p, c_p, C.c_long, c_p, c_p, c_i, C.c_float, C.c_float, c_p]),
+    "m3l_sac_critic_loss_w_fwd": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

@@ -18,6 +18,8 @@
 // n-step returns ("n-step returns" in the header): nstep_rows walks from each sampled step towards newer ones, up to n_steps - 1 of them, and
 // the next observation then belongs to the step the walk ended at: another row than the observation's.  The *_rows2 forms of both gathers
 // take that second row list; their kernels are the ones above with one more select (stacked) or 2 fs single-destination pieces (frames).
+//
+// Prioritised replay ("prioritised replay" in the header): the priority structure, its sampler and its updates are at the end of the file.
 #include <math.h>
 #include <string.h>
 
@@ -432,6 +434,281 @@ int replay_frames_launch(const char* who, const void* image_frames, const void* 
     return 0;
 }
 
+
+// ---- prioritised replay ("prioritised replay" in the header): proportional PER over a two-level structure.  mass [N] holds priority^alpha per
+// store row (0: never sampled), block_mass / block_min [nb] the sum and the smallest positive leaf of each run of M3L_PER_BLOCK rows.  A block's
+// two values are always recomputed from its leaves in an order that depends on nothing but the leaf's place in the block: no drift, and equal
+// leaves give equal bits.  No tree, no float atomics.
+//
+// The sampling rule (restated in float64 in tests/per_cases.py), every operation a separate fp32 round-to-nearest one:
+//   1. total = the sum of block_mass (the last entry of the block prefix P, formed in one fixed order)
+//   2. x_k = (k + u_k) * (total / B) if stratified, else u_k * total
+//   3. block j = the smallest j with block_mass[j] > 0 and P[j] > x_k
+//   4. residual = x_k - P[j - 1] (0 in front of block 0)
+//   5. leaf i = the smallest i of block j with mass > 0 and p[i] > residual, p the inclusive prefix of the block's leaves
+//   where rounding leaves no such leaf / block: the last leaf / block of positive mass.  The prefixes are sums in a tree order, so under
+//   rounding they need not be monotone over a run of zeros; the "> 0" in 3 and 5 keeps a row of zero mass from ever being returned (in exact
+//   arithmetic the prefix grows at positive entries only and the condition changes nothing).
+//   weight = (min over block_min / mass[row])^beta.
+// Everything here is latency-bound: the structure of 10^6 rows is 977 block sums (L2) and one 4 KB leaf block per sample.
+constexpr int PER_BLOCK = M3L_PER_BLOCK;
+constexpr int PER_MAX_BLOCKS = M3L_PER_MAX_BLOCKS;
+constexpr int PER_LANE = PER_BLOCK / 64;         // leaves of one lane when a wave scans a block
+static_assert(PER_BLOCK == 1024 && PER_LANE == 16, "a workgroup of 256 refreshes a block with 4 leaves per thread, a wave scans it with 16 per lane");
+
+__device__ __forceinline__ float per_inf() { return __int_as_float(0x7f800000); }
+
+// inclusive sum over the lanes of a wave, lane l gets entries 0..l (every lane active); separate additions in one fixed order
+__device__ __forceinline__ float per_wave_scan(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(v, o, 64);
+        if (lane >= o) v = __fadd_rn(v, t);
+    }
+    return v;
+}
+
+// block `blk` of mass -> block_mass[blk], block_min[blk]; the whole workgroup of 256 calls it (4 leaves per thread, then a butterfly whose lane 0
+// holds a fixed association of the 64 partial sums, then the four waves in order).  red: 8 floats of LDS
+__device__ __forceinline__ void per_refresh_block(const float* __restrict__ mass, long N, long blk, float* __restrict__ block_mass,
+                                                  float* __restrict__ block_min, float* red) {
+    const long base = blk * PER_BLOCK + 4L * threadIdx.x;
+    float m[4];
+    if (base + 4 <= N) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(mass + base);
+        m[0] = v[0], m[1] = v[1], m[2] = v[2], m[3] = v[3];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m[k] = base + k < N ? mass[base + k] : 0.f;
+    }
+    float s = __fadd_rn(__fadd_rn(m[0], m[1]), __fadd_rn(m[2], m[3])), mn = per_inf();
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (m[k] > 0.f) mn = fminf(mn, m[k]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s = __fadd_rn(s, __shfl_xor(s, o, 64));
+        mn = fminf(mn, __shfl_xor(mn, o, 64));
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = s, red[4 + wave] = mn;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        block_mass[blk] = __fadd_rn(__fadd_rn(red[0], red[1]), __fadd_rn(red[2], red[3]));
+        block_min[blk] = fminf(fminf(red[4], red[5]), fminf(red[6], red[7]));
+    }
+}
+
+// one workgroup per block of the structure
+__global__ void __launch_bounds__(256) per_refresh_all_kernel(const float* __restrict__ mass, long N, float* __restrict__ block_mass,
+                                                              float* __restrict__ block_min) {
+    __shared__ float red[8];
+    per_refresh_block(mass, N, blockIdx.x, block_mass, block_min, red);
+}
+
+// the blocks that the ring range of rows [first, first + len) mod N touches: c1 blocks from b1 (the part up to the ring end), then the blocks
+// from 0 (the wrapped part).  A block in both parts is recomputed twice, to the same bits
+__global__ void __launch_bounds__(256) per_refresh_range_kernel(const float* __restrict__ mass, long N, int b1, int c1, float* __restrict__ block_mass,
+                                                                float* __restrict__ block_min) {
+    __shared__ float red[8];
+    const int g = blockIdx.x;
+    per_refresh_block(mass, N, g < c1 ? b1 + g : g - c1, block_mass, block_min, red);
+}
+
+// add(): n_set rows from `first` (modulo N) take max_priority^alpha, the n_zero rows after them 0
+__global__ void per_add_leaves_kernel(float* __restrict__ mass, long N, long first, long n_set, long n_zero, float alpha,
+                                      const float* __restrict__ max_priority) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_set + n_zero) return;
+    long row = first + i;
+    if (row >= N) row -= N;
+    mass[row] = i < n_set ? powf(max_priority[0], alpha) : 0.f;
+}
+
+// the priority an entry of the batch asks for: |td| + eps, or for a non-finite td the max_priority of before the call
+__device__ __forceinline__ float per_priority(float td, float eps, float old_max) { return isfinite(td) ? __fadd_rn(fabsf(td), eps) : old_max; }
+
+// update, launch 1: entry b writes mass[rows[b]] = priority_b^alpha unless its row is outside [0, N), has zero mass (an invalid row: skipped) or
+// another entry of the same row wins: the larger priority, and among equal ones the smaller b.  Every thread compares its row with the whole
+// batch (tiles of 256 through LDS): B^2 / 64 wave steps, nothing for a SAC batch; no atomics and no "last writer".  mass[r] is read while
+// duplicates may write it: both the old and the new value of a written row are positive and a zero row is never written, so the test holds.
+__global__ void __launch_bounds__(256) per_update_leaves_kernel(float* __restrict__ mass, long N, const int64_t* __restrict__ rows,
+                                                                const float* __restrict__ td, int B, float alpha, float eps,
+                                                                const float* __restrict__ max_priority) {
+    __shared__ int srow[256];                                          // N <= 2^22: a row in range fits 32 bits, any other is -1 here
+    __shared__ float sp[256];
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    const float old_max = max_priority[0];
+    const int64_t r64 = b < B ? rows[b] : -1;
+    const int r = r64 >= 0 && r64 < N ? (int)r64 : -1;
+    const float p = b < B ? per_priority(td[b], eps, old_max) : 0.f;
+    bool win = r >= 0;
+    for (int t0 = 0; t0 < B; t0 += 256) {
+        const int j = t0 + threadIdx.x;
+        const int64_t rj = j < B ? rows[j] : -1;
+        srow[threadIdx.x] = rj >= 0 && rj < N ? (int)rj : -1;
+        sp[threadIdx.x] = j < B ? per_priority(td[j], eps, old_max) : 0.f;
+        __syncthreads();
+        // every lane walks the whole tile with selects, no branch: entry t0 + k beats b when it names the same row with a larger priority, or
+        // with an equal one from further in front (an entry never beats itself: neither holds for k = b - t0)
+        bool lost = false;
+#pragma unroll 8
+        for (int k = 0; k < 256; ++k) {
+            const float pk = sp[k];
+            lost |= (srow[k] == r) & ((pk > p) | ((pk == p) & (t0 + k < b)));
+        }
+        win &= !lost;
+        __syncthreads();
+    }
+    if (win && mass[r] > 0.f) mass[r] = powf(p, alpha);
+}
+
+// update, launch 2: workgroup b < B recomputes the block of rows[b] from its leaves (a block named twice is recomputed twice, to the same
+// bits); workgroup B raises max_priority to the largest finite priority of the entries that were not skipped
+__global__ void __launch_bounds__(256) per_update_blocks_kernel(const float* __restrict__ mass, long N, const int64_t* __restrict__ rows,
+                                                                const float* __restrict__ td, int B, float eps, float* __restrict__ block_mass,
+                                                                float* __restrict__ block_min, float* __restrict__ max_priority) {
+    __shared__ float red[8];
+    if ((int)blockIdx.x < B) {                                         // uniform over the workgroup
+        const int64_t r = rows[blockIdx.x];
+        if (r < 0 || r >= N) return;
+        per_refresh_block(mass, N, (long)(r / PER_BLOCK), block_mass, block_min, red);
+        return;
+    }
+    float mx = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const int64_t r = rows[b];
+        const float t = td[b];
+        if (r >= 0 && r < N && isfinite(t) && mass[r] > 0.f) mx = fmaxf(mx, __fadd_rn(fabsf(t), eps));
+    }
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) max_priority[0] = fmaxf(max_priority[0], fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+}
+
+// four samples per workgroup, a wave each.  The workgroup first forms the block prefix P and the minimum in LDS (thread t takes the blocks
+// [t chunk, (t + 1) chunk), chunk = ceil(nb / 256): a running sum of its own, then an exclusive scan of the 256 thread totals); each wave
+// then looks for its block with ballots over P, 64 blocks a step, and scans that block's leaves, 16 consecutive ones per lane.
+// rows_in: the rows are given and only the weights are formed (a row outside [0, N) or of zero mass: NaN).
+__global__ void __launch_bounds__(256) per_sample_kernel(const float* __restrict__ mass, const float* __restrict__ block_mass,
+                                                         const float* __restrict__ block_min, long N, int nb, const float* __restrict__ u,
+                                                         const int64_t* __restrict__ rows_in, int B, float beta, int stratified,
+                                                         int64_t* __restrict__ rows, float* __restrict__ weights) {
+    __shared__ float P[PER_MAX_BLOCKS], M[PER_MAX_BLOCKS];
+    __shared__ float wtot[4], wmin[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunk = (nb + 255) / 256, j0 = tid * chunk;
+    float s = 0.f, mn = per_inf();
+    for (int c = 0; c < chunk; ++c) {
+        const int j = j0 + c;
+        if (j < nb) {
+            const float m = block_mass[j];
+            s = __fadd_rn(s, m);
+            M[j] = m, P[j] = s;
+            mn = fminf(mn, block_min[j]);
+        }
+    }
+    const float inc = per_wave_scan(s, lane);
+    float exc = __shfl_up(inc, 1, 64);
+    if (lane == 0) exc = 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o, 64));
+    if (lane == 63) wtot[wave] = inc;
+    if (lane == 0) wmin[wave] = mn;
+    __syncthreads();
+    float off = 0.f;
+    for (int w = 0; w < wave; ++w) off = __fadd_rn(off, wtot[w]);
+    off = __fadd_rn(off, exc);
+    for (int c = 0; c < chunk; ++c) {
+        const int j = j0 + c;
+        if (j < nb) P[j] = __fadd_rn(off, P[j]);
+    }
+    __syncthreads();
+    const float total = P[nb - 1], min_mass = fminf(fminf(wmin[0], wmin[1]), fminf(wmin[2], wmin[3]));
+    const int k = blockIdx.x * 4 + wave;
+    if (k >= B) return;                                                 // uniform over the wave; no barrier follows
+    const float nan = __int_as_float(0x7fc00000);
+    long row = -1;
+    if (rows_in) {
+        const int64_t r = rows_in[k];
+        if (r >= 0 && r < N) row = (long)r;
+    } else if (total > 0.f) {
+        const float uk = u[k];
+        const float x = stratified ? __fmul_rn(__fadd_rn((float)k, uk), __fdiv_rn(total, (float)B)) : __fmul_rn(uk, total);
+        int blk = -1;
+        for (int base = 0; base < nb; base += 64) {
+            const int j = base + lane;
+            const unsigned long long hit = __ballot(j < nb && M[j] > 0.f && P[j] > x);
+            if (hit) {
+                blk = base + __ffsll((long long)hit) - 1;
+                break;
+            }
+        }
+        if (blk < 0)
+            for (int base = ((nb - 1) / 64) * 64; base >= 0; base -= 64) {
+                const int j = base + lane;
+                const unsigned long long hit = __ballot(j < nb && M[j] > 0.f);
+                if (hit) {
+                    blk = base + 63 - __clzll((long long)hit);
+                    break;
+                }
+            }
+        if (blk >= 0) {
+            const float res = __fsub_rn(x, blk > 0 ? P[blk - 1] : 0.f);
+            const long base = (long)blk * PER_BLOCK + (long)lane * PER_LANE;
+            float m[PER_LANE];
+            if (base + PER_LANE <= N) {
+#pragma unroll
+                for (int q = 0; q < PER_LANE / 4; ++q) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(mass + base + 4 * q);
+                    m[4 * q] = v[0], m[4 * q + 1] = v[1], m[4 * q + 2] = v[2], m[4 * q + 3] = v[3];
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < PER_LANE; ++i) m[i] = base + i < N ? mass[base + i] : 0.f;
+            }
+            float run = 0.f, pl[PER_LANE];
+#pragma unroll
+            for (int i = 0; i < PER_LANE; ++i) run = __fadd_rn(run, m[i]), pl[i] = run;
+            const float linc = per_wave_scan(run, lane);
+            float lexc = __shfl_up(linc, 1, 64);
+            if (lane == 0) lexc = 0.f;
+            int first = -1, last = -1;
+#pragma unroll
+            for (int i = 0; i < PER_LANE; ++i) {
+                const bool pos = m[i] > 0.f;
+                if (pos) last = i;
+                if (first < 0 && pos && __fadd_rn(lexc, pl[i]) > res) first = i;
+            }
+            unsigned long long hit = __ballot(first >= 0);
+            int src = -1, leaf = -1;
+            if (hit) {
+                src = __ffsll((long long)hit) - 1;
+                leaf = __shfl(first, src, 64);
+            } else if ((hit = __ballot(last >= 0)) != 0) {
+                src = 63 - __clzll((long long)hit);
+                leaf = __shfl(last, src, 64);
+            }
+            if (src >= 0) row = (long)blk * PER_BLOCK + src * PER_LANE + leaf;
+        }
+    }
+    if (lane == 0) {
+        const float m = row >= 0 ? mass[row] : 0.f;
+        if (!(m > 0.f)) row = rows_in ? row : -1;
+        rows[k] = row;
+        weights[k] = m > 0.f ? powf(__fdiv_rn(min_mass, m), beta) : nan;
+    }
+}
+
+int per_args_ok(const char* who, const void* mass, const void* block_mass, const void* block_min, long N) {
+    M3L_CHECK(mass && block_mass && block_min, "%s: NULL argument", who);
+    M3L_CHECK(N >= 1 && N <= (long)M3L_PER_BLOCK * M3L_PER_MAX_BLOCKS, "%s: N=%ld outside [1, %ld], the rows the block prefix holds", who, N,
+              (long)M3L_PER_BLOCK * M3L_PER_MAX_BLOCKS);
+    M3L_CHECK(gather_aligned(mass, 16), "%s: mass is not 16-byte aligned", who);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -506,6 +783,56 @@ int m3l_replay_nstep_rows(const float* actions, const float* rewards, const floa
     replay_nstep_rows_kernel<<<cdiv((long)B * (A + 1), 256), 256, 0, (hipStream_t)stream>>>(
         actions, rewards, dones, timeouts, T, n_envs, A, rows, row_shift, B, reward_scale, reward_clip, n_steps, gamma, newest, actions_out,
         rewards_out, dones_out, discounts_out, rows_out, next_rows_out);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_replay_per_refresh(const float* mass, long N, float* block_mass, float* block_min, void* stream) {
+    if (per_args_ok("replay_per_refresh", mass, block_mass, block_min, N)) return 1;
+    per_refresh_all_kernel<<<cdiv(N, PER_BLOCK), 256, 0, (hipStream_t)stream>>>(mass, N, block_mass, block_min);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_replay_per_add(float* mass, float* block_mass, float* block_min, const float* max_priority, long N, long first_row, long n_set, long n_zero,
+                       float alpha, void* stream) {
+    if (per_args_ok("replay_per_add", mass, block_mass, block_min, N)) return 1;
+    M3L_CHECK(max_priority, "replay_per_add: NULL argument");
+    M3L_CHECK(first_row >= 0 && first_row < N && n_set >= 1 && n_zero >= 0 && n_set + n_zero <= N,
+              "replay_per_add: first_row=%ld n_set=%ld n_zero=%ld with N=%ld", first_row, n_set, n_zero, N);
+    M3L_CHECK(alpha >= 0.f && alpha <= 1.f, "replay_per_add: alpha=%g outside [0, 1]", (double)alpha);
+    const long len = n_set + n_zero, end1 = first_row + len < N ? first_row + len : N, wrapped = first_row + len - N;
+    const int b1 = (int)(first_row / PER_BLOCK), c1 = (int)((end1 - 1) / PER_BLOCK) - b1 + 1, c2 = wrapped > 0 ? (int)((wrapped - 1) / PER_BLOCK) + 1 : 0;
+    per_add_leaves_kernel<<<cdiv(len, 256), 256, 0, (hipStream_t)stream>>>(mass, N, first_row, n_set, n_zero, alpha, max_priority);
+    M3L_LAUNCH_CHECK();
+    per_refresh_range_kernel<<<c1 + c2, 256, 0, (hipStream_t)stream>>>(mass, N, b1, c1, block_mass, block_min);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_replay_per_sample(const float* mass, const float* block_mass, const float* block_min, long N, const float* u, const int64_t* rows_in, int B,
+                          float beta, int stratified, int64_t* rows, float* weights, void* stream) {
+    if (per_args_ok("replay_per_sample", mass, block_mass, block_min, N)) return 1;
+    M3L_CHECK(B >= 1, "replay_per_sample: B=%d", B);
+    M3L_CHECK((u || rows_in) && rows && weights, "replay_per_sample: NULL argument (u may be NULL only with rows_in)");
+    M3L_CHECK(beta >= 0.f && beta <= 1.f, "replay_per_sample: beta=%g outside [0, 1]", (double)beta);
+    per_sample_kernel<<<cdiv(B, 4), 256, 0, (hipStream_t)stream>>>(mass, block_mass, block_min, N, cdiv(N, PER_BLOCK), u, rows_in, B, beta,
+                                                                   stratified != 0, rows, weights);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_replay_per_update(float* mass, float* block_mass, float* block_min, float* max_priority, long N, const int64_t* rows, const float* td, int B,
+                          float alpha, float priority_eps, void* stream) {
+    if (per_args_ok("replay_per_update", mass, block_mass, block_min, N)) return 1;
+    M3L_CHECK(max_priority && rows && td, "replay_per_update: NULL argument");
+    M3L_CHECK(B >= 1 && B <= M3L_PER_MAX_UPDATE, "replay_per_update: B=%d outside [1, %d] (every entry is compared with every other)", B,
+              M3L_PER_MAX_UPDATE);
+    M3L_CHECK(alpha >= 0.f && alpha <= 1.f, "replay_per_update: alpha=%g outside [0, 1]", (double)alpha);
+    M3L_CHECK(priority_eps > 0.f && isfinite(priority_eps), "replay_per_update: priority_eps=%g must be positive and finite", (double)priority_eps);
+    per_update_leaves_kernel<<<cdiv(B, 256), 256, 0, (hipStream_t)stream>>>(mass, N, rows, td, B, alpha, priority_eps, max_priority);
+    M3L_LAUNCH_CHECK();
+    per_update_blocks_kernel<<<B + 1, 256, 0, (hipStream_t)stream>>>(mass, N, rows, td, B, priority_eps, block_mass, block_min, max_priority);
     M3L_LAUNCH_CHECK();
     return 0;
 }

@@ -259,6 +259,29 @@ __global__ __launch_bounds__(256) void sac_critic_loss_kernel(const float* __res
     if (threadIdx.x == 0) loss[0] = 0.5f * (s0 * invB + s1 * invB);
 }
 
+// one workgroup, for prioritised replay.  loss = 0.5 sum_c mean_r w[r] (q[c, r] - t[r])^2;  coef [2, B] = dloss / dq = w[r] d / B;
+// td_abs [B] = 0.5 (|d_0| + |d_1|), the priorities' input.  w NULL: 1.  The weight multiplies d before the square is taken, so with w = 1
+// every operation is the one of sac_critic_loss_kernel and the bits are its bits.
+__global__ __launch_bounds__(256) void sac_critic_loss_w_kernel(const float* __restrict__ q, const float* __restrict__ t, const float* __restrict__ w,
+                                                                int B, float* __restrict__ loss, float* __restrict__ coef,
+                                                                float* __restrict__ td_abs) {
+    __shared__ float red[4];
+    const float invB = 1.f / (float)B;
+    float s0 = 0.f, s1 = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) {
+        const float d0 = q[r] - t[r], d1 = q[B + r] - t[r], wr = w ? w[r] : 1.f;
+        const float wd0 = wr * d0, wd1 = wr * d1;
+        s0 += wd0 * d0;
+        s1 += wd1 * d1;
+        coef[r] = wd0 * invB;
+        coef[B + r] = wd1 * invB;
+        td_abs[r] = 0.5f * (fabsf(d0) + fabsf(d1));
+    }
+    s0 = ph_block_sum(s0, red);
+    s1 = ph_block_sum(s1, red);
+    if (threadIdx.x == 0) loss[0] = 0.5f * (s0 * invB + s1 * invB);
+}
+
 // one workgroup.  loss = mean_r (ent logp[r] - min_c q[c, r]);  coef [3, B]: dloss / dlogp, then dloss / dq [2, B] (the smaller critic takes it,
 // critic 0 when they are equal)
 __global__ __launch_bounds__(256) void sac_actor_loss_kernel(const float* __restrict__ logp, const float* __restrict__ q, int B, float ent_coef,
@@ -510,6 +533,17 @@ int m3l_sac_critic_loss_fwd(const float* q, const float* target_q, int B, float*
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("sac_critic_loss_fwd", B, 0, 0, 8.0 * B, st, 20.0 * B);
     sac_critic_loss_kernel<<<1, 256, 0, st>>>(q, target_q, B, loss, coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_critic_loss_w_fwd(const float* q, const float* target_q, const float* weights, int B, float* loss, float* coef, float* td_abs,
+                              void* stream) {
+    M3L_CHECK(B >= 1, "sac_critic_loss_w_fwd: B=%d (B >= 1)", B);
+    M3L_CHECK(q && target_q && loss && coef && td_abs, "sac_critic_loss_w_fwd: null argument (weights may be NULL: ones)");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_critic_loss_w_fwd", B, 0, 0, 14.0 * B, st, 28.0 * B);
+    sac_critic_loss_w_kernel<<<1, 256, 0, st>>>(q, target_q, weights, B, loss, coef, td_abs);
     M3L_LAUNCH_CHECK();
     return 0;
 }

@@ -15,7 +15,7 @@ seam (what `get(indices=...)` is for the rollout).  A sample is three launches: 
 
 SB3 is not in the reference tree: the ring (`add`, `pos`, `full`), the single-store mode (`optimize_memory_usage`), the timeout mask and
 `VecNormalize.normalize_reward` are restated here and in tests/replay_cases.py (parity unpinned).  Not covered: `save_replay_buffer` pickling,
-HER, prioritised sampling, observation normalisation (`norm_obs`).
+HER, observation normalisation (`norm_obs`).
 
 `n_steps=n > 1` gives n-step returns (SB3's `NStepReplayBuffer` / `SAC(n_steps=)` from 2.7, restated in tests/nstep_cases.py, parity unpinned).
 From a sampled (t, e) the walk goes towards newer steps and ends at `last = (t + k*) % T`, k* the smallest k in [0, n - 1] at which
@@ -33,6 +33,21 @@ takes the per-row discount.  The single-store mode is refused, as SB3 refuses it
 newest frame of each observation, `ages` says how far back a step's stack reaches into its episode, and `gather_load_frames` puts both stacks of
 a sample together from fs + 1 frames (m3l_replay_gather_load_frames).  At the reference's shapes 10^6 transitions take 73.8 GB instead of
 295 GB.  The wrapper and the vec-env's auto-reset are restated in tests/replay_frame_cases.py (parity unpinned).
+
+`prioritized=True` gives proportional prioritised replay (Schaul et al. 2016; neither the reference tree nor SB3 has it: restated in float64 in
+tests/per_cases.py, parity unpinned) without a host-side sum tree and without reading a TD error back.  `mass` (T, n_envs) holds
+priority^alpha per row, priority = |td| + priority_eps, and 0 for every row outside `_valid_steps()`; `block_mass` / `block_min` hold the sum
+and the smallest positive leaf of each run of PER_BLOCK rows, always recomputed from the leaves (no drift, no float atomics); `max_priority`
+starts at 1 and never decreases.  add() gives the new step max_priority^alpha and zeroes the steps that left the valid window (two launches).
+`sample()`: total = sum(block_mass); x_k = (k + u_k) * (total / B) (stratified, as in the paper); the block is the first whose inclusive
+prefix exceeds x_k, the row the first leaf of it whose inclusive prefix exceeds the rest of x_k, where rounding leaves none the last of positive
+mass: a row of zero mass is never returned.  weights = (min mass / mass[row])^beta.  `update_priorities(rows, td)`: a non-finite td takes the
+max_priority of before the call, a row of zero mass or outside the ring is skipped, of duplicate rows the largest priority wins.  The loop:
+
+    batch = buffer.sample(batch_size, env=vec_normalize_env, beta=beta_t)                       # a PrioritizedReplayBatch
+    target_q = head.td_target(extractor(batch.next_observations), batch.rewards, batch.dones, batch.discounts, ...)
+    critic_loss, td = head.critic_loss(features, batch.actions, target_q, weights=batch.weights, return_td_errors=True)
+    buffer.update_priorities(batch.rows, td)
 """
 import math
 from typing import NamedTuple
@@ -195,6 +210,105 @@ def nstep_rows(actions, rewards, dones, timeouts, rows, n_steps, gamma, newest, 
     return tuple(out)
 
 
+PER_BLOCK = 1024                        # M3L_PER_BLOCK: rows per block of the priority structure
+PER_MAX_ROWS = PER_BLOCK * 4096         # M3L_PER_BLOCK * M3L_PER_MAX_BLOCKS: the rows whose block prefix fits the sampler's LDS
+PER_MAX_UPDATE = 16384                  # M3L_PER_MAX_UPDATE: entries of one per_update
+
+
+def _per_blocks(n_rows):
+    return (int(n_rows) + PER_BLOCK - 1) // PER_BLOCK
+
+
+def _check_per(who, mass, block_mass=None, block_min=None, max_priority=None):
+    """The arrays of the priority structure -> the number of rows.  block_mass / block_min / max_priority are checked when given."""
+    _require_cuda(mass, who + ": mass")
+    if mass.dtype != torch.float32 or not mass.is_contiguous() or mass.numel() < 1:
+        raise ValueError(f"{who}: mass must be a non-empty contiguous float32 tensor")
+    n = mass.numel()
+    if n > PER_MAX_ROWS:
+        raise ValueError(f"{who}: {n} rows; the priority structure holds at most {PER_MAX_ROWS} (PER_BLOCK = {PER_BLOCK} rows times 4096 blocks)")
+    for name, t, count in (("block_mass", block_mass, _per_blocks(n)), ("block_min", block_min, _per_blocks(n)), ("max_priority", max_priority, 1)):
+        if t is not None:
+            _require_cuda(t, f"{who}: {name}")
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count or t.device != mass.device:
+                raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of {count} value(s) on mass's device")
+    return n
+
+
+def _check_unit(who, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0.0 <= float(v) <= 1.0:
+        raise ValueError(f"{who}: {name}={v!r} must be a number in [0, 1]")
+    return float(v)
+
+
+def _check_eps(who, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not (float(v) > 0.0 and math.isfinite(float(v))):
+        raise ValueError(f"{who}: priority_eps={v!r} must be a positive finite number")
+    return float(v)
+
+
+def per_refresh(mass, block_mass=None, block_min=None):
+    """mass (any shape, N = T n_envs float32 values: priority^alpha per store row, 0 for a row that is not sampled) -> (block_mass, block_min),
+    (ceil(N / PER_BLOCK),) each: the sum and the smallest positive leaf (+inf: none) of every block, recomputed from the leaves in one launch
+    (m3l_replay_per_refresh).  block_mass / block_min: written in place when given."""
+    who = "replay.per_refresh"
+    n = _check_per(who, mass, block_mass, block_min)
+    if block_mass is None:
+        block_mass = torch.empty(_per_blocks(n), dtype=torch.float32, device=mass.device)
+    if block_min is None:
+        block_min = torch.empty(_per_blocks(n), dtype=torch.float32, device=mass.device)
+    L.check(L.lib().m3l_replay_per_refresh(L.ptr(mass), n, L.ptr(block_mass), L.ptr(block_min), _stream()), "m3l_replay_per_refresh")
+    return block_mass, block_min
+
+
+def per_sample(mass, block_mass, block_min, u, beta=0.4, stratified=True, rows=None):
+    """The proportional draw of prioritised replay, one launch (m3l_replay_per_sample): u (B) float32 in [0, 1) -> rows (B) int64, weights (B, 1).
+    total = sum(block_mass); x_k = (k + u_k) * (total / B) if stratified, else u_k * total; the block is the first whose inclusive prefix exceeds
+    x_k, the row the first leaf of that block whose inclusive prefix exceeds what is left of x_k; where rounding leaves none, the last of
+    positive mass.  A row of zero mass is never returned while total > 0 (total == 0: rows -1, weights NaN).
+    weights = (min positive mass / mass[row])^beta.  rows (B) int64: those rows are taken as they are (u may be None) and only their weights
+    are formed; NaN for a row outside the structure or of zero mass."""
+    who = "replay.per_sample"
+    n = _check_per(who, mass, block_mass, block_min)
+    beta = _check_unit(who, "beta", beta)
+    if rows is not None:
+        _check_rows(who, rows)
+        B = rows.shape[0]
+    if u is not None:
+        _require_cuda(u, who + ": u")
+        if u.dtype != torch.float32 or u.dim() != 1 or not u.is_contiguous() or (rows is not None and u.shape[0] != B):
+            raise ValueError(f"{who}: u must be a contiguous 1-D float32 tensor" + (" of rows' length" if rows is not None else ""))
+        B = u.shape[0]
+    elif rows is None:
+        raise ValueError(f"{who}: neither u nor rows")
+    if B < 1:
+        raise ValueError(f"{who}: an empty batch")
+    out = torch.empty(B, dtype=torch.int64, device=mass.device)
+    weights = torch.empty(B, 1, dtype=torch.float32, device=mass.device)
+    L.check(L.lib().m3l_replay_per_sample(L.ptr(mass), L.ptr(block_mass), L.ptr(block_min), n, L.ptr(u), L.ptr(rows), B, beta, int(bool(stratified)),
+                                          L.ptr(out), L.ptr(weights), _stream()), "m3l_replay_per_sample")
+    return out, weights
+
+
+def per_update(mass, block_mass, block_min, max_priority, rows, td, alpha=0.6, priority_eps=1e-6):
+    """mass[rows[b]] = (|td[b]| + priority_eps)^alpha in place, two launches and nothing read back (m3l_replay_per_update).  rows (B) int64, td
+    (B) or (B, 1) float32.  A non-finite td takes the max_priority of before the call as its priority; a row outside the structure or of zero
+    mass is skipped; of duplicate rows the largest priority wins; max_priority (1) becomes the max of itself and the finite priorities that
+    were applied; the blocks of the rows named are then recomputed from their leaves."""
+    who = "replay.per_update"
+    n = _check_per(who, mass, block_mass, block_min, max_priority)
+    alpha, eps = _check_unit(who, "alpha", alpha), _check_eps(who, priority_eps)
+    _check_rows(who, rows)
+    _require_cuda(td, who + ": td")
+    B = rows.shape[0]
+    if td.dtype != torch.float32 or tuple(td.shape) not in ((B,), (B, 1)) or not td.is_contiguous():
+        raise ValueError(f"{who}: td must be a contiguous float32 tensor of shape ({B},) or ({B}, 1)")
+    if not 1 <= B <= PER_MAX_UPDATE:
+        raise ValueError(f"{who}: {B} entries; one update takes from 1 to {PER_MAX_UPDATE} (every entry is compared with every other)")
+    L.check(L.lib().m3l_replay_per_update(L.ptr(mass), L.ptr(block_mass), L.ptr(block_min), L.ptr(max_priority), n, L.ptr(rows), L.ptr(td), B, alpha,
+                                          eps, _stream()), "m3l_replay_per_update")
+
+
 def reward_normalization(env):
     """(scale, clip) of `VecNormalize.normalize_reward` for a duck-typed env — clip(r / sqrt(ret_rms.var + epsilon), -clip_reward, clip_reward),
     the scale formed in double and rounded to float32 once — or (0.0, 0.0) for raw rewards (env None or norm_reward false).  A few Python
@@ -237,6 +351,21 @@ class NStepReplayBatch(NamedTuple):
     next_rows: torch.Tensor
 
 
+class PrioritizedReplayBatch(NamedTuple):
+    """One batch of `DeviceReplayBuffer(prioritized=True)`: `NStepReplayBatch`'s fields (with n_steps = 1: discounts = float32(gamma) and
+    next_rows == rows) plus weights (B, 1), the importance weights (min mass / mass[row])^beta that `critic_loss(..., weights=)` takes.  `rows` is
+    what `update_priorities` takes back."""
+    observations: LoadedObs
+    actions: torch.Tensor
+    next_observations: LoadedObs
+    dones: torch.Tensor
+    rewards: torch.Tensor
+    rows: torch.Tensor
+    discounts: torch.Tensor
+    next_rows: torch.Tensor
+    weights: torch.Tensor
+
+
 class DeviceReplayBuffer:
     """The surface `SAC_MAE` uses on SB3's `DictReplayBuffer` — add, sample, size, reset, pos, full — over device memory, plus the single-store
     mode of SB3's plain `ReplayBuffer` (`optimize_memory_usage`: the next observation of step t is the observation of step t + 1).
@@ -255,12 +384,19 @@ class DeviceReplayBuffer:
     n_steps, gamma  n_steps > 1: `sample()` returns n-step returns as an `NStepReplayBatch` (the module's docstring has the rule); an integer
                     from 1 to the capacity in steps, gamma in (0, 1].  n_steps = 1 is the one-step buffer and ignores gamma.  Not with
                     optimize_memory_usage=True (SB3's rule: the single store has no agreed next observation where a walk ends).
+    prioritized     proportional prioritised replay (the module's docstring has the rule): `sample()` draws rows in proportion to `mass` and
+                    returns a `PrioritizedReplayBatch`, `update_priorities(rows, td_errors)` writes the new priorities.  alpha in [0, 1] is the
+                    exponent of the priorities, beta in [0, 1] the default exponent of the weights (`sample(beta=)` overrides it), priority_eps
+                    > 0 is added to |td|.  `mass` (T, n_envs), `block_mass`, `block_min` and `max_priority` (1) live on the device; at most
+                    PER_MAX_ROWS = 2^22 transitions.  With every combination of frame_dedup, n_steps and optimize_memory_usage that is allowed
+                    without it.  False: the buffer has none of these arrays and launches none of these kernels.
     check_stacking  with frame_dedup: every add() verifies that contract with torch ops on the device and one read-back — it synchronises: for
                     tests and a first run — and raises ValueError naming the key, the environment and the rule.
     """
 
     def __init__(self, buffer_size, n_envs, obs_shapes, obs_dtypes, action_dim, optimize_memory_usage=False, handle_timeout_termination=True,
-                 image_normalization=[0, 1], tactile_normalization=[-1, 1], device="cuda", frame_dedup=False, check_stacking=False, n_steps=1, gamma=0.99):
+                 image_normalization=[0, 1], tactile_normalization=[-1, 1], device="cuda", frame_dedup=False, check_stacking=False, n_steps=1, gamma=0.99,
+                 prioritized=False, alpha=0.6, beta=0.4, priority_eps=1e-6):
         self.device = _require_device("DeviceReplayBuffer", device, "replay buffer", "DictReplayBuffer")
         self.n_envs, self.action_dim = int(n_envs), int(action_dim)
         if int(buffer_size) < 1 or self.n_envs < 1 or self.action_dim < 1:
@@ -287,8 +423,16 @@ class DeviceReplayBuffer:
         if self.n_steps > 1 and self.optimize_memory_usage:
             raise ValueError("DeviceReplayBuffer: n_steps > 1 needs optimize_memory_usage=False (the single store has no agreed next observation at "
                              "the step where a walk ends: the slot after it holds the next episode's reset stack or the ring's oldest step)")
+        self.prioritized = bool(prioritized)
+        self.alpha, self.beta = _check_unit("DeviceReplayBuffer", "alpha", alpha), _check_unit("DeviceReplayBuffer", "beta", beta)
+        self.priority_eps = _check_eps("DeviceReplayBuffer", priority_eps)
+        if self.prioritized and self.buffer_size * self.n_envs > PER_MAX_ROWS:
+            raise ValueError(f"DeviceReplayBuffer: prioritized=True holds at most {PER_MAX_ROWS} transitions (PER_BLOCK = {PER_BLOCK} rows times 4096 "
+                             f"blocks, the block prefix a sample keeps on chip); {self.buffer_size} steps of {self.n_envs} environments are "
+                             f"{self.buffer_size * self.n_envs}")
         self.observations = self.next_observations = None
         self.frames = self.next_frames = self.ages = None
+        self.mass = self.block_mass = self.block_min = self.max_priority = None
         self.reset()
 
     # ---- memory
@@ -298,11 +442,14 @@ class DeviceReplayBuffer:
         obs = per_step * self.buffer_size
         nxt = 0 if self.optimize_memory_usage else obs
         scalars = 4 * self.buffer_size * self.n_envs * (self.action_dim + 2 + int(self.handle_timeout_termination) + int(frame_dedup))
+        if self.prioritized:        # mass, block_mass, block_min, max_priority
+            scalars += 4 * (self.buffer_size * self.n_envs + 2 * _per_blocks(self.buffer_size * self.n_envs) + 1)
         return {"observations": obs, "next_observations": nxt, "scalars": scalars, "total": obs + nxt + scalars}
 
     def store_bytes(self):
         """Bytes of the stores, before or after allocation: {'observations', 'next_observations' (0 in the single-store mode), 'scalars', 'total'}.
-        With frame_dedup the first two are the frame stores and 'scalars' counts the 4 bytes per (step, environment) of `ages`."""
+        With frame_dedup the first two are the frame stores and 'scalars' counts the 4 bytes per (step, environment) of `ages`; with prioritized
+        it counts `mass`, `block_mass`, `block_min` and `max_priority`."""
         return self._store_bytes(self.frame_dedup)
 
     def _allocate(self):
@@ -330,6 +477,12 @@ class DeviceReplayBuffer:
         self.rewards = torch.empty(T, E, dtype=torch.float32, device=dev)
         self.dones = torch.empty(T, E, dtype=torch.float32, device=dev)
         self.timeouts = torch.empty(T, E, dtype=torch.float32, device=dev) if self.handle_timeout_termination else None
+        if self.prioritized:
+            self.mass = torch.zeros(T, E, dtype=torch.float32, device=dev)
+            self.block_mass = torch.empty(_per_blocks(T * E), dtype=torch.float32, device=dev)
+            self.block_min = torch.empty(_per_blocks(T * E), dtype=torch.float32, device=dev)
+            self.max_priority = torch.ones(1, dtype=torch.float32, device=dev)
+            per_refresh(self.mass, self.block_mass, self.block_min)
 
     # ---- filling
     def reset(self):
@@ -338,6 +491,10 @@ class DeviceReplayBuffer:
         self._age = np.zeros(self.n_envs, dtype=np.int32)
         self._episode_start = np.ones(self.n_envs, dtype=bool)
         self._last_next_obs = None
+        if self.mass is not None:           # prioritized: no row can be sampled, max_priority back to 1
+            self.mass.zero_()
+            per_refresh(self.mass, self.block_mass, self.block_min)
+            self.max_priority.fill_(1.0)
 
     def size(self):
         return self.buffer_size if self.full else self.pos
@@ -368,6 +525,19 @@ class DeviceReplayBuffer:
         self.pos += 1
         if self.pos == T:
             self.full, self.pos = True, 0
+        if self.prioritized:
+            self._add_priorities(p)
+
+    def _add_priorities(self, p):
+        """prioritized: the step just written takes max_priority^alpha in every environment, and the steps after it that a full ring does not
+        sample (`_valid_steps`: the slot the newest next observation lies in, the frame_stack - 1 steps whose history is gone) take 0 — they
+        follow step p in the ring, so it is one range of rows — then the blocks that range touches are recomputed (m3l_replay_per_add: two
+        launches)."""
+        skip = int(self.optimize_memory_usage) + (self.frame_stack - 1 if self.frame_dedup else 0)
+        n_zero = skip * self.n_envs if self.full else 0
+        L.check(L.lib().m3l_replay_per_add(L.ptr(self.mass), L.ptr(self.block_mass), L.ptr(self.block_min), L.ptr(self.max_priority),
+                                           self.buffer_size * self.n_envs, p * self.n_envs, self.n_envs, n_zero, self.alpha, _stream()),
+                "m3l_replay_per_add")
 
     _STACKING_RULES = ("next_obs[:, :-1] == obs[:, 1:]", "all frames of obs are equal at an episode's first step",
                        "obs equals the previous add()'s next_obs")
@@ -437,16 +607,24 @@ class DeviceReplayBuffer:
             raise ValueError(f"DeviceReplayBuffer.sample: indices name environments outside [0, {self.n_envs})")
         return (t * self.n_envs + e).to(self.device)
 
-    def sample(self, batch_size, env=None, indices=None):
+    def sample(self, batch_size, env=None, indices=None, beta=None, u=None):
         """`batch_size` transitions drawn uniformly over the valid (step, environment) pairs with one torch.randint on the device (nothing is
         read back), or the pairs of `indices` = (batch_inds, env_indices).  env: a VecNormalize-like object whose reward normalisation is
         applied (`norm_reward`, `ret_rms.var`, `epsilon`, `clip_reward`), or None for raw rewards.  With n_steps > 1 the batch is an
-        `NStepReplayBatch`: still three launches — the draw, `nstep_rows`, one gather fed rows and next_rows — and nothing read back."""
+        `NStepReplayBatch`: still three launches — the draw, `nstep_rows`, one gather fed rows and next_rows — and nothing read back.
+        prioritized: the rows are drawn in proportion to `mass` from u, `batch_size` uniform numbers of one torch.rand on the device or the
+        injected float32 tensor `u` (the parity seam), with weights of exponent `beta` (None: the buffer's) — four launches: the draw,
+        `per_sample`, `nstep_rows`, the gather — and the batch is a `PrioritizedReplayBatch`; with `indices` the rows are those and the
+        weights are still formed."""
+        if not self.prioritized and (beta is not None or u is not None):
+            raise ValueError("DeviceReplayBuffer.sample: beta= and u= belong to prioritized=True")
         scale, clip = reward_normalization(env)
         first, count = self._valid_steps()
         if count < 1:
             raise ValueError("DeviceReplayBuffer.sample: the buffer is empty" if self.size() == 0 else
                              "DeviceReplayBuffer.sample: a full single-store buffer of one step holds no transition")
+        if self.prioritized:
+            return self._sample_prioritized(batch_size, indices, beta, u, scale, clip)
         if indices is not None:
             draw, shift = self._injected(indices), 0
         else:
@@ -480,3 +658,40 @@ class DeviceReplayBuffer:
             obs, next_obs = gather_load(self.observations.get("image"), self.observations.get("tactile"), draw, self.next_observations.get("image"),
                                         self.next_observations.get("tactile"), self.image_normalization, self.tactile_normalization, shift, next_rows)
         return NStepReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows)
+
+    # ---- prioritised replay
+    def _sample_prioritized(self, batch_size, indices, beta, u, scale, clip):
+        beta = self.beta if beta is None else _check_unit("DeviceReplayBuffer.sample", "beta", beta)
+        if indices is not None:
+            if u is not None:
+                raise ValueError("DeviceReplayBuffer.sample: indices and u both name the rows")
+            rows, weights = per_sample(self.mass, self.block_mass, self.block_min, None, beta, rows=self._injected(indices))
+        else:
+            if u is None:
+                if int(batch_size) < 1:
+                    raise ValueError(f"DeviceReplayBuffer.sample: batch_size={batch_size}")
+                u = torch.rand(int(batch_size), dtype=torch.float32, device=self.device)
+            rows, weights = per_sample(self.mass, self.block_mass, self.block_min, u, beta)
+        newest = (self.pos - 1) % self.buffer_size
+        actions, rewards, dones, discounts, rows, next_rows = nstep_rows(self.actions, self.rewards, self.dones, self.timeouts, rows, self.n_steps,
+                                                                         self.gamma, newest, scale, clip)
+        second = next_rows if self.n_steps > 1 else None        # n_steps = 1: next_rows == rows, and the one-list gathers are the default buffer's
+        if self.frame_dedup:
+            nxt = self.next_frames or {}
+            obs, next_obs = gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, rows, nxt.get("image"),
+                                               nxt.get("tactile"), self.image_normalization, self.tactile_normalization, 0, second,
+                                               frame_stack=self.frame_stack)
+        else:
+            nxt = self.next_observations or {}
+            obs, next_obs = gather_load(self.observations.get("image"), self.observations.get("tactile"), rows, nxt.get("image"), nxt.get("tactile"),
+                                        self.image_normalization, self.tactile_normalization, 0, second)
+        return PrioritizedReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows, weights)
+
+    def update_priorities(self, rows, td_errors):
+        """The priorities of the sampled `rows` (B) int64 from their TD errors (B,) or (B, 1), float32 on the device (`per_update`, two launches,
+        nothing read back): the batch's `rows` and the td errors that `critic_loss(..., return_td_errors=True)` returns."""
+        if not self.prioritized:
+            raise ValueError("DeviceReplayBuffer.update_priorities: the buffer was built without prioritized=True")
+        if self.mass is None:
+            raise ValueError("DeviceReplayBuffer.update_priorities: the buffer is empty")
+        per_update(self.mass, self.block_mass, self.block_min, self.max_priority, rows, td_errors, self.alpha, self.priority_eps)

@@ -219,6 +219,31 @@ class SACCriticLossFn(torch.autograd.Function):
         return dq, None
 
 
+class SACCriticLossWFn(torch.autograd.Function):
+    """(q (2, B), target_q (B,), weights (B,) or None) -> (0.5 * sum_c mean(weights * (q_c - target_q)^2) 0-d, td_abs (B,) = the mean over the two
+    critics of |q_c - target_q|, no gradient): the critic loss under the importance weights of prioritised replay, and what
+    `update_priorities` takes.  One launch each way (m3l_sac_critic_loss_w_fwd, m3l_sac_critic_loss_bwd); the gradient goes to q."""
+
+    @staticmethod
+    def forward(ctx, q, target_q, weights):
+        B = target_q.numel()
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        coef = torch.empty(2, B, dtype=torch.float32, device=q.device)
+        td_abs = torch.empty(B, dtype=torch.float32, device=q.device)
+        L.check(L.lib().m3l_sac_critic_loss_w_fwd(L.ptr(q), L.ptr(target_q), L.ptr(weights), B, L.ptr(loss), L.ptr(coef), L.ptr(td_abs), _stream()),
+                "m3l_sac_critic_loss_w_fwd")
+        ctx.saved = (coef, B)
+        ctx.mark_non_differentiable(td_abs)
+        return loss, td_abs
+
+    @staticmethod
+    def backward(ctx, dloss, _dtd):
+        coef, B = ctx.saved
+        dq = torch.empty_like(coef)
+        L.check(L.lib().m3l_sac_critic_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), B, L.ptr(dq), _stream()), "m3l_sac_critic_loss_bwd")
+        return dq, None, None
+
+
 class SACActorLossFn(torch.autograd.Function):
     """(log_prob (B,), q (2, B), ent_coef float or None, log_ent_coef tensor or None) -> mean(ent_coef * log_prob - min_c q_c), 0-d
     (`sac_mae.py:354-356`).  One launch each way; the gradient goes to log_prob and q, the entropy coefficient is a constant (:311)."""
@@ -345,13 +370,23 @@ def td_target(params: SACHeadParams, next_features, rewards, dones, gamma, ent_c
     return out
 
 
-def critic_loss_from(q, target_q):
-    """0.5 * sum_c mse(q_c, target_q) from q (2, B) of `q_values`."""
+def critic_loss_from(q, target_q, weights=None, return_td_errors=False):
+    """0.5 * sum_c mse(q_c, target_q) from q (2, B) of `q_values`.  weights (B,) or (B, 1) float32, the importance weights of a
+    `PrioritizedReplayBatch`: 0.5 * sum_c mean(weights * (q_c - target_q)^2).  return_td_errors: (loss, td) with td (B,) the mean over the two
+    critics of |q_c - target_q|, detached: what `DeviceReplayBuffer.update_priorities` takes.  With neither, the unweighted entry runs."""
     _require_cuda(q, "q")
     B = q.shape[-1]
     if q.dim() != 2 or q.shape[0] != 2 or q.dtype != torch.float32:
         raise ValueError(f"q: (2, B) float32 expected, got {tuple(q.shape)} {q.dtype}")
-    return SACCriticLossFn.apply(q.contiguous(), _vec(target_q, "target_q", B))
+    if weights is None and not return_td_errors:
+        return SACCriticLossFn.apply(q.contiguous(), _vec(target_q, "target_q", B))
+    if weights is not None:
+        _require_cuda(weights, "weights")
+        if weights.dtype != torch.float32 or tuple(weights.shape) not in ((B,), (B, 1)):
+            raise ValueError(f"weights: a float32 tensor of shape ({B},) or ({B}, 1) expected, got {tuple(weights.shape)} {weights.dtype}")
+        weights = _vec(weights, "weights", B)
+    loss, td = SACCriticLossWFn.apply(q.contiguous(), _vec(target_q, "target_q", B), weights)
+    return (loss, td) if return_td_errors else loss
 
 
 def actor_loss_from(log_prob, q, ent_coef=None, log_ent_coef=None):
@@ -428,11 +463,12 @@ class SACHead(nn.Module):
     def td_target(self, next_features, rewards, dones, gamma, ent_coef=None, log_ent_coef=None, noise=None):
         return td_target(self.params(), next_features, rewards, dones, gamma, ent_coef, log_ent_coef, noise)
 
-    def critic_loss(self, features, actions, target_q):
-        """0.5 * sum_c mse(q_c(features, actions), target_q): 2 launches forward, 3 backward."""
+    def critic_loss(self, features, actions, target_q, weights=None, return_td_errors=False):
+        """0.5 * sum_c mse(q_c(features, actions), target_q): 2 launches forward, 3 backward.  weights / return_td_errors: the importance
+        weights of prioritised replay and the td errors for `update_priorities`, as `critic_loss_from` takes and returns them."""
         with torch.no_grad():
             a = actions.detach()
-        return critic_loss_from(q_values(self.params(), features, a), target_q)
+        return critic_loss_from(q_values(self.params(), features, a), target_q, weights, return_td_errors)
 
     def actor_loss(self, features, ent_coef=None, log_ent_coef=None, noise=None):
         """(loss, log_prob.detach()): mean(ent_coef * log_prob - min_c q_c(features, a_pi)).  The critics give their gradient in the actions only:

@@ -37,7 +37,16 @@ this commit's first, and `*_again` entries, this commit's own calls once more in
 largest of its two min-max ranges and of the gap between this commit's two slots (what the place in the alternation alone does to a median);
 `default_path_within_spread`: every median of this commit no further from the parent's than that.
 
-Usage: python tools/replay_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32] [--batches 64,256] [--dedup | --n-steps N]
+--per measures prioritised replay (EXPERIMENTS.md §5.25) on the stores of --dedup, full with pos = 0: `sample()` of a DeviceReplayBuffer with
+prioritized=True against the uniform `sample()` of a buffer over the same stores, stacked and frame-deduplicated, and `update_priorities` of the
+rows of a batch; the masses are seeded, log-uniform over six decades.  On bare priority arrays of --per-rows rows (10^6: the reference's
+default buffer_size, no observation store needed): replay.per_sample against torch.cumsum + torch.searchsorted over all rows, and
+replay.per_update against an index_put_ of (|td| + eps)^alpha, with the share of the torch pair's rows that have zero mass or differ from
+per_sample's.  --parent-lib PATH adds the uniform `sample()`, gather_rows and the one-list gathers through the parent's library, as with
+--n-steps.
+
+Usage: python tools/replay_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32] [--batches 64,256]
+                                         [--dedup | --n-steps N | --per] [--parent-lib PATH]
 (one JSON line)"""
 import argparse
 import json
@@ -325,11 +334,24 @@ def through_library(path):
     return wrap
 
 
-def resident_buffer(image_dtype, frame_dedup, n_steps, stores, next_stores, ages, dscal):
-    """A full DeviceReplayBuffer (pos = 0) standing on stores that are already on the device."""
+def seeded_mass(n, seed):
+    """n masses, log-uniform over [1e-3, 1e3], on the device."""
+    g = np.random.default_rng(seed)
+    return torch.from_numpy(np.exp(g.uniform(np.log(1e-3), np.log(1e3), n)).astype(np.float32)).to(DEV)
+
+
+def resident_buffer(image_dtype, frame_dedup, n_steps, stores, next_stores, ages, dscal, prioritized=False):
+    """A full DeviceReplayBuffer (pos = 0) standing on stores that are already on the device.  prioritized: with seeded masses on its valid
+    steps (the frame-deduplicated ring does not sample its fs - 1 oldest)."""
     shapes = {"image": (FS, H, W, 3), "tactile": (FS, 3 * S, TH, TW)}
     buf = m3l_amd.DeviceReplayBuffer(T * E, E, shapes, {"image": image_dtype, "tactile": np.float32}, A, device=DEV, frame_dedup=frame_dedup,
-                                     n_steps=n_steps, gamma=0.99)
+                                     n_steps=n_steps, gamma=0.99, prioritized=prioritized)
+    if prioritized:
+        buf.mass = seeded_mass(T * E, 4).reshape(T, E)
+        if frame_dedup:
+            buf.mass[:FS - 1] = 0
+        buf.block_mass, buf.block_min = P.per_refresh(buf.mass)
+        buf.max_priority = torch.ones(1, dtype=torch.float32, device=DEV)
     if frame_dedup:
         buf.frames, buf.next_frames, buf.ages = stores, next_stores, ages
     else:
@@ -450,6 +472,158 @@ def run_nstep(a):
     return out
 
 
+# ---- prioritised replay (--per, EXPERIMENTS.md §5.25)
+def parent_entries(fns, default_path, parent_lib):
+    """The default path through the parent's library and once more through this one, as run_nstep_config does it."""
+    wrap = through_library(parent_lib)
+    for p in default_path:
+        fns[p + "_parent"] = wrap(fns[p])
+    for p in default_path:
+        fns[p + "_again"] = (lambda f: lambda: f())(fns[p])
+
+
+def parent_verdict(res, default_path):
+    res["default_path_vs_parent"] = {}
+    for p in default_path:
+        mine, theirs, again = res[p], res[p + "_parent"], res[p + "_again"]
+        spread = max(theirs["call_us_min_max"][1] - theirs["call_us_min_max"][0], mine["call_us_min_max"][1] - mine["call_us_min_max"][0],
+                     abs(mine["call_us"] - again["call_us"]))
+        res["default_path_vs_parent"][p] = {"this_us": mine["call_us"], "parent_us": theirs["call_us"], "this_again_us": again["call_us"],
+                                            "spread_us": round(spread, 1), "within_spread": bool(abs(mine["call_us"] - theirs["call_us"]) <= spread)}
+    res["default_path_within_spread"] = all(v["within_spread"] for v in res["default_path_vs_parent"].values())
+
+
+def run_per_config(name, B, frames, next_frames, stacked, stacked_next, ages, dscal, a):
+    image_dtype = np.uint8 if name == "u8" else np.float32
+    perm = np.random.default_rng(1).permutation(T).astype(np.int64)
+    d_rows = [torch.from_numpy(perm[i:i + B]).to(DEV) for i in range(0, T - B + 1, B)]
+    scale = float(np.float32(math.sqrt(VAR + EPS)))
+    sc = (dscal["actions"], dscal["rewards"], dscal["dones"], dscal["timeouts"])
+    env = type("Env", (), dict(norm_obs=False, norm_reward=True, ret_rms=type("Rms", (), dict(var=VAR)), epsilon=EPS, clip_reward=CLIP))
+    bufs = {(dedup, per): resident_buffer(image_dtype, dedup, 1, frames if dedup else stacked, next_frames if dedup else stacked_next, ages, dscal, per)
+            for dedup in (False, True) for per in (False, True)}
+    # a prioritised batch is the uniform buffer's batch of the same rows, and every row has positive mass
+    for dedup in (False, True):
+        batch = bufs[dedup, True].sample(B, env=env)
+        rows = batch.rows.cpu()
+        assert bool((bufs[dedup, True].mass.reshape(-1)[batch.rows] > 0).all())
+        base = bufs[dedup, False].sample(1, env=env, indices=(rows // E, rows % E))
+        for fld in base._fields:
+            x, y = getattr(batch, fld), getattr(base, fld)
+            for k in (x if isinstance(x, dict) else [None]):
+                assert torch.equal(x[k] if k is not None else x, y[k] if k is not None else y), f"{name} B={B}: {fld} differs from the uniform buffer"
+    g = torch.Generator(device=DEV).manual_seed(3)
+    tds = [torch.randn(B, 1, generator=g, device=DEV) for _ in range(8)]
+    upd_rows = [bufs[False, True].sample(B).rows for _ in range(8)]
+    state = {}
+
+    def nxt(p, n):
+        i = state.get(p, 0)
+        state[p] = (i + 1) % n
+        return i
+
+    def update():
+        i = nxt("u", 8)
+        bufs[False, True].update_priorities(upd_rows[i], tds[i])
+    torch.cuda.synchronize()
+    fns = {"update_priorities": update}
+    for (dedup, per), buf in bufs.items():
+        fns[f"sample_{'frames' if dedup else 'stacked'}_{'per' if per else 'uniform'}"] = (lambda b: lambda: b.sample(B, env=env))(buf)
+    default_path = ("rows_gather_rows", "stacked_one_list", "frames_one_list", "sample_stacked_uniform", "sample_frames_uniform")
+    if a.parent_lib:
+        fns["rows_gather_rows"] = lambda: P.gather_rows(*sc, d_rows[nxt("r1", len(d_rows))], scale, CLIP, return_rows=True)
+        fns["stacked_one_list"] = lambda: P.gather_load(stacked["image"], stacked["tactile"], d_rows[nxt("s1", len(d_rows))], stacked_next["image"],
+                                                        stacked_next["tactile"])
+        fns["frames_one_list"] = lambda: P.gather_load_frames(frames["image"], frames["tactile"], ages, d_rows[nxt("f1", len(d_rows))],
+                                                              next_frames["image"], next_frames["tactile"], frame_stack=FS)
+        parent_entries(fns, default_path, a.parent_lib)
+        for p in default_path[:3]:                    # the same batch through both libraries: equal bits
+            state.clear()
+            mine = fns[p]()
+            state.clear()
+            theirs = fns[p + "_parent"]()
+            for x, y in zip(mine, theirs):
+                for k in (x if isinstance(x, dict) else [None]):
+                    assert torch.equal(x[k] if k is not None else x, y[k] if k is not None else y), f"{name} B={B}: {p} differs from the parent library"
+    res = alternate(fns, {p: a.iters for p in fns}, {p: 20 for p in fns}, a.rounds)
+    for p, fn in fns.items():
+        res[p].update(counted(fn))
+    if a.parent_lib:
+        parent_verdict(res, default_path)
+    for lay in ("stacked", "frames"):
+        res[f"sample_{lay}_per_over_uniform"] = round(res[f"sample_{lay}_per"]["call_us"] / res[f"sample_{lay}_uniform"]["call_us"], 3)
+    return res
+
+
+def run_per_bare(B, a):
+    """The priority structure alone at --per-rows rows against the torch ops a user would write on the same device."""
+    n, alpha, eps = a.per_rows, 0.6, 1e-6
+    mass = seeded_mass(n, 6)
+    mass[torch.rand(n, device=DEV) < 0.2] = 0           # steps outside the valid window, dead rows: a fifth zero
+    bm, bmin = P.per_refresh(mass)
+    mp = torch.ones(1, dtype=torch.float32, device=DEV)
+    torch_mass = mass.clone()
+    g = torch.Generator(device=DEV).manual_seed(7)
+    us = [torch.rand(B, generator=g, device=DEV) for _ in range(16)]
+    tds = [torch.randn(B, generator=g, device=DEV) for _ in range(16)]
+    rows = [P.per_sample(mass, bm, bmin, u)[0] for u in us]
+    ar = torch.arange(B, dtype=torch.float32, device=DEV)
+    state = {}
+
+    def nxt(p):
+        i = state.get(p, 0)
+        state[p] = (i + 1) % 16
+        return i
+
+    def torch_sample(i=None):
+        u = us[nxt("ts") if i is None else i]
+        c = torch.cumsum(torch_mass, 0)
+        return torch.searchsorted(c, (ar + u) * (c[-1] / B), right=True)
+
+    def torch_update():
+        i = nxt("tu")
+        torch_mass.index_put_((rows[i],), (tds[i].abs() + eps).pow(alpha))
+
+    def per_update():
+        i = nxt("pu")
+        P.per_update(mass, bm, bmin, mp, rows[i], tds[i], alpha, eps)
+    # before anything is updated both hold the same masses: how the torch pair's rows compare
+    zero = differ = 0
+    for i in range(16):
+        r = torch_sample(i).clamp(max=n - 1)
+        zero += int((mass[r] == 0).sum())
+        differ += int((r != rows[i]).sum())
+    torch.cuda.synchronize()
+    fns = {"per_sample": lambda: P.per_sample(mass, bm, bmin, us[nxt("ps")]), "torch_cumsum_searchsorted": torch_sample, "per_update": per_update,
+           "torch_index_put": torch_update}
+    res = alternate(fns, {p: a.iters for p in fns}, {p: 20 for p in fns}, a.rounds)
+    for p, fn in fns.items():
+        res[p].update(counted(fn))
+    res["rows"] = n
+    res["torch_rows_of_zero_mass"] = [zero, 16 * B]
+    res["torch_rows_that_differ_from_per_sample"] = [differ, 16 * B]
+    res["per_sample_over_torch"] = round(res["per_sample"]["call_us"] / res["torch_cumsum_searchsorted"]["call_us"], 3)
+    res["per_update_over_torch"] = round(res["per_update"]["call_us"] / res["torch_index_put"]["call_us"], 3)
+    return res
+
+
+def run_per(a):
+    ages = torch.full((T, E), FS - 1, dtype=torch.int32, device=DEV)
+    g = np.random.default_rng(2)
+    scal = dict(actions=g.standard_normal((T, E, A)).astype(np.float32), rewards=(3 * g.standard_normal((T, E))).astype(np.float32),
+                dones=(g.random((T, E)) < 0.01).astype(np.float32))
+    scal["timeouts"] = (scal["dones"] * (g.random((T, E)) < 0.5)).astype(np.float32)
+    dscal = {k: torch.from_numpy(v).to(DEV) for k, v in scal.items()}
+    out = {"bare": {f"B{B}": run_per_bare(B, a) for B in a.batches}}
+    for name in a.variants.split(","):
+        frames, next_frames, stacked, stacked_next = dedup_stores(np.uint8 if name == "u8" else np.float32, 0)
+        torch.cuda.synchronize()
+        out[name] = {f"B{B}": run_per_config(name, B, frames, next_frames, stacked, stacked_next, ages, dscal, a) for B in a.batches}
+        del frames, next_frames, stacked, stacked_next
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5, help="alternating windows per path")
@@ -459,17 +633,21 @@ def main():
     ap.add_argument("--batches", default="64,256")
     ap.add_argument("--dedup", action="store_true", help="measure the frame-deduplicated store against the stacked one instead of the three paths")
     ap.add_argument("--n-steps", type=int, default=0, help="measure n-step returns with this n_steps (>= 2) instead of the three paths")
-    ap.add_argument("--parent-lib", default=None, help="with --n-steps: a shared library built from the parent commit, timed on the default path")
+    ap.add_argument("--per", action="store_true", help="measure prioritised replay instead of the three paths")
+    ap.add_argument("--per-rows", type=int, default=1_000_000, help="with --per: rows of the bare priority arrays")
+    ap.add_argument("--parent-lib", default=None, help="with --n-steps or --per: a shared library built from the parent commit, timed on the default path")
     a = ap.parse_args()
     if a.n_steps and (a.n_steps < 2 or a.dedup):
         raise SystemExit("replay_feed_bench: --n-steps takes a value of at least 2 and excludes --dedup")
+    if a.per and (a.n_steps or a.dedup):
+        raise SystemExit("replay_feed_bench: --per excludes --dedup and --n-steps")
     a.batches = [int(b) for b in a.batches.split(",")]
     if not torch.cuda.is_available():
         raise SystemExit("replay_feed_bench: no GPU")
     out = {"shape": {"T": T, "n_envs": E, "frame_stack": FS, "image": [H, W, 3], "tactile": [3 * S, TH, TW], "B": a.batches, "action_dim": A},
            "hbm_peak_tbytes_per_s": {"float4_copy_measured": HBM_COPY_TBS, "spec": HBM_SPEC_TBS}}
-    if a.dedup or a.n_steps:
-        out.update({"n_step": run_nstep(a)} if a.n_steps else {"frame_dedup": run_dedup(a)})
+    if a.dedup or a.n_steps or a.per:
+        out.update({"prioritized": run_per(a)} if a.per else {"n_step": run_nstep(a)} if a.n_steps else {"frame_dedup": run_dedup(a)})
         print(json.dumps(out))
         return
     for name in a.variants.split(","):
