@@ -858,7 +858,8 @@ int m3l_replay_gather_load_frames(const void* image_frames, const void* image_ne
  *   rows        t n_envs + e, as gather_rows' rows_out;  next_rows  last n_envs + e: the row whose next observation the target bootstraps from
  *   actions     those of (t, e)
  * m3l_replay_nstep_rows: the inputs of m3l_replay_gather_rows plus n_steps, gamma and newest; one launch, no read-back, no atomics, one lane
- * walks one sample: two runs give the same bits, and n_steps = 1 gives gather_rows' bits.  Index contract as above: a row outside
+ * walks one sample: two runs give the same bits, and n_steps = 1 gives gather_rows' bits (m3l_replay_gather_rows launches this entry's kernel
+ * with n_steps = 1 and without the discounts and next_rows outputs).  Index contract as above: a row outside
  * [0, T n_envs) is never read, nor is anything through it; its outputs are NaN and its rows / next_rows entries -1.
  * Errors, nothing written: those of gather_rows, a NULL output, n_steps outside [1, T], gamma outside (0, 1], newest outside [0, T).
  *

@@ -106,8 +106,7 @@ __device__ __forceinline__ float* tactile_sensor(float* const (&tac_out)[M3L_MAX
     return o;
 }
 
-// one piece of one frame, loaded, normalised and written once: piece q of frame `frame` of img -> plane group `group` of img_out.  What the items
-// below do for a stacked row, for callers that put a stack together frame by frame (replay.hip, the two-list frame gather)
+// one piece of one frame, loaded, normalised and written once: piece q of frame `frame` of img -> plane group `group` of img_out
 template <typename TI>
 __device__ __forceinline__ void gather_image_piece(const GatherGeom& g, const void* img, float* img_out, long frame, long group, int q) {
     if (g.img_vec) {
@@ -130,36 +129,30 @@ __device__ __forceinline__ void gather_tactile_piece(const GatherGeom& g, const 
         o[q] = tactile_load1<TI>(g, tac, frame, s, q);
 }
 
+// item r of a sample -> its frame f and the piece q of that frame, and for a tactile item the sensor s: frame-major, then sensor, then piece
+__device__ __forceinline__ void gather_image_decode(const GatherGeom& g, int r, int& f, int& q) {
+    const int per_frame = g.img_vec ? g.HW / 4 : g.HW;
+    f = r / per_frame, q = r % per_frame;
+}
+__device__ __forceinline__ void gather_tactile_decode(const GatherGeom& g, int r, int& f, int& s, int& q) {
+    const int per_seg = g.tac_vec ? 3 * g.hw / 4 : 3 * g.hw;      // the three channels of one sensor in one frame
+    f = r / (g.S * per_seg), s = (r / per_seg) % g.S, q = r % per_seg;
+}
+
 // item r < img_per_sample of output sample b: store row `row` of img (n_rows, fs, H, W, 3) -> img_out (B, 3 fs, H, W)
 template <typename TI>
 __device__ __forceinline__ void gather_image_item(const GatherGeom& g, const void* img, float* img_out, long row, int b, int r) {
-    const int per_frame = g.img_vec ? g.HW / 4 : g.HW;
-    const int f = r / per_frame, q = r % per_frame;
-    const long frame = row >= 0 ? row * g.fs + f : -1;
-    if (g.img_vec) {
-        float v[12];
-        image_load4<TI>(g, img, frame, q, v);
-        image_store4(g, img_out, (long)b * g.fs + f, q, v);
-    } else {
-        float v[3];
-        image_load1<TI>(g, img, frame, q, v);
-        image_store1(g, img_out, (long)b * g.fs + f, q, v);
-    }
+    int f, q;
+    gather_image_decode(g, r, f, q);
+    gather_image_piece<TI>(g, img, img_out, row >= 0 ? row * g.fs + f : -1, (long)b * g.fs + f, q);
 }
-
 // item r < tac_per_sample of output sample b: store row `row` of tac (n_rows, fs, 3 S, h, w) -> tac_out[s] (B, 3 fs, h, w)
 template <typename TI>
 __device__ __forceinline__ void gather_tactile_item(const GatherGeom& g, const void* tac, float* const (&tac_out)[M3L_MAX_SENSORS], long row, int b,
                                                     int r) {
-    const long seg = 3L * g.hw;                                   // the three channels of one sensor in one frame
-    const int per_seg = g.tac_vec ? (int)(seg / 4) : (int)seg;
-    const int f = r / (g.S * per_seg), s = (r / per_seg) % g.S, q = r % per_seg;
-    const long frame = row >= 0 ? row * g.fs + f : -1;
-    float* o = tactile_sensor(tac_out, s) + ((long)b * g.fs + f) * seg;
-    if (g.tac_vec)
-        *(f32x4*)(o + 4L * q) = tactile_load4<TI>(g, tac, frame, s, q);
-    else
-        o[q] = tactile_load1<TI>(g, tac, frame, s, q);
+    int f, s, q;
+    gather_tactile_decode(g, r, f, s, q);
+    gather_tactile_piece<TI>(g, tac, tactile_sensor(tac_out, s), row >= 0 ? row * g.fs + f : -1, (long)b * g.fs + f, s, q);
 }
 
 inline bool gather_aligned(const void* p, size_t n) { return ((uintptr_t)p % n) == 0; }

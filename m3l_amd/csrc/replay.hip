@@ -30,21 +30,25 @@
 
 namespace {
 
-struct ReplayLoadArgs {
-    const void* img;                         // (T, n_envs, fs, H, W, 3) or NULL
+// The arguments of all four gather kernels.  A stacked store is (T, n_envs, fs, ...) and ages is NULL; the frame-deduplicated store holds every
+// frame once, (T, n_envs, ...) without the fs axis: slot t is the newest frame of step t's observation (img / tac) or of its next observation
+// (img_next / tac_next), and ages[t, e] says how many earlier frames of the same episode the stack of step (t, e) reaches.
+struct ReplayGatherArgs {
+    const void* img;                         // (T, n_envs, [fs,] H, W, 3) or NULL
     const void* img_next;                    // the same shape, or NULL: the next observation is img one step later
-    const void* tac;                         // (T, n_envs, fs, 3 S, h, w) or NULL
+    const void* tac;                         // (T, n_envs, [fs,] 3 S, h, w) or NULL
     const void* tac_next;
     float* img_out[2];                       // (B, 3 fs, H, W): observations, next observations
     float* tac_out[2][M3L_MAX_SENSORS];      // (B, 3 fs, h, w) each
     const int64_t* rows;                     // (B), t * n_envs + e
+    const int64_t* next_rows;                // rows2: (B), the rows of the next observations, no shift applied; else NULL
+    const int32_t* ages;                     // (T, n_envs); NULL: stacked stores
     long n_rows, shift;                      // T * n_envs; the ring offset added to every entry of rows
     int T, n_envs;
-    GatherGeom g;
-    int img_blocks, half_blocks;             // of one half: blocks [0, img_blocks) do the image, [img_blocks, half_blocks) the tactile frames
-    long img_items, tac_items;               // lanes of work of each modality in one half
-    const int64_t* next_rows;                // rows2: (B), the rows of the next observations, no shift applied; else NULL.  Last: the one-list
-                                             // kernel keeps the argument offsets it had without it
+    GatherGeom g;                            // *_per_sample count fs frames of one half (stacked), or fs + 1 (rows2: 2 fs) source frames
+    int img_blocks, half_blocks;             // of one run: blocks [0, img_blocks) do the image, [img_blocks, half_blocks) the tactile frames; the
+                                             // stacked kernels run two such halves, observations then next observations
+    long img_items, tac_items;               // lanes of work of each modality in one run
 };
 
 // store row the sample reads, (rows[b] + shift) % n_rows, or -1 when rows[b] is out of range.  step: 1 = the same environment one step later
@@ -68,7 +72,7 @@ __device__ __forceinline__ void tactile_item(const GatherGeom& g, const void* sr
 
 // ROWS2: the next half takes its rows from a.next_rows as they are
 template <bool ROWS2>
-__global__ void __launch_bounds__(256) replay_gather_load_kernel(ReplayLoadArgs a) {
+__global__ void __launch_bounds__(256) replay_gather_load_kernel(ReplayGatherArgs a) {
     const int next = (int)blockIdx.x >= a.half_blocks;                  // uniform over the block
     const int blk = (int)blockIdx.x - (next ? a.half_blocks : 0);
     const bool two = ROWS2 && next;                                     // the next half of a two-list launch
@@ -99,24 +103,24 @@ __global__ void __launch_bounds__(256) replay_gather_load_kernel(ReplayLoadArgs 
     }
 }
 
-// ---- the frame-deduplicated store: every frame lies in the ring once, (T, n_envs, ...) without the fs axis, and a sample's two stacks are put
-// together from fs + 1 of them.  ages[t, e] says how many earlier frames of the same episode the stack of step (t, e) reaches.
-struct ReplayFramesArgs {
-    const void* img;                         // (T, n_envs, H, W, 3) or NULL: slot t holds the newest frame of step t's observation
-    const void* img_next;                    // the same shape: the newest frame of step t's next observation; NULL: that is img one step later
-    const void* tac;                         // (T, n_envs, 3 S, h, w) or NULL
-    const void* tac_next;
-    float* img_out[2];                       // (B, 3 fs, H, W): observations, next observations
-    float* tac_out[2][M3L_MAX_SENSORS];      // (B, 3 fs, h, w) each
-    const int64_t* rows;                     // (B), t * n_envs + e
-    const int32_t* ages;                     // (T, n_envs)
-    long n_rows, shift;
-    int T, n_envs;
-    GatherGeom g;                            // *_per_sample count fs + 1 source frames (rows2: 2 fs)
-    int img_blocks;                          // blocks [0, img_blocks) do the image, the rest the tactile frames
-    long img_items, tac_items;
-    const int64_t* next_rows;                // rows2: as in ReplayLoadArgs, and last for the same reason
-};
+// ---- the frame-deduplicated store: a sample's two stacks are put together from fs + 1 of its frames
+
+// lane -> item (b, k, q) of the image run: piece q of source frame k of sample b; false past the last item
+__device__ __forceinline__ bool frames_image_item(const ReplayGatherArgs& a, int& b, int& k, int& q) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.img_items) return false;
+    b = (int)(i / a.g.img_per_sample);
+    gather_image_decode(a.g, (int)(i % a.g.img_per_sample), k, q);
+    return true;
+}
+// lane -> item (b, k, s, q) of the tactile run, which follows the image run: piece q of sensor s of source frame k of sample b
+__device__ __forceinline__ bool frames_tactile_item(const ReplayGatherArgs& a, int& b, int& k, int& s, int& q) {
+    const long i = (long)((int)blockIdx.x - a.img_blocks) * 256 + threadIdx.x;
+    if (i >= a.tac_items) return false;
+    b = (int)(i / a.g.tac_per_sample);
+    gather_tactile_decode(a.g, (int)(i % a.g.tac_per_sample), k, s, q);
+    return true;
+}
 
 // frame slot * n_envs + e that source k of store row `row` reads, or -1 for a row that is not read.  Source k < fs is observation frame k
 // (fs - 1 the newest): min(fs - 1 - k, age) steps back in the ring; source fs is the next observation's newest frame: the same row of the
@@ -169,14 +173,11 @@ __device__ __forceinline__ void frames_tactile_piece(const GatherGeom& g, const 
     }
 }
 
-__global__ void __launch_bounds__(256) replay_gather_load_frames_kernel(ReplayFramesArgs a) {
+__global__ void __launch_bounds__(256) replay_gather_load_frames_kernel(ReplayGatherArgs a) {
     const int fs = a.g.fs;
+    int b, k, s, q;
     if ((int)blockIdx.x < a.img_blocks) {                               // uniform over the block
-        const long i = (long)blockIdx.x * 256 + threadIdx.x;
-        if (i >= a.img_items) return;
-        const int per_frame = a.g.img_vec ? a.g.HW / 4 : a.g.HW;
-        const int b = (int)(i / a.g.img_per_sample), r = (int)(i % a.g.img_per_sample);
-        const int k = r / per_frame, q = r % per_frame;
+        if (!frames_image_item(a, b, k, q)) return;
         const bool second = k == fs && a.img_next;
         const long row = replay_row(a.rows, b, a.n_rows, a.shift, a.T, a.n_envs, 0);
         const long frame = replay_frame(a.ages, row, k, fs, a.T, a.n_envs, second);
@@ -186,11 +187,7 @@ __global__ void __launch_bounds__(256) replay_gather_load_frames_kernel(ReplayFr
         else
             frames_image_piece<float>(a.g, src, frame, a.img_out[0], a.img_out[1], b, k, q);
     } else {
-        const long i = (long)((int)blockIdx.x - a.img_blocks) * 256 + threadIdx.x;
-        if (i >= a.tac_items) return;
-        const int per_seg = a.g.tac_vec ? 3 * a.g.hw / 4 : 3 * a.g.hw;
-        const int b = (int)(i / a.g.tac_per_sample), r = (int)(i % a.g.tac_per_sample);
-        const int k = r / (a.g.S * per_seg), s = (r / per_seg) % a.g.S, q = r % per_seg;
+        if (!frames_tactile_item(a, b, k, s, q)) return;
         const bool second = k == fs && a.tac_next;
         const long row = replay_row(a.rows, b, a.n_rows, a.shift, a.T, a.n_envs, 0);
         const long frame = replay_frame(a.ages, row, k, fs, a.T, a.n_envs, second);
@@ -209,7 +206,7 @@ __global__ void __launch_bounds__(256) replay_gather_load_frames_kernel(ReplayFr
 // frames, each written once.  Source k < fs is observation frame k of rows[b]; source fs + j is next-observation frame j of next_rows[b]: for
 // j < fs - 1 observation frame j + 1 of that row (with that row's age), for j = fs - 1 its next frame.  -> the row the source belongs to (-1:
 // not read) and, in kk, the source's number in replay_frame's terms
-__device__ __forceinline__ long replay_rows2_source(const ReplayFramesArgs& a, int b, int k, int& kk, int& j) {
+__device__ __forceinline__ long replay_rows2_source(const ReplayGatherArgs& a, int b, int k, int& kk, int& j) {
     const int fs = a.g.fs;
     const bool nxt = k >= fs;
     j = nxt ? k - fs : k;                                               // the frame's place in its output stack
@@ -217,15 +214,11 @@ __device__ __forceinline__ long replay_rows2_source(const ReplayFramesArgs& a, i
     return replay_row(nxt ? a.next_rows : a.rows, b, a.n_rows, nxt ? 0 : a.shift, a.T, a.n_envs, 0);
 }
 
-__global__ void __launch_bounds__(256) replay_gather_load_frames_rows2_kernel(ReplayFramesArgs a) {
+__global__ void __launch_bounds__(256) replay_gather_load_frames_rows2_kernel(ReplayGatherArgs a) {
     const int fs = a.g.fs;
+    int b, k, s, q, kk, j;
     if ((int)blockIdx.x < a.img_blocks) {                               // uniform over the block
-        const long i = (long)blockIdx.x * 256 + threadIdx.x;
-        if (i >= a.img_items) return;
-        const int per_frame = a.g.img_vec ? a.g.HW / 4 : a.g.HW;
-        const int b = (int)(i / a.g.img_per_sample), r = (int)(i % a.g.img_per_sample);
-        const int k = r / per_frame, q = r % per_frame;
-        int kk, j;
+        if (!frames_image_item(a, b, k, q)) return;
         const long row = replay_rows2_source(a, b, k, kk, j);
         const bool second = kk == fs && a.img_next;
         const long frame = replay_frame(a.ages, row, kk, fs, a.T, a.n_envs, second);
@@ -236,12 +229,7 @@ __global__ void __launch_bounds__(256) replay_gather_load_frames_rows2_kernel(Re
         else
             gather_image_piece<float>(a.g, src, out, frame, (long)b * fs + j, q);
     } else {
-        const long i = (long)((int)blockIdx.x - a.img_blocks) * 256 + threadIdx.x;
-        if (i >= a.tac_items) return;
-        const int per_seg = a.g.tac_vec ? 3 * a.g.hw / 4 : 3 * a.g.hw;
-        const int b = (int)(i / a.g.tac_per_sample), r = (int)(i % a.g.tac_per_sample);
-        const int k = r / (a.g.S * per_seg), s = (r / per_seg) % a.g.S, q = r % per_seg;
-        int kk, j;
+        if (!frames_tactile_item(a, b, k, s, q)) return;
         const long row = replay_rows2_source(a, b, k, kk, j);
         const bool second = kk == fs && a.tac_next;
         const long frame = replay_frame(a.ages, row, kk, fs, a.T, a.n_envs, second);
@@ -270,32 +258,12 @@ __device__ __forceinline__ float replay_done(const float* __restrict__ dones, co
     return d;
 }
 
-// per-step scalars of the sampled rows: lane (b, k) copies action component k < A, the (normalised) reward, the masked done or the row number
-__global__ void replay_gather_rows_kernel(const float* __restrict__ actions, const float* __restrict__ rewards, const float* __restrict__ dones,
-                                          const float* __restrict__ timeouts, int T, int n_envs, int A, const int64_t* __restrict__ rows, long shift,
-                                          int B, float reward_scale, float reward_clip, float* __restrict__ actions_out,
-                                          float* __restrict__ rewards_out, float* __restrict__ dones_out, int64_t* __restrict__ rows_out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * (A + 3)) return;
-    const int b = (int)(i / (A + 3)), k = (int)(i % (A + 3));
-    const long row = replay_row(rows, b, (long)T * n_envs, shift, T, n_envs, 0);
-    const float nan = __int_as_float(0x7fc00000);
-    if (k == A + 2) {
-        if (rows_out) rows_out[b] = row;
-    } else if (k < A) {
-        actions_out[(long)b * A + k] = row >= 0 ? actions[row * A + k] : nan;
-    } else if (k == A) {
-        rewards_out[b] = row >= 0 ? replay_reward(rewards, row, reward_scale, reward_clip) : nan;
-    } else {
-        dones_out[b] = row >= 0 ? replay_done(dones, timeouts, row) : nan;
-    }
-}
-
-// n-step returns.  Lane (b, k): k < A copies action component k of rows[b]; lane (b, A) walks from step t of that row towards newer steps of
-// the same environment — it stops at the first done, at the write head `newest` and after n_steps - 1 moves — and writes the discounted
-// reward sum, the masked done of the last step, gamma^(steps taken), the row and the last step's row.  One lane does the whole walk of a
-// sample in ascending order with separate multiplications and additions: the sum has one order, and for a walk of no move the outputs are
-// gather_rows' bits and gamma itself.
+// The per-step scalars of the sampled rows, with n-step returns.  Lane (b, k): k < A copies action component k of rows[b]; lane (b, A) walks
+// from step t of that row towards newer steps of the same environment — it stops at the first done, at the write head `newest` and after
+// n_steps - 1 moves — and writes the discounted reward sum, the masked done of the last step, gamma^(steps taken), the row and the last step's
+// row; the last three outputs may be NULL.  One lane does the whole walk of a sample in ascending order with separate multiplications and
+// additions: the sum has one order.  m3l_replay_gather_rows is the launch with n_steps = 1, a walk of no move: the (normalised) reward and
+// the masked done of the row itself, and gamma and newest are not looked at.
 __global__ void replay_nstep_rows_kernel(const float* __restrict__ actions, const float* __restrict__ rewards, const float* __restrict__ dones,
                                          const float* __restrict__ timeouts, int T, int n_envs, int A, const int64_t* __restrict__ rows, long shift,
                                          int B, float reward_scale, float reward_clip, int n_steps, float gamma, int newest,
@@ -329,24 +297,30 @@ __global__ void replay_nstep_rows_kernel(const float* __restrict__ actions, cons
     }
     rewards_out[b] = sum;
     dones_out[b] = done;
-    discounts_out[b] = disc;
-    rows_out[b] = row;
-    next_rows_out[b] = last;
+    if (discounts_out) discounts_out[b] = disc;
+    if (rows_out) rows_out[b] = row;
+    if (next_rows_out) next_rows_out[b] = last;
 }
 
-// m3l_replay_gather_load (next_rows NULL) and m3l_replay_gather_load_rows2
-int replay_load_launch(const char* who, const void* image_store, const void* image_next_store, int image_u8, int H, int W, double img_lo,
-                       double img_hi, float* image, float* image_next, const void* tactile_store, const void* tactile_next_store, int tactile_u8, int th,
-                       int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out, float* const* tactile_next_out, int T, int n_envs,
-                       int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, int B, void* stream) {
-    M3L_CHECK(image_store || tactile_store, "%s: neither an image nor a tactile store", who);
+// The four gather entry points.  ages: the stores hold single frames (m3l_replay_gather_load_frames*) and a sample is fs + 1 source frames,
+// with next_rows 2 fs, in one run of blocks; NULL: the stores are stacked (m3l_replay_gather_load*) and a sample is fs frames in each of two
+// runs.  next_rows: the *_rows2 entry points' second row list, else NULL.
+int replay_gather_launch(const char* who, const void* image_store, const void* image_next_store, int image_u8, int H, int W,
+                         double img_lo, double img_hi, float* image, float* image_next, const void* tactile_store, const void* tactile_next_store,
+                         int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out,
+                         float* const* tactile_next_out, const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* rows, long row_shift,
+                         const int64_t* next_rows, int B, void* stream) {
+    const bool frames = ages != nullptr;
+    M3L_CHECK(image_store || tactile_store, "%s: neither an image nor a tactile %sstore", who, frames ? "frame " : "");
     M3L_CHECK((image_store || !image_next_store) && (tactile_store || !tactile_next_store), "%s: a next store without its store", who);
     M3L_CHECK(T >= 1 && n_envs >= 1 && frame_stack >= 1 && B >= 1 && rows, "%s: T=%d n_envs=%d frame_stack=%d B=%d", who, T, n_envs, frame_stack,
               B);
     M3L_CHECK(row_shift >= 0 && row_shift < (long)T * n_envs, "%s: row_shift=%ld outside [0, %ld)", who, row_shift, (long)T * n_envs);
-    ReplayLoadArgs a;
+    ReplayGatherArgs a;
     memset(&a, 0, sizeof(a));
-    a.rows = rows, a.next_rows = next_rows;
+    a.rows = rows, a.next_rows = next_rows, a.ages = ages;
+    const long sources = !frames ? frame_stack : next_rows ? 2L * frame_stack : frame_stack + 1L;       // frames of one sample in one run
+    const int runs = frames ? 1 : 2;
     a.n_rows = (long)T * n_envs, a.shift = row_shift;
     a.T = T, a.n_envs = n_envs, a.g.fs = frame_stack;
     long img_per = 0, tac_per = 0;
@@ -355,82 +329,47 @@ int replay_load_launch(const char* who, const void* image_store, const void* ima
         M3L_CHECK(image_next, "%s: the next-observation image output is NULL", who);
         a.img = image_store, a.img_next = image_next_store, a.img_out[0] = image, a.img_out[1] = image_next;
         a.g.img_vec = a.g.img_vec && gather_aligned(image_next, 16) && (!image_next_store || gather_aligned(image_next_store, image_u8 ? 4 : 16));
-        img_per = gather_image_items(a.g);
-    }
-    if (tactile_store) {
-        if (gather_tactile_geom(a.g, who, tactile_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, a.tac_out[0]))
-            return 1;
-        const int vec = a.g.tac_vec;
-        M3L_CHECK(tactile_next_out, "%s: the next-observation tactile outputs are NULL", who);
-        if (gather_tactile_geom(a.g, who, tactile_next_store ? tactile_next_store : tactile_store, tactile_u8, th, tw, n_sensors, tac_lo,
-                                tac_hi, tactile_next_out, a.tac_out[1]))
-            return 1;
-        a.g.tac_vec = a.g.tac_vec && vec;
-        a.tac = tactile_store, a.tac_next = tactile_next_store;
-        tac_per = gather_tactile_items(a.g);
-    }
-    M3L_CHECK(img_per <= INT32_MAX && tac_per <= INT32_MAX, "%s: sample too large", who);
-    a.g.img_per_sample = (int)img_per, a.g.tac_per_sample = (int)tac_per;
-    a.img_items = img_per * B, a.tac_items = tac_per * B;
-    const long img_blocks = (a.img_items + 255) / 256, tac_blocks = (a.tac_items + 255) / 256;
-    M3L_CHECK(2 * (img_blocks + tac_blocks) <= INT32_MAX, "%s: B=%d too large", who, B);
-    a.img_blocks = (int)img_blocks, a.half_blocks = (int)(img_blocks + tac_blocks);
-    if (next_rows)
-        replay_gather_load_kernel<true><<<(unsigned)(2 * a.half_blocks), 256, 0, (hipStream_t)stream>>>(a);
-    else
-        replay_gather_load_kernel<false><<<(unsigned)(2 * a.half_blocks), 256, 0, (hipStream_t)stream>>>(a);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-// m3l_replay_gather_load_frames (next_rows NULL: fs + 1 source frames per sample) and m3l_replay_gather_load_frames_rows2 (2 fs)
-int replay_frames_launch(const char* who, const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
-                         double img_hi, float* image, float* image_next, const void* tactile_frames, const void* tactile_next_frames, int tactile_u8,
-                         int th, int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out, float* const* tactile_next_out,
-                         const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, int B,
-                         void* stream) {
-    M3L_CHECK(image_frames || tactile_frames, "%s: neither an image nor a tactile frame store", who);
-    M3L_CHECK((image_frames || !image_next_frames) && (tactile_frames || !tactile_next_frames), "%s: a next store without its store", who);
-    M3L_CHECK(T >= 1 && n_envs >= 1 && frame_stack >= 1 && B >= 1 && rows, "%s: T=%d n_envs=%d frame_stack=%d B=%d", who, T, n_envs, frame_stack,
-              B);
-    M3L_CHECK(ages, "%s: ages is NULL", who);
-    M3L_CHECK(row_shift >= 0 && row_shift < (long)T * n_envs, "%s: row_shift=%ld outside [0, %ld)", who, row_shift, (long)T * n_envs);
-    ReplayFramesArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rows = rows, a.next_rows = next_rows, a.ages = ages;
-    const long sources = next_rows ? 2L * frame_stack : frame_stack + 1L;
-    a.n_rows = (long)T * n_envs, a.shift = row_shift;
-    a.T = T, a.n_envs = n_envs, a.g.fs = frame_stack;
-    long img_per = 0, tac_per = 0;
-    if (image_frames) {
-        if (gather_image_geom(a.g, who, image_frames, image_u8, H, W, img_lo, img_hi, image)) return 1;
-        M3L_CHECK(image_next, "%s: the next-observation image output is NULL", who);
-        a.img = image_frames, a.img_next = image_next_frames, a.img_out[0] = image, a.img_out[1] = image_next;
-        a.g.img_vec = a.g.img_vec && gather_aligned(image_next, 16) && (!image_next_frames || gather_aligned(image_next_frames, image_u8 ? 4 : 16));
         img_per = sources * gather_image_pieces(a.g);
     }
-    if (tactile_frames) {
-        if (gather_tactile_geom(a.g, who, tactile_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, a.tac_out[0])) return 1;
+    if (tactile_store) {
+        if (gather_tactile_geom(a.g, who, tactile_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, a.tac_out[0])) return 1;
         const int vec = a.g.tac_vec;
         M3L_CHECK(tactile_next_out, "%s: the next-observation tactile outputs are NULL", who);
-        if (gather_tactile_geom(a.g, who, tactile_next_frames ? tactile_next_frames : tactile_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi,
+        if (gather_tactile_geom(a.g, who, tactile_next_store ? tactile_next_store : tactile_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi,
                                 tactile_next_out, a.tac_out[1]))
             return 1;
         a.g.tac_vec = a.g.tac_vec && vec;
-        a.tac = tactile_frames, a.tac_next = tactile_next_frames;
+        a.tac = tactile_store, a.tac_next = tactile_next_store;
         tac_per = sources * gather_tactile_pieces(a.g);
     }
     M3L_CHECK(img_per <= INT32_MAX && tac_per <= INT32_MAX, "%s: sample too large", who);
     a.g.img_per_sample = (int)img_per, a.g.tac_per_sample = (int)tac_per;
     a.img_items = img_per * B, a.tac_items = tac_per * B;
     const long img_blocks = (a.img_items + 255) / 256, tac_blocks = (a.tac_items + 255) / 256;
-    M3L_CHECK(img_blocks + tac_blocks <= INT32_MAX, "%s: B=%d too large", who, B);
-    a.img_blocks = (int)img_blocks;
-    if (next_rows)
-        replay_gather_load_frames_rows2_kernel<<<(unsigned)(img_blocks + tac_blocks), 256, 0, (hipStream_t)stream>>>(a);
+    M3L_CHECK(runs * (img_blocks + tac_blocks) <= INT32_MAX, "%s: B=%d too large", who, B);
+    a.img_blocks = (int)img_blocks, a.half_blocks = (int)(img_blocks + tac_blocks);
+    const unsigned grid = (unsigned)(runs * a.half_blocks);
+    if (!frames && !next_rows)
+        replay_gather_load_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else if (!frames)
+        replay_gather_load_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else if (!next_rows)
+        replay_gather_load_frames_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
     else
-        replay_gather_load_frames_kernel<<<(unsigned)(img_blocks + tac_blocks), 256, 0, (hipStream_t)stream>>>(a);
+        replay_gather_load_frames_rows2_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
     M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+// what m3l_replay_gather_rows and m3l_replay_nstep_rows check alike
+int replay_rows_args_ok(const char* who, const float* actions, const float* rewards, const float* dones, int T, int n_envs, int A,
+                        const int64_t* rows, long row_shift, int B, float reward_scale, float reward_clip, const float* actions_out,
+                        const float* rewards_out, const float* dones_out) {
+    M3L_CHECK(T >= 1 && n_envs >= 1 && A >= 1 && B >= 1, "%s: T=%d n_envs=%d A=%d B=%d", who, T, n_envs, A, B);
+    M3L_CHECK(actions && rewards && dones && rows && actions_out && rewards_out && dones_out, "%s: NULL argument", who);
+    M3L_CHECK(reward_scale >= 0.f && isfinite(reward_scale) && (reward_scale == 0.f || reward_clip >= 0.f), "%s: reward_scale=%g reward_clip=%g", who,
+              (double)reward_scale, (double)reward_clip);
+    M3L_CHECK(row_shift >= 0 && row_shift < (long)T * n_envs, "%s: row_shift=%ld outside [0, %ld)", who, row_shift, (long)T * n_envs);
     return 0;
 }
 
@@ -717,9 +656,9 @@ int m3l_replay_gather_load(const void* image_store, const void* image_next_store
                            float* image, float* image_next, const void* tactile_store, const void* tactile_next_store, int tactile_u8, int th, int tw,
                            int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out, float* const* tactile_next_out, int T, int n_envs,
                            int frame_stack, const int64_t* rows, long row_shift, int B, void* stream) {
-    return replay_load_launch("replay_gather_load", image_store, image_next_store, image_u8, H, W, img_lo, img_hi, image, image_next, tactile_store,
-                              tactile_next_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, T, n_envs, frame_stack,
-                              rows, row_shift, nullptr, B, stream);
+    return replay_gather_launch("replay_gather_load", image_store, image_next_store, image_u8, H, W, img_lo, img_hi, image, image_next, tactile_store,
+                                tactile_next_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, nullptr, T, n_envs,
+                                frame_stack, rows, row_shift, nullptr, B, stream);
 }
 
 int m3l_replay_gather_load_rows2(const void* image_store, const void* image_next_store, int image_u8, int H, int W, double img_lo, double img_hi,
@@ -727,9 +666,9 @@ int m3l_replay_gather_load_rows2(const void* image_store, const void* image_next
                                  int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out, float* const* tactile_next_out, int T,
                                  int n_envs, int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, int B, void* stream) {
     M3L_CHECK(next_rows, "replay_gather_load_rows2: next_rows is NULL");
-    return replay_load_launch("replay_gather_load_rows2", image_store, image_next_store, image_u8, H, W, img_lo, img_hi, image, image_next,
-                              tactile_store, tactile_next_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, T, n_envs,
-                              frame_stack, rows, row_shift, next_rows, B, stream);
+    return replay_gather_launch("replay_gather_load_rows2", image_store, image_next_store, image_u8, H, W, img_lo, img_hi, image, image_next,
+                                tactile_store, tactile_next_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, nullptr,
+                                T, n_envs, frame_stack, rows, row_shift, next_rows, B, stream);
 }
 
 int m3l_replay_gather_load_frames(const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
@@ -737,7 +676,8 @@ int m3l_replay_gather_load_frames(const void* image_frames, const void* image_ne
                                   int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out,
                                   float* const* tactile_next_out, const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* rows,
                                   long row_shift, int B, void* stream) {
-    return replay_frames_launch("replay_gather_load_frames", image_frames, image_next_frames, image_u8, H, W, img_lo, img_hi, image, image_next,
+    M3L_CHECK(ages, "replay_gather_load_frames: ages is NULL");
+    return replay_gather_launch("replay_gather_load_frames", image_frames, image_next_frames, image_u8, H, W, img_lo, img_hi, image, image_next,
                                 tactile_frames, tactile_next_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, ages,
                                 T, n_envs, frame_stack, rows, row_shift, nullptr, B, stream);
 }
@@ -748,7 +688,8 @@ int m3l_replay_gather_load_frames_rows2(const void* image_frames, const void* im
                                         float* const* tactile_out, float* const* tactile_next_out, const int32_t* ages, int T, int n_envs,
                                         int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, int B, void* stream) {
     M3L_CHECK(next_rows, "replay_gather_load_frames_rows2: next_rows is NULL");
-    return replay_frames_launch("replay_gather_load_frames_rows2", image_frames, image_next_frames, image_u8, H, W, img_lo, img_hi, image,
+    M3L_CHECK(ages, "replay_gather_load_frames_rows2: ages is NULL");
+    return replay_gather_launch("replay_gather_load_frames_rows2", image_frames, image_next_frames, image_u8, H, W, img_lo, img_hi, image,
                                 image_next, tactile_frames, tactile_next_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out,
                                 tactile_next_out, ages, T, n_envs, frame_stack, rows, row_shift, next_rows, B, stream);
 }
@@ -756,13 +697,13 @@ int m3l_replay_gather_load_frames_rows2(const void* image_frames, const void* im
 int m3l_replay_gather_rows(const float* actions, const float* rewards, const float* dones, const float* timeouts, int T, int n_envs, int A,
                            const int64_t* rows, long row_shift, int B, float reward_scale, float reward_clip, float* actions_out,
                            float* rewards_out, float* dones_out, int64_t* rows_out, void* stream) {
-    M3L_CHECK(T >= 1 && n_envs >= 1 && A >= 1 && B >= 1, "replay_gather_rows: T=%d n_envs=%d A=%d B=%d", T, n_envs, A, B);
-    M3L_CHECK(actions && rewards && dones && rows && actions_out && rewards_out && dones_out, "replay_gather_rows: NULL argument");
-    M3L_CHECK(reward_scale >= 0.f && isfinite(reward_scale) && (reward_scale == 0.f || reward_clip >= 0.f),
-              "replay_gather_rows: reward_scale=%g reward_clip=%g", (double)reward_scale, (double)reward_clip);
-    M3L_CHECK(row_shift >= 0 && row_shift < (long)T * n_envs, "replay_gather_rows: row_shift=%ld outside [0, %ld)", row_shift, (long)T * n_envs);
-    replay_gather_rows_kernel<<<cdiv((long)B * (A + 3), 256), 256, 0, (hipStream_t)stream>>>(
-        actions, rewards, dones, timeouts, T, n_envs, A, rows, row_shift, B, reward_scale, reward_clip, actions_out, rewards_out, dones_out, rows_out);
+    if (replay_rows_args_ok("replay_gather_rows", actions, rewards, dones, T, n_envs, A, rows, row_shift, B, reward_scale, reward_clip, actions_out,
+                            rewards_out, dones_out))
+        return 1;
+    // a walk of no move: gamma = 1 and newest = 0 are not looked at
+    replay_nstep_rows_kernel<<<cdiv((long)B * (A + 1), 256), 256, 0, (hipStream_t)stream>>>(
+        actions, rewards, dones, timeouts, T, n_envs, A, rows, row_shift, B, reward_scale, reward_clip, 1, 1.f, 0, actions_out, rewards_out, dones_out,
+        nullptr, rows_out, nullptr);
     M3L_LAUNCH_CHECK();
     return 0;
 }
@@ -771,12 +712,10 @@ int m3l_replay_nstep_rows(const float* actions, const float* rewards, const floa
                           const int64_t* rows, long row_shift, int B, float reward_scale, float reward_clip, int n_steps, float gamma, int newest,
                           float* actions_out, float* rewards_out, float* dones_out, float* discounts_out, int64_t* rows_out, int64_t* next_rows_out,
                           void* stream) {
-    M3L_CHECK(T >= 1 && n_envs >= 1 && A >= 1 && B >= 1, "replay_nstep_rows: T=%d n_envs=%d A=%d B=%d", T, n_envs, A, B);
-    M3L_CHECK(actions && rewards && dones && rows && actions_out && rewards_out && dones_out && discounts_out && rows_out && next_rows_out,
-              "replay_nstep_rows: NULL argument");
-    M3L_CHECK(reward_scale >= 0.f && isfinite(reward_scale) && (reward_scale == 0.f || reward_clip >= 0.f),
-              "replay_nstep_rows: reward_scale=%g reward_clip=%g", (double)reward_scale, (double)reward_clip);
-    M3L_CHECK(row_shift >= 0 && row_shift < (long)T * n_envs, "replay_nstep_rows: row_shift=%ld outside [0, %ld)", row_shift, (long)T * n_envs);
+    if (replay_rows_args_ok("replay_nstep_rows", actions, rewards, dones, T, n_envs, A, rows, row_shift, B, reward_scale, reward_clip, actions_out,
+                            rewards_out, dones_out))
+        return 1;
+    M3L_CHECK(discounts_out && rows_out && next_rows_out, "replay_nstep_rows: NULL argument");
     M3L_CHECK(n_steps >= 1 && n_steps <= T, "replay_nstep_rows: n_steps=%d outside [1, T=%d]", n_steps, T);
     M3L_CHECK(gamma > 0.f && gamma <= 1.f, "replay_nstep_rows: gamma=%g outside (0, 1]", (double)gamma);
     M3L_CHECK(newest >= 0 && newest < T, "replay_nstep_rows: newest=%d outside [0, T=%d)", newest, T);

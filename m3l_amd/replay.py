@@ -73,6 +73,47 @@ def _check_next_rows(who, next_rows, rows):
         raise ValueError(f"{who}: next_rows must be a contiguous int64 tensor of rows' shape {tuple(rows.shape)}")
 
 
+def _gather_load(who, kind, image, tactile, rows, image_next, tactile_next, image_normalization, tactile_normalization, row_shift, next_rows,
+                 ages=None, frame_stack=None):
+    """What `gather_load` (kind "store") and `gather_load_frames` (kind "frames": ages and frame_stack are its own) share: the checks, the
+    outputs, the argument list and the entry point, one-list or rows2."""
+    frames = kind == "frames"
+    ref = image if image is not None else tactile
+    if ref is None:
+        raise ValueError(f"{who}: neither an image nor a tactile {'frame store' if frames else 'store'}")
+    for name, t, nxt in (("image", image, image_next), ("tactile", tactile, tactile_next)):
+        for what, x in ((f"{name}_{kind}", t), (f"{name}_next_{kind}", nxt)):
+            if x is not None:
+                _require_cuda(x, f"{who}: {what}")
+        if nxt is not None and (t is None or nxt.shape != t.shape or nxt.dtype != t.dtype or not nxt.is_contiguous()):
+            raise ValueError(f"{who}: {name}_next_{kind} must be a contiguous tensor of {name}_{kind}'{'' if frames else 's'} shape and dtype")
+    _check_rows(who, rows)
+    if next_rows is not None:
+        _check_next_rows(who, next_rows, rows)
+    if frames:
+        fs = int(frame_stack)
+        if fs < 1:
+            raise ValueError(f"{who}: frame_stack={frame_stack}")
+        T, n_envs, H, W, th, tw, S = _check_stores(who, image, tactile, frames=True)
+        _require_cuda(ages, who + ": ages")
+        if ages.dtype != torch.int32 or tuple(ages.shape) != (T, n_envs) or not ages.is_contiguous():
+            raise ValueError(f"{who}: ages must be a contiguous int32 tensor of shape (T, n_envs) = {(T, n_envs)}")
+    else:
+        T, n_envs, fs, H, W, th, tw, S = _check_stores(who, image, tactile)
+    B = rows.shape[0]
+    img, tacs = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
+    img_next, tacs_next = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
+    args = (L.ptr(image), L.ptr(image_next), int(image is not None and image.dtype == torch.uint8), H, W, float(image_normalization[0]),
+            float(image_normalization[1]), L.ptr(img), L.ptr(img_next), L.ptr(tactile), L.ptr(tactile_next),
+            int(tactile is not None and tactile.dtype == torch.uint8), th, tw, S, float(tactile_normalization[0]), float(tactile_normalization[1]),
+            L.ptr_array(tacs), L.ptr_array(tacs_next)) + ((L.ptr(ages),) if frames else ()) + (T, n_envs, fs, L.ptr(rows), int(row_shift))
+    entry = "m3l_replay_gather_load" + ("_frames" if frames else "")
+    if next_rows is not None:
+        entry, args = entry + "_rows2", args + (L.ptr(next_rows),)
+    L.check(getattr(L.lib(), entry)(*args, B, _stream()), entry)
+    return _as_loaded(img, tacs), _as_loaded(img_next, tacs_next)
+
+
 def gather_load(image_store, tactile_store, rows, image_next_store=None, tactile_next_store=None, image_normalization=(0, 1),
                 tactile_normalization=(-1, 1), row_shift=0, next_rows=None):
     """image_store (T, n_envs, fs, H, W, 3) and / or tactile_store (T, n_envs, fs, 3*S, h, w), uint8 or float32 CUDA tensors, and rows (B) int64
@@ -81,32 +122,8 @@ def gather_load(image_store, tactile_store, rows, image_next_store=None, tactile
     from `*_next_store` at the same row, or without one from the store itself at step (t + 1) % T.
     next_rows (B) int64: the next observations are those of these store rows instead, taken as they are — row_shift applies to rows alone —
     and an entry outside [0, T n_envs) gives NaN in that half only (m3l_replay_gather_load_rows2)."""
-    ref = image_store if image_store is not None else tactile_store
-    if ref is None:
-        raise ValueError("replay.gather_load: neither an image nor a tactile store")
-    pairs = (("image", image_store, image_next_store), ("tactile", tactile_store, tactile_next_store))
-    for name, t, nxt in pairs:
-        for what, x in ((name + "_store", t), (name + "_next_store", nxt)):
-            if x is not None:
-                _require_cuda(x, "replay.gather_load: " + what)
-        if nxt is not None and (t is None or nxt.shape != t.shape or nxt.dtype != t.dtype or not nxt.is_contiguous()):
-            raise ValueError(f"replay.gather_load: {name}_next_store must be a contiguous tensor of {name}_store's shape and dtype")
-    _check_rows("replay.gather_load", rows)
-    if next_rows is not None:
-        _check_next_rows("replay.gather_load", next_rows, rows)
-    T, n_envs, fs, H, W, th, tw, S = _check_stores("replay.gather_load", image_store, tactile_store)
-    B = rows.shape[0]
-    img, tacs = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
-    img_next, tacs_next = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
-    head = (L.ptr(image_store), L.ptr(image_next_store), int(image_store is not None and image_store.dtype == torch.uint8), H, W,
-            float(image_normalization[0]), float(image_normalization[1]), L.ptr(img), L.ptr(img_next), L.ptr(tactile_store), L.ptr(tactile_next_store),
-            int(tactile_store is not None and tactile_store.dtype == torch.uint8), th, tw, S, float(tactile_normalization[0]),
-            float(tactile_normalization[1]), L.ptr_array(tacs), L.ptr_array(tacs_next), T, n_envs, fs, L.ptr(rows), int(row_shift))
-    if next_rows is None:
-        L.check(L.lib().m3l_replay_gather_load(*head, B, _stream()), "m3l_replay_gather_load")
-    else:
-        L.check(L.lib().m3l_replay_gather_load_rows2(*head, L.ptr(next_rows), B, _stream()), "m3l_replay_gather_load_rows2")
-    return _as_loaded(img, tacs), _as_loaded(img_next, tacs_next)
+    return _gather_load("replay.gather_load", "store", image_store, tactile_store, rows, image_next_store, tactile_next_store, image_normalization,
+                        tactile_normalization, row_shift, next_rows)
 
 
 def gather_load_frames(image_frames, tactile_frames, ages, rows, image_next_frames=None, tactile_next_frames=None, image_normalization=(0, 1),
@@ -120,72 +137,12 @@ def gather_load_frames(image_frames, tactile_frames, ages, rows, image_next_fram
     next_rows (B) int64: the next observations are those of these store rows instead, taken as they are, each with its own age: 2 *
     frame_stack source frames per sample, every one written once (m3l_replay_gather_load_frames_rows2); an entry outside [0, T n_envs)
     gives NaN in that half only."""
-    who = "replay.gather_load_frames"
-    ref = image_frames if image_frames is not None else tactile_frames
-    if ref is None:
-        raise ValueError(who + ": neither an image nor a tactile frame store")
-    pairs = (("image", image_frames, image_next_frames), ("tactile", tactile_frames, tactile_next_frames))
-    for name, t, nxt in pairs:
-        for what, x in ((name + "_frames", t), (name + "_next_frames", nxt)):
-            if x is not None:
-                _require_cuda(x, f"{who}: {what}")
-        if nxt is not None and (t is None or nxt.shape != t.shape or nxt.dtype != t.dtype or not nxt.is_contiguous()):
-            raise ValueError(f"{who}: {name}_next_frames must be a contiguous tensor of {name}_frames' shape and dtype")
-    _check_rows(who, rows)
-    if next_rows is not None:
-        _check_next_rows(who, next_rows, rows)
-    fs = int(frame_stack)
-    if fs < 1:
-        raise ValueError(f"{who}: frame_stack={frame_stack}")
-    T, n_envs, H, W, th, tw, S = _check_stores(who, image_frames, tactile_frames, frames=True)
-    _require_cuda(ages, who + ": ages")
-    if ages.dtype != torch.int32 or tuple(ages.shape) != (T, n_envs) or not ages.is_contiguous():
-        raise ValueError(f"{who}: ages must be a contiguous int32 tensor of shape (T, n_envs) = {(T, n_envs)}")
-    B = rows.shape[0]
-    img, tacs = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
-    img_next, tacs_next = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
-    head = (L.ptr(image_frames), L.ptr(image_next_frames), int(image_frames is not None and image_frames.dtype == torch.uint8), H, W,
-            float(image_normalization[0]), float(image_normalization[1]), L.ptr(img), L.ptr(img_next), L.ptr(tactile_frames),
-            L.ptr(tactile_next_frames), int(tactile_frames is not None and tactile_frames.dtype == torch.uint8), th, tw, S,
-            float(tactile_normalization[0]), float(tactile_normalization[1]), L.ptr_array(tacs), L.ptr_array(tacs_next), L.ptr(ages), T, n_envs, fs,
-            L.ptr(rows), int(row_shift))
-    if next_rows is None:
-        L.check(L.lib().m3l_replay_gather_load_frames(*head, B, _stream()), "m3l_replay_gather_load_frames")
-    else:
-        L.check(L.lib().m3l_replay_gather_load_frames_rows2(*head, L.ptr(next_rows), B, _stream()), "m3l_replay_gather_load_frames_rows2")
-    return _as_loaded(img, tacs), _as_loaded(img_next, tacs_next)
+    return _gather_load("replay.gather_load_frames", "frames", image_frames, tactile_frames, rows, image_next_frames, tactile_next_frames,
+                        image_normalization, tactile_normalization, row_shift, next_rows, ages, frame_stack)
 
 
-def gather_rows(actions, rewards, dones, timeouts, rows, reward_scale=0.0, reward_clip=0.0, row_shift=0, return_rows=False):
-    """actions (T, n_envs, A) and rewards / dones / timeouts (T, n_envs) float32 CUDA tensors (timeouts may be None), rows (B) int64 ->
-    actions (B, A), rewards (B, 1), dones (B, 1) in one launch (m3l_replay_gather_rows): dones * (1 - timeouts), and with reward_scale > 0
-    clip(rewards / reward_scale, -reward_clip, reward_clip).  return_rows: also the (B) int64 rows read, (rows + row_shift) % (T n_envs)."""
-    for t in (actions, rewards, dones, timeouts):
-        if t is not None:
-            _require_cuda(t, "replay.gather_rows: every argument")
-    _check_rows("replay.gather_rows", rows)
-    T, n_envs, A = actions.shape
-    B = rows.shape[0]
-    for t in (actions, rewards, dones, timeouts):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape[:2]) != (T, n_envs)):
-            raise ValueError("replay.gather_rows: contiguous float32 (T, n_envs, ...) tensors expected")
-    dev = actions.device
-    out = [torch.empty(B, A, dtype=torch.float32, device=dev), torch.empty(B, 1, dtype=torch.float32, device=dev),
-           torch.empty(B, 1, dtype=torch.float32, device=dev)]
-    rows_out = torch.empty(B, dtype=torch.int64, device=dev) if return_rows else None
-    L.check(L.lib().m3l_replay_gather_rows(L.ptr(actions), L.ptr(rewards), L.ptr(dones), L.ptr(timeouts), T, n_envs, A, L.ptr(rows), int(row_shift), B,
-                                           float(reward_scale), float(reward_clip), *[L.ptr(t) for t in out], L.ptr(rows_out), _stream()),
-            "m3l_replay_gather_rows")
-    return tuple(out) + ((rows_out,) if return_rows else ())
-
-
-def nstep_rows(actions, rewards, dones, timeouts, rows, n_steps, gamma, newest, reward_scale=0.0, reward_clip=0.0, row_shift=0):
-    """`gather_rows` for n-step returns (m3l_replay_nstep_rows, one launch): from step t of every row the walk goes up to n_steps - 1 steps
-    towards newer ones in the ring and ends at the first done, at step `newest` (the step written last) or after n_steps - 1 moves ->
-    actions (B, A) of the rows; rewards (B, 1), the sum of gamma^k times the (normalised) rewards along the walk; dones (B, 1) of the last step,
-    masked by its timeout; discounts (B, 1), gamma^(steps walked + 1); rows (B) and next_rows (B) int64, the rows of the first and the last
-    step.  n_steps = 1 gives `gather_rows`' bits and discounts = float32(gamma).  A row outside [0, T n_envs) gives NaN and -1."""
-    who = "replay.nstep_rows"
+def _scalar_rows(who, actions, rewards, dones, timeouts, rows, reward_scale, reward_clip, row_shift, nstep=None, return_rows=True):
+    """What `gather_rows` (nstep None) and `nstep_rows` (nstep = (n_steps, gamma, newest)) share: the checks, the outputs and the launch."""
     for t in (actions, rewards, dones, timeouts):
         if t is not None:
             _require_cuda(t, who + ": every argument")
@@ -195,19 +152,43 @@ def nstep_rows(actions, rewards, dones, timeouts, rows, n_steps, gamma, newest, 
     for t in (actions, rewards, dones, timeouts):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape[:2]) != (T, n_envs)):
             raise ValueError(who + ": contiguous float32 (T, n_envs, ...) tensors expected")
+    dev = actions.device
+    out = [torch.empty(B, A, dtype=torch.float32, device=dev)] + [torch.empty(B, 1, dtype=torch.float32, device=dev) for _ in range(2)]
+    head = (L.ptr(actions), L.ptr(rewards), L.ptr(dones), L.ptr(timeouts), T, n_envs, A, L.ptr(rows), int(row_shift), B, float(reward_scale),
+            float(reward_clip))
+    if nstep is None:
+        rows_out = [torch.empty(B, dtype=torch.int64, device=dev)] if return_rows else []
+        L.check(L.lib().m3l_replay_gather_rows(*head, *[L.ptr(t) for t in out], L.ptr(rows_out[0]) if return_rows else None, _stream()),
+                "m3l_replay_gather_rows")
+        return tuple(out + rows_out)
+    n_steps, gamma, newest = nstep
     if int(n_steps) != n_steps or not 1 <= int(n_steps) <= T:
         raise ValueError(f"{who}: n_steps={n_steps} must be an integer in [1, {T}], the steps of the ring")
     if not 0.0 < float(gamma) <= 1.0:
         raise ValueError(f"{who}: gamma={gamma} must lie in (0, 1]")
     if int(newest) != newest or not 0 <= int(newest) < T:
         raise ValueError(f"{who}: newest={newest} must be a step of the ring, in [0, {T})")
-    dev = actions.device
-    out = [torch.empty(B, A, dtype=torch.float32, device=dev)] + [torch.empty(B, 1, dtype=torch.float32, device=dev) for _ in range(3)]
-    out += [torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2)]
-    L.check(L.lib().m3l_replay_nstep_rows(L.ptr(actions), L.ptr(rewards), L.ptr(dones), L.ptr(timeouts), T, n_envs, A, L.ptr(rows), int(row_shift), B,
-                                          float(reward_scale), float(reward_clip), int(n_steps), float(gamma), int(newest),
-                                          *[L.ptr(t) for t in out], _stream()), "m3l_replay_nstep_rows")
+    out += [torch.empty(B, 1, dtype=torch.float32, device=dev)] + [torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2)]
+    L.check(L.lib().m3l_replay_nstep_rows(*head, int(n_steps), float(gamma), int(newest), *[L.ptr(t) for t in out], _stream()),
+            "m3l_replay_nstep_rows")
     return tuple(out)
+
+
+def gather_rows(actions, rewards, dones, timeouts, rows, reward_scale=0.0, reward_clip=0.0, row_shift=0, return_rows=False):
+    """actions (T, n_envs, A) and rewards / dones / timeouts (T, n_envs) float32 CUDA tensors (timeouts may be None), rows (B) int64 ->
+    actions (B, A), rewards (B, 1), dones (B, 1) in one launch (m3l_replay_gather_rows): dones * (1 - timeouts), and with reward_scale > 0
+    clip(rewards / reward_scale, -reward_clip, reward_clip).  return_rows: also the (B) int64 rows read, (rows + row_shift) % (T n_envs).  A row
+    outside [0, T n_envs) gives NaN and -1."""
+    return _scalar_rows("replay.gather_rows", actions, rewards, dones, timeouts, rows, reward_scale, reward_clip, row_shift, None, return_rows)
+
+
+def nstep_rows(actions, rewards, dones, timeouts, rows, n_steps, gamma, newest, reward_scale=0.0, reward_clip=0.0, row_shift=0):
+    """`gather_rows` for n-step returns (m3l_replay_nstep_rows, one launch): from step t of every row the walk goes up to n_steps - 1 steps
+    towards newer ones in the ring and ends at the first done, at step `newest` (the step written last) or after n_steps - 1 moves ->
+    actions (B, A) of the rows; rewards (B, 1), the sum of gamma^k times the (normalised) rewards along the walk; dones (B, 1) of the last step,
+    masked by its timeout; discounts (B, 1), gamma^(steps walked + 1); rows (B) and next_rows (B) int64, the rows of the first and the last
+    step.  n_steps = 1 gives `gather_rows`' bits and discounts = float32(gamma).  A row outside [0, T n_envs) gives NaN and -1."""
+    return _scalar_rows("replay.nstep_rows", actions, rewards, dones, timeouts, rows, reward_scale, reward_clip, row_shift, (n_steps, gamma, newest))
 
 
 PER_BLOCK = 1024                        # M3L_PER_BLOCK: rows per block of the priority structure
@@ -533,8 +514,7 @@ class DeviceReplayBuffer:
         sample (`_valid_steps`: the slot the newest next observation lies in, the frame_stack - 1 steps whose history is gone) take 0 — they
         follow step p in the ring, so it is one range of rows — then the blocks that range touches are recomputed (m3l_replay_per_add: two
         launches)."""
-        skip = int(self.optimize_memory_usage) + (self.frame_stack - 1 if self.frame_dedup else 0)
-        n_zero = skip * self.n_envs if self.full else 0
+        n_zero = self._skipped_steps() * self.n_envs if self.full else 0
         L.check(L.lib().m3l_replay_per_add(L.ptr(self.mass), L.ptr(self.block_mass), L.ptr(self.block_min), L.ptr(self.max_priority),
                                            self.buffer_size * self.n_envs, p * self.n_envs, self.n_envs, n_zero, self.alpha, _stream()),
                 "m3l_replay_per_add")
@@ -580,11 +560,15 @@ class DeviceReplayBuffer:
         return cur
 
     # ---- sampling
+    def _skipped_steps(self):
+        """The oldest steps that a full ring does not sample: step `pos` in the single-store mode — the newest next observation lies there —
+        and with frame_dedup the frame_stack - 1 steps after it, whose stacks reach frames that the newest steps overwrote."""
+        return int(self.optimize_memory_usage) + (self.frame_stack - 1 if self.frame_dedup else 0)
+
     def _valid_steps(self):
-        """The steps a sample may come from, as (first, count) in the ring: count steps starting at `first`, modulo buffer_size.  A full ring
-        leaves out step `pos` in the single-store mode — the newest next observation lies there — and with frame_dedup the frame_stack - 1
-        oldest steps after it, whose stacks reach frames that the newest steps overwrote."""
-        skip = int(self.optimize_memory_usage) + (self.frame_stack - 1 if self.frame_dedup else 0)
+        """The steps a sample may come from, as (first, count) in the ring: count steps starting at `first`, modulo buffer_size: all that were
+        written but a full ring's `_skipped_steps()`."""
+        skip = self._skipped_steps()
         if self.full and skip:
             return (self.pos + skip) % self.buffer_size, self.buffer_size - skip
         return 0, self.size()
@@ -623,69 +607,55 @@ class DeviceReplayBuffer:
         if count < 1:
             raise ValueError("DeviceReplayBuffer.sample: the buffer is empty" if self.size() == 0 else
                              "DeviceReplayBuffer.sample: a full single-store buffer of one step holds no transition")
+        weights = None
         if self.prioritized:
-            return self._sample_prioritized(batch_size, indices, beta, u, scale, clip)
-        if indices is not None:
+            draw, weights = self._draw_prioritized(batch_size, indices, beta, u)
+            shift = 0
+        elif indices is not None:
             draw, shift = self._injected(indices), 0
         else:
             if int(batch_size) < 1:
                 raise ValueError(f"DeviceReplayBuffer.sample: batch_size={batch_size}")
             # rows relative to the first valid step; the kernels add `shift` modulo T n_envs
             draw, shift = torch.randint(0, count * self.n_envs, (int(batch_size),), device=self.device), first * self.n_envs
-        if self.n_steps > 1:
-            return self._sample_nstep(draw, shift, scale, clip)
-        if self.frame_dedup:
-            nxt = self.next_frames or {}
-            obs, next_obs = gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, draw, nxt.get("image"),
-                                               nxt.get("tactile"), self.image_normalization, self.tactile_normalization, shift,
-                                               frame_stack=self.frame_stack)
+        if self.prioritized or self.n_steps > 1:
+            newest = (self.pos - 1) % self.buffer_size
+            actions, rewards, dones, discounts, rows, next_rows = nstep_rows(self.actions, self.rewards, self.dones, self.timeouts, draw, self.n_steps,
+                                                                             self.gamma, newest, scale, clip, shift)
         else:
-            nxt = self.next_observations or {}
-            obs, next_obs = gather_load(self.observations.get("image"), self.observations.get("tactile"), draw, nxt.get("image"), nxt.get("tactile"),
-                                        self.image_normalization, self.tactile_normalization, shift)
-        actions, rewards, dones, rows = gather_rows(self.actions, self.rewards, self.dones, self.timeouts, draw, scale, clip, shift, return_rows=True)
+            actions, rewards, dones, rows = gather_rows(self.actions, self.rewards, self.dones, self.timeouts, draw, scale, clip, shift, return_rows=True)
+        # n_steps = 1: next_rows == rows where there are any, and the one-list gathers run
+        obs, next_obs = self._gather(draw, shift, next_rows if self.n_steps > 1 else None)
+        if self.prioritized:
+            return PrioritizedReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows, weights)
+        if self.n_steps > 1:
+            return NStepReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows)
         return ReplayBatch(obs, actions, next_obs, dones, rewards, rows)
 
-    def _sample_nstep(self, draw, shift, scale, clip):
-        newest = (self.pos - 1) % self.buffer_size
-        actions, rewards, dones, discounts, rows, next_rows = nstep_rows(self.actions, self.rewards, self.dones, self.timeouts, draw, self.n_steps,
-                                                                         self.gamma, newest, scale, clip, shift)
+    def _gather(self, rows, shift, next_rows):
+        """(observations, next_observations) of rows (+ shift in the ring) from the frame or the stacked stores, in one launch; next_rows: the
+        next observations are those rows' (n-step returns), else None."""
         if self.frame_dedup:
-            obs, next_obs = gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, draw, self.next_frames.get("image"),
-                                               self.next_frames.get("tactile"), self.image_normalization, self.tactile_normalization, shift,
-                                               next_rows, frame_stack=self.frame_stack)
-        else:
-            obs, next_obs = gather_load(self.observations.get("image"), self.observations.get("tactile"), draw, self.next_observations.get("image"),
-                                        self.next_observations.get("tactile"), self.image_normalization, self.tactile_normalization, shift, next_rows)
-        return NStepReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows)
+            nxt = self.next_frames or {}
+            return gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, rows, nxt.get("image"), nxt.get("tactile"),
+                                      self.image_normalization, self.tactile_normalization, shift, next_rows, frame_stack=self.frame_stack)
+        nxt = self.next_observations or {}
+        return gather_load(self.observations.get("image"), self.observations.get("tactile"), rows, nxt.get("image"), nxt.get("tactile"),
+                           self.image_normalization, self.tactile_normalization, shift, next_rows)
 
     # ---- prioritised replay
-    def _sample_prioritized(self, batch_size, indices, beta, u, scale, clip):
+    def _draw_prioritized(self, batch_size, indices, beta, u):
+        """-> (rows, weights): the rows of `indices`, or drawn in proportion to `mass` from u (None: one torch.rand), and their weights."""
         beta = self.beta if beta is None else _check_unit("DeviceReplayBuffer.sample", "beta", beta)
         if indices is not None:
             if u is not None:
                 raise ValueError("DeviceReplayBuffer.sample: indices and u both name the rows")
-            rows, weights = per_sample(self.mass, self.block_mass, self.block_min, None, beta, rows=self._injected(indices))
-        else:
-            if u is None:
-                if int(batch_size) < 1:
-                    raise ValueError(f"DeviceReplayBuffer.sample: batch_size={batch_size}")
-                u = torch.rand(int(batch_size), dtype=torch.float32, device=self.device)
-            rows, weights = per_sample(self.mass, self.block_mass, self.block_min, u, beta)
-        newest = (self.pos - 1) % self.buffer_size
-        actions, rewards, dones, discounts, rows, next_rows = nstep_rows(self.actions, self.rewards, self.dones, self.timeouts, rows, self.n_steps,
-                                                                         self.gamma, newest, scale, clip)
-        second = next_rows if self.n_steps > 1 else None        # n_steps = 1: next_rows == rows, and the one-list gathers are the default buffer's
-        if self.frame_dedup:
-            nxt = self.next_frames or {}
-            obs, next_obs = gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, rows, nxt.get("image"),
-                                               nxt.get("tactile"), self.image_normalization, self.tactile_normalization, 0, second,
-                                               frame_stack=self.frame_stack)
-        else:
-            nxt = self.next_observations or {}
-            obs, next_obs = gather_load(self.observations.get("image"), self.observations.get("tactile"), rows, nxt.get("image"), nxt.get("tactile"),
-                                        self.image_normalization, self.tactile_normalization, 0, second)
-        return PrioritizedReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows, weights)
+            return per_sample(self.mass, self.block_mass, self.block_min, None, beta, rows=self._injected(indices))
+        if u is None:
+            if int(batch_size) < 1:
+                raise ValueError(f"DeviceReplayBuffer.sample: batch_size={batch_size}")
+            u = torch.rand(int(batch_size), dtype=torch.float32, device=self.device)
+        return per_sample(self.mass, self.block_mass, self.block_min, u, beta)
 
     def update_priorities(self, rows, td_errors):
         """The priorities of the sampled `rows` (B) int64 from their TD errors (B,) or (B, 1), float32 on the device (`per_update`, two launches,

@@ -227,6 +227,29 @@ def test_gather_rows_bit_equal_to_index_select(A, B):
         assert torch.equal(got.cpu(), torch.from_numpy(want[k])), k
 
 
+@pytest.mark.parametrize("A", [1, 7])
+@pytest.mark.parametrize("return_rows", [False, True])
+def test_gather_rows_out_of_range_rows(A, return_rows):
+    """Rows -1 and T n_envs among B = 5: NaN in the three float outputs and -1 in `rows`, every entry in range bit-equal to index_select.  The
+    kernel's `rows` output is optional: with and without it."""
+    _, d = _scalars(A, 80 + A)
+    rows = [0, -1, T * E - 1, T * E, 2]
+    dr = torch.tensor(rows, dtype=torch.int64, device=DEV)
+    got = P.gather_rows(d["actions"], d["rewards"], d["dones"], d["timeouts"], dr, return_rows=return_rows)
+    assert len(got) == 3 + return_rows
+    actions, rewards, dones = got[:3]
+    assert actions.shape == (5, A) and rewards.shape == (5, 1) and dones.shape == (5, 1)
+    bad = torch.tensor([r < 0 or r >= T * E for r in rows], device=DEV)
+    assert bad.sum() == 2
+    ok = dr[~bad]
+    assert torch.isnan(actions[bad]).all() and torch.isnan(rewards[bad]).all() and torch.isnan(dones[bad]).all()
+    assert torch.equal(actions[~bad], _flat(d["actions"]).index_select(0, ok))
+    assert torch.equal(rewards[~bad, 0], _flat(d["rewards"]).index_select(0, ok))
+    assert torch.equal(dones[~bad, 0], (_flat(d["dones"]) * (1 - _flat(d["timeouts"]))).index_select(0, ok))
+    if return_rows:
+        assert got[3].dtype == torch.int64 and got[3].tolist() == [0, -1, T * E - 1, -1, 2]
+
+
 def test_normalised_rewards():
     sc, d = _scalars(2, 91)
     var, eps, clip = 3.7, 1e-8, 1.25
