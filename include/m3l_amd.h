@@ -362,9 +362,11 @@ int m3l_extractor_bwd_dropout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int 
                               const m3l_dropout* head_drop, void* stream);
 
 /* ---- EarlyCNN stem (early_conv_masking=True, the reference's default flag; pretrain_models.py:37-56,180-191): three
- * Conv2d+ReLU and a 1x1 Conv2d as im2col + MFMA GEMM.  srcs: nsrc NCHW f32 inputs of B samples each (the tactile sensors share
- * one stem; they are processed as one batch of nsrc*B).  tensors / grads: {conv1.w, conv1.b, ..., conv4.w, conv4.b}.
- * out: f32 (nsrc*B, h*w, dim) stem tokens (source-major). */
+ * Conv2d+ReLU and a 1x1 Conv2d.  The three Conv2d+ReLU run as direct (implicit-GEMM) convolutions in bf16 at the channel counts conv.hip
+ * has kernels for (dim 64 / 128 / 256; m3l_set_direct_conv below), otherwise, and always in fp32, as im2col + MFMA GEMM; the 1x1 is a GEMM
+ * on both paths.  The kernels of both paths are exported one by one as m3l_op_conv_* / m3l_op_im2col / m3l_op_col2im_relu ("raw kernels").
+ * srcs: nsrc NCHW f32 inputs of B samples each (the tactile sensors share one stem; they are processed as one batch of nsrc*B).
+ * tensors / grads: {conv1.w, conv1.b, ..., conv4.w, conv4.b}.  out: f32 (nsrc*B, h*w, dim) stem tokens (source-major). */
 typedef struct m3l_cnn_cfg {
     int in_channels, height, width, dim;
     int tactile;             /* 0: image stem (conv3 4/2/1), 1: tactile stem (conv3 3/1/1) */
@@ -501,6 +503,43 @@ int m3l_op_attn_bwd_dh(int dtype, const void* qkv, const void* o, const void* dO
                        int n, int H, void* stream, int dim_head);
 /* the dropout mask of site `site` of layer `layer` ("Dropout" above) for a (rows, N) tensor: out[row * N + c] = 1 kept / 0 dropped */
 int m3l_op_dropout_mask(float p, uint64_t seed, int layer, int site, long rows, int N, uint8_t* out, void* stream);
+/* (ABI 416) the EarlyCNN stem's kernels one by one: the direct convolutions (conv.hip: forward, weight gradient, input gradient, weight copies) and
+ * the lowering kernels of the im2col path (column matrix and its adjoint).  One layer is Conv2d(Ci, Co, k, stride s, padding p) + ReLU on an H x W
+ * input, output OH x OW = (H + 2 p - k) / s + 1 by (W + 2 p - k) / s + 1.  The direct kernels are bf16 and exist for the two kinds 4 / 2 / 1 and
+ * 3 / 1 / 1 at the channel counts m3l_op_conv_supported accepts: Co a multiple of 8 up to 128, Ci <= 64 (a multiple of 8 unless the layer is a
+ * first layer), (ceil(Co / 16), ceil(Ci / 16)) one of (1,1) (2,1) (4,2) (8,4).  That is every layer of the stems of dim 64 / 128 / 256 and the first
+ * two of dim 192; its third, (Ci, Co) = (48, 96), is (8,3) and has none, so the dim-192 stem as a whole runs im2col + GEMM.
+ *   input    srcs: host array of nsrc device pointers.  nchw != 0: NCHW f32 frames, Bsrc samples per source, sources concatenated on batch
+ *            (B = nsrc Bsrc, nsrc in 1..8: a first layer); nchw == 0: one NHWC activation [Bsrc, H, W, Ci] of the compute type (nsrc == 1).
+ *   sizes    wf_bytes = 2 * 16 MT * Kp, MT = 1 / 2 / 4 / 8 for Co <= 16 / 32 / 64 / 128, Kp = k k Cip rounded up to 32, Cip = Ci rounded up to 16;
+ *            wd_bytes = 2 * classes * Cip * tpc * Co, (classes, tpc) = (4, 4) for 4 / 2 / 1 and (1, 9) for 3 / 1 / 1;
+ *            slab_bytes = 4 * G * Co Ci k k, G = min(tiles, max(128, 2^24 / (Co Ci k k))) groups of the B ceil(OH / 8) ceil(OW / 8) output tiles.
+ *   prep     W f32 [Co][Ci][k][k] -> Wf bf16 [16 MT][Kp], column (kh k + kw) Cip + ci, zero elsewhere; Wd (NULL: not wanted; needs tpc Co a
+ *            multiple of 32) bf16 [class][Cip][tpc Co], column t Co + co: 4 / 2 / 1: class 2 a + c serves the input pixels of parity (ih & 1, iw & 1) =
+ *            (a, c), its tap t = 2 dh + dw is (kh, kw) = (1 - a + 2 dh, 1 - c + 2 dw); 3 / 1 / 1: one class, t = kh 3 + kw.  Rows ci >= Ci are zero.
+ *   fwd      out bf16 NHWC [B, OH, OW, Co] = relu(conv + bias), fp32 accumulation, one rounding.
+ *   wgrad    dW f32 [Co][Ci][k][k] = sum over batch and output pixels of dY (bf16 NHWC [B, OH, OW, Co]) x input; `slab` (slab_bytes) takes one
+ *            partial sum per group of tiles, reduced in a fixed order: the same bits on every run.
+ *   dgrad    dX bf16 NHWC [B, H, W, Ci] = [act > 0] * (transposed convolution of dY with W), act the layer's bf16 NHWC input.  Not for a first layer.
+ *   im2col   col [B OH OW, Kpad] of `dtype` (0 f32, 1 bf16), column (ci k + kh) k + kw, zeros outside the image and in columns Ci k k .. Kpad - 1;
+ *            any k / s / p.  bf16 with k == 4 and Kpad == 16 Ci takes a kernel of its own that writes 32-byte pieces (col 16-byte aligned).
+ *   col2im_relu  dX [Btot, H, W, Ci] = [act > 0] * the adjoint of im2col applied to dcol [Btot OH OW, Kpad]; dcol, act, dX of `dtype`.
+ * Every call refuses with a message, before any launch: a null pointer, nsrc outside 1..8, an NHWC input with nsrc != 1, an output size below 1,
+ * an odd H or W with 4 / 2 / 1 (the stems never produce one) and, for the direct kernels, channel counts m3l_op_conv_supported rejects.
+ * The stem itself does not call these; they leave m3l_earlycnn_fwd / _bwd and their workspace as they are. */
+int m3l_op_conv_supported(int Ci, int Co, int KH, int S, int P, int first_layer);
+int m3l_op_conv_sizes(int B, int Ci, int H, int W, int Co, int KH, int S, int P, size_t* wf_bytes, size_t* wd_bytes, size_t* slab_bytes);
+int m3l_op_conv_prep(const float* W, int Ci, int Co, int KH, int S, void* Wf, void* Wd, void* stream);
+int m3l_op_conv_fwd(const void* const* srcs, int nsrc, int nchw, int Bsrc, int Ci, int H, int W, int Co, int KH, int S, int P, const void* Wf,
+                    const float* bias, void* out, void* stream);
+int m3l_op_conv_wgrad(const void* const* srcs, int nsrc, int nchw, int Bsrc, int Ci, int H, int W, int Co, int KH, int S, int P, const void* dY,
+                      void* slab, float* dW, void* stream);
+int m3l_op_conv_dgrad(const void* dY, int B, int Ci, int H, int W, int Co, int KH, int S, int P, const void* Wd, const void* act, void* dX,
+                      void* stream);
+int m3l_op_im2col(int dtype, const void* const* srcs, int nsrc, int nchw, int Bsrc, int Ci, int H, int W, int KH, int S, int P, int Kpad, void* col,
+                  void* stream);
+int m3l_op_col2im_relu(int dtype, const void* dcol, int Btot, int Ci, int H, int W, int KH, int S, int P, int Kpad, const void* act, void* dX,
+                       void* stream);
 
 /* ---- DINO self-distillation step (models/vtdino.py, tactile_ssl/model/layers/dino_head.py, tactile_ssl/loss/dino_loss.py, tactile_ssl/utils/ema.py)
  * The head's MLP runs on m3l_op_gemm_nt / m3l_op_gemm_tn / m3l_op_colsum; these are the kernels it adds.  All row-major, f32 unless a dtype says

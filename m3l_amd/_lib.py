@@ -242,6 +242,15 @@ _SIGS = {
     "m3l_replay_per_sample": (c_i, [c_p, c_p, c_p, C.c_long, c_p, c_p, c_i, C.c_float, c_i, c_p, c_p, c_p]),
     "m3l_replay_per_update": (c_i, [c_p, c_p, c_p, c_p, C.c_long, c_p, c_p, c_i, C.c_float, C.c_float, c_p]),
     "m3l_sac_critic_loss_w_fwd": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
+    # the EarlyCNN stem's kernels one by one (ABI 416): direct convolutions and the im2col path's lowering kernels, for the per-kernel tests
+    "m3l_op_conv_supported": (c_i, [c_i] * 6),
+    "m3l_op_conv_sizes": (c_i, [c_i] * 8 + [C.POINTER(c_sz)] * 3),
+    "m3l_op_conv_prep": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "m3l_op_conv_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "m3l_op_conv_wgrad": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "m3l_op_conv_dgrad": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "m3l_op_im2col": (c_i, [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "m3l_op_col2im_relu": (c_i, [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

@@ -349,7 +349,7 @@ int check_tf(const m3l_tf_cfg* c, int B, int n) {
 // =================================================================================================================
 extern "C" {
 
-int m3l_version(void) { return 415; }
+int m3l_version(void) { return 416; }
 
 // diagnostic switch (bench.py's stand-alone roofline figure, PMC passes): 1 = every weight gradient on the caller's stream
 int m3l_set_wgrad_inline(int on) {
@@ -1760,6 +1760,89 @@ int m3l_op_attn_fwd_dh(int dtype, const void* qkv, void* o, float* lse, int B, i
 int m3l_op_attn_bwd_dh(int dtype, const void* qkv, const void* o, const void* dO, const float* lse, float* dsum, void* dqkv, int B,
                        int n, int H, void* stream, int dim_head) {
     return m3l_attn_bwd(dtype, qkv, o, dO, lse, dsum, dqkv, B, n, H, dim_head, (hipStream_t)stream);
+}
+
+// ---- the EarlyCNN stem's convolution and lowering kernels one by one (conv.hip, elementwise.hip), for the per-kernel tests: each export
+// checks its arguments, fills a ConvSrc and calls the launcher the stem calls.  A refusal is a message and a return code, never a launch.
+static int op_conv_shape(const char* what, int B, int Ci, int H, int W, int Co, int KH, int S, int P) {
+    M3L_CHECK(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1 && KH >= 1 && S >= 1 && P >= 0,
+              "%s: bad sizes B=%d Ci=%d H=%d W=%d Co=%d k=%d s=%d p=%d", what, B, Ci, H, W, Co, KH, S, P);
+    M3L_CHECK(H + 2 * P >= KH && W + 2 * P >= KH, "%s: output size below 1 (H=%d W=%d k=%d p=%d)", what, H, W, KH, P);
+    M3L_CHECK(!(KH == 4 && S == 2 && P == 1) || (H % 2 == 0 && W % 2 == 0), "%s: odd H=%d or W=%d with the 4x4 / stride-2 convolution", what, H, W);
+    return 0;
+}
+static int op_conv_src(const char* what, const void* const* srcs, int nsrc, int nchw, ConvSrc* cs) {
+    M3L_CHECK(srcs != nullptr, "%s: null pointer (srcs)", what);
+    M3L_CHECK(nsrc >= 1 && nsrc <= M3L_MAX_SENSORS, "%s: nsrc=%d outside 1..%d", what, nsrc, M3L_MAX_SENSORS);
+    M3L_CHECK(nchw || nsrc == 1, "%s: an NHWC input is one source (nsrc=%d)", what, nsrc);
+    memset(cs, 0, sizeof(*cs));
+    for (int i = 0; i < nsrc; ++i) {
+        M3L_CHECK(srcs[i] != nullptr, "%s: null pointer (srcs[%d])", what, i);
+        cs->src[i] = srcs[i];
+    }
+    cs->nsrc = nsrc; cs->nchw = nchw ? 1 : 0;
+    return 0;
+}
+static int op_conv_direct(const char* what, int Ci, int Co, int KH, int S, int P, int first_layer) {
+    M3L_CHECK(m3l_conv_direct_supported(1, Ci, Co, KH, S, P, first_layer), "%s: no direct convolution for Ci=%d Co=%d k=%d s=%d p=%d (%s input)", what,
+              Ci, Co, KH, S, P, first_layer ? "NCHW f32" : "NHWC bf16");
+    return 0;
+}
+int m3l_op_conv_supported(int Ci, int Co, int KH, int S, int P, int first_layer) { return m3l_conv_direct_supported(1, Ci, Co, KH, S, P, first_layer); }
+int m3l_op_conv_sizes(int B, int Ci, int H, int W, int Co, int KH, int S, int P, size_t* wf_bytes, size_t* wd_bytes, size_t* slab_bytes) {
+    if (op_conv_shape("op_conv_sizes", B, Ci, H, W, Co, KH, S, P)) return 1;
+    M3L_CHECK((KH == 4 && S == 2 && P == 1) || (KH == 3 && S == 1 && P == 1), "op_conv_sizes: k=%d s=%d p=%d is neither 4/2/1 nor 3/1/1", KH, S, P);
+    if (wf_bytes) *wf_bytes = m3l_conv_wf_elems(Ci, Co, KH) * 2;
+    if (wd_bytes) *wd_bytes = m3l_conv_wd_elems(Ci, Co, KH, S) * 2;
+    if (slab_bytes) *slab_bytes = m3l_conv_wgrad_slab_elems(B, Ci, H, W, Co, KH, S, P) * sizeof(float);
+    return 0;
+}
+int m3l_op_conv_prep(const float* W, int Ci, int Co, int KH, int S, void* Wf, void* Wd, void* stream) {
+    M3L_CHECK(W && Wf, "op_conv_prep: null pointer");
+    if (op_conv_direct("op_conv_prep", Ci, Co, KH, S, 1, Wd ? 0 : 1)) return 1;
+    M3L_CHECK(!Wd || ((S == 2 ? 4 : KH * KH) * Co) % 32 == 0, "op_conv_prep: Wd needs taps x Co = %d x %d a multiple of 32", S == 2 ? 4 : KH * KH, Co);
+    return m3l_conv_prep(W, Ci, Co, KH, S, Wf, Wd, (hipStream_t)stream);
+}
+int m3l_op_conv_fwd(const void* const* srcs, int nsrc, int nchw, int Bsrc, int Ci, int H, int W, int Co, int KH, int S, int P, const void* Wf,
+                    const float* bias, void* out, void* stream) {
+    ConvSrc cs;
+    if (op_conv_src("op_conv_fwd", srcs, nsrc, nchw, &cs)) return 1;
+    M3L_CHECK(Wf && bias && out, "op_conv_fwd: null pointer");
+    if (op_conv_shape("op_conv_fwd", Bsrc, Ci, H, W, Co, KH, S, P) || op_conv_direct("op_conv_fwd", Ci, Co, KH, S, P, cs.nchw)) return 1;
+    return m3l_conv_fwd(&cs, Bsrc, Bsrc * nsrc, Ci, H, W, Co, KH, S, P, Wf, bias, out, (hipStream_t)stream);
+}
+int m3l_op_conv_wgrad(const void* const* srcs, int nsrc, int nchw, int Bsrc, int Ci, int H, int W, int Co, int KH, int S, int P, const void* dY,
+                      void* slab, float* dW, void* stream) {
+    ConvSrc cs;
+    if (op_conv_src("op_conv_wgrad", srcs, nsrc, nchw, &cs)) return 1;
+    M3L_CHECK(dY && slab && dW, "op_conv_wgrad: null pointer");
+    if (op_conv_shape("op_conv_wgrad", Bsrc, Ci, H, W, Co, KH, S, P) || op_conv_direct("op_conv_wgrad", Ci, Co, KH, S, P, cs.nchw)) return 1;
+    return m3l_conv_wgrad(&cs, Bsrc, Bsrc * nsrc, Ci, H, W, Co, KH, S, P, dY, (float*)slab, dW, (hipStream_t)stream);
+}
+int m3l_op_conv_dgrad(const void* dY, int B, int Ci, int H, int W, int Co, int KH, int S, int P, const void* Wd, const void* act, void* dX,
+                      void* stream) {
+    M3L_CHECK(dY && Wd && act && dX, "op_conv_dgrad: null pointer");
+    if (op_conv_shape("op_conv_dgrad", B, Ci, H, W, Co, KH, S, P) || op_conv_direct("op_conv_dgrad", Ci, Co, KH, S, P, 0)) return 1;
+    M3L_CHECK(((S == 2 ? 4 : KH * KH) * Co) % 32 == 0, "op_conv_dgrad: taps x Co = %d x %d must be a multiple of 32", S == 2 ? 4 : KH * KH, Co);
+    return m3l_conv_dgrad(dY, B, Ci, H, W, Co, KH, S, P, Wd, act, dX, (hipStream_t)stream);
+}
+int m3l_op_im2col(int dtype, const void* const* srcs, int nsrc, int nchw, int Bsrc, int Ci, int H, int W, int KH, int S, int P, int Kpad, void* col,
+                  void* stream) {
+    ConvSrc cs;
+    M3L_CHECK(dtype == 0 || dtype == 1, "op_im2col: bad dtype %d", dtype);
+    if (op_conv_src("op_im2col", srcs, nsrc, nchw, &cs)) return 1;
+    M3L_CHECK(col, "op_im2col: null pointer");
+    if (op_conv_shape("op_im2col", Bsrc, Ci, H, W, 1, KH, S, P)) return 1;
+    M3L_CHECK(Kpad >= Ci * KH * KH, "op_im2col: Kpad=%d below Ci k k = %d", Kpad, Ci * KH * KH);
+    return m3l_im2col(dtype, &cs, Bsrc, Ci, H, W, KH, S, P, (H + 2 * P - KH) / S + 1, (W + 2 * P - KH) / S + 1, Kpad, col, (hipStream_t)stream);
+}
+int m3l_op_col2im_relu(int dtype, const void* dcol, int Btot, int Ci, int H, int W, int KH, int S, int P, int Kpad, const void* act, void* dX,
+                       void* stream) {
+    M3L_CHECK(dtype == 0 || dtype == 1, "op_col2im_relu: bad dtype %d", dtype);
+    M3L_CHECK(dcol && act && dX, "op_col2im_relu: null pointer");
+    if (op_conv_shape("op_col2im_relu", Btot, Ci, H, W, 1, KH, S, P)) return 1;
+    M3L_CHECK(Kpad >= Ci * KH * KH, "op_col2im_relu: Kpad=%d below Ci k k = %d", Kpad, Ci * KH * KH);
+    return m3l_col2im_relu(dtype, dcol, Btot, Ci, H, W, KH, S, P, (H + 2 * P - KH) / S + 1, (W + 2 * P - KH) / S + 1, Kpad, act, dX, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -263,7 +263,8 @@ def test_fusion_mlp_linear_act(dev, M, K, N):
 
 
 @pytest.mark.parametrize("dim,C,hw,tactile,B,nsrc", [(64, 3, 32, False, 3, 1), (64, 3, 16, True, 2, 2), (128, 6, 64, False, 2, 1), (256, 12, 64, False, 3, 1),
-                                                     (256, 12, 32, True, 2, 2), (128, 3, 40, False, 2, 1), (256, 3, 24, True, 1, 3)])
+                                                     (256, 12, 32, True, 2, 2), (128, 3, 40, False, 2, 1), (256, 3, 24, True, 1, 3),
+                                                     (192, 3, 32, False, 2, 1), (192, 12, 24, True, 1, 2)])
 def test_direct_conv_stem_vs_im2col_and_torch(dev, dim, C, hw, tactile, B, nsrc):
     """conv.hip (direct / implicit-GEMM convolutions of the EarlyCNN stem, models/pretrain_models.py:37-56) against the im2col + GEMM path
     (m3l_set_direct_conv(0)) and against torch's Conv2d in fp64: stem outputs, every weight / bias gradient; output sizes that are not
