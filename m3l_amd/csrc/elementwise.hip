@@ -5,8 +5,8 @@
 // reductions over rows go through per-workgroup partial slabs + a fixed-order reduce (bitwise reproducible).
 #include "common.cuh"
 #include "kernels.h"
+#include <algorithm>
 #include <cstring>
-#include <vector>
 
 namespace {
 
@@ -1475,66 +1475,31 @@ int m3l_colsum(int dtype, const void* Y, int M, int N, int ld, float* part_ws, f
     return m3l_reduce_rows(part_ws, G, N, N, out, accumulate, st);
 }
 
-// Weight-copy batching across the modules of one library call chain (the fused step / extractor chain, mae_step.hip): in COLLECT mode a
-// module's m3l_prep_weights only records its matrices (and the module returns right after it: m3l_prep_mode() == 1); m3l_prep_flush
-// issues them as ONE launch per 64 matrices; in SKIP mode the modules then run with their copies in place.  Thread-local, like the
-// other per-call flags (err.hip).  Four launches of 7-16 us spread over the forward become one or two at its start.
-static thread_local int g_prep_mode = 0;
-static thread_local int g_prep_dtype = -1;
-static thread_local std::vector<WeightDesc>* g_prep_list = nullptr;
-int m3l_prep_mode(void) { return g_prep_mode; }
-void m3l_prep_set_mode(int mode) {
-    g_prep_mode = mode;
-    if (mode == 1) {
-        if (!g_prep_list) g_prep_list = new std::vector<WeightDesc>();
-        g_prep_list->clear();
-        g_prep_dtype = -1;
-    }
-}
-int m3l_prep_flush(hipStream_t st) {
-    const int saved = g_prep_mode;
-    g_prep_mode = 0;
-    int rc = 0;
-    if (g_prep_list && !g_prep_list->empty()) {
-        for (size_t i = 0; i < g_prep_list->size() && !rc; i += M3L_WPACK) {
-            WeightPack pk;
-            memset(&pk, 0, sizeof(pk));
-            for (size_t k = i; k < g_prep_list->size() && k < i + M3L_WPACK; ++k) pk.d[pk.count++] = (*g_prep_list)[k];
-            rc = m3l_prep_weights(g_prep_dtype, &pk, st);
+// Compute-type copies of a list of fp32 master matrices, one launch per M3L_WPACK of them in list order.  A module issues its own list; a fused
+// chain (mae_step.hip) the lists of all its modules: four or five launches of 7-16 us spread over a forward become one or two at its start.
+int m3l_prep_weight_list(int dtype, const WeightList& list, hipStream_t st) {
+    const int count = (int)list.size();
+    for (int first = 0; first < count; first += M3L_WPACK) {
+        WeightPack pack;
+        memset(&pack, 0, sizeof(pack));
+        pack.count = std::min(count - first, M3L_WPACK);
+        int tiles = 0;
+        for (int i = 0; i < pack.count; ++i) {
+            const WeightDesc& d = pack.d[i] = list[first + i];
+            M3L_CHECK(d.ld_dst >= d.cols && d.ld_dstT >= d.rows && d.ld_dst <= ((d.cols + 63) / 64) * 64 && d.ld_dstT <= ((d.rows + 63) / 64) * 64,
+                      "prep_weights: padding of matrix %d ([%d, %d] -> [%d, %d]) must stay inside its last 64 x 64 tiles", first + i, d.rows, d.cols, d.ld_dstT, d.ld_dst);
+            pack.tile0[i] = tiles;
+            tiles += ((d.rows + 63) / 64) * ((d.cols + 63) / 64);
         }
-        g_prep_list->clear();
+        pack.tile0[pack.count] = tiles;
+        if (tiles == 0) continue;
+        ProfScope prof("prep_weights", pack.count, dtype, 0, 0.0, st);
+        if (dtype == 1)
+            prep_weights_kernel<bf16><<<tiles, 256, 0, st>>>(pack);
+        else
+            prep_weights_kernel<float><<<tiles, 256, 0, st>>>(pack);
+        M3L_LAUNCH_CHECK();
     }
-    g_prep_mode = saved;
-    return rc;
-}
-
-int m3l_prep_weights(int dtype, const WeightPack* pack_in, hipStream_t st) {
-    if (pack_in->count <= 0) return 0;
-    M3L_CHECK(pack_in->count <= M3L_WPACK, "prep_weights: %d matrices in one pack (max %d)", pack_in->count, M3L_WPACK);
-    if (g_prep_mode == 2) return 0;                 // copies already issued by m3l_prep_flush
-    if (g_prep_mode == 1) {
-        M3L_CHECK(g_prep_dtype < 0 || g_prep_dtype == dtype, "prep_weights: modules of one chain disagree on the compute type");
-        g_prep_dtype = dtype;
-        for (int i = 0; i < pack_in->count; ++i) g_prep_list->push_back(pack_in->d[i]);
-        return 0;
-    }
-    WeightPack pack = *pack_in;
-    int tiles = 0;
-    for (int i = 0; i < pack.count; ++i) {
-        const WeightDesc& d = pack.d[i];
-        M3L_CHECK(d.ld_dst >= d.cols && d.ld_dstT >= d.rows && d.ld_dst <= ((d.cols + 63) / 64) * 64 && d.ld_dstT <= ((d.rows + 63) / 64) * 64,
-                  "prep_weights: padding of matrix %d ([%d, %d] -> [%d, %d]) must stay inside its last 64 x 64 tiles", i, d.rows, d.cols, d.ld_dstT, d.ld_dst);
-        pack.tile0[i] = tiles;
-        tiles += ((d.rows + 63) / 64) * ((d.cols + 63) / 64);
-    }
-    pack.tile0[pack.count] = tiles;
-    if (tiles == 0) return 0;
-    ProfScope prof("prep_weights", pack.count, dtype, 0, 0.0, st);
-    if (dtype == 1)
-        prep_weights_kernel<bf16><<<tiles, 256, 0, st>>>(pack);
-    else
-        prep_weights_kernel<float><<<tiles, 256, 0, st>>>(pack);
-    M3L_LAUNCH_CHECK();
     return 0;
 }
 

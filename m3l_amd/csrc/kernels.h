@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #define M3L_MAX_SENSORS 8
 #define M3L_MAX_PARTIAL_BLOCKS 2048      // capacity of the partial-row workspaces; the launch grids use m3l_part_blocks() <= this
 
@@ -58,8 +60,23 @@ struct WeightDesc {
 #define M3L_WPACK 64
 struct WeightPack {
     WeightDesc d[M3L_WPACK];
-    int tile0[M3L_WPACK + 1];   // filled by m3l_prep_weights: first 64x64 tile of each matrix in the launch's tile list
+    int tile0[M3L_WPACK + 1];   // filled by m3l_prep_weight_list: first 64x64 tile of each matrix in the launch's tile list
     int count;
+};
+typedef std::vector<WeightDesc> WeightList;
+
+// bump allocator over a caller-provided workspace, 256-byte aligned; base == NULL only measures (off = bytes needed)
+struct Arena {
+    char* base;
+    size_t off = 0;
+    explicit Arena(void* b) : base(reinterpret_cast<char*>(b)) {}
+    void* take(size_t bytes) {
+        off = (off + 255) & ~size_t(255);
+        void* p = base ? base + off : nullptr;
+        off += bytes;
+        return p;
+    }
+    template <typename T> T* take_n(size_t n) { return reinterpret_cast<T*>(take(n * sizeof(T))); }
 };
 
 struct PatchGroup {
@@ -222,14 +239,32 @@ int m3l_ln_bwd(int dy_dtype, const void* dy, const float* x, int M, int D, const
                hipStream_t st);
 int m3l_reduce_rows(const float* part, int G, int stride, int count, float* out, int accumulate, hipStream_t st);
 int m3l_colsum(int dtype, const void* Y, int M, int N, int ld, float* part_ws, float* out, int accumulate, hipStream_t st);
-int m3l_prep_weights(int dtype, const WeightPack* pack_host, hipStream_t st);
-// batching of the modules' weight copies over one call chain: 0 = off, 1 = collect (modules return after recording), 2 = skip (done)
-int m3l_prep_mode(void);
-void m3l_prep_set_mode(int mode);
-int m3l_prep_flush(hipStream_t st);
+// compute-type copies (+ transposes) of a list of fp32 master matrices, in list order: one launch per M3L_WPACK of them
+int m3l_prep_weight_list(int dtype, const WeightList& list, hipStream_t st);
+// The five forward modules that compute with copies of their weights (mae_plan.hip).  m3l_*_weights is pure host code: it appends the module's
+// copies to `out`.  m3l_*_run is the forward: it issues that list first, or — copies_done — its caller (a chain of mae_step.hip) already has.
+struct m3l_geom; struct m3l_cnn_cfg; struct m3l_dropout; struct m3l_tf_cfg;
+extern "C" {
+int m3l_embed_weights(const m3l_geom* g, int D, int dtype, int B, int L, int cnt_img, const void* const* tensors, void* ws, WeightList* out);
+int m3l_embed_run(bool backward, bool copies_done, const m3l_geom* g, int D, int dtype, int B, int L, int cnt_img, const int64_t* idx,
+                  const float* image, const float* const* tactiles, const void* const* tensors, void* ws, float* tokens,
+                  const float* dtokens, float* const* grads, hipStream_t st);
+int m3l_earlycnn_weights(const m3l_cnn_cfg* c, int B, int nsrc, const void* const* tensors, void* ws, WeightList* out);
+int m3l_earlycnn_run(const m3l_cnn_cfg* c, int B, int nsrc, const float* const* srcs, const void* const* tensors, void* ws, float* out,
+                     bool copies_done, hipStream_t st);
+int m3l_transformer_weights(const m3l_tf_cfg* c, int B, int n, const void* const* tensors, void* ws, const m3l_dropout* drop, WeightList* out);
+int m3l_transformer_run(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t, float* y32,
+                        const m3l_dropout* drop, bool copies_done, hipStream_t st);
+int m3l_unshuffle_weights(int D, int dd, int dtype, int B, int nvis, const void* const* tensors, void* ws, WeightList* out);
+int m3l_unshuffle_run(const m3l_geom* g, int D, int dd, int dtype, int B, int nvis, int nmask, const int64_t* unmasked, const int64_t* masked,
+                      const float* enc32, const void* enc_t, const void* const* tensors, void* ws, float* dec_in, bool copies_done, hipStream_t st);
+int m3l_heads_weights(const m3l_geom* g, int dd, int dtype, int B, int nmask, int nm_img, const void* const* tensors, void* ws, WeightList* out);
+int m3l_heads_loss_run(const m3l_geom* g, int dd, int dtype, int B, int N, int nmask, int nm_img, const int64_t* masked, const float* image,
+                       const float* const* tactiles, const void* dec_t, const void* const* tensors, void* ws, float* loss, float* loss_parts,
+                       float* pred_img, float* tgt_img, float* pred_tac, float* tgt_tac, bool copies_done, hipStream_t st);
+}
 int m3l_axpy_t(int dtype, const float* x, const void* o, long count, float* out, hipStream_t st);          // out = x + (float)o
 int m3l_cast_f32(int dtype, const float* x, long count, void* out, hipStream_t st);                        // out = (T)x
-struct m3l_tf_cfg;
 extern "C" int m3l_transformer_rb(const m3l_tf_cfg* c, int B, int n);       // 1: the stack runs the bf16 residual stream at this shape
 int m3l_cast_bf16_f32(const void* x, long count, float* out, hipStream_t st);                               // out = (float)x
 int m3l_scale_by_dev(int dtype, const void* x, long count, const float* scale_dev, void* out, hipStream_t st);  // out = x * *scale

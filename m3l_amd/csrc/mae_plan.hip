@@ -116,19 +116,6 @@ struct SideSection {
     }
 };
 
-struct Arena {
-    char* base;
-    size_t off = 0;
-    explicit Arena(void* b) : base(reinterpret_cast<char*>(b)) {}
-    void* take(size_t bytes) {
-        off = (off + 255) & ~size_t(255);
-        void* p = base ? base + off : nullptr;
-        off += bytes;
-        return p;
-    }
-    template <typename T> T* take_n(size_t n) { return reinterpret_cast<T*>(take(n * sizeof(T))); }
-};
-
 inline int pad8(int x) { return (x + 7) & ~7; }
 inline int pad64(int x) { return (x + 63) & ~63; }
 inline size_t esz(int dtype) { return dtype ? 2 : 4; }
@@ -514,10 +501,20 @@ size_t m3l_embed_ws_bytes(const m3l_geom* g, int D, int dtype, int B, int L) {
     return emb_layout(ge, D, dtype, B, nullptr).total;
 }
 
-namespace {
-int embed_run(bool backward, const m3l_geom* g, int D, int dtype, int B, int L, int cnt_img, const int64_t* idx, const float* image,
-              const float* const* tactiles, const void* const* tensors, void* ws, float* tokens, const float* dtokens,
-              float* const* grads, hipStream_t st) {
+// compute-type weight copies of the groups present (the zero padding of K is written by the same kernel)
+int m3l_embed_weights(const m3l_geom* g, int D, int dtype, int B, int L, int cnt_img, const void* const* tensors, void* ws, WeightList* out) {
+    if (check_geom(g)) return 1;
+    const Geo ge = geo_of(g);
+    const EmbWs w = emb_layout(ge, D, dtype, B, ws);
+    const int cnt[2] = {cnt_img, L - cnt_img}, pd[2] = {ge.pd_img, ge.pd_tac}, pdp[2] = {ge.pdp_img, ge.pdp_tac};
+    for (int i = 0; i < 2; ++i)
+        if (cnt[i] != 0) out->push_back(WeightDesc{(const float*)tensors[6 * i + 2], w.g[i].w, w.g[i].wT, D, pd[i], pdp[i], D});
+    return 0;
+}
+
+int m3l_embed_run(bool backward, bool copies_done, const m3l_geom* g, int D, int dtype, int B, int L, int cnt_img, const int64_t* idx,
+                  const float* image, const float* const* tactiles, const void* const* tensors, void* ws, float* tokens,
+                  const float* dtokens, float* const* grads, hipStream_t st) {
     if (check_geom(g)) return 1;
     M3L_CHECK(D % 8 == 0 && D <= 1024, "embed: dim=%d must be a multiple of 8, <= 1024", D);
     const Geo ge = geo_of(g);
@@ -532,17 +529,8 @@ int embed_run(bool backward, const m3l_geom* g, int D, int dtype, int B, int L, 
     const float* pos[2] = {(const float*)tensors[13], (const float*)tensors[14]};
     const int mod0[2] = {0, 1};
     SideSection side;
-    if (!backward) {
-        // compute-type weight copies of both groups in ONE launch (the zero padding of K is written by the same kernel)
-        WeightPack pk;
-        memset(&pk, 0, sizeof(pk));
-        for (int i = 0; i < 2; ++i) {
-            if (cnt[i] == 0) continue;
-            pk.d[pk.count++] = WeightDesc{(const float*)tensors[6 * i + 2], w.g[i].w, w.g[i].wT, D, pd[i], pdp[i], D};
-        }
-        if (m3l_prep_weights(dtype, &pk, st)) return 1;
-        if (m3l_prep_mode() == 1) return 0;        // collect pass of a call chain (mae_step.hip): the copies are recorded, nothing else runs
-    }
+    WeightList wl;          // both groups' copies in ONE launch
+    if (!backward && !copies_done && (m3l_embed_weights(g, D, dtype, B, L, cnt_img, tensors, ws, &wl) || m3l_prep_weight_list(dtype, wl, st))) return 1;
     for (int i = 0; i < 2; ++i) {
         if (cnt[i] == 0) continue;
         const int rows = B * cnt[i];
@@ -577,16 +565,15 @@ int embed_run(bool backward, const m3l_geom* g, int D, int dtype, int B, int L, 
     }
     return side.end();
 }
-}  // namespace
 
 int m3l_embed_fwd(const m3l_geom* g, int D, int dtype, int B, int L, int cnt_img, const int64_t* idx, const float* image,
                   const float* const* tactiles, const void* const* tensors, void* ws, float* tokens, void* stream) {
-    return embed_run(false, g, D, dtype, B, L, cnt_img, idx, image, tactiles, tensors, ws, tokens, nullptr, nullptr, (hipStream_t)stream);
+    return m3l_embed_run(false, false, g, D, dtype, B, L, cnt_img, idx, image, tactiles, tensors, ws, tokens, nullptr, nullptr, (hipStream_t)stream);
 }
 int m3l_embed_bwd(const m3l_geom* g, int D, int dtype, int B, int L, int cnt_img, const int64_t* idx, const float* image,
                   const float* const* tactiles, const void* const* tensors, void* ws, const float* dtokens, float* const* grads,
                   void* stream) {
-    return embed_run(true, g, D, dtype, B, L, cnt_img, idx, image, tactiles, tensors, ws, nullptr, dtokens, grads, (hipStream_t)stream);
+    return m3l_embed_run(true, false, g, D, dtype, B, L, cnt_img, idx, image, tactiles, tensors, ws, nullptr, dtokens, grads, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -600,17 +587,36 @@ size_t m3l_transformer_ws_bytes_dropout(const m3l_tf_cfg* c, int B, int n, const
 
 int m3l_transformer_fwd(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t,
                         float* y32, void* stream) {
-    return m3l_transformer_fwd_dropout(c, B, n, x_in, tensors, ws, y_t, y32, nullptr, stream);
+    return m3l_transformer_run(c, B, n, x_in, tensors, ws, y_t, y32, nullptr, false, (hipStream_t)stream);
+}
+int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t,
+                                float* y32, const m3l_dropout* drop, void* stream) {
+    return m3l_transformer_run(c, B, n, x_in, tensors, ws, y_t, y32, drop, false, (hipStream_t)stream);
+}
+
+// compute-type weight copies (+ transposes for the dgrads) of every layer
+int m3l_transformer_weights(const m3l_tf_cfg* c, int B, int n, const void* const* tensors, void* ws, const m3l_dropout* drop, WeightList* out) {
+    if (check_tf(c, B, n)) return 1;
+    const TfWs w = tf_layout(c, B, n, ws, drop_active(drop));
+    const int D = c->dim, HD = c->heads * tf_dh(c), mlp = c->mlp_dim;
+    for (int l = 0; l < c->depth; ++l) {
+        const TfLayer& L = w.L[l];
+        const void* const* t = tensors + 11 * l;
+        out->push_back(WeightDesc{(const float*)t[2], L.wqkv, L.wqkvT, 3 * HD, D, D, 3 * HD});
+        out->push_back(WeightDesc{(const float*)t[7], L.w1, L.w1T, mlp, D, D, mlp});
+        out->push_back(WeightDesc{(const float*)t[9], L.w2, L.w2T, D, mlp, mlp, D});
+        if (c->project_out) out->push_back(WeightDesc{(const float*)t[3], L.wo, L.woT, D, HD, HD, D});
+    }
+    return 0;
 }
 
 // With a dropout descriptor of p > 0 every layer takes the per-op chain (LN, QKV GEMM, attention, out-proj GEMM, LN, fc1, fc2): the
 // masks live in the attention kernels and the NT GEMM epilogue only.  The residual mode is the one the plan picks without dropout.
 // A stack whose heads are not 64 wide takes the same per-op chain (the block, row-tile and one-launch kernels are built for 64).
 // Which kernel runs each half layer is decided once, in tf_plan (tf_plan.h).
-int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t,
-                                float* y32, const m3l_dropout* drop, void* stream) {
+int m3l_transformer_run(const m3l_tf_cfg* c, int B, int n, const float* x_in, const void* const* tensors, void* ws, void* y_t, float* y32,
+                        const m3l_dropout* drop, bool copies_done, hipStream_t st) {
     if (check_tf(c, B, n)) return 1;
-    hipStream_t st = (hipStream_t)stream;
     const TfPlan pl = tf_plan(c, B, n, drop);
     const bool dp = pl.dropout, rb = pl.rb;
     M3L_CHECK(!dp || drop->p <= 1.f, "transformer: dropout p=%g outside [0, 1]", (double)drop->p);
@@ -620,24 +626,8 @@ int m3l_transformer_fwd_dropout(const m3l_tf_cfg* c, int B, int n, const float* 
     TfWs w = tf_layout(c, B, n, ws, dp);
     const int M = B * n, D = c->dim, HD = c->heads * tf_dh(c), mlp = c->mlp_dim, dt = c->dtype;
     const float* x = x_in;
-    // compute-type weight copies (+ transposes for the dgrads) of every layer: one launch per 16 layers, on the caller's stream
-    {
-        WeightPack pk;
-        memset(&pk, 0, sizeof(pk));
-        for (int l = 0; l < c->depth; ++l) {
-            TfLayer& L = w.L[l];
-            const void* const* t = tensors + 11 * l;
-            pk.d[pk.count++] = WeightDesc{(const float*)t[2], L.wqkv, L.wqkvT, 3 * HD, D, D, 3 * HD};
-            pk.d[pk.count++] = WeightDesc{(const float*)t[7], L.w1, L.w1T, mlp, D, D, mlp};
-            pk.d[pk.count++] = WeightDesc{(const float*)t[9], L.w2, L.w2T, D, mlp, mlp, D};
-            if (c->project_out) pk.d[pk.count++] = WeightDesc{(const float*)t[3], L.wo, L.woT, D, HD, HD, D};
-            if (pk.count + 4 > M3L_WPACK || l + 1 == c->depth) {
-                if (m3l_prep_weights(dt, &pk, st)) return 1;
-                pk.count = 0;
-            }
-        }
-    }
-    if (m3l_prep_mode() == 1) return 0;            // collect pass of a call chain (mae_step.hip)
+    WeightList wl;          // one launch per 64 matrices, on the caller's stream
+    if (!copies_done && (m3l_transformer_weights(c, B, n, tensors, ws, drop, &wl) || m3l_prep_weight_list(dt, wl, st))) return 1;
     const void* const* tfin = tensors + 11 * c->depth;
     {
         std::lock_guard<std::mutex> lock(g_tf_rec_mu);
@@ -1200,21 +1190,27 @@ size_t m3l_unshuffle_ws_bytes(const m3l_geom* g, int D, int dd, int dtype, int B
 int m3l_unshuffle_fwd(const m3l_geom* g, int D, int dd, int dtype, int B, int nvis, int nmask, const int64_t* unmasked,
                       const int64_t* masked, const float* enc32, const void* enc_t, const void* const* tensors, void* ws,
                       float* dec_in, void* stream) {
+    return m3l_unshuffle_run(g, D, dd, dtype, B, nvis, nmask, unmasked, masked, enc32, enc_t, tensors, ws, dec_in, false, (hipStream_t)stream);
+}
+
+// compute-type copy of the enc_to_dec weight, where there is one (encoder and decoder widths differ)
+int m3l_unshuffle_weights(int D, int dd, int dtype, int B, int nvis, const void* const* tensors, void* ws, WeightList* out) {
+    const UnWs w = un_layout(D, dd, dtype, B, nvis, ws);
+    if (tensors[0]) out->push_back(WeightDesc{(const float*)tensors[0], w.w, w.wT, dd, D, D, dd});
+    return 0;
+}
+
+int m3l_unshuffle_run(const m3l_geom* g, int D, int dd, int dtype, int B, int nvis, int nmask, const int64_t* unmasked, const int64_t* masked,
+                      const float* enc32, const void* enc_t, const void* const* tensors, void* ws, float* dec_in, bool copies_done, hipStream_t st) {
     if (check_geom(g)) return 1;
     M3L_CHECK(dd % 8 == 0 && D % 8 == 0, "unshuffle: dims must be multiples of 8");
-    hipStream_t st = (hipStream_t)stream;
     const Geo ge = geo_of(g);
     M3L_CHECK(nvis + nmask == ge.n_img + ge.k * ge.n_tac, "unshuffle: nvis + nmask = %d != number of patches", nvis + nmask);
     UnWs w = un_layout(D, dd, dtype, B, nvis, ws);
-    const float* e2d_w = (const float*)tensors[0];
     const float* src = enc32;
-    if (e2d_w) {
-        WeightPack pk;
-        memset(&pk, 0, sizeof(pk));
-        pk.d[0] = WeightDesc{e2d_w, w.w, w.wT, dd, D, D, dd};
-        pk.count = 1;
-        if (m3l_prep_weights(dtype, &pk, st)) return 1;
-        if (m3l_prep_mode() == 1) return 0;        // collect pass of a call chain (mae_step.hip)
+    WeightList wl;
+    if (!copies_done && (m3l_unshuffle_weights(D, dd, dtype, B, nvis, tensors, ws, &wl) || m3l_prep_weight_list(dtype, wl, st))) return 1;
+    if (tensors[0]) {
         GemmEpi e = epi0(dd);
         e.bias = (const float*)tensors[1];
         e.out_f32 = w.proj;
@@ -1222,7 +1218,6 @@ int m3l_unshuffle_fwd(const m3l_geom* g, int D, int dd, int dtype, int B, int nv
         src = w.proj;
     } else {
         M3L_CHECK(D == dd, "unshuffle: enc_to_dec weight missing but encoder dim %d != decoder dim %d", D, dd);
-        if (m3l_prep_mode() == 1) return 0;
     }
     return k_unshuffle_fwd(src, (const float*)tensors[2], unmasked, nvis, masked, nmask, B, dd, ge.n_img, ge.n_tac,
                              (const float*)tensors[3], (const float*)tensors[4], (const float*)tensors[5], dec_in, st);
@@ -1306,12 +1301,29 @@ int m3l_heads_loss_fwd(const m3l_geom* g, int dd, int dtype, int B, int N, int n
                                tgt_img, pred_tac, tgt_tac, stream);
 }
 
-// loss_parts (optional, f32[2]): the two WEIGHTED terms of the loss separately: mse(image), 10 * mse(tactile)
 int m3l_heads_loss_fwd2(const m3l_geom* g, int dd, int dtype, int B, int N, int nmask, int nm_img, const int64_t* masked,
                         const float* image, const float* const* tactiles, const void* dec_t, const void* const* tensors, void* ws,
                         float* loss, float* loss_parts, float* pred_img, float* tgt_img, float* pred_tac, float* tgt_tac, void* stream) {
+    return m3l_heads_loss_run(g, dd, dtype, B, N, nmask, nm_img, masked, image, tactiles, dec_t, tensors, ws, loss, loss_parts, pred_img, tgt_img,
+                              pred_tac, tgt_tac, false, (hipStream_t)stream);
+}
+
+// compute-type weight copies of the heads whose group has rows
+int m3l_heads_weights(const m3l_geom* g, int dd, int dtype, int B, int nmask, int nm_img, const void* const* tensors, void* ws, WeightList* out) {
     if (check_geom(g)) return 1;
-    hipStream_t st = (hipStream_t)stream;
+    const Geo ge = geo_of(g);
+    const HeadWs w = head_layout(ge, dd, dtype, B, nmask, ws);
+    const int cnt[2] = {nm_img, nmask - nm_img}, pd[2] = {ge.pd_img, ge.pd_tac}, pdp[2] = {ge.pdp_img, ge.pdp_tac};
+    for (int i = 0; i < 2; ++i)
+        if (cnt[i] != 0) out->push_back(WeightDesc{(const float*)tensors[2 * i], w.g[i].w, w.g[i].wT, pd[i], dd, dd, pdp[i]});
+    return 0;
+}
+
+// loss_parts (optional, f32[2]): the two WEIGHTED terms of the loss separately: mse(image), 10 * mse(tactile)
+int m3l_heads_loss_run(const m3l_geom* g, int dd, int dtype, int B, int N, int nmask, int nm_img, const int64_t* masked, const float* image,
+                       const float* const* tactiles, const void* dec_t, const void* const* tensors, void* ws, float* loss, float* loss_parts,
+                       float* pred_img, float* tgt_img, float* pred_tac, float* tgt_tac, bool copies_done, hipStream_t st) {
+    if (check_geom(g)) return 1;
     const Geo ge = geo_of(g);
     HeadWs w = head_layout(ge, dd, dtype, B, nmask, ws);
     const int cnt[2] = {nm_img, nmask - nm_img}, j0[2] = {0, nm_img};
@@ -1322,16 +1334,8 @@ int m3l_heads_loss_fwd2(const m3l_geom* g, int dd, int dtype, int B, int N, int 
     float* pred_out[2] = {pred_img, pred_tac};
     int nparts = 0;
     int part_beg[2] = {0, 0}, part_cnt[2] = {0, 0};
-    {
-        WeightPack pk;                       // both heads' compute-type weight copies in one launch
-        memset(&pk, 0, sizeof(pk));
-        for (int i = 0; i < 2; ++i) {
-            if (cnt[i] == 0) continue;
-            pk.d[pk.count++] = WeightDesc{(const float*)tensors[2 * i], w.g[i].w, w.g[i].wT, pd[i], dd, dd, pdp[i]};
-        }
-        if (m3l_prep_weights(dtype, &pk, st)) return 1;
-        if (m3l_prep_mode() == 1) return 0;        // collect pass of a call chain (mae_step.hip)
-    }
+    WeightList wl;                      // both heads' copies in one launch
+    if (!copies_done && (m3l_heads_weights(g, dd, dtype, B, nmask, nm_img, tensors, ws, &wl) || m3l_prep_weight_list(dtype, wl, st))) return 1;
     if (m3l_gather_rows2(dtype, dec_t, N, dd, masked, nmask, cnt[0], cnt[1], B, w.g[0].dg, w.g[1].dg, st)) return 1;   // both groups' rows
     for (int i = 0; i < 2; ++i) {
         if (cnt[i] == 0) continue;
@@ -1410,10 +1414,13 @@ struct CnnWs {
 };
 // direct (implicit-GEMM) convolutions for the three strided / 3x3 layers of the stem instead of im2col + GEMM: bf16, the stems of
 // dim 64 / 128 / 256; env M3L_DIRECT_CONV=0 keeps the im2col path (A/B, and the reference point of the parity tests)
-int g_direct_conv = -1;
-bool cnn_direct(const m3l_cnn_cfg* c) {
+int g_direct_conv = -1;      // -1 = environment not read yet
+int direct_conv() {
     if (g_direct_conv < 0) g_direct_conv = getenv("M3L_DIRECT_CONV") ? (atoi(getenv("M3L_DIRECT_CONV")) > 0 ? 1 : 0) : 1;
-    if (!g_direct_conv || c->dtype != 1) return false;
+    return g_direct_conv;
+}
+bool cnn_direct(const m3l_cnn_cfg* c) {
+    if (!direct_conv() || c->dtype != 1) return false;
     const int D = c->dim, co[3] = {D / 8, D / 4, D / 2};
     int ci = c->in_channels;
     for (int l = 0; l < 3; ++l) {
@@ -1487,8 +1494,7 @@ int check_cnn(const m3l_cnn_cfg* c, int B, int nsrc) {
 }  // namespace
 
 int m3l_set_direct_conv(int on) {
-    if (g_direct_conv < 0) g_direct_conv = getenv("M3L_DIRECT_CONV") ? (atoi(getenv("M3L_DIRECT_CONV")) > 0 ? 1 : 0) : 1;
-    const int old = g_direct_conv;
+    const int old = direct_conv();
     g_direct_conv = on ? 1 : 0;
     return old;
 }
@@ -1500,19 +1506,25 @@ size_t m3l_earlycnn_ws_bytes(const m3l_cnn_cfg* c, int B, int nsrc) {
 
 int m3l_earlycnn_fwd(const m3l_cnn_cfg* c, int B, int nsrc, const float* const* srcs, const void* const* tensors, void* ws, float* out,
                      void* stream) {
+    return m3l_earlycnn_run(c, B, nsrc, srcs, tensors, ws, out, false, (hipStream_t)stream);
+}
+
+// compute-type copies of the four convolution weights as [Co, K] matrices (K padded to a multiple of 8)
+int m3l_earlycnn_weights(const m3l_cnn_cfg* c, int B, int nsrc, const void* const* tensors, void* ws, WeightList* out) {
     if (check_cnn(c, B, nsrc)) return 1;
-    hipStream_t st = (hipStream_t)stream;
+    const CnnWs w = cnn_layout(c, B * nsrc, ws);
+    for (int l = 0; l < 4; ++l)
+        out->push_back(WeightDesc{(const float*)tensors[2 * l], w.w[l], w.wT[l], w.L[l].Co, w.L[l].K, w.L[l].Kpad, w.L[l].Co});
+    return 0;
+}
+
+int m3l_earlycnn_run(const m3l_cnn_cfg* c, int B, int nsrc, const float* const* srcs, const void* const* tensors, void* ws, float* out,
+                     bool copies_done, hipStream_t st) {
+    if (check_cnn(c, B, nsrc)) return 1;
     const int Btot = B * nsrc, dt = c->dtype;
     CnnWs w = cnn_layout(c, Btot, ws);
-    for (int l = 0; l < 4; ++l) {
-        const ConvL& L = w.L[l];
-        WeightPack pk;
-        memset(&pk, 0, sizeof(pk));
-        pk.d[0] = WeightDesc{(const float*)tensors[2 * l], w.w[l], w.wT[l], L.Co, L.K, L.Kpad, L.Co};
-        pk.count = 1;
-        if (m3l_prep_weights(dt, &pk, st)) return 1;
-    }
-    if (m3l_prep_mode() == 1) return 0;            // collect pass of a call chain (mae_step.hip)
+    WeightList wl;                      // the four copies in one launch
+    if (!copies_done && (m3l_earlycnn_weights(c, B, nsrc, tensors, ws, &wl) || m3l_prep_weight_list(dt, wl, st))) return 1;
     ConvSrc cs;
     memset(&cs, 0, sizeof(cs));
     for (int i = 0; i < nsrc; ++i) cs.src[i] = srcs[i];
@@ -1717,11 +1729,7 @@ int m3l_op_colsum(int dtype, const void* Y, int M, int N, int ld, void* ws, floa
 }
 size_t m3l_op_colsum_ws_bytes(int N) { return (size_t)M3L_MAX_PARTIAL_BLOCKS * N * sizeof(float) + 256; }
 int m3l_op_prep_weight(int dtype, const float* src, int rows, int cols, void* dst, void* dstT, void* stream) {
-    WeightPack pk;
-    memset(&pk, 0, sizeof(pk));
-    pk.d[0] = WeightDesc{src, dst, dstT, rows, cols, cols, rows};
-    pk.count = 1;
-    return m3l_prep_weights(dtype, &pk, (hipStream_t)stream);
+    return m3l_prep_weight_list(dtype, WeightList{WeightDesc{src, dst, dstT, rows, cols, cols, rows}}, (hipStream_t)stream);
 }
 int m3l_op_mask_scale(int mode, const float* src, const void* ref, float scale, long count, float* out, void* stream) {
     return m3l_mask_scale(mode, src, ref, scale, count, out, (hipStream_t)stream);

@@ -10,7 +10,8 @@
 // activation (tokens, encoder / decoder outputs, their gradients) lives in ONE caller-provided workspace, the backward issues the
 // chunked transformer backwards itself and — data parallel — hands each finished prefix of the flat gradient buffer to
 // m3l_comm_allreduce (comm.hip) with the same bucket rule m3l_amd.parallel.GradSync applies.
-// Same kernels, same launch order, same workspaces per module as the per-module path: results are bit-identical to it.
+// Same kernels, same launch order, same workspaces per module as the per-module path: results are bit-identical to it.  One difference: a
+// chain issues the weight copies of all its modules (each lists its own: m3l_*_weights) at its start, one launch per 64 matrices.
 //
 // Round 4: both front ends (the patch embed, and the EarlyCNN stems of early_conv_masking=True — the reference's default flag,
 // train.py:62 — with their loss over ALL patches, pretrain_models.py:180-191,311-322) and both position modes (fixed sincos buffers, or
@@ -26,18 +27,6 @@
 #include "kernels.h"
 
 namespace {
-
-struct Arena {
-    char* base;
-    size_t off = 0;
-    explicit Arena(void* b) : base(reinterpret_cast<char*>(b)) {}
-    void* take(size_t bytes) {
-        off = (off + 255) & ~size_t(255);
-        void* p = base ? base + off : nullptr;
-        off += bytes;
-        return p;
-    }
-};
 
 // identity index rows (the early-conv loss runs the masked-patch kernels over every patch) and the token mean of the extractor
 __global__ void iota_rows_kernel(int64_t* out, long total, int N) {
@@ -193,20 +182,26 @@ Groups groups_of(const m3l_mae_cfg* c) {
     return g;
 }
 
-// weight copies of a whole chain in one launch (elementwise.hip: m3l_prep_set_mode); env M3L_PREP_BATCH=0: every module issues its own
-static int prep_first_pass() {
-    static const int on = getenv("M3L_PREP_BATCH") ? (atoi(getenv("M3L_PREP_BATCH")) > 0 ? 1 : 0) : 1;
-    return on ? 1 : 2;
+// env M3L_PREP_BATCH=0 (read once per process): a chain makes no list of weight copies, every module issues its own.  All modules of a chain
+// compute in one type (the list is issued with it): step_dims / ext_dims refuse stacks that disagree, the other modules are handed d.dt
+bool prep_batch() {
+    static const bool on = getenv("M3L_PREP_BATCH") ? atoi(getenv("M3L_PREP_BATCH")) > 0 : true;
+    return on;
 }
-static int prep_mode_of(int pass) { return prep_first_pass() == 1 ? pass : 0; }
-// ---- front end forward: -> tokens (B, L, D); idx (B, L) positions of the tokens, or NULL with L == N (all of them, in order)
-int front_fwd(const m3l_mae_cfg* c, const StepDims& d, const FrontWs& f, int B, int L, int cnt_img, const int64_t* idx, const float* image,
-              const float* const* tactiles, const void* const* t, float* tokens, hipStream_t st) {
-    if (!c->early_conv) return m3l_embed_fwd(&c->geom, d.D, d.dt, B, L, cnt_img, idx, image, tactiles, t, f.ws_embed, tokens, st);
+// ---- front end: its weight copies ...
+int front_weights(const m3l_mae_cfg* c, const StepDims& d, const FrontWs& f, int B, int L, int cnt_img, const void* const* t, WeightList* out) {
+    if (!c->early_conv) return m3l_embed_weights(&c->geom, d.D, d.dt, B, L, cnt_img, t, f.ws_embed, out);
     const m3l_cnn_cfg ci = cnn_cfg(c, false), ct = cnn_cfg(c, true);
-    if (d.n_img && m3l_earlycnn_fwd(&ci, B, 1, &image, t, f.ws_cnn_img, f.img_tok, st)) return 1;
-    if (d.k && m3l_earlycnn_fwd(&ct, B, d.k, tactiles, t + 8, f.ws_cnn_tac, f.tac_tok, st)) return 1;
-    if (m3l_prep_mode() == 1) return 0;            // collect pass: the stems have recorded their weight copies
+    if (d.n_img && m3l_earlycnn_weights(&ci, B, 1, t, f.ws_cnn_img, out)) return 1;
+    return d.k ? m3l_earlycnn_weights(&ct, B, d.k, t + 8, f.ws_cnn_tac, out) : 0;
+}
+// ... and its forward: -> tokens (B, L, D); idx (B, L) positions of the tokens, or NULL with L == N (all of them, in order)
+int front_fwd(const m3l_mae_cfg* c, const StepDims& d, const FrontWs& f, int B, int L, int cnt_img, const int64_t* idx, const float* image,
+              const float* const* tactiles, const void* const* t, float* tokens, bool copies_done, hipStream_t st) {
+    if (!c->early_conv) return m3l_embed_run(false, copies_done, &c->geom, d.D, d.dt, B, L, cnt_img, idx, image, tactiles, t, f.ws_embed, tokens, nullptr, nullptr, st);
+    const m3l_cnn_cfg ci = cnn_cfg(c, false), ct = cnn_cfg(c, true);
+    if (d.n_img && m3l_earlycnn_run(&ci, B, 1, &image, t, f.ws_cnn_img, f.img_tok, copies_done, st)) return 1;
+    if (d.k && m3l_earlycnn_run(&ct, B, d.k, tactiles, t + 8, f.ws_cnn_tac, f.tac_tok, copies_done, st)) return 1;
     float* all = idx ? f.tok_all : tokens;
     if (m3l_tokens_assemble_fwd(&c->geom, d.D, B, f.img_tok, f.tac_tok, t + 16, all, st)) return 1;
     if (idx) return m3l_gather_tokens(all, B, d.N, d.D, idx, L, tokens, st);
@@ -309,43 +304,42 @@ int m3l_mae_step_fwd_dropout(const m3l_mae_cfg* c, int B, const float* image, co
     step_drop_record(ws, enc_drop, nullptr);
     // mask sampling (pretrain_models.py:223-248) -> the caller's index lists (the backward reads them again)
     if (m3l_mask_sample_counts(&c->geom, d.nm_img, d.nm_tac, B, noise, masked, unmasked, st)) return 1;
-    // every module's compute-type weight copies in one launch per 64 matrices: a collect pass over the chain (each module records its
-    // matrices and returns), the flush, then the chain itself with the copies in place (elementwise.hip: m3l_prep_set_mode)
-    struct PrepReset { ~PrepReset() { m3l_prep_set_mode(0); } } prep_reset;
-    for (int pass = prep_first_pass(); pass <= 2; ++pass) {
-    m3l_prep_set_mode(prep_mode_of(pass));
-    if (pass == 2 && m3l_prep_flush(st)) return 1;
-    // patch embed of the visible tokens (:157-216,255-256) / EarlyCNN stems over the frames, then the visible gather (:180-191)
-    if (front_fwd(c, d, w.f, B, d.nvis, d.nvis_img, unmasked, image, tactiles, tensors + g.embed, w.tokens, st)) return 1;
-    // encoder (:266)
-    if (m3l_transformer_fwd_dropout(&c->enc, B, d.nvis, w.tokens, tensors + g.enc, w.ws_enc, w.enc_t, w.enc32, enc_drop, st)) return 1;
-    // enc_to_dec + un-shuffle + decoder positions (:270-307); f32 compute: the "compute-type" encoder output is the f32 one.  When the
-    // decoder runs the bf16 residual stream, its input (and, in the backward, the gradient of it) is exchanged as bf16: no boundary casts
-    const IoScope dec_io(step_dec_io(c, d, B));
-    if (m3l_unshuffle_fwd(&c->geom, d.D, d.dd, d.dt, B, d.nvis, d.nmask, unmasked, masked, w.enc32, d.dt ? w.enc_t : (void*)w.enc32,
-                          tensors + g.glue, w.ws_glue, w.dec_in, st))
-        return 1;
-    // decoder (:309)
-    if (m3l_transformer_fwd(&c->dec, B, d.N, w.dec_in, tensors + g.dec, w.ws_dec, w.dec_t, w.dec32, st)) return 1;
-    m3l_set_call_io(0);
-    if (pass == 1) {       // the heads' copies (their other arguments play no part in the collect pass)
-        if (m3l_heads_loss_fwd2(&c->geom, d.dd, d.dt, B, d.N, c->early_conv ? d.N : d.nmask, c->early_conv ? d.n_img : d.nm_img, masked, image, tactiles,
-                                d.dt ? w.dec_t : (void*)w.dec32, tensors + g.heads, w.ws_heads, loss, nullptr, nullptr, nullptr, nullptr, nullptr, st))
+    const int nrows = c->early_conv ? d.N : d.nmask, nrows_img = c->early_conv ? d.n_img : d.nm_img;     // early conv: every patch is scored (:311-322)
+    const bool batch = prep_batch();
+    if (batch) {          // every module's compute-type weight copies, in chain order, in one launch per 64 matrices
+        WeightList wl;
+        if (front_weights(c, d, w.f, B, d.nvis, d.nvis_img, tensors + g.embed, &wl) ||
+            m3l_transformer_weights(&c->enc, B, d.nvis, tensors + g.enc, w.ws_enc, enc_drop, &wl) ||
+            m3l_unshuffle_weights(d.D, d.dd, d.dt, B, d.nvis, tensors + g.glue, w.ws_glue, &wl) ||
+            m3l_transformer_weights(&c->dec, B, d.N, tensors + g.dec, w.ws_dec, nullptr, &wl) ||
+            m3l_heads_weights(&c->geom, d.dd, d.dt, B, nrows, nrows_img, tensors + g.heads, w.ws_heads, &wl) ||
+            m3l_prep_weight_list(d.dt, wl, st))
             return 1;
     }
+    // patch embed of the visible tokens (:157-216,255-256) / EarlyCNN stems over the frames, then the visible gather (:180-191)
+    if (front_fwd(c, d, w.f, B, d.nvis, d.nvis_img, unmasked, image, tactiles, tensors + g.embed, w.tokens, batch, st)) return 1;
+    // encoder (:266)
+    if (m3l_transformer_run(&c->enc, B, d.nvis, w.tokens, tensors + g.enc, w.ws_enc, w.enc_t, w.enc32, enc_drop, batch, st)) return 1;
+    {
+        // enc_to_dec + un-shuffle + decoder positions (:270-307); f32 compute: the "compute-type" encoder output is the f32 one.  When the
+        // decoder runs the bf16 residual stream, its input (and, in the backward, the gradient of it) is exchanged as bf16: no boundary casts
+        const IoScope dec_io(step_dec_io(c, d, B));
+        if (m3l_unshuffle_run(&c->geom, d.D, d.dd, d.dt, B, d.nvis, d.nmask, unmasked, masked, w.enc32, d.dt ? w.enc_t : (void*)w.enc32,
+                              tensors + g.glue, w.ws_glue, w.dec_in, batch, st))
+            return 1;
+        // decoder (:309)
+        if (m3l_transformer_run(&c->dec, B, d.N, w.dec_in, tensors + g.dec, w.ws_dec, w.dec_t, w.dec32, nullptr, batch, st)) return 1;
     }
-    m3l_prep_set_mode(prep_mode_of(2));      // (the heads below run with their copies in place)
-    // heads + masked MSE (:260-262,327-340); early conv: every patch is predicted and scored (:311-322)
+    // heads + masked MSE (:260-262,327-340)
     const int64_t* rows = masked;
-    int nrows = d.nmask, nrows_img = d.nm_img;
     if (c->early_conv) {
         const long total = (long)B * d.N;
         iota_rows_kernel<<<cdiv(total, 256), 256, 0, st>>>(w.all_rows, total, d.N);
         M3L_LAUNCH_CHECK();
-        rows = w.all_rows; nrows = d.N; nrows_img = d.n_img;
+        rows = w.all_rows;
     }
-    return m3l_heads_loss_fwd2(&c->geom, d.dd, d.dt, B, d.N, nrows, nrows_img, rows, image, tactiles, d.dt ? w.dec_t : (void*)w.dec32,
-                               tensors + g.heads, w.ws_heads, loss, nullptr, nullptr, nullptr, nullptr, nullptr, st);
+    return m3l_heads_loss_run(&c->geom, d.dd, d.dt, B, d.N, nrows, nrows_img, rows, image, tactiles, d.dt ? w.dec_t : (void*)w.dec32,
+                              tensors + g.heads, w.ws_heads, loss, nullptr, nullptr, nullptr, nullptr, nullptr, batch, st);
 }
 
 // Backward of the step.  grads: one f32 pointer per tensor (same order; NULL where the tensor has no gradient).  dloss: device scalar
@@ -491,15 +485,17 @@ int m3l_extractor_fwd_dropout(const m3l_mae_cfg* c, const m3l_tf_cfg* head, int 
     const ExtWs w = ext_layout(c, head, d, B, ws, enc_drop, head_drop);
     const int g_enc = front_tensors(c), g_head = g_enc + 11 * c->enc.depth + 2;
     step_drop_record(ws, enc_drop, head_drop);
-    struct PrepReset { ~PrepReset() { m3l_prep_set_mode(0); } } prep_reset;
-    for (int pass = prep_first_pass(); pass <= 2; ++pass) {        // collect the chain's weight copies, flush them as one launch, run the chain
-        m3l_prep_set_mode(prep_mode_of(pass));
-        if (pass == 2 && m3l_prep_flush(st)) return 1;
-        if (front_fwd(c, d, w.f, B, d.N, d.n_img, nullptr, image, tactiles, tensors, w.tokens, st)) return 1;
-        if (m3l_transformer_fwd_dropout(&c->enc, B, d.N, w.tokens, tensors + g_enc, w.ws_enc, nullptr, w.enc32, enc_drop, st)) return 1;
-        if (m3l_transformer_fwd_dropout(head, B, d.N, w.enc32, tensors + g_head, w.ws_head, nullptr, w.head32, head_drop, st)) return 1;
+    const bool batch = prep_batch();
+    if (batch) {          // the chain's weight copies as one launch per 64 matrices
+        WeightList wl;
+        if (front_weights(c, d, w.f, B, d.N, d.n_img, tensors, &wl) ||
+            m3l_transformer_weights(&c->enc, B, d.N, tensors + g_enc, w.ws_enc, enc_drop, &wl) ||
+            m3l_transformer_weights(head, B, d.N, tensors + g_head, w.ws_head, head_drop, &wl) || m3l_prep_weight_list(d.dt, wl, st))
+            return 1;
     }
-    m3l_prep_set_mode(0);
+    if (front_fwd(c, d, w.f, B, d.N, d.n_img, nullptr, image, tactiles, tensors, w.tokens, batch, st)) return 1;
+    if (m3l_transformer_run(&c->enc, B, d.N, w.tokens, tensors + g_enc, w.ws_enc, nullptr, w.enc32, enc_drop, batch, st)) return 1;
+    if (m3l_transformer_run(head, B, d.N, w.enc32, tensors + g_head, w.ws_head, nullptr, w.head32, head_drop, batch, st)) return 1;
     mean_tokens_kernel<<<B, 256, 0, st>>>(w.head32, d.N, d.D, out);
     M3L_LAUNCH_CHECK();
     return 0;

@@ -18,7 +18,7 @@ tests/test_stage_refs_cpu.py anchors these functions to oracle/vtmae_oracle.py (
 read off the code (struct names are those of mae_plan.hip):
 
   embed (embed_run)
-    EmbGroupWs::w / wT   the projection weight, both copies (m3l_prep_weights): forward GEMM and dxn GEMM
+    EmbGroupWs::w / wT   the projection weight, both copies (m3l_prep_weight_list): forward GEMM and dxn GEMM
     EmbGroupWs::xn       output of the first LayerNorm (patch_ln_kernel stores T); operand of the forward GEMM and of dW
     EmbGroupWs::E        stays f32 (GemmEpi::out_f32) — NOT rounded
     EmbGroupWs::dE       backward of the second LayerNorm (embed_finalize_bwd_kernel stores T); operand of dW, of the bias column sums

@@ -17,7 +17,7 @@ The rounding points of R, each read off the code.  Cited by kernel or function o
 commit ec2aef2 and only a help to find the statement):
 
   forward (TfLayer / tf_layout, launch sequence of m3l_transformer_fwd_dropout)
-    wqkv, wo, w1, w2 (+ transposes)   compute-type copies of the weights (m3l_prep_weights); both copies hold the same values
+    wqkv, wo, w1, w2 (+ transposes)   compute-type copies of the weights (m3l_prep_weight_list); both copies hold the same values
     xn1, xn2                          LayerNorm outputs (ln_fwd_kernel stores TO; attn_block_fwd_body: the two `pk[..] = (bf16)y[..]` stores)
     qkv                               GemmEpi::out_t of gemm_nt_glds_kernel; attn_block_fwd_body: `(bf16)acc[r]` into the QKV image
     P                                 exp(s - running max) of a 32-key tile, UNNORMALISED, rounded by acc_to_frag before the P V MFMA; the row
