@@ -974,6 +974,42 @@ int m3l_replay_per_sample(const float* mass, const float* block_mass, const floa
 int m3l_replay_per_update(float* mass, float* block_mass, float* block_min, float* max_priority, long N, const int64_t* rows, const float* td, int B,
                           float alpha, float priority_eps, void* stream);
 
+/* ---- random-shift augmentation (ABI 417): the image augmentation of DrQ (Kostrikov et al. 2021) and RAD (Laskin et al. 2020) inside the two
+ * observation gathers: replicate-pad a frame by `pad` pixels and crop it at a random offset, independently for the observation and the next
+ * observation of a sample.  Neither the reference tree nor SB3 has it: the rule is restated here and in tests/shift_cases.py, parity unpinned.
+ *   shifts (B, 2, 2, 2) int32, contiguous, on the device: [sample, half (0 observation, 1 next observation), modality (0 image, 1 tactile),
+ *   (dy, dx)].  One shift per (sample, half, modality): all frames of the stack, all three channels and all S sensors share it.  The kernel
+ *   clamps every entry to [-pad, pad] of its modality (image_pad, tactile_pad) by comparisons, so any int32 is an entry.  With x the tensor the
+ *   unshifted gather writes for that half, (B, 3 fs, H, W):
+ *     out[b, c, y, x] = x[b, c, clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1)]
+ *   which is F.pad(x, (p, p, p, p), mode="replicate")[..., p + dy : p + dy + H, p + dx : p + dx + W].  The normalisation is elementwise, so
+ *   the result has the bits of that indexing applied to the unshifted entry point's output.
+ * m3l_replay_gather_load_shift / m3l_replay_gather_load_frames_shift are m3l_replay_gather_load_rows2 / m3l_replay_gather_load_frames_rows2
+ * with `shifts, image_pad, tactile_pad` in front of B, and next_rows may be NULL: the next observations are then those of `rows` (a second
+ * store at the same row, or the store itself one step later), as the one-list entry points give them.  One launch each.
+ *   The shift is an address change on the read side; outputs, normalisation and 16-byte stores are those of the unshifted kernels, which keep
+ *   their code (the shifted forms are further instantiations).  Image, 16-byte form (it also needs W % 4 == 0, else the element form runs):
+ *   a lane's 4 pixels of one row have their sources in one window of 4 pixels of the clamped row, 12 consecutive elements that start at an
+ *   address of the element's own alignment; they are loaded at that alignment (float) or as the aligned 4-byte words that cover them (uint8),
+ *   and each pixel is picked from the window with selects.  Tactile: each of a lane's 4 elements is decoded to (channel, y, x) and loaded on
+ *   its own.  Frame stores: the two halves have shifts of their own, so no loaded piece serves both stacks: 2 fs frame reads a sample (fs + 1
+ *   without the shift).
+ *   shifts NULL, or a pad of 0 for every modality that is stored: the launch, and so the bits, of the entry point without `_shift`.
+ * Safety: the shift is clamped to the pad first, then every coordinate to its frame: no value of shifts causes a read outside a frame.  A row
+ * outside [0, T n_envs) is still never read and gives NaN.
+ * Errors, nothing written: those of the *_rows2 entry points but for next_rows NULL, and a pad outside [0, 2^15). */
+int m3l_replay_gather_load_shift(const void* image_store, const void* image_next_store, int image_u8, int H, int W, double img_lo, double img_hi,
+                                 float* image, float* image_next, const void* tactile_store, const void* tactile_next_store, int tactile_u8, int th,
+                                 int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out, float* const* tactile_next_out, int T,
+                                 int n_envs, int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, const int32_t* shifts,
+                                 int image_pad, int tactile_pad, int B, void* stream);
+int m3l_replay_gather_load_frames_shift(const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
+                                        double img_hi, float* image, float* image_next, const void* tactile_frames,
+                                        const void* tactile_next_frames, int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi,
+                                        float* const* tactile_out, float* const* tactile_next_out, const int32_t* ages, int T, int n_envs,
+                                        int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, const int32_t* shifts,
+                                        int image_pad, int tactile_pad, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

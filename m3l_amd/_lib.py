@@ -251,6 +251,11 @@ _SIGS = {
     "m3l_op_conv_dgrad": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "m3l_op_im2col": (c_i, [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     "m3l_op_col2im_relu": (c_i, [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    # random-shift augmentation (ABI 417): the *_rows2 gathers with shifts, image_pad and tactile_pad in front of B
+    "m3l_replay_gather_load_shift": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double,
+                                           C.c_double, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "m3l_replay_gather_load_frames_shift": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double,
+                                                  C.c_double, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_p, c_p, c_i, c_i, c_i, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

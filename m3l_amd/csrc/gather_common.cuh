@@ -129,6 +129,133 @@ __device__ __forceinline__ void gather_tactile_piece(const GatherGeom& g, const 
         o[q] = tactile_load1<TI>(g, tac, frame, s, q);
 }
 
+// ---- the shifted pieces (DrQ / RAD random shift, include/m3l_amd.h "random-shift augmentation"): the same pieces read through
+//   out[y, x] = in[clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1)]
+// of their frame, every channel alike.  A shift is an address change on the read side: the outputs, the normalisation and the 16-byte stores are
+// those above.  The callers clamp (dy, dx) to [-pad, pad] (gather_shift) and the pieces clamp every coordinate, so no shift reads outside a frame.
+__device__ __forceinline__ int gather_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// (dy, dx) of sample b, half (0: observation, 1: next observation) and modality (0: image, 1: tactile) from shifts (B, 2, 2, 2), clamped to
+// [-pad, pad] by comparisons alone: INT_MIN and INT_MAX are entries like any other
+__device__ __forceinline__ void gather_shift(const int32_t* __restrict__ shifts, int b, int half, int modality, int pad, int& dy, int& dx) {
+    const int32_t* __restrict__ s = shifts + (((long)b * 2 + half) * 2 + modality) * 2;
+    dy = gather_clamp(s[0], -pad, pad), dx = gather_clamp(s[1], -pad, pad);
+}
+
+// 12 consecutive elements from an address that has only the alignment of its element.  float: twelve 4-byte loads, which the compiler may
+// combine into wider ones of 4-byte alignment.  uint8: the aligned 4-byte words that cover the span (the fourth only when the span reaches it:
+// past a span that ends on a word boundary the store may end) and the bytes taken out of them with funnel shifts.  The store is 4-byte aligned
+// and a frame a multiple of 4 bytes where this is called, so every word that holds a byte of the frame lies in the store.
+__device__ __forceinline__ void load12_unaligned(const float* __restrict__ p, float (&v)[12]) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) v[k] = p[k];
+}
+__device__ __forceinline__ void load12_unaligned(const uint8_t* __restrict__ p, float (&v)[12]) {
+    const uintptr_t a = (uintptr_t)p;
+    const uint32_t* __restrict__ w = (const uint32_t*)(a & ~(uintptr_t)3);
+    const unsigned sh = 8u * (unsigned)(a & 3);
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+    const uint32_t w3 = sh ? w[3] : 0u;
+    const uint32_t r[3] = {(uint32_t)((((uint64_t)w1 << 32) | w0) >> sh), (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh),
+                           (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh)};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[4 * i + k] = (float)((r[i] >> (8 * k)) & 0xffu);
+}
+
+// 4 pixels q < HW / 4 of an image frame of width W, W % 4 == 0: the lane's pixels x0 .. x0 + 3 lie in one row y.  Their sources
+// clamp(x0 + j + dx, 0, W - 1) all lie in the window of 4 pixels that starts at xs = clamp(x0 + dx, 0, W - 4) of row clamp(y + dy, 0, H - 1) —
+// away from the row's ends they are the window, at an end they repeat its first or last pixel — so every lane loads the 12 consecutive
+// elements of its window and picks each pixel out of them with selects: no lane takes another path than its neighbours
+template <typename TI>
+__device__ __forceinline__ void image_load4_shift(const GatherGeom& g, const void* img, long frame, int q, int W, int dy, int dx, float (&v)[12]) {
+    if (frame >= 0) {
+        const int y = 4 * q / W, x0 = 4 * q - y * W;
+        const int yy = gather_clamp(y + dy, 0, g.HW / W - 1), xs = gather_clamp(x0 + dx, 0, W - 4);
+        float s[12];
+        load12_unaligned((const TI*)img + frame * (3L * g.HW) + 3L * (yy * W + xs), s);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = gather_clamp(x0 + j + dx, 0, W - 1) - xs;      // 0 .. 3
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float t = i == 0 ? s[c] : i == 1 ? s[3 + c] : i == 2 ? s[6 + c] : s[9 + c];
+                v[3 * j + c] = vt_norm(t, g.img_lo, g.img_span);
+            }
+        }
+    } else {
+        const float nan = __int_as_float(0x7fc00000);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) v[k] = nan;
+    }
+}
+// the element-per-lane form: pixel p < HW
+template <typename TI>
+__device__ __forceinline__ void image_load1_shift(const GatherGeom& g, const void* img, long frame, int p, int W, int dy, int dx, float (&v)[3]) {
+    const int y = p / W, x = p - y * W;
+    const int src = gather_clamp(y + dy, 0, g.HW / W - 1) * W + gather_clamp(x + dx, 0, W - 1);
+    const TI* __restrict__ s = (const TI*)img + frame * (3L * g.HW) + 3L * src;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = frame >= 0 ? vt_norm((float)s[c], g.img_lo, g.img_span) : __int_as_float(0x7fc00000);
+}
+
+// element q < 3 hw of a sensor's three (h, w) planes -> the element its shifted source is, in the same plane
+__device__ __forceinline__ int tactile_shift_source(const GatherGeom& g, int c, int y, int x, int w, int dy, int dx) {
+    return c * g.hw + gather_clamp(y + dy, 0, g.hw / w - 1) * w + gather_clamp(x + dx, 0, w - 1);
+}
+// 4 elements q < 3 hw / 4 of sensor s: they may straddle a row or a plane, so (c, y, x) is decoded once and stepped from element to element,
+// and each element is loaded on its own
+template <typename TI>
+__device__ __forceinline__ f32x4 tactile_load4_shift(const GatherGeom& g, const void* tac, long frame, int s, int q, int w, int dy, int dx) {
+    const float nan = __int_as_float(0x7fc00000);
+    f32x4 v = f32x4{nan, nan, nan, nan};
+    if (frame >= 0) {
+        const TI* __restrict__ src = (const TI*)tac + (frame * g.S + s) * (3L * g.hw);
+        const int h = g.hw / w;
+        int c = 4 * q / g.hw, y = (4 * q - c * g.hw) / w, x = 4 * q - c * g.hw - y * w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = vt_norm((float)src[tactile_shift_source(g, c, y, x, w, dy, dx)], g.tac_lo, g.tac_span);
+            if (++x == w) {
+                x = 0;
+                if (++y == h) y = 0, ++c;
+            }
+        }
+    }
+    return v;
+}
+template <typename TI>
+__device__ __forceinline__ float tactile_load1_shift(const GatherGeom& g, const void* tac, long frame, int s, int q, int w, int dy, int dx) {
+    const TI* __restrict__ src = (const TI*)tac + (frame * g.S + s) * (3L * g.hw);
+    const int c = q / g.hw, y = (q - c * g.hw) / w, x = q - c * g.hw - y * w;
+    return frame >= 0 ? vt_norm((float)src[tactile_shift_source(g, c, y, x, w, dy, dx)], g.tac_lo, g.tac_span) : __int_as_float(0x7fc00000);
+}
+
+// gather_image_piece / gather_tactile_piece through a shift; W / w: the width of a frame
+template <typename TI>
+__device__ __forceinline__ void gather_image_piece_shift(const GatherGeom& g, const void* img, float* img_out, long frame, long group, int q, int W,
+                                                         int dy, int dx) {
+    if (g.img_vec) {
+        float v[12];
+        image_load4_shift<TI>(g, img, frame, q, W, dy, dx, v);
+        image_store4(g, img_out, group, q, v);
+    } else {
+        float v[3];
+        image_load1_shift<TI>(g, img, frame, q, W, dy, dx, v);
+        image_store1(g, img_out, group, q, v);
+    }
+}
+template <typename TI>
+__device__ __forceinline__ void gather_tactile_piece_shift(const GatherGeom& g, const void* tac, float* out, long frame, long group, int s, int q,
+                                                           int w, int dy, int dx) {
+    float* o = out + group * (3L * g.hw);
+    if (g.tac_vec)
+        *(f32x4*)(o + 4L * q) = tactile_load4_shift<TI>(g, tac, frame, s, q, w, dy, dx);
+    else
+        o[q] = tactile_load1_shift<TI>(g, tac, frame, s, q, w, dy, dx);
+}
+
 // item r of a sample -> its frame f and the piece q of that frame, and for a tactile item the sensor s: frame-major, then sensor, then piece
 __device__ __forceinline__ void gather_image_decode(const GatherGeom& g, int r, int& f, int& q) {
     const int per_frame = g.img_vec ? g.HW / 4 : g.HW;

@@ -49,6 +49,10 @@ struct ReplayGatherArgs {
     int img_blocks, half_blocks;             // of one run: blocks [0, img_blocks) do the image, [img_blocks, half_blocks) the tactile frames; the
                                              // stacked kernels run two such halves, observations then next observations
     long img_items, tac_items;               // lanes of work of each modality in one run
+    // random shift (the SHIFT instantiations alone read these; they stand last, so every other field keeps its place in the argument block)
+    const int32_t* shifts;                   // (B, 2, 2, 2): [sample, half, modality, (dy, dx)]
+    int img_pad, tac_pad;                    // every shift is clamped to [-pad, pad] of its modality
+    int img_W, tac_w;                        // the widths of an image and a tactile frame
 };
 
 // store row the sample reads, (rows[b] + shift) % n_rows, or -1 when rows[b] is out of range.  step: 1 = the same environment one step later
@@ -70,8 +74,32 @@ __device__ __forceinline__ void tactile_item(const GatherGeom& g, const void* sr
         gather_tactile_item<float>(g, src, outs, row, b, r);
 }
 
-// ROWS2: the next half takes its rows from a.next_rows as they are
-template <bool ROWS2>
+// the items of the stacked kernel through the shift of (sample b, half `half`)
+__device__ __forceinline__ void image_item_shift(const ReplayGatherArgs& a, const void* src, float* out, long row, int b, int r, int half) {
+    int f, q, dy, dx;
+    gather_image_decode(a.g, r, f, q);
+    gather_shift(a.shifts, b, half, 0, a.img_pad, dy, dx);
+    const long frame = row >= 0 ? row * a.g.fs + f : -1, group = (long)b * a.g.fs + f;
+    if (a.g.img_u8)
+        gather_image_piece_shift<uint8_t>(a.g, src, out, frame, group, q, a.img_W, dy, dx);
+    else
+        gather_image_piece_shift<float>(a.g, src, out, frame, group, q, a.img_W, dy, dx);
+}
+__device__ __forceinline__ void tactile_item_shift(const ReplayGatherArgs& a, const void* src, float* const (&outs)[M3L_MAX_SENSORS], long row, int b,
+                                                   int r, int half) {
+    int f, s, q, dy, dx;
+    gather_tactile_decode(a.g, r, f, s, q);
+    gather_shift(a.shifts, b, half, 1, a.tac_pad, dy, dx);
+    const long frame = row >= 0 ? row * a.g.fs + f : -1, group = (long)b * a.g.fs + f;
+    if (a.g.tac_u8)
+        gather_tactile_piece_shift<uint8_t>(a.g, src, tactile_sensor(outs, s), frame, group, s, q, a.tac_w, dy, dx);
+    else
+        gather_tactile_piece_shift<float>(a.g, src, tactile_sensor(outs, s), frame, group, s, q, a.tac_w, dy, dx);
+}
+
+// ROWS2: the next half takes its rows from a.next_rows as they are.  SHIFT: every piece is read through the random shift of its (sample,
+// half, modality); the instantiations without it are the kernels of before
+template <bool ROWS2, bool SHIFT>
 __global__ void __launch_bounds__(256) replay_gather_load_kernel(ReplayGatherArgs a) {
     const int next = (int)blockIdx.x >= a.half_blocks;                  // uniform over the block
     const int blk = (int)blockIdx.x - (next ? a.half_blocks : 0);
@@ -84,7 +112,9 @@ __global__ void __launch_bounds__(256) replay_gather_load_kernel(ReplayGatherArg
         const long row = replay_row(two ? a.next_rows : a.rows, b, a.n_rows, two ? 0 : a.shift, a.T, a.n_envs, next && !second);
         const void* src = second ? a.img_next : a.img;
         float* out = next ? a.img_out[1] : a.img_out[0];
-        if (a.g.img_u8)
+        if constexpr (SHIFT)
+            image_item_shift(a, src, out, row, b, r, next);
+        else if (a.g.img_u8)
             gather_image_item<uint8_t>(a.g, src, out, row, b, r);
         else
             gather_image_item<float>(a.g, src, out, row, b, r);
@@ -96,7 +126,12 @@ __global__ void __launch_bounds__(256) replay_gather_load_kernel(ReplayGatherArg
         const long row = replay_row(two ? a.next_rows : a.rows, b, a.n_rows, two ? 0 : a.shift, a.T, a.n_envs, next && !second);
         const void* src = second ? a.tac_next : a.tac;
         // two calls, not a local array of selected pointers: that array would be an alloca the compiler moves to LDS
-        if (next)
+        if constexpr (SHIFT) {
+            if (next)
+                tactile_item_shift(a, src, a.tac_out[1], row, b, r, 1);
+            else
+                tactile_item_shift(a, src, a.tac_out[0], row, b, r, 0);
+        } else if (next)
             tactile_item(a.g, src, a.tac_out[1], row, b, r);
         else
             tactile_item(a.g, src, a.tac_out[0], row, b, r);
@@ -205,32 +240,45 @@ __global__ void __launch_bounds__(256) replay_gather_load_frames_kernel(ReplayGa
 // rows2: the two stacks of a sample belong to different rows and share no frame that the kernel could know of, so a sample is 2 fs source
 // frames, each written once.  Source k < fs is observation frame k of rows[b]; source fs + j is next-observation frame j of next_rows[b]: for
 // j < fs - 1 observation frame j + 1 of that row (with that row's age), for j = fs - 1 its next frame.  -> the row the source belongs to (-1:
-// not read) and, in kk, the source's number in replay_frame's terms
+// not read) and, in kk, the source's number in replay_frame's terms.  ONE_LIST: next_rows may be NULL, and the next observation is then that
+// of rows[b] itself
+template <bool ONE_LIST>
 __device__ __forceinline__ long replay_rows2_source(const ReplayGatherArgs& a, int b, int k, int& kk, int& j) {
     const int fs = a.g.fs;
     const bool nxt = k >= fs;
     j = nxt ? k - fs : k;                                               // the frame's place in its output stack
     kk = nxt ? (j == fs - 1 ? fs : j + 1) : k;
-    return replay_row(nxt ? a.next_rows : a.rows, b, a.n_rows, nxt ? 0 : a.shift, a.T, a.n_envs, 0);
+    const bool own = nxt && (!ONE_LIST || a.next_rows);                 // the source's row comes from next_rows
+    return replay_row(own ? a.next_rows : a.rows, b, a.n_rows, own ? 0 : a.shift, a.T, a.n_envs, 0);
 }
 
+// SHIFT: the random-shift form of both frame kernels.  The two halves of a sample have shifts of their own, so a loaded piece cannot go to
+// both stacks: 2 fs single-destination pieces per sample whether next_rows is given or not, each read through the shift of its half
+template <bool SHIFT>
 __global__ void __launch_bounds__(256) replay_gather_load_frames_rows2_kernel(ReplayGatherArgs a) {
     const int fs = a.g.fs;
     int b, k, s, q, kk, j;
     if ((int)blockIdx.x < a.img_blocks) {                               // uniform over the block
         if (!frames_image_item(a, b, k, q)) return;
-        const long row = replay_rows2_source(a, b, k, kk, j);
+        const long row = replay_rows2_source<SHIFT>(a, b, k, kk, j);
         const bool second = kk == fs && a.img_next;
         const long frame = replay_frame(a.ages, row, kk, fs, a.T, a.n_envs, second);
         const void* src = second ? a.img_next : a.img;
         float* out = k >= fs ? a.img_out[1] : a.img_out[0];
-        if (a.g.img_u8)
+        if constexpr (SHIFT) {
+            int dy, dx;
+            gather_shift(a.shifts, b, k >= fs, 0, a.img_pad, dy, dx);
+            if (a.g.img_u8)
+                gather_image_piece_shift<uint8_t>(a.g, src, out, frame, (long)b * fs + j, q, a.img_W, dy, dx);
+            else
+                gather_image_piece_shift<float>(a.g, src, out, frame, (long)b * fs + j, q, a.img_W, dy, dx);
+        } else if (a.g.img_u8)
             gather_image_piece<uint8_t>(a.g, src, out, frame, (long)b * fs + j, q);
         else
             gather_image_piece<float>(a.g, src, out, frame, (long)b * fs + j, q);
     } else {
         if (!frames_tactile_item(a, b, k, s, q)) return;
-        const long row = replay_rows2_source(a, b, k, kk, j);
+        const long row = replay_rows2_source<SHIFT>(a, b, k, kk, j);
         const bool second = kk == fs && a.tac_next;
         const long frame = replay_frame(a.ages, row, kk, fs, a.T, a.n_envs, second);
         const void* src = second ? a.tac_next : a.tac;
@@ -238,7 +286,14 @@ __global__ void __launch_bounds__(256) replay_gather_load_frames_rows2_kernel(Re
         float* out0 = tactile_sensor(a.tac_out[0], s);
         float* out1 = tactile_sensor(a.tac_out[1], s);
         float* out = k >= fs ? out1 : out0;
-        if (a.g.tac_u8)
+        if constexpr (SHIFT) {
+            int dy, dx;
+            gather_shift(a.shifts, b, k >= fs, 1, a.tac_pad, dy, dx);
+            if (a.g.tac_u8)
+                gather_tactile_piece_shift<uint8_t>(a.g, src, out, frame, (long)b * fs + j, s, q, a.tac_w, dy, dx);
+            else
+                gather_tactile_piece_shift<float>(a.g, src, out, frame, (long)b * fs + j, s, q, a.tac_w, dy, dx);
+        } else if (a.g.tac_u8)
             gather_tactile_piece<uint8_t>(a.g, src, out, frame, (long)b * fs + j, s, q);
         else
             gather_tactile_piece<float>(a.g, src, out, frame, (long)b * fs + j, s, q);
@@ -302,15 +357,19 @@ __global__ void replay_nstep_rows_kernel(const float* __restrict__ actions, cons
     if (next_rows_out) next_rows_out[b] = last;
 }
 
-// The four gather entry points.  ages: the stores hold single frames (m3l_replay_gather_load_frames*) and a sample is fs + 1 source frames,
+// The six gather entry points.  ages: the stores hold single frames (m3l_replay_gather_load_frames*) and a sample is fs + 1 source frames,
 // with next_rows 2 fs, in one run of blocks; NULL: the stores are stacked (m3l_replay_gather_load*) and a sample is fs frames in each of two
-// runs.  next_rows: the *_rows2 entry points' second row list, else NULL.
+// runs.  next_rows: the second row list of the *_rows2 and (there it may be NULL) the *_shift entry points, else NULL.  shifts with a pad > 0
+// of a modality that is stored: the SHIFT kernels, the frame one with 2 fs sources a sample whatever next_rows is; else the kernels of before.
 int replay_gather_launch(const char* who, const void* image_store, const void* image_next_store, int image_u8, int H, int W,
                          double img_lo, double img_hi, float* image, float* image_next, const void* tactile_store, const void* tactile_next_store,
                          int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out,
                          float* const* tactile_next_out, const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* rows, long row_shift,
-                         const int64_t* next_rows, int B, void* stream) {
+                         const int64_t* next_rows, const int32_t* shifts, int image_pad, int tactile_pad, int B, void* stream) {
     const bool frames = ages != nullptr;
+    M3L_CHECK(image_pad >= 0 && image_pad < (1 << 15) && tactile_pad >= 0 && tactile_pad < (1 << 15),
+              "%s: image_pad=%d tactile_pad=%d outside [0, 2^15)", who, image_pad, tactile_pad);
+    const bool shifted = shifts && ((image_store && image_pad) || (tactile_store && tactile_pad));
     M3L_CHECK(image_store || tactile_store, "%s: neither an image nor a tactile %sstore", who, frames ? "frame " : "");
     M3L_CHECK((image_store || !image_next_store) && (tactile_store || !tactile_next_store), "%s: a next store without its store", who);
     M3L_CHECK(T >= 1 && n_envs >= 1 && frame_stack >= 1 && B >= 1 && rows, "%s: T=%d n_envs=%d frame_stack=%d B=%d", who, T, n_envs, frame_stack,
@@ -319,7 +378,8 @@ int replay_gather_launch(const char* who, const void* image_store, const void* i
     ReplayGatherArgs a;
     memset(&a, 0, sizeof(a));
     a.rows = rows, a.next_rows = next_rows, a.ages = ages;
-    const long sources = !frames ? frame_stack : next_rows ? 2L * frame_stack : frame_stack + 1L;       // frames of one sample in one run
+    const long sources = !frames ? frame_stack : next_rows || shifted ? 2L * frame_stack : frame_stack + 1L;      // frames of one sample in one run
+    a.shifts = shifts, a.img_pad = image_pad, a.tac_pad = tactile_pad, a.img_W = W, a.tac_w = tw;
     const int runs = frames ? 1 : 2;
     a.n_rows = (long)T * n_envs, a.shift = row_shift;
     a.T = T, a.n_envs = n_envs, a.g.fs = frame_stack;
@@ -329,6 +389,7 @@ int replay_gather_launch(const char* who, const void* image_store, const void* i
         M3L_CHECK(image_next, "%s: the next-observation image output is NULL", who);
         a.img = image_store, a.img_next = image_next_store, a.img_out[0] = image, a.img_out[1] = image_next;
         a.g.img_vec = a.g.img_vec && gather_aligned(image_next, 16) && (!image_next_store || gather_aligned(image_next_store, image_u8 ? 4 : 16));
+        if (shifted) a.g.img_vec = a.g.img_vec && W % 4 == 0;          // a shifted lane's 4 pixels lie in one row
         img_per = sources * gather_image_pieces(a.g);
     }
     if (tactile_store) {
@@ -349,14 +410,20 @@ int replay_gather_launch(const char* who, const void* image_store, const void* i
     M3L_CHECK(runs * (img_blocks + tac_blocks) <= INT32_MAX, "%s: B=%d too large", who, B);
     a.img_blocks = (int)img_blocks, a.half_blocks = (int)(img_blocks + tac_blocks);
     const unsigned grid = (unsigned)(runs * a.half_blocks);
-    if (!frames && !next_rows)
-        replay_gather_load_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    if (shifted && !frames && !next_rows)
+        replay_gather_load_kernel<false, true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else if (shifted && !frames)
+        replay_gather_load_kernel<true, true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else if (shifted)
+        replay_gather_load_frames_rows2_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else if (!frames && !next_rows)
+        replay_gather_load_kernel<false, false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     else if (!frames)
-        replay_gather_load_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+        replay_gather_load_kernel<true, false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     else if (!next_rows)
         replay_gather_load_frames_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
     else
-        replay_gather_load_frames_rows2_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
+        replay_gather_load_frames_rows2_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     M3L_LAUNCH_CHECK();
     return 0;
 }
@@ -658,7 +725,7 @@ int m3l_replay_gather_load(const void* image_store, const void* image_next_store
                            int frame_stack, const int64_t* rows, long row_shift, int B, void* stream) {
     return replay_gather_launch("replay_gather_load", image_store, image_next_store, image_u8, H, W, img_lo, img_hi, image, image_next, tactile_store,
                                 tactile_next_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, nullptr, T, n_envs,
-                                frame_stack, rows, row_shift, nullptr, B, stream);
+                                frame_stack, rows, row_shift, nullptr, nullptr, 0, 0, B, stream);
 }
 
 int m3l_replay_gather_load_rows2(const void* image_store, const void* image_next_store, int image_u8, int H, int W, double img_lo, double img_hi,
@@ -668,7 +735,7 @@ int m3l_replay_gather_load_rows2(const void* image_store, const void* image_next
     M3L_CHECK(next_rows, "replay_gather_load_rows2: next_rows is NULL");
     return replay_gather_launch("replay_gather_load_rows2", image_store, image_next_store, image_u8, H, W, img_lo, img_hi, image, image_next,
                                 tactile_store, tactile_next_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, nullptr,
-                                T, n_envs, frame_stack, rows, row_shift, next_rows, B, stream);
+                                T, n_envs, frame_stack, rows, row_shift, next_rows, nullptr, 0, 0, B, stream);
 }
 
 int m3l_replay_gather_load_frames(const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
@@ -679,7 +746,7 @@ int m3l_replay_gather_load_frames(const void* image_frames, const void* image_ne
     M3L_CHECK(ages, "replay_gather_load_frames: ages is NULL");
     return replay_gather_launch("replay_gather_load_frames", image_frames, image_next_frames, image_u8, H, W, img_lo, img_hi, image, image_next,
                                 tactile_frames, tactile_next_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, ages,
-                                T, n_envs, frame_stack, rows, row_shift, nullptr, B, stream);
+                                T, n_envs, frame_stack, rows, row_shift, nullptr, nullptr, 0, 0, B, stream);
 }
 
 int m3l_replay_gather_load_frames_rows2(const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
@@ -691,7 +758,29 @@ int m3l_replay_gather_load_frames_rows2(const void* image_frames, const void* im
     M3L_CHECK(ages, "replay_gather_load_frames_rows2: ages is NULL");
     return replay_gather_launch("replay_gather_load_frames_rows2", image_frames, image_next_frames, image_u8, H, W, img_lo, img_hi, image,
                                 image_next, tactile_frames, tactile_next_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out,
-                                tactile_next_out, ages, T, n_envs, frame_stack, rows, row_shift, next_rows, B, stream);
+                                tactile_next_out, ages, T, n_envs, frame_stack, rows, row_shift, next_rows, nullptr, 0, 0, B, stream);
+}
+
+int m3l_replay_gather_load_shift(const void* image_store, const void* image_next_store, int image_u8, int H, int W, double img_lo, double img_hi,
+                                 float* image, float* image_next, const void* tactile_store, const void* tactile_next_store, int tactile_u8, int th,
+                                 int tw, int n_sensors, double tac_lo, double tac_hi, float* const* tactile_out, float* const* tactile_next_out, int T,
+                                 int n_envs, int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, const int32_t* shifts,
+                                 int image_pad, int tactile_pad, int B, void* stream) {
+    return replay_gather_launch("replay_gather_load_shift", image_store, image_next_store, image_u8, H, W, img_lo, img_hi, image, image_next,
+                                tactile_store, tactile_next_store, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out, tactile_next_out, nullptr,
+                                T, n_envs, frame_stack, rows, row_shift, next_rows, shifts, image_pad, tactile_pad, B, stream);
+}
+
+int m3l_replay_gather_load_frames_shift(const void* image_frames, const void* image_next_frames, int image_u8, int H, int W, double img_lo,
+                                        double img_hi, float* image, float* image_next, const void* tactile_frames,
+                                        const void* tactile_next_frames, int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi,
+                                        float* const* tactile_out, float* const* tactile_next_out, const int32_t* ages, int T, int n_envs,
+                                        int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, const int32_t* shifts,
+                                        int image_pad, int tactile_pad, int B, void* stream) {
+    M3L_CHECK(ages, "replay_gather_load_frames_shift: ages is NULL");
+    return replay_gather_launch("replay_gather_load_frames_shift", image_frames, image_next_frames, image_u8, H, W, img_lo, img_hi, image,
+                                image_next, tactile_frames, tactile_next_frames, tactile_u8, th, tw, n_sensors, tac_lo, tac_hi, tactile_out,
+                                tactile_next_out, ages, T, n_envs, frame_stack, rows, row_shift, next_rows, shifts, image_pad, tactile_pad, B, stream);
 }
 
 int m3l_replay_gather_rows(const float* actions, const float* rewards, const float* dones, const float* timeouts, int T, int n_envs, int A,

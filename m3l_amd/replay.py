@@ -48,6 +48,21 @@ max_priority of before the call, a row of zero mass or outside the ring is skipp
     target_q = head.td_target(extractor(batch.next_observations), batch.rewards, batch.dones, batch.discounts, ...)
     critic_loss, td = head.critic_loss(features, batch.actions, target_q, weights=batch.weights, return_td_errors=True)
     buffer.update_priorities(batch.rows, td)
+
+`random_shift=p` (or `dict(image=p_i, tactile=p_t)`) gives the random-shift augmentation of DrQ (Kostrikov et al. 2021) and RAD (Laskin et al.
+2020): replicate-pad a frame by p pixels and crop it at a random offset.  Neither the reference tree nor SB3 has it: restated in
+tests/shift_cases.py, parity unpinned.  `shifts` (B, 2, 2, 2) int32 holds one (dy, dx) per [sample, half (0 observations, 1 next
+observations), modality (0 image, 1 tactile)]: all frames of the stack, all three channels and all sensors share it, the two halves are drawn
+independently, and the kernel clamps every entry to [-p, p].  With x the unaugmented LoadedObs tensor of a half, (B, 3 fs, H, W),
+
+    out[b, c, y, x] = x[b, c, clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1)]
+
+which is `F.pad(x, (p, p, p, p), mode="replicate")[..., p + dy : p + dy + H, p + dx : p + dx + W]`, and the normalisation is elementwise, so an
+augmented batch has the bits of that indexing applied to the unaugmented batch of the same rows.  The shift is an address change on the read
+side of the same one gather launch (m3l_replay_gather_load_shift / m3l_replay_gather_load_frames_shift); `sample()` draws the shifts with one
+torch.randint per distinct nonzero pad on the device, reads nothing back and keeps them in `last_shifts`.  Both LoadedObs are augmented, so
+`mae(x)`, the actor and the critics all see the shifted observations; `sample(indices=..., shifts=torch.zeros(...))` gives the unaugmented
+batch of the same rows.  DrQ's averaging over K and M augmentations is the caller's loop over `sample(indices=...)`.
 """
 import math
 from typing import NamedTuple
@@ -73,10 +88,30 @@ def _check_next_rows(who, next_rows, rows):
         raise ValueError(f"{who}: next_rows must be a contiguous int64 tensor of rows' shape {tuple(rows.shape)}")
 
 
+MAX_SHIFT_PAD = 1 << 15                 # pads of the random shift lie in [0, 2^15)
+
+
+def _check_pad(who, name, p):
+    if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or int(p) < 0:
+        raise ValueError(f"{who}: the {name} pad {p!r} must be an integer >= 0")
+    if int(p) >= MAX_SHIFT_PAD:
+        raise ValueError(f"{who}: the {name} pad {p!r} must be below 2^15 = {MAX_SHIFT_PAD}")
+    return int(p)
+
+
+def _check_shifts(who, shifts, B, device=None):
+    """shifts (B, 2, 2, 2) int32, contiguous, on the device: [sample, half, modality, (dy, dx)]."""
+    if not isinstance(shifts, torch.Tensor) or shifts.dtype != torch.int32 or tuple(shifts.shape) != (B, 2, 2, 2) or not shifts.is_contiguous():
+        raise ValueError(f"{who}: shifts must be a contiguous int32 tensor of shape (B, 2, 2, 2) = {(B, 2, 2, 2)}: [sample, half, modality, (dy, dx)]")
+    _require_cuda(shifts, who + ": shifts")
+    if device is not None and shifts.device != device:
+        raise ValueError(f"{who}: shifts lies on {shifts.device}, the stores on {device}")
+
+
 def _gather_load(who, kind, image, tactile, rows, image_next, tactile_next, image_normalization, tactile_normalization, row_shift, next_rows,
-                 ages=None, frame_stack=None):
+                 ages=None, frame_stack=None, shifts=None, shift_pad=(0, 0)):
     """What `gather_load` (kind "store") and `gather_load_frames` (kind "frames": ages and frame_stack are its own) share: the checks, the
-    outputs, the argument list and the entry point, one-list or rows2."""
+    outputs, the argument list and the entry point, one-list, rows2 or (shifts with a nonzero pad) shift."""
     frames = kind == "frames"
     ref = image if image is not None else tactile
     if ref is None:
@@ -101,6 +136,15 @@ def _gather_load(who, kind, image, tactile, rows, image_next, tactile_next, imag
     else:
         T, n_envs, fs, H, W, th, tw, S = _check_stores(who, image, tactile)
     B = rows.shape[0]
+    try:
+        image_pad, tactile_pad = shift_pad
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: shift_pad must be a pair (image_pad, tactile_pad)") from None
+    image_pad, tactile_pad = _check_pad(who, "image", image_pad), _check_pad(who, "tactile", tactile_pad)
+    if shifts is not None:
+        _check_shifts(who, shifts, B, ref.device)
+    # a pad of a modality that is not stored shifts nothing
+    shifted = shifts is not None and bool((image is not None and image_pad) or (tactile is not None and tactile_pad))
     img, tacs = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
     img_next, tacs_next = _loaded_outputs(B, fs, H, W, th, tw, S, ref.device)
     args = (L.ptr(image), L.ptr(image_next), int(image is not None and image.dtype == torch.uint8), H, W, float(image_normalization[0]),
@@ -108,26 +152,31 @@ def _gather_load(who, kind, image, tactile, rows, image_next, tactile_next, imag
             int(tactile is not None and tactile.dtype == torch.uint8), th, tw, S, float(tactile_normalization[0]), float(tactile_normalization[1]),
             L.ptr_array(tacs), L.ptr_array(tacs_next)) + ((L.ptr(ages),) if frames else ()) + (T, n_envs, fs, L.ptr(rows), int(row_shift))
     entry = "m3l_replay_gather_load" + ("_frames" if frames else "")
-    if next_rows is not None:
+    if shifted:         # next_rows may be NULL there; without a shift the entry points of before run
+        entry, args = entry + "_shift", args + (L.ptr(next_rows), L.ptr(shifts), image_pad, tactile_pad)
+    elif next_rows is not None:
         entry, args = entry + "_rows2", args + (L.ptr(next_rows),)
     L.check(getattr(L.lib(), entry)(*args, B, _stream()), entry)
     return _as_loaded(img, tacs), _as_loaded(img_next, tacs_next)
 
 
 def gather_load(image_store, tactile_store, rows, image_next_store=None, tactile_next_store=None, image_normalization=(0, 1),
-                tactile_normalization=(-1, 1), row_shift=0, next_rows=None):
+                tactile_normalization=(-1, 1), row_shift=0, next_rows=None, shifts=None, shift_pad=(0, 0)):
     """image_store (T, n_envs, fs, H, W, 3) and / or tactile_store (T, n_envs, fs, 3*S, h, w), uint8 or float32 CUDA tensors, and rows (B) int64
     store rows t * n_envs + e -> (observations, next_observations), two LoadedObs {'image': (B, 3*fs, H, W), 'tactile1..S': (B, 3*fs, h, w)}:
     what `vt_load(_flatten_frame_stack(store[t, e]))` gives for both, in one launch (m3l_replay_gather_load).  The next observation is read
     from `*_next_store` at the same row, or without one from the store itself at step (t + 1) % T.
     next_rows (B) int64: the next observations are those of these store rows instead, taken as they are — row_shift applies to rows alone —
-    and an entry outside [0, T n_envs) gives NaN in that half only (m3l_replay_gather_load_rows2)."""
+    and an entry outside [0, T n_envs) gives NaN in that half only (m3l_replay_gather_load_rows2).
+    shifts (B, 2, 2, 2) int32 [sample, half, modality, (dy, dx)] with shift_pad = (image_pad, tactile_pad): the random shift of the module's
+    docstring, out[y, x] = in[clamp(y + dy), clamp(x + dx)] with every shift clamped to its modality's pad, in the same one launch
+    (m3l_replay_gather_load_shift).  Without shifts, or with no nonzero pad of a stored modality, the entry points above run."""
     return _gather_load("replay.gather_load", "store", image_store, tactile_store, rows, image_next_store, tactile_next_store, image_normalization,
-                        tactile_normalization, row_shift, next_rows)
+                        tactile_normalization, row_shift, next_rows, shifts=shifts, shift_pad=shift_pad)
 
 
 def gather_load_frames(image_frames, tactile_frames, ages, rows, image_next_frames=None, tactile_next_frames=None, image_normalization=(0, 1),
-                       tactile_normalization=(-1, 1), row_shift=0, next_rows=None, *, frame_stack):
+                       tactile_normalization=(-1, 1), row_shift=0, next_rows=None, shifts=None, shift_pad=(0, 0), *, frame_stack):
     """`gather_load` on frame-deduplicated stores: image_frames (T, n_envs, H, W, 3) and / or tactile_frames (T, n_envs, 3*S, h, w), uint8 or
     float32 CUDA tensors whose slot t holds the newest frame of step t's observation, ages (T, n_envs) int32 — how many earlier frames of the
     same episode the stack of a step reaches, clamped by the kernel to [0, frame_stack - 1] — and rows (B) int64 -> (observations,
@@ -136,9 +185,11 @@ def gather_load_frames(image_frames, tactile_frames, ages, rows, image_next_fram
     or without one of the store itself at step (t + 1) % T.
     next_rows (B) int64: the next observations are those of these store rows instead, taken as they are, each with its own age: 2 *
     frame_stack source frames per sample, every one written once (m3l_replay_gather_load_frames_rows2); an entry outside [0, T n_envs)
-    gives NaN in that half only."""
+    gives NaN in that half only.
+    shifts, shift_pad: as for `gather_load` (m3l_replay_gather_load_frames_shift).  The two halves of a sample have shifts of their own, so
+    the shifted form reads 2 * frame_stack source frames per sample with or without next_rows."""
     return _gather_load("replay.gather_load_frames", "frames", image_frames, tactile_frames, rows, image_next_frames, tactile_next_frames,
-                        image_normalization, tactile_normalization, row_shift, next_rows, ages, frame_stack)
+                        image_normalization, tactile_normalization, row_shift, next_rows, ages, frame_stack, shifts, shift_pad)
 
 
 def _scalar_rows(who, actions, rewards, dones, timeouts, rows, reward_scale, reward_clip, row_shift, nstep=None, return_rows=True):
@@ -371,13 +422,17 @@ class DeviceReplayBuffer:
                     > 0 is added to |td|.  `mass` (T, n_envs), `block_mass`, `block_min` and `max_priority` (1) live on the device; at most
                     PER_MAX_ROWS = 2^22 transitions.  With every combination of frame_dedup, n_steps and optimize_memory_usage that is allowed
                     without it.  False: the buffer has none of these arrays and launches none of these kernels.
+    random_shift    the random-shift augmentation of both observation dicts (the module's docstring has the rule): None is off — no new array, no
+                    new launch, the entry points of before — an integer p pads both modalities by p, dict(image=p_i, tactile=p_t) sets them
+                    separately (a missing key: 0); all pads 0 is None.  `sample()` draws the shifts on the device, or takes `shifts=`, and keeps
+                    the tensor it used in `last_shifts`.  A pad must be an integer in [0, 2^15), and 0 for a modality that is not stored.
     check_stacking  with frame_dedup: every add() verifies that contract with torch ops on the device and one read-back — it synchronises: for
                     tests and a first run — and raises ValueError naming the key, the environment and the rule.
     """
 
     def __init__(self, buffer_size, n_envs, obs_shapes, obs_dtypes, action_dim, optimize_memory_usage=False, handle_timeout_termination=True,
                  image_normalization=[0, 1], tactile_normalization=[-1, 1], device="cuda", frame_dedup=False, check_stacking=False, n_steps=1, gamma=0.99,
-                 prioritized=False, alpha=0.6, beta=0.4, priority_eps=1e-6):
+                 prioritized=False, alpha=0.6, beta=0.4, priority_eps=1e-6, random_shift=None):
         self.device = _require_device("DeviceReplayBuffer", device, "replay buffer", "DictReplayBuffer")
         self.n_envs, self.action_dim = int(n_envs), int(action_dim)
         if int(buffer_size) < 1 or self.n_envs < 1 or self.action_dim < 1:
@@ -411,10 +466,30 @@ class DeviceReplayBuffer:
             raise ValueError(f"DeviceReplayBuffer: prioritized=True holds at most {PER_MAX_ROWS} transitions (PER_BLOCK = {PER_BLOCK} rows times 4096 "
                              f"blocks, the block prefix a sample keeps on chip); {self.buffer_size} steps of {self.n_envs} environments are "
                              f"{self.buffer_size * self.n_envs}")
+        self.random_shift = self._shift_pads(random_shift)      # None, or (image_pad, tactile_pad) with a nonzero entry
+        self.last_shifts = None
         self.observations = self.next_observations = None
         self.frames = self.next_frames = self.ages = None
         self.mass = self.block_mass = self.block_min = self.max_priority = None
         self.reset()
+
+    def _shift_pads(self, random_shift):
+        """The `random_shift` keyword -> None (off) or (image_pad, tactile_pad)."""
+        who = "DeviceReplayBuffer: random_shift"
+        if random_shift is None:
+            return None
+        if isinstance(random_shift, dict):
+            unknown = sorted(str(k) for k in random_shift if k not in ("image", "tactile"))
+            if unknown:
+                raise ValueError(f"{who} has the key(s) {unknown}; it takes 'image' and 'tactile'")
+            pads = {k: _check_pad(who, k, random_shift.get(k, 0)) for k in ("image", "tactile")}
+        else:
+            p = _check_pad(who, "image and tactile", random_shift)
+            pads = {k: (p if k in self.obs_shapes else 0) for k in ("image", "tactile")}      # one integer: every modality the buffer stores
+        for k, v in pads.items():
+            if v and k not in self.obs_shapes:
+                raise ValueError(f"{who}: a pad of {v} for '{k}', which the buffer does not store (obs_shapes has {sorted(self.obs_shapes)})")
+        return (pads["image"], pads["tactile"]) if any(pads.values()) else None
 
     # ---- memory
     def _store_bytes(self, frame_dedup):
@@ -591,7 +666,33 @@ class DeviceReplayBuffer:
             raise ValueError(f"DeviceReplayBuffer.sample: indices name environments outside [0, {self.n_envs})")
         return (t * self.n_envs + e).to(self.device)
 
-    def sample(self, batch_size, env=None, indices=None, beta=None, u=None):
+    def _check_injected_shifts(self, shifts, batch_size, indices, u):
+        """`sample(shifts=)` checked before anything is launched: it belongs to random_shift and has one entry per sample."""
+        who = "DeviceReplayBuffer.sample"
+        if self.random_shift is None:
+            raise ValueError(f"{who}: shifts= belongs to a buffer built with random_shift")
+        if indices is not None:
+            try:
+                B = len(indices[0])
+            except (TypeError, IndexError):
+                raise ValueError(f"{who}: indices must be a pair (batch_inds, env_indices)") from None
+        else:
+            B = int(u.shape[0]) if isinstance(u, torch.Tensor) and u.dim() == 1 else int(batch_size)
+        _check_shifts(who, shifts, B)
+
+    def _draw_shifts(self, B):
+        """(B, 2, 2, 2) int32 on the device: one torch.randint over [-p, p] per distinct nonzero pad (one call when the pads are equal), nothing
+        read back; a modality with pad 0 keeps zeros."""
+        pi, pt = self.random_shift
+        if pi == pt:
+            return torch.randint(-pi, pi + 1, (B, 2, 2, 2), dtype=torch.int32, device=self.device)
+        shifts = torch.zeros(B, 2, 2, 2, dtype=torch.int32, device=self.device)
+        for m, p in ((0, pi), (1, pt)):
+            if p:
+                shifts[:, :, m] = torch.randint(-p, p + 1, (B, 2, 2), dtype=torch.int32, device=self.device)
+        return shifts
+
+    def sample(self, batch_size, env=None, indices=None, beta=None, u=None, shifts=None):
         """`batch_size` transitions drawn uniformly over the valid (step, environment) pairs with one torch.randint on the device (nothing is
         read back), or the pairs of `indices` = (batch_inds, env_indices).  env: a VecNormalize-like object whose reward normalisation is
         applied (`norm_reward`, `ret_rms.var`, `epsilon`, `clip_reward`), or None for raw rewards.  With n_steps > 1 the batch is an
@@ -599,9 +700,14 @@ class DeviceReplayBuffer:
         prioritized: the rows are drawn in proportion to `mass` from u, `batch_size` uniform numbers of one torch.rand on the device or the
         injected float32 tensor `u` (the parity seam), with weights of exponent `beta` (None: the buffer's) — four launches: the draw,
         `per_sample`, `nstep_rows`, the gather — and the batch is a `PrioritizedReplayBatch`; with `indices` the rows are those and the
-        weights are still formed."""
+        weights are still formed.
+        random_shift: both observation dicts leave the same gather launch augmented, with the shifts of one torch.randint per distinct nonzero
+        pad on the device or the injected int32 tensor `shifts` (B, 2, 2, 2) (the parity seam; zeros: the unaugmented batch); the tensor used
+        is kept in `last_shifts`.  The batch types and everything but the two observation dicts are as without it."""
         if not self.prioritized and (beta is not None or u is not None):
             raise ValueError("DeviceReplayBuffer.sample: beta= and u= belong to prioritized=True")
+        if shifts is not None:
+            self._check_injected_shifts(shifts, batch_size, indices, u)
         scale, clip = reward_normalization(env)
         first, count = self._valid_steps()
         if count < 1:
@@ -625,23 +731,30 @@ class DeviceReplayBuffer:
         else:
             actions, rewards, dones, rows = gather_rows(self.actions, self.rewards, self.dones, self.timeouts, draw, scale, clip, shift, return_rows=True)
         # n_steps = 1: next_rows == rows where there are any, and the one-list gathers run
-        obs, next_obs = self._gather(draw, shift, next_rows if self.n_steps > 1 else None)
+        if self.random_shift is not None:
+            if shifts is None:
+                shifts = self._draw_shifts(draw.shape[0])
+            else:
+                _check_shifts("DeviceReplayBuffer.sample", shifts, draw.shape[0])
+            self.last_shifts = shifts
+        obs, next_obs = self._gather(draw, shift, next_rows if self.n_steps > 1 else None, shifts)
         if self.prioritized:
             return PrioritizedReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows, weights)
         if self.n_steps > 1:
             return NStepReplayBatch(obs, actions, next_obs, dones, rewards, rows, discounts, next_rows)
         return ReplayBatch(obs, actions, next_obs, dones, rewards, rows)
 
-    def _gather(self, rows, shift, next_rows):
+    def _gather(self, rows, shift, next_rows, shifts=None):
         """(observations, next_observations) of rows (+ shift in the ring) from the frame or the stacked stores, in one launch; next_rows: the
-        next observations are those rows' (n-step returns), else None."""
+        next observations are those rows' (n-step returns), else None; shifts: the random shifts of a random_shift buffer, else None."""
+        aug = {} if shifts is None else dict(shifts=shifts, shift_pad=self.random_shift)
         if self.frame_dedup:
             nxt = self.next_frames or {}
             return gather_load_frames(self.frames.get("image"), self.frames.get("tactile"), self.ages, rows, nxt.get("image"), nxt.get("tactile"),
-                                      self.image_normalization, self.tactile_normalization, shift, next_rows, frame_stack=self.frame_stack)
+                                      self.image_normalization, self.tactile_normalization, shift, next_rows, frame_stack=self.frame_stack, **aug)
         nxt = self.next_observations or {}
         return gather_load(self.observations.get("image"), self.observations.get("tactile"), rows, nxt.get("image"), nxt.get("tactile"),
-                           self.image_normalization, self.tactile_normalization, shift, next_rows)
+                           self.image_normalization, self.tactile_normalization, shift, next_rows, **aug)
 
     # ---- prioritised replay
     def _draw_prioritized(self, batch_size, indices, beta, u):
