@@ -1010,6 +1010,49 @@ int m3l_replay_gather_load_frames_shift(const void* image_frames, const void* im
                                         int frame_stack, const int64_t* rows, long row_shift, const int64_t* next_rows, const int32_t* shifts,
                                         int image_pad, int tactile_pad, int B, void* stream);
 
+/* ---- rollout augmentation and frame store (ABI 418): the two read-side features of the replay gathers that carry over to PPO's rollout, inside
+ * the one launch of m3l_rollout_gather_load.  Neither the reference tree nor SB3 has either: the rules are restated here and in
+ * tests/rollout_aug_cases.py, parity unpinned.
+ *
+ * Shift (RAD, Laskin et al. 2020, was introduced on PPO; it augments the minibatch at update time and leaves the stored old_log_prob / values
+ * alone).  shifts (B, 2, 2) int32, contiguous, on the device: [sample, modality (0 image, 1 tactile), (dy, dx)].  A rollout minibatch has one
+ * observation dict, so there is no half axis.  One shift per (sample, modality): all frames of the stack, all three channels and all S sensors
+ * share it.  The kernel clamps every entry to [-pad, pad] of its modality (image_pad, tactile_pad) by comparisons, so any int32 is an entry.
+ * With x the tensor the unshifted gather writes, (B, 3 fs, H, W):
+ *     out[b, c, y, x] = x[b, c, clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1)]
+ * the rule of "random-shift augmentation" above (tests/shift_cases.random_shift_reference on the unshifted batch of the same indices).
+ * Normalisation, output layout and 16-byte stores are those of the unshifted kernel; the normalisation is elementwise, so the result has the
+ * bits of that indexing applied to the unshifted entry point's output.  The image's 16-byte form also needs W % 4 == 0, else the element form.
+ *
+ * Frame store.  The reference's FrameStack wrapper makes every observation the last fs frames of its episode, so a stacked rollout store
+ * holds each frame fs times.  image_frames (T + fs - 1, n_envs, H, W, 3), tactile_frames (T + fs - 1, n_envs, 3 S, h, w), ages (T, n_envs)
+ * int32; T is the number of steps.  Slot t + fs - 1 holds the newest frame of step t's observation; slots 0 .. fs - 2 hold the older frames
+ * of step 0's stack (the prologue).  Frame k of step (t, e), 0 the oldest and fs - 1 the newest, is read from
+ *     slot t + fs - 1 - min(fs - 1 - k, clamp(ages[t, e], 0, fs - 1))
+ * which lies in [t, t + fs - 1] for every int32 age: no value of ages leaves the store.  ages[t, e] is how many earlier frames of the same
+ * episode the stack of step (t, e) reaches: 0 at an episode's first step, where the stack is fs copies of one frame.  Unlike the replay ring
+ * there is no wrap and every step stays sampleable.  The same bytes move per sample as from the stacked store.
+ *
+ * m3l_rollout_gather_load_shift is m3l_rollout_gather_load with `shifts, image_pad, tactile_pad` in front of B;
+ * m3l_rollout_gather_load_frames takes the frame stores in place of the stacked stores and `ages` in front of T;
+ * m3l_rollout_gather_load_frames_shift takes both.  All four share one launcher and one kernel template <FRAMES, SHIFT>; the work
+ * decomposition is that of m3l_rollout_gather_load (each output piece loaded once and written once); no LDS, scratch or atomics.
+ *   shifts NULL, or a pad of 0 for every modality that is stored: the launch, and so the bits, of the entry point without `_shift`.
+ * Index contract: a flat index outside [0, T n_envs) is never read (neither a store nor ages) and gives NaN outputs.
+ * Errors, nothing written: those of m3l_rollout_gather_load, a pad outside [0, 2^15), ages NULL for a frames entry point. */
+int m3l_rollout_gather_load_shift(const void* image_store, int image_u8, int H, int W, double img_lo, double img_hi, float* image,
+                                  const void* tactile_store, int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi,
+                                  float* const* tactile_out, int T, int n_envs, int frame_stack, const int64_t* idx, const int32_t* shifts,
+                                  int image_pad, int tactile_pad, int B, void* stream);
+int m3l_rollout_gather_load_frames(const void* image_frames, int image_u8, int H, int W, double img_lo, double img_hi, float* image,
+                                   const void* tactile_frames, int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi,
+                                   float* const* tactile_out, const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* idx, int B,
+                                   void* stream);
+int m3l_rollout_gather_load_frames_shift(const void* image_frames, int image_u8, int H, int W, double img_lo, double img_hi, float* image,
+                                         const void* tactile_frames, int tactile_u8, int th, int tw, int n_sensors, double tac_lo, double tac_hi,
+                                         float* const* tactile_out, const int32_t* ages, int T, int n_envs, int frame_stack, const int64_t* idx,
+                                         const int32_t* shifts, int image_pad, int tactile_pad, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

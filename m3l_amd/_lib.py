@@ -256,6 +256,14 @@ _SIGS = {
                                            C.c_double, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_p, c_p, c_i, c_i, c_i, c_p]),
     "m3l_replay_gather_load_frames_shift": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double,
                                                   C.c_double, c_p, c_p, c_p, c_i, c_i, c_i, c_p, C.c_long, c_p, c_p, c_i, c_i, c_i, c_p]),
+    # rollout augmentation and frame store (ABI 418): m3l_rollout_gather_load with shifts and the two pads in front of B, with ages in front of T
+    # (the stores then hold single frames), and with both
+    "m3l_rollout_gather_load_shift": (c_i, [c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, c_p,
+                                            c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "m3l_rollout_gather_load_frames": (c_i, [c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, c_p,
+                                             c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
+    "m3l_rollout_gather_load_frames_shift": (c_i, [c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double,
+                                                   c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

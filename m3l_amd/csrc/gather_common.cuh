@@ -142,6 +142,22 @@ __device__ __forceinline__ void gather_shift(const int32_t* __restrict__ shifts,
     dy = gather_clamp(s[0], -pad, pad), dx = gather_clamp(s[1], -pad, pad);
 }
 
+// the same from shifts (B, 2, 2), [sample, modality, (dy, dx)]: the rollout's minibatch has one observation dict and so no half axis
+__device__ __forceinline__ void gather_shift_one(const int32_t* __restrict__ shifts, int b, int modality, int pad, int& dy, int& dx) {
+    const int32_t* __restrict__ s = shifts + ((long)b * 2 + modality) * 2;
+    dy = gather_clamp(s[0], -pad, pad), dx = gather_clamp(s[1], -pad, pad);
+}
+
+// The rollout's frame store (include/m3l_amd.h "rollout augmentation and frame store"): T + fs - 1 slots, slot t + fs - 1 holds the newest frame
+// of step t's observation and slots 0 .. fs - 2 the older frames of step 0's stack.  -> the slot that frame k (0 the oldest, fs - 1 the newest)
+// of step t reads, for a stack that reaches `age` earlier frames of its episode.  The age is clamped by comparisons, so the slot lies in
+// [t, t + fs - 1] for every int: no value of ages leaves the store.  Host and device: the stand-alone host check calls it as it is.
+__host__ __device__ inline long rollout_frame_slot(long t, int k, int fs, int age) {
+    const int reach = age < 0 ? 0 : (age > fs - 1 ? fs - 1 : age);
+    const int back = fs - 1 - k < reach ? fs - 1 - k : reach;
+    return t + (fs - 1 - back);
+}
+
 // 12 consecutive elements from an address that has only the alignment of its element.  float: twelve 4-byte loads, which the compiler may
 // combine into wider ones of 4-byte alignment.  uint8: the aligned 4-byte words that cover the span (the fourth only when the span reaches it:
 // past a span that ends on a word boundary the store may end) and the bytes taken out of them with funnel shifts.  The store is 4-byte aligned

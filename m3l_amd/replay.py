@@ -73,7 +73,8 @@ import torch
 from . import _lib as L
 from .functional import _require_cuda
 from .pretrain_utils import LoadedObs
-from .rollout import _as_loaded, _check_obs, _check_stores, _loaded_outputs, _obs_spec, _require_device, _stream
+from .rollout import (MAX_SHIFT_PAD, _as_loaded, _check_obs, _check_pad, _check_shift_pad, _check_shifts, _check_stores,  # noqa: F401
+                      _draw_shifts, _loaded_outputs, _obs_spec, _require_device, _shift_pads, _stream)
 
 
 def _check_rows(who, rows):
@@ -86,26 +87,6 @@ def _check_next_rows(who, next_rows, rows):
     _require_cuda(next_rows, who + ": next_rows")
     if next_rows.dtype != torch.int64 or next_rows.shape != rows.shape or not next_rows.is_contiguous():
         raise ValueError(f"{who}: next_rows must be a contiguous int64 tensor of rows' shape {tuple(rows.shape)}")
-
-
-MAX_SHIFT_PAD = 1 << 15                 # pads of the random shift lie in [0, 2^15)
-
-
-def _check_pad(who, name, p):
-    if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or int(p) < 0:
-        raise ValueError(f"{who}: the {name} pad {p!r} must be an integer >= 0")
-    if int(p) >= MAX_SHIFT_PAD:
-        raise ValueError(f"{who}: the {name} pad {p!r} must be below 2^15 = {MAX_SHIFT_PAD}")
-    return int(p)
-
-
-def _check_shifts(who, shifts, B, device=None):
-    """shifts (B, 2, 2, 2) int32, contiguous, on the device: [sample, half, modality, (dy, dx)]."""
-    if not isinstance(shifts, torch.Tensor) or shifts.dtype != torch.int32 or tuple(shifts.shape) != (B, 2, 2, 2) or not shifts.is_contiguous():
-        raise ValueError(f"{who}: shifts must be a contiguous int32 tensor of shape (B, 2, 2, 2) = {(B, 2, 2, 2)}: [sample, half, modality, (dy, dx)]")
-    _require_cuda(shifts, who + ": shifts")
-    if device is not None and shifts.device != device:
-        raise ValueError(f"{who}: shifts lies on {shifts.device}, the stores on {device}")
 
 
 def _gather_load(who, kind, image, tactile, rows, image_next, tactile_next, image_normalization, tactile_normalization, row_shift, next_rows,
@@ -136,11 +117,7 @@ def _gather_load(who, kind, image, tactile, rows, image_next, tactile_next, imag
     else:
         T, n_envs, fs, H, W, th, tw, S = _check_stores(who, image, tactile)
     B = rows.shape[0]
-    try:
-        image_pad, tactile_pad = shift_pad
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: shift_pad must be a pair (image_pad, tactile_pad)") from None
-    image_pad, tactile_pad = _check_pad(who, "image", image_pad), _check_pad(who, "tactile", tactile_pad)
+    image_pad, tactile_pad = _check_shift_pad(who, shift_pad)
     if shifts is not None:
         _check_shifts(who, shifts, B, ref.device)
     # a pad of a modality that is not stored shifts nothing
@@ -466,30 +443,12 @@ class DeviceReplayBuffer:
             raise ValueError(f"DeviceReplayBuffer: prioritized=True holds at most {PER_MAX_ROWS} transitions (PER_BLOCK = {PER_BLOCK} rows times 4096 "
                              f"blocks, the block prefix a sample keeps on chip); {self.buffer_size} steps of {self.n_envs} environments are "
                              f"{self.buffer_size * self.n_envs}")
-        self.random_shift = self._shift_pads(random_shift)      # None, or (image_pad, tactile_pad) with a nonzero entry
+        self.random_shift = _shift_pads("DeviceReplayBuffer: random_shift", random_shift, self.obs_shapes)      # None, or (image_pad, tactile_pad)
         self.last_shifts = None
         self.observations = self.next_observations = None
         self.frames = self.next_frames = self.ages = None
         self.mass = self.block_mass = self.block_min = self.max_priority = None
         self.reset()
-
-    def _shift_pads(self, random_shift):
-        """The `random_shift` keyword -> None (off) or (image_pad, tactile_pad)."""
-        who = "DeviceReplayBuffer: random_shift"
-        if random_shift is None:
-            return None
-        if isinstance(random_shift, dict):
-            unknown = sorted(str(k) for k in random_shift if k not in ("image", "tactile"))
-            if unknown:
-                raise ValueError(f"{who} has the key(s) {unknown}; it takes 'image' and 'tactile'")
-            pads = {k: _check_pad(who, k, random_shift.get(k, 0)) for k in ("image", "tactile")}
-        else:
-            p = _check_pad(who, "image and tactile", random_shift)
-            pads = {k: (p if k in self.obs_shapes else 0) for k in ("image", "tactile")}      # one integer: every modality the buffer stores
-        for k, v in pads.items():
-            if v and k not in self.obs_shapes:
-                raise ValueError(f"{who}: a pad of {v} for '{k}', which the buffer does not store (obs_shapes has {sorted(self.obs_shapes)})")
-        return (pads["image"], pads["tactile"]) if any(pads.values()) else None
 
     # ---- memory
     def _store_bytes(self, frame_dedup):
@@ -680,18 +639,6 @@ class DeviceReplayBuffer:
             B = int(u.shape[0]) if isinstance(u, torch.Tensor) and u.dim() == 1 else int(batch_size)
         _check_shifts(who, shifts, B)
 
-    def _draw_shifts(self, B):
-        """(B, 2, 2, 2) int32 on the device: one torch.randint over [-p, p] per distinct nonzero pad (one call when the pads are equal), nothing
-        read back; a modality with pad 0 keeps zeros."""
-        pi, pt = self.random_shift
-        if pi == pt:
-            return torch.randint(-pi, pi + 1, (B, 2, 2, 2), dtype=torch.int32, device=self.device)
-        shifts = torch.zeros(B, 2, 2, 2, dtype=torch.int32, device=self.device)
-        for m, p in ((0, pi), (1, pt)):
-            if p:
-                shifts[:, :, m] = torch.randint(-p, p + 1, (B, 2, 2), dtype=torch.int32, device=self.device)
-        return shifts
-
     def sample(self, batch_size, env=None, indices=None, beta=None, u=None, shifts=None):
         """`batch_size` transitions drawn uniformly over the valid (step, environment) pairs with one torch.randint on the device (nothing is
         read back), or the pairs of `indices` = (batch_inds, env_indices).  env: a VecNormalize-like object whose reward normalisation is
@@ -733,7 +680,7 @@ class DeviceReplayBuffer:
         # n_steps = 1: next_rows == rows where there are any, and the one-list gathers run
         if self.random_shift is not None:
             if shifts is None:
-                shifts = self._draw_shifts(draw.shape[0])
+                shifts = _draw_shifts(self.random_shift, (draw.shape[0], 2, 2, 2), self.device)
             else:
                 _check_shifts("DeviceReplayBuffer.sample", shifts, draw.shape[0])
             self.last_shifts = shifts

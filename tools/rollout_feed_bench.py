@@ -18,7 +18,18 @@ torch.profiler over a few calls in a run of their own.  For (c): gbytes_per_s = 
 one write of the float32 result) over call_us, and its share of the 6.29 TB/s a float4 copy reaches on this chip (8.0 TB/s is the data-sheet
 figure).  Without a GPU the tool fails; it has no fallback.
 
-Usage: python tools/rollout_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32]   (one JSON line on stdout)"""
+--shift / --dedup (EXPERIMENTS.md §5.30) time the read-side features of the same launch instead, on stores made on the device: a frame store
+(T + fs - 1, n_envs, ...) of random frames with the ages of episodes of 20 to 400 steps, and the stacked store that the slot rule reads out of it, so both hold the same
+observations and their batches are compared bit for bit before anything is timed.  In alternating windows of one run:
+  stacked / stacked_parent   m3l_rollout_gather_load through this build and, with --parent-lib, through the parent commit's library; then
+  / stacked_repeat           this build's once more, so that the place of a window in its round can be told from the build
+  stacked_shift              m3l_rollout_gather_load_shift, pads --pads (default 4,2), shifts drawn once per batch outside the window   (--shift)
+  frames / frames_shift      m3l_rollout_gather_load_frames[_shift] on the frame store                                                  (--dedup)
+  torch_shift                the unshifted launch plus `torch_shift_baseline` on every tensor of the batch, with its launch count      (--shift)
+and, outside the windows, one add() in both modes and store_bytes() at PPO's defaults.
+
+Usage: python tools/rollout_feed_bench.py [--rounds 5] [--iters 200] [--host-iters 5] [--variants u8,f32] [--shift] [--dedup] [--pads 4,2]
+       [--parent-lib PATH]   (one JSON line on stdout)"""
 import argparse
 import json
 import os
@@ -38,6 +49,19 @@ from m3l_amd.fusion import _flatten_frame_stack  # noqa: E402
 DEV = "cuda:0"
 T, E, FS, H, W, S, TH, TW, B = 4096, 8, 4, 64, 64, 2, 32, 32, 512
 HBM_COPY_TBS, HBM_SPEC_TBS = 6.29, 8.0
+
+
+def torch_shift_baseline(x, shifts_b, pad):
+    """The random shift from torch ops: x (B, C, H, W), shifts_b (B, 2) integers (dy, dx) -> out[b, c, y, x] = x[b, c, clamp(y + dy, 0, H - 1),
+    clamp(x + dx, 0, W - 1)] with (dy, dx) clamped to [-pad, pad].  Every index is clamped to the pad and then to the frame before either
+    torch.gather sees it: torch.gather does not check indices on the device.  tests/test_rollout_aug_cpu.py holds this function to the numpy
+    definition on CPU tensors."""
+    B, C, H, W = x.shape
+    s = shifts_b.to(torch.int64).clamp(-int(pad), int(pad))
+    ys = (torch.arange(H, device=x.device)[None, :] + s[:, 0:1]).clamp(0, H - 1)
+    xs = (torch.arange(W, device=x.device)[None, :] + s[:, 1:2]).clamp(0, W - 1)
+    rows = x.gather(2, ys[:, None, :, None].expand(B, C, H, W))
+    return rows.gather(3, xs[:, None, None, :].expand(B, C, H, W))
 
 
 def window(fn, iters):
@@ -183,19 +207,174 @@ def run_variant(name, a):
     return res
 
 
+def device_frame_stores(image_dtype):
+    """A frame store of random frames, ages and the stacked store the slot rule reads out of them, all made on the device."""
+    g = torch.Generator(device=DEV).manual_seed(0)
+    slots = T + FS - 1
+    if image_dtype == np.uint8:
+        img = torch.randint(0, 256, (slots, E, H, W, 3), dtype=torch.uint8, device=DEV, generator=g)
+    else:
+        img = torch.rand((slots, E, H, W, 3), dtype=torch.float32, device=DEV, generator=g)
+    tac = torch.rand((slots, E, 3 * S, TH, TW), dtype=torch.float32, device=DEV, generator=g) * 2 - 1
+    # ages as a rollout has them: episodes of 20 to 400 steps, so most stacks reach fs - 1 frames back and a few per cent are younger
+    rng = np.random.default_rng(4)
+    host_ages = np.empty((T, E), dtype=np.int32)
+    for env in range(E):
+        t = 0
+        while t < T:
+            n = int(rng.integers(20, 401))
+            host_ages[t:t + n, env] = np.minimum(np.arange(min(n, T - t)), FS - 1)
+            t += n
+    ages = torch.from_numpy(host_ages).to(DEV)
+    frames = {"image": img, "tactile": tac}
+    stacked = {k: torch.empty((T, E, FS) + tuple(v.shape[2:]), dtype=v.dtype, device=DEV) for k, v in frames.items()}
+    t, env = torch.arange(T, device=DEV)[:, None], torch.arange(E, device=DEV)[None, :]
+    for k in range(FS):
+        slot = t + (FS - 1) - torch.clamp(ages.long(), max=FS - 1 - k)
+        for key in frames:
+            stacked[key][:, :, k] = frames[key][slot, env]
+    torch.cuda.synchronize()
+    return frames, ages, stacked
+
+
+def parent_gather(path):
+    """m3l_rollout_gather_load of another build of the library (the parent commit's), called with `gather_load`'s arguments."""
+    import ctypes as C
+    from m3l_amd import _lib as L
+    lib = C.CDLL(path)
+    fn = lib.m3l_rollout_gather_load
+    fn.restype, fn.argtypes = L._SIGS["m3l_rollout_gather_load"]
+
+    def call(image_store, tactile_store, idx):
+        B = idx.shape[0]
+        img_out, tac_outs = R._loaded_outputs(B, FS, H, W, TH, TW, S, image_store.device)
+        rc = fn(L.ptr(image_store), int(image_store.dtype == torch.uint8), H, W, 0.0, 1.0, L.ptr(img_out), L.ptr(tactile_store), 0, TH, TW, S, -1.0, 1.0,
+                L.ptr_array(tac_outs), T, E, FS, L.ptr(idx), B, torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, "the parent library refused the call"
+        return R._as_loaded(img_out, tac_outs)
+    return call, int(lib.m3l_version())
+
+
+def add_us(mode_kw, image_dtype, n=64):
+    """Host time of one add() with a synchronise at the end of n of them, in microseconds; a buffer of n + 1 steps (the cost of an add() does not
+    depend on the buffer's length)."""
+    shapes = {"image": (FS, H, W, 3), "tactile": (FS, 3 * S, TH, TW)}
+    buf = m3l_amd.DeviceRolloutBuffer(n + 1, E, shapes, {"image": image_dtype, "tactile": np.float32}, 4, device=DEV, **mode_kw)
+    g = np.random.default_rng(2)
+    obs = {"image": (g.integers(0, 256, (E,) + shapes["image"]).astype(image_dtype) if image_dtype == np.uint8 else
+                     g.random((E,) + shapes["image"], dtype=np.float32)), "tactile": g.random((E,) + shapes["tactile"], dtype=np.float32)}
+    act, z, start = np.zeros((E, 4), np.float32), np.zeros(E, np.float32), np.zeros(E, bool)
+    buf.add(obs, act, z, np.ones(E, bool), z, z)      # allocates, and with frame_dedup uploads the whole stack
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        buf.add(obs, act, z, start, z, z)
+    torch.cuda.synchronize()
+    return round((time.perf_counter() - t0) / n * 1e6, 1)
+
+
+def ppo_store_bytes(image_dtype):
+    shapes = {"image": (FS, H, W, 3), "tactile": (FS, 3 * S, TH, TW)}
+    mk = lambda **kw: m3l_amd.DeviceRolloutBuffer(T, E, shapes, {"image": image_dtype, "tactile": np.float32}, 4, device=DEV, **kw)      # noqa: E731
+    return {"stacked": mk().store_bytes(), "frame_dedup": mk(frame_dedup=True).store_bytes()}
+
+
+def run_aug_variant(name, a):
+    image_dtype = np.uint8 if name == "u8" else np.float32
+    pads = tuple(int(p) for p in a.pads.split(","))
+    frames, ages, stacked = device_frame_stores(image_dtype)
+    n = T * E
+    perm = np.random.default_rng(1).permutation(n).astype(np.int64)
+    d_idx = [torch.from_numpy(perm[i:i + B]).to(DEV) for i in range(0, n, B)]
+    torch.manual_seed(3)
+    d_shifts = [R._draw_shifts(pads, (B, 2, 2), torch.device(DEV)) for _ in d_idx]
+    state = {}
+
+    def nxt(p):
+        i = state.get(p, 0)
+        state[p] = (i + 1) % len(d_idx)
+        return i
+
+    def stacked_plain():
+        return R.gather_load(stacked["image"], stacked["tactile"], d_idx[nxt("s")])
+
+    def stacked_shift():
+        i = nxt("ss")
+        return R.gather_load(stacked["image"], stacked["tactile"], d_idx[i], shifts=d_shifts[i], shift_pad=pads)
+
+    def frames_plain():
+        return R.gather_load_frames(frames["image"], frames["tactile"], ages, d_idx[nxt("f")], FS)
+
+    def frames_shift():
+        i = nxt("fs")
+        return R.gather_load_frames(frames["image"], frames["tactile"], ages, d_idx[i], FS, shifts=d_shifts[i], shift_pad=pads)
+
+    def torch_shift():
+        i = nxt("t")
+        x = R.gather_load(stacked["image"], stacked["tactile"], d_idx[i])
+        return {k: torch_shift_baseline(v, d_shifts[i][:, 0 if k == "image" else 1], pads[0 if k == "image" else 1]) for k, v in x.items()}
+
+    fns = {"stacked": stacked_plain}
+    if a.parent_lib:
+        call, version = parent_gather(a.parent_lib)
+        fns["stacked_parent"] = lambda: call(stacked["image"], stacked["tactile"], d_idx[nxt("p")])
+        # the same launch of this build once more, in the window after the parent's: what the place in a round is worth
+        fns["stacked_repeat"] = lambda: R.gather_load(stacked["image"], stacked["tactile"], d_idx[nxt("r")])
+    if a.shift:
+        fns["stacked_shift"] = stacked_shift
+    if a.dedup:
+        fns["frames"] = frames_plain
+        if a.shift:
+            fns["frames_shift"] = frames_shift
+    if a.shift:
+        fns["torch_shift"] = torch_shift
+    # equal bits on one minibatch before anything is timed: every unshifted path against the stacked launch, every shifted path against the
+    # torch ops on it
+    first = {p: fn() for p, fn in fns.items()}
+    torch.cuda.synchronize()
+    for p, out in first.items():
+        want = first["torch_shift"] if p.endswith("_shift") else first["stacked"]
+        for k in want:
+            assert torch.equal(out[k], want[k]), f"{name}: {p} disagrees on {k}"
+    state.clear()
+    res = alternate(fns, {p: a.iters for p in fns}, {p: 20 for p in fns}, a.rounds)
+    for p, fn in fns.items():
+        res[p].update(counted(fn))
+    isz = 1 if name == "u8" else 4
+    moved = B * (FS * H * W * 3 * isz + FS * 3 * S * TH * TW * 4) + B * (FS * H * W * 3 + FS * 3 * S * TH * TW) * 4
+    for p in fns:
+        if p != "torch_shift":
+            tbs = moved / (res[p]["call_us"] * 1e-6) / 1e12
+            res[p]["tbytes_per_s"], res[p]["share_of_measured_copy_peak"] = round(tbs, 3), round(tbs / HBM_COPY_TBS, 3)
+    res["bytes_moved"] = moved
+    if a.parent_lib:
+        res["parent_lib_version"] = version
+        lo, hi = res["stacked_parent"]["call_us_min_max"]
+        res["parent_window_spread_us"] = round(hi - lo, 1)
+        res["stacked_minus_parent_us"] = round(res["stacked"]["call_us"] - res["stacked_parent"]["call_us"], 1)
+        res["stacked_repeat_minus_parent_us"] = round(res["stacked_repeat"]["call_us"] - res["stacked_parent"]["call_us"], 1)
+    res["add_us"] = {"stacked": add_us({}, image_dtype), "frame_dedup": add_us({"frame_dedup": True}, image_dtype)}
+    res["store_bytes"] = ppo_store_bytes(image_dtype)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5, help="alternating windows per path")
     ap.add_argument("--iters", type=int, default=200, help="calls per timed window of the device paths (b) and (c)")
     ap.add_argument("--host-iters", type=int, default=5, help="calls per timed window of the host path (a)")
     ap.add_argument("--variants", default="u8,f32")
+    ap.add_argument("--shift", action="store_true", help="time the random-shift forms of the launch (see the docstring)")
+    ap.add_argument("--dedup", action="store_true", help="time the launch on the frame-deduplicated store")
+    ap.add_argument("--pads", default="4,2", help="image,tactile pads of --shift")
+    ap.add_argument("--parent-lib", default=None, help="the parent commit's libm3l_amd.so, for the unshifted launch of both builds in one run")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rollout_feed_bench: no GPU")
     out = {"shape": {"T": T, "n_envs": E, "frame_stack": FS, "image": [H, W, 3], "tactile": [3 * S, TH, TW], "B": B},
            "hbm_peak_tbytes_per_s": {"float4_copy_measured": HBM_COPY_TBS, "spec": HBM_SPEC_TBS}}
     for name in a.variants.split(","):
-        out[name] = run_variant(name, a)
+        out[name] = run_aug_variant(name, a) if a.shift or a.dedup else run_variant(name, a)
     print(json.dumps(out))
 
 
