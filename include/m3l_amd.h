@@ -783,6 +783,68 @@ int m3l_sac_actor_loss_bwd(const float* dloss, const float* coef, int B, float* 
 int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float target_entropy, int B, const float* dloss, float* loss, float* ent_coef,
                           float* dlog_ent_coef, void* stream);
 
+/* ---- SAC critic ensemble (ABI 419): the head above with N critics where it has two, for a high update-to-data ratio (REDQ, Chen et al. 2021:
+ * an ensemble of N critics, the target's minimum over a random subset of M of them, the actor trained against the ensemble's mean) and for
+ * SB3's `n_critics` of any value (sac_mae_policy.py:62 passes it on).  Neither SB3 nor a REDQ implementation is part of the reference tree:
+ * the rule is stated here and restated in float64 by tests/sac_ens_cases.py, parity unpinned.  The struct, the entry points and the results of
+ * the section above do not change; DroQ (LayerNorm and dropout critics) and TQC are not computed.  float32 throughout.
+ *   1. q_c = critic_c(cat([x, a])), c < N: the critic arithmetic of the section above, per critic.
+ *   2. target_q = r + (1 - done) g (min over the subset's entries, in list order, by fminf, of q_target_c(x', a') - ent logp'),
+ *      (a', logp') = actor(x'), g = gamma or discounts[row].  Only the listed critics are evaluated: the cost grows with M, not N.  Duplicates
+ *      are harmless.  subset lives on the device and is never read back: if any entry is outside [0, N), every row of target_q is NaN and
+ *      nothing is read through the bad index.
+ *   3. critic_loss = 0.5 sum_c mean_r w_r (q_c - t)^2 (SB3's sum over the critics);  coef[c, r] = w_r (q_c - t) / B;
+ *      td_abs[r] = (sum_c |q_c - t|) (1 / N).  Weights of ones give the bits of weights = NULL.  Per critic the rows add up in the order of the
+ *      two-critic kernels; the N means then add up from the last critic to the first, each fused onto the sum behind it:
+ *      fma(s_0, 1/B, fma(s_1, 1/B, ... s_{N-1} (1/B))), which at N = 2 is the two-critic kernel's arithmetic.
+ *   4. actor_loss, reduce = 0 (min, SB3's): mean_r (ent logp - min_c q_c); the lowest index among equal minima takes the row's gradient.
+ *   5. actor_loss, reduce = 1 (mean, REDQ's): mean_r (ent logp - (sum_c q_c) (1 / N)), critics ascending; dq_c = -1 / (N B) for every c.
+ *   6. N = 2 with subset NULL and reduce = 0: both loss kernels and td_abs give the bits of m3l_sac_critic_loss_fwd / _w_fwd and
+ *      m3l_sac_actor_loss_fwd; the net walks run the same tile functions in the same order as the two-critic entries.
+ * The actor's own forward and backward stay m3l_sac_actor_fwd / m3l_sac_actor_bwd on an m3l_sac_desc holding the actor's part, with
+ * m3l_sac_ws_bytes; the Polyak update stays m3l_op_ema over all N critics' tensors in one launch; m3l_sac_ent_coef_loss is unchanged.
+ * Launches: critic_fwd 1 (grid: row tiles x N); critic_bwd 1 chain (critics 0 .. N - 1 in order, critic c > 0 adding its dactions to what the
+ * earlier ones wrote, lane for lane) + ceil(N (n_qf + 1) / 8) grouped weight-gradient launches when `grads` is not NULL; td_target 1; each loss
+ * 1 forward and 1 backward.  No float atomics, every sum in a fixed order: two runs give the same bits.
+ * Limits: those of the section above, and 1 <= n_critics <= M3L_SAC_MAX_CRITICS, all critics and their targets alike in widths.  Anything else
+ * is an error and nothing is written.  ws: m3l_sac_ens_ws_bytes bytes (the critics' activations only), one per forward that a backward follows. */
+#define M3L_SAC_MAX_CRITICS 10
+typedef struct m3l_sac_ens_desc {
+    int features, actions;                    /* F, A */
+    int n_pi, n_qf;                           /* hidden layers of latent_pi / of each critic */
+    int pi_width[M3L_SAC_MAX_HIDDEN], qf_width[M3L_SAC_MAX_HIDDEN];
+    float* pi_weight[M3L_SAC_MAX_HIDDEN];
+    float* pi_bias[M3L_SAC_MAX_HIDDEN];
+    float* mu_weight;
+    float* mu_bias;
+    float* log_std_weight;
+    float* log_std_bias;
+    int n_critics;                            /* N, 1 .. M3L_SAC_MAX_CRITICS */
+    float* qf_weight[M3L_SAC_MAX_CRITICS][M3L_SAC_MAX_HIDDEN];  /* [c][0]: [qf_width[0], F + A] */
+    float* qf_bias[M3L_SAC_MAX_CRITICS][M3L_SAC_MAX_HIDDEN];
+    float* q_weight[M3L_SAC_MAX_CRITICS];                       /* [1, last qf width or F + A] */
+    float* q_bias[M3L_SAC_MAX_CRITICS];
+} m3l_sac_ens_desc;
+size_t m3l_sac_ens_ws_bytes(const m3l_sac_ens_desc* head, int B);
+/* q [N, B] is written; ws NULL when no backward follows */
+int m3l_sac_ens_critic_fwd(const m3l_sac_ens_desc* head, int B, const float* x, const float* actions, void* ws, float* q, void* stream);
+/* dq [N, B]: NULL = zero; dactions [B, A] or NULL (not wanted); grads NULL: no parameter gradient, the weight-gradient launches are skipped */
+int m3l_sac_ens_critic_bwd(const m3l_sac_ens_desc* head, int B, const float* dq, void* ws, float* dactions, const m3l_sac_ens_desc* grads,
+                           void* stream);
+/* target_q [B] is written; the descriptor's critics are the target critics.  discounts [B] or NULL (gamma for every row), as in
+ * m3l_sac_td_target_rows.  subset: int32 [n_subset] on the device, 1 <= n_subset <= N, or NULL: all N, ascending (n_subset 0 or N then). */
+int m3l_sac_ens_td_target(const m3l_sac_ens_desc* head, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                          const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, const int* subset, int n_subset,
+                          float* target_q, void* stream);
+/* q [N, B]; weights [B] or NULL (ones); loss[1] and coef [N, B] are written, and td_abs [B] when it is not NULL */
+int m3l_sac_ens_critic_loss_fwd(const float* q, const float* target_q, const float* weights, int N, int B, float* loss, float* coef, float* td_abs,
+                                void* stream);
+/* reduce: 0 = min, 1 = mean.  loss[1] and coef [1 + N, B] = dloss/dlogp [B] then dloss/dq [N, B] are written */
+int m3l_sac_ens_actor_loss_fwd(const float* logp, const float* q, int N, int B, int reduce, float ent_coef, const float* log_ent_coef, float* loss,
+                               float* coef, void* stream);
+/* the backward of both losses: out [n] = dloss[0] coef [n] (dloss: device scalar); n = N B for the critic loss, (1 + N) B for the actor loss */
+int m3l_sac_ens_loss_bwd(const float* dloss, const float* coef, int n, float* out, void* stream);
+
 /* ---- device-resident rollout (ABI 411): what PPO_MAE.train does between `rollout_buffer` and `self.mae(x)` for every minibatch, with the rollout
  * kept in device memory in the layout the vec-env fills it in, (T, n_envs, ...).  Nothing is swapped or flattened: idx [B] (int64) holds flat
  * indices of the reference's swapped order, j -> env = j / T, t = j % T, store row t * n_envs + env            models/ppo_dino_cat_mae.py:25-29

@@ -67,6 +67,17 @@ class SacDesc(C.Structure):
                 ("qf_weight", (c_p * 3) * 2), ("qf_bias", (c_p * 3) * 2), ("q_weight", c_p * 2), ("q_bias", c_p * 2)]
 
 
+SAC_MAX_CRITICS = 10
+
+
+class SacEnsDesc(C.Structure):
+    """m3l_sac_ens_desc: m3l_sac_desc with n_critics and critic tables of M3L_SAC_MAX_CRITICS (include/m3l_amd.h "SAC critic ensemble")."""
+    _fields_ = [("features", c_i), ("actions", c_i), ("n_pi", c_i), ("n_qf", c_i), ("pi_width", c_i * 3), ("qf_width", c_i * 3),
+                ("pi_weight", c_p * 3), ("pi_bias", c_p * 3), ("mu_weight", c_p), ("mu_bias", c_p), ("log_std_weight", c_p), ("log_std_bias", c_p),
+                ("n_critics", c_i), ("qf_weight", (c_p * 3) * SAC_MAX_CRITICS), ("qf_bias", (c_p * 3) * SAC_MAX_CRITICS),
+                ("q_weight", c_p * SAC_MAX_CRITICS), ("q_bias", c_p * SAC_MAX_CRITICS)]
+
+
 _SIGS = {
     "m3l_version": (c_i, []),
     "m3l_last_error": (c_i, [C.c_char_p, c_sz]),
@@ -264,6 +275,14 @@ _SIGS = {
                                              c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
     "m3l_rollout_gather_load_frames_shift": (c_i, [c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double,
                                                    c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p]),
+    # SAC critic ensemble (ABI 419): N critics; td_target takes discounts and gamma, then the subset and its length in front of target_q
+    "m3l_sac_ens_ws_bytes": (c_sz, [C.POINTER(SacEnsDesc), c_i]),
+    "m3l_sac_ens_critic_fwd": (c_i, [C.POINTER(SacEnsDesc), c_i, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_sac_ens_critic_bwd": (c_i, [C.POINTER(SacEnsDesc), c_i, c_p, c_p, c_p, C.POINTER(SacEnsDesc), c_p]),
+    "m3l_sac_ens_td_target": (c_i, [C.POINTER(SacEnsDesc), c_i, c_p, c_p, c_p, c_p, c_p, C.c_float, C.c_float, c_p, c_p, c_i, c_p, c_p]),
+    "m3l_sac_ens_critic_loss_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "m3l_sac_ens_actor_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p]),
+    "m3l_sac_ens_loss_bwd": (c_i, [c_p, c_p, c_i, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

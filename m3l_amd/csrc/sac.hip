@@ -16,6 +16,12 @@
 //   losses       one workgroup each, every thread over its rows in order and the threads' sums through ph_block_sum; the forward stores the
 //                per-row coefficients and the backward scales them by dloss.
 // No float atomics, every sum in a fixed order: the same bits on every run.
+//
+// The critic ensemble ("SAC critic ensemble", the sac_ens_* kernels and m3l_sac_ens_* entries at the end) is the same with n = 1 .. 10 critics:
+//   critic fwd   grid (row tiles, n), the twin kernel's body;  critic bwd: the chain over critics 0 .. n - 1, then the n (layers) Linears in
+//                grouped weight-gradient launches of PH_MAXLIN each
+//   td target    the actor once, then only the target critics that `subset` names, in list order; a bad index: NaN rows, nothing read at it
+//   losses       SB3's sum over n critics with weights and td_abs; the actor loss against min_c or mean_c; n = 2 has the twin kernels' bits
 #include <math.h>
 #include <string.h>
 
@@ -44,6 +50,23 @@ struct SacArgs {
     long total;
 };
 
+// The critic ensemble's arguments ("SAC critic ensemble"): SacArgs with n critics in tables of M3L_SAC_MAX_CRITICS.  The tile functions below are
+// templates over the two structs and read the same members of either; the twin kernels keep SacArgs, so their arguments do not grow.
+struct SacEnsArgs {
+    int B, F, A, ld;
+    int K0, Kp;
+    int n;                                   // critics, 1 .. M3L_SAC_MAX_CRITICS
+    PhMlp pi;                                // the actor, read by the TD target only (no workspace there: the offsets stay 0)
+    const float *mu_W, *mu_b, *s_W, *s_b;
+    long u_off, s_off;
+    PhMlp qf[M3L_SAC_MAX_CRITICS];
+    const float* q_W[M3L_SAC_MAX_CRITICS];
+    const float* q_b[M3L_SAC_MAX_CRITICS];
+    long xa_off, dq_off;                     // the input [B, Kp]; d q [n, B]
+    long total;
+};
+static_assert(sizeof(SacEnsArgs) <= 4096, "the ensemble's arguments travel by value: the kernel-argument segment holds 4 KB");
+
 // 1 - tanh(u)^2 without the cancellation: 4 e / (1 + e)^2 with e = exp(-2 |u|)
 __device__ __forceinline__ float sac_one_minus_tanh2(float u) {
     const float e = expf(-2.f * fabsf(u)), d = 1.f + e;
@@ -52,7 +75,8 @@ __device__ __forceinline__ float sac_one_minus_tanh2(float u) {
 
 // The actor on the rows row0 .. row0 + 15: leaves actions in hmu [16, PH_HLD] (columns < A), the rows' log-probabilities in lp_sh [16], and in
 // global memory whatever pointer is given (rows < B only).  noise null: the deterministic action tanh(mu).  Ends with a barrier.
-__device__ void sac_actor_tile(const SacArgs& p, const float* __restrict__ x, const float* __restrict__ noise, int row0, float* bufa, float* bufb, float* hmu,
+template <class P>
+__device__ void sac_actor_tile(const P& p, const float* __restrict__ x, const float* __restrict__ noise, int row0, float* bufa, float* bufb, float* hmu,
                                float* hs, float* lp_sh, float* __restrict__ ws, float* __restrict__ actions_out, float* __restrict__ logp_out) {
     const int tid = threadIdx.x, B = p.B, A = p.A;
     float* cur = bufa;
@@ -92,7 +116,8 @@ __device__ void sac_actor_tile(const SacArgs& p, const float* __restrict__ x, co
 }
 
 // the critics' input tile [x | a | zeros up to Kp] for the rows row0 .. row0 + 15 (zero past B); a: row m of the tile at asrc + m * lda
-__device__ void sac_build_xa(const SacArgs& p, const float* __restrict__ x, const float* asrc, int lda, int row0, float* buf) {
+template <class P>
+__device__ void sac_build_xa(const P& p, const float* __restrict__ x, const float* asrc, int lda, int row0, float* buf) {
     ph_load_x(x, p.F, row0, p.B, buf, p.ld);
     const int extra = p.Kp - p.F;
     for (int e = threadIdx.x; e < PH_TM * extra; e += 256) {
@@ -102,7 +127,8 @@ __device__ void sac_build_xa(const SacArgs& p, const float* __restrict__ x, cons
 }
 
 // Critic c on the input tile in bufa (which it overwrites): q of the 16 rows into column 0 of head [16, PH_HLD].  Ends with a barrier.
-__device__ void sac_critic_tile(const SacArgs& p, int c, int row0, float* bufa, float* bufb, float* head, float* __restrict__ ws) {
+template <class P>
+__device__ void sac_critic_tile(const P& p, int c, int row0, float* bufa, float* bufb, float* head, float* __restrict__ ws) {
     float* cur = bufa;
     float* nxt = bufb;
     const int K = ph_fwd_walk<PH_ACT_RELU, true>(p.qf[c], p.K0, cur, nxt, p.ld, ws, row0, p.B);
@@ -169,11 +195,10 @@ __global__ __launch_bounds__(256) void sac_actor_bwd_kernel(SacArgs p, const flo
     ph_bwd_layer<PH_ACT_NONE>(cur, p.ld, valid, W, N, p.F, nullptr, nullptr, 0, dx, false, row0, B);
 }
 
-// grid (row tiles, 2 critics).  q [2, B]
-__global__ __launch_bounds__(256) void sac_critic_fwd_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ actions, float* __restrict__ ws,
-                                                             float* __restrict__ q) {
-    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
-    __shared__ __attribute__((aligned(16))) float head[PH_TM * PH_HLD];
+// critic blockIdx.y on row tile blockIdx.x: the body of both critic forward kernels.  q [critics, B]
+template <class P>
+__device__ __forceinline__ void sac_critic_fwd_body(const P& p, const float* __restrict__ x, const float* __restrict__ actions, float* __restrict__ ws,
+                                                    float* __restrict__ q, float* sac_lds, float* head) {
     float* bufa = sac_lds;
     float* bufb = sac_lds + PH_TM * p.ld;
     const int c = blockIdx.y, row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B;
@@ -191,6 +216,14 @@ __global__ __launch_bounds__(256) void sac_critic_fwd_kernel(SacArgs p, const fl
     if (tid < PH_TM && row0 + tid < B) q[(long)c * B + row0 + tid] = head[tid * PH_HLD];
 }
 
+// grid (row tiles, 2 critics).  q [2, B]
+__global__ __launch_bounds__(256) void sac_critic_fwd_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ actions, float* __restrict__ ws,
+                                                             float* __restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float head[PH_TM * PH_HLD];
+    sac_critic_fwd_body(p, x, actions, ws, q, sac_lds, head);
+}
+
 // grid (row tiles).  dq [2, B] or null (= zero); dactions [B, A] or null (not wanted)
 __global__ __launch_bounds__(256) void sac_critic_bwd_kernel(SacArgs p, const float* __restrict__ dq, float* __restrict__ ws, float* __restrict__ dactions) {
     extern __shared__ __attribute__((aligned(16))) float sac_lds[];
@@ -205,6 +238,33 @@ __global__ __launch_bounds__(256) void sac_critic_bwd_kernel(SacArgs p, const fl
         ph_bwd_walk<PH_ACT_RELU>(p.qf[c], p.qf[c].n - 1, cur, nxt, p.ld, valid, W, N, ws, row0, B);
         // the action columns of the first weight; critic 1 adds to what critic 0 wrote, lane for lane
         if (dactions != nullptr) ph_bwd_edge(cur, p.ld, valid, W, N, p.K0, p.F, p.A, dactions, c == 1, row0, B);
+        __syncthreads();
+    }
+}
+
+// grid (row tiles, n critics).  q [n, B]
+__global__ __launch_bounds__(256) void sac_ens_critic_fwd_kernel(SacEnsArgs p, const float* __restrict__ x, const float* __restrict__ actions,
+                                                                 float* __restrict__ ws, float* __restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float head[PH_TM * PH_HLD];
+    sac_critic_fwd_body(p, x, actions, ws, q, sac_lds, head);
+}
+
+// grid (row tiles).  dq [n, B] or null (= zero); dactions [B, A] or null (not wanted).  sac_critic_bwd_kernel's chain over n critics
+__global__ __launch_bounds__(256) void sac_ens_critic_bwd_kernel(SacEnsArgs p, const float* __restrict__ dq, float* __restrict__ ws,
+                                                                 float* __restrict__ dactions) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    const int row0 = blockIdx.x * PH_TM, B = p.B;
+    for (int c = 0; c < p.n; ++c) {
+        float* cur = sac_lds;
+        float* nxt = sac_lds + PH_TM * p.ld;
+        ph_col0_tile(dq ? dq + (long)c * B : nullptr, ws + p.dq_off + (long)c * B, cur, p.ld, row0, B);      // d q of this critic
+        __syncthreads();
+        const float* W = p.q_W[c];
+        int N = 1, valid = 8;
+        ph_bwd_walk<PH_ACT_RELU>(p.qf[c], p.qf[c].n - 1, cur, nxt, p.ld, valid, W, N, ws, row0, B);
+        // the action columns of the first weight; a critic after the first adds to what the earlier ones wrote, lane for lane
+        if (dactions != nullptr) ph_bwd_edge(cur, p.ld, valid, W, N, p.K0, p.F, p.A, dactions, c > 0, row0, B);
         __syncthreads();
     }
 }
@@ -320,6 +380,113 @@ __global__ __launch_bounds__(256) void sac_ent_coef_loss_kernel(const float* __r
 __global__ __launch_bounds__(256) void sac_scale_kernel(const float* __restrict__ dloss, const float* __restrict__ coef, int n, float* __restrict__ out) {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r < n) out[r] = dloss[0] * coef[r];
+}
+
+// grid (row tiles).  The critic pointers of p are the target critics'.  subset [n_subset] names the critics whose minimum is taken, in list
+// order (NULL: 0 .. n_subset - 1); only they are evaluated.  An entry outside [0, n) makes every row NaN, and no table is read at it: the whole
+// grid sees the same list, so every workgroup leaves before its first barrier.  discounts as in sac_td_target_kernel.
+__global__ __launch_bounds__(256) void sac_ens_td_target_kernel(SacEnsArgs p, const float* __restrict__ x, const float* __restrict__ noise,
+                                                                const float* __restrict__ rewards, const float* __restrict__ dones,
+                                                                const float* __restrict__ discounts, float gamma, float ent_coef,
+                                                                const float* __restrict__ log_ent_coef, const int* __restrict__ subset, int n_subset,
+                                                                float* __restrict__ target_q) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD], hs[PH_TM * PH_HLD];
+    __shared__ float lp_sh[PH_TM], q_sh[M3L_SAC_MAX_CRITICS][PH_TM];
+    float* bufa = sac_lds;
+    float* bufb = sac_lds + PH_TM * p.ld;
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B;
+    bool bad = false;
+    if (subset != nullptr)
+        for (int j = 0; j < n_subset; ++j) bad = bad || subset[j] < 0 || subset[j] >= p.n;
+    if (bad) {
+        if (tid < PH_TM && row0 + tid < B) target_q[row0 + tid] = __builtin_nanf("");
+        return;
+    }
+    sac_actor_tile(p, x, noise, row0, bufa, bufb, hmu, hs, lp_sh, nullptr, nullptr, nullptr);
+    for (int j = 0; j < n_subset; ++j) {
+        const int c = subset ? subset[j] : j;
+        sac_build_xa(p, x, hmu, PH_HLD, row0, bufa);
+        __syncthreads();
+        sac_critic_tile(p, c, row0, bufa, bufb, hs, nullptr);
+        if (tid < PH_TM) q_sh[j][tid] = hs[tid * PH_HLD];
+        __syncthreads();
+    }
+    if (tid < PH_TM && row0 + tid < B) {
+        const int row = row0 + tid;
+        const float ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
+        float m = q_sh[0][tid];
+        for (int j = 1; j < n_subset; ++j) m = fminf(m, q_sh[j][tid]);
+        const float nq = m - ent * lp_sh[tid];
+        const float g = discounts ? discounts[row] : gamma;
+        target_q[row] = rewards[row] + (1.f - dones[row]) * g * nq;
+    }
+}
+
+// The ensemble's loss kernels spell their roundings out (fmaf, __fmul_rn, __fadd_rn), in the forms that the compiler gives the two-critic kernels
+// above, so that n = 2 has their bits whatever a later compiler contracts.
+
+// one workgroup.  loss = 0.5 sum_c mean_r w[r] (q[c, r] - t[r])^2;  coef [n, B] = w[r] d / B;  td_abs [B] (or null) = (sum_c |d_c|) (1 / n).
+// w null: 1.  Per critic the rows add up as in sac_critic_loss_w_kernel; the n means then add up from the last critic to the first, each fused
+// onto the sum behind it: fma(s_0, 1/B, fma(s_1, 1/B, ... s_{n-1} / B)), which at n = 2 is what sac_critic_loss_kernel computes.
+__global__ __launch_bounds__(256) void sac_ens_critic_loss_kernel(const float* __restrict__ q, const float* __restrict__ t, const float* __restrict__ w, int n,
+                                                                  int B, float* __restrict__ loss, float* __restrict__ coef, float* __restrict__ td_abs) {
+    __shared__ float red[4];
+    const float invB = 1.f / (float)B, invn = 1.f / (float)n;
+    float s[M3L_SAC_MAX_CRITICS];
+#pragma unroll
+    for (int c = 0; c < M3L_SAC_MAX_CRITICS; ++c) s[c] = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) {
+        const float tr = t[r], wr = w ? w[r] : 1.f;
+        float ab = 0.f;
+#pragma unroll
+        for (int c = 0; c < M3L_SAC_MAX_CRITICS; ++c) {
+            if (c >= n) break;
+            const float d = __fsub_rn(q[(long)c * B + r], tr), wd = __fmul_rn(d, wr);
+            s[c] = fmaf(d, wd, s[c]);
+            coef[(long)c * B + r] = __fmul_rn(invB, wd);
+            ab = c == 0 ? fabsf(d) : __fadd_rn(ab, fabsf(d));
+        }
+        if (td_abs) td_abs[r] = __fmul_rn(invn, ab);
+    }
+    float tot = 0.f;
+#pragma unroll
+    for (int c = M3L_SAC_MAX_CRITICS - 1; c >= 0; --c) {
+        if (c >= n) continue;                 // uniform: every thread takes the same critics through the block sums
+        const float sc = ph_block_sum(s[c], red);
+        tot = c == n - 1 ? __fmul_rn(invB, sc) : fmaf(invB, sc, tot);
+    }
+    if (threadIdx.x == 0) loss[0] = __fmul_rn(0.5f, tot);
+}
+
+// one workgroup.  reduce 0: loss = mean_r (ent logp[r] - min_c q[c, r]), the lowest index among equal minima takes the row's gradient -1 / B;
+// reduce 1: loss = mean_r (ent logp[r] - (sum_c q[c, r]) (1 / n)), every critic takes -1 / (n B).  coef [1 + n, B]: dloss / dlogp, then dloss / dq.
+__global__ __launch_bounds__(256) void sac_ens_actor_loss_kernel(const float* __restrict__ logp, const float* __restrict__ q, int n, int B, int reduce,
+                                                                 float ent_coef, const float* __restrict__ log_ent_coef, float* __restrict__ loss,
+                                                                 float* __restrict__ coef) {
+    __shared__ float red[4];
+    const float invB = 1.f / (float)B, invn = 1.f / (float)n, ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
+    const float each = -1.f / ((float)n * (float)B);
+    float s = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) {
+        float v = q[r];
+        int at = 0;
+        for (int c = 1; c < n; ++c) {
+            const float qc = q[(long)c * B + r];
+            if (reduce) {
+                v = __fadd_rn(v, qc);
+            } else if (qc < v) {
+                v = qc;
+                at = c;
+            }
+        }
+        if (reduce) v = __fmul_rn(v, invn);
+        s = __fadd_rn(s, fmaf(ent, logp[r], -v));
+        coef[r] = __fmul_rn(invB, ent);
+        for (int c = 0; c < n; ++c) coef[(long)(1 + c) * B + r] = reduce ? each : (c == at ? -invB : 0.f);
+    }
+    s = ph_block_sum(s, red);
+    if (threadIdx.x == 0) loss[0] = __fmul_rn(invB, s);
 }
 
 enum { SAC_ACTOR = 1, SAC_CRITIC = 2 };
@@ -585,6 +752,198 @@ int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float ta
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("sac_ent_coef_loss", B, 0, 0, 2.0 * B, st, 4.0 * B);
     sac_ent_coef_loss_kernel<<<1, 256, 0, st>>>(log_ent_coef, logp, target_entropy, B, dloss, loss, ent_coef, dlog_ent_coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- SAC critic ensemble (include/m3l_amd.h "SAC critic ensemble"): n critics where the entries above have two
+namespace {
+
+int sac_ens_shape_ok(const m3l_sac_ens_desc* d, int B, char* why, size_t n) {
+    if (d == nullptr) { snprintf(why, n, "null descriptor"); return 0; }
+    if (d->n_critics < 1 || d->n_critics > M3L_SAC_MAX_CRITICS) {
+        snprintf(why, n, "n_critics=%d (1 to %d)", d->n_critics, M3L_SAC_MAX_CRITICS);
+        return 0;
+    }
+    return ph_dims_ok(B, d->features, d->actions, d->n_pi, d->pi_width, d->n_qf, d->qf_width, "net", PH_MAXW + PH_MAXA, why, n);
+}
+
+// kernel arguments and the critics' workspace layout (the actor's nodes keep m3l_sac_ws_bytes); parts as in sac_args
+SacEnsArgs sac_ens_args(const m3l_sac_ens_desc* d, int B, int parts) {
+    SacEnsArgs p;
+    memset(&p, 0, sizeof(p));
+    p.B = B;
+    p.F = d->features;
+    p.A = d->actions;
+    p.n = d->n_critics;
+    p.K0 = p.F + p.A;
+    p.Kp = (p.K0 + 15) & ~15;
+    int widest = p.Kp > PH_MAXA ? p.Kp : PH_MAXA;
+    long off = 0;
+    ph_layout(p.pi, d->n_pi, d->pi_width, 0, 0, widest);      // widths only: no actor activations are stored here
+    for (int c = 0; c < p.n; ++c) off = ph_layout(p.qf[c], d->n_qf, d->qf_width, B, off, widest);
+    p.xa_off = off;
+    off += (long)B * p.Kp;
+    p.dq_off = off;
+    off = ph_round4(off + (long)p.n * B);
+    p.total = off;
+    p.ld = widest + 4;
+    if (parts & SAC_ACTOR) {
+        ph_bind(p.pi, d->pi_weight, d->pi_bias);
+        p.mu_W = d->mu_weight; p.mu_b = d->mu_bias; p.s_W = d->log_std_weight; p.s_b = d->log_std_bias;
+    }
+    if (parts & SAC_CRITIC)
+        for (int c = 0; c < p.n; ++c) {
+            ph_bind(p.qf[c], d->qf_weight[c], d->qf_bias[c]);
+            p.q_W[c] = d->q_weight[c]; p.q_b[c] = d->q_bias[c];
+        }
+    return p;
+}
+
+int sac_ens_params_ok(const m3l_sac_ens_desc* d, int parts, const char* who) {
+    int ok = 1;
+    if (parts & SAC_ACTOR)
+        ok = ok && d->mu_weight && d->mu_bias && d->log_std_weight && d->log_std_bias && ph_aligned(d->mu_weight) && ph_aligned(d->log_std_weight) &&
+             ph_ptrs_ok(d->n_pi, d->pi_weight, d->pi_bias);
+    if (parts & SAC_CRITIC)
+        for (int c = 0; c < d->n_critics; ++c)
+            ok = ok && d->q_weight[c] && d->q_bias[c] && ph_aligned(d->q_weight[c]) && ph_ptrs_ok(d->n_qf, d->qf_weight[c], d->qf_bias[c]);
+    M3L_CHECK(ok, "%s: a parameter pointer of the descriptor is null or a weight is not 16-byte aligned", who);
+    return 0;
+}
+
+int g_sac_ens_inited = 0;
+int sac_ens_init() {
+    if (g_sac_ens_inited) return 0;
+    if (ph_allow_lds({(const void*)sac_ens_critic_fwd_kernel, (const void*)sac_ens_critic_bwd_kernel, (const void*)sac_ens_td_target_kernel}, SAC_LDS_MAX))
+        return 2;
+    g_sac_ens_inited = 1;
+    return 0;
+}
+
+size_t sac_ens_lds_bytes(const SacEnsArgs& p) { return (size_t)2 * PH_TM * p.ld * 4; }
+double sac_ens_critic_flops(const SacEnsArgs& p, int critics) { return (double)critics * ph_net_flops(p.qf[0], p.B, p.K0, 1); }
+
+}  // namespace
+
+extern "C" {
+
+size_t m3l_sac_ens_ws_bytes(const m3l_sac_ens_desc* d, int B) {
+    char why[160];
+    if (!sac_ens_shape_ok(d, B, why, sizeof(why))) return 256;
+    return (size_t)sac_ens_args(d, B, 0).total * sizeof(float);
+}
+
+int m3l_sac_ens_critic_fwd(const m3l_sac_ens_desc* d, int B, const float* x, const float* actions, void* ws, float* q, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "sac_ens_critic_fwd: unsupported shape: %s", why);
+    if (sac_ens_params_ok(d, SAC_CRITIC, "sac_ens_critic_fwd")) return 1;
+    M3L_CHECK(x && actions && q && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_ens_critic_fwd: null argument, or x / ws not 16-byte aligned");
+    if (sac_ens_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacEnsArgs p = sac_ens_args(d, B, SAC_CRITIC);
+    ProfScope prof("sac_ens_critic_fwd", B, p.F, p.n, sac_ens_critic_flops(p, p.n), st, 4.0 * B * p.K0);
+    sac_ens_critic_fwd_kernel<<<dim3(cdiv(B, PH_TM), p.n), 256, sac_ens_lds_bytes(p), st>>>(p, x, actions, (float*)ws, q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_ens_critic_bwd(const m3l_sac_ens_desc* d, int B, const float* dq, void* ws, float* dactions, const m3l_sac_ens_desc* grads, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "sac_ens_critic_bwd: unsupported shape: %s", why);
+    if (sac_ens_params_ok(d, SAC_CRITIC, "sac_ens_critic_bwd")) return 1;
+    M3L_CHECK(grads == nullptr || (grads->n_qf == d->n_qf && grads->n_critics == d->n_critics),
+              "sac_ens_critic_bwd: the gradient descriptor has another layer or critic count");
+    if (grads != nullptr && sac_ens_params_ok(grads, SAC_CRITIC, "sac_ens_critic_bwd (gradients)")) return 1;
+    M3L_CHECK(ws && ph_aligned(ws), "sac_ens_critic_bwd: ws is null or not 16-byte aligned");
+    if (sac_ens_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacEnsArgs p = sac_ens_args(d, B, SAC_CRITIC);
+    float* w = (float*)ws;
+    {
+        ProfScope prof("sac_ens_critic_bwd_chain", B, p.F, p.n, sac_ens_critic_flops(p, p.n), st, 0.0);
+        sac_ens_critic_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p), st>>>(p, dq, w, dactions);
+        M3L_LAUNCH_CHECK();
+    }
+    if (grads == nullptr) return 0;
+    // the n (n_qf + 1) Linears in critic order, PH_MAXLIN to a launch: a launch's items are numbered from 0 again
+    PhWgrad q;
+    memset(&q, 0, sizeof(q));
+    q.B = B;
+    auto flush = [&]() -> int {
+        ProfScope prof("sac_ens_critic_wgrad", B, q.items, p.n, 0.0, st, 0.0);
+        sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
+        M3L_LAUNCH_CHECK();
+        memset(&q, 0, sizeof(q));
+        q.B = B;
+        return 0;
+    };
+    for (int c = 0; c < p.n; ++c) {
+        PhWgrad one;
+        memset(&one, 0, sizeof(one));
+        ph_add_net(one, p.qf[c], w, w + p.xa_off, p.K0, p.Kp, grads->qf_weight[c], grads->qf_bias[c], 1,
+                   {{w + p.dq_off + (long)c * B, grads->q_weight[c], grads->q_bias[c]}});
+        for (int l = 0; l < one.count; ++l) {
+            const PhLin& L = one.lin[l];
+            ph_add_lin(q, L.dY, L.X, L.ldx, L.dW, L.db, L.N, L.K);
+            if (q.count == PH_MAXLIN)
+                if (const int rc = flush()) return rc;
+        }
+    }
+    return q.count > 0 ? flush() : 0;
+}
+
+int m3l_sac_ens_td_target(const m3l_sac_ens_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                          const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, const int* subset, int n_subset,
+                          float* target_q, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "sac_ens_td_target: unsupported shape: %s", why);
+    if (sac_ens_params_ok(d, SAC_ACTOR | SAC_CRITIC, "sac_ens_td_target")) return 1;
+    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "sac_ens_td_target: null argument, or x_next not 16-byte aligned");
+    M3L_CHECK(subset != nullptr ? (n_subset >= 1 && n_subset <= d->n_critics) : (n_subset == 0 || n_subset == d->n_critics),
+              "sac_ens_td_target: n_subset=%d (1 to n_critics=%d entries; with subset NULL, all of them)", n_subset, d->n_critics);
+    if (sac_ens_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacEnsArgs p = sac_ens_args(d, B, SAC_ACTOR | SAC_CRITIC);
+    const int m = subset ? n_subset : p.n;
+    ProfScope prof("sac_ens_td_target", B, p.F, m, ph_net_flops(p.pi, B, p.F, 2 * p.A) + sac_ens_critic_flops(p, m), st, 4.0 * B * p.F);
+    sac_ens_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p), st>>>(p, x_next, noise, rewards, dones, discounts, gamma, ent_coef,
+                                                                               log_ent_coef, subset, m, target_q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_ens_critic_loss_fwd(const float* q, const float* target_q, const float* weights, int N, int B, float* loss, float* coef, float* td_abs,
+                                void* stream) {
+    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "sac_ens_critic_loss_fwd: N=%d B=%d (1 <= N <= %d, B >= 1)", N, B, M3L_SAC_MAX_CRITICS);
+    M3L_CHECK(q && target_q && loss && coef, "sac_ens_critic_loss_fwd: null argument (weights and td_abs may be NULL)");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_ens_critic_loss_fwd", B, N, 0, 7.0 * N * B, st, (8.0 * N + 12.0) * B);
+    sac_ens_critic_loss_kernel<<<1, 256, 0, st>>>(q, target_q, weights, N, B, loss, coef, td_abs);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_ens_actor_loss_fwd(const float* logp, const float* q, int N, int B, int reduce, float ent_coef, const float* log_ent_coef, float* loss,
+                               float* coef, void* stream) {
+    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "sac_ens_actor_loss_fwd: N=%d B=%d (1 <= N <= %d, B >= 1)", N, B, M3L_SAC_MAX_CRITICS);
+    M3L_CHECK(reduce == 0 || reduce == 1, "sac_ens_actor_loss_fwd: reduce=%d (0 = min, 1 = mean)", reduce);
+    M3L_CHECK(logp && q && loss && coef, "sac_ens_actor_loss_fwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_ens_actor_loss_fwd", B, N, reduce, (2.0 * N + 4.0) * B, st, (8.0 * N + 8.0) * B);
+    sac_ens_actor_loss_kernel<<<1, 256, 0, st>>>(logp, q, N, B, reduce, ent_coef, log_ent_coef, loss, coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_ens_loss_bwd(const float* dloss, const float* coef, int n, float* out, void* stream) {
+    M3L_CHECK(n >= 1, "sac_ens_loss_bwd: n=%d (n >= 1)", n);
+    M3L_CHECK(dloss && coef && out, "sac_ens_loss_bwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_ens_loss_bwd", n, 0, 0, 1.0 * n, st, 8.0 * n);
+    sac_scale_kernel<<<cdiv(n, 256), 256, 0, st>>>(dloss, coef, n, out);
     M3L_LAUNCH_CHECK();
     return 0;
 }

@@ -29,6 +29,7 @@ from .dino import update_moving_average
 from .functional import _require_cuda, _stream, _ws
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
+MAX_CRITICS = L.SAC_MAX_CRITICS          # of a SACEnsembleHead (sac_ensemble.py); a SACHead has exactly 2
 WB = Tuple[torch.Tensor, torch.Tensor]
 
 
@@ -52,21 +53,28 @@ class SACHeadParams(NamedTuple):
         """From a module with SB3's attribute names (`actor.latent_pi / mu / log_std`, `critic.qf0 / qf1`, `critic_target.qf0 / qf1`): a `SACHead`,
         or an SB3 `SACPolicy`, whose configuration is checked against what the kernels compute."""
         _reject_sac_flags(policy)
-        actor, critic, target = policy.actor, policy.critic, policy.critic_target
-        if getattr(actor, "use_sde", False):
-            raise ValueError("use_sde=True (generalised state-dependent exploration) is not computed by the HIP SAC head")
-        if not isinstance(getattr(actor, "log_std", None), nn.Linear):
-            raise ValueError("actor.log_std is not an nn.Linear: the HIP SAC head computes a state-dependent log_std (use_sde=False) only")
-        for name, c in (("critic", critic), ("critic_target", target)):
+        for name, c in (("critic", policy.critic), ("critic_target", policy.critic_target)):
             n = getattr(c, "n_critics", 2)
             if n != 2 or hasattr(c, "qf2") or not hasattr(c, "qf1"):
                 raise ValueError(f"{name}: n_critics={n if n != 2 else 'other than 2'}: the HIP SAC head computes exactly 2 critics")
-            if not getattr(c, "share_features_extractor", True):
-                raise ValueError("share_features_extractor=False: the HIP SAC head takes one feature vector for the actor and the critics")
-        pi = H.linear_pairs(actor.latent_pi, "actor.latent_pi", nn.ReLU, "SAC")
-        qf = tuple(_q_net(getattr(critic, f"qf{i}"), f"critic.qf{i}") for i in range(2))
-        qt = tuple(_q_net(getattr(target, f"qf{i}"), f"critic_target.qf{i}") for i in range(2))
-        return SACHeadParams(pi, (actor.mu.weight, actor.mu.bias), (actor.log_std.weight, actor.log_std.bias), qf, qt)
+        return SACHeadParams(*_read_policy(policy, 2))
+
+
+def _read_policy(policy, n_critics):
+    """(pi, mu, log_std, qf, qf_target) of a module with SB3's attribute names and `n_critics` critics `qf0 ..`, its actor and extractor sharing
+    checked against what the kernels compute; the caller has checked the critic count."""
+    actor, critic, target = policy.actor, policy.critic, policy.critic_target
+    if getattr(actor, "use_sde", False):
+        raise ValueError("use_sde=True (generalised state-dependent exploration) is not computed by the HIP SAC head")
+    if not isinstance(getattr(actor, "log_std", None), nn.Linear):
+        raise ValueError("actor.log_std is not an nn.Linear: the HIP SAC head computes a state-dependent log_std (use_sde=False) only")
+    for c in (critic, target):
+        if not getattr(c, "share_features_extractor", True):
+            raise ValueError("share_features_extractor=False: the HIP SAC head takes one feature vector for the actor and the critics")
+    pi = H.linear_pairs(actor.latent_pi, "actor.latent_pi", nn.ReLU, "SAC")
+    qf = tuple(_q_net(getattr(critic, f"qf{i}"), f"critic.qf{i}") for i in range(n_critics))
+    qt = tuple(_q_net(getattr(target, f"qf{i}"), f"critic_target.qf{i}") for i in range(n_critics))
+    return pi, (actor.mu.weight, actor.mu.bias), (actor.log_std.weight, actor.log_std.bias), qf, qt
 
 
 def _q_net(seq, name):
@@ -76,35 +84,45 @@ def _q_net(seq, name):
     return H.linear_pairs(mods[:-1], name, nn.ReLU, "SAC") + ((mods[-1].weight, mods[-1].bias),)
 
 
-def _reject_sac_flags(policy):
+def _reject_flags(policy):
     if getattr(policy, "use_sde", False):
         raise ValueError("use_sde=True (generalised state-dependent exploration) is not computed by the HIP SAC head")
     if not getattr(policy, "share_features_extractor", True):
         raise ValueError("share_features_extractor=False: the HIP SAC head takes one feature vector for the actor and the critics")
+
+
+def _reject_sac_flags(policy):
+    _reject_flags(policy)
     n = getattr(policy, "n_critics", 2)
     if n != 2:
         raise ValueError(f"n_critics={n}: the HIP SAC head computes exactly 2 critics")
 
 
-def _arch(F, params: SACHeadParams):
-    """(F, A, pi widths, qf widths) with every shape checked; raises ValueError for a head outside the kernels' limits."""
+def _arch(F, params):
+    """(F, A, pi widths, qf widths) with every shape checked; raises ValueError for a head outside the kernels' limits.  params: SACHeadParams
+    (exactly 2 critics), or the SACEnsembleParams of sac_ensemble.py (1 to MAX_CRITICS, as many targets)."""
     F = int(F)
     A = int(params.mu[0].shape[0])
     H.check_float32(params.actor_flat() + params.critic_flat() + params.critic_flat(True), "SAC")
     k, pi = H.layer_widths(F, params.pi, "pi", "SAC", "net")
     H.check_head_linear("mu", params.mu, A, k)
     H.check_head_linear("log_std", params.log_std, A, k)
+    twin = isinstance(params, SACHeadParams)
     qf = None
-    for names, nets in ((("qf0", "qf1"), params.qf), (("qf_target0", "qf_target1"), params.qf_target)):
-        if len(nets) != 2:
-            raise ValueError(f"{names[0][:-1]}: {len(nets)} critics: the HIP SAC head computes exactly 2 critics")
-        for name, net in zip(names, nets):
+    for stem, nets in (("qf", params.qf), ("qf_target", params.qf_target)):
+        if twin and len(nets) != 2:
+            raise ValueError(f"{stem}: {len(nets)} critics: the HIP SAC head computes exactly 2 critics")
+        if not twin and (not 1 <= len(nets) <= MAX_CRITICS or len(nets) != len(params.qf)):
+            raise ValueError(f"{stem}: {len(nets)} critics: the HIP SAC critic ensemble computes 1 to {MAX_CRITICS} critics and as many targets")
+        for i, net in enumerate(nets):
+            name = f"{stem}{i}"
             k, ws = H.layer_widths(F + A, net[:-1], name, "SAC", "net")
             for w, b in net[-1:]:          # the Linear(., 1) on top
                 if tuple(w.shape) != (1, k) or tuple(b.shape) != (1,):
                     raise ValueError(f"{name} layer {len(net) - 1}: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not follow an input of width {k}")
             if qf is not None and ws != qf:
-                raise ValueError(f"{name}: hidden widths {ws}, the other critics have {qf}: the two critics and their targets must be alike")
+                raise ValueError(f"{name}: hidden widths {ws}, the other critics have {qf}: the {'two' if twin else len(params.qf)} critics and their "
+                                 "targets must be alike")
             qf = ws
     H.check_limits((F,) + pi + qf, A)
     return F, A, pi, qf
@@ -336,6 +354,19 @@ def q_values(params: SACHeadParams, features, actions, target=False, param_grads
     return SACCriticFn.apply(x, a, arch, store, want, *flat)
 
 
+def _gamma_of(gamma, B):
+    """(True, discounts (B,) on the device) for a tensor of one discount per row, (False, the number) otherwise."""
+    if isinstance(gamma, torch.Tensor):
+        _require_cuda(gamma, "gamma")
+        if gamma.dtype != torch.float32 or tuple(gamma.shape) not in ((B,), (B, 1)):
+            raise ValueError(f"gamma: a number, or a float32 tensor of shape ({B},) or ({B}, 1), one discount per row; got {tuple(gamma.shape)} "
+                             f"{gamma.dtype}")
+        return True, _vec(gamma, "gamma", B)
+    if not isinstance(gamma, numbers.Real):
+        raise ValueError(f"gamma: a number or a float32 CUDA tensor of {B} values expected, got {type(gamma).__name__}")
+    return False, float(gamma)
+
+
 @torch.no_grad()
 def td_target(params: SACHeadParams, next_features, rewards, dones, gamma, ent_coef=None, log_ent_coef=None, noise=None):
     """target_q (B,) = r + (1 - done) * gamma * (min_c q_target_c(x', a') - ent_coef * logp') with (a', logp') = actor(x') (`sac_mae.py:326-335`).
@@ -349,15 +380,7 @@ def td_target(params: SACHeadParams, next_features, rewards, dones, gamma, ent_c
     noise = H.noise_of(noise, B, arch[1], x.device)
     ent, log_ent = _ent_args(ent_coef, log_ent_coef)
     r, dn = _vec(rewards, "rewards", B), _vec(dones, "dones", B)
-    per_row = isinstance(gamma, torch.Tensor)
-    if per_row:
-        _require_cuda(gamma, "gamma")
-        if gamma.dtype != torch.float32 or tuple(gamma.shape) not in ((B,), (B, 1)):
-            raise ValueError(f"gamma: a number, or a float32 tensor of shape ({B},) or ({B}, 1), one discount per row; got {tuple(gamma.shape)} "
-                             f"{gamma.dtype}")
-        gamma = _vec(gamma, "gamma", B)
-    elif not isinstance(gamma, numbers.Real):
-        raise ValueError(f"gamma: a number or a float32 CUDA tensor of {B} values expected, got {type(gamma).__name__}")
+    per_row, gamma = _gamma_of(gamma, B)
     af, cf = [_dev(t) for t in af], [_dev(t) for t in cf]
     d = _desc(arch, actor=af, critic=cf)
     out = torch.empty(B, dtype=torch.float32, device=x.device)

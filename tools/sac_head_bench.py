@@ -16,7 +16,16 @@ and, for (a), with and without the reads of the logged values: the reference rea
 The figures per path are policy_head_bench.py's (call_us, host_us, entry_points, kernel_us / launches / copies).  Both paths' losses are printed,
 so that a wrong result cannot pass as a fast one.  Without a GPU the tool fails; it has no fallback.
 
-Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30]   (one JSON line on stdout)"""
+With --critics N the tool measures the critic ensemble instead (EXPERIMENTS.md "SAC critic ensemble"), at the same shapes: per call of
+`q_values` forward + backward, of `td_target` over a subset of M (--subset, default 2) and of a whole critic update (target, loss, backward,
+Polyak update), and of one actor update with --q-reduce, on
+  ens    m3l_amd.SACEnsembleHead with N critics
+  eager  the float32 torch restatement looping over the N critics (tests/sac_ens_cases.py)
+  twin   m3l_amd.SACHead on the same two critics, when N = 2 (the subset is then None: both)
+in alternating windows of one run.
+
+Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30] [--critics N [--subset M] [--q-reduce min|mean]]
+(one JSON line on stdout)"""
 import argparse
 import json
 import os
@@ -30,6 +39,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import sac_cases as SC  # noqa: E402
+import sac_ens_cases as EC  # noqa: E402
 import m3l_amd  # noqa: E402
 from m3l_amd import sac as SH  # noqa: E402
 from policy_head_bench import alternate, counted, entry_points  # noqa: E402
@@ -38,14 +48,119 @@ DEV = "cuda:0"
 ARCH = (256, (256, 256), (256, 256), 7)
 
 
+def ensemble(a):
+    """The --critics mode: see the module docstring."""
+    N, M = a.critics, None if a.critics == 2 else min(a.subset, a.critics)
+    c = EC.make_inputs(ARCH, N, 256, seed=9)
+    head = m3l_amd.SACEnsembleHead(ARCH[0], ARCH[3], net_arch=dict(pi=list(ARCH[1]), qf=list(ARCH[2])), n_critics=N)
+    head.load_state_dict({k: torch.from_numpy(v) for k, v in c["params"].items()})
+    head = head.to(DEV)
+    heads = {"ens": head}
+    if N == 2:
+        heads["twin"] = m3l_amd.SACHead(ARCH[0], ARCH[3], net_arch=dict(pi=list(ARCH[1]), qf=list(ARCH[2]))).to(DEV)
+        heads["twin"].load_state_dict(head.state_dict())
+    P = dict(head.named_parameters())
+    t = {k: torch.from_numpy(c[k]).to(DEV) for k in ("x", "x_next", "noise_pi", "noise_next", "a_replay", "rewards", "dones")}
+    log_ent = torch.tensor([c["log_ent_coef"]], dtype=torch.float32, device=DEV)
+    critic_params = [p for n, p in P.items() if n.startswith("critic.")]
+    target_params = [p for n, p in P.items() if n.startswith("critic_target.")]
+    gamma, tau = c["gamma"], c["tau"]
+    subset = None if M is None else torch.arange(M, dtype=torch.int32, device=DEV)
+    dq = torch.ones(N, 256, device=DEV)
+
+    def zero(h):
+        for p in h.parameters():
+            p.grad = None
+
+    def hip_target(h):
+        kw = {} if h is not head else dict(subset=head.sample_subset(M) if M else None)
+        return h.td_target(t["x_next"], t["rewards"], t["dones"], gamma, log_ent_coef=log_ent, noise=t["noise_next"], **kw)
+
+    def eager_target():
+        with torch.no_grad():
+            n = SC.actor_forward(P, t["x_next"], t["noise_next"])
+            idx = torch.randperm(N, device=DEV)[:M] if M else torch.arange(N, device=DEV)
+            qn, _ = EC.critic_forward(P, "critic_target", t["x_next"], n["actions"], N)      # SB3's critic evaluates all N; the subset picks rows
+            nq = qn[idx].min(dim=0)[0] - torch.exp(log_ent) * n["log_prob"]
+            return t["rewards"] + (1 - t["dones"]) * gamma * nq
+
+    def hip_q(h):
+        zero(h)
+        q = h.q_values(t["x"], t["a_replay"])
+        q.backward(dq)
+        return q
+
+    def eager_q():
+        zero(head)
+        q, _ = EC.critic_forward(P, "critic", t["x"], t["a_replay"], N)
+        q.backward(dq)
+        return q
+
+    def hip_update(h):
+        zero(h)
+        loss = h.critic_loss(t["x"], t["a_replay"], hip_target(h))
+        loss.backward()
+        h.polyak_update(tau)
+        return loss
+
+    def eager_update():
+        zero(head)
+        target_q = eager_target()
+        q, _ = EC.critic_forward(P, "critic", t["x"], t["a_replay"], N)
+        loss = 0.5 * sum(F.mse_loss(qc, target_q) for qc in q)
+        loss.backward()
+        with torch.no_grad():
+            for p, tp in zip(critic_params, target_params):
+                tp.mul_(1 - tau)
+                torch.add(tp, p, alpha=tau, out=tp)
+        return loss
+
+    def hip_actor(h):
+        zero(h)
+        kw = dict(q_reduce=a.q_reduce) if h is head else {}
+        loss, _ = h.actor_loss(t["x"], log_ent_coef=log_ent, noise=t["noise_pi"], **kw)
+        loss.backward()
+        return loss
+
+    def eager_actor():
+        zero(head)
+        o = SC.actor_forward(P, t["x"], t["noise_pi"])
+        q, _ = EC.critic_forward(P, "critic", t["x"], o["actions"], N)
+        red = q.min(dim=0)[0] if a.q_reduce == "min" else q.mean(dim=0)
+        loss = (torch.exp(log_ent) * o["log_prob"] - red).mean()
+        loss.backward()
+        return loss
+    out = {"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}, "critics": N, "subset": M,
+           "q_reduce": a.q_reduce, "B": 256}          # SACHead's actor loss is the min: compare N = 2 with --q-reduce min
+    for what, hip_fn, eager_fn in (("q_values_fwd_bwd", hip_q, eager_q), ("td_target", hip_target, eager_target), ("critic_update", hip_update, eager_update),
+                                   ("actor_update", hip_actor, eager_actor)):
+        fns = {name: (lambda h=h, f=hip_fn: f(h)) for name, h in heads.items()}
+        fns["eager"] = eager_fn
+        res, last = alternate(fns, a.iters, a.warmup, a.rounds)
+        for name, fn in fns.items():
+            res[name].update(counted(fn))
+            res[name]["result_sum"] = float(last[name].detach().float().sum())
+        res["ens"]["entry_points"] = entry_points(fns["ens"])
+        res["ens_over_eager_call"] = round(res["ens"]["call_us"] / res["eager"]["call_us"], 3)
+        if "twin" in res:
+            res["ens_over_twin_call"] = round(res["ens"]["call_us"] / res["twin"]["call_us"], 3)
+        out[what] = res
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=500, help="calls per timed window of (a); (b) takes ten times as many")
     ap.add_argument("--rounds", type=int, default=5, help="alternating windows per path")
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--critics", type=int, default=None, help="measure the critic ensemble with this many critics (1 to 10) instead of (a) and (b)")
+    ap.add_argument("--subset", type=int, default=2, help="with --critics: critics in the target's minimum (N = 2: both)")
+    ap.add_argument("--q-reduce", choices=("min", "mean"), default="mean", help="with --critics: the actor loss's reduction over the critics")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sac_head_bench: no GPU")
+    if a.critics is not None:
+        return ensemble(a)
     out = {"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}}
 
     # (a) one gradient step
