@@ -787,7 +787,7 @@ int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float ta
  * an ensemble of N critics, the target's minimum over a random subset of M of them, the actor trained against the ensemble's mean) and for
  * SB3's `n_critics` of any value (sac_mae_policy.py:62 passes it on).  Neither SB3 nor a REDQ implementation is part of the reference tree:
  * the rule is stated here and restated in float64 by tests/sac_ens_cases.py, parity unpinned.  The struct, the entry points and the results of
- * the section above do not change; DroQ (LayerNorm and dropout critics) and TQC are not computed.  float32 throughout.
+ * the section above do not change; DroQ (LayerNorm and dropout critics) is the section below; TQC is not computed.  float32 throughout.
  *   1. q_c = critic_c(cat([x, a])), c < N: the critic arithmetic of the section above, per critic.
  *   2. target_q = r + (1 - done) g (min over the subset's entries, in list order, by fminf, of q_target_c(x', a') - ent logp'),
  *      (a', logp') = actor(x'), g = gamma or discounts[row].  Only the listed critics are evaluated: the cost grows with M, not N.  Duplicates
@@ -844,6 +844,54 @@ int m3l_sac_ens_actor_loss_fwd(const float* logp, const float* q, int N, int B, 
                                float* coef, void* stream);
 /* the backward of both losses: out [n] = dloss[0] coef [n] (dloss: device scalar); n = N B for the critic loss, (1 + N) B for the actor loss */
 int m3l_sac_ens_loss_bwd(const float* dloss, const float* coef, int n, float* out, void* stream);
+
+/* ---- SAC DroQ critics (ABI 420): the ensemble above with LayerNorm and dropout in the critics (DroQ, Hiraoka et al., ICLR 2022: two such
+ * critics reach the update-to-data ratio that REDQ buys with ten; p = 0 is the plain LayerNorm critic of pixel SAC).  Every critic and every
+ * target critic is [Linear(w_in, w), Dropout(p), LayerNorm(w), ReLU] x n_qf + Linear(w_last, 1).  Neither SB3 nor a DroQ implementation is
+ * part of the reference tree: the rule is stated here and restated in float64 by tests/droq_cases.py, parity unpinned.  The sections above
+ * and their results do not change; TQC is not computed.  float32 throughout.
+ * Per hidden layer l of critic c, on row r, with w the layer's width, gamma / beta the LayerNorm's weight / bias:
+ *   z = W h_in + b
+ *   d = z keep scale                                   (p = 0: d = z)
+ *   mean = sum d / w;  var = sum (d - mean)^2 / w      (two passes, biased, a fixed order over the columns)
+ *   rstd = 1 / sqrt(var + 1e-5);  xh = (d - mean) rstd
+ *   y = xh gamma + beta;  h = max(y, 0)
+ * keep and scale are those of "Dropout" above: Philox key = (seed low, seed high); element (r, col) uses word col % 4 of block
+ * q = r ceil(w / 4) + col / 4; kept iff word >= T = floor(p 2^32); scale = (float)(1 / (1 - p)) computed in double; the third counter word is
+ * 4 c + l, c the critic's OWN index (also when td_target evaluates a subset) and l < 3 the hidden layer: the mask of a site is
+ * m3l_op_dropout_mask(p, seed, layer = c, site = l, rows = B, N = w).  A row's mask depends on its global row index only, never on the tile;
+ * masks are never stored, the backward regenerates them from the seed.  dropout_p == 0 runs kernels without any Philox code.
+ * Backward, with g = dL / dh:
+ *   dy = g [h > 0];  d gamma = sum_r dy xh;  d beta = sum_r dy
+ *   dxh = dy gamma;  dd = rstd (dxh - mean_col(dxh) - xh mean_col(dxh xh));  dz = dd keep scale
+ * dz is the dY of the layer's weight gradient (dW and db as in the ensemble) and what goes on down the chain.
+ * Launches: critic_fwd 1 (grid: row tiles x N; the LayerNorm is a pass over the 16-row tile in LDS between two layers); critic_bwd 1 chain +
+ * ceil(N (n_qf + 1) / 8) grouped weight-gradient launches + 1 launch for d gamma / d beta of all critics and layers, the last two kinds only
+ * when `grads` is not NULL (d gamma / d beta: per column four partial sums over the rows r = 0, 1, 2, 3 mod 4, each in ascending order, added
+ * as (0 + 1) + (2 + 3)); td_target 1.  The losses are m3l_sac_ens_critic_loss_fwd / _actor_loss_fwd / _loss_bwd.  No float atomics, every sum in
+ * a fixed order: two runs with one seed give the same bits.
+ * Limits: the ensemble's, and 0 <= dropout_p < 1; the LayerNorm tensors 16-byte aligned.  A critic without a hidden layer (n_qf = 0) has no
+ * LayerNorm site: the entries then compute the ensemble's bits.  Anything else is an error and nothing is written.
+ * The gradient descriptor of critic_bwd names the gradient buffers, d gamma in ln_weight and d beta in ln_bias; its dropout_p and seed are
+ * not read.  ws: m3l_sac_droq_ws_bytes bytes, one per forward that a backward follows. */
+typedef struct m3l_sac_droq_desc {
+    m3l_sac_ens_desc ens;                                        /* the ensemble's fields, in its layout */
+    float* ln_weight[M3L_SAC_MAX_CRITICS][M3L_SAC_MAX_HIDDEN];   /* gamma [qf_width[l]] */
+    float* ln_bias[M3L_SAC_MAX_CRITICS][M3L_SAC_MAX_HIDDEN];     /* beta [qf_width[l]] */
+    float dropout_p;                                             /* 0 <= p < 1; 0: no dropout */
+    uint64_t seed;                                               /* of this call's masks; not read when dropout_p == 0 */
+} m3l_sac_droq_desc;
+size_t m3l_sac_droq_ws_bytes(const m3l_sac_droq_desc* head, int B);
+/* q [N, B] is written; ws NULL when no backward follows */
+int m3l_sac_droq_critic_fwd(const m3l_sac_droq_desc* head, int B, const float* x, const float* actions, void* ws, float* q, void* stream);
+/* head: the descriptor of the forward (the same dropout_p and seed); dq [N, B]: NULL = zero; dactions [B, A] or NULL (not wanted); grads NULL:
+ * no parameter gradient, only the chain runs */
+int m3l_sac_droq_critic_bwd(const m3l_sac_droq_desc* head, int B, const float* dq, void* ws, float* dactions, const m3l_sac_droq_desc* grads,
+                            void* stream);
+/* the arguments of m3l_sac_ens_td_target; the descriptor's critics and LayerNorm tensors are the target critics' */
+int m3l_sac_droq_td_target(const m3l_sac_droq_desc* head, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                           const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, const int* subset, int n_subset,
+                           float* target_q, void* stream);
 
 /* ---- device-resident rollout (ABI 411): what PPO_MAE.train does between `rollout_buffer` and `self.mae(x)` for every minibatch, with the rollout
  * kept in device memory in the layout the vec-env fills it in, (T, n_envs, ...).  Nothing is swapped or flattened: idx [B] (int64) holds flat

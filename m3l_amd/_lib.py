@@ -78,6 +78,13 @@ class SacEnsDesc(C.Structure):
                 ("q_weight", c_p * SAC_MAX_CRITICS), ("q_bias", c_p * SAC_MAX_CRITICS)]
 
 
+class SacDroqDesc(C.Structure):
+    """m3l_sac_droq_desc: the ensemble's descriptor, then the LayerNorm tables, the dropout rate and the call's seed (include/m3l_amd.h "SAC DroQ
+    critics")."""
+    _fields_ = [("ens", SacEnsDesc), ("ln_weight", (c_p * 3) * SAC_MAX_CRITICS), ("ln_bias", (c_p * 3) * SAC_MAX_CRITICS),
+                ("dropout_p", C.c_float), ("seed", C.c_uint64)]
+
+
 _SIGS = {
     "m3l_version": (c_i, []),
     "m3l_last_error": (c_i, [C.c_char_p, c_sz]),
@@ -283,6 +290,11 @@ _SIGS = {
     "m3l_sac_ens_critic_loss_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
     "m3l_sac_ens_actor_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p]),
     "m3l_sac_ens_loss_bwd": (c_i, [c_p, c_p, c_i, c_p, c_p]),
+    # SAC DroQ critics (ABI 420): the ensemble's critic entries on a descriptor that also carries the LayerNorm tensors, p and the seed
+    "m3l_sac_droq_ws_bytes": (c_sz, [C.POINTER(SacDroqDesc), c_i]),
+    "m3l_sac_droq_critic_fwd": (c_i, [C.POINTER(SacDroqDesc), c_i, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_sac_droq_critic_bwd": (c_i, [C.POINTER(SacDroqDesc), c_i, c_p, c_p, c_p, C.POINTER(SacDroqDesc), c_p]),
+    "m3l_sac_droq_td_target": (c_i, [C.POINTER(SacDroqDesc), c_i, c_p, c_p, c_p, c_p, c_p, C.c_float, C.c_float, c_p, c_p, c_i, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

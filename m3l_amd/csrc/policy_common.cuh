@@ -5,7 +5,8 @@
 // only 4-byte aligned and whose width is no multiple of 16 (the critics' first layer, K = F + A).
 // A net (the PPO policy and value branches, the SAC actor, each SAC critic) is a PhMlp, a run of Linear + activation layers as data: ph_fwd_walk
 // and ph_bwd_walk run it on the device, ph_layout / ph_bind / ph_add_net / ph_net_flops on the host.  The head Linears on top of a net and
-// their epilogues belong to the head's own file.
+// their epilogues belong to the head's own file.  ph_ln_fwd_tile / ph_ln_bwd_tile are the dropout + LayerNorm + ReLU pass over a finished tile
+// that the SAC DroQ critics put between two ACT_NONE layers; PhMlp does not know about it.
 #pragma once
 #include <stdio.h>
 
@@ -246,6 +247,122 @@ __device__ void ph_bwd_edge(const float* din, int ldi, int valid, const float* _
                 *p = add ? *p + acc[u][r] : acc[u][r];
             }
         }
+}
+
+// Dropout in front of a LayerNorm site (include/m3l_amd.h "SAC DroQ critics", generator contract under "Dropout"): the key, the threshold
+// and the scale of a call; the third counter word (4 critic + layer) comes with each site.
+struct PhDrop {
+    uint32_t thr, k0, k1;
+    float scale;
+};
+// keep * scale of the columns 4 cg .. 4 cg + 3 of global row `row` of a site that is nq blocks of four wide: one Philox block
+__device__ __forceinline__ f32x4 ph_drop4(const PhDrop& d, uint32_t ctr2, int row, int nq, int cg) {
+    const uint4 wd = drop_words(d.k0, d.k1, ctr2, (uint64_t)row * (uint64_t)nq + (uint64_t)cg);
+    return f32x4{wd.x >= d.thr ? d.scale : 0.f, wd.y >= d.thr ? d.scale : 0.f, wd.z >= d.thr ? d.scale : 0.f, wd.w >= d.thr ? d.scale : 0.f};
+}
+
+// The LayerNorm passes over a tile own it as 16 lanes per row (one DPP row: row m = tid >> 4), lane j the column blocks j, j + 16, ... of
+// four: a lane adds its columns in ascending order, the 16 lanes meet in row16_sum, so every sum has one fixed order.  w is a multiple of 16.
+//
+// t [16, ld] holds z = W h_in + b of a hidden layer, w columns; in place it becomes h = relu(LN(dropout(z)) gamma + beta):
+//   d = z keep scale (DROP only);  mean = sum d / w;  var = sum (d - mean)^2 / w (two passes);  rstd = 1 / sqrt(var + 1e-5)
+//   xh = (d - mean) rstd;  h = max(xh gamma + beta, 0)
+// gh, gxh [B, w] and grs [B] (all three or none): h, xh and rstd of the rows below B for the backward.  The caller puts a barrier on either side.
+template <bool DROP>
+__device__ void ph_ln_fwd_tile(float* t, int ld, int w, const float* __restrict__ gamma, const float* __restrict__ beta, const PhDrop& drop, uint32_t ctr2,
+                               int row0, int B, float* __restrict__ gh, float* __restrict__ gxh, float* __restrict__ grs) {
+    const int m = threadIdx.x >> 4, j = threadIdx.x & 15, row = row0 + m, nq = w >> 2;
+    float* tr = t + m * ld;
+    const float invw = 1.f / (float)w;
+    float s = 0.f;
+    for (int cg = j; cg < nq; cg += 16) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(tr + 4 * cg);
+        if (DROP) {
+            const f32x4 k = ph_drop4(drop, ctr2, row, nq, cg);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] *= k[e];
+            *reinterpret_cast<f32x4*>(tr + 4 * cg) = v;
+        }
+        s += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    const float mean = row16_sum(s) * invw;
+    float ss = 0.f;
+    for (int cg = j; cg < nq; cg += 16) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(tr + 4 * cg);
+        const float a = v[0] - mean, b = v[1] - mean, c = v[2] - mean, d = v[3] - mean;
+        ss += (a * a + b * b) + (c * c + d * d);
+    }
+    const float rstd = 1.f / sqrtf(row16_sum(ss) * invw + 1e-5f);
+    const bool store = gh != nullptr && row < B;
+    for (int cg = j; cg < nq; cg += 16) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(tr + 4 * cg);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 4 * cg), be = *reinterpret_cast<const f32x4*>(beta + 4 * cg);
+        f32x4 xh, h;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            xh[e] = (v[e] - mean) * rstd;
+            h[e] = fmaxf(xh[e] * g[e] + be[e], 0.f);
+        }
+        *reinterpret_cast<f32x4*>(tr + 4 * cg) = h;
+        if (store) {
+            *reinterpret_cast<f32x4*>(gh + (long)row * w + 4 * cg) = h;
+            *reinterpret_cast<f32x4*>(gxh + (long)row * w + 4 * cg) = xh;
+        }
+    }
+    if (store && j == 0) grs[row] = rstd;
+}
+
+// The way back.  t [16, ld] holds g = dL / dh of the same layer, w columns (rows past B zero); in place it becomes dz:
+//   dy = g [h > 0];  dxh = dy gamma;  dd = rstd (dxh - mean_col(dxh) - xh mean_col(dxh xh));  dz = dd keep scale (DROP only)
+// gh, gxh, grs: what the forward left.  gdy [B, w] takes dy (the d gamma / d beta launch reads it with xh), gdz [B, w] takes dz (the dY of
+// the layer's weight gradient).  Rows past B read nothing and leave zeros.  The caller puts a barrier on either side.
+template <bool DROP>
+__device__ void ph_ln_bwd_tile(float* t, int ld, int w, const float* __restrict__ gamma, const PhDrop& drop, uint32_t ctr2, int row0, int B,
+                               const float* __restrict__ gh, const float* __restrict__ gxh, const float* __restrict__ grs, float* __restrict__ gdy,
+                               float* __restrict__ gdz) {
+    const int m = threadIdx.x >> 4, j = threadIdx.x & 15, row = row0 + m, nq = w >> 2;
+    const bool live = row < B;
+    float* tr = t + m * ld;
+    const float invw = 1.f / (float)w;
+    float s1 = 0.f, s2 = 0.f;
+    for (int cg = j; cg < nq; cg += 16) {
+        f32x4 dxh = {0.f, 0.f, 0.f, 0.f};
+        if (live) {
+            const long at = (long)row * w + 4 * cg;
+            const f32x4 g = *reinterpret_cast<const f32x4*>(tr + 4 * cg);
+            const f32x4 h = *reinterpret_cast<const f32x4*>(gh + at), xh = *reinterpret_cast<const f32x4*>(gxh + at);
+            const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * cg);
+            f32x4 dy, px;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                dy[e] = h[e] > 0.f ? g[e] : 0.f;
+                dxh[e] = dy[e] * gm[e];
+                px[e] = dxh[e] * xh[e];
+            }
+            *reinterpret_cast<f32x4*>(gdy + at) = dy;
+            s1 += (dxh[0] + dxh[1]) + (dxh[2] + dxh[3]);
+            s2 += (px[0] + px[1]) + (px[2] + px[3]);
+        }
+        *reinterpret_cast<f32x4*>(tr + 4 * cg) = dxh;
+    }
+    const float m1 = row16_sum(s1) * invw, m2 = row16_sum(s2) * invw;
+    const float rstd = live ? grs[row] : 0.f;
+    for (int cg = j; cg < nq; cg += 16) {
+        f32x4 dz = {0.f, 0.f, 0.f, 0.f};
+        if (live) {
+            const long at = (long)row * w + 4 * cg;
+            const f32x4 dxh = *reinterpret_cast<const f32x4*>(tr + 4 * cg), xh = *reinterpret_cast<const f32x4*>(gxh + at);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dz[e] = rstd * (dxh[e] - m1 - xh[e] * m2);
+            if (DROP) {
+                const f32x4 k = ph_drop4(drop, ctr2, row, nq, cg);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dz[e] *= k[e];
+            }
+            *reinterpret_cast<f32x4*>(gdz + at) = dz;
+        }
+        *reinterpret_cast<f32x4*>(tr + 4 * cg) = dz;
+    }
 }
 
 // rows row0 .. row0 + 15 of x [B, F] into an LDS tile, zero past B

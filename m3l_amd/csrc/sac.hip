@@ -22,6 +22,11 @@
 //                grouped weight-gradient launches of PH_MAXLIN each
 //   td target    the actor once, then only the target critics that `subset` names, in list order; a bad index: NaN rows, nothing read at it
 //   losses       SB3's sum over n critics with weights and td_abs; the actor loss against min_c or mean_c; n = 2 has the twin kernels' bits
+//
+// DroQ critics ("SAC DroQ critics", the sac_droq_* kernels and m3l_sac_droq_* entries at the end): the ensemble's critics with
+// Linear -> Dropout -> LayerNorm -> ReLU hidden layers.  Every hidden Linear runs without its activation, and a pass over the finished 16-row
+// tile in LDS (ph_ln_fwd_tile / ph_ln_bwd_tile) does the rest between two layers; the masks come from the Philox contract by global row, so
+// nothing of them is stored.  Kernels are templates over "dropout on": p = 0 compiles no Philox code.  The losses stay the ensemble's.
 #include <math.h>
 #include <string.h>
 
@@ -826,6 +831,36 @@ int sac_ens_init() {
 size_t sac_ens_lds_bytes(const SacEnsArgs& p) { return (size_t)2 * PH_TM * p.ld * 4; }
 double sac_ens_critic_flops(const SacEnsArgs& p, int critics) { return (double)critics * ph_net_flops(p.qf[0], p.B, p.K0, 1); }
 
+// the n (n_qf + 1) Linears of all critics in critic order, PH_MAXLIN to a launch (a launch's items are numbered from 0 again), from what the
+// chain kernel left in w
+int sac_ens_wgrad_launches(const SacEnsArgs& p, float* w, const m3l_sac_ens_desc* grads, hipStream_t st) {
+    const int B = p.B;
+    PhWgrad q;
+    memset(&q, 0, sizeof(q));
+    q.B = B;
+    auto flush = [&]() -> int {
+        ProfScope prof("sac_ens_critic_wgrad", B, q.items, p.n, 0.0, st, 0.0);
+        sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
+        M3L_LAUNCH_CHECK();
+        memset(&q, 0, sizeof(q));
+        q.B = B;
+        return 0;
+    };
+    for (int c = 0; c < p.n; ++c) {
+        PhWgrad one;
+        memset(&one, 0, sizeof(one));
+        ph_add_net(one, p.qf[c], w, w + p.xa_off, p.K0, p.Kp, grads->qf_weight[c], grads->qf_bias[c], 1,
+                   {{w + p.dq_off + (long)c * B, grads->q_weight[c], grads->q_bias[c]}});
+        for (int l = 0; l < one.count; ++l) {
+            const PhLin& L = one.lin[l];
+            ph_add_lin(q, L.dY, L.X, L.ldx, L.dW, L.db, L.N, L.K);
+            if (q.count == PH_MAXLIN)
+                if (const int rc = flush()) return rc;
+        }
+    }
+    return q.count > 0 ? flush() : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -868,31 +903,7 @@ int m3l_sac_ens_critic_bwd(const m3l_sac_ens_desc* d, int B, const float* dq, vo
         M3L_LAUNCH_CHECK();
     }
     if (grads == nullptr) return 0;
-    // the n (n_qf + 1) Linears in critic order, PH_MAXLIN to a launch: a launch's items are numbered from 0 again
-    PhWgrad q;
-    memset(&q, 0, sizeof(q));
-    q.B = B;
-    auto flush = [&]() -> int {
-        ProfScope prof("sac_ens_critic_wgrad", B, q.items, p.n, 0.0, st, 0.0);
-        sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
-        M3L_LAUNCH_CHECK();
-        memset(&q, 0, sizeof(q));
-        q.B = B;
-        return 0;
-    };
-    for (int c = 0; c < p.n; ++c) {
-        PhWgrad one;
-        memset(&one, 0, sizeof(one));
-        ph_add_net(one, p.qf[c], w, w + p.xa_off, p.K0, p.Kp, grads->qf_weight[c], grads->qf_bias[c], 1,
-                   {{w + p.dq_off + (long)c * B, grads->q_weight[c], grads->q_bias[c]}});
-        for (int l = 0; l < one.count; ++l) {
-            const PhLin& L = one.lin[l];
-            ph_add_lin(q, L.dY, L.X, L.ldx, L.dW, L.db, L.N, L.K);
-            if (q.count == PH_MAXLIN)
-                if (const int rc = flush()) return rc;
-        }
-    }
-    return q.count > 0 ? flush() : 0;
+    return sac_ens_wgrad_launches(p, w, grads, st);
 }
 
 int m3l_sac_ens_td_target(const m3l_sac_ens_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
@@ -944,6 +955,343 @@ int m3l_sac_ens_loss_bwd(const float* dloss, const float* coef, int n, float* ou
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("sac_ens_loss_bwd", n, 0, 0, 1.0 * n, st, 8.0 * n);
     sac_scale_kernel<<<cdiv(n, 256), 256, 0, st>>>(dloss, coef, n, out);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- SAC DroQ critics (include/m3l_amd.h "SAC DroQ critics"): the ensemble's critics with Linear -> Dropout -> LayerNorm -> ReLU hidden layers
+namespace {
+
+// what the DroQ path adds to the ensemble's arguments: the LayerNorm tensors, its own workspace places and the dropout of the call
+struct SacDroq {
+    const float* ln_g[M3L_SAC_MAX_CRITICS][PH_MAXH];
+    const float* ln_b[M3L_SAC_MAX_CRITICS][PH_MAXH];
+    long xh_off[M3L_SAC_MAX_CRITICS][PH_MAXH];       // xh [B, w]: the normalised rows
+    long dy_off[M3L_SAC_MAX_CRITICS][PH_MAXH];       // dy [B, w]: the gradient behind the ReLU gate, for d gamma / d beta
+    long rs_off[M3L_SAC_MAX_CRITICS][PH_MAXH];       // rstd [B]
+    PhDrop drop;
+};
+struct SacDroqArgs {
+    SacEnsArgs e;                // in e.qf: h_off holds h (post-ReLU), d_off holds dz, what the grouped weight-gradient launches take
+    SacDroq q;
+};
+static_assert(sizeof(SacDroqArgs) <= 4096, "the DroQ arguments travel by value: the kernel-argument segment holds 4 KB");
+
+// Critic c on the input tile in bufa (which it overwrites): q of the 16 rows into column 0 of head [16, PH_HLD].  sac_critic_tile with the
+// LayerNorm pass behind every hidden Linear; without hidden layers it is sac_critic_tile.  Ends with a barrier.
+template <bool DROP>
+__device__ void sac_droq_critic_tile(const SacDroqArgs& p, int c, int row0, float* bufa, float* bufb, float* head, float* __restrict__ ws) {
+    const SacEnsArgs& e = p.e;
+    const PhMlp& m = e.qf[c];
+    float* cur = bufa;
+    float* nxt = bufb;
+    int K = e.K0;
+    for (int l = 0; l < m.n; ++l) {
+        const int w = m.w[l];
+        if (l == 0)
+            ph_fwd_layer<PH_ACT_NONE, true>(cur, e.ld, K, m.W[l], m.b[l], w, nxt, e.ld, nullptr, row0, e.B);
+        else
+            ph_fwd_layer<PH_ACT_NONE>(cur, e.ld, K, m.W[l], m.b[l], w, nxt, e.ld, nullptr, row0, e.B);
+        __syncthreads();
+        ph_ln_fwd_tile<DROP>(nxt, e.ld, w, p.q.ln_g[c][l], p.q.ln_b[c][l], p.q.drop, (uint32_t)(4 * c + l), row0, e.B, ws ? ws + m.h_off[l] : nullptr,
+                             ws ? ws + p.q.xh_off[c][l] : nullptr, ws ? ws + p.q.rs_off[c][l] : nullptr);
+        __syncthreads();
+        float* s = cur; cur = nxt; nxt = s;
+        K = w;
+    }
+    if (m.n == 0)
+        ph_fwd_layer<PH_ACT_NONE, true>(cur, e.ld, K, e.q_W[c], e.q_b[c], 1, head, PH_HLD, nullptr, row0, e.B);
+    else
+        ph_fwd_layer<PH_ACT_NONE>(cur, e.ld, K, e.q_W[c], e.q_b[c], 1, head, PH_HLD, nullptr, row0, e.B);
+    __syncthreads();
+}
+
+// grid (row tiles, n critics).  q [n, B].  sac_critic_fwd_body with the DroQ tile
+template <bool DROP>
+__global__ __launch_bounds__(256) void sac_droq_critic_fwd_kernel(SacDroqArgs p, const float* __restrict__ x, const float* __restrict__ actions,
+                                                                  float* __restrict__ ws, float* __restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float head[PH_TM * PH_HLD];
+    const SacEnsArgs& e = p.e;
+    float* bufa = sac_lds;
+    float* bufb = sac_lds + PH_TM * e.ld;
+    const int c = blockIdx.y, row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = e.B;
+    sac_build_xa(e, x, actions + (long)row0 * e.A, e.A, row0, bufa);
+    __syncthreads();
+    if (ws != nullptr && c == 0) {
+        const int per = e.Kp >> 2;
+        for (int i = tid; i < PH_TM * per; i += 256) {
+            const int m = i / per, k = (i - m * per) * 4;
+            if (row0 + m < B) *reinterpret_cast<f32x4*>(ws + e.xa_off + (long)(row0 + m) * e.Kp + k) = *reinterpret_cast<const f32x4*>(bufa + m * e.ld + k);
+        }
+        __syncthreads();
+    }
+    sac_droq_critic_tile<DROP>(p, c, row0, bufa, bufb, head, ws);
+    if (tid < PH_TM && row0 + tid < B) q[(long)c * B + row0 + tid] = head[tid * PH_HLD];
+}
+
+// grid (row tiles).  dq [n, B] or null (= zero); dactions [B, A] or null (not wanted).  The ensemble's chain with the LayerNorm pass between
+// two ph_bwd_layer calls: the Linear above hands g = dL / dh down ungated, the pass gates it by h, leaves dy in ws and turns it into dz
+template <bool DROP>
+__global__ __launch_bounds__(256) void sac_droq_critic_bwd_kernel(SacDroqArgs p, const float* __restrict__ dq, float* __restrict__ ws,
+                                                                  float* __restrict__ dactions) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    const SacEnsArgs& e = p.e;
+    const int row0 = blockIdx.x * PH_TM, B = e.B;
+    for (int c = 0; c < e.n; ++c) {
+        const PhMlp& m = e.qf[c];
+        float* cur = sac_lds;
+        float* nxt = sac_lds + PH_TM * e.ld;
+        ph_col0_tile(dq ? dq + (long)c * B : nullptr, ws + e.dq_off + (long)c * B, cur, e.ld, row0, B);
+        __syncthreads();
+        const float* W = e.q_W[c];
+        int N = 1, valid = 8;
+        for (int l = m.n - 1; l >= 0; --l) {
+            const int K = m.w[l];
+            ph_bwd_layer<PH_ACT_NONE>(cur, e.ld, valid, W, N, K, nullptr, nxt, e.ld, nullptr, false, row0, B);
+            __syncthreads();
+            ph_ln_bwd_tile<DROP>(nxt, e.ld, K, p.q.ln_g[c][l], p.q.drop, (uint32_t)(4 * c + l), row0, B, ws + m.h_off[l], ws + p.q.xh_off[c][l],
+                                 ws + p.q.rs_off[c][l], ws + p.q.dy_off[c][l], ws + m.d_off[l]);
+            __syncthreads();
+            float* s = cur; cur = nxt; nxt = s;
+            W = m.W[l];
+            N = K;
+            valid = K;
+        }
+        if (dactions != nullptr) ph_bwd_edge(cur, e.ld, valid, W, N, e.K0, e.F, e.A, dactions, c > 0, row0, B);
+        __syncthreads();
+    }
+}
+
+// d gamma / d beta of every LayerNorm of every critic, one launch: item i is one LayerNorm, w columns in cdiv(w, 64) workgroups of 64 columns
+struct SacLnGradItem {
+    const float* dy;             // [B, w]
+    const float* xh;             // [B, w]
+    float* dgamma;               // [w] = sum_r dy xh
+    float* dbeta;                // [w] = sum_r dy
+    int w, block0;
+};
+struct SacLnGrad {
+    SacLnGradItem it[M3L_SAC_MAX_CRITICS * PH_MAXH];
+    int count, blocks, B;
+};
+// grid (blocks).  Lane j of a workgroup owns column 64 (block - block0) + j; wave p adds the rows p, p + 4, ... in ascending order, and the four
+// partial sums meet as (0 + 1) + (2 + 3): one fixed order, no atomics
+__global__ __launch_bounds__(256) void sac_droq_ln_grad_kernel(SacLnGrad a) {
+    __shared__ float red[2][4][64];
+    int li = 0;
+    while (li + 1 < a.count && (int)blockIdx.x >= a.it[li + 1].block0) ++li;
+    const SacLnGradItem& it = a.it[li];
+    const int lane = threadIdx.x & 63, part = threadIdx.x >> 6, w = it.w, col = ((int)blockIdx.x - it.block0) * 64 + lane;
+    float sg = 0.f, sb = 0.f;
+    if (col < w)
+        for (int r = part; r < a.B; r += 4) {
+            const float dy = it.dy[(long)r * w + col];
+            sg += dy * it.xh[(long)r * w + col];
+            sb += dy;
+        }
+    red[0][part][lane] = sg;
+    red[1][part][lane] = sb;
+    __syncthreads();
+    if (part == 0 && col < w) {
+        it.dgamma[col] = (red[0][0][lane] + red[0][1][lane]) + (red[0][2][lane] + red[0][3][lane]);
+        it.dbeta[col] = (red[1][0][lane] + red[1][1][lane]) + (red[1][2][lane] + red[1][3][lane]);
+    }
+}
+
+// grid (row tiles).  sac_ens_td_target_kernel with the DroQ tile: a critic's masks follow its own index, whatever its place in the subset
+template <bool DROP>
+__global__ __launch_bounds__(256) void sac_droq_td_target_kernel(SacDroqArgs p, const float* __restrict__ x, const float* __restrict__ noise,
+                                                                 const float* __restrict__ rewards, const float* __restrict__ dones,
+                                                                 const float* __restrict__ discounts, float gamma, float ent_coef,
+                                                                 const float* __restrict__ log_ent_coef, const int* __restrict__ subset, int n_subset,
+                                                                 float* __restrict__ target_q) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD], hs[PH_TM * PH_HLD];
+    __shared__ float lp_sh[PH_TM], q_sh[M3L_SAC_MAX_CRITICS][PH_TM];
+    const SacEnsArgs& e = p.e;
+    float* bufa = sac_lds;
+    float* bufb = sac_lds + PH_TM * e.ld;
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = e.B;
+    bool bad = false;
+    if (subset != nullptr)
+        for (int j = 0; j < n_subset; ++j) bad = bad || subset[j] < 0 || subset[j] >= e.n;
+    if (bad) {
+        if (tid < PH_TM && row0 + tid < B) target_q[row0 + tid] = __builtin_nanf("");
+        return;
+    }
+    sac_actor_tile(e, x, noise, row0, bufa, bufb, hmu, hs, lp_sh, nullptr, nullptr, nullptr);
+    for (int j = 0; j < n_subset; ++j) {
+        const int c = subset ? subset[j] : j;
+        sac_build_xa(e, x, hmu, PH_HLD, row0, bufa);
+        __syncthreads();
+        sac_droq_critic_tile<DROP>(p, c, row0, bufa, bufb, hs, nullptr);
+        if (tid < PH_TM) q_sh[j][tid] = hs[tid * PH_HLD];
+        __syncthreads();
+    }
+    if (tid < PH_TM && row0 + tid < B) {
+        const int row = row0 + tid;
+        const float ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
+        float m = q_sh[0][tid];
+        for (int j = 1; j < n_subset; ++j) m = fminf(m, q_sh[j][tid]);
+        const float nq = m - ent * lp_sh[tid];
+        const float g = discounts ? discounts[row] : gamma;
+        target_q[row] = rewards[row] + (1.f - dones[row]) * g * nq;
+    }
+}
+
+int sac_droq_shape_ok(const m3l_sac_droq_desc* d, int B, char* why, size_t n) {
+    if (d == nullptr) { snprintf(why, n, "null descriptor"); return 0; }
+    if (!(d->dropout_p >= 0.f && d->dropout_p < 1.f)) { snprintf(why, n, "dropout_p=%g (0 <= p < 1)", (double)d->dropout_p); return 0; }
+    return sac_ens_shape_ok(&d->ens, B, why, n);
+}
+
+// the ensemble's arguments and workspace layout, then the DroQ path's own places behind them; parts as in sac_args
+SacDroqArgs sac_droq_args(const m3l_sac_droq_desc* d, int B, int parts) {
+    SacDroqArgs p;
+    memset(&p, 0, sizeof(p));
+    p.e = sac_ens_args(&d->ens, B, parts);
+    long off = p.e.total;
+    for (int c = 0; c < p.e.n; ++c)
+        for (int l = 0; l < p.e.qf[c].n; ++l) {
+            const long rows = (long)B * p.e.qf[c].w[l];
+            p.q.xh_off[c][l] = off;
+            off += rows;
+            p.q.dy_off[c][l] = off;
+            off += rows;
+        }
+    for (int c = 0; c < p.e.n; ++c)
+        for (int l = 0; l < p.e.qf[c].n; ++l) {
+            p.q.rs_off[c][l] = off;
+            off = ph_round4(off + B);
+        }
+    p.e.total = off;
+    if (parts & SAC_CRITIC)
+        for (int c = 0; c < p.e.n; ++c)
+            for (int l = 0; l < p.e.qf[c].n; ++l) {
+                p.q.ln_g[c][l] = d->ln_weight[c][l];
+                p.q.ln_b[c][l] = d->ln_bias[c][l];
+            }
+    const DropCtx dc = m3l_drop_ctx(d->dropout_p, d->seed, 0, 0);
+    p.q.drop.thr = dc.thr; p.q.drop.k0 = dc.k0; p.q.drop.k1 = dc.k1; p.q.drop.scale = dc.scale;
+    return p;
+}
+
+int sac_droq_params_ok(const m3l_sac_droq_desc* d, int parts, const char* who) {
+    if (sac_ens_params_ok(&d->ens, parts, who)) return 1;
+    int ok = 1;
+    if (parts & SAC_CRITIC)
+        for (int c = 0; c < d->ens.n_critics; ++c)
+            for (int l = 0; l < d->ens.n_qf; ++l) ok = ok && d->ln_weight[c][l] && d->ln_bias[c][l] && ph_aligned(d->ln_weight[c][l]) && ph_aligned(d->ln_bias[c][l]);
+    M3L_CHECK(ok, "%s: a LayerNorm pointer of the descriptor is null or not 16-byte aligned", who);
+    return 0;
+}
+
+int g_sac_droq_inited = 0;
+int sac_droq_init() {
+    if (g_sac_droq_inited) return 0;
+    if (ph_allow_lds({(const void*)sac_droq_critic_fwd_kernel<false>, (const void*)sac_droq_critic_fwd_kernel<true>,
+                      (const void*)sac_droq_critic_bwd_kernel<false>, (const void*)sac_droq_critic_bwd_kernel<true>,
+                      (const void*)sac_droq_td_target_kernel<false>, (const void*)sac_droq_td_target_kernel<true>}, SAC_LDS_MAX))
+        return 2;
+    g_sac_droq_inited = 1;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t m3l_sac_droq_ws_bytes(const m3l_sac_droq_desc* d, int B) {
+    char why[160];
+    if (!sac_droq_shape_ok(d, B, why, sizeof(why))) return 256;
+    return (size_t)sac_droq_args(d, B, 0).e.total * sizeof(float);
+}
+
+int m3l_sac_droq_critic_fwd(const m3l_sac_droq_desc* d, int B, const float* x, const float* actions, void* ws, float* q, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_droq_shape_ok(d, B, why, sizeof(why)), "sac_droq_critic_fwd: unsupported shape: %s", why);
+    if (sac_droq_params_ok(d, SAC_CRITIC, "sac_droq_critic_fwd")) return 1;
+    M3L_CHECK(x && actions && q && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_droq_critic_fwd: null argument, or x / ws not 16-byte aligned");
+    if (sac_droq_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacDroqArgs p = sac_droq_args(d, B, SAC_CRITIC);
+    const dim3 grid(cdiv(B, PH_TM), p.e.n);
+    ProfScope prof("sac_droq_critic_fwd", B, p.e.F, p.e.n, sac_ens_critic_flops(p.e, p.e.n), st, 4.0 * B * p.e.K0);
+    if (d->dropout_p > 0.f)
+        sac_droq_critic_fwd_kernel<true><<<grid, 256, sac_ens_lds_bytes(p.e), st>>>(p, x, actions, (float*)ws, q);
+    else
+        sac_droq_critic_fwd_kernel<false><<<grid, 256, sac_ens_lds_bytes(p.e), st>>>(p, x, actions, (float*)ws, q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_droq_critic_bwd(const m3l_sac_droq_desc* d, int B, const float* dq, void* ws, float* dactions, const m3l_sac_droq_desc* grads,
+                            void* stream) {
+    char why[160];
+    M3L_CHECK(sac_droq_shape_ok(d, B, why, sizeof(why)), "sac_droq_critic_bwd: unsupported shape: %s", why);
+    if (sac_droq_params_ok(d, SAC_CRITIC, "sac_droq_critic_bwd")) return 1;
+    M3L_CHECK(grads == nullptr || (grads->ens.n_qf == d->ens.n_qf && grads->ens.n_critics == d->ens.n_critics),
+              "sac_droq_critic_bwd: the gradient descriptor has another layer or critic count");
+    if (grads != nullptr && sac_droq_params_ok(grads, SAC_CRITIC, "sac_droq_critic_bwd (gradients)")) return 1;
+    M3L_CHECK(ws && ph_aligned(ws), "sac_droq_critic_bwd: ws is null or not 16-byte aligned");
+    if (sac_droq_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacDroqArgs p = sac_droq_args(d, B, SAC_CRITIC);
+    float* w = (float*)ws;
+    {
+        ProfScope prof("sac_droq_critic_bwd_chain", B, p.e.F, p.e.n, sac_ens_critic_flops(p.e, p.e.n), st, 0.0);
+        if (d->dropout_p > 0.f)
+            sac_droq_critic_bwd_kernel<true><<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e), st>>>(p, dq, w, dactions);
+        else
+            sac_droq_critic_bwd_kernel<false><<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e), st>>>(p, dq, w, dactions);
+        M3L_LAUNCH_CHECK();
+    }
+    if (grads == nullptr) return 0;
+    if (const int rc = sac_ens_wgrad_launches(p.e, w, &grads->ens, st)) return rc;
+    SacLnGrad a;
+    memset(&a, 0, sizeof(a));
+    a.B = B;
+    for (int c = 0; c < p.e.n; ++c)
+        for (int l = 0; l < p.e.qf[c].n; ++l) {
+            SacLnGradItem& it = a.it[a.count++];
+            it.dy = w + p.q.dy_off[c][l];
+            it.xh = w + p.q.xh_off[c][l];
+            it.dgamma = grads->ln_weight[c][l];
+            it.dbeta = grads->ln_bias[c][l];
+            it.w = p.e.qf[c].w[l];
+            it.block0 = a.blocks;
+            a.blocks += cdiv(it.w, 64);
+        }
+    if (a.count == 0) return 0;
+    ProfScope prof("sac_droq_ln_grad", B, a.blocks, a.count, 0.0, st, 0.0);
+    sac_droq_ln_grad_kernel<<<a.blocks, 256, 0, st>>>(a);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_droq_td_target(const m3l_sac_droq_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                           const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, const int* subset, int n_subset,
+                           float* target_q, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_droq_shape_ok(d, B, why, sizeof(why)), "sac_droq_td_target: unsupported shape: %s", why);
+    if (sac_droq_params_ok(d, SAC_ACTOR | SAC_CRITIC, "sac_droq_td_target")) return 1;
+    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "sac_droq_td_target: null argument, or x_next not 16-byte aligned");
+    M3L_CHECK(subset != nullptr ? (n_subset >= 1 && n_subset <= d->ens.n_critics) : (n_subset == 0 || n_subset == d->ens.n_critics),
+              "sac_droq_td_target: n_subset=%d (1 to n_critics=%d entries; with subset NULL, all of them)", n_subset, d->ens.n_critics);
+    if (sac_droq_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacDroqArgs p = sac_droq_args(d, B, SAC_ACTOR | SAC_CRITIC);
+    const int m = subset ? n_subset : p.e.n;
+    ProfScope prof("sac_droq_td_target", B, p.e.F, m, ph_net_flops(p.e.pi, B, p.e.F, 2 * p.e.A) + sac_ens_critic_flops(p.e, m), st, 4.0 * B * p.e.F);
+    if (d->dropout_p > 0.f)
+        sac_droq_td_target_kernel<true><<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e), st>>>(p, x_next, noise, rewards, dones, discounts, gamma, ent_coef,
+                                                                                          log_ent_coef, subset, m, target_q);
+    else
+        sac_droq_td_target_kernel<false><<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e), st>>>(p, x_next, noise, rewards, dones, discounts, gamma, ent_coef,
+                                                                                           log_ent_coef, subset, m, target_q);
     M3L_LAUNCH_CHECK();
     return 0;
 }

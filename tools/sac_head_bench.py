@@ -24,7 +24,14 @@ Polyak update), and of one actor update with --q-reduce, on
   twin   m3l_amd.SACHead on the same two critics, when N = 2 (the subset is then None: both)
 in alternating windows of one run.
 
-Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30] [--critics N [--subset M] [--q-reduce min|mean]]
+With --droq it measures one critic update (TD target, critic loss, backward, Polyak update) of the DroQ critics (EXPERIMENTS.md "SAC DroQ
+critics") at N = 2, the same shapes, p = 0.01, on
+  droq   m3l_amd.SACEnsembleHead(n_critics=2, critic_layer_norm=True, critic_dropout=0.01)
+  eager  the float32 torch restatement of tests/droq_cases.py with torch's own dropout in place of the contract's masks
+  ens10  the existing update of m3l_amd.SACEnsembleHead with N = 10 critics and a subset of 2, the REDQ recipe DroQ stands in for
+in alternating windows of one run.
+
+Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30] [--critics N [--subset M] [--q-reduce min|mean] | --droq]
 (one JSON line on stdout)"""
 import argparse
 import json
@@ -40,6 +47,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import sac_cases as SC  # noqa: E402
 import sac_ens_cases as EC  # noqa: E402
+import droq_cases as DC  # noqa: E402
 import m3l_amd  # noqa: E402
 from m3l_amd import sac as SH  # noqa: E402
 from policy_head_bench import alternate, counted, entry_points  # noqa: E402
@@ -148,6 +156,75 @@ def ensemble(a):
     print(json.dumps(out))
 
 
+def droq(a):
+    """The --droq mode: see the module docstring."""
+    N, B, p = 2, 256, 0.01
+    c = DC.make_inputs(ARCH, N, B, p, seed=9)
+    net_arch = dict(pi=list(ARCH[1]), qf=list(ARCH[2]))
+    head = m3l_amd.SACEnsembleHead(ARCH[0], ARCH[3], net_arch=net_arch, n_critics=N, critic_layer_norm=True, critic_dropout=p)
+    head.load_state_dict({k: torch.from_numpy(v) for k, v in c["params"].items()})
+    head = head.to(DEV)
+    ce = EC.make_inputs(ARCH, 10, B, seed=9)
+    ens = m3l_amd.SACEnsembleHead(ARCH[0], ARCH[3], net_arch=net_arch, n_critics=10)
+    ens.load_state_dict({k: torch.from_numpy(v) for k, v in ce["params"].items()})
+    ens = ens.to(DEV)
+    P = dict(head.named_parameters())
+    t = {k: torch.from_numpy(c[k]).to(DEV) for k in ("x", "x_next", "noise_pi", "noise_next", "a_replay", "rewards", "dones")}
+    log_ent = torch.tensor([c["log_ent_coef"]], dtype=torch.float32, device=DEV)
+    critic_params = [q for n, q in P.items() if n.startswith("critic.")]
+    target_params = [q for n, q in P.items() if n.startswith("critic_target.")]
+    gamma, tau = c["gamma"], c["tau"]
+
+    def zero(h):
+        for q in h.parameters():
+            q.grad = None
+
+    def eager_critics(prefix, x, actions):
+        """The restatement's critics in float32 with torch's own dropout in place of the contract's masks (other masks, the same work)."""
+        xa = torch.cat([x, actions], dim=1)
+        qs = []
+        for ci in range(N):
+            h = xa
+            for l, w in enumerate(ARCH[2]):
+                z = F.dropout(F.linear(h, P[f"{prefix}.qf{ci}.{4 * l}.weight"], P[f"{prefix}.qf{ci}.{4 * l}.bias"]), p, True)
+                h = torch.relu(F.layer_norm(z, (w,), P[f"{prefix}.qf{ci}.{4 * l + 2}.weight"], P[f"{prefix}.qf{ci}.{4 * l + 2}.bias"], 1e-5))
+            qs.append(F.linear(h, P[f"{prefix}.qf{ci}.{4 * len(ARCH[2])}.weight"], P[f"{prefix}.qf{ci}.{4 * len(ARCH[2])}.bias"]).flatten())
+        return torch.stack(qs)
+
+    def hip_update(h, **kw):
+        zero(h)
+        target_q = h.td_target(t["x_next"], t["rewards"], t["dones"], gamma, log_ent_coef=log_ent, noise=t["noise_next"], **kw)
+        loss = h.critic_loss(t["x"], t["a_replay"], target_q)
+        loss.backward()
+        h.polyak_update(tau)
+        return loss
+
+    def eager_update():
+        zero(head)
+        with torch.no_grad():
+            n = SC.actor_forward(P, t["x_next"], t["noise_next"])
+            nq = eager_critics("critic_target", t["x_next"], n["actions"]).min(dim=0)[0] - torch.exp(log_ent) * n["log_prob"]
+            target_q = t["rewards"] + (1 - t["dones"]) * gamma * nq
+        q = eager_critics("critic", t["x"], t["a_replay"])
+        loss = 0.5 * sum(F.mse_loss(qc, target_q) for qc in q)
+        loss.backward()
+        with torch.no_grad():
+            for q_, tp in zip(critic_params, target_params):
+                tp.mul_(1 - tau)
+                torch.add(tp, q_, alpha=tau, out=tp)
+        return loss
+    fns = {"droq": lambda: hip_update(head), "eager": eager_update, "ens10": lambda: hip_update(ens, subset=ens.sample_subset(2))}
+    res, last = alternate(fns, a.iters, a.warmup, a.rounds)
+    for name, fn in fns.items():
+        res[name].update(counted(fn))
+        res[name]["result_sum"] = float(last[name].detach().float().sum())
+    res["droq"]["entry_points"] = entry_points(fns["droq"])
+    res["droq_over_eager_call"] = round(res["droq"]["call_us"] / res["eager"]["call_us"], 3)
+    res["droq_over_ens10_call"] = round(res["droq"]["call_us"] / res["ens10"]["call_us"], 3)
+    print(json.dumps({"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}, "critics": N, "dropout": p, "B": B,
+                      "critic_update": res}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=500, help="calls per timed window of (a); (b) takes ten times as many")
@@ -156,9 +233,12 @@ def main():
     ap.add_argument("--critics", type=int, default=None, help="measure the critic ensemble with this many critics (1 to 10) instead of (a) and (b)")
     ap.add_argument("--subset", type=int, default=2, help="with --critics: critics in the target's minimum (N = 2: both)")
     ap.add_argument("--q-reduce", choices=("min", "mean"), default="mean", help="with --critics: the actor loss's reduction over the critics")
+    ap.add_argument("--droq", action="store_true", help="measure a critic update of the DroQ critics (N = 2, p = 0.01) against eager torch and the N = 10 ensemble")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sac_head_bench: no GPU")
+    if a.droq:
+        return droq(a)
     if a.critics is not None:
         return ensemble(a)
     out = {"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}}
