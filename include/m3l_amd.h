@@ -787,7 +787,7 @@ int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float ta
  * an ensemble of N critics, the target's minimum over a random subset of M of them, the actor trained against the ensemble's mean) and for
  * SB3's `n_critics` of any value (sac_mae_policy.py:62 passes it on).  Neither SB3 nor a REDQ implementation is part of the reference tree:
  * the rule is stated here and restated in float64 by tests/sac_ens_cases.py, parity unpinned.  The struct, the entry points and the results of
- * the section above do not change; DroQ (LayerNorm and dropout critics) is the section below; TQC is not computed.  float32 throughout.
+ * the section above do not change; DroQ (LayerNorm and dropout critics) is the section below, TQC the one after it.  float32 throughout.
  *   1. q_c = critic_c(cat([x, a])), c < N: the critic arithmetic of the section above, per critic.
  *   2. target_q = r + (1 - done) g (min over the subset's entries, in list order, by fminf, of q_target_c(x', a') - ent logp'),
  *      (a', logp') = actor(x'), g = gamma or discounts[row].  Only the listed critics are evaluated: the cost grows with M, not N.  Duplicates
@@ -849,7 +849,7 @@ int m3l_sac_ens_loss_bwd(const float* dloss, const float* coef, int n, float* ou
  * critics reach the update-to-data ratio that REDQ buys with ten; p = 0 is the plain LayerNorm critic of pixel SAC).  Every critic and every
  * target critic is [Linear(w_in, w), Dropout(p), LayerNorm(w), ReLU] x n_qf + Linear(w_last, 1).  Neither SB3 nor a DroQ implementation is
  * part of the reference tree: the rule is stated here and restated in float64 by tests/droq_cases.py, parity unpinned.  The sections above
- * and their results do not change; TQC is not computed.  float32 throughout.
+ * and their results do not change; TQC (the section below) runs plain critics only.  float32 throughout.
  * Per hidden layer l of critic c, on row r, with w the layer's width, gamma / beta the LayerNorm's weight / bias:
  *   z = W h_in + b
  *   d = z keep scale                                   (p = 0: d = z)
@@ -892,6 +892,62 @@ int m3l_sac_droq_critic_bwd(const m3l_sac_droq_desc* head, int B, const float* d
 int m3l_sac_droq_td_target(const m3l_sac_droq_desc* head, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
                            const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, const int* subset, int n_subset,
                            float* target_q, void* stream);
+
+/* ---- SAC TQC critics (ABI 421): truncated quantile critics (TQC, Kuznetsov et al., ICML 2020; sb3_contrib.TQC) on the ensemble's nets.  Every
+ * critic and target critic is the ensemble's critic with Linear(w_last, n_quantiles) as its last layer.  sb3-contrib is not part of the
+ * reference tree: the rule is stated here from its `TQC.train`, `Critic` and `quantile_huber_loss` and restated in float64 by
+ * tests/tqc_cases.py, parity unpinned.  The sections above and their results do not change.  float32 throughout.
+ * With N critics, nq = n_quantiles, d = top_quantiles_to_drop (per net), K = N (nq - d):
+ *   1. z_c = critic_c(cat([x, a])) [B, nq], c < N;  z [N, B, nq].
+ *   2. target: (a', logp') = actor(x'); the N nq outputs of the target critics at (x', a') of a row are pooled and sorted ascending, the K
+ *      smallest kept:  target[b, k] = r_b + (1 - done_b) g_b (sorted[b, k] - ent logp'_b),  g = gamma or discounts[row];  target [B, K].
+ *      The sort is a rank count in LDS: an element's place is the number of pool elements in front of it by (value, index), NaN as the
+ *      largest value, so its addressing does not depend on the data and every place 0 .. N nq - 1 is taken exactly once: NaN quantiles
+ *      sort last (the N d dropped places take them first), infinite ones where their value puts them; nothing is read or written out of
+ *      range and every element of target is written.  Equal values keep their index order, which no output shows.
+ *   3. critic_loss = (1 / (B N nq K)) sum_{b, c, j, k} w_b |tau_j - [delta < 0]| huber(delta),  tau_j = (j + 0.5) / nq,
+ *      delta = target[b, k] - z[c, b, j],  huber(delta) = 0.5 delta^2 if |delta| <= 1 else |delta| - 0.5;  w NULL: ones (the same bits).
+ *      coef[c, b, j] = dloss / dz = -(w_b / (B N nq K)) sum_k |tau_j - [delta < 0]| clamp(delta, -1, 1) (the indicator is a constant);
+ *      td_abs[b] = (1 / (N nq K)) sum_{c, j, k} |delta|.  The target takes no gradient.  sum_over_quantiles is not computed.
+ *   4. actor_loss = mean_b (ent logp_b - (1 / (N nq)) sum_{c, j} z[c, b, j]);  coef: dloss / dlogp [B] = ent / B, then dloss / dz [N, B, nq] =
+ *      -1 / (B N nq).
+ * The actor's forward and backward stay m3l_sac_actor_fwd / _bwd, the entropy-coefficient loss m3l_sac_ent_coef_loss, the Polyak update
+ * m3l_op_ema over all critics' tensors in one launch, the backward of both losses m3l_sac_ens_loss_bwd (n = N B nq, and B + N B nq).
+ * Launches: critic_fwd 1 (grid: row tiles x N); critic_bwd 1 chain (from a [16, 64] tile of dz with (nq + 7) & ~7 written columns; critics in
+ * order, critic c > 0 adding its dactions lane for lane) + ceil(N (n_qf + 1) / 8) grouped weight-gradient launches when `grads` is not NULL
+ * (the head's [nq, w_last] gradient is one of their items); td_target 1 (per row tile: the actor, the N target critics one after another
+ * into a pool [16, N nq] in LDS, the rank count, the Bellman line); critic_loss_fwd 2 (grid row tiles x N: one thread per (row, j) adds
+ * its K pair terms in ascending k, the block's sum goes to the scratch; then one workgroup adds the partial sums in index order and
+ * finishes td_abs); actor_loss_fwd 1.  A critic update (td_target, critic_loss, backward) at N = 2, n_qf = 2 is 1 + (1 + 2) + (1 + 1 + 1)
+ * = 7 launches.  No float atomics, every sum in a fixed order: two runs give the same bits.
+ * Limits: the ensemble's; 1 <= n_quantiles <= 64 (the width of the head tile); 0 <= top_quantiles_to_drop < n_quantiles; the pool
+ * N n_quantiles <= M3L_TQC_MAX_POOL = 512.  The limit is the target kernel's LDS budget: 2 x 16 x (widest + 4) floats of activation
+ * buffers (74 240 B at the widest net), 16 x (pool + 1) words of pool (32 832 B at 512) and 8 256 B of head tiles, 115 328 B of the
+ * 160 KiB a gfx950 workgroup may take, and it bounds the rank count's pool^2 comparisons per row; it admits N = 10 with nq = 25 and N = 8
+ * with nq = 64.  Anything else is an error and nothing is written.
+ * ws: m3l_tqc_ws_bytes bytes, one per critic forward that a backward follows; m3l_tqc_loss_ws_bytes bytes of scratch per critic_loss_fwd
+ * (read and written inside the call only). */
+#define M3L_TQC_MAX_POOL 512
+typedef struct m3l_tqc_desc {
+    m3l_sac_ens_desc ens;                     /* the ensemble's fields, in its layout; q_weight[c] is [n_quantiles, last qf width or F + A] */
+    int n_quantiles;                          /* nq, 1 .. 64 */
+    int top_quantiles_to_drop;                /* d per net, 0 .. nq - 1; read by td_target only, checked by every entry */
+} m3l_tqc_desc;
+size_t m3l_tqc_ws_bytes(const m3l_tqc_desc* head, int B);
+/* z [N, B, nq] is written; ws NULL when no backward follows */
+int m3l_tqc_critic_fwd(const m3l_tqc_desc* head, int B, const float* x, const float* actions, void* ws, float* z, void* stream);
+/* dz [N, B, nq]: NULL = zero; dactions [B, A] or NULL (not wanted); grads NULL: no parameter gradient, the weight-gradient launches are skipped */
+int m3l_tqc_critic_bwd(const m3l_tqc_desc* head, int B, const float* dz, void* ws, float* dactions, const m3l_tqc_desc* grads, void* stream);
+/* target [B, K] is written; the descriptor's critics are the target critics; discounts [B] or NULL (gamma for every row) */
+int m3l_tqc_td_target(const m3l_tqc_desc* head, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                      const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, float* target, void* stream);
+size_t m3l_tqc_loss_ws_bytes(int N, int B);
+/* z [N, B, nq], target [B, K], weights [B] or NULL (ones); loss[1] and coef [N, B, nq] are written, and td_abs [B] when it is not NULL */
+int m3l_tqc_critic_loss_fwd(const float* z, const float* target, const float* weights, int N, int B, int n_quantiles, int K, void* ws, float* loss,
+                            float* coef, float* td_abs, void* stream);
+/* loss[1] and coef [B + N B nq] = dloss/dlogp [B] then dloss/dz [N, B, nq] are written */
+int m3l_tqc_actor_loss_fwd(const float* logp, const float* z, int N, int B, int n_quantiles, float ent_coef, const float* log_ent_coef, float* loss,
+                           float* coef, void* stream);
 
 /* ---- device-resident rollout (ABI 411): what PPO_MAE.train does between `rollout_buffer` and `self.mae(x)` for every minibatch, with the rollout
  * kept in device memory in the layout the vec-env fills it in, (T, n_envs, ...).  Nothing is swapped or flattened: idx [B] (int64) holds flat

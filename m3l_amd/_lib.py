@@ -85,6 +85,15 @@ class SacDroqDesc(C.Structure):
                 ("dropout_p", C.c_float), ("seed", C.c_uint64)]
 
 
+TQC_MAX_POOL = 512          # M3L_TQC_MAX_POOL: most pooled target quantiles per row, n_critics * n_quantiles
+TQC_MAX_QUANTILES = 64      # the width of the head tile
+
+
+class TqcDesc(C.Structure):
+    """m3l_tqc_desc: the ensemble's descriptor, then n_quantiles and top_quantiles_to_drop (include/m3l_amd.h "SAC TQC critics")."""
+    _fields_ = [("ens", SacEnsDesc), ("n_quantiles", c_i), ("top_quantiles_to_drop", c_i)]
+
+
 _SIGS = {
     "m3l_version": (c_i, []),
     "m3l_last_error": (c_i, [C.c_char_p, c_sz]),
@@ -295,6 +304,14 @@ _SIGS = {
     "m3l_sac_droq_critic_fwd": (c_i, [C.POINTER(SacDroqDesc), c_i, c_p, c_p, c_p, c_p, c_p]),
     "m3l_sac_droq_critic_bwd": (c_i, [C.POINTER(SacDroqDesc), c_i, c_p, c_p, c_p, C.POINTER(SacDroqDesc), c_p]),
     "m3l_sac_droq_td_target": (c_i, [C.POINTER(SacDroqDesc), c_i, c_p, c_p, c_p, c_p, c_p, C.c_float, C.c_float, c_p, c_p, c_i, c_p, c_p]),
+    # SAC TQC critics (ABI 421): the ensemble's critic entries with heads of n_quantiles outputs, the sorted target [B, K], the quantile-Huber loss
+    "m3l_tqc_ws_bytes": (c_sz, [C.POINTER(TqcDesc), c_i]),
+    "m3l_tqc_critic_fwd": (c_i, [C.POINTER(TqcDesc), c_i, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_tqc_critic_bwd": (c_i, [C.POINTER(TqcDesc), c_i, c_p, c_p, c_p, C.POINTER(TqcDesc), c_p]),
+    "m3l_tqc_td_target": (c_i, [C.POINTER(TqcDesc), c_i, c_p, c_p, c_p, c_p, c_p, C.c_float, C.c_float, c_p, c_p, c_p]),
+    "m3l_tqc_loss_ws_bytes": (c_sz, [c_i, c_i]),
+    "m3l_tqc_critic_loss_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "m3l_tqc_actor_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

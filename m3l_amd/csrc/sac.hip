@@ -27,6 +27,11 @@
 // Linear -> Dropout -> LayerNorm -> ReLU hidden layers.  Every hidden Linear runs without its activation, and a pass over the finished 16-row
 // tile in LDS (ph_ln_fwd_tile / ph_ln_bwd_tile) does the rest between two layers; the masks come from the Philox contract by global row, so
 // nothing of them is stored.  Kernels are templates over "dropout on": p = 0 compiles no Philox code.  The losses stay the ensemble's.
+//
+// TQC critics ("SAC TQC critics", the sac_tqc_* kernels and m3l_tqc_* entries at the end): the ensemble's critics with a head of nq <= 64
+// quantiles.  The TD target pools the n nq target quantiles of a row in LDS and ranks them by (key, index), NaN last, so the K smallest go out
+// in one launch without data-dependent addressing; the quantile-Huber loss runs on a grid (row tiles, critics) with per-block partial sums
+// that a one-workgroup launch adds in index order.
 #include <math.h>
 #include <string.h>
 
@@ -832,8 +837,8 @@ size_t sac_ens_lds_bytes(const SacEnsArgs& p) { return (size_t)2 * PH_TM * p.ld 
 double sac_ens_critic_flops(const SacEnsArgs& p, int critics) { return (double)critics * ph_net_flops(p.qf[0], p.B, p.K0, 1); }
 
 // the n (n_qf + 1) Linears of all critics in critic order, PH_MAXLIN to a launch (a launch's items are numbered from 0 again), from what the
-// chain kernel left in w
-int sac_ens_wgrad_launches(const SacEnsArgs& p, float* w, const m3l_sac_ens_desc* grads, hipStream_t st) {
+// chain kernel left in w.  rows: the outputs of each critic's head (1; the TQC critics' n_quantiles), its output gradient [B, rows] per critic
+int sac_ens_wgrad_launches(const SacEnsArgs& p, float* w, const m3l_sac_ens_desc* grads, hipStream_t st, int rows = 1) {
     const int B = p.B;
     PhWgrad q;
     memset(&q, 0, sizeof(q));
@@ -849,8 +854,8 @@ int sac_ens_wgrad_launches(const SacEnsArgs& p, float* w, const m3l_sac_ens_desc
     for (int c = 0; c < p.n; ++c) {
         PhWgrad one;
         memset(&one, 0, sizeof(one));
-        ph_add_net(one, p.qf[c], w, w + p.xa_off, p.K0, p.Kp, grads->qf_weight[c], grads->qf_bias[c], 1,
-                   {{w + p.dq_off + (long)c * B, grads->q_weight[c], grads->q_bias[c]}});
+        ph_add_net(one, p.qf[c], w, w + p.xa_off, p.K0, p.Kp, grads->qf_weight[c], grads->qf_bias[c], rows,
+                   {{w + p.dq_off + (long)c * B * rows, grads->q_weight[c], grads->q_bias[c]}});
         for (int l = 0; l < one.count; ++l) {
             const PhLin& L = one.lin[l];
             ph_add_lin(q, L.dY, L.X, L.ldx, L.dW, L.db, L.N, L.K);
@@ -1292,6 +1297,378 @@ int m3l_sac_droq_td_target(const m3l_sac_droq_desc* d, int B, const float* x_nex
     else
         sac_droq_td_target_kernel<false><<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e), st>>>(p, x_next, noise, rewards, dones, discounts, gamma, ent_coef,
                                                                                            log_ent_coef, subset, m, target_q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- SAC TQC critics (include/m3l_amd.h "SAC TQC critics"): the ensemble's critics with a head of n_quantiles outputs, the pooled and sorted
+// target quantiles, and the pairwise quantile-Huber loss
+namespace {
+
+struct SacTqcArgs {
+    SacEnsArgs e;                // e.dq_off: dz [n, B, nq], per critic the [B, nq] output gradient of its head's weight gradient
+    int nq, K;                   // quantiles per critic; target quantiles kept per row, n (nq - drop)
+    int pool, pld;               // n nq, and the leading dimension of the pool in LDS (odd: rows fall on different banks)
+};
+static_assert(sizeof(SacTqcArgs) <= 4096, "the TQC arguments travel by value: the kernel-argument segment holds 4 KB");
+
+// Critic c on the input tile in bufa (which it overwrites): its nq quantiles of the 16 rows into the columns < nq of head [16, PH_HLD].
+// sac_critic_tile with a head of width nq.  Ends with a barrier.
+__device__ void sac_tqc_critic_tile(const SacEnsArgs& e, int nq, int c, int row0, float* bufa, float* bufb, float* head, float* __restrict__ ws) {
+    float* cur = bufa;
+    float* nxt = bufb;
+    const int K = ph_fwd_walk<PH_ACT_RELU, true>(e.qf[c], e.K0, cur, nxt, e.ld, ws, row0, e.B);
+    if (e.qf[c].n == 0)                      // the head is the first Linear then: K = F + A, the EDGE form
+        ph_fwd_layer<PH_ACT_NONE, true>(cur, e.ld, K, e.q_W[c], e.q_b[c], nq, head, PH_HLD, nullptr, row0, e.B);
+    else
+        ph_fwd_layer<PH_ACT_NONE>(cur, e.ld, K, e.q_W[c], e.q_b[c], nq, head, PH_HLD, nullptr, row0, e.B);
+    __syncthreads();
+}
+
+// grid (row tiles, n critics).  z [n, B, nq].  sac_critic_fwd_body with the wider head
+__global__ __launch_bounds__(256) void sac_tqc_critic_fwd_kernel(SacTqcArgs p, const float* __restrict__ x, const float* __restrict__ actions,
+                                                                 float* __restrict__ ws, float* __restrict__ z) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float head[PH_TM * PH_HLD];
+    const SacEnsArgs& e = p.e;
+    float* bufa = sac_lds;
+    float* bufb = sac_lds + PH_TM * e.ld;
+    const int c = blockIdx.y, row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = e.B, nq = p.nq;
+    sac_build_xa(e, x, actions + (long)row0 * e.A, e.A, row0, bufa);
+    __syncthreads();
+    if (ws != nullptr && c == 0) {
+        const int per = e.Kp >> 2;
+        for (int i = tid; i < PH_TM * per; i += 256) {
+            const int m = i / per, k = (i - m * per) * 4;
+            if (row0 + m < B) *reinterpret_cast<f32x4*>(ws + e.xa_off + (long)(row0 + m) * e.Kp + k) = *reinterpret_cast<const f32x4*>(bufa + m * e.ld + k);
+        }
+        __syncthreads();
+    }
+    sac_tqc_critic_tile(e, nq, c, row0, bufa, bufb, head, ws);
+    for (int i = tid; i < PH_TM * nq; i += 256) {
+        const int m = i / nq, j = i - m * nq;
+        if (row0 + m < B) z[((long)c * B + row0 + m) * nq + j] = head[m * PH_HLD + j];
+    }
+}
+
+// grid (row tiles).  dz [n, B, nq] or null (= zero); dactions [B, A] or null (not wanted).  The ensemble's chain from a gradient tile of
+// (nq + 7) & ~7 written columns, as the actor's mu head starts its way back
+__global__ __launch_bounds__(256) void sac_tqc_critic_bwd_kernel(SacTqcArgs p, const float* __restrict__ dz, float* __restrict__ ws,
+                                                                 float* __restrict__ dactions) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    const SacEnsArgs& e = p.e;
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = e.B, nq = p.nq, hv = (nq + 7) & ~7;
+    for (int c = 0; c < e.n; ++c) {
+        float* cur = sac_lds;
+        float* nxt = sac_lds + PH_TM * e.ld;
+        for (int i = tid; i < PH_TM * hv; i += 256) {                         // d z of this critic; it also stays in ws for the head's weight gradient
+            const int m = i / hv, j = i - m * hv, row = row0 + m;
+            float v = 0.f;
+            if (j < nq && row < B) {
+                const long at = ((long)c * B + row) * nq + j;
+                v = dz ? dz[at] : 0.f;
+                ws[e.dq_off + at] = v;
+            }
+            cur[m * e.ld + j] = v;
+        }
+        __syncthreads();
+        const float* W = e.q_W[c];
+        int N = nq, valid = hv;
+        ph_bwd_walk<PH_ACT_RELU>(e.qf[c], e.qf[c].n - 1, cur, nxt, e.ld, valid, W, N, ws, row0, B);
+        if (dactions != nullptr) ph_bwd_edge(cur, e.ld, valid, W, N, e.K0, e.F, e.A, dactions, c > 0, row0, B);
+        __syncthreads();
+    }
+}
+
+// A float as an integer whose signed order is the floats' order, every NaN as the largest: the sort below then has a total order whatever the
+// data holds, and its addressing never depends on a comparison's outcome being consistent.  tqc_unkey is the way back (a NaN comes back as one).
+__device__ __forceinline__ int tqc_key(float v) {
+    if (v != v) return 0x7fffffff;
+    const int k = __float_as_int(v);
+    return k ^ ((k >> 31) & 0x7fffffff);
+}
+__device__ __forceinline__ float tqc_unkey(int k) { return __int_as_float(k ^ ((k >> 31) & 0x7fffffff)); }
+
+// grid (row tiles).  The critic pointers of p are the target critics'.  Per row tile: the actor, then the n target critics one after another,
+// each leaving its nq columns in the pool [16, n nq] behind the two activation buffers; then every row's pool is ranked (16 lanes per row, an
+// element's rank = how many elements come before it by (key, index): a stable count, every rank 0 .. pool - 1 taken exactly once) and the
+// K lowest ranks go through the Bellman line into target [B, K].  discounts as in sac_td_target_kernel.
+__global__ __launch_bounds__(256) void sac_tqc_td_target_kernel(SacTqcArgs p, const float* __restrict__ x, const float* __restrict__ noise,
+                                                                const float* __restrict__ rewards, const float* __restrict__ dones,
+                                                                const float* __restrict__ discounts, float gamma, float ent_coef,
+                                                                const float* __restrict__ log_ent_coef, float* __restrict__ target) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD], hs[PH_TM * PH_HLD];
+    __shared__ float lp_sh[PH_TM];
+    const SacEnsArgs& e = p.e;
+    float* bufa = sac_lds;
+    float* bufb = sac_lds + PH_TM * e.ld;
+    int* pool = reinterpret_cast<int*>(sac_lds + 2 * PH_TM * e.ld);
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = e.B, nq = p.nq, P = p.pool, K = p.K;
+    sac_actor_tile(e, x, noise, row0, bufa, bufb, hmu, hs, lp_sh, nullptr, nullptr, nullptr);
+    for (int c = 0; c < e.n; ++c) {
+        sac_build_xa(e, x, hmu, PH_HLD, row0, bufa);
+        __syncthreads();
+        sac_tqc_critic_tile(e, nq, c, row0, bufa, bufb, hs, nullptr);
+        for (int i = tid; i < PH_TM * nq; i += 256) {
+            const int m = i / nq, j = i - m * nq;
+            pool[m * p.pld + c * nq + j] = tqc_key(hs[m * PH_HLD + j]);
+        }
+        __syncthreads();
+    }
+    const int m = tid >> 4, row = row0 + m;
+    if (row >= B) return;                     // no barrier follows
+    const int* pr = pool + m * p.pld;
+    const float ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
+    const float shift = ent * lp_sh[m], g = discounts ? discounts[row] : gamma, r = rewards[row], live = 1.f - dones[row];
+    for (int i = tid & 15; i < P; i += 16) {
+        const int ki = pr[i];
+        int rank = 0;
+        for (int j = 0; j < P; ++j) {
+            const int kj = pr[j];
+            rank += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
+        }
+        if (rank < K) {
+            const float nv = tqc_unkey(ki) - shift;
+            target[(long)row * K + rank] = r + live * g * nv;
+        }
+    }
+}
+
+// grid (row tiles, n critics), dynamic LDS 16 (K | 1) floats.  z [n, B, nq], t [B, K], w [B] or null (ones).  Per (row, quantile j) of the tile
+// one thread adds the K pair terms in ascending k: with d = t[k] - z, a = |tau_j - [d < 0]|,
+//   sl = sum a huber(d),  sg = sum a clamp(d, -1, 1),  sa = sum |d|;   coef [n, B, nq] = -(w scale) sg, scale = 1 / (B n nq K)
+// part_loss [n, row tiles]: the block's sum of w sl (thread sums in pair order, then ph_block_sum); part_abs [n, B]: the row's sum of sa over j
+__global__ __launch_bounds__(256) void sac_tqc_critic_loss_kernel(const float* __restrict__ z, const float* __restrict__ t, const float* __restrict__ w, int B,
+                                                                  int nq, int K, float scale, float* __restrict__ part_loss,
+                                                                  float* __restrict__ part_abs, float* __restrict__ coef) {
+    extern __shared__ __attribute__((aligned(16))) float tqc_t[];
+    __shared__ float ab[PH_TM * PH_HLD];
+    __shared__ float red[4];
+    const int c = blockIdx.y, row0 = blockIdx.x * PH_TM, tid = threadIdx.x, kld = K | 1;
+    for (int i = tid; i < PH_TM * K; i += 256) {
+        const int m = i / K, k = i - m * K;
+        tqc_t[m * kld + k] = row0 + m < B ? t[(long)(row0 + m) * K + k] : 0.f;
+    }
+    __syncthreads();
+    float s = 0.f;
+    for (int i = tid; i < PH_TM * nq; i += 256) {
+        const int m = i / nq, j = i - m * nq, row = row0 + m;
+        float sl = 0.f, sg = 0.f, sa = 0.f;
+        if (row < B) {
+            const long at = ((long)c * B + row) * nq + j;
+            const float zv = z[at], tau = ((float)j + 0.5f) / (float)nq, wr = w ? w[row] : 1.f;
+            const float* tr = tqc_t + m * kld;
+            for (int k = 0; k < K; ++k) {
+                const float d = tr[k] - zv, a = fabsf(d);
+                const float wt = d < 0.f ? 1.f - tau : tau;
+                sl += wt * (a <= 1.f ? 0.5f * d * d : a - 0.5f);
+                sg += wt * fminf(fmaxf(d, -1.f), 1.f);
+                sa += a;
+            }
+            coef[at] = -(wr * scale) * sg;
+            s += wr * sl;
+        }
+        ab[m * PH_HLD + j] = sa;
+    }
+    __syncthreads();
+    if (tid < PH_TM && row0 + tid < B) {
+        float a = 0.f;
+        for (int j = 0; j < nq; ++j) a += ab[tid * PH_HLD + j];
+        part_abs[(long)c * B + row0 + tid] = a;
+    }
+    s = ph_block_sum(s, red);
+    if (tid == 0) part_loss[blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// one workgroup.  loss = scale (the partial sums in index order per thread, then ph_block_sum);  td_abs [B] (or null) = inv_row sum_c part_abs[c, r]
+__global__ __launch_bounds__(256) void sac_tqc_loss_finish_kernel(const float* __restrict__ part_loss, int parts, const float* __restrict__ part_abs, int n,
+                                                                  int B, float scale, float inv_row, float* __restrict__ loss,
+                                                                  float* __restrict__ td_abs) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < parts; i += 256) s += part_loss[i];
+    s = ph_block_sum(s, red);
+    if (threadIdx.x == 0) loss[0] = s * scale;
+    if (td_abs != nullptr)
+        for (int r = threadIdx.x; r < B; r += 256) {
+            float a = 0.f;
+            for (int c = 0; c < n; ++c) a += part_abs[(long)c * B + r];
+            td_abs[r] = a * inv_row;
+        }
+}
+
+// one workgroup.  loss = mean_r (ent logp[r] - (sum_{c, j} z[c, r, j]) inv_nn), critics then quantiles ascending;  coef [B + n B nq]: dloss / dlogp
+// = ent / B, then dloss / dz = each = -1 / (B n nq) for every entry
+__global__ __launch_bounds__(256) void sac_tqc_actor_loss_kernel(const float* __restrict__ logp, const float* __restrict__ z, int n, int B, int nq,
+                                                                 float inv_nn, float each, float ent_coef, const float* __restrict__ log_ent_coef,
+                                                                 float* __restrict__ loss, float* __restrict__ coef) {
+    __shared__ float red[4];
+    const float invB = 1.f / (float)B, ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
+    float s = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) {
+        float v = 0.f;
+        for (int c = 0; c < n; ++c) {
+            const long at = ((long)c * B + r) * nq;
+            for (int j = 0; j < nq; ++j) {
+                v += z[at + j];
+                coef[B + at + j] = each;
+            }
+        }
+        s += ent * logp[r] - v * inv_nn;
+        coef[r] = invB * ent;
+    }
+    s = ph_block_sum(s, red);
+    if (threadIdx.x == 0) loss[0] = invB * s;
+}
+
+int sac_tqc_counts_ok(int n, int nq, int drop, char* why, size_t len) {
+    if (nq < 1 || nq > PH_HLD) { snprintf(why, len, "n_quantiles=%d (1 to %d)", nq, PH_HLD); return 0; }
+    if (drop < 0 || drop >= nq) { snprintf(why, len, "top_quantiles_to_drop=%d (0 <= drop < n_quantiles=%d)", drop, nq); return 0; }
+    if (n * nq > M3L_TQC_MAX_POOL) {
+        snprintf(why, len, "pool of n_critics n_quantiles = %d values per row (at most %d)", n * nq, M3L_TQC_MAX_POOL);
+        return 0;
+    }
+    return 1;
+}
+
+int sac_tqc_shape_ok(const m3l_tqc_desc* d, int B, char* why, size_t len) {
+    if (d == nullptr) { snprintf(why, len, "null descriptor"); return 0; }
+    if (!sac_ens_shape_ok(&d->ens, B, why, len)) return 0;
+    if (!sac_tqc_counts_ok(d->ens.n_critics, d->n_quantiles, d->top_quantiles_to_drop, why, len)) return 0;
+    if ((long)B * d->ens.n_critics * d->n_quantiles >= 2147483647L / 4) { snprintf(why, len, "B=%d rows are more than the kernels index", B); return 0; }
+    return 1;
+}
+
+// the ensemble's arguments and workspace layout with d z [n, B, nq] where it keeps d q [n, B]
+SacTqcArgs sac_tqc_args(const m3l_tqc_desc* d, int B, int parts) {
+    SacTqcArgs p;
+    memset(&p, 0, sizeof(p));
+    p.e = sac_ens_args(&d->ens, B, parts);
+    p.nq = d->n_quantiles;
+    p.K = p.e.n * (d->n_quantiles - d->top_quantiles_to_drop);
+    p.pool = p.e.n * p.nq;
+    p.pld = p.pool | 1;
+    p.e.total = ph_round4(p.e.dq_off + (long)p.e.n * B * p.nq);
+    return p;
+}
+
+#define TQC_POOL_LDS_MAX (PH_TM * (M3L_TQC_MAX_POOL + 1) * 4)
+int g_sac_tqc_inited = 0;
+int sac_tqc_init() {
+    if (g_sac_tqc_inited) return 0;
+    if (ph_allow_lds({(const void*)sac_tqc_critic_fwd_kernel, (const void*)sac_tqc_critic_bwd_kernel}, SAC_LDS_MAX)) return 2;
+    if (ph_allow_lds({(const void*)sac_tqc_td_target_kernel}, SAC_LDS_MAX + TQC_POOL_LDS_MAX)) return 2;
+    g_sac_tqc_inited = 1;
+    return 0;
+}
+
+int sac_tqc_loss_dims_ok(const char* who, int N, int B, int nq) {
+    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS && nq >= 1 && nq <= PH_HLD, "%s: N=%d B=%d n_quantiles=%d (1 <= N <= %d, B >= 1, 1 <= n_quantiles <= %d)",
+              who, N, B, nq, M3L_SAC_MAX_CRITICS, PH_HLD);
+    M3L_CHECK((long)B * N * nq < 2147483647L / 4, "%s: B=%d rows are more than the kernels index", who, B);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t m3l_tqc_ws_bytes(const m3l_tqc_desc* d, int B) {
+    char why[160];
+    if (!sac_tqc_shape_ok(d, B, why, sizeof(why))) return 256;
+    return (size_t)sac_tqc_args(d, B, 0).e.total * sizeof(float);
+}
+
+int m3l_tqc_critic_fwd(const m3l_tqc_desc* d, int B, const float* x, const float* actions, void* ws, float* z, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_tqc_shape_ok(d, B, why, sizeof(why)), "tqc_critic_fwd: unsupported shape: %s", why);
+    if (sac_ens_params_ok(&d->ens, SAC_CRITIC, "tqc_critic_fwd")) return 1;
+    M3L_CHECK(x && actions && z && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "tqc_critic_fwd: null argument, or x / ws not 16-byte aligned");
+    if (sac_tqc_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacTqcArgs p = sac_tqc_args(d, B, SAC_CRITIC);
+    ProfScope prof("tqc_critic_fwd", B, p.e.F, p.e.n, (double)p.e.n * ph_net_flops(p.e.qf[0], B, p.e.K0, p.nq), st, 4.0 * B * p.e.K0);
+    sac_tqc_critic_fwd_kernel<<<dim3(cdiv(B, PH_TM), p.e.n), 256, sac_ens_lds_bytes(p.e), st>>>(p, x, actions, (float*)ws, z);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_tqc_critic_bwd(const m3l_tqc_desc* d, int B, const float* dz, void* ws, float* dactions, const m3l_tqc_desc* grads, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_tqc_shape_ok(d, B, why, sizeof(why)), "tqc_critic_bwd: unsupported shape: %s", why);
+    if (sac_ens_params_ok(&d->ens, SAC_CRITIC, "tqc_critic_bwd")) return 1;
+    M3L_CHECK(grads == nullptr || (grads->ens.n_qf == d->ens.n_qf && grads->ens.n_critics == d->ens.n_critics),
+              "tqc_critic_bwd: the gradient descriptor has another layer or critic count");
+    if (grads != nullptr && sac_ens_params_ok(&grads->ens, SAC_CRITIC, "tqc_critic_bwd (gradients)")) return 1;
+    M3L_CHECK(ws && ph_aligned(ws), "tqc_critic_bwd: ws is null or not 16-byte aligned");
+    if (sac_tqc_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacTqcArgs p = sac_tqc_args(d, B, SAC_CRITIC);
+    float* w = (float*)ws;
+    {
+        ProfScope prof("tqc_critic_bwd_chain", B, p.e.F, p.e.n, (double)p.e.n * ph_net_flops(p.e.qf[0], B, p.e.K0, p.nq), st, 0.0);
+        sac_tqc_critic_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e), st>>>(p, dz, w, dactions);
+        M3L_LAUNCH_CHECK();
+    }
+    if (grads == nullptr) return 0;
+    return sac_ens_wgrad_launches(p.e, w, &grads->ens, st, p.nq);
+}
+
+int m3l_tqc_td_target(const m3l_tqc_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                      const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, float* target, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_tqc_shape_ok(d, B, why, sizeof(why)), "tqc_td_target: unsupported shape: %s", why);
+    if (sac_ens_params_ok(&d->ens, SAC_ACTOR | SAC_CRITIC, "tqc_td_target")) return 1;
+    M3L_CHECK(x_next && rewards && dones && target && ph_aligned(x_next), "tqc_td_target: null argument, or x_next not 16-byte aligned");
+    if (sac_tqc_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacTqcArgs p = sac_tqc_args(d, B, SAC_ACTOR | SAC_CRITIC);
+    ProfScope prof("tqc_td_target", B, p.e.F, p.e.n, ph_net_flops(p.e.pi, B, p.e.F, 2 * p.e.A) + (double)p.e.n * ph_net_flops(p.e.qf[0], B, p.e.K0, p.nq), st,
+                   4.0 * B * p.e.F);
+    sac_tqc_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e) + (size_t)PH_TM * p.pld * 4, st>>>(p, x_next, noise, rewards, dones, discounts,
+                                                                                                           gamma, ent_coef, log_ent_coef, target);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t m3l_tqc_loss_ws_bytes(int N, int B) {
+    if (N < 1 || N > M3L_SAC_MAX_CRITICS || B < 1) return 256;
+    return ((size_t)N * cdiv(B, PH_TM) + (size_t)N * B) * sizeof(float);
+}
+
+int m3l_tqc_critic_loss_fwd(const float* z, const float* target, const float* weights, int N, int B, int nq, int K, void* ws, float* loss, float* coef,
+                            float* td_abs, void* stream) {
+    if (sac_tqc_loss_dims_ok("tqc_critic_loss_fwd", N, B, nq)) return 1;
+    M3L_CHECK(K >= 1 && K <= M3L_TQC_MAX_POOL, "tqc_critic_loss_fwd: K=%d target quantiles per row (1 to %d)", K, M3L_TQC_MAX_POOL);
+    M3L_CHECK(z && target && ws && loss && coef, "tqc_critic_loss_fwd: null argument (weights and td_abs may be NULL)");
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = cdiv(B, PH_TM);
+    float* part_loss = (float*)ws;
+    float* part_abs = part_loss + (size_t)N * tiles;
+    const double pairs = (double)B * N * nq * K;
+    const float scale = (float)(1.0 / pairs), inv_row = (float)(1.0 / ((double)N * nq * K));
+    {
+        ProfScope prof("tqc_critic_loss_fwd", B, N * nq, K, 12.0 * pairs, st, 4.0 * ((double)B * K + 2.0 * B * N * nq));
+        sac_tqc_critic_loss_kernel<<<dim3(tiles, N), 256, (size_t)PH_TM * (K | 1) * 4, st>>>(z, target, weights, B, nq, K, scale, part_loss, part_abs, coef);
+        M3L_LAUNCH_CHECK();
+    }
+    ProfScope prof("tqc_critic_loss_finish", B, N, tiles, 1.0 * N * (tiles + B), st, 4.0 * N * (tiles + B));
+    sac_tqc_loss_finish_kernel<<<1, 256, 0, st>>>(part_loss, N * tiles, part_abs, N, B, scale, inv_row, loss, td_abs);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_tqc_actor_loss_fwd(const float* logp, const float* z, int N, int B, int nq, float ent_coef, const float* log_ent_coef, float* loss, float* coef,
+                           void* stream) {
+    if (sac_tqc_loss_dims_ok("tqc_actor_loss_fwd", N, B, nq)) return 1;
+    M3L_CHECK(logp && z && loss && coef, "tqc_actor_loss_fwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const double nn = (double)N * nq;
+    ProfScope prof("tqc_actor_loss_fwd", B, N, nq, (nn + 4.0) * B, st, (8.0 * nn + 8.0) * B);
+    sac_tqc_actor_loss_kernel<<<1, 256, 0, st>>>(logp, z, N, B, nq, (float)(1.0 / nn), (float)(-1.0 / (nn * B)), ent_coef, log_ent_coef, loss, coef);
     M3L_LAUNCH_CHECK();
     return 0;
 }

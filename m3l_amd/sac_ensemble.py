@@ -12,7 +12,7 @@ against the ensemble's mean), and SB3's `n_critics` of any value, which `MAESACP
 
 Neither SB3 nor a REDQ implementation is part of the reference tree: PARITY UNPINNED; tests/sac_ens_cases.py restates the rule in float64.
 `SACHead` and its refusal of any `n_critics` but 2 are unchanged; with N = 2, subset=None and q_reduce="min" the losses here have its bits.
-TQC (quantile critics) is not computed.  Everything is float32; there is no eager fallback.
+TQC (quantile critics) is `m3l_amd.tqc.TQCHead`.  Everything is float32; there is no eager fallback.
 
 DroQ critics (include/m3l_amd.h "SAC DroQ critics", Hiraoka et al. 2022): `SACEnsembleHead(critic_layer_norm=True, critic_dropout=p)` gives every
 critic and target critic hidden layers Linear -> Dropout(p) -> LayerNorm -> ReLU, and `q_values` / `td_target` then run the m3l_sac_droq_*

@@ -31,7 +31,14 @@ critics") at N = 2, the same shapes, p = 0.01, on
   ens10  the existing update of m3l_amd.SACEnsembleHead with N = 10 critics and a subset of 2, the REDQ recipe DroQ stands in for
 in alternating windows of one run.
 
-Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30] [--critics N [--subset M] [--q-reduce min|mean] | --droq]
+With --tqc it measures one critic update of the TQC head (EXPERIMENTS.md "SAC TQC critics"): `td_target` + `critic_loss` + backward at the same
+shapes, n_quantiles = 25, top_quantiles_to_drop_per_net = 2 and N = 2 critics (--critics N for another count, e.g. 10), on
+  tqc    m3l_amd.TQCHead
+  eager  the float32 torch restatement of tests/tqc_cases.py (torch.sort over the pooled quantiles, the 4-D broadcast of the quantile-Huber loss)
+  ens2   the same three calls of m3l_amd.SACEnsembleHead with N = 2 critics, the scalar-critic update TQC replaces
+in alternating windows of one run.
+
+Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30] [--critics N [--subset M] [--q-reduce min|mean] | --droq | --tqc [--critics N]]
 (one JSON line on stdout)"""
 import argparse
 import json
@@ -48,6 +55,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import sac_cases as SC  # noqa: E402
 import sac_ens_cases as EC  # noqa: E402
 import droq_cases as DC  # noqa: E402
+import tqc_cases as TC  # noqa: E402
 import m3l_amd  # noqa: E402
 from m3l_amd import sac as SH  # noqa: E402
 from policy_head_bench import alternate, counted, entry_points  # noqa: E402
@@ -225,6 +233,57 @@ def droq(a):
                       "critic_update": res}))
 
 
+def tqc(a):
+    """The --tqc mode: see the module docstring."""
+    N, nq, drop, B = a.critics or 2, 25, 2, 256
+    c = TC.make_inputs(ARCH, N, nq, drop, B, seed=9)
+    K = c["K"]
+    net_arch = dict(pi=list(ARCH[1]), qf=list(ARCH[2]))
+    head = m3l_amd.TQCHead(ARCH[0], ARCH[3], net_arch=net_arch, n_critics=N, n_quantiles=nq, top_quantiles_to_drop_per_net=drop)
+    head.load_state_dict({k: torch.from_numpy(v) for k, v in c["params"].items()})
+    head = head.to(DEV)
+    ce = EC.make_inputs(ARCH, 2, B, seed=9)
+    ens = m3l_amd.SACEnsembleHead(ARCH[0], ARCH[3], net_arch=net_arch, n_critics=2)
+    ens.load_state_dict({k: torch.from_numpy(v) for k, v in ce["params"].items()})
+    ens = ens.to(DEV)
+    P = dict(head.named_parameters())
+    t = {k: torch.from_numpy(c[k]).to(DEV) for k in ("x", "x_next", "noise_pi", "noise_next", "a_replay", "rewards", "dones")}
+    log_ent = torch.tensor([c["log_ent_coef"]], dtype=torch.float32, device=DEV)
+    gamma = c["gamma"]
+
+    def zero(h):
+        for q in h.parameters():
+            q.grad = None
+
+    def hip_update(h):
+        zero(h)
+        target = h.td_target(t["x_next"], t["rewards"], t["dones"], gamma, log_ent_coef=log_ent, noise=t["noise_next"])
+        loss = h.critic_loss(t["x"], t["a_replay"], target)
+        loss.backward()
+        return loss
+
+    def eager_update():
+        zero(head)
+        with torch.no_grad():
+            n = SC.actor_forward(P, t["x_next"], t["noise_next"])
+            zn, _ = TC.critic_forward(P, "critic_target", t["x_next"], n["actions"], N)
+            target = TC.truncated_target(zn, n["log_prob"], t["rewards"], t["dones"], gamma, torch.exp(log_ent), K)
+        z, _ = TC.critic_forward(P, "critic", t["x"], t["a_replay"], N)
+        loss = TC.quantile_huber_loss(z, target)
+        loss.backward()
+        return loss
+    fns = {"tqc": lambda: hip_update(head), "eager": eager_update, "ens2": lambda: hip_update(ens)}
+    res, last = alternate(fns, a.iters, a.warmup, a.rounds)
+    for name, fn in fns.items():
+        res[name].update(counted(fn))
+        res[name]["result_sum"] = float(last[name].detach().float().sum())
+    res["tqc"]["entry_points"] = entry_points(fns["tqc"])
+    res["tqc_over_eager_call"] = round(res["tqc"]["call_us"] / res["eager"]["call_us"], 3)
+    res["tqc_over_ens2_call"] = round(res["tqc"]["call_us"] / res["ens2"]["call_us"], 3)
+    print(json.dumps({"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}, "critics": N, "n_quantiles": nq,
+                      "top_quantiles_to_drop_per_net": drop, "K": K, "B": B, "critic_update": res}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=500, help="calls per timed window of (a); (b) takes ten times as many")
@@ -234,11 +293,14 @@ def main():
     ap.add_argument("--subset", type=int, default=2, help="with --critics: critics in the target's minimum (N = 2: both)")
     ap.add_argument("--q-reduce", choices=("min", "mean"), default="mean", help="with --critics: the actor loss's reduction over the critics")
     ap.add_argument("--droq", action="store_true", help="measure a critic update of the DroQ critics (N = 2, p = 0.01) against eager torch and the N = 10 ensemble")
+    ap.add_argument("--tqc", action="store_true", help="measure a critic update of the TQC head (n_quantiles 25, 2 dropped per net; --critics N, default 2) against eager torch and the N = 2 ensemble")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sac_head_bench: no GPU")
     if a.droq:
         return droq(a)
+    if a.tqc:
+        return tqc(a)
     if a.critics is not None:
         return ensemble(a)
     out = {"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}}
