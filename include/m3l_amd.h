@@ -949,6 +949,48 @@ int m3l_tqc_critic_loss_fwd(const float* z, const float* target, const float* we
 int m3l_tqc_actor_loss_fwd(const float* logp, const float* z, int N, int B, int n_quantiles, float ent_coef, const float* log_ent_coef, float* loss,
                            float* coef, void* stream);
 
+/* ---- TD3 head (ABI 422): a deterministic actor over the ensemble's critics, the head of DDPG (Lillicrap et al. 2016), TD3 (Fujimoto et al.
+ * 2018; SB3's `TD3Policy`) and DrQ-v2 (Yarats et al. 2022).  Neither SB3 nor a DrQ-v2 implementation is part of the reference tree: the rule is
+ * stated here and restated in float64 by tests/td3_cases.py, parity unpinned.  The sections above and their results do not change.  float32
+ * throughout.  The descriptor is m3l_sac_ens_desc as it is: the actor's hidden layers in pi_*, the action Linear [A, last pi width or F] in
+ * mu_weight / mu_bias, log_std_* NULL (never read); N = n_critics from 1 to M3L_SAC_MAX_CRITICS.
+ *   1. mu(x) = tanh(Linear_A(ReLU-MLP(x))), 0 to 3 hidden layers.
+ *   2. smooth(a, n, sigma, c) = clamp(a + clamp(sigma n, -c, c), -1, 1); sigma >= 0; c <= 0: no inner clamp.  sigma = 0, noise NULL, or a
+ *      noise of zeros each give the bits of a.  One device function serves the actor forward and the target.
+ *   3. actions = smooth(mu(x), noise, sigma, c); d pre = d actions (1 - tanh(pre)^2) in the cancellation-free form 4 e / (1 + e)^2,
+ *      e = exp(-2 |pre|), on the stored pre-activation; both clamps pass the gradient straight through (DrQ-v2's TruncatedNormal.sample(clip=)).
+ *      The gradient goes to x and to the actor's parameters.
+ *   4. target_q = r + (1 - done) g min_c q_target_c(x', a'),  a' = smooth(mu(x'), noise, sigma, c),  the minimum by fminf over all N critics of
+ *      the descriptor, ascending;  g = gamma or discounts[row] as in m3l_sac_td_target_rows (a constant discounts gives the scalar's bits).
+ *      The descriptor carries whichever actor the caller puts in: the target actor (TD3, DDPG) or the online one (DrQ-v2).
+ *   5. critic_loss = sum_c mean_r w_r (q_c - t)^2 (SB3's TD3 line, without the SAC line's 0.5);  coef[c, r] = 2 w_r (q_c - t) / B;
+ *      td_abs[r] = (sum_c |q_c - t|) (1 / N).  The kernel is m3l_sac_ens_critic_loss_fwd's with the finished loss and every coefficient
+ *      multiplied by 2: bit for bit twice that entry's results, no sum in another order.
+ *   6. actor_loss = -mean_r reduce_c q_c;  reduce 0 (min): the lowest index among equal minima takes the row's gradient -1 / B;  reduce 1
+ *      (mean): (sum_c q_c) (1 / N), critics ascending, dq_c = -1 / (N B).  SB3's q1_forward is N = 1 on a one-critic descriptor.
+ * The critics' forward and backward are m3l_sac_ens_critic_fwd / _bwd, the backward of both losses m3l_sac_ens_loss_bwd (n = N B), the Polyak
+ * update of both target nets m3l_op_ema.  policy_delay and every noise schedule are the caller's loop.
+ * Launches: actor_fwd 1 (grid: row tiles of 16); actor_bwd 1 chain + 1 grouped weight-gradient launch; td_target 1 (per row tile: the actor,
+ * the smoothing in LDS, the N critics on [x' | a'] in LDS); each loss 1 forward and 1 backward.  No float atomics, every sum in a fixed order:
+ * two runs give the same bits.
+ * Limits: the ensemble's.  Anything else, a sigma that is negative or not finite, or a NULL pointer that is not named optional is an error and
+ * nothing is written.  ws: m3l_td3_ws_bytes bytes (the actor's activations, pre and d pre), one per actor forward that a backward follows. */
+size_t m3l_td3_ws_bytes(const m3l_sac_ens_desc* head, int B);
+/* actions [B, A] is written; noise [B, A] or NULL (zero); clip <= 0: no inner clamp; ws NULL when no backward follows */
+int m3l_td3_actor_fwd(const m3l_sac_ens_desc* head, int B, const float* x, const float* noise, float sigma, float clip, void* ws, float* actions,
+                      void* stream);
+/* dactions [B, A]; dx [B, F] and the gradients of the hidden layers and of mu_weight / mu_bias (the buffers `grads` names) are written */
+int m3l_td3_actor_bwd(const m3l_sac_ens_desc* head, int B, const float* x, const float* dactions, void* ws, float* dx, const m3l_sac_ens_desc* grads,
+                      void* stream);
+/* target_q [B] is written; the descriptor's critics are the target critics; discounts [B] or NULL (gamma for every row) */
+int m3l_td3_td_target(const m3l_sac_ens_desc* head, int B, const float* x_next, const float* noise, float sigma, float clip, const float* rewards,
+                      const float* dones, const float* discounts, float gamma, float* target_q, void* stream);
+/* the arguments of m3l_sac_ens_critic_loss_fwd; loss[1], coef [N, B] and td_abs [B] (when not NULL) are written */
+int m3l_td3_critic_loss_fwd(const float* q, const float* target_q, const float* weights, int N, int B, float* loss, float* coef, float* td_abs,
+                            void* stream);
+/* q [N, B]; reduce: 0 = min, 1 = mean.  loss[1] and coef [N, B] = dloss/dq are written; the backward is m3l_sac_ens_loss_bwd */
+int m3l_td3_actor_loss_fwd(const float* q, int N, int B, int reduce, float* loss, float* coef, void* stream);
+
 /* ---- device-resident rollout (ABI 411): what PPO_MAE.train does between `rollout_buffer` and `self.mae(x)` for every minibatch, with the rollout
  * kept in device memory in the layout the vec-env fills it in, (T, n_envs, ...).  Nothing is swapped or flattened: idx [B] (int64) holds flat
  * indices of the reference's swapped order, j -> env = j / T, t = j % T, store row t * n_envs + env            models/ppo_dino_cat_mae.py:25-29

@@ -312,6 +312,13 @@ _SIGS = {
     "m3l_tqc_loss_ws_bytes": (c_sz, [c_i, c_i]),
     "m3l_tqc_critic_loss_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "m3l_tqc_actor_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_float, c_p, c_p, c_p, c_p]),
+    # TD3 head (ABI 422): the deterministic actor, the smoothed TD target, the critic loss without the 0.5, the actor loss; on m3l_sac_ens_desc
+    "m3l_td3_ws_bytes": (c_sz, [C.POINTER(SacEnsDesc), c_i]),
+    "m3l_td3_actor_fwd": (c_i, [C.POINTER(SacEnsDesc), c_i, c_p, c_p, C.c_float, C.c_float, c_p, c_p, c_p]),
+    "m3l_td3_actor_bwd": (c_i, [C.POINTER(SacEnsDesc), c_i, c_p, c_p, c_p, c_p, C.POINTER(SacEnsDesc), c_p]),
+    "m3l_td3_td_target": (c_i, [C.POINTER(SacEnsDesc), c_i, c_p, c_p, C.c_float, C.c_float, c_p, c_p, c_p, C.c_float, c_p, c_p]),
+    "m3l_td3_critic_loss_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "m3l_td3_actor_loss_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

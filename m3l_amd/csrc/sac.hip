@@ -32,6 +32,17 @@
 // quantiles.  The TD target pools the n nq target quantiles of a row in LDS and ranks them by (key, index), NaN last, so the K smallest go out
 // in one launch without data-dependent addressing; the quantile-Huber loss runs on a grid (row tiles, critics) with per-block partial sums
 // that a one-workgroup launch adds in index order.
+//
+// TD3 head ("TD3 head", the td3_* kernels and m3l_td3_* entries at the end): a deterministic actor tanh(Linear_A(ReLU-MLP(x))) over the ensemble's
+// critics, for DDPG, TD3 and DrQ-v2.
+//   actor fwd    one launch, grid (row tiles of 16): x -> LDS, the hidden walk, the [16, A] head tile, tanh, td3_smooth (the clipped noise and
+//                the clamp to [-1, 1]); with a workspace the post-ReLU activations and the head's pre-activation stay for the backward
+//   actor bwd    chain kernel per row tile: d actions -> the tanh gate on the stored pre-activation (both clamps pass the gradient straight
+//                through) -> the head -> the hidden layers -> dx; then the grouped weight-gradient launch
+//   td target    one launch per row tile: the actor the descriptor carries on x' in LDS, td3_smooth, a' handed to all n target critics in LDS,
+//                their minimum, the Bellman line
+//   losses       the critic loss is the ensemble's kernel with the loss and the coefficients doubled (SB3's TD3 line has no 0.5); the actor
+//                loss is -mean_r of min_c or mean_c, one workgroup; "first" is n = 1 on a one-critic descriptor
 #include <math.h>
 #include <string.h>
 
@@ -439,6 +450,8 @@ __global__ __launch_bounds__(256) void sac_ens_td_target_kernel(SacEnsArgs p, co
 // one workgroup.  loss = 0.5 sum_c mean_r w[r] (q[c, r] - t[r])^2;  coef [n, B] = w[r] d / B;  td_abs [B] (or null) = (sum_c |d_c|) (1 / n).
 // w null: 1.  Per critic the rows add up as in sac_critic_loss_w_kernel; the n means then add up from the last critic to the first, each fused
 // onto the sum behind it: fma(s_0, 1/B, fma(s_1, 1/B, ... s_{n-1} / B)), which at n = 2 is what sac_critic_loss_kernel computes.
+// TWICE (the TD3 head's line, without the 0.5): the finished loss and every coefficient times 2, an exact scale behind the same arithmetic.
+template <bool TWICE>
 __global__ __launch_bounds__(256) void sac_ens_critic_loss_kernel(const float* __restrict__ q, const float* __restrict__ t, const float* __restrict__ w, int n,
                                                                   int B, float* __restrict__ loss, float* __restrict__ coef, float* __restrict__ td_abs) {
     __shared__ float red[4];
@@ -454,7 +467,8 @@ __global__ __launch_bounds__(256) void sac_ens_critic_loss_kernel(const float* _
             if (c >= n) break;
             const float d = __fsub_rn(q[(long)c * B + r], tr), wd = __fmul_rn(d, wr);
             s[c] = fmaf(d, wd, s[c]);
-            coef[(long)c * B + r] = __fmul_rn(invB, wd);
+            const float cf = __fmul_rn(invB, wd);
+            coef[(long)c * B + r] = TWICE ? __fmul_rn(2.f, cf) : cf;
             ab = c == 0 ? fabsf(d) : __fadd_rn(ab, fabsf(d));
         }
         if (td_abs) td_abs[r] = __fmul_rn(invn, ab);
@@ -466,7 +480,8 @@ __global__ __launch_bounds__(256) void sac_ens_critic_loss_kernel(const float* _
         const float sc = ph_block_sum(s[c], red);
         tot = c == n - 1 ? __fmul_rn(invB, sc) : fmaf(invB, sc, tot);
     }
-    if (threadIdx.x == 0) loss[0] = __fmul_rn(0.5f, tot);
+    const float half = __fmul_rn(0.5f, tot);
+    if (threadIdx.x == 0) loss[0] = TWICE ? __fmul_rn(2.f, half) : half;
 }
 
 // one workgroup.  reduce 0: loss = mean_r (ent logp[r] - min_c q[c, r]), the lowest index among equal minima takes the row's gradient -1 / B;
@@ -937,7 +952,7 @@ int m3l_sac_ens_critic_loss_fwd(const float* q, const float* target_q, const flo
     M3L_CHECK(q && target_q && loss && coef, "sac_ens_critic_loss_fwd: null argument (weights and td_abs may be NULL)");
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("sac_ens_critic_loss_fwd", B, N, 0, 7.0 * N * B, st, (8.0 * N + 12.0) * B);
-    sac_ens_critic_loss_kernel<<<1, 256, 0, st>>>(q, target_q, weights, N, B, loss, coef, td_abs);
+    sac_ens_critic_loss_kernel<false><<<1, 256, 0, st>>>(q, target_q, weights, N, B, loss, coef, td_abs);
     M3L_LAUNCH_CHECK();
     return 0;
 }
@@ -1669,6 +1684,276 @@ int m3l_tqc_actor_loss_fwd(const float* logp, const float* z, int N, int B, int 
     const double nn = (double)N * nq;
     ProfScope prof("tqc_actor_loss_fwd", B, N, nq, (nn + 4.0) * B, st, (8.0 * nn + 8.0) * B);
     sac_tqc_actor_loss_kernel<<<1, 256, 0, st>>>(logp, z, N, B, nq, (float)(1.0 / nn), (float)(-1.0 / (nn * B)), ent_coef, log_ent_coef, loss, coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- TD3 head (include/m3l_amd.h "TD3 head"): a deterministic actor tanh(Linear_A(ReLU-MLP(x))) over the ensemble's critics, for DDPG, TD3 and
+// DrQ-v2.  The descriptor is the ensemble's with the action Linear in mu_weight / mu_bias and log_std_* NULL.
+namespace {
+
+// what the actor's nodes add to the ensemble's arguments: in e.pi the offsets of the actor's own workspace (m3l_td3_ws_bytes), then the head's
+// pre-activation and its gradient, [B, A] each
+struct Td3Args {
+    SacEnsArgs e;
+    long pre_off, dpre_off, total;
+};
+static_assert(sizeof(Td3Args) <= 4096, "the TD3 arguments travel by value: the kernel-argument segment holds 4 KB");
+
+// clamp(a + clamp(sigma n, -c, c), -1, 1); c <= 0: no inner clamp.  A perturbation of zero returns a itself, whatever its sign bit.
+__device__ __forceinline__ float td3_smooth(float a, float n, float sigma, float clip) {
+    float e = __fmul_rn(sigma, n);
+    if (clip > 0.f) e = fminf(fmaxf(e, -clip), clip);
+    return e == 0.f ? a : fminf(fmaxf(__fadd_rn(a, e), -1.f), 1.f);
+}
+
+// The actor on the rows row0 .. row0 + 15: leaves smooth(tanh(pre), noise) in hmu [16, PH_HLD] (columns < A) and, for the rows below B, in
+// actions_out when given; with a workspace the post-ReLU activations and pre stay for the backward.  noise null: zero.  Ends with a barrier.
+__device__ void td3_actor_tile(const SacEnsArgs& p, const float* __restrict__ x, const float* __restrict__ noise, float sigma, float clip, int row0,
+                               float* bufa, float* bufb, float* hmu, float* __restrict__ ws, long pre_off, float* __restrict__ actions_out) {
+    const int tid = threadIdx.x, B = p.B, A = p.A;
+    float* cur = bufa;
+    float* nxt = bufb;
+    ph_load_x(x, p.F, row0, B, cur, p.ld);
+    __syncthreads();
+    const int K = ph_fwd_walk<PH_ACT_RELU>(p.pi, p.F, cur, nxt, p.ld, ws, row0, B);
+    ph_fwd_layer<PH_ACT_NONE>(cur, p.ld, K, p.mu_W, p.mu_b, A, hmu, PH_HLD, nullptr, row0, B);
+    __syncthreads();
+    for (int e = tid; e < PH_TM * A; e += 256) {
+        const int m = e / A, j = e - m * A, row = row0 + m;
+        const float pre = hmu[m * PH_HLD + j];
+        const float n = (noise != nullptr && row < B) ? noise[(long)row * A + j] : 0.f;
+        const float a = td3_smooth(tanhf(pre), n, sigma, clip);
+        if (row < B) {
+            if (actions_out) actions_out[(long)row * A + j] = a;
+            if (ws) ws[pre_off + (long)row * A + j] = pre;
+        }
+        hmu[m * PH_HLD + j] = a;
+    }
+    __syncthreads();
+}
+
+// grid (row tiles)
+__global__ __launch_bounds__(256) void td3_actor_fwd_kernel(Td3Args p, const float* __restrict__ x, const float* __restrict__ noise, float sigma, float clip,
+                                                            float* __restrict__ ws, float* __restrict__ actions) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD];
+    td3_actor_tile(p.e, x, noise, sigma, clip, blockIdx.x * PH_TM, sac_lds, sac_lds + PH_TM * p.e.ld, hmu, ws, p.pre_off, actions);
+}
+
+// grid (row tiles).  dactions [B, A].  d pre = d actions (1 - tanh(pre)^2): both clamps pass the gradient straight through
+__global__ __launch_bounds__(256) void td3_actor_bwd_kernel(Td3Args p, const float* __restrict__ dactions, float* __restrict__ ws, float* __restrict__ dx) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float tmu[PH_TM * PH_HLD];
+    const SacEnsArgs& e = p.e;
+    float* cur = sac_lds;
+    float* nxt = sac_lds + PH_TM * e.ld;
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = e.B, A = e.A;
+    for (int i = tid; i < PH_TM * PH_HLD; i += 256) {
+        const int m = i >> 6, j = i & 63, row = row0 + m;
+        float dm = 0.f;
+        if (j < A && row < B) {
+            const long at = (long)row * A + j;
+            dm = dactions[at] * sac_one_minus_tanh2(ws[p.pre_off + at]);
+            ws[p.dpre_off + at] = dm;
+        }
+        tmu[i] = dm;
+    }
+    __syncthreads();
+    const int hv = (A + 7) & ~7;
+    if (e.pi.n == 0) {
+        ph_bwd_layer<PH_ACT_NONE>(tmu, PH_HLD, hv, e.mu_W, A, e.F, nullptr, nullptr, 0, dx, false, row0, B);
+        return;
+    }
+    const int l = e.pi.n - 1;
+    int N = e.pi.w[l], valid = N;
+    ph_bwd_layer<PH_ACT_RELU>(tmu, PH_HLD, hv, e.mu_W, A, N, ws + e.pi.h_off[l], cur, e.ld, ws + e.pi.d_off[l], false, row0, B);
+    __syncthreads();
+    const float* W = e.pi.W[l];
+    ph_bwd_walk<PH_ACT_RELU>(e.pi, l - 1, cur, nxt, e.ld, valid, W, N, ws, row0, B);      // the layers below the one the head feeds
+    ph_bwd_layer<PH_ACT_NONE>(cur, e.ld, valid, W, N, e.F, nullptr, nullptr, 0, dx, false, row0, B);
+}
+
+// grid (row tiles).  The actor of p is whichever the caller put in (the target actor, or the online one); the critics are the target critics.
+// a' = smooth(actor(x'), noise) stays in LDS and goes to all n critics, ascending; discounts as in sac_td_target_kernel.
+__global__ __launch_bounds__(256) void td3_td_target_kernel(SacEnsArgs p, const float* __restrict__ x, const float* __restrict__ noise, float sigma, float clip,
+                                                            const float* __restrict__ rewards, const float* __restrict__ dones,
+                                                            const float* __restrict__ discounts, float gamma, float* __restrict__ target_q) {
+    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
+    __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD], hs[PH_TM * PH_HLD];
+    __shared__ float q_sh[M3L_SAC_MAX_CRITICS][PH_TM];
+    float* bufa = sac_lds;
+    float* bufb = sac_lds + PH_TM * p.ld;
+    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B;
+    td3_actor_tile(p, x, noise, sigma, clip, row0, bufa, bufb, hmu, nullptr, 0, nullptr);
+    for (int c = 0; c < p.n; ++c) {
+        sac_build_xa(p, x, hmu, PH_HLD, row0, bufa);
+        __syncthreads();
+        sac_critic_tile(p, c, row0, bufa, bufb, hs, nullptr);
+        if (tid < PH_TM) q_sh[c][tid] = hs[tid * PH_HLD];
+        __syncthreads();
+    }
+    if (tid < PH_TM && row0 + tid < B) {
+        const int row = row0 + tid;
+        float m = q_sh[0][tid];
+        for (int c = 1; c < p.n; ++c) m = fminf(m, q_sh[c][tid]);
+        const float g = discounts ? discounts[row] : gamma;
+        target_q[row] = rewards[row] + (1.f - dones[row]) * g * m;
+    }
+}
+
+// one workgroup.  reduce 0: loss = -mean_r min_c q[c, r], the lowest index among equal minima takes the row's gradient -1 / B; reduce 1:
+// loss = -mean_r (sum_c q[c, r]) (1 / n), critics ascending, every critic takes -1 / (n B).  coef [n, B] = dloss / dq.
+__global__ __launch_bounds__(256) void td3_actor_loss_kernel(const float* __restrict__ q, int n, int B, int reduce, float* __restrict__ loss,
+                                                             float* __restrict__ coef) {
+    __shared__ float red[4];
+    const float invB = 1.f / (float)B, invn = 1.f / (float)n;
+    const float each = -1.f / ((float)n * (float)B);
+    float s = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) {
+        float v = q[r];
+        int at = 0;
+        for (int c = 1; c < n; ++c) {
+            const float qc = q[(long)c * B + r];
+            if (reduce) {
+                v = __fadd_rn(v, qc);
+            } else if (qc < v) {
+                v = qc;
+                at = c;
+            }
+        }
+        if (reduce) v = __fmul_rn(v, invn);
+        s = __fadd_rn(s, v);
+        for (int c = 0; c < n; ++c) coef[(long)c * B + r] = reduce ? each : (c == at ? -invB : 0.f);
+    }
+    s = ph_block_sum(s, red);
+    if (threadIdx.x == 0) loss[0] = -__fmul_rn(invB, s);
+}
+
+// the ensemble's arguments with the actor's workspace laid out behind offset 0: activations and gradients of the hidden layers, pre, d pre
+Td3Args td3_args(const m3l_sac_ens_desc* d, int B, int parts) {
+    Td3Args p;
+    memset(&p, 0, sizeof(p));
+    p.e = sac_ens_args(d, B, parts);
+    int widest = 0;
+    long off = ph_layout(p.e.pi, d->n_pi, d->pi_width, B, 0, widest);
+    p.pre_off = off;
+    off = ph_round4(off + (long)B * p.e.A);
+    p.dpre_off = off;
+    off = ph_round4(off + (long)B * p.e.A);
+    p.total = off;
+    return p;
+}
+
+// the actor's pointers of a TD3 descriptor: the hidden layers and the action Linear; log_std_* is not read
+int td3_actor_ok(const m3l_sac_ens_desc* d, const char* who) {
+    M3L_CHECK(d->mu_weight && d->mu_bias && ph_aligned(d->mu_weight) && ph_ptrs_ok(d->n_pi, d->pi_weight, d->pi_bias),
+              "%s: an actor pointer of the descriptor is null or a weight is not 16-byte aligned", who);
+    return 0;
+}
+
+int td3_noise_ok(const char* who, float sigma) {
+    M3L_CHECK(sigma >= 0.f && sigma <= 3.0e38f, "%s: sigma=%g (a finite value >= 0)", who, (double)sigma);
+    return 0;
+}
+
+int g_td3_inited = 0;
+int td3_init() {
+    if (g_td3_inited) return 0;
+    if (ph_allow_lds({(const void*)td3_actor_fwd_kernel, (const void*)td3_actor_bwd_kernel, (const void*)td3_td_target_kernel}, SAC_LDS_MAX)) return 2;
+    g_td3_inited = 1;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t m3l_td3_ws_bytes(const m3l_sac_ens_desc* d, int B) {
+    char why[160];
+    if (!sac_ens_shape_ok(d, B, why, sizeof(why))) return 256;
+    const size_t n = (size_t)td3_args(d, B, 0).total * sizeof(float);
+    return n ? n : 256;
+}
+
+int m3l_td3_actor_fwd(const m3l_sac_ens_desc* d, int B, const float* x, const float* noise, float sigma, float clip, void* ws, float* actions,
+                      void* stream) {
+    char why[160];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "td3_actor_fwd: unsupported shape: %s", why);
+    if (td3_actor_ok(d, "td3_actor_fwd") || td3_noise_ok("td3_actor_fwd", sigma)) return 1;
+    M3L_CHECK(x && actions && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "td3_actor_fwd: null argument, or x / ws not 16-byte aligned");
+    if (td3_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const Td3Args p = td3_args(d, B, SAC_ACTOR);
+    ProfScope prof("td3_actor_fwd", B, p.e.F, p.e.A, ph_net_flops(p.e.pi, B, p.e.F, p.e.A), st, 4.0 * B * p.e.F);
+    td3_actor_fwd_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e), st>>>(p, x, noise, sigma, clip, (float*)ws, actions);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_td3_actor_bwd(const m3l_sac_ens_desc* d, int B, const float* x, const float* dactions, void* ws, float* dx, const m3l_sac_ens_desc* grads,
+                      void* stream) {
+    char why[160];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "td3_actor_bwd: unsupported shape: %s", why);
+    if (td3_actor_ok(d, "td3_actor_bwd")) return 1;
+    M3L_CHECK(grads != nullptr && grads->n_pi == d->n_pi, "td3_actor_bwd: the gradient descriptor is null or has another layer count");
+    if (td3_actor_ok(grads, "td3_actor_bwd (gradients)")) return 1;
+    M3L_CHECK(x && dactions && ws && dx && ph_aligned(x) && ph_aligned(ws) && ph_aligned(dx),
+              "td3_actor_bwd: null argument, or x / ws / dx not 16-byte aligned");
+    if (td3_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const Td3Args p = td3_args(d, B, SAC_ACTOR);
+    float* w = (float*)ws;
+    PhWgrad q;
+    memset(&q, 0, sizeof(q));
+    q.B = B;
+    ph_add_net(q, p.e.pi, w, x, p.e.F, p.e.F, grads->pi_weight, grads->pi_bias, p.e.A, {{w + p.dpre_off, grads->mu_weight, grads->mu_bias}});
+    {
+        ProfScope prof("td3_actor_bwd_chain", B, p.e.F, p.e.A, ph_net_flops(p.e.pi, B, p.e.F, p.e.A), st, 4.0 * B * p.e.F);
+        td3_actor_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p.e), st>>>(p, dactions, w, dx);
+        M3L_LAUNCH_CHECK();
+    }
+    ProfScope prof("td3_actor_wgrad", B, q.items, p.e.A, ph_net_flops(p.e.pi, B, p.e.F, p.e.A), st, 0.0);
+    sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_td3_td_target(const m3l_sac_ens_desc* d, int B, const float* x_next, const float* noise, float sigma, float clip, const float* rewards,
+                      const float* dones, const float* discounts, float gamma, float* target_q, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "td3_td_target: unsupported shape: %s", why);
+    if (td3_actor_ok(d, "td3_td_target") || sac_ens_params_ok(d, SAC_CRITIC, "td3_td_target") || td3_noise_ok("td3_td_target", sigma)) return 1;
+    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "td3_td_target: null argument, or x_next not 16-byte aligned");
+    if (td3_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacEnsArgs p = sac_ens_args(d, B, SAC_ACTOR | SAC_CRITIC);
+    ProfScope prof("td3_td_target", B, p.F, p.n, ph_net_flops(p.pi, B, p.F, p.A) + sac_ens_critic_flops(p, p.n), st, 4.0 * B * p.F);
+    td3_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p), st>>>(p, x_next, noise, sigma, clip, rewards, dones, discounts, gamma, target_q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_td3_critic_loss_fwd(const float* q, const float* target_q, const float* weights, int N, int B, float* loss, float* coef, float* td_abs,
+                            void* stream) {
+    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "td3_critic_loss_fwd: N=%d B=%d (1 <= N <= %d, B >= 1)", N, B, M3L_SAC_MAX_CRITICS);
+    M3L_CHECK(q && target_q && loss && coef, "td3_critic_loss_fwd: null argument (weights and td_abs may be NULL)");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("td3_critic_loss_fwd", B, N, 0, 7.0 * N * B, st, (8.0 * N + 12.0) * B);
+    sac_ens_critic_loss_kernel<true><<<1, 256, 0, st>>>(q, target_q, weights, N, B, loss, coef, td_abs);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_td3_actor_loss_fwd(const float* q, int N, int B, int reduce, float* loss, float* coef, void* stream) {
+    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "td3_actor_loss_fwd: N=%d B=%d (1 <= N <= %d, B >= 1)", N, B, M3L_SAC_MAX_CRITICS);
+    M3L_CHECK(reduce == 0 || reduce == 1, "td3_actor_loss_fwd: reduce=%d (0 = min, 1 = mean)", reduce);
+    M3L_CHECK(q && loss && coef, "td3_actor_loss_fwd: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("td3_actor_loss_fwd", B, N, reduce, (2.0 * N + 2.0) * B, st, 8.0 * N * B);
+    td3_actor_loss_kernel<<<1, 256, 0, st>>>(q, N, B, reduce, loss, coef);
     M3L_LAUNCH_CHECK();
     return 0;
 }

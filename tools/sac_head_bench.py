@@ -38,7 +38,14 @@ shapes, n_quantiles = 25, top_quantiles_to_drop_per_net = 2 and N = 2 critics (-
   ens2   the same three calls of m3l_amd.SACEnsembleHead with N = 2 critics, the scalar-critic update TQC replaces
 in alternating windows of one run.
 
-Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30] [--critics N [--subset M] [--q-reduce min|mean] | --droq | --tqc [--critics N]]
+With --td3 it measures the TD3 head (EXPERIMENTS.md "TD3 head") at the same shapes and N = 2: a critic update (`td_target` with SB3's target-policy
+smoothing, `critic_loss`, backward) and an actor update (`actor_loss` with q_reduce="first", backward), on
+  td3    m3l_amd.TD3Head
+  eager  the float32 torch restatement of tests/td3_cases.py
+  ens2   the same calls of m3l_amd.SACEnsembleHead with N = 2 critics (its actor loss with the min reduction), the stochastic head's update
+in alternating windows of one run.
+
+Usage: python tools/sac_head_bench.py [--iters 500] [--rounds 5] [--warmup 30] [--critics N [--subset M] [--q-reduce min|mean] | --droq | --tqc [--critics N] | --td3]
 (one JSON line on stdout)"""
 import argparse
 import json
@@ -56,6 +63,7 @@ import sac_cases as SC  # noqa: E402
 import sac_ens_cases as EC  # noqa: E402
 import droq_cases as DC  # noqa: E402
 import tqc_cases as TC  # noqa: E402
+import td3_cases as T3C  # noqa: E402
 import m3l_amd  # noqa: E402
 from m3l_amd import sac as SH  # noqa: E402
 from policy_head_bench import alternate, counted, entry_points  # noqa: E402
@@ -284,6 +292,90 @@ def tqc(a):
                       "top_quantiles_to_drop_per_net": drop, "K": K, "B": B, "critic_update": res}))
 
 
+def td3(a):
+    """The --td3 mode: see the module docstring."""
+    N, B = 2, 256
+    c = T3C.make_inputs(ARCH, N, B, seed=9)
+    net_arch = dict(pi=list(ARCH[1]), qf=list(ARCH[2]))
+    head = m3l_amd.TD3Head(ARCH[0], ARCH[3], net_arch=net_arch, n_critics=N)
+    head.load_state_dict({k: torch.from_numpy(v) for k, v in c["params"].items()})
+    head = head.to(DEV)
+    ce = EC.make_inputs(ARCH, N, B, seed=9)
+    ens = m3l_amd.SACEnsembleHead(ARCH[0], ARCH[3], net_arch=net_arch, n_critics=N)
+    ens.load_state_dict({k: torch.from_numpy(v) for k, v in ce["params"].items()})
+    ens = ens.to(DEV)
+    P = dict(head.named_parameters())
+    t = {k: torch.from_numpy(c[k]).to(DEV) for k in ("x", "x_next", "noise_pi", "noise_next", "a_replay", "rewards", "dones")}
+    log_ent = torch.tensor([ce["log_ent_coef"]], dtype=torch.float32, device=DEV)
+    gamma, sigma, clip = c["gamma"], 0.2, 0.5          # SB3's target_policy_noise and target_noise_clip
+
+    def zero(h):
+        for q in h.parameters():
+            q.grad = None
+
+    def td3_critic():
+        zero(head)
+        target_q = head.td_target(t["x_next"], t["rewards"], t["dones"], gamma, noise=t["noise_next"], target_policy_noise=sigma, target_noise_clip=clip)
+        loss = head.critic_loss(t["x"], t["a_replay"], target_q)
+        loss.backward()
+        return loss
+
+    def eager_critic():
+        zero(head)
+        with torch.no_grad():
+            mu, _, _ = T3C.actor_forward(P, "actor_target", t["x_next"])
+            an = (mu + (sigma * t["noise_next"]).clamp(-clip, clip)).clamp(-1, 1)          # SB3's TD3.train
+            qn, _ = EC.critic_forward(P, "critic_target", t["x_next"], an, N)
+            target_q = t["rewards"] + (1 - t["dones"]) * gamma * qn.min(dim=0)[0]
+        q, _ = EC.critic_forward(P, "critic", t["x"], t["a_replay"], N)
+        loss = sum(F.mse_loss(qc, target_q) for qc in q)
+        loss.backward()
+        return loss
+
+    def ens_critic():
+        zero(ens)
+        target_q = ens.td_target(t["x_next"], t["rewards"], t["dones"], gamma, log_ent_coef=log_ent, noise=t["noise_next"])
+        loss = ens.critic_loss(t["x"], t["a_replay"], target_q)
+        loss.backward()
+        return loss
+
+    def td3_actor():
+        zero(head)
+        loss = head.actor_loss(t["x"])
+        loss.backward()
+        return loss
+
+    def eager_actor():
+        zero(head)
+        mu, _, _ = T3C.actor_forward(P, "actor", t["x"])
+        xa = torch.cat([t["x"], mu], dim=1)          # SB3's q1_forward: the first critic alone
+        h = xa
+        for l in range(len(ARCH[2])):
+            h = torch.relu(F.linear(h, P[f"critic.qf0.{2 * l}.weight"], P[f"critic.qf0.{2 * l}.bias"]))
+        loss = -F.linear(h, P[f"critic.qf0.{2 * len(ARCH[2])}.weight"], P[f"critic.qf0.{2 * len(ARCH[2])}.bias"]).mean()
+        loss.backward()
+        return loss
+
+    def ens_actor():
+        zero(ens)
+        loss, _ = ens.actor_loss(t["x"], log_ent_coef=log_ent, noise=t["noise_pi"], q_reduce="min")
+        loss.backward()
+        return loss
+    out = {"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}, "critics": N, "B": B,
+           "target_policy_noise": sigma, "target_noise_clip": clip}
+    for what, fns in (("critic_update", {"td3": td3_critic, "eager": eager_critic, "ens2": ens_critic}),
+                      ("actor_update", {"td3": td3_actor, "eager": eager_actor, "ens2": ens_actor})):
+        res, last = alternate(fns, a.iters, a.warmup, a.rounds)
+        for name, fn in fns.items():
+            res[name].update(counted(fn))
+            res[name]["result_sum"] = float(last[name].detach().float().sum())
+        res["td3"]["entry_points"] = entry_points(fns["td3"])
+        res["td3_over_eager_call"] = round(res["td3"]["call_us"] / res["eager"]["call_us"], 3)
+        res["td3_over_ens2_call"] = round(res["td3"]["call_us"] / res["ens2"]["call_us"], 3)
+        out[what] = res
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=500, help="calls per timed window of (a); (b) takes ten times as many")
@@ -294,6 +386,7 @@ def main():
     ap.add_argument("--q-reduce", choices=("min", "mean"), default="mean", help="with --critics: the actor loss's reduction over the critics")
     ap.add_argument("--droq", action="store_true", help="measure a critic update of the DroQ critics (N = 2, p = 0.01) against eager torch and the N = 10 ensemble")
     ap.add_argument("--tqc", action="store_true", help="measure a critic update of the TQC head (n_quantiles 25, 2 dropped per net; --critics N, default 2) against eager torch and the N = 2 ensemble")
+    ap.add_argument("--td3", action="store_true", help="measure a critic update and an actor update of the TD3 head (N = 2) against eager torch and the N = 2 ensemble")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sac_head_bench: no GPU")
@@ -301,6 +394,8 @@ def main():
         return droq(a)
     if a.tqc:
         return tqc(a)
+    if a.td3:
+        return td3(a)
     if a.critics is not None:
         return ensemble(a)
     out = {"arch": {"features": ARCH[0], "pi": list(ARCH[1]), "qf": list(ARCH[2]), "actions": ARCH[3]}}
