@@ -799,8 +799,8 @@ int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float ta
  *      fma(s_0, 1/B, fma(s_1, 1/B, ... s_{N-1} (1/B))), which at N = 2 is the two-critic kernel's arithmetic.
  *   4. actor_loss, reduce = 0 (min, SB3's): mean_r (ent logp - min_c q_c); the lowest index among equal minima takes the row's gradient.
  *   5. actor_loss, reduce = 1 (mean, REDQ's): mean_r (ent logp - (sum_c q_c) (1 / N)), critics ascending; dq_c = -1 / (N B) for every c.
- *   6. N = 2 with subset NULL and reduce = 0: both loss kernels and td_abs give the bits of m3l_sac_critic_loss_fwd / _w_fwd and
- *      m3l_sac_actor_loss_fwd; the net walks run the same tile functions in the same order as the two-critic entries.
+ *   6. N = 2 with subset NULL and reduce = 0 is what the two-critic entries of the section above compute: they lift their m3l_sac_desc to this
+ *      section's descriptor with n_critics = 2 and run the same kernels, so every output and gradient has the same bits either way.
  * The actor's own forward and backward stay m3l_sac_actor_fwd / m3l_sac_actor_bwd on an m3l_sac_desc holding the actor's part, with
  * m3l_sac_ws_bytes; the Polyak update stays m3l_op_ema over all N critics' tensors in one launch; m3l_sac_ent_coef_loss is unchanged.
  * Launches: critic_fwd 1 (grid: row tiles x N); critic_bwd 1 chain (critics 0 .. N - 1 in order, critic c > 0 adding its dactions to what the

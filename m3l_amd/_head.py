@@ -1,14 +1,15 @@
-"""What the two policy heads (policy.py: PPO, Tanh, "branch"; sac.py: SAC, ReLU, "net") do alike on the Python side: reading Linear / activation
-pairs out of a module, walking a net's layer shapes, the limits of the kernels (csrc/policy_common.cuh), and preparing features, noise and row
-vectors for a call.  Every function takes what differs as an argument: the activation class, and the head's name (`head`: "policy" / "SAC")
-and its word for one net (`noun`) for the messages.  Nothing here launches a kernel."""
+"""What the policy heads (policy.py: PPO, Tanh, "branch"; sac.py and the heads built on it, sac_ensemble.py, tqc.py, td3.py: ReLU, "net") do alike
+on the Python side: reading Linear / activation pairs out of a module, walking a net's layer shapes, the limits of the kernels
+(csrc/policy_common.cuh), and preparing features, noise, actions, weights and row vectors for a call.  Every function takes what differs as an
+argument: the activation class, and the head's name (`head`: "policy" / "SAC" / "TD3") and its word for one net (`noun`) for the messages.
+Only `scale_coef`, the backward that the critic heads' losses share, launches a kernel."""
 import numbers
 
 import torch
 from torch import nn
 
 from . import _lib as L
-from .functional import _require_cuda
+from .functional import _require_cuda, _stream
 
 MAX_HIDDEN, MAX_WIDTH, MAX_ACTIONS = 3, 512, 64
 
@@ -155,6 +156,41 @@ def noise_of(noise, B, A, device, deterministic=False):
     if noise.shape[0] != B:
         raise ValueError(f"{B} feature rows but {noise.shape[0]} noise rows")
     return noise
+
+
+def actions_of(actions, B, A):
+    """actions (B, A) beside B feature rows as the critics read them: float32, contiguous, 16-byte aligned, by differentiable operations."""
+    _require_cuda(actions, "actions")
+    if actions.dim() != 2 or actions.shape[1] != A:
+        raise ValueError(f"actions: (B, {A}) expected, got {tuple(actions.shape)}")
+    if actions.shape[0] != B:
+        raise ValueError(f"{B} feature rows but {actions.shape[0]} action rows")
+    a = actions.float().contiguous()
+    return a.clone() if a.data_ptr() % 16 else a
+
+
+def weights_of(weights, B):
+    """The importance weights of a critic loss, float32 (B,) or (B, 1), as the kernels read them; None (ones) stays None."""
+    if weights is None:
+        return None
+    _require_cuda(weights, "weights")
+    if weights.dtype != torch.float32 or tuple(weights.shape) not in ((B,), (B, 1)):
+        raise ValueError(f"weights: a float32 tensor of shape ({B},) or ({B}, 1) expected, got {tuple(weights.shape)} {weights.dtype}")
+    return _vec(weights, "weights", B)
+
+
+def scale_coef(dloss, coef):
+    """The backward of a loss whose forward stored coef = d loss / d input: dloss * coef in coef's shape, one launch (m3l_sac_ens_loss_bwd)."""
+    out = torch.empty_like(coef)
+    L.check(L.lib().m3l_sac_ens_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), coef.numel(), L.ptr(out), _stream()), "m3l_sac_ens_loss_bwd")
+    return out
+
+
+def require_shared_extractor(module, head, name=None):
+    """Refuses a policy or critic module with share_features_extractor=False; name: the sub-module's, in front of the message."""
+    if not getattr(module, "share_features_extractor", True):
+        raise ValueError(f"{name + ': ' if name else ''}share_features_extractor=False: the HIP {head} head takes one feature vector for the actor and "
+                         "the critics")
 
 
 def no_workspace(node):

@@ -1,27 +1,26 @@
 // SAC policy head (include/m3l_amd.h "SAC policy head"): the squashed-Gaussian actor (latent_pi, mu, a state-dependent clamped log_std, tanh),
-// the twin critics over cat([x, actions]), the TD target, and the three losses of SAC_MAE.train.  float32 throughout on the exact-f32 MFMA, with
-// the row-tile pieces of policy_common.cuh (ReLU instead of the PPO head's Tanh); the actor and each critic are PhMlp nets run by its walks.
+// n = 1 .. 10 critics over cat([x, actions]) ("SAC critic ensemble"), the TD target, and the three losses of SAC_MAE.train.  float32 throughout on
+// the exact-f32 MFMA, with the row-tile pieces of policy_common.cuh (ReLU instead of the PPO head's Tanh); the actor and each critic are PhMlp
+// nets run by its walks.  There is one critic path: the two-critic entries of "SAC policy head" (m3l_sac_critic_*, m3l_sac_td_target*,
+// m3l_sac_critic_loss_*, m3l_sac_actor_loss_*) lift their descriptor to the ensemble's with n = 2 and run what the m3l_sac_ens_* entries run.
 //
 //   actor fwd    one launch, grid (row tiles of 16): x -> LDS, the hidden layers ping-pong between two LDS buffers, the mu and log_std heads
 //                leave two [16, A] tiles, then u = mu + exp(s) noise, a = tanh(u) and the row's log-probability.  With a workspace the
 //                post-ReLU activations, u and the pre-clamp log_std stay for the backward.
 //   actor bwd    chain kernel per row tile: (d actions, d log_prob) -> d mu, d log_std (clamp gate) -> back through both heads (the second
 //                adds to the first in LDS, the same lane owning an element) and the hidden layers to dx; then the grouped weight-gradient launch.
-//   critic fwd   one launch, grid (row tiles, 2 critics): the input tile is [x | a | zeros to a multiple of 16]; the first Linear has
+//   critic fwd   one launch, grid (row tiles, n critics): the input tile is [x | a | zeros to a multiple of 16]; the first Linear has
 //                K = F + A and rows that are only 4-byte aligned, so its weights come in by dword loads (EDGE path), every other as in the PPO head.
-//   critic bwd   chain kernel per row tile, critic 0 then critic 1: d q -> hidden layers (ReLU gates) -> d actions through the action columns of
-//                the first weight (critic 1 adds to what critic 0 wrote); the features get no gradient.  The grouped weight-gradient launch
-//                runs only when parameter gradients are asked for; dW of the first layer is stored element by element.
-//   td target    one launch per row tile: the actor on x' in LDS, a' handed to both target critics in LDS, min, entropy term, Bellman line.
+//   critic bwd   chain kernel per row tile, critics 0 .. n - 1 in order: d q -> hidden layers (ReLU gates) -> d actions through the action columns
+//                of the first weight (a critic after the first adds to what the earlier ones wrote); the features get no gradient.  The n (layers)
+//                Linears go to grouped weight-gradient launches of PH_MAXLIN each, only when parameter gradients are asked for; dW of the first
+//                layer is stored element by element.
+//   td target    one launch per row tile: the actor on x' in LDS, a' handed in LDS to the target critics that `subset` names, in list order
+//                (NULL: all), min, entropy term, Bellman line; a bad index: NaN rows, nothing read at it.
 //   losses       one workgroup each, every thread over its rows in order and the threads' sums through ph_block_sum; the forward stores the
-//                per-row coefficients and the backward scales them by dloss.
+//                per-row coefficients and the backward scales them by dloss.  SB3's sum over n critics with weights and td_abs; the actor loss
+//                against min_c or mean_c.
 // No float atomics, every sum in a fixed order: the same bits on every run.
-//
-// The critic ensemble ("SAC critic ensemble", the sac_ens_* kernels and m3l_sac_ens_* entries at the end) is the same with n = 1 .. 10 critics:
-//   critic fwd   grid (row tiles, n), the twin kernel's body;  critic bwd: the chain over critics 0 .. n - 1, then the n (layers) Linears in
-//                grouped weight-gradient launches of PH_MAXLIN each
-//   td target    the actor once, then only the target critics that `subset` names, in list order; a bad index: NaN rows, nothing read at it
-//   losses       SB3's sum over n critics with weights and td_abs; the actor loss against min_c or mean_c; n = 2 has the twin kernels' bits
 //
 // DroQ critics ("SAC DroQ critics", the sac_droq_* kernels and m3l_sac_droq_* entries at the end): the ensemble's critics with
 // Linear -> Dropout -> LayerNorm -> ReLU hidden layers.  Every hidden Linear runs without its activation, and a pass over the finished 16-row
@@ -44,6 +43,7 @@
 //   losses       the critic loss is the ensemble's kernel with the loss and the coefficients doubled (SB3's TD3 line has no 0.5); the actor
 //                loss is -mean_r of min_c or mean_c, one workgroup; "first" is n = 1 on a one-critic descriptor
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 
 #include "../../include/m3l_amd.h"
@@ -58,29 +58,25 @@
 
 namespace {
 
+// The arguments of the two actor kernels, which run at B = 8 on every environment step: the actor alone, so that they stay small.
 struct SacArgs {
     int B, F, A, ld;             // ld: leading dimension of the LDS activation buffers
-    int K0, Kp;                  // the critics' input width F + A, and the same rounded up to 16
     PhMlp pi;                                // actor: latent_pi, then the mu and log_std heads [A, .]
     const float *mu_W, *mu_b, *s_W, *s_b;
     long u_off, s_off, dmu_off, ds_off;      // u, pre-clamp log_std, d mu, d (pre-clamp log_std): [B, A] each
-    PhMlp qf[2];                             // critics: alike in their widths; layer 0 [., F + A], then the head [1, .]
-    const float* q_W[2];
-    const float* q_b[2];
-    long xa_off, dq_off;                     // the input [B, Kp]; d q [2, B]
-    long total;
+    long total;                              // the end of the actor's part of an m3l_sac_ws_bytes workspace; the critics' part starts here
 };
 
-// The critic ensemble's arguments ("SAC critic ensemble"): SacArgs with n critics in tables of M3L_SAC_MAX_CRITICS.  The tile functions below are
-// templates over the two structs and read the same members of either; the twin kernels keep SacArgs, so their arguments do not grow.
+// The arguments of every kernel that runs critics: n critics in tables of M3L_SAC_MAX_CRITICS, and the actor for the TD targets.  The DroQ, TQC
+// and TD3 argument structs are built on it.  sac_actor_tile is a template over SacArgs and this struct and reads the same members of either.
 struct SacEnsArgs {
     int B, F, A, ld;
-    int K0, Kp;
+    int K0, Kp;                  // the critics' input width F + A, and the same rounded up to 16
     int n;                                   // critics, 1 .. M3L_SAC_MAX_CRITICS
     PhMlp pi;                                // the actor, read by the TD target only (no workspace there: the offsets stay 0)
     const float *mu_W, *mu_b, *s_W, *s_b;
     long u_off, s_off;
-    PhMlp qf[M3L_SAC_MAX_CRITICS];
+    PhMlp qf[M3L_SAC_MAX_CRITICS];           // critics: alike in their widths; layer 0 [., F + A], then the head [1, .]
     const float* q_W[M3L_SAC_MAX_CRITICS];
     const float* q_b[M3L_SAC_MAX_CRITICS];
     long xa_off, dq_off;                     // the input [B, Kp]; d q [n, B]
@@ -137,8 +133,7 @@ __device__ void sac_actor_tile(const P& p, const float* __restrict__ x, const fl
 }
 
 // the critics' input tile [x | a | zeros up to Kp] for the rows row0 .. row0 + 15 (zero past B); a: row m of the tile at asrc + m * lda
-template <class P>
-__device__ void sac_build_xa(const P& p, const float* __restrict__ x, const float* asrc, int lda, int row0, float* buf) {
+__device__ void sac_build_xa(const SacEnsArgs& p, const float* __restrict__ x, const float* asrc, int lda, int row0, float* buf) {
     ph_load_x(x, p.F, row0, p.B, buf, p.ld);
     const int extra = p.Kp - p.F;
     for (int e = threadIdx.x; e < PH_TM * extra; e += 256) {
@@ -148,8 +143,7 @@ __device__ void sac_build_xa(const P& p, const float* __restrict__ x, const floa
 }
 
 // Critic c on the input tile in bufa (which it overwrites): q of the 16 rows into column 0 of head [16, PH_HLD].  Ends with a barrier.
-template <class P>
-__device__ void sac_critic_tile(const P& p, int c, int row0, float* bufa, float* bufb, float* head, float* __restrict__ ws) {
+__device__ void sac_critic_tile(const SacEnsArgs& p, int c, int row0, float* bufa, float* bufb, float* head, float* __restrict__ ws) {
     float* cur = bufa;
     float* nxt = bufb;
     const int K = ph_fwd_walk<PH_ACT_RELU, true>(p.qf[c], p.K0, cur, nxt, p.ld, ws, row0, p.B);
@@ -216,9 +210,8 @@ __global__ __launch_bounds__(256) void sac_actor_bwd_kernel(SacArgs p, const flo
     ph_bwd_layer<PH_ACT_NONE>(cur, p.ld, valid, W, N, p.F, nullptr, nullptr, 0, dx, false, row0, B);
 }
 
-// critic blockIdx.y on row tile blockIdx.x: the body of both critic forward kernels.  q [critics, B]
-template <class P>
-__device__ __forceinline__ void sac_critic_fwd_body(const P& p, const float* __restrict__ x, const float* __restrict__ actions, float* __restrict__ ws,
+// critic blockIdx.y on row tile blockIdx.x.  q [n, B]
+__device__ __forceinline__ void sac_critic_fwd_body(const SacEnsArgs& p, const float* __restrict__ x, const float* __restrict__ actions, float* __restrict__ ws,
                                                     float* __restrict__ q, float* sac_lds, float* head) {
     float* bufa = sac_lds;
     float* bufb = sac_lds + PH_TM * p.ld;
@@ -237,32 +230,6 @@ __device__ __forceinline__ void sac_critic_fwd_body(const P& p, const float* __r
     if (tid < PH_TM && row0 + tid < B) q[(long)c * B + row0 + tid] = head[tid * PH_HLD];
 }
 
-// grid (row tiles, 2 critics).  q [2, B]
-__global__ __launch_bounds__(256) void sac_critic_fwd_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ actions, float* __restrict__ ws,
-                                                             float* __restrict__ q) {
-    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
-    __shared__ __attribute__((aligned(16))) float head[PH_TM * PH_HLD];
-    sac_critic_fwd_body(p, x, actions, ws, q, sac_lds, head);
-}
-
-// grid (row tiles).  dq [2, B] or null (= zero); dactions [B, A] or null (not wanted)
-__global__ __launch_bounds__(256) void sac_critic_bwd_kernel(SacArgs p, const float* __restrict__ dq, float* __restrict__ ws, float* __restrict__ dactions) {
-    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
-    const int row0 = blockIdx.x * PH_TM, B = p.B;
-    for (int c = 0; c < 2; ++c) {
-        float* cur = sac_lds;
-        float* nxt = sac_lds + PH_TM * p.ld;
-        ph_col0_tile(dq ? dq + (long)c * B : nullptr, ws + p.dq_off + (long)c * B, cur, p.ld, row0, B);      // d q of this critic
-        __syncthreads();
-        const float* W = p.q_W[c];
-        int N = 1, valid = 8;
-        ph_bwd_walk<PH_ACT_RELU>(p.qf[c], p.qf[c].n - 1, cur, nxt, p.ld, valid, W, N, ws, row0, B);
-        // the action columns of the first weight; critic 1 adds to what critic 0 wrote, lane for lane
-        if (dactions != nullptr) ph_bwd_edge(cur, p.ld, valid, W, N, p.K0, p.F, p.A, dactions, c == 1, row0, B);
-        __syncthreads();
-    }
-}
-
 // grid (row tiles, n critics).  q [n, B]
 __global__ __launch_bounds__(256) void sac_ens_critic_fwd_kernel(SacEnsArgs p, const float* __restrict__ x, const float* __restrict__ actions,
                                                                  float* __restrict__ ws, float* __restrict__ q) {
@@ -271,7 +238,7 @@ __global__ __launch_bounds__(256) void sac_ens_critic_fwd_kernel(SacEnsArgs p, c
     sac_critic_fwd_body(p, x, actions, ws, q, sac_lds, head);
 }
 
-// grid (row tiles).  dq [n, B] or null (= zero); dactions [B, A] or null (not wanted).  sac_critic_bwd_kernel's chain over n critics
+// grid (row tiles).  dq [n, B] or null (= zero); dactions [B, A] or null (not wanted)
 __global__ __launch_bounds__(256) void sac_ens_critic_bwd_kernel(SacEnsArgs p, const float* __restrict__ dq, float* __restrict__ ws,
                                                                  float* __restrict__ dactions) {
     extern __shared__ __attribute__((aligned(16))) float sac_lds[];
@@ -292,95 +259,6 @@ __global__ __launch_bounds__(256) void sac_ens_critic_bwd_kernel(SacEnsArgs p, c
 
 // grid (cdiv(items, 4)): wave w of block b takes item 4 b + w
 __global__ __launch_bounds__(256) void sac_wgrad_kernel(PhWgrad q) { ph_wgrad_block(q, blockIdx.x); }
-
-// grid (row tiles).  The critic pointers of p are the target critics'.  discounts: one discount per row (n-step returns), or NULL: gamma for
-// every row; the value enters one expression either way, so a constant discounts gives the bits of the scalar.
-__global__ __launch_bounds__(256) void sac_td_target_kernel(SacArgs p, const float* __restrict__ x, const float* __restrict__ noise,
-                                                            const float* __restrict__ rewards, const float* __restrict__ dones,
-                                                            const float* __restrict__ discounts, float gamma, float ent_coef,
-                                                            const float* __restrict__ log_ent_coef, float* __restrict__ target_q) {
-    extern __shared__ __attribute__((aligned(16))) float sac_lds[];
-    __shared__ __attribute__((aligned(16))) float hmu[PH_TM * PH_HLD], hs[PH_TM * PH_HLD];
-    __shared__ float lp_sh[PH_TM], q_sh[2][PH_TM];
-    float* bufa = sac_lds;
-    float* bufb = sac_lds + PH_TM * p.ld;
-    const int row0 = blockIdx.x * PH_TM, tid = threadIdx.x, B = p.B;
-    sac_actor_tile(p, x, noise, row0, bufa, bufb, hmu, hs, lp_sh, nullptr, nullptr, nullptr);
-    for (int c = 0; c < 2; ++c) {
-        sac_build_xa(p, x, hmu, PH_HLD, row0, bufa);
-        __syncthreads();
-        sac_critic_tile(p, c, row0, bufa, bufb, hs, nullptr);
-        if (tid < PH_TM) q_sh[c][tid] = hs[tid * PH_HLD];
-        __syncthreads();
-    }
-    if (tid < PH_TM && row0 + tid < B) {
-        const int row = row0 + tid;
-        const float ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
-        const float nq = fminf(q_sh[0][tid], q_sh[1][tid]) - ent * lp_sh[tid];
-        const float g = discounts ? discounts[row] : gamma;
-        target_q[row] = rewards[row] + (1.f - dones[row]) * g * nq;
-    }
-}
-
-// one workgroup.  loss = 0.5 sum_c mean_r (q[c, r] - t[r])^2;  coef [2, B] = dloss / dq
-__global__ __launch_bounds__(256) void sac_critic_loss_kernel(const float* __restrict__ q, const float* __restrict__ t, int B, float* __restrict__ loss,
-                                                              float* __restrict__ coef) {
-    __shared__ float red[4];
-    const float invB = 1.f / (float)B;
-    float s0 = 0.f, s1 = 0.f;
-    for (int r = threadIdx.x; r < B; r += 256) {
-        const float d0 = q[r] - t[r], d1 = q[B + r] - t[r];
-        s0 += d0 * d0;
-        s1 += d1 * d1;
-        coef[r] = d0 * invB;
-        coef[B + r] = d1 * invB;
-    }
-    s0 = ph_block_sum(s0, red);
-    s1 = ph_block_sum(s1, red);
-    if (threadIdx.x == 0) loss[0] = 0.5f * (s0 * invB + s1 * invB);
-}
-
-// one workgroup, for prioritised replay.  loss = 0.5 sum_c mean_r w[r] (q[c, r] - t[r])^2;  coef [2, B] = dloss / dq = w[r] d / B;
-// td_abs [B] = 0.5 (|d_0| + |d_1|), the priorities' input.  w NULL: 1.  The weight multiplies d before the square is taken, so with w = 1
-// every operation is the one of sac_critic_loss_kernel and the bits are its bits.
-__global__ __launch_bounds__(256) void sac_critic_loss_w_kernel(const float* __restrict__ q, const float* __restrict__ t, const float* __restrict__ w,
-                                                                int B, float* __restrict__ loss, float* __restrict__ coef,
-                                                                float* __restrict__ td_abs) {
-    __shared__ float red[4];
-    const float invB = 1.f / (float)B;
-    float s0 = 0.f, s1 = 0.f;
-    for (int r = threadIdx.x; r < B; r += 256) {
-        const float d0 = q[r] - t[r], d1 = q[B + r] - t[r], wr = w ? w[r] : 1.f;
-        const float wd0 = wr * d0, wd1 = wr * d1;
-        s0 += wd0 * d0;
-        s1 += wd1 * d1;
-        coef[r] = wd0 * invB;
-        coef[B + r] = wd1 * invB;
-        td_abs[r] = 0.5f * (fabsf(d0) + fabsf(d1));
-    }
-    s0 = ph_block_sum(s0, red);
-    s1 = ph_block_sum(s1, red);
-    if (threadIdx.x == 0) loss[0] = 0.5f * (s0 * invB + s1 * invB);
-}
-
-// one workgroup.  loss = mean_r (ent logp[r] - min_c q[c, r]);  coef [3, B]: dloss / dlogp, then dloss / dq [2, B] (the smaller critic takes it,
-// critic 0 when they are equal)
-__global__ __launch_bounds__(256) void sac_actor_loss_kernel(const float* __restrict__ logp, const float* __restrict__ q, int B, float ent_coef,
-                                                             const float* __restrict__ log_ent_coef, float* __restrict__ loss, float* __restrict__ coef) {
-    __shared__ float red[4];
-    const float invB = 1.f / (float)B, ent = log_ent_coef ? expf(log_ent_coef[0]) : ent_coef;
-    float s = 0.f;
-    for (int r = threadIdx.x; r < B; r += 256) {
-        const float q0 = q[r], q1 = q[B + r];
-        const bool first = q0 <= q1;
-        s += ent * logp[r] - (first ? q0 : q1);
-        coef[r] = ent * invB;
-        coef[B + r] = first ? -invB : 0.f;
-        coef[2 * B + r] = first ? 0.f : -invB;
-    }
-    s = ph_block_sum(s, red);
-    if (threadIdx.x == 0) loss[0] = s * invB;
-}
 
 // one workgroup.  m = mean_r (logp[r] + target_entropy):  loss = -log_ent_coef m,  ent_coef = exp(log_ent_coef),  dlog = -dloss m (dloss null: 1)
 __global__ __launch_bounds__(256) void sac_ent_coef_loss_kernel(const float* __restrict__ log_ent_coef, const float* __restrict__ logp, float target_entropy, int B,
@@ -405,7 +283,8 @@ __global__ __launch_bounds__(256) void sac_scale_kernel(const float* __restrict_
 
 // grid (row tiles).  The critic pointers of p are the target critics'.  subset [n_subset] names the critics whose minimum is taken, in list
 // order (NULL: 0 .. n_subset - 1); only they are evaluated.  An entry outside [0, n) makes every row NaN, and no table is read at it: the whole
-// grid sees the same list, so every workgroup leaves before its first barrier.  discounts as in sac_td_target_kernel.
+// grid sees the same list, so every workgroup leaves before its first barrier.  discounts: one discount per row (n-step returns), or NULL:
+// gamma for every row; the value enters one expression either way, so a constant discounts gives the bits of the scalar.
 __global__ __launch_bounds__(256) void sac_ens_td_target_kernel(SacEnsArgs p, const float* __restrict__ x, const float* __restrict__ noise,
                                                                 const float* __restrict__ rewards, const float* __restrict__ dones,
                                                                 const float* __restrict__ discounts, float gamma, float ent_coef,
@@ -444,12 +323,12 @@ __global__ __launch_bounds__(256) void sac_ens_td_target_kernel(SacEnsArgs p, co
     }
 }
 
-// The ensemble's loss kernels spell their roundings out (fmaf, __fmul_rn, __fadd_rn), in the forms that the compiler gives the two-critic kernels
-// above, so that n = 2 has their bits whatever a later compiler contracts.
+// The loss kernels spell their roundings out (fmaf, __fmul_rn, __fadd_rn), so that their bits do not depend on what a compiler contracts: at
+// n = 2 they are the bits of the two-critic kernels that the "SAC policy head" entries ran before they came here (EXPERIMENTS.md 5.31).
 
 // one workgroup.  loss = 0.5 sum_c mean_r w[r] (q[c, r] - t[r])^2;  coef [n, B] = w[r] d / B;  td_abs [B] (or null) = (sum_c |d_c|) (1 / n).
-// w null: 1.  Per critic the rows add up as in sac_critic_loss_w_kernel; the n means then add up from the last critic to the first, each fused
-// onto the sum behind it: fma(s_0, 1/B, fma(s_1, 1/B, ... s_{n-1} / B)), which at n = 2 is what sac_critic_loss_kernel computes.
+// w null: 1; the weight multiplies d before the square is taken, so w = 1 gives the bits of w null.  Per critic every thread adds its rows in
+// order; the n means then add up from the last critic to the first, each fused onto the sum behind it: fma(s_0, 1/B, fma(s_1, 1/B, ... s_{n-1} / B)).
 // TWICE (the TD3 head's line, without the 0.5): the finished loss and every coefficient times 2, an exact scale behind the same arithmetic.
 template <bool TWICE>
 __global__ __launch_bounds__(256) void sac_ens_critic_loss_kernel(const float* __restrict__ q, const float* __restrict__ t, const float* __restrict__ w, int n,
@@ -516,22 +395,26 @@ __global__ __launch_bounds__(256) void sac_ens_actor_loss_kernel(const float* __
 
 enum { SAC_ACTOR = 1, SAC_CRITIC = 2 };
 
+int sac_init();                  // at the end of the file, behind the last kernel
+#define SAC_LDS_MAX (2 * PH_TM * (PH_MAXW + PH_MAXA + 4) * 4)
+
 // the limits of the header; 0 and a message when the head is outside them
 int sac_shape_ok(const m3l_sac_desc* d, int B, char* why, size_t n) {
     if (d == nullptr) { snprintf(why, n, "null descriptor"); return 0; }
     return ph_dims_ok(B, d->features, d->actions, d->n_pi, d->pi_width, d->n_qf, d->qf_width, "net", PH_MAXW + PH_MAXA, why, n);
 }
 
-// kernel arguments and workspace layout; parts: whose parameter pointers are read (0 only sizes the workspace)
-SacArgs sac_args(const m3l_sac_desc* d, int B, int parts) {
+// the actor kernels' arguments and the actor's part of the workspace; bind: the actor's parameter pointers are read (0 only sizes the workspace)
+SacArgs sac_args(const m3l_sac_desc* d, int B, int bind) {
     SacArgs p;
     memset(&p, 0, sizeof(p));
     p.B = B;
     p.F = d->features;
     p.A = d->actions;
-    p.K0 = p.F + p.A;
-    p.Kp = (p.K0 + 15) & ~15;
-    int widest = p.Kp > PH_MAXA ? p.Kp : PH_MAXA;
+    const int Kp = (p.F + p.A + 15) & ~15;
+    int widest = Kp > PH_MAXA ? Kp : PH_MAXA;
+    PhMlp qf;                    // widths only: ld follows the widest row of either kind of net, the critic kernels' ld
+    ph_layout(qf, d->n_qf, d->qf_width, 0, 0, widest);
     long off = ph_layout(p.pi, d->n_pi, d->pi_width, B, 0, widest);
     p.u_off = off;
     off = ph_round4(off + (long)B * p.A);
@@ -541,250 +424,24 @@ SacArgs sac_args(const m3l_sac_desc* d, int B, int parts) {
     off = ph_round4(off + (long)B * p.A);
     p.ds_off = off;
     off = ph_round4(off + (long)B * p.A);
-    for (int c = 0; c < 2; ++c) off = ph_layout(p.qf[c], d->n_qf, d->qf_width, B, off, widest);
-    p.xa_off = off;
-    off += (long)B * p.Kp;
-    p.dq_off = off;
-    off = ph_round4(off + 2L * B);
     p.total = off;
     p.ld = widest + 4;
-    if (parts & SAC_ACTOR) {
+    if (bind) {
         ph_bind(p.pi, d->pi_weight, d->pi_bias);
         p.mu_W = d->mu_weight; p.mu_b = d->mu_bias; p.s_W = d->log_std_weight; p.s_b = d->log_std_bias;
     }
-    if (parts & SAC_CRITIC)
-        for (int c = 0; c < 2; ++c) {
-            ph_bind(p.qf[c], d->qf_weight[c], d->qf_bias[c]);
-            p.q_W[c] = d->q_weight[c]; p.q_b[c] = d->q_bias[c];
-        }
     return p;
 }
 
-int sac_params_ok(const m3l_sac_desc* d, int parts, const char* who) {
-    int ok = 1;
-    if (parts & SAC_ACTOR)
-        ok = ok && d->mu_weight && d->mu_bias && d->log_std_weight && d->log_std_bias && ph_aligned(d->mu_weight) && ph_aligned(d->log_std_weight) &&
-             ph_ptrs_ok(d->n_pi, d->pi_weight, d->pi_bias);
-    if (parts & SAC_CRITIC)
-        for (int c = 0; c < 2; ++c) ok = ok && d->q_weight[c] && d->q_bias[c] && ph_aligned(d->q_weight[c]) && ph_ptrs_ok(d->n_qf, d->qf_weight[c], d->qf_bias[c]);
-    M3L_CHECK(ok, "%s: a parameter pointer of the descriptor is null or a weight is not 16-byte aligned", who);
-    return 0;
-}
-
-int g_sac_inited = 0;
-#define SAC_LDS_MAX (2 * PH_TM * (PH_MAXW + PH_MAXA + 4) * 4)
-int sac_init() {
-    if (g_sac_inited) return 0;
-    if (ph_allow_lds({(const void*)sac_actor_fwd_kernel, (const void*)sac_actor_bwd_kernel, (const void*)sac_critic_fwd_kernel,
-                      (const void*)sac_critic_bwd_kernel, (const void*)sac_td_target_kernel}, SAC_LDS_MAX))
-        return 2;
-    g_sac_inited = 1;
+int sac_params_ok(const m3l_sac_desc* d, const char* who) {
+    M3L_CHECK(d->mu_weight && d->mu_bias && d->log_std_weight && d->log_std_bias && ph_aligned(d->mu_weight) && ph_aligned(d->log_std_weight) &&
+                  ph_ptrs_ok(d->n_pi, d->pi_weight, d->pi_bias),
+              "%s: a parameter pointer of the descriptor is null or a weight is not 16-byte aligned", who);
     return 0;
 }
 
 size_t sac_lds_bytes(const SacArgs& p) { return (size_t)2 * PH_TM * p.ld * 4; }
-
 double sac_actor_flops(const SacArgs& p) { return ph_net_flops(p.pi, p.B, p.F, 2 * p.A); }
-double sac_critic_flops(const SacArgs& p) { return 2.0 * ph_net_flops(p.qf[0], p.B, p.K0, 1); }
-
-}  // namespace
-
-extern "C" {
-
-size_t m3l_sac_ws_bytes(const m3l_sac_desc* d, int B) {
-    char why[160];
-    if (!sac_shape_ok(d, B, why, sizeof(why))) return 256;
-    return (size_t)sac_args(d, B, 0).total * sizeof(float);
-}
-
-int m3l_sac_actor_fwd(const m3l_sac_desc* d, int B, const float* x, const float* noise, void* ws, float* actions, float* logp, void* stream) {
-    char why[160];
-    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_actor_fwd: unsupported shape: %s", why);
-    if (sac_params_ok(d, SAC_ACTOR, "sac_actor_fwd")) return 1;
-    M3L_CHECK(x && actions && logp && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_actor_fwd: null argument, or x / ws not 16-byte aligned");
-    if (sac_init()) return 2;
-    hipStream_t st = (hipStream_t)stream;
-    const SacArgs p = sac_args(d, B, SAC_ACTOR);
-    ProfScope prof("sac_actor_fwd", B, p.F, p.A, sac_actor_flops(p), st, 4.0 * B * p.F);
-    sac_actor_fwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, x, noise, (float*)ws, actions, logp);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-int m3l_sac_actor_bwd(const m3l_sac_desc* d, int B, const float* x, const float* noise, const float* dactions, const float* dlogp, void* ws, float* dx,
-                      const m3l_sac_desc* grads, void* stream) {
-    char why[160];
-    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_actor_bwd: unsupported shape: %s", why);
-    if (sac_params_ok(d, SAC_ACTOR, "sac_actor_bwd")) return 1;
-    M3L_CHECK(grads != nullptr && grads->n_pi == d->n_pi, "sac_actor_bwd: the gradient descriptor is null or has another layer count");
-    if (sac_params_ok(grads, SAC_ACTOR, "sac_actor_bwd (gradients)")) return 1;
-    M3L_CHECK(x && ws && dx && ph_aligned(x) && ph_aligned(ws) && ph_aligned(dx), "sac_actor_bwd: null argument, or x / ws / dx not 16-byte aligned");
-    if (sac_init()) return 2;
-    hipStream_t st = (hipStream_t)stream;
-    const SacArgs p = sac_args(d, B, SAC_ACTOR);
-    float* w = (float*)ws;
-    PhWgrad q;
-    memset(&q, 0, sizeof(q));
-    q.B = B;
-    ph_add_net(q, p.pi, w, x, p.F, p.F, grads->pi_weight, grads->pi_bias, p.A,
-               {{w + p.dmu_off, grads->mu_weight, grads->mu_bias}, {w + p.ds_off, grads->log_std_weight, grads->log_std_bias}});
-    {
-        ProfScope prof("sac_actor_bwd_chain", B, p.F, p.A, sac_actor_flops(p), st, 4.0 * B * p.F);
-        sac_actor_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, noise, dactions, dlogp, w, dx);
-        M3L_LAUNCH_CHECK();
-    }
-    {
-        ProfScope prof("sac_actor_wgrad", B, q.items, p.A, sac_actor_flops(p), st, 0.0);
-        sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
-        M3L_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
-int m3l_sac_critic_fwd(const m3l_sac_desc* d, int B, const float* x, const float* actions, void* ws, float* q, void* stream) {
-    char why[160];
-    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_critic_fwd: unsupported shape: %s", why);
-    if (sac_params_ok(d, SAC_CRITIC, "sac_critic_fwd")) return 1;
-    M3L_CHECK(x && actions && q && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_critic_fwd: null argument, or x / ws not 16-byte aligned");
-    if (sac_init()) return 2;
-    hipStream_t st = (hipStream_t)stream;
-    const SacArgs p = sac_args(d, B, SAC_CRITIC);
-    ProfScope prof("sac_critic_fwd", B, p.F, p.A, sac_critic_flops(p), st, 4.0 * B * p.K0);
-    sac_critic_fwd_kernel<<<dim3(cdiv(B, PH_TM), 2), 256, sac_lds_bytes(p), st>>>(p, x, actions, (float*)ws, q);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-int m3l_sac_critic_bwd(const m3l_sac_desc* d, int B, const float* dq, void* ws, float* dactions, const m3l_sac_desc* grads, void* stream) {
-    char why[160];
-    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_critic_bwd: unsupported shape: %s", why);
-    if (sac_params_ok(d, SAC_CRITIC, "sac_critic_bwd")) return 1;
-    M3L_CHECK(grads == nullptr || grads->n_qf == d->n_qf, "sac_critic_bwd: the gradient descriptor has another layer count");
-    if (grads != nullptr && sac_params_ok(grads, SAC_CRITIC, "sac_critic_bwd (gradients)")) return 1;
-    M3L_CHECK(ws && ph_aligned(ws), "sac_critic_bwd: ws is null or not 16-byte aligned");
-    if (sac_init()) return 2;
-    hipStream_t st = (hipStream_t)stream;
-    const SacArgs p = sac_args(d, B, SAC_CRITIC);
-    float* w = (float*)ws;
-    {
-        ProfScope prof("sac_critic_bwd_chain", B, p.F, p.A, sac_critic_flops(p), st, 0.0);
-        sac_critic_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, dq, w, dactions);
-        M3L_LAUNCH_CHECK();
-    }
-    if (grads == nullptr) return 0;
-    PhWgrad q;
-    memset(&q, 0, sizeof(q));
-    q.B = B;
-    for (int c = 0; c < 2; ++c)
-        ph_add_net(q, p.qf[c], w, w + p.xa_off, p.K0, p.Kp, grads->qf_weight[c], grads->qf_bias[c], 1,
-                   {{w + p.dq_off + (long)c * B, grads->q_weight[c], grads->q_bias[c]}});
-    ProfScope prof("sac_critic_wgrad", B, q.items, p.A, sac_critic_flops(p), st, 0.0);
-    sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-}  // extern "C"
-
-namespace {
-// m3l_sac_td_target (discounts NULL) and m3l_sac_td_target_rows
-int sac_td_target_launch(const char* who, const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards,
-                         const float* dones, const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, float* target_q,
-                         void* stream) {
-    char why[160];
-    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "%s: unsupported shape: %s", who, why);
-    if (sac_params_ok(d, SAC_ACTOR | SAC_CRITIC, who)) return 1;
-    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "%s: null argument, or x_next not 16-byte aligned", who);
-    if (sac_init()) return 2;
-    hipStream_t st = (hipStream_t)stream;
-    const SacArgs p = sac_args(d, B, SAC_ACTOR | SAC_CRITIC);
-    ProfScope prof(who, B, p.F, p.A, sac_actor_flops(p) + sac_critic_flops(p), st, 4.0 * B * p.F);
-    sac_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, x_next, noise, rewards, dones, discounts, gamma, ent_coef, log_ent_coef,
-                                                                       target_q);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-}  // namespace
-
-extern "C" {
-
-int m3l_sac_td_target(const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones, float gamma,
-                      float ent_coef, const float* log_ent_coef, float* target_q, void* stream) {
-    return sac_td_target_launch("sac_td_target", d, B, x_next, noise, rewards, dones, nullptr, gamma, ent_coef, log_ent_coef, target_q, stream);
-}
-
-int m3l_sac_td_target_rows(const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
-                           const float* discounts, float ent_coef, const float* log_ent_coef, float* target_q, void* stream) {
-    M3L_CHECK(discounts, "sac_td_target_rows: discounts is NULL");
-    return sac_td_target_launch("sac_td_target_rows", d, B, x_next, noise, rewards, dones, discounts, 0.f, ent_coef, log_ent_coef, target_q, stream);
-}
-
-int m3l_sac_critic_loss_fwd(const float* q, const float* target_q, int B, float* loss, float* coef, void* stream) {
-    M3L_CHECK(B >= 1, "sac_critic_loss_fwd: B=%d (B >= 1)", B);
-    M3L_CHECK(q && target_q && loss && coef, "sac_critic_loss_fwd: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_critic_loss_fwd", B, 0, 0, 8.0 * B, st, 20.0 * B);
-    sac_critic_loss_kernel<<<1, 256, 0, st>>>(q, target_q, B, loss, coef);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-int m3l_sac_critic_loss_w_fwd(const float* q, const float* target_q, const float* weights, int B, float* loss, float* coef, float* td_abs,
-                              void* stream) {
-    M3L_CHECK(B >= 1, "sac_critic_loss_w_fwd: B=%d (B >= 1)", B);
-    M3L_CHECK(q && target_q && loss && coef && td_abs, "sac_critic_loss_w_fwd: null argument (weights may be NULL: ones)");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_critic_loss_w_fwd", B, 0, 0, 14.0 * B, st, 28.0 * B);
-    sac_critic_loss_w_kernel<<<1, 256, 0, st>>>(q, target_q, weights, B, loss, coef, td_abs);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-int m3l_sac_critic_loss_bwd(const float* dloss, const float* coef, int B, float* dq, void* stream) {
-    M3L_CHECK(B >= 1, "sac_critic_loss_bwd: B=%d (B >= 1)", B);
-    M3L_CHECK(dloss && coef && dq, "sac_critic_loss_bwd: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_critic_loss_bwd", B, 0, 0, 2.0 * B, st, 16.0 * B);
-    sac_scale_kernel<<<cdiv(2L * B, 256), 256, 0, st>>>(dloss, coef, 2 * B, dq);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-int m3l_sac_actor_loss_fwd(const float* logp, const float* q, int B, float ent_coef, const float* log_ent_coef, float* loss, float* coef, void* stream) {
-    M3L_CHECK(B >= 1, "sac_actor_loss_fwd: B=%d (B >= 1)", B);
-    M3L_CHECK(logp && q && loss && coef, "sac_actor_loss_fwd: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_actor_loss_fwd", B, 0, 0, 6.0 * B, st, 24.0 * B);
-    sac_actor_loss_kernel<<<1, 256, 0, st>>>(logp, q, B, ent_coef, log_ent_coef, loss, coef);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-int m3l_sac_actor_loss_bwd(const float* dloss, const float* coef, int B, float* dlogp_dq, void* stream) {
-    M3L_CHECK(B >= 1, "sac_actor_loss_bwd: B=%d (B >= 1)", B);
-    M3L_CHECK(dloss && coef && dlogp_dq, "sac_actor_loss_bwd: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_actor_loss_bwd", B, 0, 0, 3.0 * B, st, 24.0 * B);
-    sac_scale_kernel<<<cdiv(3L * B, 256), 256, 0, st>>>(dloss, coef, 3 * B, dlogp_dq);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float target_entropy, int B, const float* dloss, float* loss, float* ent_coef,
-                          float* dlog_ent_coef, void* stream) {
-    M3L_CHECK(B >= 1, "sac_ent_coef_loss: B=%d (B >= 1)", B);
-    M3L_CHECK(log_ent_coef && logp && (loss || ent_coef || dlog_ent_coef), "sac_ent_coef_loss: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_ent_coef_loss", B, 0, 0, 2.0 * B, st, 4.0 * B);
-    sac_ent_coef_loss_kernel<<<1, 256, 0, st>>>(log_ent_coef, logp, target_entropy, B, dloss, loss, ent_coef, dlog_ent_coef);
-    M3L_LAUNCH_CHECK();
-    return 0;
-}
-
-}  // extern "C"
-
-// ---- SAC critic ensemble (include/m3l_amd.h "SAC critic ensemble"): n critics where the entries above have two
-namespace {
 
 int sac_ens_shape_ok(const m3l_sac_ens_desc* d, int B, char* why, size_t n) {
     if (d == nullptr) { snprintf(why, n, "null descriptor"); return 0; }
@@ -795,8 +452,9 @@ int sac_ens_shape_ok(const m3l_sac_ens_desc* d, int B, char* why, size_t n) {
     return ph_dims_ok(B, d->features, d->actions, d->n_pi, d->pi_width, d->n_qf, d->qf_width, "net", PH_MAXW + PH_MAXA, why, n);
 }
 
-// kernel arguments and the critics' workspace layout (the actor's nodes keep m3l_sac_ws_bytes); parts as in sac_args
-SacEnsArgs sac_ens_args(const m3l_sac_ens_desc* d, int B, int parts) {
+// kernel arguments and the critics' workspace layout from `start` on: 0 for a workspace of the critics' own (m3l_sac_ens_ws_bytes), the end of
+// the actor's part for the two-critic entries' (m3l_sac_ws_bytes).  parts: whose parameter pointers are read (0 only sizes the workspace)
+SacEnsArgs sac_ens_args(const m3l_sac_ens_desc* d, int B, int parts, long start = 0) {
     SacEnsArgs p;
     memset(&p, 0, sizeof(p));
     p.B = B;
@@ -806,7 +464,7 @@ SacEnsArgs sac_ens_args(const m3l_sac_ens_desc* d, int B, int parts) {
     p.K0 = p.F + p.A;
     p.Kp = (p.K0 + 15) & ~15;
     int widest = p.Kp > PH_MAXA ? p.Kp : PH_MAXA;
-    long off = 0;
+    long off = start;
     ph_layout(p.pi, d->n_pi, d->pi_width, 0, 0, widest);      // widths only: no actor activations are stored here
     for (int c = 0; c < p.n; ++c) off = ph_layout(p.qf[c], d->n_qf, d->qf_width, B, off, widest);
     p.xa_off = off;
@@ -839,27 +497,18 @@ int sac_ens_params_ok(const m3l_sac_ens_desc* d, int parts, const char* who) {
     return 0;
 }
 
-int g_sac_ens_inited = 0;
-int sac_ens_init() {
-    if (g_sac_ens_inited) return 0;
-    if (ph_allow_lds({(const void*)sac_ens_critic_fwd_kernel, (const void*)sac_ens_critic_bwd_kernel, (const void*)sac_ens_td_target_kernel}, SAC_LDS_MAX))
-        return 2;
-    g_sac_ens_inited = 1;
-    return 0;
-}
-
 size_t sac_ens_lds_bytes(const SacEnsArgs& p) { return (size_t)2 * PH_TM * p.ld * 4; }
 double sac_ens_critic_flops(const SacEnsArgs& p, int critics) { return (double)critics * ph_net_flops(p.qf[0], p.B, p.K0, 1); }
 
 // the n (n_qf + 1) Linears of all critics in critic order, PH_MAXLIN to a launch (a launch's items are numbered from 0 again), from what the
 // chain kernel left in w.  rows: the outputs of each critic's head (1; the TQC critics' n_quantiles), its output gradient [B, rows] per critic
-int sac_ens_wgrad_launches(const SacEnsArgs& p, float* w, const m3l_sac_ens_desc* grads, hipStream_t st, int rows = 1) {
+int sac_ens_wgrad_launches(const char* prof_name, const SacEnsArgs& p, float* w, const m3l_sac_ens_desc* grads, hipStream_t st, int rows = 1) {
     const int B = p.B;
     PhWgrad q;
     memset(&q, 0, sizeof(q));
     q.B = B;
     auto flush = [&]() -> int {
-        ProfScope prof("sac_ens_critic_wgrad", B, q.items, p.n, 0.0, st, 0.0);
+        ProfScope prof(prof_name, B, q.items, p.n, 0.0, st, 0.0);
         sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
         M3L_LAUNCH_CHECK();
         memset(&q, 0, sizeof(q));
@@ -881,9 +530,245 @@ int sac_ens_wgrad_launches(const SacEnsArgs& p, float* w, const m3l_sac_ens_desc
     return q.count > 0 ? flush() : 0;
 }
 
+// ---- The critic entries.  Each is one function that takes the entry's name for its messages and its profile scope; the m3l_sac_ens_* entry and
+// the two-critic entry of "SAC policy head" both call it.  ws_start: see sac_ens_args.
+
+int sac_ens_critic_fwd_impl(const char* who, const m3l_sac_ens_desc* d, int B, const float* x, const float* actions, void* ws, long ws_start, float* q,
+                            void* stream) {
+    char why[160];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "%s: unsupported shape: %s", who, why);
+    if (sac_ens_params_ok(d, SAC_CRITIC, who)) return 1;
+    M3L_CHECK(x && actions && q && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "%s: null argument, or x / ws not 16-byte aligned", who);
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacEnsArgs p = sac_ens_args(d, B, SAC_CRITIC, ws_start);
+    ProfScope prof(who, B, p.F, p.n, sac_ens_critic_flops(p, p.n), st, 4.0 * B * p.K0);
+    sac_ens_critic_fwd_kernel<<<dim3(cdiv(B, PH_TM), p.n), 256, sac_ens_lds_bytes(p), st>>>(p, x, actions, (float*)ws, q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+// wgrad: the profile scope of the weight-gradient launches; the chain's is who + "_chain"
+int sac_ens_critic_bwd_impl(const char* who, const char* wgrad, const m3l_sac_ens_desc* d, int B, const float* dq, void* ws, long ws_start, float* dactions,
+                            const m3l_sac_ens_desc* grads, void* stream) {
+    char why[160], name[64];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "%s: unsupported shape: %s", who, why);
+    if (sac_ens_params_ok(d, SAC_CRITIC, who)) return 1;
+    M3L_CHECK(grads == nullptr || (grads->n_qf == d->n_qf && grads->n_critics == d->n_critics),
+              "%s: the gradient descriptor has another layer or critic count", who);
+    snprintf(name, sizeof(name), "%s (gradients)", who);
+    if (grads != nullptr && sac_ens_params_ok(grads, SAC_CRITIC, name)) return 1;
+    M3L_CHECK(ws && ph_aligned(ws), "%s: ws is null or not 16-byte aligned", who);
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacEnsArgs p = sac_ens_args(d, B, SAC_CRITIC, ws_start);
+    float* w = (float*)ws;
+    {
+        snprintf(name, sizeof(name), "%s_chain", who);
+        ProfScope prof(name, B, p.F, p.n, sac_ens_critic_flops(p, p.n), st, 0.0);
+        sac_ens_critic_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p), st>>>(p, dq, w, dactions);
+        M3L_LAUNCH_CHECK();
+    }
+    if (grads == nullptr) return 0;
+    return sac_ens_wgrad_launches(wgrad, p, w, grads, st);
+}
+
+int sac_ens_td_target_impl(const char* who, const m3l_sac_ens_desc* d, int B, const float* x_next, const float* noise, const float* rewards,
+                           const float* dones, const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, const int* subset,
+                           int n_subset, float* target_q, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "%s: unsupported shape: %s", who, why);
+    if (sac_ens_params_ok(d, SAC_ACTOR | SAC_CRITIC, who)) return 1;
+    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "%s: null argument, or x_next not 16-byte aligned", who);
+    M3L_CHECK(subset != nullptr ? (n_subset >= 1 && n_subset <= d->n_critics) : (n_subset == 0 || n_subset == d->n_critics),
+              "%s: n_subset=%d (1 to n_critics=%d entries; with subset NULL, all of them)", who, n_subset, d->n_critics);
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacEnsArgs p = sac_ens_args(d, B, SAC_ACTOR | SAC_CRITIC);
+    const int m = subset ? n_subset : p.n;
+    ProfScope prof(who, B, p.F, m, ph_net_flops(p.pi, B, p.F, 2 * p.A) + sac_ens_critic_flops(p, m), st, 4.0 * B * p.F);
+    sac_ens_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p), st>>>(p, x_next, noise, rewards, dones, discounts, gamma, ent_coef,
+                                                                               log_ent_coef, subset, m, target_q);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+// twice: the TD3 head's line (sac_ens_critic_loss_kernel)
+int sac_ens_critic_loss_impl(const char* who, bool twice, const float* q, const float* target_q, const float* weights, int N, int B, float* loss,
+                             float* coef, float* td_abs, void* stream) {
+    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "%s: N=%d B=%d (1 <= N <= %d, B >= 1)", who, N, B, M3L_SAC_MAX_CRITICS);
+    M3L_CHECK(q && target_q && loss && coef, "%s: null argument (weights and td_abs may be NULL)", who);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(who, B, N, 0, 7.0 * N * B, st, (8.0 * N + 12.0) * B);
+    if (twice)
+        sac_ens_critic_loss_kernel<true><<<1, 256, 0, st>>>(q, target_q, weights, N, B, loss, coef, td_abs);
+    else
+        sac_ens_critic_loss_kernel<false><<<1, 256, 0, st>>>(q, target_q, weights, N, B, loss, coef, td_abs);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int sac_ens_actor_loss_impl(const char* who, const float* logp, const float* q, int N, int B, int reduce, float ent_coef, const float* log_ent_coef,
+                            float* loss, float* coef, void* stream) {
+    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "%s: N=%d B=%d (1 <= N <= %d, B >= 1)", who, N, B, M3L_SAC_MAX_CRITICS);
+    M3L_CHECK(reduce == 0 || reduce == 1, "%s: reduce=%d (0 = min, 1 = mean)", who, reduce);
+    M3L_CHECK(logp && q && loss && coef, "%s: null argument", who);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(who, B, N, reduce, (2.0 * N + 4.0) * B, st, (8.0 * N + 8.0) * B);
+    sac_ens_actor_loss_kernel<<<1, 256, 0, st>>>(logp, q, N, B, reduce, ent_coef, log_ent_coef, loss, coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int sac_ens_loss_bwd_impl(const char* who, const float* dloss, const float* coef, int n, float* out, void* stream) {
+    M3L_CHECK(n >= 1, "%s: n=%d (n >= 1)", who, n);
+    M3L_CHECK(dloss && coef && out, "%s: null argument", who);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof(who, n, 0, 0, 1.0 * n, st, 8.0 * n);
+    sac_scale_kernel<<<cdiv(n, 256), 256, 0, st>>>(dloss, coef, n, out);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+// The two-critic descriptor as the ensemble's with n_critics = 2, for the entries of "SAC policy head"; NULL stays NULL, which the shape check
+// refuses.  The fields in front of the critics' tables sit at the same offsets in both structs.
+static_assert(offsetof(m3l_sac_desc, qf_weight) == offsetof(m3l_sac_ens_desc, n_critics), "m3l_sac_desc and m3l_sac_ens_desc start alike");
+const m3l_sac_ens_desc* sac_lift(const m3l_sac_desc* d, m3l_sac_ens_desc& e) {
+    if (d == nullptr) return nullptr;
+    memset(&e, 0, sizeof(e));
+    memcpy(&e, d, offsetof(m3l_sac_desc, qf_weight));
+    e.n_critics = 2;
+    for (int c = 0; c < 2; ++c) {
+        for (int l = 0; l < M3L_SAC_MAX_HIDDEN; ++l) { e.qf_weight[c][l] = d->qf_weight[c][l]; e.qf_bias[c][l] = d->qf_bias[c][l]; }
+        e.q_weight[c] = d->q_weight[c]; e.q_bias[c] = d->q_bias[c];
+    }
+    return &e;
+}
+
+// where the critics' part of an m3l_sac_ws_bytes workspace starts: behind the actor's.  0 for a head that the entry's shape check refuses
+long sac_critic_start(const m3l_sac_desc* d, int B) {
+    char why[160];
+    return sac_shape_ok(d, B, why, sizeof(why)) ? sac_args(d, B, 0).total : 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t m3l_sac_ws_bytes(const m3l_sac_desc* d, int B) {
+    char why[160];
+    if (!sac_shape_ok(d, B, why, sizeof(why))) return 256;
+    m3l_sac_ens_desc e;
+    return (size_t)sac_ens_args(sac_lift(d, e), B, 0, sac_critic_start(d, B)).total * sizeof(float);
+}
+
+int m3l_sac_actor_fwd(const m3l_sac_desc* d, int B, const float* x, const float* noise, void* ws, float* actions, float* logp, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_actor_fwd: unsupported shape: %s", why);
+    if (sac_params_ok(d, "sac_actor_fwd")) return 1;
+    M3L_CHECK(x && actions && logp && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_actor_fwd: null argument, or x / ws not 16-byte aligned");
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacArgs p = sac_args(d, B, 1);
+    ProfScope prof("sac_actor_fwd", B, p.F, p.A, sac_actor_flops(p), st, 4.0 * B * p.F);
+    sac_actor_fwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, x, noise, (float*)ws, actions, logp);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+int m3l_sac_actor_bwd(const m3l_sac_desc* d, int B, const float* x, const float* noise, const float* dactions, const float* dlogp, void* ws, float* dx,
+                      const m3l_sac_desc* grads, void* stream) {
+    char why[160];
+    M3L_CHECK(sac_shape_ok(d, B, why, sizeof(why)), "sac_actor_bwd: unsupported shape: %s", why);
+    if (sac_params_ok(d, "sac_actor_bwd")) return 1;
+    M3L_CHECK(grads != nullptr && grads->n_pi == d->n_pi, "sac_actor_bwd: the gradient descriptor is null or has another layer count");
+    if (sac_params_ok(grads, "sac_actor_bwd (gradients)")) return 1;
+    M3L_CHECK(x && ws && dx && ph_aligned(x) && ph_aligned(ws) && ph_aligned(dx), "sac_actor_bwd: null argument, or x / ws / dx not 16-byte aligned");
+    if (sac_init()) return 2;
+    hipStream_t st = (hipStream_t)stream;
+    const SacArgs p = sac_args(d, B, 1);
+    float* w = (float*)ws;
+    PhWgrad q;
+    memset(&q, 0, sizeof(q));
+    q.B = B;
+    ph_add_net(q, p.pi, w, x, p.F, p.F, grads->pi_weight, grads->pi_bias, p.A,
+               {{w + p.dmu_off, grads->mu_weight, grads->mu_bias}, {w + p.ds_off, grads->log_std_weight, grads->log_std_bias}});
+    {
+        ProfScope prof("sac_actor_bwd_chain", B, p.F, p.A, sac_actor_flops(p), st, 4.0 * B * p.F);
+        sac_actor_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_lds_bytes(p), st>>>(p, noise, dactions, dlogp, w, dx);
+        M3L_LAUNCH_CHECK();
+    }
+    {
+        ProfScope prof("sac_actor_wgrad", B, q.items, p.A, sac_actor_flops(p), st, 0.0);
+        sac_wgrad_kernel<<<cdiv(q.items, 4), 256, 0, st>>>(q);
+        M3L_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int m3l_sac_critic_fwd(const m3l_sac_desc* d, int B, const float* x, const float* actions, void* ws, float* q, void* stream) {
+    m3l_sac_ens_desc e;
+    return sac_ens_critic_fwd_impl("sac_critic_fwd", sac_lift(d, e), B, x, actions, ws, sac_critic_start(d, B), q, stream);
+}
+
+int m3l_sac_critic_bwd(const m3l_sac_desc* d, int B, const float* dq, void* ws, float* dactions, const m3l_sac_desc* grads, void* stream) {
+    m3l_sac_ens_desc e, g;
+    return sac_ens_critic_bwd_impl("sac_critic_bwd", "sac_critic_wgrad", sac_lift(d, e), B, dq, ws, sac_critic_start(d, B), dactions, sac_lift(grads, g),
+                                   stream);
+}
+
+int m3l_sac_td_target(const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones, float gamma,
+                      float ent_coef, const float* log_ent_coef, float* target_q, void* stream) {
+    m3l_sac_ens_desc e;
+    return sac_ens_td_target_impl("sac_td_target", sac_lift(d, e), B, x_next, noise, rewards, dones, nullptr, gamma, ent_coef, log_ent_coef, nullptr, 0,
+                                  target_q, stream);
+}
+
+int m3l_sac_td_target_rows(const m3l_sac_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
+                           const float* discounts, float ent_coef, const float* log_ent_coef, float* target_q, void* stream) {
+    M3L_CHECK(discounts, "sac_td_target_rows: discounts is NULL");
+    m3l_sac_ens_desc e;
+    return sac_ens_td_target_impl("sac_td_target_rows", sac_lift(d, e), B, x_next, noise, rewards, dones, discounts, 0.f, ent_coef, log_ent_coef, nullptr, 0,
+                                  target_q, stream);
+}
+
+int m3l_sac_critic_loss_fwd(const float* q, const float* target_q, int B, float* loss, float* coef, void* stream) {
+    return sac_ens_critic_loss_impl("sac_critic_loss_fwd", false, q, target_q, nullptr, 2, B, loss, coef, nullptr, stream);
+}
+
+int m3l_sac_critic_loss_w_fwd(const float* q, const float* target_q, const float* weights, int B, float* loss, float* coef, float* td_abs,
+                              void* stream) {
+    M3L_CHECK(B >= 1, "sac_critic_loss_w_fwd: B=%d (B >= 1)", B);
+    M3L_CHECK(q && target_q && loss && coef && td_abs, "sac_critic_loss_w_fwd: null argument (weights may be NULL: ones)");
+    return sac_ens_critic_loss_impl("sac_critic_loss_w_fwd", false, q, target_q, weights, 2, B, loss, coef, td_abs, stream);
+}
+
+int m3l_sac_critic_loss_bwd(const float* dloss, const float* coef, int B, float* dq, void* stream) {
+    M3L_CHECK(B >= 1, "sac_critic_loss_bwd: B=%d (B >= 1)", B);
+    return sac_ens_loss_bwd_impl("sac_critic_loss_bwd", dloss, coef, 2 * B, dq, stream);
+}
+
+int m3l_sac_actor_loss_fwd(const float* logp, const float* q, int B, float ent_coef, const float* log_ent_coef, float* loss, float* coef, void* stream) {
+    return sac_ens_actor_loss_impl("sac_actor_loss_fwd", logp, q, 2, B, 0, ent_coef, log_ent_coef, loss, coef, stream);
+}
+
+int m3l_sac_actor_loss_bwd(const float* dloss, const float* coef, int B, float* dlogp_dq, void* stream) {
+    M3L_CHECK(B >= 1, "sac_actor_loss_bwd: B=%d (B >= 1)", B);
+    return sac_ens_loss_bwd_impl("sac_actor_loss_bwd", dloss, coef, 3 * B, dlogp_dq, stream);
+}
+
+int m3l_sac_ent_coef_loss(const float* log_ent_coef, const float* logp, float target_entropy, int B, const float* dloss, float* loss, float* ent_coef,
+                          float* dlog_ent_coef, void* stream) {
+    M3L_CHECK(B >= 1, "sac_ent_coef_loss: B=%d (B >= 1)", B);
+    M3L_CHECK(log_ent_coef && logp && (loss || ent_coef || dlog_ent_coef), "sac_ent_coef_loss: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope prof("sac_ent_coef_loss", B, 0, 0, 2.0 * B, st, 4.0 * B);
+    sac_ent_coef_loss_kernel<<<1, 256, 0, st>>>(log_ent_coef, logp, target_entropy, B, dloss, loss, ent_coef, dlog_ent_coef);
+    M3L_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- SAC critic ensemble (include/m3l_amd.h "SAC critic ensemble")
 
 size_t m3l_sac_ens_ws_bytes(const m3l_sac_ens_desc* d, int B) {
     char why[160];
@@ -892,91 +777,32 @@ size_t m3l_sac_ens_ws_bytes(const m3l_sac_ens_desc* d, int B) {
 }
 
 int m3l_sac_ens_critic_fwd(const m3l_sac_ens_desc* d, int B, const float* x, const float* actions, void* ws, float* q, void* stream) {
-    char why[160];
-    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "sac_ens_critic_fwd: unsupported shape: %s", why);
-    if (sac_ens_params_ok(d, SAC_CRITIC, "sac_ens_critic_fwd")) return 1;
-    M3L_CHECK(x && actions && q && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_ens_critic_fwd: null argument, or x / ws not 16-byte aligned");
-    if (sac_ens_init()) return 2;
-    hipStream_t st = (hipStream_t)stream;
-    const SacEnsArgs p = sac_ens_args(d, B, SAC_CRITIC);
-    ProfScope prof("sac_ens_critic_fwd", B, p.F, p.n, sac_ens_critic_flops(p, p.n), st, 4.0 * B * p.K0);
-    sac_ens_critic_fwd_kernel<<<dim3(cdiv(B, PH_TM), p.n), 256, sac_ens_lds_bytes(p), st>>>(p, x, actions, (float*)ws, q);
-    M3L_LAUNCH_CHECK();
-    return 0;
+    return sac_ens_critic_fwd_impl("sac_ens_critic_fwd", d, B, x, actions, ws, 0, q, stream);
 }
 
 int m3l_sac_ens_critic_bwd(const m3l_sac_ens_desc* d, int B, const float* dq, void* ws, float* dactions, const m3l_sac_ens_desc* grads, void* stream) {
-    char why[160];
-    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "sac_ens_critic_bwd: unsupported shape: %s", why);
-    if (sac_ens_params_ok(d, SAC_CRITIC, "sac_ens_critic_bwd")) return 1;
-    M3L_CHECK(grads == nullptr || (grads->n_qf == d->n_qf && grads->n_critics == d->n_critics),
-              "sac_ens_critic_bwd: the gradient descriptor has another layer or critic count");
-    if (grads != nullptr && sac_ens_params_ok(grads, SAC_CRITIC, "sac_ens_critic_bwd (gradients)")) return 1;
-    M3L_CHECK(ws && ph_aligned(ws), "sac_ens_critic_bwd: ws is null or not 16-byte aligned");
-    if (sac_ens_init()) return 2;
-    hipStream_t st = (hipStream_t)stream;
-    const SacEnsArgs p = sac_ens_args(d, B, SAC_CRITIC);
-    float* w = (float*)ws;
-    {
-        ProfScope prof("sac_ens_critic_bwd_chain", B, p.F, p.n, sac_ens_critic_flops(p, p.n), st, 0.0);
-        sac_ens_critic_bwd_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p), st>>>(p, dq, w, dactions);
-        M3L_LAUNCH_CHECK();
-    }
-    if (grads == nullptr) return 0;
-    return sac_ens_wgrad_launches(p, w, grads, st);
+    return sac_ens_critic_bwd_impl("sac_ens_critic_bwd", "sac_ens_critic_wgrad", d, B, dq, ws, 0, dactions, grads, stream);
 }
 
 int m3l_sac_ens_td_target(const m3l_sac_ens_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
                           const float* discounts, float gamma, float ent_coef, const float* log_ent_coef, const int* subset, int n_subset,
                           float* target_q, void* stream) {
-    char why[160];
-    M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "sac_ens_td_target: unsupported shape: %s", why);
-    if (sac_ens_params_ok(d, SAC_ACTOR | SAC_CRITIC, "sac_ens_td_target")) return 1;
-    M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "sac_ens_td_target: null argument, or x_next not 16-byte aligned");
-    M3L_CHECK(subset != nullptr ? (n_subset >= 1 && n_subset <= d->n_critics) : (n_subset == 0 || n_subset == d->n_critics),
-              "sac_ens_td_target: n_subset=%d (1 to n_critics=%d entries; with subset NULL, all of them)", n_subset, d->n_critics);
-    if (sac_ens_init()) return 2;
-    hipStream_t st = (hipStream_t)stream;
-    const SacEnsArgs p = sac_ens_args(d, B, SAC_ACTOR | SAC_CRITIC);
-    const int m = subset ? n_subset : p.n;
-    ProfScope prof("sac_ens_td_target", B, p.F, m, ph_net_flops(p.pi, B, p.F, 2 * p.A) + sac_ens_critic_flops(p, m), st, 4.0 * B * p.F);
-    sac_ens_td_target_kernel<<<cdiv(B, PH_TM), 256, sac_ens_lds_bytes(p), st>>>(p, x_next, noise, rewards, dones, discounts, gamma, ent_coef,
-                                                                               log_ent_coef, subset, m, target_q);
-    M3L_LAUNCH_CHECK();
-    return 0;
+    return sac_ens_td_target_impl("sac_ens_td_target", d, B, x_next, noise, rewards, dones, discounts, gamma, ent_coef, log_ent_coef, subset, n_subset,
+                                  target_q, stream);
 }
 
 int m3l_sac_ens_critic_loss_fwd(const float* q, const float* target_q, const float* weights, int N, int B, float* loss, float* coef, float* td_abs,
                                 void* stream) {
-    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "sac_ens_critic_loss_fwd: N=%d B=%d (1 <= N <= %d, B >= 1)", N, B, M3L_SAC_MAX_CRITICS);
-    M3L_CHECK(q && target_q && loss && coef, "sac_ens_critic_loss_fwd: null argument (weights and td_abs may be NULL)");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_ens_critic_loss_fwd", B, N, 0, 7.0 * N * B, st, (8.0 * N + 12.0) * B);
-    sac_ens_critic_loss_kernel<false><<<1, 256, 0, st>>>(q, target_q, weights, N, B, loss, coef, td_abs);
-    M3L_LAUNCH_CHECK();
-    return 0;
+    return sac_ens_critic_loss_impl("sac_ens_critic_loss_fwd", false, q, target_q, weights, N, B, loss, coef, td_abs, stream);
 }
 
 int m3l_sac_ens_actor_loss_fwd(const float* logp, const float* q, int N, int B, int reduce, float ent_coef, const float* log_ent_coef, float* loss,
                                float* coef, void* stream) {
-    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "sac_ens_actor_loss_fwd: N=%d B=%d (1 <= N <= %d, B >= 1)", N, B, M3L_SAC_MAX_CRITICS);
-    M3L_CHECK(reduce == 0 || reduce == 1, "sac_ens_actor_loss_fwd: reduce=%d (0 = min, 1 = mean)", reduce);
-    M3L_CHECK(logp && q && loss && coef, "sac_ens_actor_loss_fwd: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_ens_actor_loss_fwd", B, N, reduce, (2.0 * N + 4.0) * B, st, (8.0 * N + 8.0) * B);
-    sac_ens_actor_loss_kernel<<<1, 256, 0, st>>>(logp, q, N, B, reduce, ent_coef, log_ent_coef, loss, coef);
-    M3L_LAUNCH_CHECK();
-    return 0;
+    return sac_ens_actor_loss_impl("sac_ens_actor_loss_fwd", logp, q, N, B, reduce, ent_coef, log_ent_coef, loss, coef, stream);
 }
 
 int m3l_sac_ens_loss_bwd(const float* dloss, const float* coef, int n, float* out, void* stream) {
-    M3L_CHECK(n >= 1, "sac_ens_loss_bwd: n=%d (n >= 1)", n);
-    M3L_CHECK(dloss && coef && out, "sac_ens_loss_bwd: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("sac_ens_loss_bwd", n, 0, 0, 1.0 * n, st, 8.0 * n);
-    sac_scale_kernel<<<cdiv(n, 256), 256, 0, st>>>(dloss, coef, n, out);
-    M3L_LAUNCH_CHECK();
-    return 0;
+    return sac_ens_loss_bwd_impl("sac_ens_loss_bwd", dloss, coef, n, out, stream);
 }
 
 }  // extern "C"
@@ -1168,7 +994,7 @@ int sac_droq_shape_ok(const m3l_sac_droq_desc* d, int B, char* why, size_t n) {
     return sac_ens_shape_ok(&d->ens, B, why, n);
 }
 
-// the ensemble's arguments and workspace layout, then the DroQ path's own places behind them; parts as in sac_args
+// the ensemble's arguments and workspace layout, then the DroQ path's own places behind them; parts as in sac_ens_args
 SacDroqArgs sac_droq_args(const m3l_sac_droq_desc* d, int B, int parts) {
     SacDroqArgs p;
     memset(&p, 0, sizeof(p));
@@ -1209,17 +1035,6 @@ int sac_droq_params_ok(const m3l_sac_droq_desc* d, int parts, const char* who) {
     return 0;
 }
 
-int g_sac_droq_inited = 0;
-int sac_droq_init() {
-    if (g_sac_droq_inited) return 0;
-    if (ph_allow_lds({(const void*)sac_droq_critic_fwd_kernel<false>, (const void*)sac_droq_critic_fwd_kernel<true>,
-                      (const void*)sac_droq_critic_bwd_kernel<false>, (const void*)sac_droq_critic_bwd_kernel<true>,
-                      (const void*)sac_droq_td_target_kernel<false>, (const void*)sac_droq_td_target_kernel<true>}, SAC_LDS_MAX))
-        return 2;
-    g_sac_droq_inited = 1;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1235,7 +1050,7 @@ int m3l_sac_droq_critic_fwd(const m3l_sac_droq_desc* d, int B, const float* x, c
     M3L_CHECK(sac_droq_shape_ok(d, B, why, sizeof(why)), "sac_droq_critic_fwd: unsupported shape: %s", why);
     if (sac_droq_params_ok(d, SAC_CRITIC, "sac_droq_critic_fwd")) return 1;
     M3L_CHECK(x && actions && q && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "sac_droq_critic_fwd: null argument, or x / ws not 16-byte aligned");
-    if (sac_droq_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const SacDroqArgs p = sac_droq_args(d, B, SAC_CRITIC);
     const dim3 grid(cdiv(B, PH_TM), p.e.n);
@@ -1257,7 +1072,7 @@ int m3l_sac_droq_critic_bwd(const m3l_sac_droq_desc* d, int B, const float* dq, 
               "sac_droq_critic_bwd: the gradient descriptor has another layer or critic count");
     if (grads != nullptr && sac_droq_params_ok(grads, SAC_CRITIC, "sac_droq_critic_bwd (gradients)")) return 1;
     M3L_CHECK(ws && ph_aligned(ws), "sac_droq_critic_bwd: ws is null or not 16-byte aligned");
-    if (sac_droq_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const SacDroqArgs p = sac_droq_args(d, B, SAC_CRITIC);
     float* w = (float*)ws;
@@ -1270,7 +1085,7 @@ int m3l_sac_droq_critic_bwd(const m3l_sac_droq_desc* d, int B, const float* dq, 
         M3L_LAUNCH_CHECK();
     }
     if (grads == nullptr) return 0;
-    if (const int rc = sac_ens_wgrad_launches(p.e, w, &grads->ens, st)) return rc;
+    if (const int rc = sac_ens_wgrad_launches("sac_ens_critic_wgrad", p.e, w, &grads->ens, st)) return rc;
     SacLnGrad a;
     memset(&a, 0, sizeof(a));
     a.B = B;
@@ -1301,7 +1116,7 @@ int m3l_sac_droq_td_target(const m3l_sac_droq_desc* d, int B, const float* x_nex
     M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "sac_droq_td_target: null argument, or x_next not 16-byte aligned");
     M3L_CHECK(subset != nullptr ? (n_subset >= 1 && n_subset <= d->ens.n_critics) : (n_subset == 0 || n_subset == d->ens.n_critics),
               "sac_droq_td_target: n_subset=%d (1 to n_critics=%d entries; with subset NULL, all of them)", n_subset, d->ens.n_critics);
-    if (sac_droq_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const SacDroqArgs p = sac_droq_args(d, B, SAC_ACTOR | SAC_CRITIC);
     const int m = subset ? n_subset : p.e.n;
@@ -1409,7 +1224,7 @@ __device__ __forceinline__ float tqc_unkey(int k) { return __int_as_float(k ^ ((
 // grid (row tiles).  The critic pointers of p are the target critics'.  Per row tile: the actor, then the n target critics one after another,
 // each leaving its nq columns in the pool [16, n nq] behind the two activation buffers; then every row's pool is ranked (16 lanes per row, an
 // element's rank = how many elements come before it by (key, index): a stable count, every rank 0 .. pool - 1 taken exactly once) and the
-// K lowest ranks go through the Bellman line into target [B, K].  discounts as in sac_td_target_kernel.
+// K lowest ranks go through the Bellman line into target [B, K].  discounts as in sac_ens_td_target_kernel.
 __global__ __launch_bounds__(256) void sac_tqc_td_target_kernel(SacTqcArgs p, const float* __restrict__ x, const float* __restrict__ noise,
                                                                 const float* __restrict__ rewards, const float* __restrict__ dones,
                                                                 const float* __restrict__ discounts, float gamma, float ent_coef,
@@ -1571,15 +1386,6 @@ SacTqcArgs sac_tqc_args(const m3l_tqc_desc* d, int B, int parts) {
 }
 
 #define TQC_POOL_LDS_MAX (PH_TM * (M3L_TQC_MAX_POOL + 1) * 4)
-int g_sac_tqc_inited = 0;
-int sac_tqc_init() {
-    if (g_sac_tqc_inited) return 0;
-    if (ph_allow_lds({(const void*)sac_tqc_critic_fwd_kernel, (const void*)sac_tqc_critic_bwd_kernel}, SAC_LDS_MAX)) return 2;
-    if (ph_allow_lds({(const void*)sac_tqc_td_target_kernel}, SAC_LDS_MAX + TQC_POOL_LDS_MAX)) return 2;
-    g_sac_tqc_inited = 1;
-    return 0;
-}
-
 int sac_tqc_loss_dims_ok(const char* who, int N, int B, int nq) {
     M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS && nq >= 1 && nq <= PH_HLD, "%s: N=%d B=%d n_quantiles=%d (1 <= N <= %d, B >= 1, 1 <= n_quantiles <= %d)",
               who, N, B, nq, M3L_SAC_MAX_CRITICS, PH_HLD);
@@ -1602,7 +1408,7 @@ int m3l_tqc_critic_fwd(const m3l_tqc_desc* d, int B, const float* x, const float
     M3L_CHECK(sac_tqc_shape_ok(d, B, why, sizeof(why)), "tqc_critic_fwd: unsupported shape: %s", why);
     if (sac_ens_params_ok(&d->ens, SAC_CRITIC, "tqc_critic_fwd")) return 1;
     M3L_CHECK(x && actions && z && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "tqc_critic_fwd: null argument, or x / ws not 16-byte aligned");
-    if (sac_tqc_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const SacTqcArgs p = sac_tqc_args(d, B, SAC_CRITIC);
     ProfScope prof("tqc_critic_fwd", B, p.e.F, p.e.n, (double)p.e.n * ph_net_flops(p.e.qf[0], B, p.e.K0, p.nq), st, 4.0 * B * p.e.K0);
@@ -1619,7 +1425,7 @@ int m3l_tqc_critic_bwd(const m3l_tqc_desc* d, int B, const float* dz, void* ws, 
               "tqc_critic_bwd: the gradient descriptor has another layer or critic count");
     if (grads != nullptr && sac_ens_params_ok(&grads->ens, SAC_CRITIC, "tqc_critic_bwd (gradients)")) return 1;
     M3L_CHECK(ws && ph_aligned(ws), "tqc_critic_bwd: ws is null or not 16-byte aligned");
-    if (sac_tqc_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const SacTqcArgs p = sac_tqc_args(d, B, SAC_CRITIC);
     float* w = (float*)ws;
@@ -1629,7 +1435,7 @@ int m3l_tqc_critic_bwd(const m3l_tqc_desc* d, int B, const float* dz, void* ws, 
         M3L_LAUNCH_CHECK();
     }
     if (grads == nullptr) return 0;
-    return sac_ens_wgrad_launches(p.e, w, &grads->ens, st, p.nq);
+    return sac_ens_wgrad_launches("sac_ens_critic_wgrad", p.e, w, &grads->ens, st, p.nq);
 }
 
 int m3l_tqc_td_target(const m3l_tqc_desc* d, int B, const float* x_next, const float* noise, const float* rewards, const float* dones,
@@ -1638,7 +1444,7 @@ int m3l_tqc_td_target(const m3l_tqc_desc* d, int B, const float* x_next, const f
     M3L_CHECK(sac_tqc_shape_ok(d, B, why, sizeof(why)), "tqc_td_target: unsupported shape: %s", why);
     if (sac_ens_params_ok(&d->ens, SAC_ACTOR | SAC_CRITIC, "tqc_td_target")) return 1;
     M3L_CHECK(x_next && rewards && dones && target && ph_aligned(x_next), "tqc_td_target: null argument, or x_next not 16-byte aligned");
-    if (sac_tqc_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const SacTqcArgs p = sac_tqc_args(d, B, SAC_ACTOR | SAC_CRITIC);
     ProfScope prof("tqc_td_target", B, p.e.F, p.e.n, ph_net_flops(p.e.pi, B, p.e.F, 2 * p.e.A) + (double)p.e.n * ph_net_flops(p.e.qf[0], B, p.e.K0, p.nq), st,
@@ -1777,7 +1583,7 @@ __global__ __launch_bounds__(256) void td3_actor_bwd_kernel(Td3Args p, const flo
 }
 
 // grid (row tiles).  The actor of p is whichever the caller put in (the target actor, or the online one); the critics are the target critics.
-// a' = smooth(actor(x'), noise) stays in LDS and goes to all n critics, ascending; discounts as in sac_td_target_kernel.
+// a' = smooth(actor(x'), noise) stays in LDS and goes to all n critics, ascending; discounts as in sac_ens_td_target_kernel.
 __global__ __launch_bounds__(256) void td3_td_target_kernel(SacEnsArgs p, const float* __restrict__ x, const float* __restrict__ noise, float sigma, float clip,
                                                             const float* __restrict__ rewards, const float* __restrict__ dones,
                                                             const float* __restrict__ discounts, float gamma, float* __restrict__ target_q) {
@@ -1859,14 +1665,6 @@ int td3_noise_ok(const char* who, float sigma) {
     return 0;
 }
 
-int g_td3_inited = 0;
-int td3_init() {
-    if (g_td3_inited) return 0;
-    if (ph_allow_lds({(const void*)td3_actor_fwd_kernel, (const void*)td3_actor_bwd_kernel, (const void*)td3_td_target_kernel}, SAC_LDS_MAX)) return 2;
-    g_td3_inited = 1;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1884,7 +1682,7 @@ int m3l_td3_actor_fwd(const m3l_sac_ens_desc* d, int B, const float* x, const fl
     M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "td3_actor_fwd: unsupported shape: %s", why);
     if (td3_actor_ok(d, "td3_actor_fwd") || td3_noise_ok("td3_actor_fwd", sigma)) return 1;
     M3L_CHECK(x && actions && ph_aligned(x) && (ws == nullptr || ph_aligned(ws)), "td3_actor_fwd: null argument, or x / ws not 16-byte aligned");
-    if (td3_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const Td3Args p = td3_args(d, B, SAC_ACTOR);
     ProfScope prof("td3_actor_fwd", B, p.e.F, p.e.A, ph_net_flops(p.e.pi, B, p.e.F, p.e.A), st, 4.0 * B * p.e.F);
@@ -1902,7 +1700,7 @@ int m3l_td3_actor_bwd(const m3l_sac_ens_desc* d, int B, const float* x, const fl
     if (td3_actor_ok(grads, "td3_actor_bwd (gradients)")) return 1;
     M3L_CHECK(x && dactions && ws && dx && ph_aligned(x) && ph_aligned(ws) && ph_aligned(dx),
               "td3_actor_bwd: null argument, or x / ws / dx not 16-byte aligned");
-    if (td3_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const Td3Args p = td3_args(d, B, SAC_ACTOR);
     float* w = (float*)ws;
@@ -1927,7 +1725,7 @@ int m3l_td3_td_target(const m3l_sac_ens_desc* d, int B, const float* x_next, con
     M3L_CHECK(sac_ens_shape_ok(d, B, why, sizeof(why)), "td3_td_target: unsupported shape: %s", why);
     if (td3_actor_ok(d, "td3_td_target") || sac_ens_params_ok(d, SAC_CRITIC, "td3_td_target") || td3_noise_ok("td3_td_target", sigma)) return 1;
     M3L_CHECK(x_next && rewards && dones && target_q && ph_aligned(x_next), "td3_td_target: null argument, or x_next not 16-byte aligned");
-    if (td3_init()) return 2;
+    if (sac_init()) return 2;
     hipStream_t st = (hipStream_t)stream;
     const SacEnsArgs p = sac_ens_args(d, B, SAC_ACTOR | SAC_CRITIC);
     ProfScope prof("td3_td_target", B, p.F, p.n, ph_net_flops(p.pi, B, p.F, p.A) + sac_ens_critic_flops(p, p.n), st, 4.0 * B * p.F);
@@ -1938,13 +1736,7 @@ int m3l_td3_td_target(const m3l_sac_ens_desc* d, int B, const float* x_next, con
 
 int m3l_td3_critic_loss_fwd(const float* q, const float* target_q, const float* weights, int N, int B, float* loss, float* coef, float* td_abs,
                             void* stream) {
-    M3L_CHECK(B >= 1 && N >= 1 && N <= M3L_SAC_MAX_CRITICS, "td3_critic_loss_fwd: N=%d B=%d (1 <= N <= %d, B >= 1)", N, B, M3L_SAC_MAX_CRITICS);
-    M3L_CHECK(q && target_q && loss && coef, "td3_critic_loss_fwd: null argument (weights and td_abs may be NULL)");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope prof("td3_critic_loss_fwd", B, N, 0, 7.0 * N * B, st, (8.0 * N + 12.0) * B);
-    sac_ens_critic_loss_kernel<true><<<1, 256, 0, st>>>(q, target_q, weights, N, B, loss, coef, td_abs);
-    M3L_LAUNCH_CHECK();
-    return 0;
+    return sac_ens_critic_loss_impl("td3_critic_loss_fwd", true, q, target_q, weights, N, B, loss, coef, td_abs, stream);
 }
 
 int m3l_td3_actor_loss_fwd(const float* q, int N, int B, int reduce, float* loss, float* coef, void* stream) {
@@ -1959,3 +1751,24 @@ int m3l_td3_actor_loss_fwd(const float* q, int N, int B, int reduce, float* loss
 }
 
 }  // extern "C"
+
+namespace {
+
+// Every kernel of this file with dynamic LDS may ask for the two widest activation buffers; the TQC TD target also for its pool behind them.
+int sac_init() {
+    static int inited = 0;
+    if (inited) return 0;
+    if (ph_allow_lds({(const void*)sac_actor_fwd_kernel, (const void*)sac_actor_bwd_kernel, (const void*)sac_ens_critic_fwd_kernel,
+                      (const void*)sac_ens_critic_bwd_kernel, (const void*)sac_ens_td_target_kernel,
+                      (const void*)sac_droq_critic_fwd_kernel<false>, (const void*)sac_droq_critic_fwd_kernel<true>,
+                      (const void*)sac_droq_critic_bwd_kernel<false>, (const void*)sac_droq_critic_bwd_kernel<true>,
+                      (const void*)sac_droq_td_target_kernel<false>, (const void*)sac_droq_td_target_kernel<true>,
+                      (const void*)sac_tqc_critic_fwd_kernel, (const void*)sac_tqc_critic_bwd_kernel,
+                      (const void*)td3_actor_fwd_kernel, (const void*)td3_actor_bwd_kernel, (const void*)td3_td_target_kernel}, SAC_LDS_MAX))
+        return 2;
+    if (ph_allow_lds({(const void*)sac_tqc_td_target_kernel}, SAC_LDS_MAX + TQC_POOL_LDS_MAX)) return 2;
+    inited = 1;
+    return 0;
+}
+
+}  // namespace

@@ -69,8 +69,7 @@ def _read_policy(policy, n_critics):
     if not isinstance(getattr(actor, "log_std", None), nn.Linear):
         raise ValueError("actor.log_std is not an nn.Linear: the HIP SAC head computes a state-dependent log_std (use_sde=False) only")
     for c in (critic, target):
-        if not getattr(c, "share_features_extractor", True):
-            raise ValueError("share_features_extractor=False: the HIP SAC head takes one feature vector for the actor and the critics")
+        H.require_shared_extractor(c, "SAC")
     pi = H.linear_pairs(actor.latent_pi, "actor.latent_pi", nn.ReLU, "SAC")
     qf = tuple(_q_net(getattr(critic, f"qf{i}"), f"critic.qf{i}") for i in range(n_critics))
     qt = tuple(_q_net(getattr(target, f"qf{i}"), f"critic_target.qf{i}") for i in range(n_critics))
@@ -87,8 +86,7 @@ def _q_net(seq, name):
 def _reject_flags(policy):
     if getattr(policy, "use_sde", False):
         raise ValueError("use_sde=True (generalised state-dependent exploration) is not computed by the HIP SAC head")
-    if not getattr(policy, "share_features_extractor", True):
-        raise ValueError("share_features_extractor=False: the HIP SAC head takes one feature vector for the actor and the critics")
+    H.require_shared_extractor(policy, "SAC")
 
 
 def _reject_sac_flags(policy):
@@ -341,14 +339,7 @@ def q_values(params: SACHeadParams, features, actions, target=False, param_grads
     H.require_params(flat, "SAC head parameter")
     x = H.features_of(features, on_tape=False)
     arch = _arch(x.shape[1], params)
-    _require_cuda(actions, "actions")
-    if actions.dim() != 2 or actions.shape[1] != arch[1]:
-        raise ValueError(f"actions: (B, {arch[1]}) expected, got {tuple(actions.shape)}")
-    if actions.shape[0] != x.shape[0]:
-        raise ValueError(f"{x.shape[0]} feature rows but {actions.shape[0]} action rows")
-    a = actions.float().contiguous()
-    if a.data_ptr() % 16:
-        a = a.clone()
+    a = H.actions_of(actions, x.shape[0], arch[1])
     want = param_grads and any(t.requires_grad for t in flat)
     store = torch.is_grad_enabled() and (a.requires_grad or want)
     return SACCriticFn.apply(x, a, arch, store, want, *flat)
@@ -403,11 +394,7 @@ def critic_loss_from(q, target_q, weights=None, return_td_errors=False):
         raise ValueError(f"q: (2, B) float32 expected, got {tuple(q.shape)} {q.dtype}")
     if weights is None and not return_td_errors:
         return SACCriticLossFn.apply(q.contiguous(), _vec(target_q, "target_q", B))
-    if weights is not None:
-        _require_cuda(weights, "weights")
-        if weights.dtype != torch.float32 or tuple(weights.shape) not in ((B,), (B, 1)):
-            raise ValueError(f"weights: a float32 tensor of shape ({B},) or ({B}, 1) expected, got {tuple(weights.shape)} {weights.dtype}")
-        weights = _vec(weights, "weights", B)
+    weights = H.weights_of(weights, B)
     loss, td = SACCriticLossWFn.apply(q.contiguous(), _vec(target_q, "target_q", B), weights)
     return (loss, td) if return_td_errors else loss
 

@@ -301,9 +301,7 @@ class SACEnsCriticLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dtd):
         coef = ctx.saved
-        dq = torch.empty_like(coef)
-        L.check(L.lib().m3l_sac_ens_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), coef.numel(), L.ptr(dq), _stream()), "m3l_sac_ens_loss_bwd")
-        return dq, None, None, None
+        return H.scale_coef(dloss, coef), None, None, None
 
 
 class SACEnsActorLossFn(torch.autograd.Function):
@@ -323,8 +321,7 @@ class SACEnsActorLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss):
         coef = ctx.saved
-        out = torch.empty_like(coef)
-        L.check(L.lib().m3l_sac_ens_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), coef.numel(), L.ptr(out), _stream()), "m3l_sac_ens_loss_bwd")
+        out = H.scale_coef(dloss, coef)
         return out[0], out[1:], None, None, None
 
 
@@ -387,14 +384,7 @@ def q_values(params: SACEnsembleParams, features, actions, target=False, param_g
     x = H.features_of(features, on_tape=False)
     arch = S._arch(x.shape[1], params)
     ln = _ln_of(params, arch, target)
-    _require_cuda(actions, "actions")
-    if actions.dim() != 2 or actions.shape[1] != arch[1]:
-        raise ValueError(f"actions: (B, {arch[1]}) expected, got {tuple(actions.shape)}")
-    if actions.shape[0] != x.shape[0]:
-        raise ValueError(f"{x.shape[0]} feature rows but {actions.shape[0]} action rows")
-    a = actions.float().contiguous()
-    if a.data_ptr() % 16:
-        a = a.clone()
+    a = H.actions_of(actions, x.shape[0], arch[1])
     want = param_grads and any(t.requires_grad for t in flat + ln)
     store = torch.is_grad_enabled() and (a.requires_grad or want)
     if not params.layer_norm:
@@ -444,11 +434,7 @@ def critic_loss_from(q, target_q, weights=None, return_td_errors=False):
     """0.5 * sum_c mean(weights * (q_c - target_q)^2) from q (N, B) of `q_values`; weights (B,) or (B, 1) float32 or None (ones).
     return_td_errors: (loss, td) with td (B,) the mean over the critics of |q_c - target_q|, detached: what `update_priorities` takes."""
     q, _, B = _q_of(q)
-    if weights is not None:
-        _require_cuda(weights, "weights")
-        if weights.dtype != torch.float32 or tuple(weights.shape) not in ((B,), (B, 1)):
-            raise ValueError(f"weights: a float32 tensor of shape ({B},) or ({B}, 1) expected, got {tuple(weights.shape)} {weights.dtype}")
-        weights = _vec(weights, "weights", B)
+    weights = H.weights_of(weights, B)
     loss, td = SACEnsCriticLossFn.apply(q, _vec(target_q, "target_q", B), weights, bool(return_td_errors))
     return (loss, td) if return_td_errors else loss
 

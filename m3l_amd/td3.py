@@ -25,7 +25,7 @@ from . import _lib as L
 from . import sac_ensemble as SE
 from ._head import _dev, _vec
 from .dino import update_moving_average
-from .functional import _require_cuda, _stream, _ws
+from .functional import _stream, _ws
 from .sac import MAX_CRITICS, WB, _gamma_of, _q_net
 
 Q_REDUCE = {"first": 0, "min": 0, "mean": 1}          # the kernel's reduce code; "first" hands it critic 0 alone
@@ -56,13 +56,11 @@ class TD3Params(NamedTuple):
     def from_policy(policy) -> "TD3Params":
         """From a module with SB3's `TD3Policy` attribute names (`actor.mu`, `actor_target.mu`, `critic.qf0 ..`, `critic_target.qf0 ..`): a
         `TD3Head`, or an SB3 policy, whose configuration is checked against what the kernels compute."""
-        if not getattr(policy, "share_features_extractor", True):
-            raise ValueError("share_features_extractor=False: the HIP TD3 head takes one feature vector for the actor and the critics")
+        H.require_shared_extractor(policy, "TD3")
         counts = []
         for name in ("critic", "critic_target"):
             c = getattr(policy, name)
-            if not getattr(c, "share_features_extractor", True):
-                raise ValueError(f"{name}: share_features_extractor=False: the HIP TD3 head takes one feature vector for the actor and the critics")
+            H.require_shared_extractor(c, "TD3", name)
             n = 0
             while hasattr(c, f"qf{n}"):
                 n += 1
@@ -213,9 +211,7 @@ class TD3CriticLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dtd):
         coef = ctx.saved
-        dq = torch.empty_like(coef)
-        L.check(L.lib().m3l_sac_ens_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), coef.numel(), L.ptr(dq), _stream()), "m3l_sac_ens_loss_bwd")
-        return dq, None, None, None
+        return H.scale_coef(dloss, coef), None, None, None
 
 
 class TD3ActorLossFn(torch.autograd.Function):
@@ -233,9 +229,7 @@ class TD3ActorLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss):
         coef = ctx.saved
-        dq = torch.empty_like(coef)
-        L.check(L.lib().m3l_sac_ens_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), coef.numel(), L.ptr(dq), _stream()), "m3l_sac_ens_loss_bwd")
-        return dq, None
+        return H.scale_coef(dloss, coef), None
 
 
 def actions(params: TD3Params, features, noise=None, noise_std=0.0, noise_clip=None):
@@ -261,14 +255,7 @@ def q_values(params: TD3Params, features, actions, target=False, param_grads=Tru
     x = H.features_of(features, on_tape=False)
     arch = _arch(x.shape[1], params)
     flat = flat[:2 * n * (len(arch[3]) + 1)]
-    _require_cuda(actions, "actions")
-    if actions.dim() != 2 or actions.shape[1] != arch[1]:
-        raise ValueError(f"actions: (B, {arch[1]}) expected, got {tuple(actions.shape)}")
-    if actions.shape[0] != x.shape[0]:
-        raise ValueError(f"{x.shape[0]} feature rows but {actions.shape[0]} action rows")
-    a = actions.float().contiguous()
-    if a.data_ptr() % 16:
-        a = a.clone()
+    a = H.actions_of(actions, x.shape[0], arch[1])
     want = param_grads and any(t.requires_grad for t in flat)
     store = torch.is_grad_enabled() and (a.requires_grad or want)
     return SE.SACEnsCriticFn.apply(x, a, arch, n, store, want, *flat)
@@ -301,11 +288,7 @@ def critic_loss_from(q, target_q, weights=None, return_td_errors=False):
     """sum_c mean(weights * (q_c - target_q)^2) from q (N, B) of `q_values`; weights (B,) or (B, 1) float32 or None (ones).
     return_td_errors: (loss, td) with td (B,) the mean over the critics of |q_c - target_q|, detached: what `update_priorities` takes."""
     q, _, B = SE._q_of(q)
-    if weights is not None:
-        _require_cuda(weights, "weights")
-        if weights.dtype != torch.float32 or tuple(weights.shape) not in ((B,), (B, 1)):
-            raise ValueError(f"weights: a float32 tensor of shape ({B},) or ({B}, 1) expected, got {tuple(weights.shape)} {weights.dtype}")
-        weights = _vec(weights, "weights", B)
+    weights = H.weights_of(weights, B)
     loss, td = TD3CriticLossFn.apply(q, _vec(target_q, "target_q", B), weights, bool(return_td_errors))
     return (loss, td) if return_td_errors else loss
 
@@ -337,8 +320,7 @@ class TD3Head(nn.Module):
         if activation_fn is not nn.ReLU:
             raise ValueError(f"activation_fn={getattr(activation_fn, '__name__', activation_fn)}: the HIP TD3 head computes ReLU only")
         self.share_features_extractor = bool(share_features_extractor)
-        if not self.share_features_extractor:
-            raise ValueError("share_features_extractor=False: the HIP TD3 head takes one feature vector for the actor and the critics")
+        H.require_shared_extractor(self, "TD3")
         self.n_critics = SE._n_critics_of(n_critics)
         try:
             self.features_dim, self.action_dim, pi, qf = H.head_dims(features_dim, action_dim, net_arch, [256, 256], "qf", "TD3", "net")

@@ -217,9 +217,7 @@ class TQCCriticLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dtd):
         coef = ctx.saved
-        dz = torch.empty_like(coef)
-        L.check(L.lib().m3l_sac_ens_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), coef.numel(), L.ptr(dz), _stream()), "m3l_sac_ens_loss_bwd")
-        return dz, None, None, None
+        return H.scale_coef(dloss, coef), None, None, None
 
 
 class TQCActorLossFn(torch.autograd.Function):
@@ -239,8 +237,7 @@ class TQCActorLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss):
         coef, shape = ctx.saved
-        out = torch.empty_like(coef)
-        L.check(L.lib().m3l_sac_ens_loss_bwd(L.ptr(_dev(dloss)), L.ptr(coef), coef.numel(), L.ptr(out), _stream()), "m3l_sac_ens_loss_bwd")
+        out = H.scale_coef(dloss, coef)
         B = shape[1]
         return out[:B], out[B:].reshape(shape), None, None
 
@@ -273,14 +270,7 @@ def quantiles(params: TQCParams, features, actions, target=False, param_grads=Tr
     H.require_params(flat, "SAC head parameter")
     x = H.features_of(features, on_tape=False)
     arch = _arch(x.shape[1], params)
-    _require_cuda(actions, "actions")
-    if actions.dim() != 2 or actions.shape[1] != arch[1]:
-        raise ValueError(f"actions: (B, {arch[1]}) expected, got {tuple(actions.shape)}")
-    if actions.shape[0] != x.shape[0]:
-        raise ValueError(f"{x.shape[0]} feature rows but {actions.shape[0]} action rows")
-    a = actions.float().contiguous()
-    if a.data_ptr() % 16:
-        a = a.clone()
+    a = H.actions_of(actions, x.shape[0], arch[1])
     want = param_grads and any(t.requires_grad for t in flat)
     store = torch.is_grad_enabled() and (a.requires_grad or want)
     counts = _Counts(params.n_critics, params.n_quantiles, params.top_quantiles_to_drop_per_net)
@@ -316,11 +306,7 @@ def _loss_args(B, target, weights, K=None):
     _require_cuda(target, "target")
     if target.dim() != 2 or target.shape[0] != B or not 1 <= target.shape[1] <= MAX_POOL or target.dtype != torch.float32:
         raise ValueError(f"target: ({B}, K) float32 with 1 <= K <= {MAX_POOL} expected, got {tuple(target.shape)} {target.dtype}")
-    if weights is not None:
-        _require_cuda(weights, "weights")
-        if weights.dtype != torch.float32 or tuple(weights.shape) not in ((B,), (B, 1)):
-            raise ValueError(f"weights: a float32 tensor of shape ({B},) or ({B}, 1) expected, got {tuple(weights.shape)} {weights.dtype}")
-        weights = _vec(weights, "weights", B)
+    weights = H.weights_of(weights, B)
     return _dev(target), weights
 
 

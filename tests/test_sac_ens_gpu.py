@@ -177,8 +177,9 @@ def test_losses_and_their_gradients_against_the_restatement(name):
 
 def test_two_critics_anchor_against_sac_head():
     """N = 2, subset None, the min reduction: from the same q, critic_loss (weighted and not), td_abs and actor_loss have SACHead's bits, and so
-    have their gradients in q and log_prob.  q, target_q and the parameter gradients through the net walks are asserted to 1e-4 of SACHead's,
-    and whether their bits are equal is printed (expected: the same tile functions run in the same order)."""
+    have their gradients in q and log_prob.  q, both TD targets, actor_loss, d actions, dx and every parameter gradient through the net walks
+    have SACHead's bits too (SACHead's critic entries lift their descriptor to n_critics = 2 and run the ensemble's kernels: this compares the
+    lifted call with the direct one), beside the 1e-4 checks against SACHead's values."""
     c = EC.case(EC.ANCHOR)
     ens, twin = _head(c), _head(c, m3l_amd.SACHead)
     x, a, w, logent = _t(c, "x"), _t(c, "a_replay"), _t(c, "weights"), _log_ent(c)
@@ -224,6 +225,7 @@ def test_two_critics_anchor_against_sac_head():
     for k, want in walks["twin"].items():
         got = walks["ens"][k]
         print(f"[anchor] {k}: bits {'equal' if torch.equal(got, want) else 'DIFFER'}")
+        assert torch.equal(got, want), f"{k} differs from SACHead's bits"
         if k in ("q", "target_q", "target_rows", "actor_loss"):
             _check_values("anchor " + k, got, want.double().cpu().numpy())
         else:

@@ -332,6 +332,46 @@ def test_memory_contract(monkeypatch, name):
     assert counts[0] == counts[1] and counts[0][0] == 3          # three workspaces: the actor node's and the two critic nodes'
 
 
+@pytest.mark.parametrize("name", ["a64_b17", "nohid_b3"])
+def test_one_workspace_serves_the_actor_and_the_critics(name):
+    """The header's promise at the C ABI: the actor and critic parts of one m3l_sac_ws_bytes workspace do not overlap.  One workspace handed to
+    m3l_sac_actor_fwd and m3l_sac_critic_fwd, then to m3l_sac_critic_bwd (with grads) and m3l_sac_actor_bwd, gives every output and gradient
+    the bits of the same four calls on two separate workspaces.  a64_b17: two row tiles, the second ragged; nohid_b3: no hidden layer, the
+    smallest layouts, where an off-by-one in the critics' start lands inside the neighbour's part."""
+    c = SC.gpu_case(name)
+    p = _head(c).params()
+    x, a, noise = _t(c, "x"), _t(c, "a_replay"), _t(c, "noise_pi")
+    B, A = noise.shape
+    arch = SH._arch(x.shape[1], p)
+    af, cf = [SH._dev(t) for t in p.actor_flat()], [SH._dev(t) for t in p.critic_flat()]
+    d = SH._desc(arch, actor=af, critic=cf)
+    lib = L.lib()
+    nbytes = lib.m3l_sac_ws_bytes(C.byref(d), B)
+    g = torch.Generator().manual_seed(11)
+    dq, da, dl = torch.randn(2, B, generator=g).to(DEV), torch.randn(B, A, generator=g).to(DEV), torch.randn(B, generator=g).to(DEV)
+
+    def run(ws_actor, ws_critic):
+        grads = [torch.zeros_like(t) for t in af + cf]
+        gd = SH._desc(arch, actor=grads[:len(af)], critic=grads[len(af):])
+        actions, logp, q = torch.empty(B, A, device=DEV), torch.empty(B, device=DEV), torch.empty(2, B, device=DEV)
+        dactions, dx = torch.empty(B, A, device=DEV), torch.empty_like(x)
+        L.check(lib.m3l_sac_actor_fwd(C.byref(d), B, L.ptr(x), L.ptr(noise), L.ptr(ws_actor), L.ptr(actions), L.ptr(logp), None), "m3l_sac_actor_fwd")
+        L.check(lib.m3l_sac_critic_fwd(C.byref(d), B, L.ptr(x), L.ptr(a), L.ptr(ws_critic), L.ptr(q), None), "m3l_sac_critic_fwd")
+        L.check(lib.m3l_sac_critic_bwd(C.byref(d), B, L.ptr(dq), L.ptr(ws_critic), L.ptr(dactions), C.byref(gd), None), "m3l_sac_critic_bwd")
+        L.check(lib.m3l_sac_actor_bwd(C.byref(d), B, L.ptr(x), L.ptr(noise), L.ptr(da), L.ptr(dl), L.ptr(ws_actor), L.ptr(dx), C.byref(gd), None),
+                "m3l_sac_actor_bwd")
+        torch.cuda.synchronize()
+        return [actions, logp, q, dactions, dx] + grads
+
+    def ws():
+        return torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=DEV)          # NaN in every float: a stale read would show
+    shared = ws()
+    one, two = run(shared, shared), run(ws(), ws())
+    assert all(bool(torch.isfinite(t).all()) for t in two) and any(bool(t.any()) for t in two[5:])
+    for i, (got, want) in enumerate(zip(one, two)):
+        assert torch.equal(got, want), f"tensor {i} of the shared-workspace run differs from the run on two workspaces"
+
+
 @pytest.mark.parametrize("name", ["mixed_b33", "a256_b130"])
 def test_no_grad_calls_take_no_workspace(monkeypatch, name):
     c = SC.gpu_case(name)
