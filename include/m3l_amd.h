@@ -154,11 +154,20 @@ int m3l_side_pending(void);      /* number of un-joined deferred tails (diagnost
  * rows per workgroup (t192.hip).  Bit mask: 1 (default) = sequences longer than 48 tokens, 2 = also the MLP halves of short
  * sequences (48-row tiles, two chunk parities; correct, measured equal to the per-sample block kernels); env M3L_T192 sets the
  * initial mode, 0 falls back to the per-op kernels.  Returns the previous mode. */
-/* Hidden activation h = GELU(u) of the fused feed-forward kernels: 1 = not written by the forward (one store stream less, 1.5 KB per token row
- * and layer less HBM traffic); the weight-gradient kernel of fc2 then stages u and applies the GELU itself (bit-identical gradients; that
- * kernel gets 40 % longer, the step time does not change).  Default 0.
- * Set it BEFORE a forward and keep it until its backward has run.  env M3L_DROP_H.  Returns the previous setting. */
+/* Hidden activation h = GELU(u) of the fused feed-forward kernels: not written by the forward (one store stream less, 1.5 KB per token row
+ * and layer less HBM traffic); the weight-gradient kernel of fc2 then stages u and applies the GELU itself, every wave on the pieces it
+ * staged and one ring stage ahead (bit-identical gradients).  Tri-state: -1 (default) = auto, the stacks whose forward feed-forward runs
+ * on a family of m3l_set_drop_h_auto; 1 = every stack; 0 = h is always saved.  Per-op and dropout stacks save h whatever the setting.
+ * Set it BEFORE a forward and keep it until its backward has run.  env M3L_DROP_H (unset = auto).  Returns the previous setting (-1, 0, 1). */
 int m3l_set_drop_h(int on);
+/* The families auto covers, a bit mask: 1 (default) = the row tiles (the MAE decoder), 2 = the per-sample blocks (the encoder over the visible
+ * tokens).  env M3L_DROP_H_AUTO.  Returns the previous mask. */
+int m3l_set_drop_h_auto(int families);
+/* How the fc2 weight gradient of a stack without saved h turns the staged u into h: 1 = per wave on its own pieces, one stage ahead, no extra
+ * barrier, every wave multiplying first and converting after; 2 (default) = the same with the middle wave of each SIMD's three converting first, so that
+ * VALU and MFMA work of neighbouring waves overlap; 0 = the earlier all-wave pass after the stage barrier, with a second barrier (the A/B
+ * partner).  Same bits in every mode.  env M3L_WGRAD_GELU_AHEAD (EXPERIMENTS 5.36).  Returns the previous setting. */
+int m3l_set_wgrad_gelu_ahead(int on);
 int m3l_set_t192(int on);
 /* height of the tall row tiles at width 192: 12 token tiles = 192 rows, one workgroup per CU, or 6 = 96 rows, 6 + 2 waves
  * and a 3-stage ring so that two workgroups share a CU and overlap each other's memory-only phases; env M3L_T192_TT.  Returns the previous value. */
@@ -239,7 +248,7 @@ typedef struct m3l_tf_plan {
     int rowln_cfg;           /* 1: m3l_set_rowln is on and the row widths allow the GEMM + LayerNorm epilogue */
     int rowln;               /* rowln_cfg && !per_op: the layers run it */
     int rb;                  /* 1: bf16 residual stream (what m3l_set_residual_bf16 asks for, where every kernel of the stack supports it) */
-    int drop_h;              /* m3l_set_drop_h at the time of the call */
+    int drop_h;              /* the fused forward of this stack does not save h: m3l_set_drop_h at the time of the call, resolved where it is auto */
     int h_from_u;            /* 1: the fused forward did not write h; the fc2 weight gradient stages u and applies the GELU itself */
     int mega_fwd;            /* 1: the whole forward of the stack in one launch (m3l_set_enc_mega bit 1) */
     int mega_bwd;            /* 1: the backward in one launch per weight-gradient group of layers (bit 2) */
@@ -479,6 +488,13 @@ int m3l_op_gemm_tn_acc(int dtype, const void* Y, int ldy, const void* X, int ldx
 size_t m3l_op_gemm_tn_grouped_ws_bytes(int dtype, int count, int M, const int* N, const int* K);
 int m3l_op_gemm_tn_grouped(int dtype, int count, int M, const void* const* Y, const int* ldy, const void* const* X, const int* ldx, const int* N,
                            const int* K, float* const* out, void* ws, size_t ws_bytes, void* stream);
+/* (ABI 423) the same with gelu_x[i] per problem (bf16 only): 0 = X_i as it is; 1 / 2 = X_i holds a pre-activation u and the product is over
+ * (bf16)GELU((float)u), erf form / fitted form — what the fc2 weight gradient of a stack that did not save h computes (m3l_set_drop_h). */
+int m3l_op_gemm_tn_grouped_gelu(int dtype, int count, int M, const void* const* Y, const int* ldy, const void* const* X, const int* ldx, const int* N,
+                                const int* K, float* const* out, void* ws, size_t ws_bytes, const int* gelu_x, void* stream);
+/* (ABI 423) what the bf16 launch of such a group picks, by host arithmetic alone (no launch): the tile is 64 na x 64 tbt outputs, the M rows are
+ * cut into nsplit ranges of rows_per_split rows (the last may be shorter), each staged in steps of 32 rows. */
+int m3l_op_gemm_tn_grouped_plan(int count, int M, const int* N, const int* K, int* na, int* tbt, int* nsplit, int* rows_per_split);
 /* building blocks of the trainable fusion MLP of the cfg-5 extractor (models/pretrain_models_dino_cat_mae.py:828-836,899-903: Linear + ReLU +
  * Dropout x 2, Linear, over cat(pooled MAE tokens, DINOv2 feature)): column sums (bias gradients), compute-type + transposed weight copy
  * (dst / dstT may be NULL), keep-mask / ReLU-mask scaling (mode 0: ref = uint8 mask; mode 1: ref = f32, on where ref > 0), and the

@@ -104,6 +104,8 @@ _SIGS = {
     "m3l_set_attn_t192_bwd_prefetch": (c_i, [c_i]),
     "m3l_set_enc_mega": (c_i, [c_i]),
     "m3l_set_drop_h": (c_i, [c_i]),
+    "m3l_set_drop_h_auto": (c_i, [c_i]),
+    "m3l_set_wgrad_gelu_ahead": (c_i, [c_i]),
     "m3l_set_direct_conv": (c_i, [c_i]),
     "m3l_set_t192": (c_i, [c_i]),
     "m3l_set_t192_tt": (c_i, [c_i]),
@@ -194,6 +196,9 @@ _SIGS = {
     "m3l_op_gemm_tn_acc": (c_i, [c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p, c_i, c_i, c_p]),
     "m3l_op_gemm_tn_grouped_ws_bytes": (c_sz, [c_i, c_i, c_i, c_p, c_p]),
     "m3l_op_gemm_tn_grouped": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    # fc2 weight gradient without saved h (ABI 423): the grouped launch with gelu_x per problem, and the tile shape / split it picks
+    "m3l_op_gemm_tn_grouped_gelu": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
+    "m3l_op_gemm_tn_grouped_plan": (c_i, [c_i, c_i, c_p, c_p, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i)]),
     "m3l_op_colsum_ws_bytes": (c_sz, [c_i]),
     "m3l_op_colsum": (c_i, [c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "m3l_op_prep_weight": (c_i, [c_i, c_p, c_i, c_i, c_p, c_p, c_p]),

@@ -165,6 +165,8 @@ size_t m3l_wgrad_ws_bytes(int M, const TnProblem* probs, int count);
 int m3l_wgrad_layers_per_launch(int M, const TnProblem* layer_probs, int count);
 int m3l_wgrad_bf16(TnProblem* probs, int count, int M, float* ws, size_t ws_bytes, int accumulate, hipStream_t st, const TnExtra* extras,
                    int extra_count);
+// tile shape (64 na x 64 tbt), number of row ranges and rows per range the bf16 launch picks for a problem list (host arithmetic, no launch)
+void m3l_wgrad_plan(int M, const TnProblem* probs, int count, int* na, int* tbt, int* nsplit, int* rows_per_split);
 int m3l_gemm_init();
 int m3l_gemm_nt_colsum_rows(int M, int N);   // number of partial rows written through GemmEpi::colsum_part
 

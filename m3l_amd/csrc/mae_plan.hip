@@ -336,7 +336,7 @@ int check_tf(const m3l_tf_cfg* c, int B, int n) {
 // =================================================================================================================
 extern "C" {
 
-int m3l_version(void) { return 422; }
+int m3l_version(void) { return 423; }
 
 // diagnostic switch (bench.py's stand-alone roofline figure, PMC passes): 1 = every weight gradient on the caller's stream
 int m3l_set_wgrad_inline(int on) {
@@ -408,9 +408,15 @@ int m3l_set_residual_bf16(int on) {
     return old;
 }
 
+// -1 = auto (h is not saved where the plan says its recompute is hidden), 0 / 1 force; returns the previous setting, -1 included
 int m3l_set_drop_h(int on) {
-    const int old = drop_h() ? 1 : 0;
-    g_drop_h = on ? 1 : 0;
+    const int old = drop_h_mode();
+    g_drop_h = on < 0 ? -1 : on ? 1 : 0;
+    return old;
+}
+int m3l_set_drop_h_auto(int families) {
+    const int old = drop_h_auto();
+    g_drop_h_auto = families & 3;
     return old;
 }
 
@@ -1722,6 +1728,29 @@ int m3l_op_gemm_tn_grouped(int dtype, int count, int M, const void* const* Y, co
         pr[i].out = out[i]; pr[i].ldo = K[i]; pr[i].nvalid = N[i]; pr[i].kvalid = K[i];
     }
     return m3l_gemm_tn_grouped(dtype, pr, count, M, (float*)ws, ws_bytes, 0, (hipStream_t)stream);
+}
+int m3l_op_gemm_tn_grouped_gelu(int dtype, int count, int M, const void* const* Y, const int* ldy, const void* const* X, const int* ldx, const int* N,
+                                const int* K, float* const* out, void* ws, size_t ws_bytes, const int* gelu_x, void* stream) {
+    M3L_CHECK(count >= 1 && count <= M3L_TN_MAX_PROBLEMS && Y && X && ldy && ldx && N && K && out && ws && gelu_x,
+              "gemm_tn_grouped_gelu: bad arguments (count %d)", count);
+    TnProblem pr[M3L_TN_MAX_PROBLEMS];
+    memset(pr, 0, sizeof(pr));
+    for (int i = 0; i < count; ++i) {
+        M3L_CHECK(gelu_x[i] >= 0 && gelu_x[i] <= 2 && (gelu_x[i] == 0 || dtype == 1), "gemm_tn_grouped_gelu: gelu_x[%d] = %d (0, 1, 2; bf16 only)", i,
+                  gelu_x[i]);
+        pr[i].Y = Y[i]; pr[i].X = X[i]; pr[i].ldy = ldy[i]; pr[i].ldx = ldx[i]; pr[i].N = N[i]; pr[i].K = K[i];
+        pr[i].out = out[i]; pr[i].ldo = K[i]; pr[i].nvalid = N[i]; pr[i].kvalid = K[i]; pr[i].gelu_x = gelu_x[i];
+    }
+    return m3l_gemm_tn_grouped(dtype, pr, count, M, (float*)ws, ws_bytes, 0, (hipStream_t)stream);
+}
+int m3l_op_gemm_tn_grouped_plan(int count, int M, const int* N, const int* K, int* na, int* tbt, int* nsplit, int* rows_per_split) {
+    M3L_CHECK(count >= 1 && count <= M3L_TN_MAX_PROBLEMS && M > 0 && N && K && na && tbt && nsplit && rows_per_split,
+              "gemm_tn_grouped_plan: bad arguments (count %d, M %d)", count, M);
+    TnProblem pr[M3L_TN_MAX_PROBLEMS];
+    memset(pr, 0, sizeof(pr));
+    for (int i = 0; i < count; ++i) { pr[i].N = N[i]; pr[i].K = K[i]; }
+    m3l_wgrad_plan(M, pr, count, na, tbt, nsplit, rows_per_split);
+    return 0;
 }
 // ---- building blocks of the cfg-5 fusion head's trainable MLP (models/pretrain_models_dino_cat_mae.py:828-836,899-903) ----
 int m3l_op_colsum(int dtype, const void* Y, int M, int N, int ld, void* ws, float* out, void* stream) {

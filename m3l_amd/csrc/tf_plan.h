@@ -18,14 +18,22 @@ inline bool use_rowln() {
     if (g_rowln < 0) g_rowln = getenv("M3L_ROWLN") != nullptr ? 1 : 0;
     return g_rowln == 1;
 }
-// Hidden activation h = GELU(u) of the fused MLP kernels: 1 = not written by the forward — the weight-gradient kernel of fc2 stages the
-// pre-activation u instead and applies the GELU in its LDS stage (wgrad.hip), bit-identical gradients, 0.7 GB less HBM traffic per cfg-2
-// step — and a 40 % longer weight-gradient kernel (140 -> 196 us: the GELU pass is NOT hidden behind its memory waits), which the side
-// stream absorbs: same step time.  0 (default) = saved.  env M3L_DROP_H / m3l_set_drop_h.
-int g_drop_h = -1;
-inline bool drop_h() {
-    if (g_drop_h < 0) g_drop_h = getenv("M3L_DROP_H") ? (atoi(getenv("M3L_DROP_H")) > 0 ? 1 : 0) : 0;
-    return g_drop_h == 1;
+// Hidden activation h = GELU(u) of the fused MLP kernels: not written by the forward — the weight-gradient kernel of fc2 stages the
+// pre-activation u instead and every wave applies the GELU to the pieces it staged, one ring stage ahead (wgrad.hip, GM 2): bit-identical
+// gradients, one [M, mlp] store stream less per layer.  Tri-state: -1 (default, env unset) = auto, the stacks whose forward feed-forward
+// family is in drop_h_auto(); 1 = every stack (h_from_u only where a fused family runs: the per-op fc2 GEMM reads h), 0 = h always saved.
+// env M3L_DROP_H / m3l_set_drop_h.
+int g_drop_h = -2;           // -2 = environment not read yet
+inline int drop_h_mode() {
+    if (g_drop_h < -1) g_drop_h = getenv("M3L_DROP_H") ? (atoi(getenv("M3L_DROP_H")) > 0 ? 1 : 0) : -1;
+    return g_drop_h;
+}
+// the fused families auto covers, a bit mask: 1 = the row tiles (T192 / IN_TAIL: the decoder, whose forward is bound by its stores), 2 = the
+// per-sample blocks (BLOCK: the encoder).  env M3L_DROP_H_AUTO / m3l_set_drop_h_auto; the default is the measured one (EXPERIMENTS 5.36).
+int g_drop_h_auto = -1;
+inline int drop_h_auto() {
+    if (g_drop_h_auto < 0) g_drop_h_auto = getenv("M3L_DROP_H_AUTO") ? (atoi(getenv("M3L_DROP_H_AUTO")) & 3) : 1;
+    return g_drop_h_auto;
 }
 // bf16 residual stream (round 4; default ON, env M3L_RES_BF16=0 / m3l_set_residual_bf16(0) restore fp32): x, x1, xout of every layer of a stack and its running
 // residual gradient travel through HBM as bf16 instead of fp32 (fp32 in registers: the arithmetic is unchanged, each half layer's result is
@@ -60,7 +68,6 @@ inline TfPlan tf_plan(const m3l_tf_cfg* c, int B, int n, const m3l_dropout* drop
     // K = 3 HD where the forward's have K = HD and K = mlp; both K tiles are powers of two, so 3 HD is a multiple exactly when HD is.)
     p.rowln_cfg = (use_rowln() && m3l_gemm_nt_rowln_supported(dt, D, HD) && m3l_gemm_nt_rowln_supported(dt, D, mlp)) ? 1 : 0;
     p.rowln = (p.rowln_cfg && !p.per_op) ? 1 : 0;
-    p.drop_h = drop_h() ? 1 : 0;
     const bool fused = !p.per_op && !p.rowln;             // the block and row-tile families are open to this stack
     const bool ablock = m3l_attn_block_supported(dt, D, H, n, pout, dh);
     const bool t192 = m3l_mlp_t192_supported(dt, D, mlp, M), t192_short = t192 && m3l_mlp_t192_short();
@@ -86,7 +93,11 @@ inline TfPlan tf_plan(const m3l_tf_cfg* c, int B, int n, const m3l_dropout* drop
     // short sequences whose every half layer takes a block kernel: the whole stack in ONE launch (enc_mega.hip)
     p.mega_fwd = ((m3l_enc_mega_enabled() & 1) && f_mblock && c->depth >= 1 && c->depth <= M3L_MEGA_MAX_LAYERS) ? 1 : 0;
     // the fc2 weight gradient stages u and applies the fitted GELU (every bf16 kernel evaluates that form): the fused forward did not write h
-    p.h_from_u = (p.drop_h && (p.fwd_mlp == M3L_TF_BLOCK || p.fwd_mlp == M3L_TF_T192 || p.fwd_mlp == M3L_TF_IN_TAIL)) ? 1 : 0;
+    // (auto: exactly the stacks whose family is in the measured set, so drop_h == h_from_u there; forced 1: every stack carries drop_h)
+    const bool rowtile_mlp = p.fwd_mlp == M3L_TF_T192 || p.fwd_mlp == M3L_TF_IN_TAIL, block_mlp = p.fwd_mlp == M3L_TF_BLOCK;
+    const int dh_mode = drop_h_mode();
+    p.drop_h = dh_mode >= 0 ? dh_mode : (((drop_h_auto() & 1) && rowtile_mlp) || ((drop_h_auto() & 2) && block_mlp)) ? 1 : 0;
+    p.h_from_u = (p.drop_h && (rowtile_mlp || block_mlp)) ? 1 : 0;
 
     // ---- backward.  Asymmetries kept: the MLP block backward does not ask for an out-projection (a project_out == 0 stack whose forward was
     // per-op takes it); the row tiles also take the short sequences the MLP block backward has no LDS for; the attention block needs the

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 
+#include "../../include/m3l_amd.h"
 #include "common.cuh"
 #include "kernels.h"
 
@@ -115,7 +116,16 @@ __device__ __forceinline__ void wait_vm(int n) {
 // staged columns per token row against 3072 unique ones — and panels of the wide operand that lie outside the problem (the second
 // tile of the 576-wide qkv gradient holds 192 columns, the out-projection's 192 of 384) are neither staged nor multiplied: their waves
 // only keep the barriers.
-template <int NA, int TBT, bool NTL>
+//
+// GM: how a group that holds GELU problems (TnProblem::gelu_x: the staged operand is the pre-activation u, the product is over h = GELU(u))
+// turns u into h in LDS.  0 = the group holds none (no GELU code at all).  2 (m3l_set_wgrad_gelu_ahead(1)) = every wave converts
+// the pieces IT staged, one stage ahead: after the MFMAs of stage t it waits for its own pieces of stage t + 1 (the counted wait the next
+// iteration would issue anyway), converts them in place (a piece is lane-linear, 64 x 16 B: one ds_read_b128 + one ds_write_b128 per lane,
+// conflict-free; nobody else touches the piece before barrier t + 1) and the loop's ordinary barrier publishes DMA data and GELU results
+// together: one barrier per stage in every tile, the VALU work of stage t + 1 behind the memory wait of the ring.  1 = the earlier pass
+// (all waves over the whole operand after the barrier, then a second barrier), kept as the A/B partner and the bit-identity oracle.
+// 3 (default, m3l_set_wgrad_gelu_ahead(2)) = 2 with the middle wave of every SIMD's three converting before it multiplies (see the loop).
+template <int NA, int TBT, bool NTL, int GM>
 __global__ __launch_bounds__(128 * NA) void wgrad_kernel(WgGroup grp, int M, int rows_per_split, int nsplit, float* __restrict__ slabs, int per_xcd) {
     constexpr int TA = 64 * NA, TB = 64 * TBT, NB = TB / 32, NT = 4 * NB, NW = 2 * NA;
     constexpr int SLOT = (NA + TBT) * 4096, P = 4 * (NA + TBT), JMAX = (P + NW - 1) / NW;
@@ -174,6 +184,29 @@ __global__ __launch_bounds__(128 * NA) void wgrad_kernel(WgGroup grp, int M, int
         }
     };
     const bool work = a0 + 64 * wr < pb.a;                     // this wave's 64 rows of the output tile exist (wave-uniform)
+    // GM 2 / 3: h = GELU(u) in place on this wave's own pieces of stage t (landed: the caller waited), rounded as the forward rounded it.  Rows
+    // past M were staged as zeros (GELU(0) = 0); chunks past the operand inside a partly valid panel hold valid u values and are never multiplied
+    const int gform = GM ? (pb.gelu_a | pb.gelu_b) : 0;       // workgroup-uniform
+    bool pg[JMAX];                                            // this piece belongs to the operand that carries the GELU (wave-uniform)
+#pragma unroll
+    for (int j = 0; j < JMAX; ++j) pg[j] = GM && pv[j] && (pa[j] ? pb.gelu_a : pb.gelu_b) != 0;
+    auto gelu_pieces = [&](char* base, auto gelu) {           // one branch on the form per stage, none per value
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j) {
+            if (!pg[j]) continue;
+            bf16x8* q = reinterpret_cast<bf16x8*>(base + pdst[j]);
+            bf16x8 v = *q;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (bf16)gelu((float)v[e]);
+            *q = v;
+        }
+    };
+    auto gelu_own = [&](int t) {
+        char* base = smem + (t % WG_NST) * SLOT + lane * 16;
+        if (gform == 1) gelu_pieces(base, [](float x) { return gelu_f(x); });
+        else gelu_pieces(base, [](float x) { return gelu_fast(x); });
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
 
     f32x4 acc[4][NB];
 #pragma unroll
@@ -182,17 +215,21 @@ __global__ __launch_bounds__(128 * NA) void wgrad_kernel(WgGroup grp, int M, int
         for (int y = 0; y < NB; ++y) acc[x][y] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int t = 0; t < WG_NST - 1 && t < nst; ++t) issue(t);
+    if (GM >= 2 && gform && nst > 0) {                        // stage 0 has no stage in front of it to hide behind
+        wait_vm(min(WG_NST - 2, nst - 1) * mine);
+        gelu_own(0);
+    }
     for (int t = 0; t < nst; ++t) {
         // this wave's pieces of stage t have landed once at most the pieces of the (up to two) younger stages remain (in-order retire)
         wait_vm(min(WG_NST - 2, nst - 1 - t) * mine);
         __builtin_amdgcn_s_barrier();                         // ... everyone's have; everyone is done reading stage t - 1
         asm volatile("" ::: "memory");
         if (t + WG_NST - 1 < nst) issue(t + WG_NST - 1);      // into the slot stage t - 1 occupied
-        if (pb.gelu_a | pb.gelu_b) {                          // workgroup-uniform
+        if (GM == 1 && gform) {
             // the staged operand is the pre-activation u: h = GELU(u) in place, rounded as the forward rounded it, 8 values per thread
             // and pass (rows past M were staged as zeros: GELU(0) = 0).  The kernel waits on HBM most of its time: the pass hides there.
             char* base = smem + (t % WG_NST) * SLOT + (pb.gelu_a ? 0 : NA * 4096);
-            const int bytes = pb.gelu_a ? NA * 4096 : TBT * 4096, form = pb.gelu_a | pb.gelu_b;
+            const int bytes = pb.gelu_a ? NA * 4096 : TBT * 4096, form = gform;
             for (int off = tid * 16; off < bytes; off += 64 * NW * 16) {
                 bf16x8 v = *reinterpret_cast<bf16x8*>(base + off);
 #pragma unroll
@@ -202,28 +239,41 @@ __global__ __launch_bounds__(128 * NA) void wgrad_kernel(WgGroup grp, int M, int
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-        if ((WG_ABL & 2) || !work) continue;
-        const char* As = smem + (t % WG_NST) * SLOT + wr * 4096;
-        const char* Bs = smem + (t % WG_NST) * SLOT + NA * 4096;
-        Frag<bf16> fa[4], fb[NB];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) fa[x] = ldtr(As, 0, x * 16, lane);
-#pragma unroll
-        for (int y = 0; y < NB; ++y) {
-            const int col = wc * (TB / 2) + y * 16;
-            fb[y] = ldtr(Bs + (col >> 6) * 4096, 0, col & 63, lane);
+        // GM 3: the middle wave of a SIMD's three (waves v, v + 4, v + 8 share a SIMD) converts first and multiplies after: its VALU work
+        // runs under the MFMAs of its neighbours and theirs under its own, instead of all waves multiplying and then all converting
+        const bool gelu_first = GM == 3 && gform && ((wave >> 2) & 1);
+        if (gelu_first && t + 1 < nst) {
+            wait_vm(min(WG_NST - 2, nst - 2 - t) * mine);
+            gelu_own(t + 1);
         }
-        if (WG_ABL & 1) {
+        if (!(WG_ABL & 2) && work) {
+            const char* As = smem + (t % WG_NST) * SLOT + wr * 4096;
+            const char* Bs = smem + (t % WG_NST) * SLOT + NA * 4096;
+            Frag<bf16> fa[4], fb[NB];
 #pragma unroll
-            for (int x = 0; x < 4; ++x) asm volatile("" ::"v"(fa[x].v));
+            for (int x = 0; x < 4; ++x) fa[x] = ldtr(As, 0, x * 16, lane);
 #pragma unroll
-            for (int y = 0; y < NB; ++y) asm volatile("" ::"v"(fb[y].v));
-            continue;
+            for (int y = 0; y < NB; ++y) {
+                const int col = wc * (TB / 2) + y * 16;
+                fb[y] = ldtr(Bs + (col >> 6) * 4096, 0, col & 63, lane);
+            }
+            if (WG_ABL & 1) {
+#pragma unroll
+                for (int x = 0; x < 4; ++x) asm volatile("" ::"v"(fa[x].v));
+#pragma unroll
+                for (int y = 0; y < NB; ++y) asm volatile("" ::"v"(fb[y].v));
+            } else {
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+#pragma unroll
+                    for (int y = 0; y < NB; ++y) acc[x][y] = mma16(fa[x], fb[y], acc[x][y]);
+            }
         }
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-#pragma unroll
-            for (int y = 0; y < NB; ++y) acc[x][y] = mma16(fa[x], fb[y], acc[x][y]);
+        // the waves without output rows own pieces too
+        if (GM >= 2 && gform && !gelu_first && t + 1 < nst) {
+            wait_vm(min(WG_NST - 2, nst - 2 - t) * mine);      // own pieces of stage t + 1 (the next iteration's wait: the ring keeps its depth)
+            gelu_own(t + 1);
+        }
     }
     if (WG_ABL & 8) return;
     // fragment-order slab: [wave][tile x * NB + y][lane] float4 (rows 4 g .. 4 g + 3 of the 16 x 16 tile, column li).  16 x 16 tiles that lie
@@ -412,23 +462,32 @@ WgPlanHost plan_of(int M, const TnProblem* probs, int count, WgGroup* grp) {
     return pl;
 }
 
-template <int NA, int TBT>
-int launch_wgrad(const WgGroup& grp, const WgPlanHost& pl, int M, float* ws, int accumulate, int maxw, int extra_count, hipStream_t st, int count,
-                 double flops, double bytes, int nt) {
+// m3l_set_wgrad_gelu_ahead / env M3L_WGRAD_GELU_AHEAD: 1 = GELU problems convert a wave's own pieces one stage ahead (GM 2 of wgrad_kernel),
+// 2 (default) = the same with the middle wave of a SIMD converting first (GM 3), 0 = the earlier all-wave pass with its second barrier
+// (GM 1).  Same bits in every mode.  Decoder launch of cfg 2 in-step: 298 us with h saved, 440 / 387 / 372 us in modes 0 / 1 / 2 (EXPERIMENTS 5.36).
+int g_gelu_ahead = -1;
+int gelu_ahead() {
+    if (g_gelu_ahead < 0) g_gelu_ahead = getenv("M3L_WGRAD_GELU_AHEAD") ? std::min(2, std::max(0, atoi(getenv("M3L_WGRAD_GELU_AHEAD")))) : 2;
+    return g_gelu_ahead;
+}
+
+template <int NA, int TBT, int GM>
+int launch_wgrad_gm(const WgGroup& grp, const WgPlanHost& pl, int M, float* ws, int accumulate, int maxw, int extra_count, hipStream_t st, int count,
+                    double flops, double bytes, int nt) {
     constexpr int TA = 64 * NA, TB = 64 * TBT;
     constexpr size_t lds = (size_t)WG_NST * (NA + TBT) * 4096;
     static bool inited = false;
     if (!inited) {
-        M3L_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<NA, TBT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        M3L_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<NA, TBT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        M3L_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<NA, TBT, false, GM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        M3L_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<NA, TBT, true, GM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         inited = true;
     }
     {
         ProfScope prof(count >= 3 ? "wgrad" : "wgrad_small", M, pl.tiles_total, pl.S, flops, st, bytes);   // grouped layer launches vs single Linears
         const int per_xcd = cdiv((long)pl.tiles_total * pl.S, 8);
         const dim3 g1(8 * per_xcd);
-        if (nt) wgrad_kernel<NA, TBT, true><<<g1, 128 * NA, lds, st>>>(grp, M, pl.rows_per_split, pl.S, ws, per_xcd);
-        else wgrad_kernel<NA, TBT, false><<<g1, 128 * NA, lds, st>>>(grp, M, pl.rows_per_split, pl.S, ws, per_xcd);
+        if (nt) wgrad_kernel<NA, TBT, true, GM><<<g1, 128 * NA, lds, st>>>(grp, M, pl.rows_per_split, pl.S, ws, per_xcd);
+        else wgrad_kernel<NA, TBT, false, GM><<<g1, 128 * NA, lds, st>>>(grp, M, pl.rows_per_split, pl.S, ws, per_xcd);
     }
     M3L_LAUNCH_CHECK();
     ProfScope prof2("wgrad_reduce", pl.S, pl.tiles_total, count, 0.0, st, (double)pl.ws_bytes);
@@ -437,8 +496,31 @@ int launch_wgrad(const WgGroup& grp, const WgPlanHost& pl, int M, float* ws, int
     M3L_LAUNCH_CHECK();
     return 0;
 }
+// a group without a GELU problem takes the instantiation that holds no GELU code
+template <int NA, int TBT>
+int launch_wgrad(const WgGroup& grp, const WgPlanHost& pl, int M, float* ws, int accumulate, int maxw, int extra_count, hipStream_t st, int count,
+                 double flops, double bytes, int nt) {
+    bool gelu = false;
+    for (int i = 0; i < grp.count; ++i) gelu = gelu || grp.p[i].gelu_a || grp.p[i].gelu_b;
+    if (!gelu) return launch_wgrad_gm<NA, TBT, 0>(grp, pl, M, ws, accumulate, maxw, extra_count, st, count, flops, bytes, nt);
+    if (gelu_ahead() == 2) return launch_wgrad_gm<NA, TBT, 3>(grp, pl, M, ws, accumulate, maxw, extra_count, st, count, flops, bytes, nt);
+    if (gelu_ahead() == 1) return launch_wgrad_gm<NA, TBT, 2>(grp, pl, M, ws, accumulate, maxw, extra_count, st, count, flops, bytes, nt);
+    return launch_wgrad_gm<NA, TBT, 1>(grp, pl, M, ws, accumulate, maxw, extra_count, st, count, flops, bytes, nt);
+}
 
 }  // namespace
+
+int m3l_set_wgrad_gelu_ahead(int on) {
+    const int old = gelu_ahead();
+    g_gelu_ahead = std::min(2, std::max(0, on));
+    return old;
+}
+
+// tile shape and split of a problem list as the launch would pick them (host arithmetic; the CU count is the device attribute)
+void m3l_wgrad_plan(int M, const TnProblem* probs, int count, int* na, int* tbt, int* nsplit, int* rows_per_split) {
+    const WgPlanHost pl = plan_of(M, probs, count, nullptr);
+    *na = pl.na; *tbt = pl.tbt; *nsplit = pl.S; *rows_per_split = pl.rows_per_split;
+}
 
 size_t m3l_wgrad_ws_bytes(int M, const TnProblem* probs, int count) { return plan_of(M, probs, count, nullptr).ws_bytes; }
 
